@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Msamples/s (pixels x spp) of the path-tracing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c1|head|c3|c4|c5] [--spp S]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c1|head|c3|c4|c5] [--spp S] [--dump-outputs DIR]
 
 A "step" is one full render of the workload: trace kernel(s) + ordered sample reduction + tone map,
 scene already resident in HBM.  Steps are pipelined two deep (two resident copies of the scene, two streams), so that
@@ -84,6 +84,26 @@ def algorithmic_bytes(c):
     return (c["box_tests"] * S_NODE + c["sphere_tests"] * S_SPHERE + c["moving_sphere_tests"] * S_MSPHERE +
             c["rect_tests"] * S_RECT + c["triangle_tests"] * S_TRI + c["scatters"] * S_MAT + c["texels"] * S_TEXEL +
             c["perlin_calls"] * S_PERLIN + c["samples"] * S_OUT)
+
+
+DUMP_BYTES = 64 << 20     # --dump-outputs budget
+DUMP_SAMPLE_PIXELS = 1 << 21  # pixels kept when a frame exceeds it: 12 B of colour + 8 B of index each (40 MB)
+
+
+def dump_outputs(out_dir, rgb8):
+    """--dump-outputs: the frame the last timed step delivered (RGB8, rows x width x 3, in the library's row order) as
+    <out_dir>/rgb8.npy in float32.  A frame over DUMP_BYTES is written as a fixed, seeded sample of its pixels instead:
+    rgb8_sample.npy (n x 3, float32) and rgb8_sample_index.npy (their flat pixel indices, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.asarray(rgb8, dtype=np.float32)
+    if img.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "rgb8.npy"), img)
+        return
+    px = img.reshape(-1, 3)
+    idx = np.sort(np.random.default_rng(0).choice(px.shape[0], size=DUMP_SAMPLE_PIXELS, replace=False))
+    np.save(os.path.join(out_dir, "rgb8_sample.npy"), px[idx])
+    np.save(os.path.join(out_dir, "rgb8_sample_index.npy"), idx.astype(np.float64))
 
 
 def usable_cores():
@@ -312,6 +332,8 @@ def single_process(args):
         for _ in range(steps):
             screen = ms.render(w["cam"], w["cfg"], want_accum=False)
         elapsed = time.perf_counter() - t0
+        if name == args.workload and args.dump_outputs:
+            dump_outputs(args.dump_outputs, screen.rgb8)
         st = screen.stats
         assert int(np.count_nonzero(screen.rgb8)) > 0
         out[name] = {"workload": w["desc"] + ("" if spp == 0 else " -- run at %d spp" % w["spp"]),
@@ -360,7 +382,11 @@ def main():
     ap.add_argument("--c5-spp", type=int, default=96, help="N > 1: spp of the extra C5 frame (3840x2160; BASELINE's scaling config at reduced spp)")
     ap.add_argument("--max-leaf", type=int, default=0, help="BVH leaf size override (0 = library default)")
     ap.add_argument("--sah-bins", type=int, default=0, help="SAH bin count override (0 = library default)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the frame the last one "
+                    "delivered to DIR/rgb8.npy (float32; a fixed, seeded pixel sample if it exceeds 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.pmc_child:
         return pmc_child(args)
 
@@ -471,6 +497,17 @@ def main():
     last = (step_no[0] - 1) % N_PIPE
     d_rgb8 = bufs[last]
     gather_list = gather_lists[last]
+    # ---- image assembled on rank 0 (also a sanity check of the gather), before the untimed renders below reuse bufs[0]
+    if rank == 0:
+        img = np.zeros((height, width, 3), dtype=np.uint8)
+        parts = gather_list if world_size > 1 else [d_rgb8]
+        for r in range(world_size):
+            rows = list(range(r, height, shard[1]))
+            img[rows] = parts[r].cpu().numpy()[: len(rows) * width * 3].reshape(len(rows), width, 3)
+        if os.environ.get("BENCH_WRITE_PPM"):
+            rtsr.Screen(width, height, img).write_to_ppm_file(os.environ["BENCH_WRITE_PPM"])
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, img)
     # the trace kernel's own duration: HIP events around its launches on the launch stream, in three untimed frames of the same
     # shard run one at a time (inside the pipelined region the events of two streams would interleave)
     trace_ms = []
@@ -499,16 +536,6 @@ def main():
             c5 = c5_leg(rtsr, torch, dist, rank, world_size, use_gloo, args.c5_spp)
         except Exception as e:  # noqa: BLE001  (the headline line must still be printed)
             c5 = {"error": repr(e)[:300]}
-
-    # ---- image assembled on rank 0 (also a sanity check of the gather)
-    if rank == 0:
-        img = np.zeros((height, width, 3), dtype=np.uint8)
-        parts = gather_list if world_size > 1 else [d_rgb8]
-        for r in range(world_size):
-            rows = list(range(r, height, shard[1]))
-            img[rows] = parts[r].cpu().numpy()[: len(rows) * width * 3].reshape(len(rows), width, 3)
-        if os.environ.get("BENCH_WRITE_PPM"):
-            rtsr.Screen(width, height, img).write_to_ppm_file(os.environ["BENCH_WRITE_PPM"])
 
     out = None
     if rank == 0:
