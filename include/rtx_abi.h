@@ -271,6 +271,41 @@ rtx_status rtx_multi_render(rtx_multi* m, const RtxCamera* cam, const RtxConfig*
 /* Convenience: create on devices 0..n_gpus-1 (block_rows 1), render once, destroy. */
 rtx_status rtx_render_multi(const rtx_flat* f, const RtxCamera* cam, const RtxConfig* cfg, int32_t n_gpus, RtxFrame* out);
 
+/* ---- progressive rendering: one frame accumulated over several calls, with a noise estimate ----------------------- */
+/* A handle owns the device accumulators of one (scene, camera, config, shard): S, the per-pixel sums of radiance, and Q,
+ * their sums of squares.  cfg->samples_per_pixel is the BUDGET: rtx_progressive_add(p, n) traces the next n samples of
+ * every pixel (absolute sample indices [spp_done, spp_done + n)) and returns RTX_EINVAL past the budget.  Random streams
+ * are keyed by absolute (pixel, sample), and samples are added in sample order, so the frame after k samples is
+ * bit-identical to a one-shot render at k spp however the k samples were split into calls.
+ * The handle uses the scene's render workspace: it must not run concurrently with another render of the same scene on
+ * another stream, and it must be destroyed before its scene.  Argument errors are reported before any device call. */
+typedef struct rtx_progressive rtx_progressive;
+typedef struct RtxNoiseStats {
+  int32_t spp_done;      /* samples per pixel accumulated so far */
+  int32_t pixels;        /* active pixels of the shard (row_chunk_compat's skipped rows excluded) */
+  int32_t pixels_above;  /* pixels whose relative error r > target_rel_err */
+  int32_t reserved;
+  double max_rel_err, mean_rel_err, target_rel_err;
+} RtxNoiseStats;
+/* shard NULL = the whole image.  Blocking; allocates 48 bytes per pixel of the shard. */
+rtx_status rtx_progressive_create(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
+                                  rtx_progressive** out);
+void rtx_progressive_destroy(rtx_progressive* p); /* NULL-safe */
+int32_t rtx_progressive_spp(const rtx_progressive* p); /* samples per pixel so far (-1: NULL handle) */
+/* Asynchronous on hip_stream (NULL = default stream) unless stats != NULL, as rtx_render_device.  1 <= n_samples <=
+ * budget - spp_done.  A failed add leaves the handle unusable (every later call returns RTX_EINVAL). */
+rtx_status rtx_progressive_add(rtx_progressive* p, int32_t n_samples, void* hip_stream, RtxRenderStats* stats);
+/* Blocking.  out->accum_rgb (S), out->rgb8 (tone-mapped at spp_done) and sumsq_rgb (Q) are each optional host buffers of
+ * rows*w*3 elements in rtx_render_device's shard layout.  Needs spp_done >= 1. */
+rtx_status rtx_progressive_read(const rtx_progressive* p, RtxFrame* out, double* sumsq_rgb);
+/* Blocking.  Per active pixel and channel, with n = spp_done >= 2:  m = S/n,  var = max(0, (Q - S*S/n) / (n - 1)),
+ * se = sqrt(var / n),  r_c = se / (m + 1/256);  the pixel's r = max_c r_c.  Reports max r, mean r and the count of
+ * r > target_rel_err (>= 0), reduced in a fixed order: the same bits on every call. */
+rtx_status rtx_progressive_stats(rtx_progressive* p, double target_rel_err, RtxNoiseStats* out);
+/* Blocking.  Adds `batch` samples at a time (the last batch clipped to the budget) and stops at the first batch boundary
+ * where pixels_above == 0 (checked on entry too once spp_done >= 2), or at the budget.  out: the last stats. */
+rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double target_rel_err, RtxNoiseStats* out);
+
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one
  * upload): 500 x 500, 500 spp, depth 50, background (0.7, 0.8, 1), camera (13,2,3) -> (0,0,0), vfov 20, aspect 1,

@@ -86,6 +86,11 @@ class RtxShard(C.Structure):
     _fields_ = [("shard_index", C.c_int32), ("shard_count", C.c_int32), ("block_rows", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RtxNoiseStats(C.Structure):
+    _fields_ = [("spp_done", C.c_int32), ("pixels", C.c_int32), ("pixels_above", C.c_int32), ("reserved", C.c_int32),
+                ("max_rel_err", C.c_double), ("mean_rel_err", C.c_double), ("target_rel_err", C.c_double)]
+
+
 # Every symbol include/rtx_abi.h declares: (restype, argtypes).  tests/test_abi_symbols.py checks
 # this table against the header and against the loaded library.
 _D3 = C.POINTER(C.c_double)
@@ -152,6 +157,13 @@ ABI = {
     "rtx_write_ppm": (C.c_int32, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rtx_device_math": (C.c_int32, [C.c_int32, _D3, _D3, C.c_int64, _D3]),
     "rtx_device_stream": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _D3]),
+    "rtx_progressive_create": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxShard), C.POINTER(_VP)]),
+    "rtx_progressive_destroy": (None, [_VP]),
+    "rtx_progressive_spp": (C.c_int32, [_VP]),
+    "rtx_progressive_add": (C.c_int32, [_VP, C.c_int32, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_progressive_read": (C.c_int32, [_VP, C.POINTER(RtxFrame), _D3]),
+    "rtx_progressive_stats": (C.c_int32, [_VP, C.c_double, C.POINTER(RtxNoiseStats)]),
+    "rtx_progressive_until": (C.c_int32, [_VP, C.c_int32, C.c_double, C.POINTER(RtxNoiseStats)]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -445,11 +457,74 @@ class Scene:
                                      C.byref(stats) if stats else None))
         return stats
 
+    def progressive(self, cam, cfg, shard=None):
+        """A frame accumulated over several calls (rtx_progressive); cfg.samples_per_pixel is the sample budget."""
+        return Progressive(self, cam, cfg, shard)
+
     def render_count(self, cam, cfg, shard=None):
         sh = RtxShard(*shard, 0) if shard is not None else None
         stats = RtxRenderStats()
         _check(lib.rtx_render_count(self._p, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None, C.byref(stats)))
         return stats
+
+
+class Progressive:
+    """Accumulators of one (scene, camera, config, shard) kept on the device across calls (rtx_progressive_*).
+
+    After k samples, however they were split into add() calls, screen() and moments() are bit-identical to a one-shot
+    render at k spp.  Holds a reference to its Scene, which must not render on another stream while this one does.
+    """
+
+    def __init__(self, scene, cam, cfg, shard=None):
+        self.scene = scene  # the handle must be destroyed before its scene
+        self.width = cfg.image_width
+        self.height = shard_rows(cfg, shard) if shard is not None else image_height(cfg)
+        sh = RtxShard(*shard, 0) if shard is not None else None
+        p = _VP()
+        _check(lib.rtx_progressive_create(scene.ptr, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None, C.byref(p)))
+        self._p = p
+
+    def __del__(self):
+        p, self._p = getattr(self, "_p", None), None
+        if p:
+            lib.rtx_progressive_destroy(p)
+
+    @property
+    def spp_done(self):
+        return lib.rtx_progressive_spp(self._p)
+
+    def add(self, n, stream=0, want_stats=False):
+        """Trace the next n samples of every pixel (asynchronous on `stream` unless want_stats)."""
+        stats = RtxRenderStats() if want_stats else None
+        _check(lib.rtx_progressive_add(self._p, n, _VP(stream or None), C.byref(stats) if stats else None))
+        return stats
+
+    def screen(self, want_accum=True):
+        """The frame at the current sample count, as Scene.render returns it."""
+        accum = np.zeros((self.height, self.width, 3), dtype=np.float64) if want_accum else None
+        rgb8 = np.zeros((self.height, self.width, 3), dtype=np.uint8)
+        frame = RtxFrame(accum.ctypes.data_as(_D3) if want_accum else None, rgb8.ctypes.data_as(C.POINTER(C.c_uint8)))
+        _check(lib.rtx_progressive_read(self._p, C.byref(frame), None))
+        return Screen(self.width, self.height, rgb8, accum)
+
+    def moments(self):
+        """(S, Q): per-pixel sums of the samples' radiances and of their squares, shaped like Screen.accum."""
+        s = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        q = np.zeros_like(s)
+        frame = RtxFrame(s.ctypes.data_as(_D3), None)
+        _check(lib.rtx_progressive_read(self._p, C.byref(frame), q.ctypes.data_as(_D3)))
+        return s, q
+
+    def stats(self, target_rel_err=0.0):
+        out = RtxNoiseStats()
+        _check(lib.rtx_progressive_stats(self._p, target_rel_err, C.byref(out)))
+        return out
+
+    def until(self, batch, target_rel_err):
+        """Add `batch` samples at a time until no pixel's relative error exceeds the target, or the budget is spent."""
+        out = RtxNoiseStats()
+        _check(lib.rtx_progressive_until(self._p, batch, target_rel_err, C.byref(out)))
+        return out
 
 
 class MultiScene:
@@ -540,3 +615,14 @@ def render_scene(builder, world, cam, background, config, max_leaf=0):
     cfg.background[0], cfg.background[1], cfg.background[2] = background
     scene = builder.flatten(world, max_leaf=max_leaf).upload()
     return scene.render(cam, cfg)
+
+
+def render_scene_progressive(builder, world, cam, background, config, batch, target_rel_err, max_leaf=0):
+    """render_scene, refined `batch` samples at a time until no pixel's relative error exceeds target_rel_err or
+    config.samples_per_pixel is reached.  Returns (Screen, RtxNoiseStats of the last batch)."""
+    cfg = RtxConfig.from_buffer_copy(config)
+    cfg.background[0], cfg.background[1], cfg.background[2] = background
+    scene = builder.flatten(world, max_leaf=max_leaf).upload()
+    prog = scene.progressive(cam, cfg)
+    stats = prog.until(batch, target_rel_err)
+    return prog.screen(), stats

@@ -5,11 +5,16 @@
 //
 //   rtx_render [--scene ID] [--aspect A] [--width W] [--spp S] [--depth D] [--threads T] [--seed N]
 //              [--scene-seed N] [--out FILE.ppm] [--camera-aspect A] [--ply FILE] [--earth FILE.ppm]
-//              [--row-chunk-compat]
+//              [--row-chunk-compat] [--batch N --target-error E [--snapshot-every K]]
+//
+// --batch / --target-error render progressively: N samples at a time until no pixel's relative error exceeds E or --spp
+// samples are in (rtx_progressive_until); the spp reached and the final noise stats go to stderr.  --snapshot-every K
+// also writes the frame after every K samples to <out>.<spp>.ppm (needs --out).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include "../csrc/host/world.hpp"
 
 static const size_t THREADS = 11;  // main.rs:4
@@ -25,6 +30,8 @@ int main(int argc, char** argv) {
   const char* ply = nullptr;
   const char* earth = nullptr;
   bool compat = false;
+  int batch = 0, snapshot_every = 0;
+  double target_error = -1.0;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* flag) -> const char* {
       if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", flag); exit(2); }
@@ -43,7 +50,19 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--ply")) ply = need("--ply");
     else if (!strcmp(argv[i], "--earth")) earth = need("--earth");
     else if (!strcmp(argv[i], "--row-chunk-compat")) compat = true;
+    else if (!strcmp(argv[i], "--batch")) batch = atoi(need("--batch"));
+    else if (!strcmp(argv[i], "--target-error")) target_error = atof(need("--target-error"));
+    else if (!strcmp(argv[i], "--snapshot-every")) snapshot_every = atoi(need("--snapshot-every"));
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
+  }
+  const bool progressive = batch > 0 || target_error >= 0.0;
+  if (progressive && (batch <= 0 || !(target_error >= 0.0))) {
+    fprintf(stderr, "--batch N (> 0) and --target-error E (>= 0) go together\n");
+    return 2;
+  }
+  if (snapshot_every > 0 && (!progressive || !out)) {
+    fprintf(stderr, "--snapshot-every needs --batch, --target-error and --out\n");
+    return 2;
   }
   try {
     rtsr::Scene scene(scene_seed);
@@ -56,7 +75,20 @@ int main(int argc, char** argv) {
     rtsr::Config config = rtsr::Config::new_(aspect, width, spp, depth, threads);  // main.rs:11
     config.c.seed = seed;
     config.c.row_chunk_compat = compat ? 1 : 0;
-    rtsr::Screen screen = rtsr::render_scene(scene, wc.world, wc.cam, wc.background, config);  // main.rs:13
+    rtsr::Screen screen;
+    if (progressive) {
+      RtxNoiseStats ns = {};
+      auto snap = [&](const rtsr::Screen& s, int spp_now) {
+        std::string path = std::string(out) + "." + std::to_string(spp_now) + ".ppm";
+        s.write_to_ppm_file(path.c_str());
+      };
+      screen = rtsr::render_scene_progressive(scene, wc.world, wc.cam, wc.background, config, batch, target_error, &ns,
+                                              snapshot_every, snap);
+      fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", ns.spp_done,
+              spp, target_error, ns.pixels_above, ns.pixels, ns.max_rel_err, ns.mean_rel_err);
+    } else {
+      screen = rtsr::render_scene(scene, wc.world, wc.cam, wc.background, config);  // main.rs:13
+    }
     if (out) screen.write_to_ppm_file(out);
     else screen.write_to_ppm();
   } catch (const rtsr::Error& e) {

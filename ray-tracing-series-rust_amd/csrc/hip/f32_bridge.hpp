@@ -3,7 +3,7 @@
 // render.hip is compiled twice: as itself (arithmetic type rt::real = double: the bit-exact path every parity test
 // checks) and through render_f32.hip (rt::real = float, namespaces renamed to rt32 / rtx32: the statistical fast mode of
 // SURVEY.md 8f-4).  The f64 compilation owns the C ABI and its handle types; it hands the f32 compilation byte images of
-// the flat arrays already converted to the f32 layouts (f32_convert.inc) and calls it through the four functions below.
+// the flat arrays already converted to the f32 layouts (f32_convert.inc) and calls it through the functions below.
 // Nothing here mentions a type of either namespace, so both compilations see the same declarations.
 #pragma once
 #include <cstddef>
@@ -26,6 +26,12 @@ struct RtxF32Blobs {
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);
 rtx_status rtx_f32_render(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
                           double* d_accum_rgb, uint8_t* d_rgb8, void* hip_stream, RtxRenderStats* stats);
+// progressive.inc: trace the absolute samples [first, first + count) onto d_accum_rgb (continuing its sums when cont != 0;
+// d_sumsq_rgb, if not NULL, gets the sums of squares), and tone-map an accumulator of spp samples.
+rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
+                                double* d_accum_rgb, double* d_sumsq_rgb, uint32_t first, uint32_t count, int32_t cont,
+                                void* hip_stream, RtxRenderStats* stats);
+rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream);
 rtx_status rtx_f32_trim(void* device_scene);
 void rtx_f32_destroy(void* device_scene);
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error

@@ -16,6 +16,115 @@ __global__ __launch_bounds__(256) void k_reduce_samples(const double* __restrict
   accum[3 * (size_t)lp] = r; accum[3 * (size_t)lp + 1] = g; accum[3 * (size_t)lp + 2] = b;
 }
 
+// k_reduce_samples that also keeps the per-pixel, per-channel sum of squares Q += x*x (progressive rendering,
+// progressive.inc).  S gets exactly k_reduce_samples' adds; the square and its add are separately rounded, so a host
+// restatement of the same in-order loop is bit-equal.
+__global__ __launch_bounds__(256) void k_reduce_samples_moments(const double* __restrict__ samples,
+                                                                double* __restrict__ accum, double* __restrict__ sumsq,
+                                                                uint32_t npix, uint32_t s_count, int first_pass) {
+#pragma clang fp contract(off)
+  uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+  if (lp >= npix) return;
+  double r = 0.0, g = 0.0, b = 0.0, qr = 0.0, qg = 0.0, qb = 0.0;
+  if (!first_pass) {
+    r = accum[3 * (size_t)lp]; g = accum[3 * (size_t)lp + 1]; b = accum[3 * (size_t)lp + 2];
+    qr = sumsq[3 * (size_t)lp]; qg = sumsq[3 * (size_t)lp + 1]; qb = sumsq[3 * (size_t)lp + 2];
+  }
+  for (uint32_t s = 0; s < s_count; ++s) {
+    const double* p = samples + 3 * ((size_t)s * npix + lp);
+    const double x0 = p[0], x1 = p[1], x2 = p[2];
+    r += x0; g += x1; b += x2;
+    qr = __dadd_rn(qr, __dmul_rn(x0, x0));
+    qg = __dadd_rn(qg, __dmul_rn(x1, x1));
+    qb = __dadd_rn(qb, __dmul_rn(x2, x2));
+  }
+  accum[3 * (size_t)lp] = r; accum[3 * (size_t)lp + 1] = g; accum[3 * (size_t)lp + 2] = b;
+  sumsq[3 * (size_t)lp] = qr; sumsq[3 * (size_t)lp + 1] = qg; sumsq[3 * (size_t)lp + 2] = qb;
+}
+
+// Noise estimate of a progressive frame after n >= 2 samples, per pixel and channel:
+//   m = S/n,  var = max(0, (Q - S*S/n) / (n - 1)),  se = sqrt(var / n),  r_c = se / (m + 1/256)
+// and the pixel's error r = max_c r_c.  Every operation is correctly rounded and none is contracted, so r equals a
+// numpy restatement bit for bit.  Reduced over the active pixels to (max r, sum r, count r > target) in a fixed order:
+//   stage 1 (k_noise_stats): one partial per 256-pixel block -- xor-shuffle butterfly inside each wave64, then wave 0
+//            combines the block's four waves from LDS in wave order;
+//   stage 2 (k_noise_stats_final): one block folds the partials -- thread t takes partials t, t + 256, ... in
+//            ascending order, then the same wave / LDS tree.
+// No atomics: the result depends on npix alone, never on scheduling.
+struct NoisePartial {
+  double max_r, sum_r;
+  unsigned long long above;
+};
+
+__device__ __forceinline__ double pixel_rel_err(const double* __restrict__ S, const double* __restrict__ Q, size_t lp,
+                                                double n) {
+#pragma clang fp contract(off)
+  double r = 0.0;
+  for (int c = 0; c < 3; ++c) {
+    const double s = S[3 * lp + c], q = Q[3 * lp + c];
+    const double m = __ddiv_rn(s, n);
+    double var = __ddiv_rn(__dsub_rn(q, __ddiv_rn(__dmul_rn(s, s), n)), __dsub_rn(n, 1.0));
+    var = var > 0.0 ? var : 0.0;
+    const double se = __dsqrt_rn(__ddiv_rn(var, n));
+    const double rc = __ddiv_rn(se, __dadd_rn(m, 1.0 / 256.0));
+    r = rc > r ? rc : r;
+  }
+  return r;
+}
+
+// Block-wide (256 lanes, four waves) reduction in a fixed pattern; the result is valid in thread 0.
+__device__ __forceinline__ NoisePartial noise_block_reduce(NoisePartial v) {
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double om = __shfl_xor(v.max_r, off, 64);
+    const double os = __shfl_xor(v.sum_r, off, 64);
+    const unsigned long long oa = __shfl_xor(v.above, off, 64);
+    v.max_r = om > v.max_r ? om : v.max_r;
+    v.sum_r = v.sum_r + os;
+    v.above += oa;
+  }
+  __shared__ NoisePartial wave_part[4];
+  const uint32_t wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0) wave_part[wave] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    v = wave_part[0];
+    for (int k = 1; k < 4; ++k) {
+      v.max_r = wave_part[k].max_r > v.max_r ? wave_part[k].max_r : v.max_r;
+      v.sum_r = v.sum_r + wave_part[k].sum_r;
+      v.above += wave_part[k].above;
+    }
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void k_noise_stats(const double* __restrict__ S, const double* __restrict__ Q,
+                                                     uint32_t npix, uint32_t spp, double target,
+                                                     NoisePartial* __restrict__ partials) {
+  const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+  NoisePartial v = {0.0, 0.0, 0ull};
+  if (lp < npix) {
+    const double r = pixel_rel_err(S, Q, lp, (double)spp);
+    v.max_r = r;
+    v.sum_r = r;
+    v.above = r > target ? 1ull : 0ull;
+  }
+  v = noise_block_reduce(v);
+  if (threadIdx.x == 0) partials[blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(256) void k_noise_stats_final(const NoisePartial* __restrict__ partials, uint32_t n_partials,
+                                                           NoisePartial* __restrict__ out) {
+  NoisePartial v = {0.0, 0.0, 0ull};
+  for (uint32_t k = threadIdx.x; k < n_partials; k += 256u) {
+    const NoisePartial p = partials[k];
+    v.max_r = p.max_r > v.max_r ? p.max_r : v.max_r;
+    v.sum_r = v.sum_r + p.sum_r;
+    v.above += p.above;
+  }
+  v = noise_block_reduce(v);
+  if (threadIdx.x == 0) *out = v;
+}
+
 __global__ __launch_bounds__(256) void k_tonemap(const double* __restrict__ accum,
                                                  uint8_t* __restrict__ rgb8, uint32_t npix,
                                                  uint32_t spp) {

@@ -30,7 +30,7 @@
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
 #else
-// The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports the four
+// The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports the
 // functions of f32_bridge.hpp and render.hip proper owns the handles.
 namespace rtx { void set_error(const std::string& msg); }
 #endif
@@ -401,10 +401,19 @@ static rtx_status wave_pass(DeviceScene* ds, const rt::RenderParams& rp, const S
   return RTX_OK;
 }
 
+// The slice of a frame's samples one call traces (progressive rendering, progressive.inc): the absolute sample indices
+// [first, first + count), added onto the sums already in the accumulator when cont != 0, with the per-pixel sum of
+// squares kept in sumsq when it is not NULL.  A render without one (range == NULL) is the whole frame from sample 0.
+struct SampleRange {
+  uint32_t first, count;
+  int cont;
+  double* sumsq;
+};
+
 template <bool COUNT>
 static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxConfig* cfg,
                               const RtxShard* shard, double* d_accum_out, uint8_t* d_rgb8_out,
-                              hipStream_t stream, RtxRenderStats* stats) {
+                              hipStream_t stream, RtxRenderStats* stats, const SampleRange* range = nullptr) {
   RtxShard sh;
   rtx_status st = validate(ds, cam, cfg, shard, &sh);
   if (st != RTX_OK) return st;
@@ -447,7 +456,8 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
     if (budget < ds->samples_bytes) budget = ds->samples_bytes;  // what is already there can be used
   }
   uint64_t per_sample_plane = npix * 24ull;
-  uint32_t spp = (uint32_t)cfg->samples_per_pixel;
+  const uint32_t s_first = range ? range->first : 0u;
+  uint32_t spp = range ? range->count : (uint32_t)cfg->samples_per_pixel;  // samples of every pixel this call traces
   uint32_t spp_pass = spp;
   // Two passes in flight (below) when the render needs several passes anyway (C5: 16, C3: 10): each pass then gets half of the
   // buffer.  A render that fits one pass stays one launch -- cut in two it gains the overlapped half of its reduction and loses as
@@ -504,6 +514,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   if (npix < npix_all) {
     HIP_TRY(hipMemsetAsync(accum + 3 * npix, 0, (size_t)(npix_all - npix) * 24, stream));
     if (d_rgb8_out) HIP_TRY(hipMemsetAsync(d_rgb8_out + 3 * npix, 0, (size_t)(npix_all - npix) * 3, stream));
+    if (range && range->sumsq) HIP_TRY(hipMemsetAsync(range->sumsq + 3 * npix, 0, (size_t)(npix_all - npix) * 24, stream));
   }
 
   ShardMap sm = {w, sh.block_rows, sh.shard_index, sh.shard_count};
@@ -534,12 +545,13 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       HIP_TRY(hipEventRecord(ds->ev_pass[2], caller_stream));
       HIP_TRY(hipStreamWaitEvent(ds->aux_stream, ds->ev_pass[2], 0));
     }
-    for (uint32_t s_begin = 0; s_begin < spp; s_begin += spp_pass, ++passes) {
+    for (uint32_t s_off = 0; s_off < spp; s_off += spp_pass, ++passes) {
+      const uint32_t s_begin = s_first + s_off;  // absolute index of the pass's first sample: the key of its random streams
       const int half = pipeline ? (passes & 1) : 0;
       hipStream_t stream = half ? ds->aux_stream : caller_stream;  // (shadows the parameter: every launch below goes to this pass's stream)
       ds->samples = samples_base + (size_t)half * (size_t)spp_pass * (size_t)npix * 3u;
       ds->work_counter = counter_base + half;
-      uint32_t s_count = spp - s_begin < spp_pass ? spp - s_begin : spp_pass;
+      uint32_t s_count = spp - s_off < spp_pass ? spp - s_off : spp_pass;
       uint32_t total = (uint32_t)((uint64_t)s_count * npix);
       if (stats) HIP_TRY(hipEventRecord(ds->ev[0], stream));
       if (use_simple) {
@@ -790,15 +802,20 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       }
       uint32_t pgrid = (uint32_t)((npix + 255) / 256);
       if (pipeline && passes > 0) HIP_TRY(hipStreamWaitEvent(stream, ds->ev_pass[1 - half], 0));  // the previous pass's sums are in
-      hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, stream, ds->samples, accum,
-                         (uint32_t)npix, s_count, s_begin == 0 ? 1 : 0);
+      const int first_pass = s_off == 0 && !(range && range->cont) ? 1 : 0;
+      if (range && range->sumsq)
+        hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, stream, ds->samples, accum, range->sumsq,
+                           (uint32_t)npix, s_count, first_pass);
+      else
+        hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, stream, ds->samples, accum,
+                           (uint32_t)npix, s_count, first_pass);
       HIP_TRY(hipGetLastError());
       if (pipeline) HIP_TRY(hipEventRecord(ds->ev_pass[half], stream));
     }
     if (pipeline && passes > 0 && ((passes - 1) & 1)) HIP_TRY(hipStreamWaitEvent(caller_stream, ds->ev_pass[1], 0));
     if (d_rgb8_out) {
       uint32_t pgrid = (uint32_t)((npix + 255) / 256);
-      hipLaunchKernelGGL(k_tonemap, dim3(pgrid), dim3(256), 0, stream, accum, d_rgb8_out, (uint32_t)npix, spp);
+      hipLaunchKernelGGL(k_tonemap, dim3(pgrid), dim3(256), 0, stream, accum, d_rgb8_out, (uint32_t)npix, s_first + spp);
       HIP_TRY(hipGetLastError());
     }
   }
@@ -819,6 +836,14 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       stats->scatters = c.scatters; stats->texels = c.texels; stats->perlin_calls = c.perlin_calls;
     }
   }
+  return RTX_OK;
+}
+
+// Tone map of an accumulator holding spp samples per pixel (progressive.inc reads a frame at any sample count).
+static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, uint32_t npix, uint32_t spp, hipStream_t stream) {
+  if (npix == 0) return RTX_OK;
+  hipLaunchKernelGGL(k_tonemap, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, npix, spp);
+  HIP_TRY(hipGetLastError());
   return RTX_OK;
 }
 
@@ -1401,4 +1426,5 @@ extern "C" rtx_status rtx_render_scene_with_time(const rtx_scene* s, double t0, 
 }
 
 #include "multi.inc"  // rtx_multi_*: one process, several GPUs, one RCCL gather
+#include "progressive.inc"  // rtx_progressive_*: a frame accumulated over several calls, with its noise estimate
 #endif  // !RTX_F32_TU

@@ -224,6 +224,53 @@ inline Screen render_scene(Scene& s, Hittable world, const Camera& cam, const Co
   return scr;
 }
 
+// render_scene refined `batch` samples at a time (rtx_progressive_*): stops at the first batch boundary where no pixel's
+// relative error exceeds target_rel_err, or at config's samples_per_pixel.  snapshot(screen, spp), if given, is called
+// with the frame at every multiple of snapshot_every samples that falls on a batch boundary.
+template <class Snapshot = void (*)(const Screen&, int)>
+inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
+                                       int batch, double target_rel_err, RtxNoiseStats* stats_out = nullptr,
+                                       int snapshot_every = 0, Snapshot snapshot = nullptr) {
+  config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
+  rtx_flat* flat = nullptr;
+  check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
+  rtx_scene* scene = nullptr;
+  rtx_status st = rtx_scene_upload(flat, &scene);
+  rtx_flat_destroy(flat);
+  check(st);
+  rtx_progressive* prog = nullptr;
+  st = rtx_progressive_create(scene, &cam.c, &config.c, nullptr, &prog);
+  Screen scr;
+  scr.width = config.c.image_width;
+  scr.height = rtx_image_height(&config.c);
+  scr.rgb8.resize((size_t)scr.width * scr.height * 3);
+  scr.accum.resize((size_t)scr.width * scr.height * 3);
+  RtxFrame frame = {scr.accum.data(), scr.rgb8.data()};
+  RtxNoiseStats ns = {};
+  if (st == RTX_OK && snapshot_every <= 0) st = rtx_progressive_until(prog, batch, target_rel_err, &ns);
+  if (st == RTX_OK && snapshot_every > 0) {  // rtx_progressive_until's rule, one batch per step
+    if (batch <= 0) st = rtx_progressive_until(prog, batch, target_rel_err, &ns);  // (reports the bad argument)
+    for (int done = 0; st == RTX_OK && done < config.c.samples_per_pixel;) {
+      const int n = config.c.samples_per_pixel - done < batch ? config.c.samples_per_pixel - done : batch;
+      st = rtx_progressive_add(prog, n, nullptr, nullptr);
+      done += n;
+      if (st == RTX_OK && done % snapshot_every == 0) {
+        st = rtx_progressive_read(prog, &frame, nullptr);
+        if (st == RTX_OK) snapshot(scr, done);
+      }
+      if (st != RTX_OK || done < 2) continue;
+      st = rtx_progressive_stats(prog, target_rel_err, &ns);
+      if (st == RTX_OK && ns.pixels_above == 0) break;
+    }
+  }
+  if (st == RTX_OK) st = rtx_progressive_read(prog, &frame, nullptr);
+  if (stats_out) *stats_out = ns;
+  rtx_progressive_destroy(prog);
+  rtx_scene_destroy(scene);
+  check(st);
+  return scr;
+}
+
 // render_scene on n GPUs of this process: row-interleaved shards, one RCCL gather (replaces the band threads and the
 // collect loop of world.rs:1198-1244 at node scale).
 inline Screen render_scene_multi(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config, int n_gpus) {
