@@ -63,96 +63,119 @@ struct VoteTop {
   rt::FlatRect rect[8];
 };
 
-struct DeviceScene {
-  int device = -1;
-  std::vector<void*> allocations;
-  rt::SceneView view;   // device pointers
-  size_t scene_bytes = 0;
-  int32_t n_nodes = 0;
-  // workspace (grown on demand by render calls)
+// RTX_TRACE_KERNEL: the kernel family a render is forced to (none: choose_trace_kernel decides).
+enum class ForcedKernel { none, simple, persistent, vote, world, wavefront };
+
+// Every RTX_* switch of the launcher, read once per rtx_scene_upload by read_switches (DESIGN section 4 lists them).  A numeric
+// switch outside its range keeps the default; an on/off switch is off when set to anything atoi reads as 0.
+struct TraceSwitches {
+  ForcedKernel kernel = ForcedKernel::none;  // RTX_TRACE_KERNEL
+  bool diag = false;  // RTX_TRACE_KERNEL=vote_diag / world_diag: region counters on stderr (never timed)
+  int ring = -1, wide = -1, scene_lds = -1;  // RTX_RING / RTX_WIDE / RTX_SCENE_LDS: 0 / 1 when set, -1 when not
+  bool vote_top = true, tri_direct = true, mat_lds = true, perlin_lds = true;  // RTX_VOTE_TOP / _TRI_DIRECT / _MAT_LDS / _PERLIN_LDS
+  bool mv_common = true, motion = true, motion_axis = true, lds_wide = false;  // RTX_MV_COMMON / _MOTION / _MOTION_AXIS / _LDS_WIDE
+  bool single_leaf = true, pass_pipeline = true, validate = false;  // RTX_SINGLE_LEAF / _PASS_PIPELINE; RTX_VALIDATE: set at all
+  uint32_t chunk = TRACE_CHUNK_DEFAULT;  // RTX_CHUNK [64, 65536]: sample indices a k_trace_lds wave reserves per grab
+  uint32_t world_threshold = 8;  // RTX_WORLD_THRESHOLD [0, 64]: k_trace_world's walk steps go first while this many lanes walk (0: majority)
+  uint32_t walk_threshold = 0, regen_min = 0, leaf_weight = 0;  // RTX_WALK_THRESHOLD / _REGEN_MIN / _LEAF_WEIGHT [1, 64]; 0: WalkTuning's
+  // wavefront integrator: RTX_WF_PATHS [256, 2^27] path slots; RTX_WF_REFILL [1, 64] free lanes a wave waits for before it takes new
+  // slots; RTX_WF_CHECK [1, 4096] iterations between two looks at the counters; RTX_WF_OCC [4, 6] blocks per CU k_wf_trace is
+  // compiled for (mesh room); RTX_WF_VERBOSE set at all
+  uint32_t wf_paths = 1u << 22, wf_refill = 16, wf_check = 8;
+  int wf_occ = 4;
+  bool wf_verbose = false;
+};
+
+// Render workspace, grown on demand by render calls.  Passes of one render run two deep (render_impl): odd passes on aux_stream
+// with their own half of the sample buffer and their own work counter.
+struct Workspace {
   double* samples = nullptr;
   size_t samples_bytes = 0;
   double* accum = nullptr;
   size_t accum_bytes = 0;
   rt::TraceCounters* counters = nullptr;
-  unsigned int* work_counter = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  int n_cu = 256;
-  int blocks_per_cu[3] = {1, 1, 1};  // resident 256-thread blocks per CU for each preset's persistent kernel
-  bool force_simple = false;          // RTX_TRACE_KERNEL=simple
-  bool force_persistent = false;      // RTX_TRACE_KERNEL=persistent
-  bool force_stream = false;          // RTX_TRACE_KERNEL=stream
-  bool force_vote = false;            // RTX_TRACE_KERNEL=vote
-  bool vote_diag = false;             // RTX_TRACE_KERNEL=vote_diag: occupancy counters on stderr (never timed)
-  unsigned long long* diag = nullptr;
-  int vote_blocks_per_cu[2] = {1, 1};
-  bool vote_ring[2] = {false, false}; // k_trace_vote keeps a ring of ready primary rays in LDS (when it costs no occupancy)
-  bool single_bvh = false;            // world == one BVH entry -> k_trace_lds / k_trace_stream / k_trace_wq apply
-  FlatNode4Dev* nodes4 = nullptr;     // 4-wide culling tree of the BVH entry (big triangle meshes), built at upload
-  int wide_levels = 0, wide_blocks_per_cu = 1;
-  int wide_pers_blocks_per_cu[3] = {1, 1, 1};
-  bool vote_ok = false;               // world == one BVH entry + plain primitive entries -> k_trace_vote applies
-  int32_t vote_bvh_pos = 0;           // position of the BVH entry in the top-level list
-  int32_t vote_tri_base = -1;         // >= 0: that BVH is a pure triangle mesh whose slot s is triangle vote_tri_base + s
-  int stream_blocks_per_cu[2] = {1, 1};
-  uint32_t walk_threshold = 18;       // RTX_WALK_THRESHOLD (1 = never carry a walk over); 18 measured best on C2 (12..22 within 1 %)
-  uint32_t regen_min = 1;             // wide k_trace_vote: lanes that must be waiting before the wave regenerates (RTX_REGEN_MIN)
-  bool single_leaf = false;           // every BVH leaf holds one primitive (k_trace_lds tests it without a loop)
-  uint32_t leaf_weight = 3;           // RTX_LEAF_WEIGHT: node lanes x weight >= leaf lanes -> node step (default: leaf size + 1... see upload)
-  // the same plan for the time-aware instantiation (bigger node records: its own ring size); chosen per render, when the camera's
-  // shutter lies inside the BVH's time interval [motion_t0, motion_t1] (RTX_MOTION=0 turns it off)
-  // ... and for the 4-wide collapse of the tree (static worlds; RTX_LDS_WIDE=0 turns it off): its node image, ring and stack depth
-  bool w4_ok = false, w4_ring = false;
-  uint32_t w4_ring_cap = 0, w4_levels = 0;
-  LdsSceneDims w4_dims = {0, 0, 0, 0, 0, 0};
-  const uint32_t* w4_image = nullptr;
-  bool motion_ok = false, motion_ring = false;
-  uint32_t motion_ring_cap = 0;
-  LdsSceneDims motion_dims = {0, 0, 0, 0, 0, 0};
-  int motion_axis = -1;               // 0 / 1 / 2: every slope of the time-aware boxes is zero except along this axis (-1: no such axis)
-  double motion_t0 = 0.0, motion_t1 = 0.0;
-  // Passes of one render pipelined two deep (render_impl): odd passes run on an internal stream with their own half of the sample
-  // buffer and their own work counter, so the tail, the reduction of pass k and the start of pass k + 1 overlap.  RTX_PASS_PIPELINE=0: off.
+  unsigned int* work_counter = nullptr;   // two: one per pass stream
+  unsigned long long* diag = nullptr;     // region counters of the diagnostic instantiations (diag_clear / diag_print)
+  hipEvent_t ev[2] = {nullptr, nullptr};  // trace time of a pass (stats)
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_pass[3] = {nullptr, nullptr, nullptr};  // reduction of an even / odd pass done; start of the render
-  bool pass_pipeline = true;
-  bool mv_common = false;             // every MovingSphere of the scene has the same (time0, time1) = (mv_t0, mv_t1): k_trace_lds divides once per bounce (RTX_MV_COMMON=0: off)
-  double mv_t0 = 0.0, mv_t1 = 1.0;
-  bool lds_ok = false;                // scene geometry fits in LDS -> k_trace_lds (RTX_SCENE_LDS=0 turns it off)
-  bool lds_ring = false;
-  uint32_t lds_ring_cap = 64;         // entries per wave ring: 64, or 48 / 32 when the scene leaves less LDS
-  uint32_t lds_chunk = TRACE_CHUNK_DEFAULT;  // sample indices a wave reserves per grab (RTX_CHUNK)
-  LdsSceneDims lds_dims = {0, 0, 0, 0, 0, 0};
-  bool force_wq = false;              // RTX_TRACE_KERNEL=wq: workgroup-queue kernel (trace_wq.inc)
-  bool wq_diag = false;               // RTX_TRACE_KERNEL=wq_diag: stage occupancy counters on stderr (never timed)
-  bool wq_ok = false;                 // world fits k_trace_wq's 16-bit work items and LDS budget
-  uint32_t wq_paths = 0, wq_levels = 0, wq_walkers = 12, wq_batch_min = 48;
-  unsigned int* error_word = nullptr;
-  bool force_world = false;           // RTX_TRACE_KERNEL=world: k_trace_world even where a more special kernel applies (A/B)
-  bool world_diag = false;            // RTX_TRACE_KERNEL=world_diag: region counters of k_trace_world on stderr (never timed)
-  uint32_t world_threshold = 8;       // k_trace_world: walk steps have priority while this many lanes walk (RTX_WORLD_THRESHOLD; 0 = plain majority vote)
-  int world_blocks_per_cu[4][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}};  // [book2 preset / any / all incl. gravity spheres / no sphere media][binary / wide]
-  const struct WorldDesc* world_desc = nullptr;       // per-slot records of the world list for k_trace_world
-  VoteTop vote_top;                   // the plain entries beside the BVH, for k_trace_vote's kernarg (n = -1: not applicable)
-  double gravity_time_limit = 1e300;  // scenes with GravitySpheres: the largest shutter time a render accepts (set at upload)
-  uint32_t vote_tables = 0;           // wide k_trace_vote: materials | textures << 16 to keep in LDS (0: none; RTX_MAT_LDS=0)
-  size_t vote_tables_bytes = 0;
-  uint32_t world_mat_lds = 0, world_tex_lds = 0;  // material / texture records k_trace_world copies into LDS (RTX_MAT_LDS=0: none)
-  uint32_t world_perlin_lds = 0;      // Perlin tables k_trace_world copies into LDS (RTX_PERLIN_LDS=0: none)
-  // wavefront integrator (trace_wave.inc): path pool in HBM, grown on demand by render calls
-  bool wave_ok = false;               // world == one BVH + plain primitive entries, sphere / mesh preset
-  bool force_wave = false;            // RTX_TRACE_KERNEL=wavefront
-  bool wave_default = false;          // the launcher prefers it for this scene (set at upload)
-  uint32_t wave_paths = 1u << 22;     // RTX_WF_PATHS: path slots P
-  uint32_t wave_refill = 16;          // RTX_WF_REFILL: free lanes a wave waits for before it takes new slots
-  uint32_t wave_check = 8;            // RTX_WF_CHECK: iterations between two looks at the counters
-  void* wave_mem = nullptr;
+  void* wave_mem = nullptr;               // the wavefront integrator's path pool
   size_t wave_bytes = 0;
-  uint32_t* wave_host_ctrl = nullptr; // pinned
-  int wave_blocks_per_cu = 1;
-  int wave_iterations = 0;            // of the last render (diagnostics)
-  int wave_occ = 4;                   // RTX_WF_OCC: 256-thread blocks per CU k_wf_trace is compiled for (4 / 5 / 6; mesh room)
-  bool wave_verbose = false;          // RTX_WF_VERBOSE
+  uint32_t* wave_host_ctrl = nullptr;     // pinned
+};
+
+// k_trace_vote (trace_vote.inc), binary tree; the wavefront integrator applies to the same worlds.
+struct VotePlan {
+  bool ok = false;                // world == one BVH entry + plain primitive entries
+  int32_t bvh_pos = 0;            // position of the BVH entry in the top-level list
+  int32_t tri_base = -1;          // >= 0: that BVH is a pure triangle mesh whose slot s is triangle tri_base + s
+  VoteTop top;                    // the plain entries beside the BVH, for the kernarg (n = -1: not applicable)
+  int blocks_per_cu[2] = {1, 1};  // [preset]
+  bool ring[2] = {false, false};  // a ring of ready primary rays in LDS (when it costs no occupancy)
+  uint32_t tables = 0;            // wide k_trace_vote: materials | textures << 16 to keep in LDS (0: none)
+  size_t tables_bytes = 0;
+};
+
+// 4-wide culling tree (FlatNode4) of every BVH of the scene, for k_trace_vote, k_trace_persistent and k_trace_world.
+struct WidePlan {
+  FlatNode4Dev* nodes4 = nullptr;
+  int levels = 0;                 // stack levels of a wide walk
+  int vote_blocks_per_cu = 1;
+  int pers_blocks_per_cu[3] = {1, 1, 1};  // [preset]
+};
+
+// k_trace_world (trace_world.inc).
+struct WorldPlan {
+  const WorldDesc* desc = nullptr;  // per-slot records of the world list
+  uint32_t mat_lds = 0, tex_lds = 0;  // material / texture records it copies into LDS
+  uint32_t perlin_lds = 0;          // Perlin tables it copies into LDS
+  int blocks_per_cu[4][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}};  // [book2 preset / any / all incl. gravity spheres / no sphere media][binary / wide]
+};
+
+// One k_trace_lds variant fitted into the LDS of a block (fit_lds).
+struct LdsFit {
+  bool ok = false;
+  uint32_t ring_cap = 0;          // entries per wave ring: 64 or 48 (0: no ring)
+  uint32_t levels = 0;            // stack levels
+  LdsSceneDims dims = {0, 0, 0, 0, 0, 0};
+};
+
+// k_trace_lds (trace_lds.inc): sphere worlds of one BVH whose geometry fits in LDS.
+struct LdsPlan {
+  LdsFit plain;                   // the binary tree
+  LdsFit w4;                      // the 4-wide collapse of the tree (static worlds, RTX_LDS_WIDE=1) and its node image
+  const uint32_t* w4_image = nullptr;
+  // time-aware boxes: chosen per render, when the camera's shutter lies inside the BVH's time interval [motion_t0, motion_t1]
+  LdsFit motion;
+  int motion_axis = -1;           // 0 / 1 / 2: every slope of the time-aware boxes is zero except along this axis (-1: no such axis)
+  double motion_t0 = 0.0, motion_t1 = 0.0;
+  bool mv_common = false;         // every MovingSphere of the scene has the same (time0, time1) = (mv_t0, mv_t1): one division per bounce
+  double mv_t0 = 0.0, mv_t1 = 1.0;
+};
+
+// Tuning of the voting walks (k_trace_vote, k_trace_lds, k_trace_world, k_trace_persistent, the wavefront integrator).
+struct WalkTuning {
+  uint32_t walk_threshold = 18;   // 1 = never carry a walk over; 18 measured best on C2 (12..22 within 1 %)
+  uint32_t regen_min = 1;         // wide k_trace_vote: lanes that must be waiting before the wave regenerates
+  uint32_t leaf_weight = 3;       // node lanes x weight >= leaf lanes -> node step
+  bool single_leaf = false;       // every BVH leaf holds one primitive (k_trace_lds tests it without a loop)
+};
+
+struct DeviceScene {
+  int device = -1;
+  std::vector<void*> allocations;
+  rt::SceneView view;   // device pointers
+  size_t scene_bytes = 0;
+  int n_cu = 256;
+  double gravity_time_limit = 1e300;  // scenes with GravitySpheres: the largest shutter time a render accepts
+  TraceSwitches sw;
+  Workspace ws;
+  int pers_blocks_per_cu[3] = {1, 1, 1};  // resident 256-thread blocks per CU for each preset's k_trace_persistent
+  VotePlan vote;
+  WidePlan wide;
+  WorldPlan world;
+  LdsPlan lds;
+  WalkTuning walk;
 };
 
 #define HIP_TRY(expr)                                                                      \
@@ -180,20 +203,20 @@ static rtx_status upload_array(DeviceScene* ds, const std::vector<T>& v, const T
 
 static void free_device_scene(DeviceScene* ds) {
   if (!ds) return;
+  Workspace& ws = ds->ws;
   for (void* p : ds->allocations) (void)hipFree(p);
-  if (ds->samples) (void)hipFree(ds->samples);
-  if (ds->accum) (void)hipFree(ds->accum);
-  if (ds->counters) (void)hipFree(ds->counters);
-  if (ds->work_counter) (void)hipFree(ds->work_counter);
-  if (ds->diag) (void)hipFree(ds->diag);
-  if (ds->error_word) (void)hipFree(ds->error_word);
-  if (ds->wave_mem) (void)hipFree(ds->wave_mem);
-  if (ds->wave_host_ctrl) (void)hipHostFree(ds->wave_host_ctrl);
+  if (ws.samples) (void)hipFree(ws.samples);
+  if (ws.accum) (void)hipFree(ws.accum);
+  if (ws.counters) (void)hipFree(ws.counters);
+  if (ws.work_counter) (void)hipFree(ws.work_counter);
+  if (ws.diag) (void)hipFree(ws.diag);
+  if (ws.wave_mem) (void)hipFree(ws.wave_mem);
+  if (ws.wave_host_ctrl) (void)hipHostFree(ws.wave_host_ctrl);
   for (int i = 0; i < 2; ++i)
-    if (ds->ev[i]) (void)hipEventDestroy(ds->ev[i]);
+    if (ws.ev[i]) (void)hipEventDestroy(ws.ev[i]);
   for (int i = 0; i < 3; ++i)
-    if (ds->ev_pass[i]) (void)hipEventDestroy(ds->ev_pass[i]);
-  if (ds->aux_stream) (void)hipStreamDestroy(ds->aux_stream);
+    if (ws.ev_pass[i]) (void)hipEventDestroy(ws.ev_pass[i]);
+  if (ws.aux_stream) (void)hipStreamDestroy(ws.aux_stream);
   delete ds;
 }
 
@@ -262,12 +285,9 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 }
 
 // ------------------------------------------------------------------ kernels
-#include "trace_basic.inc"   // k_trace_simple, k_trace_persistent, k_trace_stream
+#include "trace_basic.inc"   // k_trace_simple, k_trace_persistent
 #include "trace_vote.inc"    // voting walk, 4-wide tree, k_trace_vote
 #include "trace_world.inc"   // k_trace_world: any world, per-lane scan of the world list with carried-over walks
-#ifdef RTX_EXPERIMENTAL_KERNELS
-#include "trace_wq.inc"      // k_trace_wq: measured dead end kept for A/B (build with -DRTX_EXPERIMENTAL_KERNELS)
-#endif
 #include "trace_lds.inc"     // k_trace_lds (the headline kernel)
 #include "trace_wave.inc"    // k_wf_generate / k_wf_trace / k_wf_shade: the split-kernel integrator (path state in HBM)
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
@@ -312,25 +332,556 @@ static rt::RenderParams make_params(const RtxCamera* cam, const RtxConfig* cfg) 
   return rp;
 }
 
-// One pass (s_count samples of every pixel of the shard) through the wavefront integrator: iterations of
-// generate -> trace -> shade over the P path slots until every sample of the pass has been written.
-static rtx_status wave_pass(DeviceScene* ds, const rt::RenderParams& rp, const ShardMap& sm, uint32_t s_begin, uint32_t total,
-                            uint32_t npix, hipStream_t stream, int preset, uint32_t feat) {
-  uint32_t P = ds->wave_paths;
-  if ((uint64_t)P > (uint64_t)total) P = total;
+// ------------------------------------------------------------------ switches and common helpers
+static TraceSwitches read_switches() {
+  // a numeric switch: its value when set and within [lo, hi], else dflt; an on/off switch: 1 or 0 when set, -1 when not
+  auto num = [](const char* n, int lo, int hi, uint32_t dflt) { const char* s = getenv(n); return s && atoi(s) >= lo && atoi(s) <= hi ? (uint32_t)atoi(s) : dflt; };
+  auto flag = [](const char* n) { const char* s = getenv(n); return s ? (atoi(s) != 0 ? 1 : 0) : -1; };
+  TraceSwitches sw;
+  if (const char* k = getenv("RTX_TRACE_KERNEL")) {
+    const std::string s = k;
+    if (s == "simple") sw.kernel = ForcedKernel::simple;
+    else if (s == "persistent") sw.kernel = ForcedKernel::persistent;
+    else if (s == "vote" || s == "vote_diag") sw.kernel = ForcedKernel::vote;
+    else if (s == "world" || s == "world_diag") sw.kernel = ForcedKernel::world;
+    else if (s == "wavefront") sw.kernel = ForcedKernel::wavefront;
+    sw.diag = s == "vote_diag" || s == "world_diag";
+  }
+  sw.ring = flag("RTX_RING"); sw.wide = flag("RTX_WIDE"); sw.scene_lds = flag("RTX_SCENE_LDS");
+  sw.vote_top = flag("RTX_VOTE_TOP") != 0; sw.tri_direct = flag("RTX_TRI_DIRECT") != 0;
+  sw.mat_lds = flag("RTX_MAT_LDS") != 0; sw.perlin_lds = flag("RTX_PERLIN_LDS") != 0;
+  sw.mv_common = flag("RTX_MV_COMMON") != 0; sw.motion = flag("RTX_MOTION") != 0; sw.motion_axis = flag("RTX_MOTION_AXIS") != 0;
+  sw.lds_wide = flag("RTX_LDS_WIDE") == 1; sw.single_leaf = flag("RTX_SINGLE_LEAF") != 0; sw.pass_pipeline = flag("RTX_PASS_PIPELINE") != 0;
+  sw.validate = getenv("RTX_VALIDATE") != nullptr;
+  sw.chunk = num("RTX_CHUNK", 64, 65536, sw.chunk);
+  sw.world_threshold = num("RTX_WORLD_THRESHOLD", 0, 64, sw.world_threshold);
+  sw.walk_threshold = num("RTX_WALK_THRESHOLD", 1, 64, 0); sw.regen_min = num("RTX_REGEN_MIN", 1, 64, 0); sw.leaf_weight = num("RTX_LEAF_WEIGHT", 1, 64, 0);
+  const char* wp = getenv("RTX_WF_PATHS");
+  if (wp && atol(wp) >= 256 && atol(wp) <= (1l << 27)) sw.wf_paths = (uint32_t)atol(wp);
+  sw.wf_refill = num("RTX_WF_REFILL", 1, 64, sw.wf_refill); sw.wf_check = num("RTX_WF_CHECK", 1, 4096, sw.wf_check);
+  sw.wf_occ = (int)num("RTX_WF_OCC", 4, 6, (uint32_t)sw.wf_occ); sw.wf_verbose = getenv("RTX_WF_VERBOSE") != nullptr;
+  return sw;
+}
+
+// LDS bytes of the traversal stacks of a TRACE_BLOCK-thread block
+static size_t stack_bytes(uint32_t levels) { return (size_t)levels * TRACE_BLOCK * sizeof(int32_t); }
+
+// Resident TRACE_BLOCK-thread blocks per CU of a kernel with `lds` bytes of dynamic LDS (0: the query failed).
+template <class K>
+static int occupancy(K kernel, size_t lds) {
+  int nb = 0;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, TRACE_BLOCK, lds) == hipSuccess ? nb : 0;
+}
+
+// Grid of a persistent launch: one block per `block` work items, at most `resident` blocks.
+static uint32_t grid_size(uint32_t total, uint32_t block, uint64_t resident) {
+  const uint64_t want = ((uint64_t)total + block - 1) / block;
+  return (uint32_t)(want < resident ? want : resident);
+}
+
+// A device buffer grown to `need` bytes (its contents are not kept); the stream's work is finished before the old one is freed.
+static rtx_status grow_buffer(void** p, size_t* bytes, size_t need, hipStream_t stream) {
+  if (need <= *bytes) return RTX_OK;
+  if (*p) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(*p)); *p = nullptr; *bytes = 0; }
+  HIP_TRY(hipMalloc(p, need));
+  *bytes = need;
+  return RTX_OK;
+}
+
+// What every trace launch of one pass takes (render_impl's pass loop).
+struct PassArgs {
+  rt::RenderParams rp;
+  ShardMap sm;
+  uint32_t s_begin, total, npix;  // absolute index of the pass's first sample; (sample, pixel) items of the pass; pixels of the shard
+  double* samples;                // this pass's half of the sample buffer, its work counter and stream
+  unsigned int* work_counter;
+  hipStream_t stream;
+  int preset;                     // 0 spheres / 1 mesh / 2 anything (P_SPHERES, P_MESH); feat: the scene's features
+  uint32_t feat;
+  uint32_t stack_levels;          // of the binary tree (max_stack + 1) and the bytes of its stacks
+  size_t stack_lds;
+};
+
+// The diagnostic instantiations (RTX_TRACE_KERNEL=vote_diag / world_diag) count executions and active lanes per region into
+// ws.diag.  run_diag clears the counters, launches, waits for the kernel and prints one line per region into stderr; h gets
+// the counters.  Never timed; scripts/kernel_diag.py and DESIGN section 5.3 read these lines.
+template <class Launch>
+static rtx_status run_diag(DeviceScene* ds, hipStream_t stream, Launch launch, const char* tag, int width, const char* const* names,
+                           int n, unsigned long long (&h)[24]) {
+  if (!ds->ws.diag) HIP_TRY(hipMalloc((void**)&ds->ws.diag, sizeof(h)));
+  HIP_TRY(hipMemsetAsync(ds->ws.diag, 0, sizeof(h), stream));
+  launch();
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(h, ds->ws.diag, sizeof(h), hipMemcpyDeviceToHost));
+  for (int k = 0; k < n; ++k)
+    fprintf(stderr, "[%s] %-*s executions %llu lanes %llu mean lanes %.2f\n", tag, width, names[k], h[2 * k], h[2 * k + 1],
+            h[2 * k] ? (double)h[2 * k + 1] / (double)h[2 * k] : 0.0);
+  return RTX_OK;
+}
+
+// Leaves of the scene's binary BVH nodes: the most primitives in one leaf, the end of the highest leaf slot.
+struct LeafScan { uint32_t max_count = 0, max_end = 0; };
+static LeafScan scan_leaves(const FlatScene& fs) {
+  LeafScan s;
+  for (const rt::FlatNode& nd : fs.nodes)
+    for (int ch = 0; ch < 2; ++ch)
+      if (nd.child[ch] < 0) {
+        s.max_count = std::max(s.max_count, rt::leaf_count(nd.child[ch]));
+        s.max_end = std::max(s.max_end, rt::leaf_first(nd.child[ch]) + rt::leaf_count(nd.child[ch]));
+      }
+  return s;
+}
+
+// ------------------------------------------------------------------ k_trace_vote
+static void plan_vote(DeviceScene* ds, const FlatScene& fs) {
+  VotePlan& p = ds->vote;
+  const TraceSwitches& sw = ds->sw;
+  const size_t lds = stack_bytes((uint32_t)fs.max_stack + 1u), lds_ring = lds + (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE;
+  const bool ring_fits = lds_ring <= 64 * 1024;
+  auto fit = [&](int preset, int nb0, int nb1, bool ring_by_default) {
+    p.ring[preset] = ring_by_default && nb1 > 0 && nb1 >= nb0 && ring_fits;
+    if (sw.ring >= 0 && nb1 > 0 && ring_fits) p.ring[preset] = sw.ring != 0;
+    const int nb = p.ring[preset] ? nb1 : nb0;
+    if (nb > 0) p.blocks_per_cu[preset] = nb;
+  };
+  fit(0, occupancy(k_trace_vote<P_SPHERES, false, false, false>, lds), occupancy(k_trace_vote<P_SPHERES, false, true, false>, lds_ring), true);
+  // measured on the mesh room: no gain from the ring, and its live state spills 50 dwords there
+  fit(1, occupancy(k_trace_vote<P_MESH, false, false, false>, lds), occupancy(k_trace_vote<P_MESH, false, true, false>, lds_ring), false);
+
+  memset(&p.top, 0, sizeof(p.top));
+  p.top.n = -1;
+  int n_bvh = 0, n_other = 0;
+  for (size_t k = 0; k < fs.top_level.size(); ++k) {
+    const int32_t kind = fs.entries[fs.top_level[k]].kind;
+    if (kind == rt::ENTRY_BVH) { ++n_bvh; p.bvh_pos = (int32_t)k; }
+    else if (kind != rt::ENTRY_PRIM) ++n_other;
+  }
+  p.ok = n_bvh == 1 && n_other == 0;
+  if (p.ok && fs.top_level.size() <= 9 && sw.vote_top) {
+    p.top.n = 0;
+    p.top.all_rects = 1;
+    for (size_t k = 0; k < fs.top_level.size(); ++k) {
+      if ((int32_t)k == p.bvh_pos) continue;
+      const rt::PrimRef ref = (rt::PrimRef)fs.entries[fs.top_level[k]].a;
+      p.top.k[p.top.n] = (int32_t)k;
+      p.top.ref[p.top.n] = (uint32_t)ref;
+      if (rt::primref_type(ref) == rt::PRIM_RECT) p.top.rect[p.top.n] = fs.rects[rt::primref_index(ref)];
+      else p.top.all_rects = 0;
+      p.top.n += 1;
+    }
+    if (!p.top.all_rects) p.top.n = -1;
+  }
+  if (p.ok) {
+    const rt::FlatEntry& be = fs.entries[fs.top_level[p.bvh_pos]];
+    bool pure = be.c > 0 && rt::primref_type(fs.refs[be.b]) == rt::PRIM_TRIANGLE;
+    const uint32_t t0 = pure ? rt::primref_index(fs.refs[be.b]) : 0u;
+    for (int32_t k = 0; pure && k < be.c; ++k)
+      pure = fs.refs[be.b + k] == rt::make_primref(rt::PRIM_TRIANGLE, t0 + (uint32_t)k);
+    if (pure && sw.tri_direct) p.tri_base = (int32_t)t0;
+  }
+  if (!fs.materials.empty() && !fs.textures.empty() && fs.materials.size() <= 16 && fs.textures.size() <= 16 && sw.mat_lds) {
+    p.tables = (uint32_t)fs.materials.size() | ((uint32_t)fs.textures.size() << 16);
+    p.tables_bytes = fs.materials.size() * sizeof(rt::FlatMaterial) + fs.textures.size() * sizeof(rt::FlatTexture);
+  }
+}
+
+// The wide instantiations (preset 1 with a 4-wide tree): material / texture records behind the stacks when that costs no
+// resident block.
+static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag) {
+  const VotePlan& p = ds->vote;
+  const WidePlan& wt = ds->wide;
+  uint32_t lds_tables = 0;
+  size_t lds = stack_bytes((uint32_t)wt.levels);
+  if (p.tables_bytes > 0 && (lds + p.tables_bytes) * (size_t)wt.vote_blocks_per_cu <= 160 * 1024) {
+    lds_tables = p.tables;
+    lds += p.tables_bytes;
+  }
+  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)wt.vote_blocks_per_cu);
+  const uint32_t threshold = ds->walk.walk_threshold | (ds->walk.regen_min << 16);
+#define LAUNCH_VOTE_WIDE(FEAT, DIAGF, THRESHOLD)                                                                       \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, false, true>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
+                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter,                      \
+                     DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, THRESHOLD, (uint32_t)wt.levels,              \
+                     (uint32_t)p.bvh_pos, wt.nodes4, p.tri_base, lds_tables, p.top)
+  // a triangle mesh in a room of rectangles, no spheres / lists / glass (the dragon room): the leaner instantiation
+  const bool room = (a.feat & ~P_MESH_ROOM) == 0;
+  if (diag && room) {
+    unsigned long long h[24];
+    static const char* const names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "shade_all"};
+    const rtx_status st = run_diag(ds, a.stream, [&] { LAUNCH_VOTE_WIDE(P_MESH_ROOM, true, ds->walk.walk_threshold); }, "vote_diag", 10, names, 6, h);
+    if (st != RTX_OK) return st;
+    if (h[12]) {
+      float v[12];
+      for (int k = 0; k < 6; ++k) { uint32_t lo = (uint32_t)h[13 + k], hi = (uint32_t)(h[13 + k] >> 32); memcpy(&v[2 * k], &lo, 4); memcpy(&v[2 * k + 1], &hi, 4); }
+      fprintf(stderr, "[vote_diag] %llu walks of >= 50000 node steps; the first: origin (%g %g %g) direction (%g %g %g) 1/d (%g %g %g) err2 %g t_min %g t_max %g depth left %llu\n",
+              h[12], v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], h[19]);
+    }
+  } else if (room) {
+    LAUNCH_VOTE_WIDE(P_MESH_ROOM, false, threshold);
+  } else {
+    LAUNCH_VOTE_WIDE(P_MESH, false, threshold);
+  }
+#undef LAUNCH_VOTE_WIDE
+  return RTX_OK;
+}
+
+static rtx_status launch_vote(DeviceScene* ds, const PassArgs& a) {
+  const VotePlan& p = ds->vote;
+  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
+  const bool diag = ds->sw.kernel == ForcedKernel::vote && ds->sw.diag;
+  if (a.preset == 1 && ds->wide.nodes4) return launch_vote_wide(ds, a, diag);
+  const bool ring = p.ring[a.preset];
+  const size_t lds = a.stack_lds + (ring ? (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE : 0);
+  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[a.preset]);
+#define LAUNCH_VOTE2(FEAT, DIAGF, RINGF)                                                                                 \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
+                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter,                       \
+                     DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, ds->walk.walk_threshold, a.stack_levels,      \
+                     (uint32_t)p.bvh_pos, (const FlatNode4*)nullptr, p.tri_base, 0u, p.top)
+#define LAUNCH_VOTE(FEAT, DIAGF) do { if (ring) { LAUNCH_VOTE2(FEAT, DIAGF, true); } else { LAUNCH_VOTE2(FEAT, DIAGF, false); } } while (0)
+  if (diag && a.preset == 0) {
+    unsigned long long h[24];
+    static const char* const names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "walking"};
+    return run_diag(ds, a.stream, [&] { LAUNCH_VOTE(P_SPHERES, true); }, "vote_diag", 10, names, 6, h);
+  }
+  if (a.preset == 0) { LAUNCH_VOTE(P_SPHERES, false); }
+  else { LAUNCH_VOTE(P_MESH, false); }
+#undef LAUNCH_VOTE
+#undef LAUNCH_VOTE2
+  return RTX_OK;
+}
+
+// ------------------------------------------------------------------ 4-wide tree
+// Host check (RTX_VALIDATE): walk every wide tree, codes in range, stack use within `levels`.
+static void validate_wide_tree(const FlatScene& fs, const std::vector<FlatNode4>& wide, int levels) {
+  for (const rt::FlatEntry& e : fs.entries) {
+    if (e.kind != rt::ENTRY_BVH) continue;
+    std::vector<std::pair<int32_t, int>> todo;  // (code, stack entries below it)
+    todo.push_back({e.a, 0});
+    size_t visited = 0, bad = 0; int deepest = 0;
+    while (!todo.empty()) {
+      auto [code, below] = todo.back(); todo.pop_back();
+      if (code < 0) { if (rt::leaf_first(code) + rt::leaf_count(code) > (uint32_t)e.c) ++bad; continue; }
+      if ((size_t)code >= wide.size()) { ++bad; continue; }
+      ++visited;
+      int nk = 0;
+      for (int k = 0; k < 4; ++k) if (wide[code].child[k] != 0x7fffffff) ++nk;
+      deepest = std::max(deepest, below + nk);
+      for (int k = 0; k < 4; ++k) if (wide[code].child[k] != 0x7fffffff) todo.push_back({wide[code].child[k], below + nk - 1});
+    }
+    fprintf(stderr, "[rtx] RTX_VALIDATE: BVH root %d refs %d: %zu wide nodes walked, %zu bad codes, deepest stack %d of %d levels, sizeof(real) %zu\n",
+            e.a, e.c, visited, bad, deepest, levels, sizeof(rt::real));
+  }
+}
+
+// 4-wide culling tree (see FlatNode4) for every BVH of the scene: big triangle meshes under k_trace_vote (needs VotePlan::ok),
+// and any world that takes k_trace_persistent (Book-2: two BVHs walked per bounce, each step a dependent L2 fetch).
+// RTX_WIDE=0/1 overrides the size tests.
+static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
+  WidePlan& p = ds->wide;
+  const bool spheres_preset = (fs.features & ~P_SPHERES) == 0;
+  const bool mesh_preset = !spheres_preset && (fs.features & ~P_MESH) == 0;
+  const int preset = spheres_preset ? 0 : (mesh_preset ? 1 : 2);
+  const bool for_vote = ds->vote.ok && mesh_preset;
+  const bool for_pers = !(ds->vote.ok && preset < 2) && preset >= 1;
+  bool want_wide = (for_vote && fs.nodes.size() >= 4096) || (for_pers && fs.nodes.size() >= 256);
+  if (ds->sw.wide >= 0) want_wide = (for_vote || for_pers) && ds->sw.wide != 0 && !fs.nodes.empty();
+  if (!want_wide) return RTX_OK;
+  std::vector<FlatNode4> wide(fs.nodes.size());
+  memset(wide.data(), 0, wide.size() * sizeof(FlatNode4));
+  int peak = 0;
+  for (const rt::FlatEntry& e : fs.entries)
+    if (e.kind == rt::ENTRY_BVH) peak = std::max(peak, build_wide_nodes(fs.nodes, e.a, &wide));
+  p.levels = peak + 1;  // (the spare level is the bottom slot of LdsStackB; walk_node_step4 needs none of its own)
+  const size_t lds = stack_bytes((uint32_t)p.levels);
+  bool ok = lds <= 64 * 1024;
+  if (ok && for_vote) {
+    const int nb = occupancy(k_trace_vote<P_MESH, false, false, true>, lds);
+    ok = nb > 0;
+    if (ok) p.vote_blocks_per_cu = nb;
+  }
+  if (ok) {
+    const int n1 = occupancy(k_trace_persistent<P_MESH, true>, lds), n2 = occupancy(k_trace_persistent<P_ANY, true>, lds);
+    if (n1 > 0) p.pers_blocks_per_cu[1] = n1;
+    if (n2 > 0) p.pers_blocks_per_cu[2] = n2;
+    ok = n1 > 0 && n2 > 0;
+  }
+  if (ok) {
+    rtx_status st = upload_array(ds, wide, &p.nodes4);
+    if (st != RTX_OK) return st;
+  }
+  if (ds->sw.wide >= 0) fprintf(stderr, "[rtx] RTX_WIDE: 4-wide tree %s (%d stack levels)\n", p.nodes4 ? "on" : "off", p.levels);
+  if (ds->sw.validate) validate_wide_tree(fs, wide, p.levels);
+  return RTX_OK;
+}
+
+// ------------------------------------------------------------------ k_trace_world
+// Needs WidePlan: the LDS tables go with the stacks of the tree the kernel walks.
+static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
+  WorldPlan& p = ds->world;
+  const TraceSwitches& sw = ds->sw;
+  rtx_status st = upload_array(ds, build_world_desc(fs), &p.desc);
+  if (st != RTX_OK) return st;
+  for (int wd = 0; wd < 2; ++wd) {
+    const uint32_t levels = (uint32_t)(wd ? ds->wide.levels : fs.max_stack + 1);
+    size_t wl = stack_bytes(levels) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real);
+    if (wl > 64 * 1024) continue;
+    // Perlin tables in LDS when that costs no resident block (3 per CU at 168 VGPRs: up to 53 KB each)
+    if ((wd != 0) == (ds->wide.nodes4 != nullptr)) {
+      const size_t n_p = fs.perlins.size();
+      if (n_p >= 1 && n_p <= 2 && sw.perlin_lds && wl + n_p * sizeof(rt::FlatPerlin) <= 52 * 1024) {
+        p.perlin_lds = (uint32_t)n_p;
+        wl += n_p * sizeof(rt::FlatPerlin);
+      }
+      const size_t mt = fs.materials.size() * sizeof(rt::FlatMaterial) + fs.textures.size() * sizeof(rt::FlatTexture);
+      if (!fs.materials.empty() && !fs.textures.empty() && fs.materials.size() <= 64 && fs.textures.size() <= 64 && sw.mat_lds &&
+          wl + mt <= 52 * 1024) {
+        p.mat_lds = (uint32_t)fs.materials.size();
+        p.tex_lds = (uint32_t)fs.textures.size();
+        wl += mt;
+      }
+    }
+    int n = 0;
+#define WORLD_OCC(I, FEAT) if ((n = occupancy(wd ? k_trace_world<FEAT, true, WORLD_WPS> : k_trace_world<FEAT, false, WORLD_WPS>, wl)) > 0) p.blocks_per_cu[I][wd] = n
+    WORLD_OCC(0, P_BOOK2); WORLD_OCC(1, P_ANY); WORLD_OCC(2, P_ALL); WORLD_OCC(3, P_NO_SPHERE_MEDIA);
+#undef WORLD_OCC
+  }
+  return RTX_OK;
+}
+
+static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
+  const WorldPlan& p = ds->world;
+  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
+  const bool wide = ds->wide.nodes4 != nullptr;
+  const bool book2 = (a.feat & ~P_BOOK2) == 0;
+  const bool has_gravity = (a.feat & rt::F_GRAVITY_SPHERE) != 0;
+  const bool no_sphere_media = (a.feat & rt::F_MEDIUM_SPHERE) == 0;
+  const uint32_t levels = wide ? (uint32_t)ds->wide.levels : a.stack_levels;
+  const size_t lds = stack_bytes(levels) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real) +
+                     (size_t)p.perlin_lds * sizeof(rt::FlatPerlin) + (size_t)p.mat_lds * sizeof(rt::FlatMaterial) +
+                     (size_t)p.tex_lds * sizeof(rt::FlatTexture);
+  const int family = has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1));
+  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[family][wide ? 1 : 0]);
+  const rt::SceneView& v = ds->view;
+#define LAUNCH_WORLD2(FEAT, WIDEF, DIAGF)                                                                                   \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<FEAT, WIDEF, WORLD_WPS, DIAGF>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
+                     v, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, v.entries, v.top_level, v.spheres, \
+                     v.moving_spheres, v.rects, v.triangles, v.materials, v.textures, v.refs, ds->wide.nodes4, p.desc,     \
+                     ds->walk.leaf_weight, ds->sw.world_threshold, levels, p.perlin_lds, p.mat_lds, p.tex_lds,             \
+                     DIAGF ? ds->ws.diag : nullptr)
+#define LAUNCH_WORLD(FEAT) do { if (wide) { LAUNCH_WORLD2(FEAT, true, false); } else { LAUNCH_WORLD2(FEAT, false, false); } } while (0)
+  if (ds->sw.kernel == ForcedKernel::world && ds->sw.diag && book2 && wide) {
+    unsigned long long h[24];
+    static const char* const names[8] = {"node_step", "leaf_step", "sweep", "shade(lean)", "regen", "direct_entry(all)", "direct_entry(run)", "shade(rare)"};
+    return run_diag(ds, a.stream, [&] { LAUNCH_WORLD2(P_BOOK2, true, true); }, "world_diag", 18, names, 8, h);
+  }
+  if (has_gravity) { LAUNCH_WORLD(P_ALL); }  // the bouncing-ball scene: the instantiation that carries GravitySphere code
+  else if (book2) { LAUNCH_WORLD(P_BOOK2); }
+  else if (no_sphere_media) { LAUNCH_WORLD(P_NO_SPHERE_MEDIA); }
+  else { LAUNCH_WORLD(P_ANY); }
+#undef LAUNCH_WORLD
+#undef LAUNCH_WORLD2
+  return RTX_OK;
+}
+
+// ------------------------------------------------------------------ k_trace_lds
+// Fits one k_trace_lds variant (f->levels, f->dims) into lds_max bytes: with a primary-ray ring of 64, else 48 entries when
+// want_ring, else without one.  (A small ring is worse than none: its refills run with that few lanes -- HEAD Book-1, ring of
+// 16: 3137 Msamples/s against 3774 without; ring of 32 on the final build of round 3: 4963 against 5196.)
+static void fit_lds(LdsFit* f, bool want_ring, uint32_t lds_max) {
+  for (uint32_t cap : {64u, 48u, 0u})
+    if ((want_ring || cap == 0u) && ldsk_layout(f->levels, cap, f->dims).total <= lds_max) {
+      f->ok = true;
+      f->ring_cap = cap;
+      return;
+    }
+}
+
+// The plain, 4-wide and time-aware variants for a sphere world of one BVH.  The record dims chosen here must match the
+// instantiation launch_lds picks for the scene (UNI: trace_lds.inc).
+static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan& leaves) {
+  const bool single_bvh = fs.top_level.size() == 1 && fs.entries[fs.top_level[0]].kind == rt::ENTRY_BVH;
+  if (!single_bvh || (fs.features & ~P_SPHERES) != 0 || fs.nodes32.size() > LDSK_MAX_NODES) return RTX_OK;
+  LdsPlan& p = ds->lds;
+  const TraceSwitches& sw = ds->sw;
+  const uint32_t max_end = leaves.max_end, levels = (uint32_t)fs.max_stack + 1u;
+  int lds_max = 0;
+  (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ds->device);
+  if (lds_max > 160 * 1024) lds_max = 160 * 1024;
+  // primitive records in LDS: one per leaf slot, in slot order (trace_lds.inc) -- spheres, or moving spheres when the scene has any
+  p.plain.levels = levels;
+  p.plain.dims = {(uint32_t)fs.nodes32.size(), max_end, max_end, 0u, LDSK_NODE_DWORDS, 0u};
+  if (!fs.moving_spheres.empty()) {
+    bool same = sw.mv_common;
+    for (const rt::FlatMovingSphere& ms : fs.moving_spheres)
+      same = same && ms.time0 == fs.moving_spheres[0].time0 && ms.time1 == fs.moving_spheres[0].time1;
+    if (same) { p.mv_common = true; p.mv_t0 = (double)fs.moving_spheres[0].time0; p.mv_t1 = (double)fs.moving_spheres[0].time1; }
+  }
+  if (fs.features & rt::F_MOVING_SPHERE) {  // k_trace_lds<P_SPHERES>: one kind of primitive in LDS (trace_lds.inc: UNI)
+    p.plain.dims.n_uni = (uint32_t)fs.spheres.size();
+    p.plain.dims.n_moving = max_end;
+    p.plain.dims.n_spheres = 0u;
+  }
+  p.motion.levels = levels;
+  p.motion.dims = p.plain.dims;
+  p.motion.dims.node_dwords = LDSK_MOTION_NODE_DWORDS;
+  {
+    // slopes along one axis only?  (a scene whose spheres all move the same way; the y-only instantiation exists: Book-1 at HEAD)
+    bool moves[3] = {false, false, false};
+    for (const rt::FlatMotion32& m : fs.motion32)
+      for (int ch = 0; ch < 2; ++ch)
+        for (int a = 0; a < 3; ++a) moves[a] = moves[a] || m.dlo[ch][a] != 0.0f || m.dhi[ch][a] != 0.0f;
+    if (!fs.motion32.empty() && moves[1] && !moves[0] && !moves[2] && sw.motion_axis) {
+      p.motion_axis = 1;
+      p.motion.dims.node_dwords = LDSK_MOTION1_NODE_DWORDS;
+    }
+  }
+  if (leaves.max_count <= 4 && max_end <= LDSK_MAX_SLOTS && sw.scene_lds != 0 && lds_max > 0) {
+    const bool want_ring = sw.ring != 0;
+    fit_lds(&p.plain, want_ring, (uint32_t)lds_max);
+    const rt::FlatEntry& be = fs.entries[fs.top_level[0]];
+    // the 4-wide collapse of the tree
+    // Measured on C2 and NOT the default: 236 wide nodes, 5.05 steps per ray against 10.6, bit-identical -- and 2.4 % slower
+    // (5997 against 6143 Msamples/s): sorting four children by entry distance and four conditional stack writes make a wide
+    // step ~2.3 x a binary one, whose near / far order comes for free out of the address.  Kept as the A/B partner (RTX_LDS_WIDE=1).
+    if (p.plain.ok && sw.lds_wide) {
+      std::vector<uint32_t> image;
+      uint32_t n_wide = 0;
+      const uint32_t wl = build_lds_wide_image(fs.nodes, be.a, &image, &n_wide);
+      if (wl > 0u) {
+        p.w4.levels = wl;
+        p.w4.dims = p.plain.dims;
+        p.w4.dims.n_nodes = n_wide;
+        p.w4.dims.node_dwords = LDSK_WIDE_NODE_DWORDS;
+        fit_lds(&p.w4, want_ring, (uint32_t)lds_max);
+        if (p.w4.ok) {
+          rtx_status st = upload_array(ds, image, &p.w4_image);
+          if (st != RTX_OK) return st;
+        }
+      }
+    }
+    // the time-aware instantiation: the world's one BVH holds moving spheres and came with an interval
+    if (p.plain.ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && (double)be.f[0] < (double)be.f[1] && sw.motion) {
+      p.motion_t0 = (double)be.f[0]; p.motion_t1 = (double)be.f[1];
+      fit_lds(&p.motion, want_ring, (uint32_t)lds_max);
+    }
+  }
+  if (p.plain.ok) {
+    // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
+    // scenes uploaded earlier (with other LDS sizes) keep launching
+    hipError_t ae = hipSuccess;
+#define LDS_ATTR(FEAT, RINGF, MOTIONF, W4F) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)k_trace_lds<FEAT, RINGF, MOTIONF, W4F>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
+    LDS_ATTR(P_SPHERES, true, 0u, false); LDS_ATTR(P_SPHERES, false, 0u, false); LDS_ATTR(P_STATIC_SPHERES, true, 0u, false); LDS_ATTR(P_STATIC_SPHERES, false, 0u, false);
+    LDS_ATTR(P_SPHERES, true, 1u, false); LDS_ATTR(P_SPHERES, false, 1u, false); LDS_ATTR(P_SPHERES, true, 3u, false); LDS_ATTR(P_SPHERES, false, 3u, false);
+    LDS_ATTR(P_SPHERES, true, 0u, true); LDS_ATTR(P_SPHERES, false, 0u, true); LDS_ATTR(P_STATIC_SPHERES, true, 0u, true); LDS_ATTR(P_STATIC_SPHERES, false, 0u, true);
+#undef LDS_ATTR
+    if (ae != hipSuccess) { (void)hipGetLastError(); p.plain.ok = false; }
+  }
+  if (sw.scene_lds >= 0) {
+    auto bytes = [](const LdsFit& f) { return f.ok ? ldsk_layout(f.levels, f.ring_cap, f.dims).total : 0u; };
+    fprintf(stderr, "[rtx] RTX_SCENE_LDS: 4-wide tree %s (%u nodes, %u levels, ring of %u, %u B)\n", p.w4.ok ? "on" : "off",
+            p.w4.dims.n_nodes, p.w4.levels, p.w4.ring_cap, bytes(p.w4));
+    fprintf(stderr, "[rtx] RTX_SCENE_LDS: k_trace_lds %s (ring of %u, %u B of LDS); time-aware boxes %s (ring of %u, %u B)\n",
+            p.plain.ok ? "on" : "off", p.plain.ring_cap, ldsk_layout(levels, p.plain.ring_cap, p.plain.dims).total,
+            p.motion.ok ? "on" : "off", p.motion.ring_cap, bytes(p.motion));
+  }
+  return RTX_OK;
+}
+
+static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera* cam) {
+  const LdsPlan& p = ds->lds;
+  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
+  // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
+  const bool motion = p.motion.ok && (double)cam->time1 >= p.motion_t0 && (double)cam->time2 <= p.motion_t1;
+  const bool w4 = !motion && p.w4.ok;
+  const LdsFit& f = motion ? p.motion : (w4 ? p.w4 : p.plain);
+  const bool ring = f.ring_cap != 0u;
+  const rt::real m_t0 = (rt::real)p.motion_t0, m_inv = (rt::real)(1.0 / (p.motion_t1 - p.motion_t0));
+  const LdsKernelLayout L = ldsk_layout(f.levels, f.ring_cap, f.dims);
+  const uint32_t grid = grid_size(a.total, LDSK_BLOCK, (uint64_t)ds->n_cu);
+  const WalkTuning& wk = ds->walk;
+#define LAUNCH_LDS2(FEAT, RINGF, MOTIONF, W4F)                                                                          \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, W4F>), dim3(grid), dim3(LDSK_BLOCK), L.total, a.stream, \
+                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, wk.leaf_weight,       \
+                     wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,    \
+                     m_t0, m_inv, p.w4_image, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1)
+#define LAUNCH_LDS(FEAT, MOTIONF, W4F) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF, W4F); } else { LAUNCH_LDS2(FEAT, false, MOTIONF, W4F); } } while (0)
+  // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
+  if ((a.feat & ~P_STATIC_SPHERES) == 0) { if (w4) { LAUNCH_LDS(P_STATIC_SPHERES, 0u, true); } else { LAUNCH_LDS(P_STATIC_SPHERES, 0u, false); } }
+  else if (motion && p.motion_axis == 1) { LAUNCH_LDS(P_SPHERES, 3u, false); }  // slopes along y only (Book-1 at HEAD)
+  else if (motion) { LAUNCH_LDS(P_SPHERES, 1u, false); }
+  else if (w4) { LAUNCH_LDS(P_SPHERES, 0u, true); }
+  else { LAUNCH_LDS(P_SPHERES, 0u, false); }
+#undef LAUNCH_LDS
+#undef LAUNCH_LDS2
+  return RTX_OK;
+}
+
+// ------------------------------------------------------------------ k_trace_persistent, k_trace_simple
+static void plan_persistent(DeviceScene* ds) {
+  const size_t lds = stack_bytes((uint32_t)ds->view.max_stack + 1u);
+  const int nb[3] = {occupancy(k_trace_persistent<P_SPHERES, false>, lds), occupancy(k_trace_persistent<P_MESH, false>, lds),
+                     occupancy(k_trace_persistent<P_ANY, false>, lds)};
+  for (int i = 0; i < 3; ++i)
+    if (nb[i] > 0) ds->pers_blocks_per_cu[i] = nb[i];
+}
+
+static rtx_status launch_persistent(DeviceScene* ds, const PassArgs& a) {
+  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
+  const bool wide = ds->wide.nodes4 && a.preset >= 1;
+  rt::SceneView v = ds->view;
+  v.pad = ds->walk.leaf_weight;
+  if (wide) v.nodes = (const rt::FlatNode*)ds->wide.nodes4;  // the wide tree rides in the slot of the (unused) f64 tree
+  const size_t lds = wide ? stack_bytes((uint32_t)ds->wide.levels) : a.stack_lds;
+  const int nb = wide ? ds->wide.pers_blocks_per_cu[a.preset] : ds->pers_blocks_per_cu[a.preset];
+  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)nb);
+  const rt::SceneView& dv = ds->view;
+#define LAUNCH_PERSISTENT(FEAT, WIDEF)                                                                                   \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_persistent<FEAT, WIDEF>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, v, a.rp, \
+                     a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, dv.entries, dv.top_level, dv.spheres,  \
+                     dv.moving_spheres, dv.rects, dv.triangles, dv.materials, dv.textures, dv.refs)
+  if (wide && a.preset == 1) { LAUNCH_PERSISTENT(P_MESH, true); }
+  else if (wide) { LAUNCH_PERSISTENT(P_ANY, true); }
+  else if (a.preset == 0) { LAUNCH_PERSISTENT(P_SPHERES, false); }
+  else if (a.preset == 1) { LAUNCH_PERSISTENT(P_MESH, false); }
+  else { LAUNCH_PERSISTENT(P_ANY, false); }
+#undef LAUNCH_PERSISTENT
+  return RTX_OK;
+}
+
+template <bool COUNT>
+static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
+  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
+#define LAUNCH_SIMPLE(FEAT)                                                                                             \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT>), dim3(grid), dim3(TRACE_BLOCK), a.stack_lds, a.stream, \
+                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, ds->ws.counters)
+  if constexpr (COUNT) { LAUNCH_SIMPLE(P_ALL); }
+  else {
+    if (a.preset == 0) { LAUNCH_SIMPLE(P_SPHERES); }
+    else if (a.preset == 1) { LAUNCH_SIMPLE(P_MESH); }
+    else { LAUNCH_SIMPLE(P_ALL); }
+  }
+#undef LAUNCH_SIMPLE
+}
+
+// ------------------------------------------------------------------ wavefront integrator
+// One pass (a.total (sample, pixel) items) through the wavefront integrator: iterations of generate -> trace -> shade over the P
+// path slots until every sample of the pass has been written.  It applies where k_trace_vote does (VotePlan::ok).
+static rtx_status wave_pass(DeviceScene* ds, const PassArgs& a) {
+  Workspace& ws = ds->ws;
+  const hipStream_t stream = a.stream;
+  uint32_t P = ds->sw.wf_paths;
+  if ((uint64_t)P > (uint64_t)a.total) P = a.total;
   P = (P + WF_SEG - 1u) & ~(WF_SEG - 1u);
   const uint32_t n_seg = P / WF_SEG;
   const size_t R = sizeof(rt::real);
   const size_t bytes = 64 + (size_t)P * (16 + 7 * R + 3 * R + 3 * R + R + 4 + 4 + 4 + 4) + (size_t)n_seg * 8;
-  if (bytes > ds->wave_bytes) {
-    if (ds->wave_mem) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(ds->wave_mem)); ds->wave_mem = nullptr; ds->wave_bytes = 0; }
-    HIP_TRY(hipMalloc(&ds->wave_mem, bytes));
-    ds->wave_bytes = bytes;
-  }
-  if (!ds->wave_host_ctrl) HIP_TRY(hipHostMalloc((void**)&ds->wave_host_ctrl, 4 * sizeof(uint32_t), hipHostMallocDefault));
+  rtx_status st = grow_buffer(&ws.wave_mem, &ws.wave_bytes, bytes, stream);
+  if (st != RTX_OK) return st;
+  if (!ws.wave_host_ctrl) HIP_TRY(hipHostMalloc((void**)&ws.wave_host_ctrl, 4 * sizeof(uint32_t), hipHostMallocDefault));
   WavePool pool;
   {
-    unsigned char* m = (unsigned char*)ds->wave_mem;
+    unsigned char* m = (unsigned char*)ws.wave_mem;
     pool.ctrl = (uint32_t*)m; m += 64;
     pool.rng = (unsigned long long*)m; m += (size_t)P * 16;
     pool.ray = (rt::real*)m; m += (size_t)P * 7 * R;
@@ -345,13 +896,14 @@ static rtx_status wave_pass(DeviceScene* ds, const rt::RenderParams& rp, const S
     pool.cursor = (uint32_t*)m; m += (size_t)n_seg * 4;
     pool.P = P;
   }
-  const bool wide = preset == 1 && ds->nodes4 != nullptr;
-  const uint32_t levels = (uint32_t)(wide ? ds->wide_levels : ds->view.max_stack + 1);
-  const size_t lds = (size_t)levels * TRACE_BLOCK * sizeof(int32_t);
+  const int preset = a.preset;
+  const bool wide = preset == 1 && ds->wide.nodes4 != nullptr;
+  const uint32_t levels = wide ? (uint32_t)ds->wide.levels : a.stack_levels;
+  const size_t lds = stack_bytes(levels);
   if (lds > 64 * 1024) { set_error("render: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
-  const bool room = (feat & ~P_MESH_ROOM) == 0;
-  const int occ = ds->wave_occ;
-  const uint32_t leaf_weight = ds->leaf_weight, refill = ds->wave_refill, bvh_pos = (uint32_t)ds->vote_bvh_pos;
+  const bool room = (a.feat & ~P_MESH_ROOM) == 0;
+  const int occ = ds->sw.wf_occ;
+  const uint32_t leaf_weight = ds->walk.leaf_weight, refill = ds->sw.wf_refill, bvh_pos = (uint32_t)ds->vote.bvh_pos;
   // every combination the launcher can ask for, once: (trace kernel, shade kernel) by preset / tree / occupancy target
 #define WF_CASES(X)                                                                                                          \
   if (preset == 0) { X(P_SPHERES, false, 4); }                                                                               \
@@ -366,39 +918,66 @@ static rtx_status wave_pass(DeviceScene* ds, const rt::RenderParams& rp, const S
   WF_CASES(WF_OCC)
 #undef WF_OCC
   if (oe != hipSuccess || nb <= 0) { (void)hipGetLastError(); nb = 1; }
-  ds->wave_blocks_per_cu = nb;
-  const uint64_t want = ((uint64_t)P + TRACE_BLOCK - 1) / TRACE_BLOCK;
-  const uint64_t resident = (uint64_t)ds->n_cu * (uint64_t)nb;
-  const uint32_t tgrid = (uint32_t)(want < resident ? want : resident);
+  const uint32_t tgrid = grid_size(P, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)nb);
   hipLaunchKernelGGL(k_wf_init, dim3((P + 255u) / 256u), dim3(256), 0, stream, pool);
-  uint32_t check_every = ds->wave_check;
+  uint32_t check_every = ds->sw.wf_check;
   int it = 0;
   for (;; ++it) {
-    hipLaunchKernelGGL(k_wf_generate, dim3(n_seg), dim3(WF_SEG), 0, stream, pool, rp, sm, s_begin, total, npix);
+    hipLaunchKernelGGL(k_wf_generate, dim3(n_seg), dim3(WF_SEG), 0, stream, pool, a.rp, a.sm, a.s_begin, a.total, a.npix);
     if ((uint32_t)(it + 1) % check_every == 0u) {
       HIP_TRY(hipMemsetAsync(pool.ctrl, 0, 16, stream));
       hipLaunchKernelGGL(k_wf_count, dim3(256), dim3(256), 0, stream, pool);
       HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemcpyAsync(ds->wave_host_ctrl, pool.ctrl, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipMemcpyAsync(ws.wave_host_ctrl, pool.ctrl, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));
       // no path alive after a generation: every segment's share of the pass is used up and every path has ended
-      if (ds->wave_host_ctrl[0] == 0u) break;
-      if (ds->wave_host_ctrl[0] < P / 2u) check_every = 2;  // the tail: the pool drains within max_depth iterations
+      if (ws.wave_host_ctrl[0] == 0u) break;
+      if (ws.wave_host_ctrl[0] < P / 2u) check_every = 2;  // the tail: the pool drains within max_depth iterations
       if (it > 100000000) { set_error("render: wavefront integrator did not converge"); return RTX_EHIP; }
     }
 #define WF_LAUNCH(FEAT, WIDEF, MB)                                                                                           \
   do {                                                                                                                       \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_trace<FEAT, WIDEF, MB>), dim3(tgrid), dim3(TRACE_BLOCK), lds, stream, ds->view, pool, \
-                       leaf_weight, refill, bvh_pos, ds->nodes4, ds->vote_tri_base);                                          \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_shade<FEAT>), dim3(n_seg), dim3(WF_SEG), 0, stream, ds->view, pool, rp, ds->samples, bvh_pos); \
+                       leaf_weight, refill, bvh_pos, ds->wide.nodes4, ds->vote.tri_base);                                    \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_shade<FEAT>), dim3(n_seg), dim3(WF_SEG), 0, stream, ds->view, pool, a.rp, a.samples, bvh_pos); \
   } while (0)
     WF_CASES(WF_LAUNCH)
 #undef WF_LAUNCH
   }
 #undef WF_CASES
-  ds->wave_iterations = it + 1;
-  if (ds->wave_verbose) fprintf(stderr, "[rtx] wavefront: %u slots, %d iterations, %d blocks per CU (%u stack levels)\n", P, it + 1, nb, levels);
+  if (ds->sw.wf_verbose) fprintf(stderr, "[rtx] wavefront: %u slots, %d iterations, %d blocks per CU (%u stack levels)\n", P, it + 1, nb, levels);
   return RTX_OK;
+}
+
+// ------------------------------------------------------------------ walk tuning
+// Needs WidePlan and LdsPlan.  A leaf step costs about (primitives per leaf) x 1.3 node steps for spheres: vote weight 1 for
+// single-primitive leaves, 3 otherwise (measured on C2 / HEAD / C4).
+static void plan_walk(DeviceScene* ds, const LeafScan& leaves) {
+  WalkTuning& w = ds->walk;
+  const TraceSwitches& sw = ds->sw;
+  w.leaf_weight = leaves.max_count <= 1 ? 1u : 3u;
+  w.single_leaf = leaves.max_count <= 1;
+  // latency-bound wide walks: measured best on the dragon room (639 vs 575 Msamples/s)
+  if (ds->wide.nodes4) { w.leaf_weight = 1u; w.walk_threshold = 24u; w.regen_min = 8u; }  // regeneration waits for 8 lanes: 803 -> 824 on C4 (4: 817, 16: 801)
+  // k_trace_lds since the ground is asked first and the node step got shorter (round 3): C2 10 / 12 / 14 / 16 / 18 -> 6153 / 6188 /
+  // 6185 / 6170 / 6140, HEAD Book-1 3859 / 3850 / 3830 / 3808 / 3750 Msamples/s
+  else if (ds->lds.plain.ok) w.walk_threshold = 12u;
+  if (sw.regen_min) w.regen_min = sw.regen_min;
+  if (sw.leaf_weight) w.leaf_weight = sw.leaf_weight;
+  if (!sw.single_leaf) w.single_leaf = false;
+  if (sw.walk_threshold) w.walk_threshold = sw.walk_threshold;
+}
+
+// ------------------------------------------------------------------ render
+// The trace kernel of every pass of a render (RtxRenderStats.trace_kernel), in this order of precedence:
+static int32_t choose_trace_kernel(const DeviceScene* ds, int preset, bool count) {
+  const ForcedKernel k = ds->sw.kernel;
+  if (count || k == ForcedKernel::simple) return RTX_KERNEL_SIMPLE;  // the counting kernel
+  if (ds->lds.plain.ok && preset == 0 && k == ForcedKernel::none) return RTX_KERNEL_LDS;
+  if (ds->vote.ok && preset < 2 && k == ForcedKernel::wavefront) return RTX_KERNEL_WAVEFRONT;
+  if (ds->vote.ok && preset < 2 && k != ForcedKernel::persistent && k != ForcedKernel::world) return RTX_KERNEL_VOTE;
+  if (k != ForcedKernel::persistent || (ds->view.features & rt::F_GRAVITY_SPHERE)) return RTX_KERNEL_WORLD;
+  return RTX_KERNEL_PERSISTENT;
 }
 
 // The slice of a frame's samples one call traces (progressive rendering, progressive.inc): the absolute sample indices
@@ -409,6 +988,84 @@ struct SampleRange {
   int cont;
   double* sumsq;
 };
+
+// How one render is cut into passes: samples of every pixel per pass, passes two deep or not, bytes of the sample buffer.
+struct PassPlan {
+  uint32_t spp_pass;
+  bool pipeline;
+  size_t sample_bytes;
+};
+
+// Sizes the passes of a render of spp samples of npix pixels and grows the workspace for them (accum: the caller's accumulator,
+// or NULL for the scene's own).  serial: the counting / timing entry points, which synchronise per pass.
+static rtx_status prepare_workspace(DeviceScene* ds, const RtxConfig* cfg, uint64_t npix, uint64_t npix_all, uint32_t spp, bool serial,
+                                    hipStream_t stream, double** accum, PassPlan* pp) {
+  Workspace& ws = ds->ws;
+  // Default budget: 24 GiB (of 288 GB: C5 takes 16 passes instead of 67, C3 10 instead of 40), but never more than a third of the
+  // HBM that is free right now plus what this handle already holds -- other scene handles, a second frame in flight, torch's caching
+  // allocator or a smaller part shrink it, and a frame then takes more passes instead of failing.  An explicit
+  // cfg->sample_buffer_bytes is taken as given.
+  uint64_t budget = cfg->sample_buffer_bytes;
+  if (budget == 0) {
+    budget = 24ull << 30;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+      const uint64_t avail = ((uint64_t)free_b + ws.samples_bytes) / 3;
+      if (avail < budget) budget = avail;
+    } else {
+      (void)hipGetLastError();
+    }
+    if (budget < ws.samples_bytes) budget = ws.samples_bytes;  // what is already there can be used
+  }
+  const uint64_t per_sample_plane = npix * 24ull;
+  uint32_t spp_pass = spp;
+  // Two passes in flight (render_impl) when the render needs several passes anyway (C5: 16, C3: 10): each pass then gets half of
+  // the buffer.  A render that fits one pass stays one launch -- cut in two it gains the overlapped half of its reduction and loses
+  // as much to the second launch (C2: 6550 against 6574 Msamples/s; with two FRAMES in flight on top, 6644 against 6722), whereas
+  // C5 gains 1.7 %.
+  const bool pipeline = ds->sw.pass_pipeline && !serial && ds->sw.kernel != ForcedKernel::simple && per_sample_plane > 0 &&
+                        (uint64_t)spp * per_sample_plane > budget && budget / 2 >= per_sample_plane;
+  const uint64_t pass_budget = pipeline ? budget / 2 : budget;
+  if (per_sample_plane > 0 && (uint64_t)spp_pass * per_sample_plane > pass_budget) {
+    spp_pass = (uint32_t)(pass_budget / per_sample_plane);
+    if (spp_pass < 1) spp_pass = 1;
+  }
+  // a pass's (sample, pixel) index space is addressed with 32-bit indices
+  while (spp_pass > 1 && (uint64_t)spp_pass * npix >= 0xFFFF0000ull) --spp_pass;
+  if ((uint64_t)spp_pass * npix >= 0xFFFF0000ull) { set_error("render: shard too large for one pass"); return RTX_EINVAL; }
+  size_t need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
+  if (need_samples > ws.samples_bytes) {
+    if (ws.samples) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(ws.samples)); ws.samples = nullptr; ws.samples_bytes = 0; }
+    // out of memory: halve the pass until the buffer fits (down to one sample per pass) before giving up
+    for (;;) {
+      hipError_t me = hipMalloc((void**)&ws.samples, need_samples);
+      if (me == hipSuccess) break;
+      (void)hipGetLastError();
+      ws.samples = nullptr;
+      if (me != hipErrorOutOfMemory || spp_pass <= 1) {
+        set_error(std::string("render: sample buffer of ") + std::to_string(need_samples) + " bytes: " + hipGetErrorString(me));
+        return me == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
+      }
+      spp_pass = (spp_pass + 1) / 2;
+      need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
+    }
+    ws.samples_bytes = need_samples;
+  }
+  if (!*accum) {
+    const rtx_status st = grow_buffer((void**)&ws.accum, &ws.accum_bytes, (size_t)npix_all * 24, stream);
+    if (st != RTX_OK) return st;
+    *accum = ws.accum;
+  }
+  if (!ws.counters) HIP_TRY(hipMalloc((void**)&ws.counters, sizeof(rt::TraceCounters)));
+  if (!ws.work_counter) HIP_TRY(hipMalloc((void**)&ws.work_counter, 2 * sizeof(unsigned int)));
+  if (pipeline && !ws.aux_stream) {
+    HIP_TRY(hipStreamCreateWithFlags(&ws.aux_stream, hipStreamNonBlocking));
+    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventCreateWithFlags(&ws.ev_pass[i], hipEventDisableTiming));
+  }
+  if (!ws.ev[0]) { HIP_TRY(hipEventCreate(&ws.ev[0])); HIP_TRY(hipEventCreate(&ws.ev[1])); }
+  *pp = {spp_pass, pipeline, need_samples};
+  return RTX_OK;
+}
 
 template <bool COUNT>
 static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxConfig* cfg,
@@ -438,77 +1095,14 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   if (stats) memset(stats, 0, sizeof(*stats));
   if (npix_all == 0) return RTX_OK;
 
-  // ---- workspace
-  // Default budget: 24 GiB (of 288 GB: C5 takes 16 passes instead of 67, C3 10 instead of 40), but never more than a third of the
-  // HBM that is free right now plus what this handle already holds -- other scene handles, a second frame in flight, torch's caching
-  // allocator or a smaller part shrink it, and a frame then takes more passes instead of failing.  An explicit
-  // cfg->sample_buffer_bytes is taken as given.
-  uint64_t budget = cfg->sample_buffer_bytes;
-  if (budget == 0) {
-    budget = 24ull << 30;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const uint64_t avail = ((uint64_t)free_b + ds->samples_bytes) / 3;
-      if (avail < budget) budget = avail;
-    } else {
-      (void)hipGetLastError();
-    }
-    if (budget < ds->samples_bytes) budget = ds->samples_bytes;  // what is already there can be used
-  }
-  uint64_t per_sample_plane = npix * 24ull;
   const uint32_t s_first = range ? range->first : 0u;
-  uint32_t spp = range ? range->count : (uint32_t)cfg->samples_per_pixel;  // samples of every pixel this call traces
-  uint32_t spp_pass = spp;
-  // Two passes in flight (below) when the render needs several passes anyway (C5: 16, C3: 10): each pass then gets half of the
-  // buffer.  A render that fits one pass stays one launch -- cut in two it gains the overlapped half of its reduction and loses as
-  // much to the second launch (C2: 6550 against 6574 Msamples/s; with two FRAMES in flight on top, 6644 against 6722), whereas
-  // C5 gains 1.7 %.  Not for the counting / timing entry points (stats != NULL synchronises per pass).
-  const bool pipeline = ds->pass_pipeline && !COUNT && stats == nullptr && !ds->force_simple && per_sample_plane > 0 &&
-                        (uint64_t)spp * per_sample_plane > budget && budget / 2 >= per_sample_plane;
-  const uint64_t pass_budget = pipeline ? budget / 2 : budget;
-  if (per_sample_plane > 0 && (uint64_t)spp_pass * per_sample_plane > pass_budget) {
-    spp_pass = (uint32_t)(pass_budget / per_sample_plane);
-    if (spp_pass < 1) spp_pass = 1;
-  }
-  // a pass's (sample, pixel) index space is addressed with 32-bit indices
-  while (spp_pass > 1 && (uint64_t)spp_pass * npix >= 0xFFFF0000ull) --spp_pass;
-  if ((uint64_t)spp_pass * npix >= 0xFFFF0000ull) { set_error("render: shard too large for one pass"); return RTX_EINVAL; }
-  size_t need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
-  if (need_samples > ds->samples_bytes) {
-    if (ds->samples) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(ds->samples)); ds->samples = nullptr; ds->samples_bytes = 0; }
-    // out of memory: halve the pass until the buffer fits (down to one sample per pass) before giving up
-    for (;;) {
-      hipError_t me = hipMalloc((void**)&ds->samples, need_samples);
-      if (me == hipSuccess) break;
-      (void)hipGetLastError();
-      ds->samples = nullptr;
-      if (me != hipErrorOutOfMemory || spp_pass <= 1) {
-        set_error(std::string("render: sample buffer of ") + std::to_string(need_samples) + " bytes: " + hipGetErrorString(me));
-        return me == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
-      }
-      spp_pass = (spp_pass + 1) / 2;
-      need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
-    }
-    ds->samples_bytes = need_samples;
-  }
+  const uint32_t spp = range ? range->count : (uint32_t)cfg->samples_per_pixel;  // samples of every pixel this call traces
   double* accum = d_accum_out;
-  if (!accum) {
-    size_t need = (size_t)npix_all * 24;
-    if (need > ds->accum_bytes) {
-      if (ds->accum) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(ds->accum)); ds->accum = nullptr; ds->accum_bytes = 0; }
-      HIP_TRY(hipMalloc((void**)&ds->accum, need));
-      ds->accum_bytes = need;
-    }
-    accum = ds->accum;
-  }
-  if (!ds->counters) HIP_TRY(hipMalloc((void**)&ds->counters, sizeof(rt::TraceCounters)));
-  if (!ds->work_counter) HIP_TRY(hipMalloc((void**)&ds->work_counter, 2 * sizeof(unsigned int)));
-  if (pipeline && !ds->aux_stream) {
-    HIP_TRY(hipStreamCreateWithFlags(&ds->aux_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventCreateWithFlags(&ds->ev_pass[i], hipEventDisableTiming));
-  }
-  if (!ds->ev[0]) { HIP_TRY(hipEventCreate(&ds->ev[0])); HIP_TRY(hipEventCreate(&ds->ev[1])); }
-  if (COUNT) HIP_TRY(hipMemsetAsync(ds->counters, 0, sizeof(rt::TraceCounters), stream));
+  PassPlan pp;
+  st = prepare_workspace(ds, cfg, npix, npix_all, spp, COUNT || stats != nullptr, stream, &accum, &pp);
+  if (st != RTX_OK) return st;
+  Workspace& ws = ds->ws;
+  if (COUNT) HIP_TRY(hipMemsetAsync(ws.counters, 0, sizeof(rt::TraceCounters), stream));
 
   // rows skipped by row_chunk_compat stay (0,0,0) as in the reference's Screen::new
   if (npix < npix_all) {
@@ -517,302 +1111,64 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
     if (range && range->sumsq) HIP_TRY(hipMemsetAsync(range->sumsq + 3 * npix, 0, (size_t)(npix_all - npix) * 24, stream));
   }
 
-  ShardMap sm = {w, sh.block_rows, sh.shard_index, sh.shard_count};
-  int stack_levels = ds->view.max_stack + 1;
-  size_t lds_bytes = (size_t)stack_levels * TRACE_BLOCK * sizeof(int32_t);
-  if (lds_bytes > 64 * 1024) { set_error("render: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
+  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
+  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("render: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
   const uint32_t feat = ds->view.features;
   const int preset = ((feat & ~P_SPHERES) == 0) ? 0 : (((feat & ~P_MESH) == 0) ? 1 : 2);
-  const bool use_simple = COUNT || ds->force_simple;
+  const int32_t kernel = choose_trace_kernel(ds, preset, COUNT);
+  PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)npix, nullptr, nullptr, stream,
+                preset, feat, stack_levels, stack_bytes(stack_levels)};
 
   float trace_ms = 0.f;
   int passes = 0;
-  int32_t kernel_used = RTX_KERNEL_SIMPLE;
   if (npix > 0) {
-    // Passes two deep: even passes on the caller's stream, odd ones on ds->aux_stream, each with its own half of the sample
+    // Passes two deep: even passes on the caller's stream, odd ones on ws.aux_stream, each with its own half of the sample
     // buffer and its own work counter.  Within a stream: trace(k), reduce(k), trace(k + 2), ... -- so a half is not overwritten
     // before it has been summed; across streams reduce(k) waits for reduce(k - 1) -- so every pixel's samples are still added in
     // ascending order, bit for bit what one stream does.  What overlaps: the last waves of trace(k) (a few long paths in
     // otherwise idle CUs), reduce(k) and the first waves of trace(k + 1).
-    double* const samples_base = ds->samples;
-    unsigned int* const counter_base = ds->work_counter;
-    struct RestoreScene {
-      DeviceScene* d; double* s; unsigned int* w;
-      ~RestoreScene() { d->samples = s; d->work_counter = w; }
-    } restore_scene{ds, samples_base, counter_base};
-    hipStream_t const caller_stream = stream;
-    if (pipeline) {
-      HIP_TRY(hipEventRecord(ds->ev_pass[2], caller_stream));
-      HIP_TRY(hipStreamWaitEvent(ds->aux_stream, ds->ev_pass[2], 0));
+    if (pp.pipeline) {
+      HIP_TRY(hipEventRecord(ws.ev_pass[2], stream));
+      HIP_TRY(hipStreamWaitEvent(ws.aux_stream, ws.ev_pass[2], 0));
     }
-    for (uint32_t s_off = 0; s_off < spp; s_off += spp_pass, ++passes) {
-      const uint32_t s_begin = s_first + s_off;  // absolute index of the pass's first sample: the key of its random streams
-      const int half = pipeline ? (passes & 1) : 0;
-      hipStream_t stream = half ? ds->aux_stream : caller_stream;  // (shadows the parameter: every launch below goes to this pass's stream)
-      ds->samples = samples_base + (size_t)half * (size_t)spp_pass * (size_t)npix * 3u;
-      ds->work_counter = counter_base + half;
-      uint32_t s_count = spp - s_off < spp_pass ? spp - s_off : spp_pass;
-      uint32_t total = (uint32_t)((uint64_t)s_count * npix);
-      if (stats) HIP_TRY(hipEventRecord(ds->ev[0], stream));
-      if (use_simple) {
-        kernel_used = RTX_KERNEL_SIMPLE;
-        uint64_t want = ((uint64_t)total + TRACE_BLOCK - 1) / TRACE_BLOCK;
-        uint32_t grid = (uint32_t)(want < (uint64_t)ds->n_cu * 8 ? want : (uint64_t)ds->n_cu * 8);
-#define LAUNCH_SIMPLE(FEAT)                                                                          \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT>), dim3(grid), dim3(TRACE_BLOCK),     \
-                     lds_bytes, stream, ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, \
-                     ds->counters)
-        if constexpr (COUNT) { LAUNCH_SIMPLE(P_ALL); }
-        else {
-          if (preset == 0) { LAUNCH_SIMPLE(P_SPHERES); }
-          else if (preset == 1) { LAUNCH_SIMPLE(P_MESH); }
-          else { LAUNCH_SIMPLE(P_ALL); }
-        }
-#undef LAUNCH_SIMPLE
-      } else if (ds->lds_ok && preset == 0 && !ds->force_wq && !ds->force_vote && !ds->force_persistent && !ds->force_stream && !ds->force_world && !ds->force_wave) {
-        kernel_used = RTX_KERNEL_LDS;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
-        const bool motion = ds->motion_ok && (double)cam->time1 >= ds->motion_t0 && (double)cam->time2 <= ds->motion_t1;
-        const bool w4 = !motion && ds->w4_ok;
-        const bool ring = motion ? ds->motion_ring : (w4 ? ds->w4_ring : ds->lds_ring);
-        const uint32_t ring_cap = motion ? ds->motion_ring_cap : (w4 ? ds->w4_ring_cap : ds->lds_ring_cap);
-        const LdsSceneDims dims = motion ? ds->motion_dims : (w4 ? ds->w4_dims : ds->lds_dims);
-        const uint32_t lds_levels = w4 ? ds->w4_levels : (uint32_t)stack_levels;
-        const rt::real m_t0 = (rt::real)ds->motion_t0, m_inv = (rt::real)(1.0 / (ds->motion_t1 - ds->motion_t0));
-        const LdsKernelLayout L = ldsk_layout(lds_levels, ring ? ring_cap : 0u, dims);
-        uint64_t want = ((uint64_t)total + LDSK_BLOCK - 1) / LDSK_BLOCK;
-        uint32_t grid = (uint32_t)(want < (uint64_t)ds->n_cu ? want : (uint64_t)ds->n_cu);
-#define LAUNCH_LDS2(FEAT, RINGF, MOTIONF, W4F)                                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, W4F>), dim3(grid), dim3(LDSK_BLOCK), L.total, stream, \
-                     ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter,      \
-                     ds->leaf_weight, ds->walk_threshold | (ds->single_leaf ? 0x100u : 0u), ds->lds_chunk, ring_cap, lds_levels, dims, m_t0, m_inv, ds->w4_image, \
-                     ds->mv_common ? 1u : 0u, (rt::real)ds->mv_t0, (rt::real)ds->mv_t1)
-#define LAUNCH_LDS(FEAT, MOTIONF, W4F) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF, W4F); } else { LAUNCH_LDS2(FEAT, false, MOTIONF, W4F); } } while (0)
-        // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
-        if ((feat & ~P_STATIC_SPHERES) == 0) { if (w4) { LAUNCH_LDS(P_STATIC_SPHERES, 0u, true); } else { LAUNCH_LDS(P_STATIC_SPHERES, 0u, false); } }
-        else if (motion && ds->motion_axis == 1) { LAUNCH_LDS(P_SPHERES, 3u, false); }  // slopes along y only (Book-1 at HEAD)
-        else if (motion) { LAUNCH_LDS(P_SPHERES, 1u, false); }
-        else if (w4) { LAUNCH_LDS(P_SPHERES, 0u, true); }
-        else { LAUNCH_LDS(P_SPHERES, 0u, false); }
-#undef LAUNCH_LDS
-#undef LAUNCH_LDS2
-#ifdef RTX_EXPERIMENTAL_KERNELS
-      } else if (ds->force_wq && ds->wq_ok && preset == 0) {
-        kernel_used = RTX_KERNEL_WQ;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        if (!ds->error_word) HIP_TRY(hipMalloc((void**)&ds->error_word, sizeof(unsigned int)));
-        HIP_TRY(hipMemsetAsync(ds->error_word, 0, sizeof(unsigned int), stream));
-        const WqLayout L = wq_layout(ds->wq_paths, ds->wq_levels);
-        uint64_t want = ((uint64_t)total + ds->wq_paths - 1) / ds->wq_paths;
-        uint32_t grid = (uint32_t)(want < (uint64_t)ds->n_cu ? want : (uint64_t)ds->n_cu);
-        if (ds->wq_diag) {
-          if (!ds->diag) HIP_TRY(hipMalloc((void**)&ds->diag, 24 * sizeof(unsigned long long)));
-          HIP_TRY(hipMemsetAsync(ds->diag, 0, 24 * sizeof(unsigned long long), stream));
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_wq<P_SPHERES, true>), dim3(grid), dim3(WQ_THREADS), L.total, stream,
-                             ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter,
-                             ds->error_word, ds->wq_paths, ds->wq_levels, ds->wq_walkers, ds->wq_batch_min, ds->diag);
-          HIP_TRY(hipStreamSynchronize(stream));
-          unsigned long long h[24];
-          HIP_TRY(hipMemcpy(h, ds->diag, sizeof(h), hipMemcpyDeviceToHost));
-          const char* tnames[6] = {"gen", "walk(total)", "walk:refill", "shade", "idle", "kernel"};
-          for (int k = 0; k < 6; ++k)
-            fprintf(stderr, "[wq_diag] wave-time %-12s %6.2f %%\n", tnames[k], h[16 + 5] ? 100.0 * (double)h[16 + k] / (double)h[16 + 5] : 0.0);
-          const char* names[8] = {"node_step", "leaf_step", "refill", "shade", "gen", "idle_poll", "walk_loop", "short_refill"};
-          for (int k = 0; k < 8; ++k)
-            fprintf(stderr, "[wq_diag] %-12s executions %llu lanes %llu mean %.2f\n", names[k], h[2 * k], h[2 * k + 1],
-                    h[2 * k] ? (double)h[2 * k + 1] / (double)h[2 * k] : 0.0);
-        } else {
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_wq<P_SPHERES, false>), dim3(grid), dim3(WQ_THREADS), L.total, stream,
-                             ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter,
-                             ds->error_word, ds->wq_paths, ds->wq_levels, ds->wq_walkers, ds->wq_batch_min, (unsigned long long*)nullptr);
-        }
-        HIP_TRY(hipGetLastError());
-        unsigned int err = 0;
-        HIP_TRY(hipMemcpyAsync(&err, ds->error_word, sizeof(err), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (err != 0) { set_error("render: k_trace_wq aborted (bounded wait tripped, code " + std::to_string(err) + ")"); return RTX_EHIP; }
-#endif
-      } else if (ds->wave_ok && preset < 2 && (ds->force_wave || (ds->wave_default && !ds->force_vote && !ds->force_persistent && !ds->force_world && !ds->force_stream))) {
-        kernel_used = RTX_KERNEL_WAVEFRONT;
-        st = wave_pass(ds, rp, sm, s_begin, total, (uint32_t)npix, stream, preset, feat);
-        if (st != RTX_OK) return st;
-      } else if (ds->vote_ok && preset < 2 && !ds->force_persistent && !ds->force_world && !(ds->force_stream && ds->single_bvh)) {
-        kernel_used = RTX_KERNEL_VOTE;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        uint64_t want = ((uint64_t)total + TRACE_BLOCK - 1) / TRACE_BLOCK;
-        uint64_t resident = (uint64_t)ds->n_cu * (uint64_t)ds->vote_blocks_per_cu[preset];
-        uint32_t grid = 0;
-        const bool ring = ds->vote_ring[preset];
-        const size_t vote_lds = lds_bytes + (ring ? (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE : 0);
-        grid = (uint32_t)(want < resident ? want : resident);
-#define LAUNCH_VOTE(FEAT, DIAGF, RINGF, DIAGP)                                                        \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false>), dim3(grid), dim3(TRACE_BLOCK), vote_lds, \
-                     stream, ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples,            \
-                     ds->work_counter, DIAGP, ds->leaf_weight, ds->walk_threshold, (uint32_t)stack_levels, (uint32_t)ds->vote_bvh_pos, \
-                     (const FlatNode4*)nullptr, ds->vote_tri_base, 0u, ds->vote_top)
-        if (ds->vote_diag && preset == 0) {
-          if (!ds->diag) HIP_TRY(hipMalloc((void**)&ds->diag, 24 * sizeof(unsigned long long)));
-          HIP_TRY(hipMemsetAsync(ds->diag, 0, 12 * sizeof(unsigned long long), stream));
-          if (ring) { LAUNCH_VOTE(P_SPHERES, true, true, ds->diag); } else { LAUNCH_VOTE(P_SPHERES, true, false, ds->diag); }
-          HIP_TRY(hipStreamSynchronize(stream));
-          unsigned long long h[12];
-          HIP_TRY(hipMemcpy(h, ds->diag, sizeof(h), hipMemcpyDeviceToHost));
-          const char* names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "walking"};
-          for (int k = 0; k < 6; ++k)
-            fprintf(stderr, "[vote_diag] %-10s executions %llu lanes %llu mean lanes %.2f\n", names[k], h[2 * k], h[2 * k + 1],
-                    h[2 * k] ? (double)h[2 * k + 1] / (double)h[2 * k] : 0.0);
-        }
-        else if (preset == 0) { if (ring) { LAUNCH_VOTE(P_SPHERES, false, true, (unsigned long long*)nullptr); } else { LAUNCH_VOTE(P_SPHERES, false, false, (unsigned long long*)nullptr); } }
-        else if (ds->nodes4) {
-          // material / texture records behind the stacks when that costs no resident block
-          uint32_t lds_tables = 0;
-          size_t wide_lds = (size_t)ds->wide_levels * TRACE_BLOCK * sizeof(int32_t);
-          if (ds->vote_tables_bytes > 0 && (wide_lds + ds->vote_tables_bytes) * (size_t)ds->wide_blocks_per_cu <= 160 * 1024) {
-            lds_tables = ds->vote_tables;
-            wide_lds += ds->vote_tables_bytes;
-          }
-          uint64_t res4 = (uint64_t)ds->n_cu * (uint64_t)ds->wide_blocks_per_cu;
-          grid = (uint32_t)(want < res4 ? want : res4);
-#define LAUNCH_VOTE_WIDE(FEAT)                                                                         \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, false, false, true>), dim3(grid), dim3(TRACE_BLOCK), wide_lds, \
-                     stream, ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter,  \
-                     (unsigned long long*)nullptr, ds->leaf_weight, ds->walk_threshold | (ds->regen_min << 16), (uint32_t)ds->wide_levels, \
-                     (uint32_t)ds->vote_bvh_pos, ds->nodes4, ds->vote_tri_base, lds_tables, ds->vote_top)
-          // a triangle mesh in a room of rectangles, no spheres / lists / glass (the dragon room): the leaner instantiation
-          if (ds->vote_diag && (feat & ~P_MESH_ROOM) == 0) {
-            if (!ds->diag) HIP_TRY(hipMalloc((void**)&ds->diag, 24 * sizeof(unsigned long long)));
-            HIP_TRY(hipMemsetAsync(ds->diag, 0, 24 * sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<P_MESH_ROOM, true, false, true>), dim3(grid), dim3(TRACE_BLOCK), wide_lds,
-                               stream, ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter,
-                               ds->diag, ds->leaf_weight, ds->walk_threshold, (uint32_t)ds->wide_levels,
-                               (uint32_t)ds->vote_bvh_pos, ds->nodes4, ds->vote_tri_base, lds_tables, ds->vote_top);
-            HIP_TRY(hipStreamSynchronize(stream));
-            unsigned long long h[24];
-            HIP_TRY(hipMemcpy(h, ds->diag, sizeof(h), hipMemcpyDeviceToHost));
-            const char* names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "shade_all"};
-            for (int k = 0; k < 6; ++k)
-              fprintf(stderr, "[vote_diag] %-10s executions %llu lanes %llu mean lanes %.2f\n", names[k], h[2 * k], h[2 * k + 1],
-                      h[2 * k] ? (double)h[2 * k + 1] / (double)h[2 * k] : 0.0);
-            if (h[12]) {
-              float v[12];
-              for (int k = 0; k < 6; ++k) { uint32_t lo = (uint32_t)h[13 + k], hi = (uint32_t)(h[13 + k] >> 32); memcpy(&v[2 * k], &lo, 4); memcpy(&v[2 * k + 1], &hi, 4); }
-              fprintf(stderr, "[vote_diag] %llu walks of >= 50000 node steps; the first: origin (%g %g %g) direction (%g %g %g) 1/d (%g %g %g) err2 %g t_min %g t_max %g depth left %llu\n",
-                      h[12], v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], h[19]);
-            }
-          }
-          else if ((feat & ~P_MESH_ROOM) == 0) { LAUNCH_VOTE_WIDE(P_MESH_ROOM); } else { LAUNCH_VOTE_WIDE(P_MESH); }
-#undef LAUNCH_VOTE_WIDE
-        }
-        else { if (ring) { LAUNCH_VOTE(P_MESH, false, true, (unsigned long long*)nullptr); } else { LAUNCH_VOTE(P_MESH, false, false, (unsigned long long*)nullptr); } }
-#undef LAUNCH_VOTE
-#ifdef RTX_EXPERIMENTAL_KERNELS
-      } else if (ds->single_bvh && preset < 2 && ds->force_stream) {
-        kernel_used = RTX_KERNEL_STREAM;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        uint64_t want = ((uint64_t)total + TRACE_BLOCK - 1) / TRACE_BLOCK;
-        uint64_t resident = (uint64_t)ds->n_cu * (uint64_t)ds->stream_blocks_per_cu[preset];
-        uint32_t grid = (uint32_t)(want < resident ? want : resident);
-#define LAUNCH_STREAM(FEAT)                                                                           \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_stream<FEAT>), dim3(grid), dim3(TRACE_BLOCK), lds_bytes,  \
-                     stream, ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples,            \
-                     ds->work_counter, ds->walk_threshold)
-        if (preset == 0) { LAUNCH_STREAM(P_SPHERES); }
-        else { LAUNCH_STREAM(P_MESH); }
-#undef LAUNCH_STREAM
-#endif
-      } else if (!ds->force_persistent || (feat & rt::F_GRAVITY_SPHERE)) {
-        kernel_used = RTX_KERNEL_WORLD;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        const bool wide = ds->nodes4 != nullptr;
-        const bool book2 = (feat & ~P_BOOK2) == 0;
-        const bool has_gravity = (feat & rt::F_GRAVITY_SPHERE) != 0;
-        const bool no_sphere_media = (feat & rt::F_MEDIUM_SPHERE) == 0;
-        const uint32_t levels = (uint32_t)(wide ? ds->wide_levels : stack_levels);
-        const size_t world_lds = (size_t)levels * TRACE_BLOCK * sizeof(int32_t) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real) +
-                                 (size_t)ds->world_perlin_lds * sizeof(rt::FlatPerlin) +
-                                 (size_t)ds->world_mat_lds * sizeof(rt::FlatMaterial) + (size_t)ds->world_tex_lds * sizeof(rt::FlatTexture);
-        uint64_t want = ((uint64_t)total + TRACE_BLOCK - 1) / TRACE_BLOCK;
-        uint64_t resident = (uint64_t)ds->n_cu * (uint64_t)ds->world_blocks_per_cu[has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1))][wide ? 1 : 0];
-        uint32_t grid = (uint32_t)(want < resident ? want : resident);
-#define LAUNCH_WORLD(FEAT, WIDEF, WPS)                                                                   \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<FEAT, WIDEF, WPS>), dim3(grid), dim3(TRACE_BLOCK), world_lds, stream, \
-                     ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter, ds->view.entries, \
-                     ds->view.top_level, ds->view.spheres, ds->view.moving_spheres, ds->view.rects, ds->view.triangles, \
-                     ds->view.materials, ds->view.textures, ds->view.refs, ds->nodes4, ds->world_desc, ds->leaf_weight, ds->world_threshold, levels, ds->world_perlin_lds, ds->world_mat_lds, ds->world_tex_lds)
-        if (ds->world_diag && book2 && wide) {
-          if (!ds->diag) HIP_TRY(hipMalloc((void**)&ds->diag, 24 * sizeof(unsigned long long)));
-          HIP_TRY(hipMemsetAsync(ds->diag, 0, 24 * sizeof(unsigned long long), stream));
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<P_BOOK2, true, WORLD_WPS, true>), dim3(grid), dim3(TRACE_BLOCK), world_lds, stream,
-                             ds->view, rp, sm, s_begin, total, (uint32_t)npix, ds->samples, ds->work_counter, ds->view.entries,
-                             ds->view.top_level, ds->view.spheres, ds->view.moving_spheres, ds->view.rects, ds->view.triangles,
-                             ds->view.materials, ds->view.textures, ds->view.refs, ds->nodes4, ds->world_desc, ds->leaf_weight, ds->world_threshold, levels, ds->world_perlin_lds, ds->world_mat_lds, ds->world_tex_lds, ds->diag);
-          HIP_TRY(hipStreamSynchronize(stream));
-          unsigned long long hd[16];
-          HIP_TRY(hipMemcpy(hd, ds->diag, sizeof(hd), hipMemcpyDeviceToHost));
-          const char* names[8] = {"node_step", "leaf_step", "sweep", "shade(lean)", "regen", "direct_entry(all)", "direct_entry(run)", "shade(rare)"};
-          for (int k = 0; k < 8; ++k)
-            fprintf(stderr, "[world_diag] %-18s executions %llu lanes %llu mean lanes %.2f\n", names[k], hd[2 * k], hd[2 * k + 1],
-                    hd[2 * k] ? (double)hd[2 * k + 1] / (double)hd[2 * k] : 0.0);
-        } else if (has_gravity) {  // the bouncing-ball scene: the instantiation that carries GravitySphere code
-          if (wide) { LAUNCH_WORLD(P_ALL, true, WORLD_WPS); } else { LAUNCH_WORLD(P_ALL, false, WORLD_WPS); }
-        } else if (book2) {
-          if (wide) { LAUNCH_WORLD(P_BOOK2, true, WORLD_WPS); } else { LAUNCH_WORLD(P_BOOK2, false, WORLD_WPS); }
-        } else if (no_sphere_media) {
-          if (wide) { LAUNCH_WORLD(P_NO_SPHERE_MEDIA, true, WORLD_WPS); } else { LAUNCH_WORLD(P_NO_SPHERE_MEDIA, false, WORLD_WPS); }
-        } else {
-          if (wide) { LAUNCH_WORLD(P_ANY, true, WORLD_WPS); } else { LAUNCH_WORLD(P_ANY, false, WORLD_WPS); }
-        }
-#undef LAUNCH_WORLD
-      } else {
-        kernel_used = RTX_KERNEL_PERSISTENT;
-        HIP_TRY(hipMemsetAsync(ds->work_counter, 0, sizeof(unsigned int), stream));
-        uint64_t want = ((uint64_t)total + TRACE_BLOCK - 1) / TRACE_BLOCK;
-        uint64_t resident = (uint64_t)ds->n_cu * (uint64_t)ds->blocks_per_cu[preset];
-        uint32_t grid = (uint32_t)(want < resident ? want : resident);
-#define LAUNCH_PERSISTENT(FEAT, WIDEF, VIEW, LDSB)                                                     \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_persistent<FEAT, WIDEF>), dim3(grid), dim3(TRACE_BLOCK),  \
-                     LDSB, stream, VIEW, rp, sm, s_begin, total, (uint32_t)npix, ds->samples,            \
-                     ds->work_counter, ds->view.entries, ds->view.top_level, ds->view.spheres,             \
-                     ds->view.moving_spheres, ds->view.rects, ds->view.triangles, ds->view.materials,      \
-                     ds->view.textures, ds->view.refs)
-        rt::SceneView pv = ds->view;
-        pv.pad = ds->leaf_weight;
-        if (ds->nodes4 && preset >= 1) {
-          rt::SceneView wv = pv;
-          wv.nodes = (const rt::FlatNode*)ds->nodes4;  // the wide tree rides in the slot of the (unused) f64 tree
-          const size_t wide_lds = (size_t)ds->wide_levels * TRACE_BLOCK * sizeof(int32_t);
-          resident = (uint64_t)ds->n_cu * (uint64_t)ds->wide_pers_blocks_per_cu[preset];
-          grid = (uint32_t)(want < resident ? want : resident);
-          if (preset == 1) { LAUNCH_PERSISTENT(P_MESH, true, wv, wide_lds); }
-          else { LAUNCH_PERSISTENT(P_ANY, true, wv, wide_lds); }
-        }
-        else if (preset == 0) { LAUNCH_PERSISTENT(P_SPHERES, false, pv, lds_bytes); }
-        else if (preset == 1) { LAUNCH_PERSISTENT(P_MESH, false, pv, lds_bytes); }
-        else { LAUNCH_PERSISTENT(P_ANY, false, pv, lds_bytes); }
-#undef LAUNCH_PERSISTENT
+    for (uint32_t s_off = 0; s_off < spp; s_off += pp.spp_pass, ++passes) {
+      const int half = pp.pipeline ? (passes & 1) : 0;
+      const uint32_t s_count = spp - s_off < pp.spp_pass ? spp - s_off : pp.spp_pass;
+      a.s_begin = s_first + s_off;  // absolute index of the pass's first sample: the key of its random streams
+      a.total = (uint32_t)((uint64_t)s_count * npix);
+      a.stream = half ? ws.aux_stream : stream;  // every launch of the pass goes to this stream
+      a.samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)npix * 3u;
+      a.work_counter = ws.work_counter + half;
+      if (stats) HIP_TRY(hipEventRecord(ws.ev[0], a.stream));
+      switch (kernel) {
+        case RTX_KERNEL_SIMPLE: launch_simple<COUNT>(ds, a); break;
+        case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam); break;
+        case RTX_KERNEL_WAVEFRONT: st = wave_pass(ds, a); break;
+        case RTX_KERNEL_VOTE: st = launch_vote(ds, a); break;
+        case RTX_KERNEL_WORLD: st = launch_world(ds, a); break;
+        default: st = launch_persistent(ds, a); break;
       }
+      if (st != RTX_OK) return st;
       HIP_TRY(hipGetLastError());
       if (stats) {
-        HIP_TRY(hipEventRecord(ds->ev[1], stream));
-        HIP_TRY(hipEventSynchronize(ds->ev[1]));
+        HIP_TRY(hipEventRecord(ws.ev[1], a.stream));
+        HIP_TRY(hipEventSynchronize(ws.ev[1]));
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ds->ev[0], ds->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]));
         trace_ms += ms;
       }
       uint32_t pgrid = (uint32_t)((npix + 255) / 256);
-      if (pipeline && passes > 0) HIP_TRY(hipStreamWaitEvent(stream, ds->ev_pass[1 - half], 0));  // the previous pass's sums are in
+      if (pp.pipeline && passes > 0) HIP_TRY(hipStreamWaitEvent(a.stream, ws.ev_pass[1 - half], 0));  // the previous pass's sums are in
       const int first_pass = s_off == 0 && !(range && range->cont) ? 1 : 0;
       if (range && range->sumsq)
-        hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, stream, ds->samples, accum, range->sumsq,
+        hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, a.stream, a.samples, accum, range->sumsq,
                            (uint32_t)npix, s_count, first_pass);
       else
-        hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, stream, ds->samples, accum,
-                           (uint32_t)npix, s_count, first_pass);
+        hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, a.stream, a.samples, accum, (uint32_t)npix, s_count, first_pass);
       HIP_TRY(hipGetLastError());
-      if (pipeline) HIP_TRY(hipEventRecord(ds->ev_pass[half], stream));
+      if (pp.pipeline) HIP_TRY(hipEventRecord(ws.ev_pass[half], a.stream));
     }
-    if (pipeline && passes > 0 && ((passes - 1) & 1)) HIP_TRY(hipStreamWaitEvent(caller_stream, ds->ev_pass[1], 0));
+    if (pp.pipeline && passes > 0 && ((passes - 1) & 1)) HIP_TRY(hipStreamWaitEvent(stream, ws.ev_pass[1], 0));
     if (d_rgb8_out) {
       uint32_t pgrid = (uint32_t)((npix + 255) / 256);
       hipLaunchKernelGGL(k_tonemap, dim3(pgrid), dim3(256), 0, stream, accum, d_rgb8_out, (uint32_t)npix, s_first + spp);
@@ -824,12 +1180,12 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
     stats->trace_ms = trace_ms;
     stats->trace_launches = passes;
     stats->passes = passes;
-    stats->trace_kernel = kernel_used;
-    stats->sample_buffer_bytes = need_samples;
+    stats->trace_kernel = passes > 0 ? kernel : RTX_KERNEL_SIMPLE;  // (nothing traced: no kernel ran)
+    stats->sample_buffer_bytes = pp.sample_bytes;
     stats->samples = (uint64_t)spp * npix;  // (pixel, sample) paths this call traced; the work counters below only in count mode
     if (COUNT) {
       rt::TraceCounters c;
-      HIP_TRY(hipMemcpy(&c, ds->counters, sizeof(c), hipMemcpyDeviceToHost));
+      HIP_TRY(hipMemcpy(&c, ws.counters, sizeof(c), hipMemcpyDeviceToHost));
       stats->samples = c.samples; stats->rays = c.rays; stats->box_tests = c.box_tests;
       stats->sphere_tests = c.sphere_tests; stats->moving_sphere_tests = c.moving_sphere_tests;
       stats->rect_tests = c.rect_tests; stats->triangle_tests = c.triangle_tests;
@@ -847,13 +1203,11 @@ static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, uint32_t npix
   return RTX_OK;
 }
 
-// Upload one flattened scene to the current device and size the launches of every kernel for it.
+// Upload one flattened scene to the current device and plan the launches of every kernel family for it.
 static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   *out = nullptr;
   DeviceScene* ds = new (std::nothrow) DeviceScene();
   if (!ds) { set_error("out of memory"); return RTX_ENOMEM; }
-  memset(&ds->vote_top, 0, sizeof(ds->vote_top));
-  ds->vote_top.n = -1;
   hipError_t e = hipGetDevice(&ds->device);
   if (e != hipSuccess) {
     set_error(std::string("hipGetDevice: ") + hipGetErrorString(e) + " (this library has no CPU render path)");
@@ -872,382 +1226,24 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   v.n_top_level = (int32_t)fs.top_level.size();
   v.max_stack = fs.max_stack;
   v.features = fs.features;
-  ds->n_nodes = (int32_t)fs.nodes.size();
   // GravitySphere::get_center (hit.rs:369-391) leaves its stored trajectory for a brute-force loop of (time - time0) / 0.001
   // steps, per sphere test, per ray: a shutter far beyond the table is an effectively unbounded kernel.  Renders are limited to
   // RTX_GRAVITY_SLACK_S seconds past the shortest table (10 000 loop steps); rtx_render* return RTX_EINVAL beyond.
-  ds->gravity_time_limit = 1e300;
   for (const rt::FlatGravitySphere& g : fs.gravity_spheres)
     ds->gravity_time_limit = std::min(ds->gravity_time_limit, (double)g.table_len * 0.001 + 10.0);
-  {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, ds->device) == hipSuccess && prop.multiProcessorCount > 0)
-      ds->n_cu = prop.multiProcessorCount;
-    size_t lds = (size_t)(fs.max_stack + 1) * TRACE_BLOCK * sizeof(int32_t);
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_persistent<P_SPHERES, false>, TRACE_BLOCK, lds) == hipSuccess && nb > 0) ds->blocks_per_cu[0] = nb;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_persistent<P_MESH, false>, TRACE_BLOCK, lds) == hipSuccess && nb > 0) ds->blocks_per_cu[1] = nb;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_persistent<P_ANY, false>, TRACE_BLOCK, lds) == hipSuccess && nb > 0) ds->blocks_per_cu[2] = nb;
-#ifdef RTX_EXPERIMENTAL_KERNELS
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_stream<P_SPHERES>, TRACE_BLOCK, lds) == hipSuccess && nb > 0) ds->stream_blocks_per_cu[0] = nb;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_trace_stream<P_MESH>, TRACE_BLOCK, lds) == hipSuccess && nb > 0) ds->stream_blocks_per_cu[1] = nb;
-#endif
-    const char* k = getenv("RTX_TRACE_KERNEL");
-    ds->force_simple = (k && strcmp(k, "simple") == 0);
-    ds->force_persistent = (k && strcmp(k, "persistent") == 0);
-#ifdef RTX_EXPERIMENTAL_KERNELS
-    ds->force_stream = (k && strcmp(k, "stream") == 0);
-#endif
-    ds->vote_diag = (k && strcmp(k, "vote_diag") == 0);
-    ds->world_diag = (k && strcmp(k, "world_diag") == 0);
-    ds->force_world = ds->world_diag || (k && strcmp(k, "world") == 0);
-    ds->force_vote = ds->vote_diag || (k && strcmp(k, "vote") == 0);
-    ds->force_wave = (k && strcmp(k, "wavefront") == 0);
-    {
-      const char* wp = getenv("RTX_WF_PATHS");
-      if (wp && atol(wp) >= 256 && atol(wp) <= (1l << 27)) ds->wave_paths = (uint32_t)atol(wp);
-      const char* wr = getenv("RTX_WF_REFILL");
-      if (wr && atoi(wr) >= 1 && atoi(wr) <= 64) ds->wave_refill = (uint32_t)atoi(wr);
-      const char* wo = getenv("RTX_WF_OCC");
-      if (wo && atoi(wo) >= 4 && atoi(wo) <= 6) ds->wave_occ = atoi(wo);
-      ds->wave_verbose = getenv("RTX_WF_VERBOSE") != nullptr;
-      const char* wc = getenv("RTX_WF_CHECK");
-      if (wc && atoi(wc) >= 1 && atoi(wc) <= 4096) ds->wave_check = (uint32_t)atoi(wc);
-    }
-    {
-      const size_t lds_ring = lds + (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE;
-      int nb0 = 0, nb1 = 0;
-      const char* rg = getenv("RTX_RING");
-      // preset 0
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb0, k_trace_vote<P_SPHERES, false, false, false>, TRACE_BLOCK, lds) != hipSuccess) nb0 = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb1, k_trace_vote<P_SPHERES, false, true, false>, TRACE_BLOCK, lds_ring) != hipSuccess) nb1 = 0;
-      ds->vote_ring[0] = nb1 > 0 && nb1 >= nb0 && lds_ring <= 64 * 1024;
-      if (rg && nb1 > 0 && lds_ring <= 64 * 1024) ds->vote_ring[0] = atoi(rg) != 0;
-      nb = ds->vote_ring[0] ? nb1 : nb0;
-      if (nb > 0) ds->vote_blocks_per_cu[0] = nb;
-      // preset 1
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb0, k_trace_vote<P_MESH, false, false, false>, TRACE_BLOCK, lds) != hipSuccess) nb0 = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb1, k_trace_vote<P_MESH, false, true, false>, TRACE_BLOCK, lds_ring) != hipSuccess) nb1 = 0;
-      ds->vote_ring[1] = false;  // measured on the mesh room: no gain, and the ring's live state spills 50 dwords there
-      if (rg && nb1 > 0 && lds_ring <= 64 * 1024) ds->vote_ring[1] = atoi(rg) != 0;
-      nb = ds->vote_ring[1] ? nb1 : nb0;
-      if (nb > 0) ds->vote_blocks_per_cu[1] = nb;
-    }
-    ds->single_bvh = fs.top_level.size() == 1 && fs.entries[fs.top_level[0]].kind == rt::ENTRY_BVH;
-    {
-      int n_bvh = 0, n_other = 0;
-      for (size_t k = 0; k < fs.top_level.size(); ++k) {
-        const int32_t kind = fs.entries[fs.top_level[k]].kind;
-        if (kind == rt::ENTRY_BVH) { ++n_bvh; ds->vote_bvh_pos = (int32_t)k; }
-        else if (kind != rt::ENTRY_PRIM) ++n_other;
-      }
-      ds->vote_ok = n_bvh == 1 && n_other == 0;
-      if (ds->vote_ok && fs.top_level.size() <= 9 && !(getenv("RTX_VOTE_TOP") && atoi(getenv("RTX_VOTE_TOP")) == 0)) {
-        ds->vote_top.n = 0;
-        ds->vote_top.all_rects = 1;
-        for (size_t k = 0; k < fs.top_level.size(); ++k) {
-          if ((int32_t)k == ds->vote_bvh_pos) continue;
-          const rt::PrimRef ref = (rt::PrimRef)fs.entries[fs.top_level[k]].a;
-          ds->vote_top.k[ds->vote_top.n] = (int32_t)k;
-          ds->vote_top.ref[ds->vote_top.n] = (uint32_t)ref;
-          if (rt::primref_type(ref) == rt::PRIM_RECT) ds->vote_top.rect[ds->vote_top.n] = fs.rects[rt::primref_index(ref)];
-          else ds->vote_top.all_rects = 0;
-          ds->vote_top.n += 1;
-        }
-        if (!ds->vote_top.all_rects) ds->vote_top.n = -1;
-      }
-      ds->wave_ok = ds->vote_ok;
-      if (ds->vote_ok) {
-        const rt::FlatEntry& be = fs.entries[fs.top_level[ds->vote_bvh_pos]];
-        bool pure = be.c > 0 && rt::primref_type(fs.refs[be.b]) == rt::PRIM_TRIANGLE;
-        const uint32_t t0 = pure ? rt::primref_index(fs.refs[be.b]) : 0u;
-        for (int32_t k = 0; pure && k < be.c; ++k)
-          pure = fs.refs[be.b + k] == rt::make_primref(rt::PRIM_TRIANGLE, t0 + (uint32_t)k);
-        const char* tb = getenv("RTX_TRI_DIRECT");
-        if (pure && !(tb && atoi(tb) == 0)) ds->vote_tri_base = (int32_t)t0;
-      }
-    }
-    // 4-wide culling tree (see FlatNode4) for every BVH of the scene: big triangle meshes under k_trace_vote, and any
-    // world that takes k_trace_persistent (Book-2: two BVHs walked per bounce, each step a dependent L2 fetch).
-    // RTX_WIDE=0/1 overrides the size tests.
-    {
-      const bool spheres_preset = (fs.features & ~P_SPHERES) == 0;
-      const bool mesh_preset = !spheres_preset && (fs.features & ~P_MESH) == 0;
-      const int preset_i = spheres_preset ? 0 : (mesh_preset ? 1 : 2);
-      const char* wd = getenv("RTX_WIDE");
-      const bool for_vote = ds->vote_ok && mesh_preset;
-      const bool for_pers = !(ds->vote_ok && preset_i < 2) && preset_i >= 1;
-      bool want_wide = (for_vote && fs.nodes.size() >= 4096) || (for_pers && fs.nodes.size() >= 256);
-      if (wd) want_wide = (for_vote || for_pers) && atoi(wd) != 0 && !fs.nodes.empty();
-      if (want_wide) {
-        std::vector<FlatNode4> wide(fs.nodes.size());
-        memset(wide.data(), 0, wide.size() * sizeof(FlatNode4));
-        int peak = 0;
-        for (const rt::FlatEntry& e : fs.entries)
-          if (e.kind == rt::ENTRY_BVH) peak = std::max(peak, build_wide_nodes(fs.nodes, e.a, &wide));
-        ds->wide_levels = peak + 1;  // (the spare level is the bottom slot of LdsStackB; walk_node_step4 needs none of its own)
-        const size_t wide_lds = (size_t)ds->wide_levels * TRACE_BLOCK * sizeof(int32_t);
-        int nbw = 0;
-        bool ok = wide_lds <= 64 * 1024;
-        if (ok && for_vote) ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nbw, k_trace_vote<P_MESH, false, false, true>, TRACE_BLOCK, wide_lds) == hipSuccess && nbw > 0;
-        if (ok && for_vote) ds->wide_blocks_per_cu = nbw;
-        if (ok) {
-          int n1 = 0, n2 = 0;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, k_trace_persistent<P_MESH, true>, TRACE_BLOCK, wide_lds) == hipSuccess && n1 > 0) ds->wide_pers_blocks_per_cu[1] = n1;
-          if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, k_trace_persistent<P_ANY, true>, TRACE_BLOCK, wide_lds) == hipSuccess && n2 > 0) ds->wide_pers_blocks_per_cu[2] = n2;
-          ok = n1 > 0 && n2 > 0;
-        }
-        if (ok) {
-          const FlatNode4* dptr = nullptr;
-          if ((st = upload_array(ds, wide, &dptr)) != RTX_OK) { free_device_scene(ds); return st; }
-          ds->nodes4 = dptr;
-        }
-        if (wd) fprintf(stderr, "[rtx] RTX_WIDE: 4-wide tree %s (%d stack levels)\n", ds->nodes4 ? "on" : "off", ds->wide_levels);
-        if (getenv("RTX_VALIDATE")) {  // walk every wide tree on the host: codes in range, stack use within wide_levels
-          for (const rt::FlatEntry& e : fs.entries) {
-            if (e.kind != rt::ENTRY_BVH) continue;
-            std::vector<std::pair<int32_t, int>> todo;  // (code, stack entries below it)
-            todo.push_back({e.a, 0});
-            size_t visited = 0, bad = 0; int deepest = 0;
-            while (!todo.empty()) {
-              auto [code, below] = todo.back(); todo.pop_back();
-              if (code < 0) { if (rt::leaf_first(code) + rt::leaf_count(code) > (uint32_t)e.c) ++bad; continue; }
-              if ((size_t)code >= wide.size()) { ++bad; continue; }
-              ++visited;
-              int nk = 0;
-              for (int k = 0; k < 4; ++k) if (wide[code].child[k] != 0x7fffffff) ++nk;
-              deepest = std::max(deepest, below + nk);
-              for (int k = 0; k < 4; ++k) if (wide[code].child[k] != 0x7fffffff) todo.push_back({wide[code].child[k], below + nk - 1});
-            }
-            fprintf(stderr, "[rtx] RTX_VALIDATE: BVH root %d refs %d: %zu wide nodes walked, %zu bad codes, deepest stack %d of %d levels, sizeof(real) %zu\n",
-                    e.a, e.c, visited, bad, deepest, ds->wide_levels, sizeof(rt::real));
-          }
-        }
-      }
-    }
-    {
-      const char* ml = getenv("RTX_MAT_LDS");
-      if (!fs.materials.empty() && !fs.textures.empty() && fs.materials.size() <= 16 && fs.textures.size() <= 16 && !(ml && atoi(ml) == 0)) {
-        ds->vote_tables = (uint32_t)fs.materials.size() | ((uint32_t)fs.textures.size() << 16);
-        ds->vote_tables_bytes = fs.materials.size() * sizeof(rt::FlatMaterial) + fs.textures.size() * sizeof(rt::FlatTexture);
-      }
-    }
-    {
-      const std::vector<WorldDesc> wd = build_world_desc(fs);
-      const WorldDesc* dptr = nullptr;
-      if ((st = upload_array(ds, wd, &dptr)) != RTX_OK) { free_device_scene(ds); return st; }
-      ds->world_desc = dptr;
-    }
-    {
-      const char* wth = getenv("RTX_WORLD_THRESHOLD");
-      if (wth && atoi(wth) >= 0 && atoi(wth) <= 64) ds->world_threshold = (uint32_t)atoi(wth);
-      for (int wd = 0; wd < 2; ++wd) {
-        const uint32_t levels = (uint32_t)(wd ? ds->wide_levels : fs.max_stack + 1);
-        size_t wl = (size_t)levels * TRACE_BLOCK * sizeof(int32_t) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real);
-        if (wl > 64 * 1024) continue;
-        // Perlin tables in LDS when that costs no resident block (3 per CU at 168 VGPRs: up to 53 KB each)
-        if ((wd != 0) == (ds->nodes4 != nullptr)) {
-          const char* pl = getenv("RTX_PERLIN_LDS");
-          const size_t n_p = fs.perlins.size();
-          if (n_p >= 1 && n_p <= 2 && !(pl && atoi(pl) == 0) && wl + n_p * sizeof(rt::FlatPerlin) <= 52 * 1024) {
-            ds->world_perlin_lds = (uint32_t)n_p;
-            wl += n_p * sizeof(rt::FlatPerlin);
-          }
-          const char* ml = getenv("RTX_MAT_LDS");
-          const size_t mt = fs.materials.size() * sizeof(rt::FlatMaterial) + fs.textures.size() * sizeof(rt::FlatTexture);
-          if (!fs.materials.empty() && !fs.textures.empty() && fs.materials.size() <= 64 && fs.textures.size() <= 64 && !(ml && atoi(ml) == 0) &&
-              wl + mt <= 52 * 1024) {
-            ds->world_mat_lds = (uint32_t)fs.materials.size();
-            ds->world_tex_lds = (uint32_t)fs.textures.size();
-            wl += mt;
-          }
-        }
-        int n = 0;
-#define WORLD_OCC(FEAT, WIDEF, WPS, OUT) if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_trace_world<FEAT, WIDEF, WPS>, TRACE_BLOCK, wl) == hipSuccess && n > 0) OUT = n
-        if (wd) { WORLD_OCC(P_BOOK2, true, WORLD_WPS, ds->world_blocks_per_cu[0][1]); WORLD_OCC(P_ANY, true, WORLD_WPS, ds->world_blocks_per_cu[1][1]); WORLD_OCC(P_ALL, true, WORLD_WPS, ds->world_blocks_per_cu[2][1]); WORLD_OCC(P_NO_SPHERE_MEDIA, true, WORLD_WPS, ds->world_blocks_per_cu[3][1]); }
-        else { WORLD_OCC(P_BOOK2, false, WORLD_WPS, ds->world_blocks_per_cu[0][0]); WORLD_OCC(P_ANY, false, WORLD_WPS, ds->world_blocks_per_cu[1][0]); WORLD_OCC(P_ALL, false, WORLD_WPS, ds->world_blocks_per_cu[2][0]); WORLD_OCC(P_NO_SPHERE_MEDIA, false, WORLD_WPS, ds->world_blocks_per_cu[3][0]); }
-#undef WORLD_OCC
-      }
-    }
-    if (ds->single_bvh && (fs.features & ~P_SPHERES) == 0 && fs.nodes32.size() <= LDSK_MAX_NODES) {
-      uint32_t max_count = 0, max_end = 0;
-      for (const rt::FlatNode& nd : fs.nodes)
-        for (int ch = 0; ch < 2; ++ch)
-          if (nd.child[ch] < 0) {
-            max_count = std::max(max_count, rt::leaf_count(nd.child[ch]));
-            max_end = std::max(max_end, rt::leaf_first(nd.child[ch]) + rt::leaf_count(nd.child[ch]));
-          }
-      int lds_max = 0;
-      (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ds->device);
-      if (lds_max > 160 * 1024) lds_max = 160 * 1024;
-      // primitive records in LDS: one per leaf slot, in slot order (trace_lds.inc) -- spheres, or moving spheres when the scene has any
-      ds->lds_dims = {(uint32_t)fs.nodes32.size(), max_end, max_end, 0u, LDSK_NODE_DWORDS, 0u};
-      if (!fs.moving_spheres.empty()) {
-        const char* mc = getenv("RTX_MV_COMMON");
-        bool same = !(mc && atoi(mc) == 0);
-        for (const rt::FlatMovingSphere& ms : fs.moving_spheres)
-          same = same && ms.time0 == fs.moving_spheres[0].time0 && ms.time1 == fs.moving_spheres[0].time1;
-        if (same) { ds->mv_common = true; ds->mv_t0 = (double)fs.moving_spheres[0].time0; ds->mv_t1 = (double)fs.moving_spheres[0].time1; }
-      }
-      if (fs.features & rt::F_MOVING_SPHERE) {  // k_trace_lds<P_SPHERES>: one kind of primitive in LDS (trace_lds.inc: UNI)
-        ds->lds_dims.n_uni = (uint32_t)fs.spheres.size();
-        ds->lds_dims.n_moving = max_end;
-        ds->lds_dims.n_spheres = 0u;
-      }
-      ds->motion_dims = ds->lds_dims;
-      ds->motion_dims.node_dwords = LDSK_MOTION_NODE_DWORDS;
-      {
-        // slopes along one axis only?  (a scene whose spheres all move the same way; the y-only instantiation exists: Book-1 at HEAD)
-        bool moves[3] = {false, false, false};
-        for (const rt::FlatMotion32& m : fs.motion32)
-          for (int ch = 0; ch < 2; ++ch)
-            for (int a = 0; a < 3; ++a) moves[a] = moves[a] || m.dlo[ch][a] != 0.0f || m.dhi[ch][a] != 0.0f;
-        const char* ma = getenv("RTX_MOTION_AXIS");
-        if (!fs.motion32.empty() && moves[1] && !moves[0] && !moves[2] && !(ma && atoi(ma) == 0)) {
-          ds->motion_axis = 1;
-          ds->motion_dims.node_dwords = LDSK_MOTION1_NODE_DWORDS;
-        }
-      }
-      const uint32_t levels = (uint32_t)fs.max_stack + 1u;
-      const char* ck = getenv("RTX_CHUNK");
-      if (ck && atoi(ck) >= 64 && atoi(ck) <= 65536) ds->lds_chunk = (uint32_t)atoi(ck);
-      const char* sl = getenv("RTX_SCENE_LDS");
-      const char* rg = getenv("RTX_RING");
-      const bool want_ring = !(rg && atoi(rg) == 0);
-      if (max_count <= 4 && max_end <= LDSK_MAX_SLOTS && !(sl && atoi(sl) == 0) && lds_max > 0) {
-        for (uint32_t cap : {64u, 48u}) {
-          if (want_ring && !ds->lds_ok && ldsk_layout(levels, cap, ds->lds_dims).total <= (uint32_t)lds_max) {
-            ds->lds_ok = true; ds->lds_ring = true; ds->lds_ring_cap = cap;
-          }
-        }
-        if (!ds->lds_ok && ldsk_layout(levels, 0u, ds->lds_dims).total <= (uint32_t)lds_max) { ds->lds_ok = true; ds->lds_ring = false; }
-        const rt::FlatEntry& be = fs.entries[fs.top_level[0]];
-        // the 4-wide collapse of the tree
-        // Measured on C2 and NOT the default: 236 wide nodes, 5.05 steps per ray against 10.6, bit-identical -- and 2.4 % slower
-        // (5997 against 6143 Msamples/s): sorting four children by entry distance and four conditional stack writes make a wide
-        // step ~2.3 x a binary one, whose near / far order comes for free out of the address.  Kept as the A/B partner (RTX_LDS_WIDE=1).
-        const char* lw = getenv("RTX_LDS_WIDE");
-        if (ds->lds_ok && lw && atoi(lw) != 0) {
-          std::vector<uint32_t> image;
-          uint32_t n_wide = 0;
-          const uint32_t wl = build_lds_wide_image(fs.nodes, be.a, &image, &n_wide);
-          if (wl > 0u) {
-            ds->w4_dims = ds->lds_dims;
-            ds->w4_dims.n_nodes = n_wide;
-            ds->w4_dims.node_dwords = LDSK_WIDE_NODE_DWORDS;
-            ds->w4_levels = wl;
-            for (uint32_t cap : {64u, 48u}) {
-              if (want_ring && !ds->w4_ok && ldsk_layout(wl, cap, ds->w4_dims).total <= (uint32_t)lds_max) {
-                ds->w4_ok = true; ds->w4_ring = true; ds->w4_ring_cap = cap;
-              }
-            }
-            if (!ds->w4_ok && ldsk_layout(wl, 0u, ds->w4_dims).total <= (uint32_t)lds_max) { ds->w4_ok = true; ds->w4_ring = false; }
-            if (ds->w4_ok) {
-              const uint32_t* dptr = nullptr;
-              if ((st = upload_array(ds, image, &dptr)) != RTX_OK) { free_device_scene(ds); return st; }
-              ds->w4_image = dptr;
-            }
-          }
-        }
-        // the time-aware instantiation: the world's one BVH holds moving spheres and came with an interval
-        const char* mo = getenv("RTX_MOTION");
-        if (ds->lds_ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && (double)be.f[0] < (double)be.f[1] && !(mo && atoi(mo) == 0)) {
-          ds->motion_t0 = (double)be.f[0]; ds->motion_t1 = (double)be.f[1];
-          // (a small ring is worse than none: its refills run with that few lanes -- HEAD Book-1, ring of 16: 3137 Msamples/s against
-          // 3774 without; ring of 32 on the final build of round 3: 4963 against 5196.  Rings are 64 or 48 entries, or absent.)
-          for (uint32_t cap : {64u, 48u}) {
-            if (want_ring && !ds->motion_ok && ldsk_layout(levels, cap, ds->motion_dims).total <= (uint32_t)lds_max) {
-              ds->motion_ok = true; ds->motion_ring = true; ds->motion_ring_cap = cap;
-            }
-          }
-          if (!ds->motion_ok && ldsk_layout(levels, 0u, ds->motion_dims).total <= (uint32_t)lds_max) { ds->motion_ok = true; ds->motion_ring = false; }
-        }
-      }
-      if (ds->lds_ok) {
-        // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
-        // scenes uploaded earlier (with other LDS sizes) keep launching
-        const int bytes = lds_max;
-        hipError_t ae = hipSuccess;
-#define LDS_ATTR(FEAT, RINGF, MOTIONF, W4F) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)k_trace_lds<FEAT, RINGF, MOTIONF, W4F>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)
-        LDS_ATTR(P_SPHERES, true, 0u, false); LDS_ATTR(P_SPHERES, false, 0u, false); LDS_ATTR(P_STATIC_SPHERES, true, 0u, false); LDS_ATTR(P_STATIC_SPHERES, false, 0u, false);
-        LDS_ATTR(P_SPHERES, true, 1u, false); LDS_ATTR(P_SPHERES, false, 1u, false); LDS_ATTR(P_SPHERES, true, 3u, false); LDS_ATTR(P_SPHERES, false, 3u, false);
-        LDS_ATTR(P_SPHERES, true, 0u, true); LDS_ATTR(P_SPHERES, false, 0u, true); LDS_ATTR(P_STATIC_SPHERES, true, 0u, true); LDS_ATTR(P_STATIC_SPHERES, false, 0u, true);
-#undef LDS_ATTR
-        if (ae != hipSuccess) { (void)hipGetLastError(); ds->lds_ok = false; }
-      }
-      if (sl) fprintf(stderr, "[rtx] RTX_SCENE_LDS: 4-wide tree %s (%u nodes, %u levels, ring of %u, %u B)\n", ds->w4_ok ? "on" : "off", ds->w4_dims.n_nodes, ds->w4_levels,
-                      ds->w4_ring ? ds->w4_ring_cap : 0u, ds->w4_ok ? ldsk_layout(ds->w4_levels, ds->w4_ring ? ds->w4_ring_cap : 0u, ds->w4_dims).total : 0u);
-      if (sl) fprintf(stderr, "[rtx] RTX_SCENE_LDS: k_trace_lds %s (ring of %u, %u B of LDS); time-aware boxes %s (ring of %u, %u B)\n", ds->lds_ok ? "on" : "off",
-                      ds->lds_ring ? ds->lds_ring_cap : 0u, ldsk_layout(levels, ds->lds_ring ? ds->lds_ring_cap : 0u, ds->lds_dims).total,
-                      ds->motion_ok ? "on" : "off", ds->motion_ring ? ds->motion_ring_cap : 0u,
-                      ds->motion_ok ? ldsk_layout(levels, ds->motion_ring ? ds->motion_ring_cap : 0u, ds->motion_dims).total : 0u);
-    }
-#ifdef RTX_EXPERIMENTAL_KERNELS
-    ds->wq_diag = (k && strcmp(k, "wq_diag") == 0);
-    ds->force_wq = ds->wq_diag || (k && strcmp(k, "wq") == 0);
-    if (ds->single_bvh && (fs.features & ~P_SPHERES) == 0 && fs.nodes.size() <= WQ_MAX_NODES) {
-      const rt::FlatEntry& be = fs.entries[fs.top_level[0]];
-      uint32_t max_count = 0, max_end = 0;
-      for (const rt::FlatNode& nd : fs.nodes)
-        for (int ch = 0; ch < 2; ++ch)
-          if (nd.child[ch] < 0) {
-            max_count = std::max(max_count, rt::leaf_count(nd.child[ch]));
-            max_end = std::max(max_end, rt::leaf_first(nd.child[ch]) + rt::leaf_count(nd.child[ch]));
-          }
-      int lds_max = 0;
-      (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ds->device);
-      if (lds_max > 160 * 1024) lds_max = 160 * 1024;
-      ds->wq_levels = (uint32_t)fs.max_stack + 1u;
-      ds->wq_paths = lds_max > 0 ? wq_paths_for(ds->wq_levels, (uint32_t)lds_max) : 0u;
-      const char* wp = getenv("RTX_WQ_PATHS");
-      if (wp && atoi(wp) >= 64 && (uint32_t)atoi(wp) <= ds->wq_paths) ds->wq_paths = (uint32_t)atoi(wp) & ~63u;
-      const char* ww = getenv("RTX_WQ_WALKERS");
-      ds->wq_walkers = ds->wq_paths >= 192 ? (ds->wq_paths - 128) / 64 : 1;
-      if (ww && atoi(ww) >= 1 && atoi(ww) <= 16) ds->wq_walkers = (uint32_t)atoi(ww);
-      (void)be;
-      const char* wb = getenv("RTX_WQ_BATCH");
-      if (wb && atoi(wb) >= 1 && atoi(wb) <= 64) ds->wq_batch_min = (uint32_t)atoi(wb);
-      ds->wq_ok = ds->wq_paths > 0 && max_count <= 4 && max_end <= WQ_MAX_SLOTS;
-      if (ds->wq_ok && ds->force_wq) {
-        const WqLayout L = wq_layout(ds->wq_paths, ds->wq_levels);
-        (void)L;
-        if (hipFuncSetAttribute((const void*)k_trace_wq<P_SPHERES, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_trace_wq<P_SPHERES, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) {
-          (void)hipGetLastError();
-          ds->wq_ok = false;
-        }
-      }
-    }
-    if (ds->force_wq)
-      fprintf(stderr, "[rtx] RTX_TRACE_KERNEL=wq: %s (paths %u, stack levels %u, walkers %u)\n",
-              ds->wq_ok ? "applies" : "does NOT apply to this world, default kernel runs", ds->wq_paths, ds->wq_levels, ds->wq_walkers);
-#endif
-    // a leaf step costs about (primitives per leaf) x 1.3 node steps for spheres: vote weight 1 for single-primitive
-    // leaves, 3 otherwise (measured on C2 / HEAD / C4)
-    {
-      uint32_t max_count = 1;
-      for (const rt::FlatNode& nd : fs.nodes)
-        for (int ch = 0; ch < 2; ++ch)
-          if (nd.child[ch] < 0) max_count = std::max(max_count, rt::leaf_count(nd.child[ch]));
-      ds->leaf_weight = max_count <= 1 ? 1u : 3u;
-      ds->single_leaf = max_count <= 1;
-      // latency-bound wide walks: measured best on the dragon room (639 vs 575 Msamples/s)
-      if (ds->nodes4) { ds->leaf_weight = 1u; ds->walk_threshold = 24u; ds->regen_min = 8u; }  // regeneration waits for 8 lanes: 803 -> 824 on C4 (4: 817, 16: 801)
-      // k_trace_lds since the ground is asked first and the node step got shorter (round 3): C2 10 / 12 / 14 / 16 / 18 -> 6153 / 6188 /
-      // 6185 / 6170 / 6140, HEAD Book-1 3859 / 3850 / 3830 / 3808 / 3750 Msamples/s
-      else if (ds->lds_ok) ds->walk_threshold = 12u;
-    }
-    const char* rm = getenv("RTX_REGEN_MIN");
-    if (rm && atoi(rm) >= 1 && atoi(rm) <= 64) ds->regen_min = (uint32_t)atoi(rm);
-    const char* lw = getenv("RTX_LEAF_WEIGHT");
-    if (lw && atoi(lw) >= 1 && atoi(lw) <= 64) ds->leaf_weight = (uint32_t)atoi(lw);
-    const char* pp = getenv("RTX_PASS_PIPELINE");
-    if (pp) ds->pass_pipeline = atoi(pp) != 0;
-    const char* sg = getenv("RTX_SINGLE_LEAF");
-    if (sg && atoi(sg) == 0) ds->single_leaf = false;  // A/B: the general leaf loop on a tree of one-primitive leaves
-    const char* wt = getenv("RTX_WALK_THRESHOLD");
-    if (wt && atoi(wt) >= 1 && atoi(wt) <= 64) ds->walk_threshold = (uint32_t)atoi(wt);
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, ds->device) == hipSuccess && prop.multiProcessorCount > 0) ds->n_cu = prop.multiProcessorCount;
+
+  // one plan per kernel family; the order is their dependencies: wide tree <- vote, world <- wide, walk <- wide + lds
+  ds->sw = read_switches();
+  const LeafScan leaves = scan_leaves(fs);
+  plan_persistent(ds);
+  plan_vote(ds, fs);
+  if ((st = plan_wide(ds, fs)) != RTX_OK || (st = plan_world(ds, fs)) != RTX_OK || (st = plan_lds(ds, fs, leaves)) != RTX_OK) {
+    free_device_scene(ds);
+    return st;
   }
+  plan_walk(ds, leaves);
   *out = ds;
   return RTX_OK;
 }
@@ -1257,8 +1253,9 @@ static rtx_status scene_trim_impl(DeviceScene* ds) {
   HIP_TRY(hipGetDevice(&cur));
   if (cur != ds->device) { set_error("rtx_scene_trim: scene lives on a different device than the current one"); return RTX_EINVAL; }
   HIP_TRY(hipDeviceSynchronize());
-  if (ds->samples) { HIP_TRY(hipFree(ds->samples)); ds->samples = nullptr; ds->samples_bytes = 0; }
-  if (ds->accum) { HIP_TRY(hipFree(ds->accum)); ds->accum = nullptr; ds->accum_bytes = 0; }
+  Workspace& ws = ds->ws;
+  if (ws.samples) { HIP_TRY(hipFree(ws.samples)); ws.samples = nullptr; ws.samples_bytes = 0; }
+  if (ws.accum) { HIP_TRY(hipFree(ws.accum)); ws.accum = nullptr; ws.accum_bytes = 0; }
   return RTX_OK;
 }
 

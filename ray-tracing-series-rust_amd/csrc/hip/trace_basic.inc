@@ -1,4 +1,4 @@
-// Grid-stride, persistent and streaming trace kernels (included by render.hip, namespace rtx).
+// Grid-stride and persistent trace kernels (included by render.hip, namespace rtx).
 
 // ------------------------------------------------------------------ kernels
 // Feature presets the trace kernels are compiled for (see core/flat_types.hpp Feature).
@@ -132,124 +132,3 @@ __global__ __launch_bounds__(TRACE_BLOCK, (F == P_ANY ? 3 : 1)) void k_trace_per
     }
   }
 }
-
-#ifdef RTX_EXPERIMENTAL_KERNELS  // A/B partner of the voting kernels, not part of the product binary
-// Stage-synchronous persistent kernel for worlds that are ONE BVH (Book-1: world = BvhNode,
-// world.rs:162-166).  k_trace_persistent keeps every lane busy at BOUNCE granularity, but inside a
-// bounce the wave still walks the BVH until its slowest ray is done (measured: 31 % VALU lane
-// utilisation).  Here the walk itself is resumable (core/geometry.hpp bvh_step) and a lane is in
-// one of three stages:
-//     NEED   no path: wants a sample index          (regenerated with __ballot + mbcnt compaction)
-//     WALK   its ray is inside the BVH               (one bvh_step per inner iteration)
-//     SHADE  walk finished: wants finalize + scatter (path_bounce_end) -> WALK again or NEED
-// The wave alternates two phases: (1) ALL lanes that are not walking shade / regenerate together,
-// (2) node steps run while at least `walk_threshold` lanes are still walking (all remaining ones
-// once the queue is empty).  Lanes that finish a walk wait at most until the walking population
-// falls under the threshold, so both phases run with a well-filled wave instead of the whole wave
-// waiting for the longest walk of every bounce.  Which lane does what is invisible in the result.
-enum : int { STAGE_NEED = 0, STAGE_WALK = 1, STAGE_SHADE = 2 };
-template <uint32_t F>
-__global__ __launch_bounds__(TRACE_BLOCK) void k_trace_stream(rt::SceneView sv, rt::RenderParams rp,
-                                                              ShardMap sm, uint32_t s_begin,
-                                                              uint32_t total, uint32_t npix,
-                                                              double* __restrict__ samples,
-                                                              unsigned int* work_counter,
-                                                              uint32_t walk_threshold) {
-  extern __shared__ int32_t lds_stack[];
-  LdsStack stack;
-  stack.base = lds_stack + threadIdx.x;
-  stack.n = 0;
-  const uint32_t lane = threadIdx.x & 63u;
-  const rt::FlatEntry& bvh = sv.entries[sv.top_level[0]];
-  const int32_t root = bvh.a;
-  const uint32_t first_ref = (uint32_t)bvh.b;
-  uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
-  bool queue_empty = false;               // wave-uniform
-  int stage = STAGE_NEED;
-  uint32_t g = 0;
-  rt::PathState ps;
-  rt::Closest best;
-  rt::Vec3 inv_d = rt::v3(0, 0, 0);
-  uint32_t dir_neg = 0;
-  int32_t node = -1;  // -1: the lane's ray has not begun its bounce yet (phase 1c), >= 0: mid-walk
-  best.t = 0.0; best.ref = 0; best.order = 0; best.hit = false;
-  for (;;) {
-    // ---- phase 1a: shade the lanes whose walk has finished
-    if (stage == STAGE_SHADE) {
-      rt::HitRecord rec;
-      if (best.hit) rt::prim_finalize<F>(sv, best.ref, ps.ray, best.t, &rec);
-      if (rt::path_bounce_end<F, false>(sv, rp, &ps, best.hit, rec, nullptr)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
-        stage = STAGE_NEED;
-      } else {
-        stage = STAGE_WALK;  // new ray: bounce begins below
-      }
-    }
-    // ---- phase 1b: regenerate (wave-cooperative; executed by the whole wave)
-    {
-      unsigned long long need_mask = wave_ballot(stage == STAGE_NEED);
-      if (need_mask != 0ull) {
-        if (chunk_pos >= chunk_end && !queue_empty) {
-          uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(work_counter, TRACE_CHUNK);
-          base = __builtin_amdgcn_readfirstlane(base);
-          if (base >= total) {
-            queue_empty = true;
-          } else {
-            chunk_pos = base;
-            chunk_end = (total - base < TRACE_CHUNK) ? total : base + TRACE_CHUNK;
-          }
-        }
-        if (chunk_pos < chunk_end) {
-          uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32),
-                                                    __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
-          uint32_t n_need = (uint32_t)__popcll(need_mask);
-          uint32_t avail = chunk_end - chunk_pos;
-          if (stage == STAGE_NEED && rank < avail) {
-            g = chunk_pos + rank;
-            uint32_t s_local = g / npix;
-            uint32_t lp = g - s_local * npix;
-            uint32_t i, j;
-            shard_pixel(sm, lp, &i, &j);
-            rt::path_begin(rp, i, j, s_begin + s_local, &ps);
-            stage = STAGE_WALK;  // node == -1 here: phase 1c begins the first bounce
-          }
-          chunk_pos += (n_need < avail) ? n_need : avail;
-        }
-      }
-    }
-    // ---- phase 1c: begin the bounce of every lane that has a new ray (world.rs:64-68)
-    if (stage == STAGE_WALK && node < 0) {
-      if (rt::path_bounce_begin(&ps)) {  // depth exhausted: the path ends with what it gathered
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
-        stage = STAGE_NEED;
-      } else {
-        inv_d = rt::ray_inv_dir(ps.ray);
-        dir_neg = rt::ray_dir_neg(ps.ray);
-        best.t = RT_INFINITY; best.hit = false; best.ref = 0; best.order = 0;
-        stack.reset();
-        node = root;
-      }
-    }
-    // ---- exit: nothing walking, nothing to shade, queue drained
-    unsigned long long walk_mask = wave_ballot(stage == STAGE_WALK);
-    if (walk_mask == 0ull) {
-      if (queue_empty && wave_ballot(stage != STAGE_NEED) == 0ull) break;
-      continue;  // lanes whose path ended in 1c: go regenerate
-    }
-    // ---- phase 2: node steps while enough lanes walk
-    const uint32_t threshold = queue_empty ? 1u : walk_threshold;
-    do {
-      if (stage == STAGE_WALK) {
-        if (!rt::bvh_step<F, false>(sv, first_ref, ps.ray, inv_d, dir_neg, rt::ray_t_min(ps.ray), &node, &best, stack, nullptr)) {
-          stage = STAGE_SHADE;
-          node = -1;  // the next ray of this lane starts a new bounce
-        }
-      }
-      walk_mask = wave_ballot(stage == STAGE_WALK);
-    } while ((uint32_t)__popcll(walk_mask) >= threshold);
-  }
-}
-#endif  // RTX_EXPERIMENTAL_KERNELS

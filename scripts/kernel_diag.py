@@ -1,4 +1,4 @@
-"""Run one C2-shaped frame under a diagnostic trace kernel (RTX_TRACE_KERNEL=vote_diag | wq_diag); counters go to stderr."""
+"""Run one C2-shaped frame under a diagnostic trace kernel (RTX_TRACE_KERNEL=vote_diag | world_diag); counters go to stderr."""
 import importlib
 import os
 import sys

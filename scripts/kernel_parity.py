@@ -1,6 +1,6 @@
 """Bit-exact A/B of trace-kernel variants on the GPU box (the RTX_* environment is read at scene upload).
 
-    python scripts/kernel_parity.py RTX_TRACE_KERNEL=wq [time]    # variant vs baseline, then timed C2 frames
+    python scripts/kernel_parity.py RTX_TRACE_KERNEL=world [time]  # variant vs baseline, then timed C2 frames
     python scripts/kernel_parity.py RTX_RING=1 time
 
 The baseline is the plain voting kernel (RTX_RING=0 RTX_SCENE_LDS=0, no RTX_TRACE_KERNEL), which tests/test_gpu_parity.py pins
