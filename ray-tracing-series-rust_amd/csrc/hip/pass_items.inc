@@ -1,0 +1,49 @@
+// A pass's index space as the trace kernels see it (included by render.hip, namespace rtx): item -> pixel and path, the
+// sample store, the chunk size of the persistent kernels' work counter and the size of the per-wave primary-ray ring.
+//
+// A pass of `total` items is one index space [0, total): item g = s_local * npix + lp is sample s_begin + s_local of the
+// shard's local pixel lp, so 64 consecutive items are 64 consecutive pixels of one sample: coherent primary rays, coalesced
+// sample-buffer stores.  Which lane traces an item cannot matter: streams are keyed by (pixel, sample) and every item owns its
+// output slot.
+
+// Local pixel lp of a shard -> image (column i, row j).  Rows of a shard are the rows j with
+// (j / block_rows) % shard_count == shard_index, compacted in ascending j.
+struct ShardMap {
+  int32_t width, block_rows, shard_index, shard_count;
+};
+__device__ __forceinline__ void shard_pixel(const ShardMap& m, uint32_t lp, uint32_t* i, uint32_t* j) {
+  uint32_t lr = lp / (uint32_t)m.width;
+  *i = lp - lr * (uint32_t)m.width;
+  uint32_t k = lr / (uint32_t)m.block_rows;
+  uint32_t within = lr - k * (uint32_t)m.block_rows;
+  *j = (k * (uint32_t)m.shard_count + (uint32_t)m.shard_index) * (uint32_t)m.block_rows + within;
+}
+
+// Item g of the pass -> image pixel (i, j); returns the item's sample index within the pass.
+__device__ __forceinline__ uint32_t item_pixel(const ShardMap& sm, uint32_t npix, uint32_t g, uint32_t* i, uint32_t* j) {
+  const uint32_t s_local = g / npix;
+  shard_pixel(sm, g - s_local * npix, i, j);
+  return s_local;
+}
+
+// The camera ray and RNG stream of item g (path_begin, core/integrator.hpp).
+__device__ __forceinline__ void start_path(const rt::RenderParams& rp, const ShardMap& sm, uint32_t npix, uint32_t s_begin,
+                                           uint32_t g, rt::PathState* ps) {
+  uint32_t i, j;
+  const uint32_t s_local = item_pixel(sm, npix, g, &i, &j);
+  rt::path_begin(rp, i, j, s_begin + s_local, ps);
+}
+
+// Item g's radiance into the pass's sample buffer (k_reduce_samples adds it onto the accumulator in sample order).
+__device__ __forceinline__ void store_sample(double* samples, uint32_t g, const rt::Color& c) {
+  double* o = samples + 3 * (size_t)g;
+  o[0] = c.x; o[1] = c.y; o[2] = c.z;
+}
+
+// Items a wave claims from the pass's work counter per grab (k_trace_lds: RTX_CHUNK, this by default).
+#define TRACE_CHUNK 512u
+
+// A wave's ring of ready primary rays in LDS (k_trace_vote, k_trace_lds; RTX_RING): f64 [RING_F64][cap] (origin(3),
+// direction(3), time, rng.s0, rng.s1), then u32 [cap] (the item).  Bytes per wave:
+#define RING_F64 9u
+__host__ __device__ constexpr uint32_t ring_bytes(uint32_t cap) { return cap * (RING_F64 * 8u + 4u); }

@@ -37,8 +37,9 @@ namespace rtx { void set_error(const std::string& msg); }
 
 namespace rtx {
 
+#include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, ring_bytes
+
 // ------------------------------------------------------------------ device scene
-#define TRACE_CHUNK_DEFAULT 512u
 struct FlatNode4;
 typedef const FlatNode4 FlatNode4Dev;
 struct WorldDesc;
@@ -75,7 +76,7 @@ struct TraceSwitches {
   bool vote_top = true, tri_direct = true, mat_lds = true, perlin_lds = true;  // RTX_VOTE_TOP / _TRI_DIRECT / _MAT_LDS / _PERLIN_LDS
   bool mv_common = true, motion = true, motion_axis = true, lds_wide = false;  // RTX_MV_COMMON / _MOTION / _MOTION_AXIS / _LDS_WIDE
   bool single_leaf = true, pass_pipeline = true, validate = false;  // RTX_SINGLE_LEAF / _PASS_PIPELINE; RTX_VALIDATE: set at all
-  uint32_t chunk = TRACE_CHUNK_DEFAULT;  // RTX_CHUNK [64, 65536]: sample indices a k_trace_lds wave reserves per grab
+  uint32_t chunk = TRACE_CHUNK;  // RTX_CHUNK [64, 65536]: sample indices a k_trace_lds wave reserves per grab
   uint32_t world_threshold = 8;  // RTX_WORLD_THRESHOLD [0, 64]: k_trace_world's walk steps go first while this many lanes walk (0: majority)
   uint32_t walk_threshold = 0, regen_min = 0, leaf_weight = 0;  // RTX_WALK_THRESHOLD / _REGEN_MIN / _LEAF_WEIGHT [1, 64]; 0: WalkTuning's
   // wavefront integrator: RTX_WF_PATHS [256, 2^27] path slots; RTX_WF_REFILL [1, 64] free lanes a wave waits for before it takes new
@@ -226,20 +227,6 @@ __device__ __forceinline__ T dev_load_uniform(const T* p) { return *(const __att
 
 // 64-bit lane mask of a predicate, straight from the compare (HIP's __ballot(int) first materialises 0/1 in a VGPR).
 __device__ __forceinline__ unsigned long long wave_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
-// ------------------------------------------------------------------ pixel enumeration
-// Local pixel lp of a shard -> image (column i, row j).  Rows of a shard are the rows j with
-// (j / block_rows) % shard_count == shard_index, compacted in ascending j.
-struct ShardMap {
-  int32_t width, block_rows, shard_index, shard_count;
-};
-__device__ __forceinline__ void shard_pixel(const ShardMap& m, uint32_t lp, uint32_t* i, uint32_t* j) {
-  uint32_t lr = lp / (uint32_t)m.width;
-  *i = lp - lr * (uint32_t)m.width;
-  uint32_t k = lr / (uint32_t)m.block_rows;
-  uint32_t within = lr - k * (uint32_t)m.block_rows;
-  *j = (k * (uint32_t)m.shard_count + (uint32_t)m.shard_index) * (uint32_t)m.block_rows + within;
-}
 
 // ------------------------------------------------------------------ LDS traversal stack
 // Slot (level, lane) lives at base[level * TRACE_BLOCK]: lanes of a wave touch consecutive
@@ -436,7 +423,7 @@ static LeafScan scan_leaves(const FlatScene& fs) {
 static void plan_vote(DeviceScene* ds, const FlatScene& fs) {
   VotePlan& p = ds->vote;
   const TraceSwitches& sw = ds->sw;
-  const size_t lds = stack_bytes((uint32_t)fs.max_stack + 1u), lds_ring = lds + (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE;
+  const size_t lds = stack_bytes((uint32_t)fs.max_stack + 1u), lds_ring = lds + (TRACE_BLOCK / 64) * ring_bytes(64);
   const bool ring_fits = lds_ring <= 64 * 1024;
   auto fit = [&](int preset, int nb0, int nb1, bool ring_by_default) {
     p.ring[preset] = ring_by_default && nb1 > 0 && nb1 >= nb0 && ring_fits;
@@ -531,7 +518,7 @@ static rtx_status launch_vote(DeviceScene* ds, const PassArgs& a) {
   const bool diag = ds->sw.kernel == ForcedKernel::vote && ds->sw.diag;
   if (a.preset == 1 && ds->wide.nodes4) return launch_vote_wide(ds, a, diag);
   const bool ring = p.ring[a.preset];
-  const size_t lds = a.stack_lds + (ring ? (TRACE_BLOCK / 64) * RING_BYTES_PER_WAVE : 0);
+  const size_t lds = a.stack_lds + (ring ? (TRACE_BLOCK / 64) * ring_bytes(64) : 0);
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[a.preset]);
 #define LAUNCH_VOTE2(FEAT, DIAGF, RINGF)                                                                                 \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \

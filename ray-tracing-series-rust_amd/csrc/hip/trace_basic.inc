@@ -14,9 +14,8 @@ constexpr uint32_t P_MESH_ROOM = rt::F_RECT | rt::F_TRIANGLE | rt::F_PRIM_ENTRY 
 constexpr uint32_t P_ALL = rt::F_ALL;                            // everything, GravitySphere included (k_trace_simple, scene 8)
 constexpr uint32_t P_ANY = rt::F_ALL & ~rt::F_GRAVITY_SPHERE;    // any world of the catalogue's BASELINE scenes
 
-// Straightforward form: grid-stride over the pass's (sample, pixel) index space, one whole
-// path per loop iteration.  g = s_local * npix + lp, so a wave's lanes are 64 consecutive
-// pixels of the same sample: coherent primary rays, coalesced sample-buffer stores.
+// Straightforward form: grid-stride over the pass's (sample, pixel) index space (pass_items.inc), one whole
+// path per loop iteration.
 // Kept as the A/B partner of k_trace_persistent (RTX_TRACE_KERNEL=simple) and as the
 // instrumented (COUNT) build.
 template <uint32_t F, bool COUNT>
@@ -33,29 +32,23 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_simple(rt::SceneView sv, 
   if (COUNT) memset(&cnt, 0, sizeof(cnt));
   for (uint64_t g64 = (uint64_t)blockIdx.x * TRACE_BLOCK + threadIdx.x; g64 < total;
        g64 += (uint64_t)gridDim.x * TRACE_BLOCK) {
-    uint32_t g = (uint32_t)g64;
-    uint32_t s_local = g / npix;
-    uint32_t lp = g - s_local * npix;
+    const uint32_t g = (uint32_t)g64;
     uint32_t i, j;
-    shard_pixel(sm, lp, &i, &j);
-    rt::Color c = rt::trace_sample<F, COUNT>(sv, rp, i, j, s_begin + s_local, stack, &cnt);
-    double* o = samples + 3 * (size_t)g;
-    o[0] = c.x; o[1] = c.y; o[2] = c.z;
+    const uint32_t s_local = item_pixel(sm, npix, g, &i, &j);
+    store_sample(samples, g, rt::trace_sample<F, COUNT>(sv, rp, i, j, s_begin + s_local, stack, &cnt));
   }
   if (COUNT) flush_counters(cnt, counters);
 }
 
 template <bool WIDE> struct VoteWalkT;  // wave-cooperative BVH walker, defined with the voting walk below
 
-// Persistent waves with path regeneration.  The pass's samples form one index space
-// [0, total); waves pull chunks of it from a global counter and hand indices to their lanes
-// as lanes finish paths: every loop iteration the lanes without a path are compacted with a
-// 64-bit __ballot and ranked with mbcnt (the wavefront prefix sum), take consecutive indices
+// Persistent waves with path regeneration.  Waves pull TRACE_CHUNK-item chunks of the pass's
+// index space (pass_items.inc) from a global counter and hand items to their lanes as lanes
+// finish paths: every loop iteration the lanes without a path are compacted with a 64-bit
+// __ballot and ranked with mbcnt (the wavefront prefix sum), take consecutive items
 // (= consecutive pixels of one sample: coherent camera rays) and start a new path, then ALL
 // lanes advance their path by one bounce.  A lane therefore never idles while the queue has
-// work, whatever the length of its neighbours' paths.  Which lane runs which sample cannot
-// matter: streams are keyed by (pixel, sample) and every sample owns its output slot.
-#define TRACE_CHUNK 512u
+// work, whatever the length of its neighbours' paths.
 // WIDE: sv_in.nodes carries the 4-wide culling tree (FlatNode4, see below) instead of the f64 binary tree, which
 // this kernel never reads.
 template <uint32_t F, bool WIDE>
@@ -112,11 +105,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, (F == P_ANY ? 3 : 1)) void k_trace_per
         uint32_t avail = chunk_end - chunk_pos;
         if (!active && rank < avail) {
           g = chunk_pos + rank;
-          uint32_t s_local = g / npix;
-          uint32_t lp = g - s_local * npix;
-          uint32_t i, j;
-          shard_pixel(sm, lp, &i, &j);
-          rt::path_begin(rp, i, j, s_begin + s_local, &ps);
+          start_path(rp, sm, npix, s_begin, g, &ps);
           active = true;
         }
         chunk_pos += (n_need < avail) ? n_need : avail;
@@ -125,8 +114,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, (F == P_ANY ? 3 : 1)) void k_trace_per
     if (wave_ballot(active) == 0ull) break;  // queue drained and every lane's path has ended
     if (active) {
       if (rt::path_step<F, false, LdsStack, VoteWalkT<WIDE>>(sv, rp, &ps, stack, nullptr)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+        store_sample(samples, g, ps.output);
         active = false;
       }
     }

@@ -39,7 +39,7 @@ __host__ __device__ inline LdsKernelLayout ldsk_layout(uint32_t levels, uint32_t
   LdsKernelLayout L;
   uint32_t o = levels * LDSK_BLOCK * 2u;
   o = (o + 15u) & ~15u;
-  L.off_ring = o; o += (LDSK_BLOCK / 64u) * ring_cap * (RING_F64 * 8u + 4u);
+  L.off_ring = o; o += (LDSK_BLOCK / 64u) * ring_bytes(ring_cap);
   L.off_nodes = o; o += (d.n_nodes * d.node_dwords * 4u + 15u) & ~15u;
   L.off_refs = o;  // (no reference array since the records are kept in slot order)
   L.off_spheres = o; o += (d.n_spheres * (uint32_t)sizeof(rt::FlatSphere) + 15u) & ~15u;
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   LdsStack16 stack;
   stack.base = (unsigned short*)ldsk + threadIdx.x;
   stack.init();
-  double* const ring_f = (double*)(ldsk + L.off_ring + (threadIdx.x >> 6) * ring_cap * (RING_F64 * 8u + 4u));
+  double* const ring_f = (double*)(ldsk + L.off_ring + (threadIdx.x >> 6) * ring_bytes(ring_cap));
   uint32_t* const ring_g = (uint32_t*)(ring_f + RING_F64 * ring_cap);
   uint32_t ring_n = 0;                    // wave-uniform
   uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
@@ -299,12 +299,8 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
           const uint32_t m = room < avail ? room : avail;
           if (lane < m) {
             const uint32_t gg = chunk_pos + lane;
-            uint32_t s_local = gg / npix;
-            uint32_t lp = gg - s_local * npix;
-            uint32_t i, j;
-            shard_pixel(sm, lp, &i, &j);
             rt::PathState fresh;
-            rt::path_begin(rp, i, j, s_begin + s_local, &fresh);
+            start_path(rp, sm, npix, s_begin, gg, &fresh);
             const uint32_t slot = ring_n + lane;
             ring_f[0 * ring_cap + slot] = fresh.ray.origin.x; ring_f[1 * ring_cap + slot] = fresh.ray.origin.y;
             ring_f[2 * ring_cap + slot] = fresh.ray.origin.z; ring_f[3 * ring_cap + slot] = fresh.ray.direction.x;
@@ -348,11 +344,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
           const uint32_t avail = chunk_end - chunk_pos;
           if (!active && rank < avail) {
             g = chunk_pos + rank;
-            uint32_t s_local = g / npix;
-            uint32_t lp = g - s_local * npix;
-            uint32_t i, j;
-            shard_pixel(sm, lp, &i, &j);
-            rt::path_begin(rp, i, j, s_begin + s_local, &ps);
+            start_path(rp, sm, npix, s_begin, g, &ps);
             active = true;
           }
           chunk_pos += (n_need < avail) ? n_need : avail;
@@ -363,8 +355,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
     // ---- begin a bounce for every lane that is not in the middle of a carried-over walk
     if (active && !midwalk) {
       if (rt::path_bounce_begin(&ps)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+        store_sample(samples, g, ps.output);
         active = false;
       } else {
         q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
@@ -474,8 +465,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
       const bool hit = best.ref != LDSK_NO_REF;
       if (hit) rt::prim_finalize<FL>(lsv, best.ref, ps.ray, best.t, &rec);
       if (rt::path_bounce_end<F, false>(sv, rp, &ps, hit, rec, nullptr)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+        store_sample(samples, g, ps.output);
         active = false;
       }
     }

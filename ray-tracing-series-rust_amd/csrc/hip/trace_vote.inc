@@ -288,8 +288,6 @@ struct VoteWalkT {
 // when the ring cannot serve the request does the whole wave run the regeneration code, all lanes at
 // once, to top the ring up.  Which lane traces a sample is invisible in the result.
 // (VoteTop, the plain entries beside the BVH as a kernel argument, is declared in render.hip next to DeviceScene.)
-#define RING_F64 9  // origin(3) direction(3) time rng.s0 rng.s1
-#define RING_BYTES_PER_WAVE (64u * (RING_F64 * 8u + 4u))
 template <uint32_t F, bool DIAG, bool RING, bool WIDE>
 __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv, rt::RenderParams rp,
                                                             ShardMap sm, uint32_t s_begin, uint32_t total,
@@ -310,7 +308,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
   // Worlds with a handful of materials (the mesh room: 8) keep the material and texture records in LDS behind the stacks
   // (and the ring): every shading fetches material -> texture, two dependent per-lane loads.  lds_tables = materials | textures << 16.
   if (lds_tables != 0u) {
-    uint32_t* const dst = (uint32_t*)(lds_stack + stack_levels * TRACE_BLOCK) + (RING ? (TRACE_BLOCK / 64u) * (RING_BYTES_PER_WAVE / 4u) : 0u);
+    uint32_t* const dst = (uint32_t*)(lds_stack + stack_levels * TRACE_BLOCK) + (RING ? (TRACE_BLOCK / 64u) * (ring_bytes(64) / 4u) : 0u);
     const uint32_t mw = (lds_tables & 0xffffu) * (uint32_t)(sizeof(rt::FlatMaterial) / 4u), tw = (lds_tables >> 16) * (uint32_t)(sizeof(rt::FlatTexture) / 4u);
     const uint32_t* const ms = (const uint32_t*)sv.materials;
     const uint32_t* const ts = (const uint32_t*)sv.textures;
@@ -325,7 +323,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
   walk_threshold &= 0xffffu;
   // this wave's ring of ready primary rays: f64 [RING_F64][64], then u32 [64] (sample index)
   double* const ring_f = (double*)((unsigned char*)(lds_stack + stack_levels * TRACE_BLOCK) +
-                                   (threadIdx.x >> 6) * RING_BYTES_PER_WAVE);
+                                   (threadIdx.x >> 6) * ring_bytes(64));
   uint32_t* const ring_g = (uint32_t*)(ring_f + RING_F64 * 64);
   uint32_t ring_n = 0;                    // wave-uniform: entries in the ring (a stack)
   const rt::FlatEntry& bvh = sv.entries[sv.top_level[bvh_pos]];
@@ -366,12 +364,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
           DIAG_ADD(1, wave_ballot(lane < m));
           if (lane < m) {
             const uint32_t gg = chunk_pos + lane;
-            uint32_t s_local = gg / npix;
-            uint32_t lp = gg - s_local * npix;
-            uint32_t i, j;
-            shard_pixel(sm, lp, &i, &j);
             rt::PathState fresh;
-            rt::path_begin(rp, i, j, s_begin + s_local, &fresh);
+            start_path(rp, sm, npix, s_begin, gg, &fresh);
             const uint32_t slot = ring_n + lane;
             ring_f[0 * 64 + slot] = fresh.ray.origin.x; ring_f[1 * 64 + slot] = fresh.ray.origin.y;
             ring_f[2 * 64 + slot] = fresh.ray.origin.z; ring_f[3 * 64 + slot] = fresh.ray.direction.x;
@@ -422,11 +416,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
         DIAG_ADD(1, wave_ballot(!active && rank < avail));
         if (!active && rank < avail) {
           g = chunk_pos + rank;
-          uint32_t s_local = g / npix;
-          uint32_t lp = g - s_local * npix;
-          uint32_t i, j;
-          shard_pixel(sm, lp, &i, &j);
-          rt::path_begin(rp, i, j, s_begin + s_local, &ps);
+          start_path(rp, sm, npix, s_begin, g, &ps);
           active = true;
         }
         chunk_pos += (n_need < avail) ? n_need : avail;
@@ -437,8 +427,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
     // ---- begin a bounce for every lane that is not in the middle of a carried-over walk
     if (active && !midwalk) {
       if (rt::path_bounce_begin(&ps)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+        store_sample(samples, g, ps.output);
         active = false;
       } else {
         q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
@@ -532,8 +521,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
         rec.mat = win_rect >> 2;
       } else if (hit) rt::prim_finalize<F>(sv, best.ref, ps.ray, best.t, &rec);
       if (rt::path_bounce_end<F, false>(sv, rp, &ps, hit, rec, nullptr)) {
-        double* o = samples + 3 * (size_t)g;
-        o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+        store_sample(samples, g, ps.output);
         active = false;
       }
     }

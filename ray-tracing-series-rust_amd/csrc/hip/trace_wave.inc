@@ -101,12 +101,8 @@ __global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::Rende
   const uint32_t g = (uint32_t)g64;
   const uint32_t P = pool.P;
   const uint32_t slot = pool.free_list[b * WF_SEG + k];
-  const uint32_t s_local = g / npix;
-  const uint32_t lp = g - s_local * npix;
-  uint32_t i, j;
-  shard_pixel(sm, lp, &i, &j);
   rt::PathState ps;
-  rt::path_begin(rp, i, j, s_begin + s_local, &ps);
+  start_path(rp, sm, npix, s_begin, g, &ps);
   const bool ended = rt::path_bounce_begin(&ps);  // world.rs:64-67 (max_depth >= 1: never at birth in f64)
   pool.ray[0 * (size_t)P + slot] = ps.ray.origin.x; pool.ray[1 * (size_t)P + slot] = ps.ray.origin.y; pool.ray[2 * (size_t)P + slot] = ps.ray.origin.z;
   pool.ray[3 * (size_t)P + slot] = ps.ray.direction.x; pool.ray[4 * (size_t)P + slot] = ps.ray.direction.y; pool.ray[5 * (size_t)P + slot] = ps.ray.direction.z;
@@ -265,8 +261,7 @@ __global__ __launch_bounds__(WF_SEG) void k_wf_shade(rt::SceneView sv, WavePool 
       }
     }
     if (ended) {
-      double* o = samples + 3 * (size_t)g;
-      o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
+      store_sample(samples, g, ps.output);
       pool.g[s] = WF_FREE;
     }
   }

@@ -238,10 +238,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     walk_root = root;
     first_ref = fref;
   };
-  auto write_sample = [&]() {
-    double* o = samples + 3 * (size_t)g;
-    o[0] = ps.output.x; o[1] = ps.output.y; o[2] = ps.output.z;
-  };
+  auto write_sample = [&]() { store_sample(samples, g, ps.output); };
   // a new ray starts its scan (world.rs:64-68: depth first)
   auto begin_bounce = [&]() {
     if (rt::path_bounce_begin(&ps)) { write_sample(); stage = WS_NEED; }
@@ -501,11 +498,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
           const uint32_t avail = chunk_end - chunk_pos;
           if (stage == WS_NEED && rank < avail) {
             g = chunk_pos + rank;
-            const uint32_t s_local = g / npix;
-            const uint32_t lp = g - s_local * npix;
-            uint32_t i, j;
-            shard_pixel(sm, lp, &i, &j);
-            rt::path_begin(rp, i, j, s_begin + s_local, &ps);
+            start_path(rp, sm, npix, s_begin, g, &ps);
             begin_bounce_fast();
           }
           chunk_pos += (n_want < avail) ? n_want : avail;
