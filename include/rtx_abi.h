@@ -209,11 +209,11 @@ typedef struct RtxRenderStats {
   int32_t trace_kernel; /* which trace kernel the launcher chose: RTX_KERNEL_* (rtx_trace_kernel_name) */
   int32_t reserved;
 } RtxRenderStats;
-/* Trace kernels (all produce identical results; the launcher picks by world shape and LDS budget).  Ids 2 and 5 are retired: their
-   kernels were removed and the launcher never reports them; the ids and names stay reserved. */
+/* Trace kernels (all produce identical results; the launcher picks by world shape and LDS budget).  Ids 1, 2 and 5 are retired:
+   their kernels were removed and the launcher never reports them; the ids and names stay reserved. */
 enum {
   RTX_KERNEL_SIMPLE = 0,     /* grid-stride, one whole path per thread (also the counting kernel) */
-  RTX_KERNEL_PERSISTENT = 1, /* persistent waves + path regeneration, wave-synchronous list scan; any world (A/B partner of WORLD) */
+  RTX_KERNEL_PERSISTENT = 1, /* retired: persistent waves + path regeneration, wave-synchronous list scan */
   RTX_KERNEL_STREAM = 2,     /* retired: stage-synchronous persistent kernel */
   RTX_KERNEL_VOTE = 3,       /* worlds that are one BVH: node/leaf voting walk, f32 culling, carry-over */
   RTX_KERNEL_LDS = 4,        /* RTX_KERNEL_VOTE with the geometry resident in LDS (sphere worlds that fit) */

@@ -193,7 +193,7 @@ struct SceneView {
   int32_t n_top_level;
   int32_t max_stack;  // deepest traversal stack any BVH of this scene needs
   uint32_t features;  // Feature bits the scene can reach
-  uint32_t pad;
+  uint32_t pad;       // padding to a multiple of 8 bytes
 };
 
 // Per-render constants.

@@ -429,19 +429,8 @@ RT_HD void bvh_closest(const SceneView& sv, int32_t root, uint32_t first_ref, co
   }
 }
 
-// How a BVH entry is walked.  SerialWalk is the portable one (CPU checker, simple kernels); the
-// device supplies a wave-cooperative walker (hip/render.hip VoteWalk).  Any walker must return the
-// closest hit under offer_prim's rule, so the choice is invisible in results.
-struct SerialWalk {
-  template <uint32_t F, bool COUNT, class STACK>
-  RT_HD static void run(const SceneView& sv, int32_t root, uint32_t first_ref, const Ray& r, real t_min,
-                        Closest* best, STACK& stack, TraceCounters* cnt) {
-    bvh_closest<F, COUNT>(sv, root, first_ref, r, t_min, best, stack, cnt);
-  }
-};
-
 // PRIM / GROUP / BVH entries: find the closest candidate in [t_min, t_max].
-template <uint32_t F, bool COUNT, class STACK, class WALK = SerialWalk>
+template <uint32_t F, bool COUNT, class STACK>
 RT_HD void geom_closest(const SceneView& sv, const FlatEntry& e, const Ray& r, real t_min,
                         real t_max, Closest* best, STACK& stack, TraceCounters* cnt) {
   best->t = t_max;
@@ -449,7 +438,7 @@ RT_HD void geom_closest(const SceneView& sv, const FlatEntry& e, const Ray& r, r
   best->ref = 0;
   best->order = 0;
   if ((F & F_BVH) && (e.kind == ENTRY_BVH || !(F & (F_PRIM_ENTRY | F_GROUP)))) {
-    WALK::template run<F, COUNT>(sv, e.a, (uint32_t)e.b, r, t_min, best, stack, cnt);
+    bvh_closest<F, COUNT>(sv, e.a, (uint32_t)e.b, r, t_min, best, stack, cnt);
     return;
   }
   if ((F & F_PRIM_ENTRY) && (e.kind == ENTRY_PRIM || !(F & F_GROUP))) {
@@ -521,7 +510,7 @@ RT_HD void xform_record_chain(const FlatXformOp* ops, int nops, const Ray& outer
 // A ConstantMedium asks its boundary twice (rec1 over (-inf, inf), rec2 from rec1.t + 0.0001),
 // then draws one uniform from the path's stream -- inside the intersection, exactly where
 // the reference draws it (hit.rs:969).
-template <uint32_t F, bool COUNT, class STACK, class WALK = SerialWalk>
+template <uint32_t F, bool COUNT, class STACK>
 RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, HitRecord* rec,
                      Rng& rng, STACK& stack, TraceCounters* cnt) {
   if (COUNT) cnt->rays++;
@@ -566,7 +555,7 @@ RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, 
     bool ok = true;
     const int n_query = is_medium ? 2 : 1;
     for (int q = 0; q < n_query; ++q) {
-      geom_closest<F, COUNT, STACK, WALK>(sv, geom_rec, rq, q_min, q_max, &best, stack, cnt);
+      geom_closest<F, COUNT>(sv, geom_rec, rq, q_min, q_max, &best, stack, cnt);
       if (!best.hit) { ok = false; break; }
       if (q == 0) { rec1_t = best.t; q_min = rec1_t + real(0.0001); }
     }

@@ -65,7 +65,7 @@ struct VoteTop {
 };
 
 // RTX_TRACE_KERNEL: the kernel family a render is forced to (none: choose_trace_kernel decides).
-enum class ForcedKernel { none, simple, persistent, vote, world, wavefront };
+enum class ForcedKernel { none, simple, vote, world, wavefront };
 
 // Every RTX_* switch of the launcher, read once per rtx_scene_upload by read_switches (DESIGN section 4 lists them).  A numeric
 // switch outside its range keeps the default; an on/off switch is off when set to anything atoi reads as 0.
@@ -74,7 +74,7 @@ struct TraceSwitches {
   bool diag = false;  // RTX_TRACE_KERNEL=vote_diag / world_diag: region counters on stderr (never timed)
   int ring = -1, wide = -1, scene_lds = -1;  // RTX_RING / RTX_WIDE / RTX_SCENE_LDS: 0 / 1 when set, -1 when not
   bool vote_top = true, tri_direct = true, mat_lds = true, perlin_lds = true;  // RTX_VOTE_TOP / _TRI_DIRECT / _MAT_LDS / _PERLIN_LDS
-  bool mv_common = true, motion = true, motion_axis = true, lds_wide = false;  // RTX_MV_COMMON / _MOTION / _MOTION_AXIS / _LDS_WIDE
+  bool mv_common = true, motion = true, motion_axis = true;  // RTX_MV_COMMON / _MOTION / _MOTION_AXIS
   bool single_leaf = true, pass_pipeline = true, validate = false;  // RTX_SINGLE_LEAF / _PASS_PIPELINE; RTX_VALIDATE: set at all
   uint32_t chunk = TRACE_CHUNK;  // RTX_CHUNK [64, 65536]: sample indices a k_trace_lds wave reserves per grab
   uint32_t world_threshold = 8;  // RTX_WORLD_THRESHOLD [0, 64]: k_trace_world's walk steps go first while this many lanes walk (0: majority)
@@ -117,12 +117,11 @@ struct VotePlan {
   size_t tables_bytes = 0;
 };
 
-// 4-wide culling tree (FlatNode4) of every BVH of the scene, for k_trace_vote, k_trace_persistent and k_trace_world.
+// 4-wide culling tree (FlatNode4) of every BVH of the scene, for k_trace_vote, k_trace_world and the wavefront integrator.
 struct WidePlan {
   FlatNode4Dev* nodes4 = nullptr;
   int levels = 0;                 // stack levels of a wide walk
   int vote_blocks_per_cu = 1;
-  int pers_blocks_per_cu[3] = {1, 1, 1};  // [preset]
 };
 
 // k_trace_world (trace_world.inc).
@@ -144,8 +143,6 @@ struct LdsFit {
 // k_trace_lds (trace_lds.inc): sphere worlds of one BVH whose geometry fits in LDS.
 struct LdsPlan {
   LdsFit plain;                   // the binary tree
-  LdsFit w4;                      // the 4-wide collapse of the tree (static worlds, RTX_LDS_WIDE=1) and its node image
-  const uint32_t* w4_image = nullptr;
   // time-aware boxes: chosen per render, when the camera's shutter lies inside the BVH's time interval [motion_t0, motion_t1]
   LdsFit motion;
   int motion_axis = -1;           // 0 / 1 / 2: every slope of the time-aware boxes is zero except along this axis (-1: no such axis)
@@ -154,7 +151,7 @@ struct LdsPlan {
   double mv_t0 = 0.0, mv_t1 = 1.0;
 };
 
-// Tuning of the voting walks (k_trace_vote, k_trace_lds, k_trace_world, k_trace_persistent, the wavefront integrator).
+// Tuning of the voting walks (k_trace_vote, k_trace_lds, k_trace_world, the wavefront integrator).
 struct WalkTuning {
   uint32_t walk_threshold = 18;   // 1 = never carry a walk over; 18 measured best on C2 (12..22 within 1 %)
   uint32_t regen_min = 1;         // wide k_trace_vote: lanes that must be waiting before the wave regenerates
@@ -171,7 +168,6 @@ struct DeviceScene {
   double gravity_time_limit = 1e300;  // scenes with GravitySpheres: the largest shutter time a render accepts
   TraceSwitches sw;
   Workspace ws;
-  int pers_blocks_per_cu[3] = {1, 1, 1};  // resident 256-thread blocks per CU for each preset's k_trace_persistent
   VotePlan vote;
   WidePlan wide;
   WorldPlan world;
@@ -272,7 +268,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 }
 
 // ------------------------------------------------------------------ kernels
-#include "trace_basic.inc"   // k_trace_simple, k_trace_persistent
+#include "trace_basic.inc"   // feature presets, k_trace_simple
 #include "trace_vote.inc"    // voting walk, 4-wide tree, k_trace_vote
 #include "trace_world.inc"   // k_trace_world: any world, per-lane scan of the world list with carried-over walks
 #include "trace_lds.inc"     // k_trace_lds (the headline kernel)
@@ -328,7 +324,6 @@ static TraceSwitches read_switches() {
   if (const char* k = getenv("RTX_TRACE_KERNEL")) {
     const std::string s = k;
     if (s == "simple") sw.kernel = ForcedKernel::simple;
-    else if (s == "persistent") sw.kernel = ForcedKernel::persistent;
     else if (s == "vote" || s == "vote_diag") sw.kernel = ForcedKernel::vote;
     else if (s == "world" || s == "world_diag") sw.kernel = ForcedKernel::world;
     else if (s == "wavefront") sw.kernel = ForcedKernel::wavefront;
@@ -338,7 +333,7 @@ static TraceSwitches read_switches() {
   sw.vote_top = flag("RTX_VOTE_TOP") != 0; sw.tri_direct = flag("RTX_TRI_DIRECT") != 0;
   sw.mat_lds = flag("RTX_MAT_LDS") != 0; sw.perlin_lds = flag("RTX_PERLIN_LDS") != 0;
   sw.mv_common = flag("RTX_MV_COMMON") != 0; sw.motion = flag("RTX_MOTION") != 0; sw.motion_axis = flag("RTX_MOTION_AXIS") != 0;
-  sw.lds_wide = flag("RTX_LDS_WIDE") == 1; sw.single_leaf = flag("RTX_SINGLE_LEAF") != 0; sw.pass_pipeline = flag("RTX_PASS_PIPELINE") != 0;
+  sw.single_leaf = flag("RTX_SINGLE_LEAF") != 0; sw.pass_pipeline = flag("RTX_PASS_PIPELINE") != 0;
   sw.validate = getenv("RTX_VALIDATE") != nullptr;
   sw.chunk = num("RTX_CHUNK", 64, 65536, sw.chunk);
   sw.world_threshold = num("RTX_WORLD_THRESHOLD", 0, 64, sw.world_threshold);
@@ -562,17 +557,17 @@ static void validate_wide_tree(const FlatScene& fs, const std::vector<FlatNode4>
 }
 
 // 4-wide culling tree (see FlatNode4) for every BVH of the scene: big triangle meshes under k_trace_vote (needs VotePlan::ok),
-// and any world that takes k_trace_persistent (Book-2: two BVHs walked per bounce, each step a dependent L2 fetch).
-// RTX_WIDE=0/1 overrides the size tests.
+// and any world but a sphere-only one that k_trace_world walks (Book-2: two BVHs walked per bounce, each step a dependent L2
+// fetch).  RTX_WIDE=0/1 overrides the size tests.
 static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
   WidePlan& p = ds->wide;
   const bool spheres_preset = (fs.features & ~P_SPHERES) == 0;
   const bool mesh_preset = !spheres_preset && (fs.features & ~P_MESH) == 0;
   const int preset = spheres_preset ? 0 : (mesh_preset ? 1 : 2);
   const bool for_vote = ds->vote.ok && mesh_preset;
-  const bool for_pers = !(ds->vote.ok && preset < 2) && preset >= 1;
-  bool want_wide = (for_vote && fs.nodes.size() >= 4096) || (for_pers && fs.nodes.size() >= 256);
-  if (ds->sw.wide >= 0) want_wide = (for_vote || for_pers) && ds->sw.wide != 0 && !fs.nodes.empty();
+  const bool for_world = !(ds->vote.ok && preset < 2) && preset >= 1;
+  bool want_wide = (for_vote && fs.nodes.size() >= 4096) || (for_world && fs.nodes.size() >= 256);
+  if (ds->sw.wide >= 0) want_wide = (for_vote || for_world) && ds->sw.wide != 0 && !fs.nodes.empty();
   if (!want_wide) return RTX_OK;
   std::vector<FlatNode4> wide(fs.nodes.size());
   memset(wide.data(), 0, wide.size() * sizeof(FlatNode4));
@@ -586,12 +581,6 @@ static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
     const int nb = occupancy(k_trace_vote<P_MESH, false, false, true>, lds);
     ok = nb > 0;
     if (ok) p.vote_blocks_per_cu = nb;
-  }
-  if (ok) {
-    const int n1 = occupancy(k_trace_persistent<P_MESH, true>, lds), n2 = occupancy(k_trace_persistent<P_ANY, true>, lds);
-    if (n1 > 0) p.pers_blocks_per_cu[1] = n1;
-    if (n2 > 0) p.pers_blocks_per_cu[2] = n2;
-    ok = n1 > 0 && n2 > 0;
   }
   if (ok) {
     rtx_status st = upload_array(ds, wide, &p.nodes4);
@@ -684,7 +673,7 @@ static void fit_lds(LdsFit* f, bool want_ring, uint32_t lds_max) {
     }
 }
 
-// The plain, 4-wide and time-aware variants for a sphere world of one BVH.  The record dims chosen here must match the
+// The plain and time-aware variants for a sphere world of one BVH.  The record dims chosen here must match the
 // instantiation launch_lds picks for the scene (UNI: trace_lds.inc).
 static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan& leaves) {
   const bool single_bvh = fs.top_level.size() == 1 && fs.entries[fs.top_level[0]].kind == rt::ENTRY_BVH;
@@ -727,26 +716,6 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
     const bool want_ring = sw.ring != 0;
     fit_lds(&p.plain, want_ring, (uint32_t)lds_max);
     const rt::FlatEntry& be = fs.entries[fs.top_level[0]];
-    // the 4-wide collapse of the tree
-    // Measured on C2 and NOT the default: 236 wide nodes, 5.05 steps per ray against 10.6, bit-identical -- and 2.4 % slower
-    // (5997 against 6143 Msamples/s): sorting four children by entry distance and four conditional stack writes make a wide
-    // step ~2.3 x a binary one, whose near / far order comes for free out of the address.  Kept as the A/B partner (RTX_LDS_WIDE=1).
-    if (p.plain.ok && sw.lds_wide) {
-      std::vector<uint32_t> image;
-      uint32_t n_wide = 0;
-      const uint32_t wl = build_lds_wide_image(fs.nodes, be.a, &image, &n_wide);
-      if (wl > 0u) {
-        p.w4.levels = wl;
-        p.w4.dims = p.plain.dims;
-        p.w4.dims.n_nodes = n_wide;
-        p.w4.dims.node_dwords = LDSK_WIDE_NODE_DWORDS;
-        fit_lds(&p.w4, want_ring, (uint32_t)lds_max);
-        if (p.w4.ok) {
-          rtx_status st = upload_array(ds, image, &p.w4_image);
-          if (st != RTX_OK) return st;
-        }
-      }
-    }
     // the time-aware instantiation: the world's one BVH holds moving spheres and came with an interval
     if (p.plain.ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && (double)be.f[0] < (double)be.f[1] && sw.motion) {
       p.motion_t0 = (double)be.f[0]; p.motion_t1 = (double)be.f[1];
@@ -757,17 +726,14 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
     // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
     // scenes uploaded earlier (with other LDS sizes) keep launching
     hipError_t ae = hipSuccess;
-#define LDS_ATTR(FEAT, RINGF, MOTIONF, W4F) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)k_trace_lds<FEAT, RINGF, MOTIONF, W4F>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
-    LDS_ATTR(P_SPHERES, true, 0u, false); LDS_ATTR(P_SPHERES, false, 0u, false); LDS_ATTR(P_STATIC_SPHERES, true, 0u, false); LDS_ATTR(P_STATIC_SPHERES, false, 0u, false);
-    LDS_ATTR(P_SPHERES, true, 1u, false); LDS_ATTR(P_SPHERES, false, 1u, false); LDS_ATTR(P_SPHERES, true, 3u, false); LDS_ATTR(P_SPHERES, false, 3u, false);
-    LDS_ATTR(P_SPHERES, true, 0u, true); LDS_ATTR(P_SPHERES, false, 0u, true); LDS_ATTR(P_STATIC_SPHERES, true, 0u, true); LDS_ATTR(P_STATIC_SPHERES, false, 0u, true);
+#define LDS_ATTR(FEAT, RINGF, MOTIONF) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)k_trace_lds<FEAT, RINGF, MOTIONF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
+    LDS_ATTR(P_SPHERES, true, 0u); LDS_ATTR(P_SPHERES, false, 0u); LDS_ATTR(P_STATIC_SPHERES, true, 0u); LDS_ATTR(P_STATIC_SPHERES, false, 0u);
+    LDS_ATTR(P_SPHERES, true, 1u); LDS_ATTR(P_SPHERES, false, 1u); LDS_ATTR(P_SPHERES, true, 3u); LDS_ATTR(P_SPHERES, false, 3u);
 #undef LDS_ATTR
     if (ae != hipSuccess) { (void)hipGetLastError(); p.plain.ok = false; }
   }
   if (sw.scene_lds >= 0) {
     auto bytes = [](const LdsFit& f) { return f.ok ? ldsk_layout(f.levels, f.ring_cap, f.dims).total : 0u; };
-    fprintf(stderr, "[rtx] RTX_SCENE_LDS: 4-wide tree %s (%u nodes, %u levels, ring of %u, %u B)\n", p.w4.ok ? "on" : "off",
-            p.w4.dims.n_nodes, p.w4.levels, p.w4.ring_cap, bytes(p.w4));
     fprintf(stderr, "[rtx] RTX_SCENE_LDS: k_trace_lds %s (ring of %u, %u B of LDS); time-aware boxes %s (ring of %u, %u B)\n",
             p.plain.ok ? "on" : "off", p.plain.ring_cap, ldsk_layout(levels, p.plain.ring_cap, p.plain.dims).total,
             p.motion.ok ? "on" : "off", p.motion.ring_cap, bytes(p.motion));
@@ -780,62 +746,29 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
   HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
   const bool motion = p.motion.ok && (double)cam->time1 >= p.motion_t0 && (double)cam->time2 <= p.motion_t1;
-  const bool w4 = !motion && p.w4.ok;
-  const LdsFit& f = motion ? p.motion : (w4 ? p.w4 : p.plain);
+  const LdsFit& f = motion ? p.motion : p.plain;
   const bool ring = f.ring_cap != 0u;
   const rt::real m_t0 = (rt::real)p.motion_t0, m_inv = (rt::real)(1.0 / (p.motion_t1 - p.motion_t0));
   const LdsKernelLayout L = ldsk_layout(f.levels, f.ring_cap, f.dims);
   const uint32_t grid = grid_size(a.total, LDSK_BLOCK, (uint64_t)ds->n_cu);
   const WalkTuning& wk = ds->walk;
-#define LAUNCH_LDS2(FEAT, RINGF, MOTIONF, W4F)                                                                          \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, W4F>), dim3(grid), dim3(LDSK_BLOCK), L.total, a.stream, \
+#define LAUNCH_LDS2(FEAT, RINGF, MOTIONF)                                                                               \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF>), dim3(grid), dim3(LDSK_BLOCK), L.total, a.stream, \
                      ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, wk.leaf_weight,       \
                      wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,    \
-                     m_t0, m_inv, p.w4_image, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1)
-#define LAUNCH_LDS(FEAT, MOTIONF, W4F) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF, W4F); } else { LAUNCH_LDS2(FEAT, false, MOTIONF, W4F); } } while (0)
+                     m_t0, m_inv, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1)
+#define LAUNCH_LDS(FEAT, MOTIONF) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF); } else { LAUNCH_LDS2(FEAT, false, MOTIONF); } } while (0)
   // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
-  if ((a.feat & ~P_STATIC_SPHERES) == 0) { if (w4) { LAUNCH_LDS(P_STATIC_SPHERES, 0u, true); } else { LAUNCH_LDS(P_STATIC_SPHERES, 0u, false); } }
-  else if (motion && p.motion_axis == 1) { LAUNCH_LDS(P_SPHERES, 3u, false); }  // slopes along y only (Book-1 at HEAD)
-  else if (motion) { LAUNCH_LDS(P_SPHERES, 1u, false); }
-  else if (w4) { LAUNCH_LDS(P_SPHERES, 0u, true); }
-  else { LAUNCH_LDS(P_SPHERES, 0u, false); }
+  if ((a.feat & ~P_STATIC_SPHERES) == 0) { LAUNCH_LDS(P_STATIC_SPHERES, 0u); }
+  else if (motion && p.motion_axis == 1) { LAUNCH_LDS(P_SPHERES, 3u); }  // slopes along y only (Book-1 at HEAD)
+  else if (motion) { LAUNCH_LDS(P_SPHERES, 1u); }
+  else { LAUNCH_LDS(P_SPHERES, 0u); }
 #undef LAUNCH_LDS
 #undef LAUNCH_LDS2
   return RTX_OK;
 }
 
-// ------------------------------------------------------------------ k_trace_persistent, k_trace_simple
-static void plan_persistent(DeviceScene* ds) {
-  const size_t lds = stack_bytes((uint32_t)ds->view.max_stack + 1u);
-  const int nb[3] = {occupancy(k_trace_persistent<P_SPHERES, false>, lds), occupancy(k_trace_persistent<P_MESH, false>, lds),
-                     occupancy(k_trace_persistent<P_ANY, false>, lds)};
-  for (int i = 0; i < 3; ++i)
-    if (nb[i] > 0) ds->pers_blocks_per_cu[i] = nb[i];
-}
-
-static rtx_status launch_persistent(DeviceScene* ds, const PassArgs& a) {
-  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
-  const bool wide = ds->wide.nodes4 && a.preset >= 1;
-  rt::SceneView v = ds->view;
-  v.pad = ds->walk.leaf_weight;
-  if (wide) v.nodes = (const rt::FlatNode*)ds->wide.nodes4;  // the wide tree rides in the slot of the (unused) f64 tree
-  const size_t lds = wide ? stack_bytes((uint32_t)ds->wide.levels) : a.stack_lds;
-  const int nb = wide ? ds->wide.pers_blocks_per_cu[a.preset] : ds->pers_blocks_per_cu[a.preset];
-  const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)nb);
-  const rt::SceneView& dv = ds->view;
-#define LAUNCH_PERSISTENT(FEAT, WIDEF)                                                                                   \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_persistent<FEAT, WIDEF>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, v, a.rp, \
-                     a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, dv.entries, dv.top_level, dv.spheres,  \
-                     dv.moving_spheres, dv.rects, dv.triangles, dv.materials, dv.textures, dv.refs)
-  if (wide && a.preset == 1) { LAUNCH_PERSISTENT(P_MESH, true); }
-  else if (wide) { LAUNCH_PERSISTENT(P_ANY, true); }
-  else if (a.preset == 0) { LAUNCH_PERSISTENT(P_SPHERES, false); }
-  else if (a.preset == 1) { LAUNCH_PERSISTENT(P_MESH, false); }
-  else { LAUNCH_PERSISTENT(P_ANY, false); }
-#undef LAUNCH_PERSISTENT
-  return RTX_OK;
-}
-
+// ------------------------------------------------------------------ k_trace_simple
 template <bool COUNT>
 static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
@@ -962,9 +895,8 @@ static int32_t choose_trace_kernel(const DeviceScene* ds, int preset, bool count
   if (count || k == ForcedKernel::simple) return RTX_KERNEL_SIMPLE;  // the counting kernel
   if (ds->lds.plain.ok && preset == 0 && k == ForcedKernel::none) return RTX_KERNEL_LDS;
   if (ds->vote.ok && preset < 2 && k == ForcedKernel::wavefront) return RTX_KERNEL_WAVEFRONT;
-  if (ds->vote.ok && preset < 2 && k != ForcedKernel::persistent && k != ForcedKernel::world) return RTX_KERNEL_VOTE;
-  if (k != ForcedKernel::persistent || (ds->view.features & rt::F_GRAVITY_SPHERE)) return RTX_KERNEL_WORLD;
-  return RTX_KERNEL_PERSISTENT;
+  if (ds->vote.ok && preset < 2 && k != ForcedKernel::world) return RTX_KERNEL_VOTE;
+  return RTX_KERNEL_WORLD;
 }
 
 // The slice of a frame's samples one call traces (progressive rendering, progressive.inc): the absolute sample indices
@@ -1132,8 +1064,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
         case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam); break;
         case RTX_KERNEL_WAVEFRONT: st = wave_pass(ds, a); break;
         case RTX_KERNEL_VOTE: st = launch_vote(ds, a); break;
-        case RTX_KERNEL_WORLD: st = launch_world(ds, a); break;
-        default: st = launch_persistent(ds, a); break;
+        default: st = launch_world(ds, a); break;  // RTX_KERNEL_WORLD
       }
       if (st != RTX_OK) return st;
       HIP_TRY(hipGetLastError());
@@ -1224,7 +1155,6 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   // one plan per kernel family; the order is their dependencies: wide tree <- vote, world <- wide, walk <- wide + lds
   ds->sw = read_switches();
   const LeafScan leaves = scan_leaves(fs);
-  plan_persistent(ds);
   plan_vote(ds, fs);
   if ((st = plan_wide(ds, fs)) != RTX_OK || (st = plan_world(ds, fs)) != RTX_OK || (st = plan_lds(ds, fs, leaves)) != RTX_OK) {
     free_device_scene(ds);

@@ -29,7 +29,6 @@
 #endif
 #define LDSK_MOTION_NODE_DWORDS 39u  // time-aware boxes: per child 9 planes + 9 slopes + the item (19), twice, + 1 of padding
 #define LDSK_MOTION1_NODE_DWORDS 27u  // ... when everything moves along ONE axis: per child 9 planes + that axis's 3 slopes + the item (13)
-#define LDSK_WIDE_NODE_DWORDS 27u    // 4-wide tree: 24 planes (FlatNode4's field-major layout) + four 16-bit items (2) + 1 of padding
 
 struct LdsKernelLayout {
   uint32_t off_ring, off_nodes, off_refs, off_spheres, off_moving, total;
@@ -67,106 +66,24 @@ __host__ __device__ __forceinline__ int32_t ldsk_item(int32_t child) {
   return (int32_t)(short)(unsigned short)(0x8000u | (rt::leaf_first(child) << 2) | (rt::leaf_count(child) - 1u));
 }
 
-// Host: the 4-wide collapse of the world's one BVH (build_wide_nodes, trace_vote.inc) as the exact dwords k_trace_lds<.., W4>
-// copies into LDS: wide nodes renumbered in depth-first order from 0 (the root), per node FlatNode4's 24 plane floats, then the
-// four children as 16-bit work items (node: its new index; leaf: 0x8000 | first_slot << 2 | count - 1; empty slot: 0xFFFF), then a
-// dword of padding (odd stride: a wave's unrelated nodes spread over the LDS banks).  Returns the stack levels a walk needs, 0 when
-// the tree does not fit the 16-bit encoding.
-static uint32_t build_lds_wide_image(const std::vector<rt::FlatNode>& nodes, int32_t root, std::vector<uint32_t>* image, uint32_t* n_wide) {
-  std::vector<FlatNode4> wide(nodes.size());
-  memset((void*)wide.data(), 0, wide.size() * sizeof(FlatNode4));
-  const int peak = build_wide_nodes(nodes, root, &wide);
-  std::vector<int32_t> new_id(nodes.size(), -1), order;
-  std::vector<int32_t> todo{root};
-  while (!todo.empty()) {
-    const int32_t n = todo.back();
-    todo.pop_back();
-    new_id[(size_t)n] = (int32_t)order.size();
-    order.push_back(n);
-    for (int k = 3; k >= 0; --k)
-      if (wide[(size_t)n].child[k] >= 0 && wide[(size_t)n].child[k] != WALK_DONE) todo.push_back(wide[(size_t)n].child[k]);
-  }
-  if (order.size() > LDSK_MAX_NODES) return 0u;
-  image->assign(order.size() * LDSK_WIDE_NODE_DWORDS, 0u);
-  for (size_t i = 0; i < order.size(); ++i) {
-    const FlatNode4& w = wide[(size_t)order[i]];
-    uint32_t* d = image->data() + i * LDSK_WIDE_NODE_DWORDS;
-    memcpy(d, w.lo, 12 * sizeof(float));
-    memcpy(d + 12, w.hi, 12 * sizeof(float));
-    uint32_t items[4];
-    for (int k = 0; k < 4; ++k) {
-      const int32_t c = w.child[k];
-      int32_t item;
-      if (c == WALK_DONE) item = -1;
-      else if (c >= 0) item = new_id[(size_t)c];
-      else {
-        if (rt::leaf_first(c) + rt::leaf_count(c) > LDSK_MAX_SLOTS || rt::leaf_count(c) > 4u) return 0u;
-        item = ldsk_item(c);
-      }
-      items[k] = (uint32_t)item & 0xFFFFu;
-    }
-    d[24] = items[0] | (items[1] << 16);
-    d[25] = items[2] | (items[3] << 16);
-  }
-  *n_wide = (uint32_t)order.size();
-  return (uint32_t)peak + 1u;
-}
-
-// One 4-wide step on the LDS copy (cf. walk_node_step4): the four child boxes against the ray, the hit ones pushed so that the
-// nearest ends on top, then popped.  `wofs` = wide_sign_pack of the ray: per axis the byte offset of the near planes' float4.
-__device__ __forceinline__ void ldsk_wide_step(const uint32_t* lds_nodes, const rt::Ray32& q, uint32_t wofs, float t_max32, int32_t* cur, LdsStack16& stack) {
-  const unsigned char* base = (const unsigned char*)(lds_nodes + (uint32_t)*cur * LDSK_WIDE_NODE_DWORDS);
-  const uint32_t ox = wofs & 0xffu, oy = (wofs >> 8) & 0xffu, oz = wofs >> 16;
-  const float *nx = (const float*)(base + ox), *fx = (const float*)(base + (48u - ox));
-  const float *ny = (const float*)(base + oy), *fy = (const float*)(base + (80u - oy));
-  const float *nz = (const float*)(base + oz), *fz = (const float*)(base + (112u - oz));
-  const uint32_t w0 = *(const uint32_t*)(base + 96), w1 = *(const uint32_t*)(base + 100);
-  const int32_t c0 = (int32_t)(short)(w0 & 0xffffu), c1 = (int32_t)(short)(w0 >> 16), c2 = (int32_t)(short)(w1 & 0xffffu), c3 = (int32_t)(short)(w1 >> 16);
-  float k0, k1, k2, k3;
-  const bool h0 = slab_interval_nf(nx[0], fx[0], ny[0], fy[0], nz[0], fz[0], q, t_max32, &k0) && c0 != LDSK_DONE;
-  const bool h1 = slab_interval_nf(nx[1], fx[1], ny[1], fy[1], nz[1], fz[1], q, t_max32, &k1) && c1 != LDSK_DONE;
-  const bool h2 = slab_interval_nf(nx[2], fx[2], ny[2], fy[2], nz[2], fz[2], q, t_max32, &k2) && c2 != LDSK_DONE;
-  const bool h3 = slab_interval_nf(nx[3], fx[3], ny[3], fy[3], nz[3], fz[3], q, t_max32, &k3) && c3 != LDSK_DONE;
-  const float inf = __builtin_huge_valf();
-  k0 = h0 ? k0 : inf; k1 = h1 ? k1 : inf; k2 = h2 ? k2 : inf; k3 = h3 ? k3 : inf;
-  // rank = number of children that come before this one (ties: lower slot first); hits rank 0 .. nh-1
-  const int b10 = k1 < k0, b20 = k2 < k0, b30 = k3 < k0, b21 = k2 < k1, b31 = k3 < k1, b32 = k3 < k2;
-  const int r0 = b10 + b20 + b30;
-  const int r1 = (1 - b10) + b21 + b31;
-  const int r2 = (1 - b20) + (1 - b21) + b32;
-  const int r3 = (1 - b30) + (1 - b31) + (1 - b32);
-  const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
-  const int top = stack.n + nh - 1;  // the nearest hit goes here
-  if (h0) stack.base[(top - r0) * LDSK_BLOCK] = (unsigned short)c0;
-  if (h1) stack.base[(top - r1) * LDSK_BLOCK] = (unsigned short)c1;
-  if (h2) stack.base[(top - r2) * LDSK_BLOCK] = (unsigned short)c2;
-  if (h3) stack.base[(top - r3) * LDSK_BLOCK] = (unsigned short)c3;
-  stack.n += nh;
-  *cur = stack.pop();
-}
-
-// W4: the culling tree in LDS is the 4-wide collapse (build_lds_wide_image): half the node steps per ray (Book-1: 5.05 against
-// 10.6), each testing four boxes and sorting the hit children by entry distance.  Measured 2.4 % SLOWER than the binary tree on
-// C2 (render.hip, where the launcher decides): the A/B partner, RTX_LDS_WIDE=1.
 // MOTION: time-aware culling boxes (core/flat_types.hpp: FlatMotion32).  Every plane of a child block is followed, 36 bytes on, by
 // its slope over the BVH's time interval, and a node step evaluates plane + s * slope (one fma) with the ray's own normalised
 // time s before the slab test.  Only launched when the camera's shutter lies inside that interval (render.hip).
 // MOTION = 1: slopes for every axis; MOTION = 2 + a: every moving sphere of the scene moves along axis a alone (Book-1 at HEAD: y), so only
 // that axis's planes carry slopes -- 4 fmas and 4 LDS dwords per child pair instead of 12 and 12, node records of 27 dwords.
-template <uint32_t F, bool RING, uint32_t MOTION, bool W4>
+template <uint32_t F, bool RING, uint32_t MOTION>
 __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::RenderParams rp, ShardMap sm,
                                                           uint32_t s_begin, uint32_t total, uint32_t npix,
                                                           double* __restrict__ samples, unsigned int* work_counter,
                                                           uint32_t leaf_weight, uint32_t walk_threshold, uint32_t chunk, uint32_t ring_cap,
                                                           uint32_t stack_levels, LdsSceneDims dims, rt::real motion_t0, rt::real motion_inv_dt,
-                                                          const uint32_t* __restrict__ wide_image, uint32_t mv_common, rt::real mv_t0, rt::real mv_t1) {
+                                                          uint32_t mv_common, rt::real mv_t0, rt::real mv_t1) {
   static_assert(!MOTION || (F & rt::F_MOVING_SPHERE), "time-aware boxes only make sense with moving spheres");
   // the launcher packs two small numbers into one kernel argument: bits 0-7 the walk threshold, bit 8 "every leaf holds one primitive"
   const bool single_leaf = (walk_threshold & 0x100u) != 0u;
   walk_threshold &= 0xFFu;
   constexpr bool UNI = (F & rt::F_MOVING_SPHERE) != 0;               // static spheres as moving spheres that stand still (see the copy below)
   constexpr uint32_t FL = UNI ? (F & ~rt::F_SPHERE) : F;             // what the leaf tests and the HitRecord are compiled for
-  static_assert(!(MOTION && W4), "the 4-wide LDS tree has no time-aware form yet");
   static_assert(MOTION <= 4u, "0: no slopes, 1: all axes, 2 + a: axis a only");
   constexpr uint32_t ND = MOTION == 1u ? LDSK_MOTION_NODE_DWORDS : (MOTION >= 2u ? LDSK_MOTION1_NODE_DWORDS : LDSK_NODE_DWORDS);  // dwords per LDS node record
   constexpr uint32_t CBD = MOTION == 1u ? 19u : (MOTION >= 2u ? 13u : 10u);                                                    // dwords per child block
@@ -179,7 +96,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   const LdsKernelLayout L = ldsk_layout(stack_levels, RING ? ring_cap : 0u, dims);
   const uint32_t lane = threadIdx.x & 63u;
   const rt::FlatEntry& bvh = sv.entries[sv.top_level[0]];
-  const int32_t root = W4 ? 0 : (bvh.a | (sv.nodes32[bvh.a].axis << 13));
+  const int32_t root = bvh.a | (sv.nodes32[bvh.a].axis << 13);
   const uint32_t first_ref = (uint32_t)bvh.b;
 
   // ---- geometry -> LDS
@@ -194,9 +111,6 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
     // ray on a` -- no min / max to sort the planes (core/cull32.hpp: cull32_may_hit_nf) -- and the child's work item at dword 9.
     const uint32_t* src = (const uint32_t*)sv.nodes32;
     const uint32_t* msrc = (const uint32_t*)sv.motion32;  // FlatMotion32: lo0[2][3] at 0, hi0 at 6, dlo at 12, dhi at 18
-    if (W4) {  // the host prepared the image dword for dword
-      for (uint32_t k = threadIdx.x; k < dims.n_nodes * LDSK_WIDE_NODE_DWORDS; k += LDSK_BLOCK) lds_nodes[k] = wide_image[k];
-    } else
     for (uint32_t k = threadIdx.x; k < dims.n_nodes * 2u * CBD; k += LDSK_BLOCK) {
       const uint32_t node = k / (2u * CBD), field = k - node * (2u * CBD);
       const uint32_t c = field / CBD, r = field - c * CBD;
@@ -359,9 +273,9 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
         active = false;
       } else {
         q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
-        dir_neg = W4 ? wide_sign_pack(ps.ray) : rt::ray_dir_neg(ps.ray);  // wide walks keep their plane offsets in this register
+        dir_neg = rt::ray_dir_neg(ps.ray);
         off_x = (dir_neg & 1u) << 2; off_y = 12u + ((dir_neg & 2u) << 1); off_z = 24u + (dir_neg & 4u);
-        if (!W4) flip_b = ((dir_neg & 1u) * CB) | (((dir_neg >> 1) & 1u) * (CB << 8)) | (((dir_neg >> 2) & 1u) * (CB << 16));
+        flip_b = ((dir_neg & 1u) * CB) | (((dir_neg >> 1) & 1u) * (CB << 8)) | (((dir_neg >> 2) & 1u) * (CB << 16));
         t_max32 = __builtin_huge_valf();
         if (UNI && mv_common != 0u) mv_ratio = (ps.ray.time - mv_t0) / (mv_t1 - mv_t0);
         if (MOTION) s32 = __builtin_fminf(__builtin_fmaxf((float)((ps.ray.time - motion_t0) * motion_inv_dt), 0.f), 1.f);
@@ -436,14 +350,10 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
       const uint32_t n_node = (uint32_t)__popcll(wave_ballot(is_node)), n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
       if (n_node + n_leaf < threshold) break;
       if (n_node * leaf_weight >= n_leaf) {
-        if (W4) {
-          if (is_node) ldsk_wide_step(lds_nodes, q, dir_neg, t_max32, &cur, stack);
-        } else {
-          if (is_node) node_step();
+        if (is_node) node_step();
 #if LDSK_NODE_BURST >= 2
-          if (cur >= 0) node_step();  // a second node step without a vote in between (the lanes that left for a leaf sit it out)
+        if (cur >= 0) node_step();  // a second node step without a vote in between (the lanes that left for a leaf sit it out)
 #endif
-        }
       } else {
         if (is_leaf) {
           const uint32_t f = ((uint32_t)cur & 0x7FFFu) >> 2;

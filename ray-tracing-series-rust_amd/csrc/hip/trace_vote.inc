@@ -1,5 +1,5 @@
-// The voting walk: node / leaf steps, the 4-wide culling tree, the walker policy of the persistent kernel and
-// k_trace_vote (included by render.hip, namespace rtx).
+// The voting walk: node / leaf steps, the 4-wide culling tree and k_trace_vote (included by render.hip,
+// namespace rtx).
 
 // ---- wave-synchronous BVH walk with deferred leaves --------------------------------------------
 // In bvh_step a leaf child is intersected inline, i.e. inside a branch only the lanes that reached
@@ -241,42 +241,11 @@ __device__ __forceinline__ void walk_node_step4(const FlatNode4* __restrict__ no
   }
 }
 
-// The voting walk as a world_hit walker policy (core/geometry.hpp): every lane that reaches a BVH
-// entry walks it together with the rest of its wave.  Top-level entry kinds are the same for all
-// lanes, so the enclosing control flow is wave-uniform up to lanes that already missed.
-template <bool WIDE>
-struct VoteWalkT {
-  template <uint32_t F, bool COUNT, class STACK>
-  __device__ __forceinline__ static void run(const rt::SceneView& sv, int32_t root, uint32_t first_ref,
-                                             const rt::Ray& r, rt::real t_min, rt::Closest* best, STACK& stack,
-                                             rt::TraceCounters*) {
-    rt::Ray32 q = rt::make_ray32(r, t_min);
-    const uint32_t dir_neg = WIDE ? wide_sign_pack(r) : rt::ray_dir_neg(r);  // wide walks keep their plane offsets in the same register
-    float t_max32 = rt::cull_round_up(best->t);
-    stack.reset();
-    int32_t cur = root;
-    const uint32_t leaf_weight = sv.pad ? sv.pad : 3u;  // the launcher passes the vote weight in SceneView.pad
-    for (;;) {
-      bool is_leaf = cur < 0;
-      bool is_node = !is_leaf && cur != WALK_DONE;
-      unsigned long long m_node = wave_ballot(is_node), m_leaf = wave_ballot(is_leaf);
-      if ((m_node | m_leaf) == 0ull) break;
-      if ((uint32_t)__popcll(m_node) * leaf_weight >= (uint32_t)__popcll(m_leaf)) {
-        if (is_node) {
-          if (WIDE) walk_node_step4((const FlatNode4*)sv.nodes, q, dir_neg, t_max32, &cur, stack);
-          else walk_node_step32(sv.nodes32[cur], q, dir_neg, t_max32, &cur, stack);
-        }
-      } else {
-        if (is_leaf) {
-          walk_leaf_step<F>(sv, first_ref, r, t_min, best, &cur, stack);
-          t_max32 = rt::cull_round_up(best->t);
-        }
-      }
-    }
-  }
-};
-
-// k_trace_persistent with the deferred-leaf walk, for worlds that are one BVH.
+// Persistent waves with path regeneration and the deferred-leaf walk, for worlds that are one BVH.  Waves pull
+// TRACE_CHUNK-item chunks of the pass's index space (pass_items.inc) from a global counter and hand items to their lanes
+// as lanes finish paths: the lanes without a path are compacted with a 64-bit __ballot and ranked with mbcnt (the
+// wavefront prefix sum), and take consecutive items (= consecutive pixels of one sample: coherent camera rays).  A lane
+// therefore never idles while the queue has work, whatever the length of its neighbours' paths.
 // DIAG: per-region occupancy counters (diag[2k] = times the wave executed region k, diag[2k+1] = lanes
 // active in it); regions: 0 outer iteration, 1 regenerate, 2 node step, 3 leaf step, 4 shade (hit lanes),
 // 5 shade (all walking lanes).  Diagnostic build only (RTX_TRACE_KERNEL=vote_diag); never timed.

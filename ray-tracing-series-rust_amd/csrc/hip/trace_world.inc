@@ -2,9 +2,9 @@
 //
 // HittableList::hit (hit.rs:660-690) scans the world's entries in order; in the reference's big scenes two of those
 // entries are BVHs (Book-2: 400 boxes, and the 1000-sphere cube under Translate(RotateY(..))) and the rest are plain
-// primitives and media.  k_trace_persistent runs that scan wave-synchronously: every lane of the wave is at the same
-// entry, so each BVH walk lasts as long as the wave's slowest ray -- twice per bounce (measured on Book-2: 30 % of the
-// VALU lanes busy).  Here the scan is a per-lane state machine, so that walks can be carried over exactly as
+// primitives and media.  world_hit (core/geometry.hpp) runs that scan wave-synchronously: every lane of the wave is at
+// the same entry, so each BVH walk lasts as long as the wave's slowest ray -- twice per bounce (measured on Book-2 in the
+// since-removed k_trace_persistent: 30 % of the VALU lanes busy).  Here the scan is a per-lane state machine, so that walks can be carried over exactly as
 // k_trace_vote carries them over within one BVH:
 //
 //   ENTRY(e)  the lane must process world entry e next        WALK(e)  its ray is inside the BVH of entry e

@@ -31,7 +31,7 @@ def test_library_is_in_tree_and_links_hip(rtsr):
     assert rtsr.LIB_PATH.startswith(ROOT) and os.path.exists(rtsr.LIB_PATH)
     blob = open(rtsr.LIB_PATH, "rb").read()
     assert b"amdgcn-amd-amdhsa--gfx950" in blob  # carries a gfx950 code object
-    assert b"k_trace_persistent" in blob
+    assert b"_ZN3rtx11k_trace_lds" in blob  # a trace kernel's mangled symbol: the code object carries the kernels
 
 
 def test_config_new_asserts(rtsr):  # world.rs:36-40
@@ -118,19 +118,20 @@ def test_no_cpu_fallback_without_gpu(rtsr):
 
 
 def test_trace_kernel_names_retired_ids(rtsr):
-    """RtxRenderStats.trace_kernel ids map to the kernel names rocprofv3 prints.  Ids 2 and 5 (k_trace_stream, k_trace_wq) are
-    retired: their kernels were removed, their names stay reserved, and no launcher source can report them."""
+    """RtxRenderStats.trace_kernel ids map to the kernel names rocprofv3 prints.  Ids 1, 2 and 5 (k_trace_persistent,
+    k_trace_stream, k_trace_wq) are retired: their kernels were removed, their names stay reserved, and no launcher source can
+    report them."""
     names = [rtsr.trace_kernel_name(k) for k in range(8)]
     assert names == ["k_trace_simple", "k_trace_persistent", "k_trace_stream", "k_trace_vote", "k_trace_lds", "k_trace_wq", "k_trace_world", "k_wf_trace"]
     assert rtsr.trace_kernel_name(99) == "?"
     hip_dir = os.path.join(ROOT, "ray-tracing-series-rust_amd", "csrc", "hip")
     sources = [open(os.path.join(hip_dir, f)).read() for f in os.listdir(hip_dir) if f.endswith((".hip", ".inc"))]
-    retired = {2, 5}  # RTX_KERNEL_STREAM, RTX_KERNEL_WQ (rtx_abi.h)
+    retired = {1, 2, 5}  # RTX_KERNEL_PERSISTENT, RTX_KERNEL_STREAM, RTX_KERNEL_WQ (rtx_abi.h)
     for k, n in enumerate(names):  # every name the launcher can report is a kernel that exists in the sources
         if k not in retired:
             assert any(n in src for src in sources), n
     for src in sources:  # the retired ids: their kernels are gone, and no launcher source can report them
-        assert "RTX_KERNEL_STREAM" not in src and "RTX_KERNEL_WQ" not in src
+        assert "RTX_KERNEL_PERSISTENT" not in src and "RTX_KERNEL_STREAM" not in src and "RTX_KERNEL_WQ" not in src
 
 
 def test_product_never_touches_the_oracle():

@@ -125,10 +125,9 @@ def test_shared_objects_on_the_device(rtsr, orc):
             assert np.array_equal(screen.rgb8, r1), (name, kw)
 
 
-@pytest.mark.parametrize("env", [{}, {"RTX_TRACE_KERNEL": "simple"}, {"RTX_TRACE_KERNEL": "persistent"}, {"RTX_WIDE": "1"}],
-                         ids=["default", "simple", "persistent", "wide"])
+@pytest.mark.parametrize("env", [{}, {"RTX_TRACE_KERNEL": "simple"}, {"RTX_WIDE": "1"}], ids=["default", "simple", "wide"])
 def test_axis_aligned_triangles_on_the_device(rtsr, orc, monkeypatch, env):
-    """Zero-thickness leaf boxes through every walker (f64 boxes: simple; f32 culling: vote / persistent; 4-wide)."""
+    """Zero-thickness leaf boxes through every walker (f64 boxes: simple; f32 culling: the default voting walk; 4-wide)."""
     from test_oracle_pairs import axis_aligned_world
     cam = rtsr.Camera.new((0.5, 3.0, 9.0), (0.0, 0.3, 0.0), (0.0, 1.0, 0.0), 55.0, 1.5, 0.0, 9.0, 0.0, 1.0)
     cfg = rtsr.Config.new(1.5, 96, 4, 8, 4, seed=3, background=(0.6, 0.7, 0.9))

@@ -42,7 +42,7 @@ def test_every_walker_through_a_gpu_built_tree(rtsr, monkeypatch):
     cfg = rtsr.Config.new(16.0 / 9.0, 96, 4, 50, 10, seed=6, background=bg)
     expect = flat_host.upload().render(cam, cfg)
     flat_gpu = b.flatten(world, gpu_builder=True)
-    for env in ({}, {"RTX_WIDE": "0"}, {"RTX_WIDE": "1"}, {"RTX_TRACE_KERNEL": "simple"}, {"RTX_TRACE_KERNEL": "world"}, {"RTX_TRACE_KERNEL": "persistent"}):
+    for env in ({}, {"RTX_WIDE": "0"}, {"RTX_WIDE": "1"}, {"RTX_TRACE_KERNEL": "simple"}, {"RTX_TRACE_KERNEL": "world"}):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         got = flat_gpu.upload().render(cam, cfg)
