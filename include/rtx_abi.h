@@ -296,16 +296,55 @@ int32_t rtx_progressive_spp(const rtx_progressive* p); /* samples per pixel so f
 /* Asynchronous on hip_stream (NULL = default stream) unless stats != NULL, as rtx_render_device.  1 <= n_samples <=
  * budget - spp_done.  A failed add leaves the handle unusable (every later call returns RTX_EINVAL). */
 rtx_status rtx_progressive_add(rtx_progressive* p, int32_t n_samples, void* hip_stream, RtxRenderStats* stats);
-/* Blocking.  out->accum_rgb (S), out->rgb8 (tone-mapped at spp_done) and sumsq_rgb (Q) are each optional host buffers of
- * rows*w*3 elements in rtx_render_device's shard layout.  Needs spp_done >= 1. */
+/* Blocking.  out->accum_rgb (S), out->rgb8 (tone-mapped at spp_done; once a pixel has retired -- adaptive rounds below --
+ * each pixel at its own count n_p) and sumsq_rgb (Q) are each optional host buffers of rows*w*3 elements in
+ * rtx_render_device's shard layout.  Needs spp_done >= 1. */
 rtx_status rtx_progressive_read(const rtx_progressive* p, RtxFrame* out, double* sumsq_rgb);
 /* Blocking.  Per active pixel and channel, with n = spp_done >= 2:  m = S/n,  var = max(0, (Q - S*S/n) / (n - 1)),
  * se = sqrt(var / n),  r_c = se / (m + 1/256);  the pixel's r = max_c r_c.  Reports max r, mean r and the count of
- * r > target_rel_err (>= 0), reduced in a fixed order: the same bits on every call. */
+ * r > target_rel_err (>= 0), reduced in a fixed order: the same bits on every call.  Once a pixel has retired (adaptive
+ * rounds below), each pixel's r is taken at its own count n_p. */
 rtx_status rtx_progressive_stats(rtx_progressive* p, double target_rel_err, RtxNoiseStats* out);
 /* Blocking.  Adds `batch` samples at a time (the last batch clipped to the budget) and stops at the first batch boundary
  * where pixels_above == 0 (checked on entry too once spp_done >= 2), or at the budget.  out: the last stats. */
 rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double target_rel_err, RtxNoiseStats* out);
+
+/* Adaptive sampling: pixels that reach the target stop receiving samples.  An adaptive ROUND of n samples does two things:
+ *  1. Retirement check, only when spp_done >= max(2, min_spp): every still-active pixel gets its r (the formula of
+ *     rtx_progressive_stats, n = spp_done); a pixel with r <= target_rel_err RETIRES: its count n_p is frozen at spp_done and
+ *     it never receives another sample (its S and Q no longer change, so it stays retired).
+ *  2. Tracing: the absolute samples [spp_done, spp_done + n) of the still-active pixels only (spp_done then advances by n,
+ *     even when no pixel is active).
+ * Every active pixel therefore holds spp_done samples, and a pixel that stopped at n_p holds exactly the bits a uniform
+ * render at n_p spp gives it.  The first adaptive call allocates 4 * (2 * pixels + pixels of the shard) bytes and a little
+ * scratch; until a pixel retires, the handle behaves as a uniform one.  Once one has, rtx_progressive_add and
+ * rtx_progressive_until return RTX_EINVAL (they would leave a gap in the retired pixels' sample indices);
+ * rtx_progressive_read, _stats and _pixel_spp take each pixel at its own n_p.
+ * Argument errors (NULL handle, n_samples or batch <= 0, min_spp < 2 or above the budget, a negative or NaN target, past the
+ * budget) are reported before any device call. */
+typedef struct RtxAdaptiveStats {
+  int32_t spp_done;       /* samples of every still-active pixel */
+  int32_t min_spp;        /* the rule's min_spp and target, as passed */
+  int32_t pixels;         /* pixels of the shard (row_chunk_compat's skipped rows excluded) */
+  int32_t pixels_active;  /* of which not retired */
+  int32_t pixels_above;   /* pixels whose r > target_rel_err, each at its own n_p */
+  int32_t reserved;
+  uint64_t samples;       /* sum of n_p over the pixels: the (pixel, sample) paths the frame holds */
+  double max_rel_err, mean_rel_err;  /* of r, each pixel at its own n_p; reduced in a fixed order (the same bits every call) */
+  double target_rel_err;
+} RtxAdaptiveStats;
+/* One adaptive round (1 <= n_samples <= budget - spp_done).  The retirement check blocks (the host needs the count of the
+ * pixels left); the tracing is asynchronous on hip_stream unless stats != NULL, as rtx_progressive_add.  stats->samples:
+ * the paths this round traced. */
+rtx_status rtx_progressive_add_adaptive(rtx_progressive* p, int32_t n_samples, int32_t min_spp, double target_rel_err,
+                                        void* hip_stream, RtxRenderStats* stats);
+/* Blocking.  Rounds of `batch` samples (the last one clipped to the budget) until no pixel is active; at the budget, a final
+ * retirement check, so that out describes the finished frame. */
+rtx_status rtx_progressive_until_adaptive(rtx_progressive* p, int32_t batch, int32_t min_spp, double target_rel_err,
+                                          RtxAdaptiveStats* out);
+/* Blocking.  spp: a host buffer of rows*w counts in rtx_render_device's shard layout -- n_p of every pixel (spp_done for one
+ * still active, and for every pixel of a handle that never ran an adaptive round); rows skipped by row_chunk_compat get 0. */
+rtx_status rtx_progressive_pixel_spp(const rtx_progressive* p, int32_t* spp);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

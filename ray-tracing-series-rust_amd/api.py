@@ -91,6 +91,12 @@ class RtxNoiseStats(C.Structure):
                 ("max_rel_err", C.c_double), ("mean_rel_err", C.c_double), ("target_rel_err", C.c_double)]
 
 
+class RtxAdaptiveStats(C.Structure):
+    _fields_ = [("spp_done", C.c_int32), ("min_spp", C.c_int32), ("pixels", C.c_int32), ("pixels_active", C.c_int32),
+                ("pixels_above", C.c_int32), ("reserved", C.c_int32), ("samples", C.c_uint64),
+                ("max_rel_err", C.c_double), ("mean_rel_err", C.c_double), ("target_rel_err", C.c_double)]
+
+
 # Every symbol include/rtx_abi.h declares: (restype, argtypes).  tests/test_abi_symbols.py checks
 # this table against the header and against the loaded library.
 _D3 = C.POINTER(C.c_double)
@@ -164,6 +170,9 @@ ABI = {
     "rtx_progressive_read": (C.c_int32, [_VP, C.POINTER(RtxFrame), _D3]),
     "rtx_progressive_stats": (C.c_int32, [_VP, C.c_double, C.POINTER(RtxNoiseStats)]),
     "rtx_progressive_until": (C.c_int32, [_VP, C.c_int32, C.c_double, C.POINTER(RtxNoiseStats)]),
+    "rtx_progressive_add_adaptive": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_double, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_progressive_until_adaptive": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_double, C.POINTER(RtxAdaptiveStats)]),
+    "rtx_progressive_pixel_spp": (C.c_int32, [_VP, C.POINTER(C.c_int32)]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -473,6 +482,8 @@ class Progressive:
 
     After k samples, however they were split into add() calls, screen() and moments() are bit-identical to a one-shot
     render at k spp.  Holds a reference to its Scene, which must not render on another stream while this one does.
+    add_adaptive() / until_adaptive() stop tracing the pixels that reach a target error (rtx_abi.h gives the rule); a pixel
+    that stopped at n_p samples (pixel_spp()) then holds the bits of a one-shot render at n_p spp.
     """
 
     def __init__(self, scene, cam, cfg, shard=None):
@@ -500,7 +511,7 @@ class Progressive:
         return stats
 
     def screen(self, want_accum=True):
-        """The frame at the current sample count, as Scene.render returns it."""
+        """The frame at the current sample count, as Scene.render returns it (each pixel tone-mapped at its own count)."""
         accum = np.zeros((self.height, self.width, 3), dtype=np.float64) if want_accum else None
         rgb8 = np.zeros((self.height, self.width, 3), dtype=np.uint8)
         frame = RtxFrame(accum.ctypes.data_as(_D3) if want_accum else None, rgb8.ctypes.data_as(C.POINTER(C.c_uint8)))
@@ -524,6 +535,26 @@ class Progressive:
         """Add `batch` samples at a time until no pixel's relative error exceeds the target, or the budget is spent."""
         out = RtxNoiseStats()
         _check(lib.rtx_progressive_until(self._p, batch, target_rel_err, C.byref(out)))
+        return out
+
+    def add_adaptive(self, n, min_spp, target_rel_err, stream=0, want_stats=False):
+        """One adaptive round: retire the pixels at or below the target (once spp_done >= min_spp), then trace the next n
+        samples of the others."""
+        stats = RtxRenderStats() if want_stats else None
+        _check(lib.rtx_progressive_add_adaptive(self._p, n, min_spp, target_rel_err, _VP(stream or None),
+                                                C.byref(stats) if stats else None))
+        return stats
+
+    def until_adaptive(self, batch, min_spp, target_rel_err):
+        """Adaptive rounds of `batch` samples until no pixel is active or the budget is spent -> RtxAdaptiveStats."""
+        out = RtxAdaptiveStats()
+        _check(lib.rtx_progressive_until_adaptive(self._p, batch, min_spp, target_rel_err, C.byref(out)))
+        return out
+
+    def pixel_spp(self):
+        """Samples each pixel holds (int32, rows x width; 0 on rows row_chunk_compat never renders)."""
+        out = np.zeros((self.height, self.width), dtype=np.int32)
+        _check(lib.rtx_progressive_pixel_spp(self._p, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
 
@@ -617,12 +648,20 @@ def render_scene(builder, world, cam, background, config, max_leaf=0):
     return scene.render(cam, cfg)
 
 
-def render_scene_progressive(builder, world, cam, background, config, batch, target_rel_err, max_leaf=0):
+def render_scene_progressive(builder, world, cam, background, config, batch, target_rel_err, max_leaf=0, adaptive=False,
+                             min_spp=2):
     """render_scene, refined `batch` samples at a time until no pixel's relative error exceeds target_rel_err or
-    config.samples_per_pixel is reached.  Returns (Screen, RtxNoiseStats of the last batch)."""
+    config.samples_per_pixel is reached.  Returns (Screen, RtxNoiseStats of the last batch).
+    adaptive=True: pixels at or below the target stop receiving samples (checked from min_spp samples on); returns
+    (Screen, RtxAdaptiveStats), and Screen.spp holds each pixel's sample count."""
     cfg = RtxConfig.from_buffer_copy(config)
     cfg.background[0], cfg.background[1], cfg.background[2] = background
     scene = builder.flatten(world, max_leaf=max_leaf).upload()
     prog = scene.progressive(cam, cfg)
+    if adaptive:
+        stats = prog.until_adaptive(batch, min_spp, target_rel_err)
+        screen = prog.screen()
+        screen.spp = prog.pixel_spp()
+        return screen, stats
     stats = prog.until(batch, target_rel_err)
     return prog.screen(), stats

@@ -6,10 +6,14 @@
 //   rtx_render [--scene ID] [--aspect A] [--width W] [--spp S] [--depth D] [--threads T] [--seed N]
 //              [--scene-seed N] [--out FILE.ppm] [--camera-aspect A] [--ply FILE] [--earth FILE.ppm]
 //              [--row-chunk-compat] [--batch N --target-error E [--snapshot-every K]]
+//              [--batch N --target-error E --adaptive [--min-spp M] [--spp-map FILE.pgm]]
 //
 // --batch / --target-error render progressively: N samples at a time until no pixel's relative error exceeds E or --spp
 // samples are in (rtx_progressive_until); the spp reached and the final noise stats go to stderr.  --snapshot-every K
 // also writes the frame after every K samples to <out>.<spp>.ppm (needs --out).
+// --adaptive stops tracing each pixel once its relative error is at most E, checked at every batch boundary from M samples
+// on (default 2; rtx_progressive_until_adaptive); stderr also gets the samples traced against a uniform render's.
+// --spp-map writes each pixel's sample count as a plain PGM (top row first, maxval = --spp).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -30,8 +34,10 @@ int main(int argc, char** argv) {
   const char* ply = nullptr;
   const char* earth = nullptr;
   bool compat = false;
-  int batch = 0, snapshot_every = 0;
+  int batch = 0, snapshot_every = 0, min_spp = 2;
   double target_error = -1.0;
+  bool adaptive = false;
+  const char* spp_map = nullptr;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* flag) -> const char* {
       if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", flag); exit(2); }
@@ -53,6 +59,9 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--batch")) batch = atoi(need("--batch"));
     else if (!strcmp(argv[i], "--target-error")) target_error = atof(need("--target-error"));
     else if (!strcmp(argv[i], "--snapshot-every")) snapshot_every = atoi(need("--snapshot-every"));
+    else if (!strcmp(argv[i], "--adaptive")) adaptive = true;
+    else if (!strcmp(argv[i], "--min-spp")) min_spp = atoi(need("--min-spp"));
+    else if (!strcmp(argv[i], "--spp-map")) spp_map = need("--spp-map");
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool progressive = batch > 0 || target_error >= 0.0;
@@ -62,6 +71,22 @@ int main(int argc, char** argv) {
   }
   if (snapshot_every > 0 && (!progressive || !out)) {
     fprintf(stderr, "--snapshot-every needs --batch, --target-error and --out\n");
+    return 2;
+  }
+  if (adaptive && !progressive) {
+    fprintf(stderr, "--adaptive needs --batch N (> 0) and --target-error E (>= 0)\n");
+    return 2;
+  }
+  if (!adaptive && (spp_map || min_spp != 2)) {
+    fprintf(stderr, "--min-spp and --spp-map need --adaptive\n");
+    return 2;
+  }
+  if (adaptive && (min_spp < 2 || min_spp > spp)) {
+    fprintf(stderr, "--min-spp M must be in [2, --spp]\n");
+    return 2;
+  }
+  if (adaptive && snapshot_every > 0) {
+    fprintf(stderr, "--snapshot-every and --adaptive do not go together\n");
     return 2;
   }
   try {
@@ -76,7 +101,17 @@ int main(int argc, char** argv) {
     config.c.seed = seed;
     config.c.row_chunk_compat = compat ? 1 : 0;
     rtsr::Screen screen;
-    if (progressive) {
+    if (adaptive) {
+      RtxAdaptiveStats as = {};
+      screen = rtsr::render_scene_adaptive(scene, wc.world, wc.cam, wc.background, config, batch, min_spp, target_error, &as);
+      const double uniform = (double)as.spp_done * (double)as.pixels;
+      fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", as.spp_done,
+              spp, target_error, as.pixels_above, as.pixels, as.max_rel_err, as.mean_rel_err);
+      fprintf(stderr, "adaptive: %llu samples traced, %.4g of a uniform render's %d spp x %d pixels; %d pixels still active\n",
+              (unsigned long long)as.samples, uniform > 0 ? (double)as.samples / uniform : 0.0, as.spp_done, as.pixels,
+              as.pixels_active);
+      if (spp_map) screen.write_spp_pgm_file(spp_map, spp);
+    } else if (progressive) {
       RtxNoiseStats ns = {};
       auto snap = [&](const rtsr::Screen& s, int spp_now) {
         std::string path = std::string(out) + "." + std::to_string(spp_now) + ".ppm";

@@ -27,11 +27,14 @@ rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);
 rtx_status rtx_f32_render(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
                           double* d_accum_rgb, uint8_t* d_rgb8, void* hip_stream, RtxRenderStats* stats);
 // progressive.inc: trace the absolute samples [first, first + count) onto d_accum_rgb (continuing its sums when cont != 0;
-// d_sumsq_rgb, if not NULL, gets the sums of squares), and tone-map an accumulator of spp samples.
+// d_sumsq_rgb, if not NULL, gets the sums of squares) -- of the n_active local pixels listed in d_active only, when that is
+// not NULL -- and tone-map an accumulator of spp samples, or of d_counts[lp] samples per pixel (spp where that is 0).
 rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
                                 double* d_accum_rgb, double* d_sumsq_rgb, uint32_t first, uint32_t count, int32_t cont,
-                                void* hip_stream, RtxRenderStats* stats);
+                                const uint32_t* d_active, uint32_t n_active, void* hip_stream, RtxRenderStats* stats);
 rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream);
+rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix,
+                                  uint32_t spp, void* hip_stream);
 rtx_status rtx_f32_trim(void* device_scene);
 void rtx_f32_destroy(void* device_scene);
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error

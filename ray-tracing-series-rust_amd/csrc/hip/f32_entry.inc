@@ -41,13 +41,17 @@ rtx_status rtx_f32_render(void* device_scene, const RtxCamera* cam, const RtxCon
 }
 rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
                                 double* d_accum_rgb, double* d_sumsq_rgb, uint32_t first, uint32_t count, int32_t cont,
-                                void* hip_stream, RtxRenderStats* stats) {
-  const SampleRange range = {first, count, cont, d_sumsq_rgb};
+                                const uint32_t* d_active, uint32_t n_active, void* hip_stream, RtxRenderStats* stats) {
+  const SampleRange range = {first, count, cont, d_sumsq_rgb, d_active, n_active};
   return render_impl<false>((DeviceScene*)device_scene, cam, cfg, shard, d_accum_rgb, nullptr, (hipStream_t)hip_stream, stats,
                             &range);
 }
 rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream) {
   return tonemap_impl(d_accum_rgb, d_rgb8, npix, spp, (hipStream_t)hip_stream);
+}
+rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix,
+                                  uint32_t spp, void* hip_stream) {
+  return tonemap_counts_impl(d_accum_rgb, d_rgb8, d_counts, npix, spp, (hipStream_t)hip_stream);
 }
 rtx_status rtx_f32_trim(void* device_scene) { return scene_trim_impl((DeviceScene*)device_scene); }
 void rtx_f32_destroy(void* device_scene) { free_device_scene((DeviceScene*)device_scene); }

@@ -5,12 +5,24 @@
 // shard's local pixel lp, so 64 consecutive items are 64 consecutive pixels of one sample: coherent primary rays, coalesced
 // sample-buffer stores.  Which lane traces an item cannot matter: streams are keyed by (pixel, sample) and every item owns its
 // output slot.
+//
+// An adaptive pass (progressive.inc) traces only the shard's still-active pixels: its map is an ActiveMap, whose list holds
+// their local pixels in ascending order, and npix is then the length of that list -- item g = s_local * npix + k is sample
+// s_begin + s_local of local pixel active[k].  The list is ascending, so 64 consecutive items are still mostly neighbouring
+// pixels of one sample.  The map's type is a template parameter of every trace kernel (SM, default ShardMap): a uniform
+// pass's instantiation has neither the list nor a test for it -- a runtime test on a kernel argument cost 0.4 - 1.6 % on the
+// k_trace_lds and k_trace_world legs of bench.py, through the kernels' register assignment.
 
 // Local pixel lp of a shard -> image (column i, row j).  Rows of a shard are the rows j with
 // (j / block_rows) % shard_count == shard_index, compacted in ascending j.
 struct ShardMap {
   int32_t width, block_rows, shard_index, shard_count;
 };
+struct ActiveMap : ShardMap {
+  const uint32_t* active;  // the pass's active local pixels, ascending
+};
+__device__ __forceinline__ uint32_t map_pixel(const ShardMap&, uint32_t k) { return k; }
+__device__ __forceinline__ uint32_t map_pixel(const ActiveMap& m, uint32_t k) { return m.active[k]; }
 __device__ __forceinline__ void shard_pixel(const ShardMap& m, uint32_t lp, uint32_t* i, uint32_t* j) {
   uint32_t lr = lp / (uint32_t)m.width;
   *i = lp - lr * (uint32_t)m.width;
@@ -20,14 +32,16 @@ __device__ __forceinline__ void shard_pixel(const ShardMap& m, uint32_t lp, uint
 }
 
 // Item g of the pass -> image pixel (i, j); returns the item's sample index within the pass.
-__device__ __forceinline__ uint32_t item_pixel(const ShardMap& sm, uint32_t npix, uint32_t g, uint32_t* i, uint32_t* j) {
+template <class SM>
+__device__ __forceinline__ uint32_t item_pixel(const SM& sm, uint32_t npix, uint32_t g, uint32_t* i, uint32_t* j) {
   const uint32_t s_local = g / npix;
-  shard_pixel(sm, g - s_local * npix, i, j);
+  shard_pixel(sm, map_pixel(sm, g - s_local * npix), i, j);
   return s_local;
 }
 
 // The camera ray and RNG stream of item g (path_begin, core/integrator.hpp).
-__device__ __forceinline__ void start_path(const rt::RenderParams& rp, const ShardMap& sm, uint32_t npix, uint32_t s_begin,
+template <class SM>
+__device__ __forceinline__ void start_path(const rt::RenderParams& rp, const SM& sm, uint32_t npix, uint32_t s_begin,
                                            uint32_t g, rt::PathState* ps) {
   uint32_t i, j;
   const uint32_t s_local = item_pixel(sm, npix, g, &i, &j);

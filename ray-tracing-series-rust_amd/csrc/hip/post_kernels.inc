@@ -42,6 +42,31 @@ __global__ __launch_bounds__(256) void k_reduce_samples_moments(const double* __
   sumsq[3 * (size_t)lp] = qr; sumsq[3 * (size_t)lp + 1] = qg; sumsq[3 * (size_t)lp + 2] = qb;
 }
 
+// k_reduce_samples_moments for an adaptive pass (pass_items.inc): the pass's items are the pixels of the active list, so lane
+// k adds its samples onto local pixel active[k]'s S and Q with the same in-order, non-contracted arithmetic.  Adaptive passes
+// always continue sums already there (a pixel can retire only after 2 samples, progressive.inc).
+__global__ __launch_bounds__(256) void k_reduce_samples_moments_active(const double* __restrict__ samples,
+                                                                       double* __restrict__ accum, double* __restrict__ sumsq,
+                                                                       const uint32_t* __restrict__ active, uint32_t n_active,
+                                                                       uint32_t s_count) {
+#pragma clang fp contract(off)
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n_active) return;
+  const size_t lp = active[k];
+  double r = accum[3 * lp], g = accum[3 * lp + 1], b = accum[3 * lp + 2];
+  double qr = sumsq[3 * lp], qg = sumsq[3 * lp + 1], qb = sumsq[3 * lp + 2];
+  for (uint32_t s = 0; s < s_count; ++s) {
+    const double* p = samples + 3 * ((size_t)s * n_active + k);
+    const double x0 = p[0], x1 = p[1], x2 = p[2];
+    r += x0; g += x1; b += x2;
+    qr = __dadd_rn(qr, __dmul_rn(x0, x0));
+    qg = __dadd_rn(qg, __dmul_rn(x1, x1));
+    qb = __dadd_rn(qb, __dmul_rn(x2, x2));
+  }
+  accum[3 * lp] = r; accum[3 * lp + 1] = g; accum[3 * lp + 2] = b;
+  sumsq[3 * lp] = qr; sumsq[3 * lp + 1] = qg; sumsq[3 * lp + 2] = qb;
+}
+
 // Noise estimate of a progressive frame after n >= 2 samples, per pixel and channel:
 //   m = S/n,  var = max(0, (Q - S*S/n) / (n - 1)),  se = sqrt(var / n),  r_c = se / (m + 1/256)
 // and the pixel's error r = max_c r_c.  Every operation is correctly rounded and none is contracted, so r equals a
@@ -125,6 +150,98 @@ __global__ __launch_bounds__(256) void k_noise_stats_final(const NoisePartial* _
   if (threadIdx.x == 0) *out = v;
 }
 
+// k_noise_stats for a frame whose pixels hold different sample counts (adaptive progressive rendering): pixel lp's n is
+// counts[lp], or spp where counts[lp] == 0 (a pixel still active).  The same pixel_rel_err and the same reduction tree.
+__global__ __launch_bounds__(256) void k_noise_stats_counts(const double* __restrict__ S, const double* __restrict__ Q,
+                                                            const int32_t* __restrict__ counts, uint32_t npix, uint32_t spp,
+                                                            double target, NoisePartial* __restrict__ partials) {
+  const uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+  NoisePartial v = {0.0, 0.0, 0ull};
+  if (lp < npix) {
+    const int32_t c = counts[lp];
+    const double r = pixel_rel_err(S, Q, lp, (double)(c != 0 ? (uint32_t)c : spp));
+    v.max_r = r;
+    v.sum_r = r;
+    v.above = r > target ? 1ull : 0ull;
+  }
+  v = noise_block_reduce(v);
+  if (threadIdx.x == 0) partials[blockIdx.x] = v;
+}
+
+// Adaptive retirement (progressive.inc) over the n pixels of the ascending active list, in three launches:
+//   k_retire_flag:    lane k computes pixel active[k]'s r at n = spp; the pixel retires when r <= target (counts[lp] = spp,
+//                     its sample count from now on).  Each wave's ballot of the survivors goes to keep_mask[k / 64], the
+//                     block's survivor count to block_count[blockIdx.x].
+//   k_retire_scan:    one block turns the block counts into exclusive offsets, block_offset[n_blocks] = the survivors.
+//   k_retire_scatter: a survivor's slot in the next list is its block's offset + the survivors of the block's earlier waves
+//                     (scanned through LDS) + those of the lower lanes of its wave (mbcnt on the ballot).
+// A stable compaction: the next list is ascending again, and it depends on the data alone, never on scheduling.
+__global__ __launch_bounds__(256) void k_retire_flag(const double* __restrict__ S, const double* __restrict__ Q,
+                                                     const uint32_t* __restrict__ active, uint32_t n, uint32_t spp,
+                                                     double target, int32_t* __restrict__ counts,
+                                                     unsigned long long* __restrict__ keep_mask,
+                                                     uint32_t* __restrict__ block_count) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  bool keep = false;
+  if (k < n) {
+    const uint32_t lp = active[k];
+    const double r = pixel_rel_err(S, Q, lp, (double)spp);
+    keep = !(r <= target);  // (a NaN r stays active)
+    if (!keep) counts[lp] = (int32_t)spp;
+  }
+  const unsigned long long m = __ballot(keep);
+  __shared__ uint32_t wave_n[4];
+  if ((threadIdx.x & 63u) == 0) {
+    keep_mask[k >> 6] = m;
+    wave_n[threadIdx.x >> 6] = (uint32_t)__popcll(m);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) block_count[blockIdx.x] = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+}
+
+__global__ __launch_bounds__(256) void k_retire_scan(const uint32_t* __restrict__ block_count, uint32_t n_blocks,
+                                                     uint32_t* __restrict__ block_offset) {
+  // thread t owns the contiguous blocks [t * per, (t + 1) * per): its sum, an exclusive scan of the 256 sums, then its offsets
+  const uint32_t per = (n_blocks + 255u) / 256u, lo = threadIdx.x * per;
+  const uint32_t hi = lo + per < n_blocks ? lo + per : n_blocks;
+  uint32_t sum = 0;
+  for (uint32_t b = lo; b < hi; ++b) sum += block_count[b];
+  __shared__ uint32_t part[256];
+  part[threadIdx.x] = sum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t run = 0;
+    for (int t = 0; t < 256; ++t) { const uint32_t c = part[t]; part[t] = run; run += c; }
+    block_offset[n_blocks] = run;
+  }
+  __syncthreads();
+  uint32_t run = part[threadIdx.x];
+  for (uint32_t b = lo; b < hi; ++b) { block_offset[b] = run; run += block_count[b]; }
+}
+
+__global__ __launch_bounds__(256) void k_retire_scatter(const uint32_t* __restrict__ active, uint32_t n,
+                                                        const unsigned long long* __restrict__ keep_mask,
+                                                        const uint32_t* __restrict__ block_offset,
+                                                        uint32_t* __restrict__ next) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  __shared__ uint32_t wave_base[4];
+  if (threadIdx.x == 0) {
+    uint32_t b = block_offset[blockIdx.x];
+    for (int w = 0; w < 4; ++w) { wave_base[w] = b; b += (uint32_t)__popcll(keep_mask[4 * blockIdx.x + w]); }
+  }
+  __syncthreads();
+  if (k >= n) return;
+  const unsigned long long m = keep_mask[k >> 6];
+  if (!((m >> (threadIdx.x & 63u)) & 1ull)) return;
+  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  next[wave_base[threadIdx.x >> 6] + rank] = active[k];
+}
+
+__global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ out, uint32_t n) {
+  const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+  if (k < n) out[k] = k;
+}
+
 __global__ __launch_bounds__(256) void k_tonemap(const double* __restrict__ accum,
                                                  uint8_t* __restrict__ rgb8, uint32_t npix,
                                                  uint32_t spp) {
@@ -132,6 +249,19 @@ __global__ __launch_bounds__(256) void k_tonemap(const double* __restrict__ accu
   if (lp >= npix) return;
   int32_t c[3];
   rt::tone_map(rt::v3(accum[3 * (size_t)lp], accum[3 * (size_t)lp + 1], accum[3 * (size_t)lp + 2]), spp, c);
+  rgb8[3 * (size_t)lp] = (uint8_t)c[0];
+  rgb8[3 * (size_t)lp + 1] = (uint8_t)c[1];
+  rgb8[3 * (size_t)lp + 2] = (uint8_t)c[2];
+}
+
+// k_tonemap for a frame whose pixels hold different sample counts: pixel lp's is counts[lp], or spp where that is 0.
+__global__ __launch_bounds__(256) void k_tonemap_counts(const double* __restrict__ accum, uint8_t* __restrict__ rgb8,
+                                                        const int32_t* __restrict__ counts, uint32_t npix, uint32_t spp) {
+  uint32_t lp = blockIdx.x * 256u + threadIdx.x;
+  if (lp >= npix) return;
+  const int32_t n = counts[lp];
+  int32_t c[3];
+  rt::tone_map(rt::v3(accum[3 * (size_t)lp], accum[3 * (size_t)lp + 1], accum[3 * (size_t)lp + 2]), n != 0 ? (uint32_t)n : spp, c);
   rgb8[3 * (size_t)lp] = (uint8_t)c[0];
   rgb8[3 * (size_t)lp + 1] = (uint8_t)c[1];
   rgb8[3 * (size_t)lp + 2] = (uint8_t)c[2];

@@ -6,6 +6,12 @@
 // Q in sample order.  Since every path's random stream is keyed by its absolute (pixel, sample) index, the frame after k
 // samples -- however they were split across calls -- is bit-identical to a one-shot render at k spp.
 //
+// Adaptive rounds (rtx_progressive_add_adaptive / _until_adaptive) stop tracing the pixels that reached the target: a
+// retirement check (k_retire_flag / _scan / _scatter) freezes a pixel's count n_p at spp_done once its relative error is at
+// most the target, and compacts the ascending list of the still-active pixels; the round's samples are then traced for the
+// listed pixels only (SampleRange::active, pass_items.inc).  Every active pixel holds spp_done samples, so a pass keeps one
+// s_begin.  Until the first pixel retires, rounds trace through the uniform path and the handle is a uniform one.
+//
 // The handle borrows the scene's render workspace (sample buffer, work counters, pipelining stream): it must not run at the
 // same time as another render of the same scene on another stream, and it must be destroyed before its scene.
 
@@ -23,6 +29,16 @@ struct rtx_progressive {
   double* Q;
   NoisePartial* partials;  // one per 256 active pixels, then the final result
   uint32_t n_partials;
+  // adaptive state, allocated by the first adaptive call (a uniform handle keeps its 48 bytes per pixel)
+  bool adaptive;
+  int cur;                  // active[cur]: the ascending list of the n_active local pixels still active
+  uint32_t* active[2];      // (the other one: the compaction's target)
+  uint32_t n_active;        // npix until the first pixel retires
+  int32_t* counts;          // per pixel of the shard: n_p of a retired pixel, 0 for an active one (or a row never rendered)
+  unsigned long long* keep_mask;  // compaction scratch: one ballot per wave, the block counts, their offsets and total
+  uint32_t* block_count;
+  uint32_t* block_offset;
+  uint64_t retired_samples;  // sum of n_p over the retired pixels
 };
 
 namespace {
@@ -31,6 +47,12 @@ void progressive_free(rtx_progressive* p) {
   if (p->S) (void)hipFree(p->S);
   if (p->Q) (void)hipFree(p->Q);
   if (p->partials) (void)hipFree(p->partials);
+  for (uint32_t* a : p->active)
+    if (a) (void)hipFree(a);
+  if (p->counts) (void)hipFree(p->counts);
+  if (p->keep_mask) (void)hipFree(p->keep_mask);
+  if (p->block_count) (void)hipFree(p->block_count);
+  if (p->block_offset) (void)hipFree(p->block_offset);
   delete p;
 }
 
@@ -39,11 +61,30 @@ rtx_status progressive_add(rtx_progressive* p, int32_t n_samples, hipStream_t st
   rtx_status st;
   if (p->scene->f32)
     st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
-                              range.cont, (void*)stream, stats);
+                              range.cont, nullptr, 0u, (void*)stream, stats);
   else
     st = render_impl<false>(scene_device(p->scene), &p->cam, &p->cfg, &p->shard, p->S, nullptr, stream, stats, &range);
   if (st != RTX_OK) { p->broken = true; return st; }
   p->spp_done += n_samples;
+  return RTX_OK;
+}
+
+bool any_retired(const rtx_progressive* p) { return p->adaptive && p->n_active < p->npix; }
+
+// Reduces r over the shard's active pixels into partials[n_partials] (each pixel at its own n_p once one has retired).
+rtx_status noise_reduce(rtx_progressive* p, double target, NoisePartial* r) {
+  HIP_TRY(hipDeviceSynchronize());  // the adds ran on the caller's stream
+  if (any_retired(p))
+    hipLaunchKernelGGL(k_noise_stats_counts, dim3(p->n_partials), dim3(256), 0, (hipStream_t) nullptr, p->S, p->Q, p->counts,
+                       p->npix, (uint32_t)p->spp_done, target, p->partials);
+  else
+    hipLaunchKernelGGL(k_noise_stats, dim3(p->n_partials), dim3(256), 0, (hipStream_t) nullptr, p->S, p->Q, p->npix,
+                       (uint32_t)p->spp_done, target, p->partials);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_noise_stats_final, dim3(1), dim3(256), 0, (hipStream_t) nullptr, p->partials, p->n_partials,
+                     p->partials + p->n_partials);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(r, p->partials + p->n_partials, sizeof(*r), hipMemcpyDeviceToHost));
   return RTX_OK;
 }
 
@@ -53,15 +94,9 @@ rtx_status progressive_stats(rtx_progressive* p, double target, RtxNoiseStats* o
   out->pixels = (int32_t)p->npix;
   out->target_rel_err = target;
   if (p->npix == 0) return RTX_OK;
-  HIP_TRY(hipDeviceSynchronize());  // the adds ran on the caller's stream
-  hipLaunchKernelGGL(k_noise_stats, dim3(p->n_partials), dim3(256), 0, (hipStream_t) nullptr, p->S, p->Q, p->npix,
-                     (uint32_t)p->spp_done, target, p->partials);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_noise_stats_final, dim3(1), dim3(256), 0, (hipStream_t) nullptr, p->partials, p->n_partials,
-                     p->partials + p->n_partials);
-  HIP_TRY(hipGetLastError());
   NoisePartial r;
-  HIP_TRY(hipMemcpy(&r, p->partials + p->n_partials, sizeof(r), hipMemcpyDeviceToHost));
+  const rtx_status st = noise_reduce(p, target, &r);
+  if (st != RTX_OK) return st;
   out->pixels_above = (int32_t)r.above;
   out->max_rel_err = r.max_r;
   out->mean_rel_err = r.sum_r / (double)p->npix;
@@ -72,6 +107,125 @@ bool progressive_usable(const rtx_progressive* p, const char* fn) {
   if (!p) { set_error(std::string(fn) + ": NULL handle"); return false; }
   if (p->broken) { set_error(std::string(fn) + ": an earlier rtx_progressive_add failed; the accumulators are incomplete"); return false; }
   return true;
+}
+
+// The uniform entries would give every pixel the next samples, leaving a gap in a retired pixel's sample indices.
+bool uniform_allowed(const rtx_progressive* p, const char* fn) {
+  if (!any_retired(p)) return true;
+  set_error(std::string(fn) + ": pixels of this handle have retired (adaptive rounds); continue with the adaptive entries");
+  return false;
+}
+
+// The adaptive entries' common argument checks (before any device call).
+bool adaptive_args_ok(const rtx_progressive* p, const char* fn, int32_t min_spp, double target) {
+  if (min_spp < 2 || min_spp > p->cfg.samples_per_pixel) {
+    set_error(std::string(fn) + ": min_spp must be in [2, samples_per_pixel] = [2, " + std::to_string(p->cfg.samples_per_pixel) + "]");
+    return false;
+  }
+  if (!(target >= 0.0)) { set_error(std::string(fn) + ": target_rel_err must be >= 0"); return false; }
+  return true;
+}
+
+// Allocates the adaptive buffers on the first adaptive call: every active pixel listed, no count frozen.
+rtx_status adaptive_init(rtx_progressive* p) {
+  if (p->adaptive) return RTX_OK;
+  const uint32_t nb = (p->npix + 255u) / 256u;
+  hipError_t e = hipSuccess;
+  for (uint32_t*& a : p->active)
+    if (e == hipSuccess) e = hipMalloc((void**)&a, ((size_t)p->npix + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->counts, ((size_t)p->npix_all + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->keep_mask, ((size_t)nb * 4 + 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->block_count, ((size_t)nb + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->block_offset, ((size_t)nb + 1) * 4);
+  if (e == hipSuccess) e = hipMemset(p->counts, 0, ((size_t)p->npix_all + 1) * 4);
+  if (e == hipSuccess && p->npix) {
+    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, p->active[0], p->npix);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    set_error(std::string("progressive: adaptive buffers: ") + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
+  }
+  p->adaptive = true;
+  p->cur = 0;
+  p->n_active = p->npix;
+  p->retired_samples = 0;
+  return RTX_OK;
+}
+
+// The retirement check of an adaptive round at n = spp_done (the caller has checked spp_done >= max(2, min_spp)): freezes the
+// count of every active pixel with r <= target and compacts the list of the others.  Blocking (the host needs the new count).
+rtx_status adaptive_retire_launch(rtx_progressive* p, double target, hipStream_t stream) {
+  if (p->n_active == 0) return RTX_OK;
+  const uint32_t n = p->n_active, nb = (n + 255u) / 256u, spp = (uint32_t)p->spp_done;
+  uint32_t* list = p->active[p->cur];
+  uint32_t* next = p->active[1 - p->cur];
+  hipLaunchKernelGGL(k_retire_flag, dim3(nb), dim3(256), 0, stream, p->S, p->Q, list, n, spp, target, p->counts,
+                     p->keep_mask, p->block_count);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(256), 0, stream, p->block_count, nb, p->block_offset);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_retire_scatter, dim3(nb), dim3(256), 0, stream, list, n, p->keep_mask, p->block_offset, next);
+  HIP_TRY(hipGetLastError());
+  uint32_t kept = 0;
+  HIP_TRY(hipMemcpyAsync(&kept, p->block_offset + nb, sizeof(kept), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (kept > n) { set_error("progressive: the retirement check counted more pixels than it was given"); return RTX_EHIP; }
+  p->retired_samples += (uint64_t)(n - kept) * spp;
+  p->n_active = kept;
+  p->cur = 1 - p->cur;
+  return RTX_OK;
+}
+
+rtx_status adaptive_retire(rtx_progressive* p, double target, hipStream_t stream) {
+  const rtx_status st = adaptive_retire_launch(p, target, stream);
+  if (st != RTX_OK) p->broken = true;  // counts may be frozen for a list that was not compacted
+  return st;
+}
+
+// The tracing half of an adaptive round: samples [spp_done, spp_done + n) of the pixels still active.  With none retired yet
+// that is a uniform add; with none active it traces nothing (spp_done still advances).
+rtx_status adaptive_trace(rtx_progressive* p, int32_t n, hipStream_t stream, RtxRenderStats* stats) {
+  if (p->n_active == p->npix) return progressive_add(p, n, stream, stats);
+  if (p->n_active == 0) {
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->trace_kernel = RTX_KERNEL_SIMPLE; }  // nothing traced
+    p->spp_done += n;
+    return RTX_OK;
+  }
+  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n, 1, p->Q, p->active[p->cur], p->n_active};
+  rtx_status st;
+  if (p->scene->f32)
+    st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
+                              range.cont, range.active, range.n_active, (void*)stream, stats);
+  else
+    st = render_impl<false>(scene_device(p->scene), &p->cam, &p->cfg, &p->shard, p->S, nullptr, stream, stats, &range);
+  if (st != RTX_OK) { p->broken = true; return st; }
+  p->spp_done += n;
+  return RTX_OK;
+}
+
+// A retirement check is due at spp_done >= max(2, min_spp); min_spp >= 2 is checked by every entry.
+bool check_due(const rtx_progressive* p, int32_t min_spp) { return p->spp_done >= min_spp; }
+
+rtx_status adaptive_stats(rtx_progressive* p, int32_t min_spp, double target, RtxAdaptiveStats* out) {
+  memset(out, 0, sizeof(*out));
+  out->spp_done = p->spp_done;
+  out->min_spp = min_spp;
+  out->pixels = (int32_t)p->npix;
+  out->pixels_active = (int32_t)(p->adaptive ? p->n_active : p->npix);
+  out->samples = p->adaptive ? p->retired_samples + (uint64_t)p->n_active * (uint64_t)p->spp_done
+                             : (uint64_t)p->npix * (uint64_t)p->spp_done;
+  out->target_rel_err = target;
+  if (p->npix == 0 || p->spp_done < 2) return RTX_OK;
+  NoisePartial r;
+  const rtx_status st = noise_reduce(p, target, &r);
+  if (st != RTX_OK) return st;
+  out->pixels_above = (int32_t)r.above;
+  out->max_rel_err = r.max_r;
+  out->mean_rel_err = r.sum_r / (double)p->npix;
+  return RTX_OK;
 }
 
 }  // namespace
@@ -123,7 +277,7 @@ void rtx_progressive_destroy(rtx_progressive* p) {
 int32_t rtx_progressive_spp(const rtx_progressive* p) { return p ? p->spp_done : -1; }
 
 rtx_status rtx_progressive_add(rtx_progressive* p, int32_t n_samples, void* hip_stream, RtxRenderStats* stats) {
-  if (!progressive_usable(p, "rtx_progressive_add")) return RTX_EINVAL;
+  if (!progressive_usable(p, "rtx_progressive_add") || !uniform_allowed(p, "rtx_progressive_add")) return RTX_EINVAL;
   if (n_samples <= 0 || n_samples > p->cfg.samples_per_pixel - p->spp_done) {
     set_error("rtx_progressive_add: n_samples must be in [1, samples_per_pixel - spp_done] = [1, " +
               std::to_string(p->cfg.samples_per_pixel - p->spp_done) + "]");
@@ -146,8 +300,12 @@ rtx_status rtx_progressive_read(const rtx_progressive* p, RtxFrame* out, double*
     rtx_status st = RTX_OK;
     hipError_t e = hipMemset(d_rgb, 0, (size_t)p->npix_all * 3);
     if (e == hipSuccess) {
-      st = p->scene->f32 ? rtx_f32_tonemap(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, nullptr)
-                         : tonemap_impl(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, (hipStream_t) nullptr);
+      if (any_retired(p))  // each pixel by its own count
+        st = p->scene->f32 ? rtx_f32_tonemap_counts(p->S, d_rgb, p->counts, p->npix, (uint32_t)p->spp_done, nullptr)
+                           : tonemap_counts_impl(p->S, d_rgb, p->counts, p->npix, (uint32_t)p->spp_done, (hipStream_t) nullptr);
+      else
+        st = p->scene->f32 ? rtx_f32_tonemap(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, nullptr)
+                           : tonemap_impl(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, (hipStream_t) nullptr);
       if (st == RTX_OK) e = hipMemcpy(out->rgb8, d_rgb, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost);
     }
     (void)hipFree(d_rgb);
@@ -166,7 +324,7 @@ rtx_status rtx_progressive_stats(rtx_progressive* p, double target_rel_err, RtxN
 }
 
 rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double target_rel_err, RtxNoiseStats* out) {
-  if (!progressive_usable(p, "rtx_progressive_until")) return RTX_EINVAL;
+  if (!progressive_usable(p, "rtx_progressive_until") || !uniform_allowed(p, "rtx_progressive_until")) return RTX_EINVAL;
   if (!out) { set_error("rtx_progressive_until: NULL out"); return RTX_EINVAL; }
   if (batch <= 0) { set_error("rtx_progressive_until: batch must be > 0"); return RTX_EINVAL; }
   if (!(target_rel_err >= 0.0)) { set_error("rtx_progressive_until: target_rel_err must be >= 0"); return RTX_EINVAL; }
@@ -189,6 +347,58 @@ rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double targe
     st = progressive_stats(p, target_rel_err, out);
     if (st != RTX_OK || out->pixels_above == 0) return st;
   }
+  return RTX_OK;
+}
+
+rtx_status rtx_progressive_add_adaptive(rtx_progressive* p, int32_t n_samples, int32_t min_spp, double target_rel_err,
+                                        void* hip_stream, RtxRenderStats* stats) {
+  if (!progressive_usable(p, "rtx_progressive_add_adaptive")) return RTX_EINVAL;
+  if (n_samples <= 0 || n_samples > p->cfg.samples_per_pixel - p->spp_done) {
+    set_error("rtx_progressive_add_adaptive: n_samples must be in [1, samples_per_pixel - spp_done] = [1, " +
+              std::to_string(p->cfg.samples_per_pixel - p->spp_done) + "]");
+    return RTX_EINVAL;
+  }
+  if (!adaptive_args_ok(p, "rtx_progressive_add_adaptive", min_spp, target_rel_err)) return RTX_EINVAL;
+  rtx_status st = adaptive_init(p);
+  if (st == RTX_OK && check_due(p, min_spp)) st = adaptive_retire(p, target_rel_err, (hipStream_t)hip_stream);
+  if (st != RTX_OK) return st;
+  return adaptive_trace(p, n_samples, (hipStream_t)hip_stream, stats);
+}
+
+rtx_status rtx_progressive_until_adaptive(rtx_progressive* p, int32_t batch, int32_t min_spp, double target_rel_err,
+                                          RtxAdaptiveStats* out) {
+  if (!progressive_usable(p, "rtx_progressive_until_adaptive")) return RTX_EINVAL;
+  if (!out) { set_error("rtx_progressive_until_adaptive: NULL out"); return RTX_EINVAL; }
+  if (batch <= 0) { set_error("rtx_progressive_until_adaptive: batch must be > 0"); return RTX_EINVAL; }
+  if (!adaptive_args_ok(p, "rtx_progressive_until_adaptive", min_spp, target_rel_err)) return RTX_EINVAL;
+  HIP_TRY(hipDeviceSynchronize());  // earlier rounds may have run on the caller's stream; this loop runs on the default one
+  rtx_status st = adaptive_init(p);
+  if (st != RTX_OK) return st;
+  const int32_t budget = p->cfg.samples_per_pixel;
+  for (;;) {
+    if (check_due(p, min_spp)) {  // every batch boundary, and the budget's
+      st = adaptive_retire(p, target_rel_err, (hipStream_t) nullptr);
+      if (st != RTX_OK) return st;
+    }
+    if (p->n_active == 0 || p->spp_done >= budget) break;
+    const int32_t n = budget - p->spp_done < batch ? budget - p->spp_done : batch;
+    st = adaptive_trace(p, n, (hipStream_t) nullptr, nullptr);
+    if (st != RTX_OK) return st;
+  }
+  return adaptive_stats(p, min_spp, target_rel_err, out);
+}
+
+rtx_status rtx_progressive_pixel_spp(const rtx_progressive* p, int32_t* spp) {
+  if (!progressive_usable(p, "rtx_progressive_pixel_spp")) return RTX_EINVAL;
+  if (!spp) { set_error("rtx_progressive_pixel_spp: NULL out"); return RTX_EINVAL; }
+  if (p->adaptive && p->npix_all) {
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(spp, p->counts, (size_t)p->npix_all * 4, hipMemcpyDeviceToHost));
+  } else {
+    memset(spp, 0, (size_t)p->npix_all * 4);
+  }
+  for (uint32_t lp = 0; lp < p->npix; ++lp)
+    if (spp[lp] == 0) spp[lp] = p->spp_done;  // still active
   return RTX_OK;
 }
 

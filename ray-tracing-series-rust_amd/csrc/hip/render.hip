@@ -382,7 +382,16 @@ struct PassArgs {
   uint32_t feat;
   uint32_t stack_levels;          // of the binary tree (max_stack + 1) and the bytes of its stacks
   size_t stack_lds;
+  const uint32_t* active;         // an adaptive pass: its list of active local pixels (ActiveMap, pass_items.inc); else NULL
 };
+
+// Calls launch(map) with the pass's pixel map: the shard's ShardMap, or an ActiveMap over an adaptive pass's list.  Each trace
+// kernel has one instantiation per map type, so the uniform one carries neither the list nor a test for it.
+template <class Launch>
+static void with_map(const PassArgs& a, Launch launch) {
+  if (a.active) launch(ActiveMap{a.sm, a.active});
+  else launch(a.sm);
+}
 
 // The diagnostic instantiations (RTX_TRACE_KERNEL=vote_diag / world_diag) count executions and active lanes per region into
 // ws.diag.  run_diag clears the counters, launches, waits for the kernel and prints one line per region into stderr; h gets
@@ -480,9 +489,9 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
   }
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)wt.vote_blocks_per_cu);
   const uint32_t threshold = ds->walk.walk_threshold | (ds->walk.regen_min << 16);
-#define LAUNCH_VOTE_WIDE(FEAT, DIAGF, THRESHOLD)                                                                       \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, false, true>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
-                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter,                      \
+#define LAUNCH_VOTE_WIDE(FEAT, DIAGF, THRESHOLD, MAP)                                                                  \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, false, true, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter,             \
                      DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, THRESHOLD, (uint32_t)wt.levels,              \
                      (uint32_t)p.bvh_pos, wt.nodes4, p.tri_base, lds_tables, p.top)
   // a triangle mesh in a room of rectangles, no spheres / lists / glass (the dragon room): the leaner instantiation
@@ -490,7 +499,7 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
   if (diag && room) {
     unsigned long long h[24];
     static const char* const names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "shade_all"};
-    const rtx_status st = run_diag(ds, a.stream, [&] { LAUNCH_VOTE_WIDE(P_MESH_ROOM, true, ds->walk.walk_threshold); }, "vote_diag", 10, names, 6, h);
+    const rtx_status st = run_diag(ds, a.stream, [&] { LAUNCH_VOTE_WIDE(P_MESH_ROOM, true, ds->walk.walk_threshold, a.sm); }, "vote_diag", 10, names, 6, h);
     if (st != RTX_OK) return st;
     if (h[12]) {
       float v[12];
@@ -499,9 +508,9 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
               h[12], v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8], v[9], v[10], v[11], h[19]);
     }
   } else if (room) {
-    LAUNCH_VOTE_WIDE(P_MESH_ROOM, false, threshold);
+    with_map(a, [&](auto map) { LAUNCH_VOTE_WIDE(P_MESH_ROOM, false, threshold, map); });
   } else {
-    LAUNCH_VOTE_WIDE(P_MESH, false, threshold);
+    with_map(a, [&](auto map) { LAUNCH_VOTE_WIDE(P_MESH, false, threshold, map); });
   }
 #undef LAUNCH_VOTE_WIDE
   return RTX_OK;
@@ -510,26 +519,30 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
 static rtx_status launch_vote(DeviceScene* ds, const PassArgs& a) {
   const VotePlan& p = ds->vote;
   HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
-  const bool diag = ds->sw.kernel == ForcedKernel::vote && ds->sw.diag;
+  const bool diag = ds->sw.kernel == ForcedKernel::vote && ds->sw.diag && !a.active;  // (diagnostics: uniform passes only)
   if (a.preset == 1 && ds->wide.nodes4) return launch_vote_wide(ds, a, diag);
   const bool ring = p.ring[a.preset];
   const size_t lds = a.stack_lds + (ring ? (TRACE_BLOCK / 64) * ring_bytes(64) : 0);
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[a.preset]);
-#define LAUNCH_VOTE2(FEAT, DIAGF, RINGF)                                                                                 \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
-                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter,                       \
+#define LAUNCH_VOTE3(FEAT, DIAGF, RINGF, MAP)                                                                            \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter,              \
                      DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, ds->walk.walk_threshold, a.stack_levels,      \
                      (uint32_t)p.bvh_pos, (const FlatNode4*)nullptr, p.tri_base, 0u, p.top)
-#define LAUNCH_VOTE(FEAT, DIAGF) do { if (ring) { LAUNCH_VOTE2(FEAT, DIAGF, true); } else { LAUNCH_VOTE2(FEAT, DIAGF, false); } } while (0)
-  if (diag && a.preset == 0) {
+#define LAUNCH_VOTE2(FEAT, RINGF) with_map(a, [&](auto map) { LAUNCH_VOTE3(FEAT, false, RINGF, map); })
+#define LAUNCH_VOTE(FEAT) do { if (ring) { LAUNCH_VOTE2(FEAT, true); } else { LAUNCH_VOTE2(FEAT, false); } } while (0)
+  if (diag && a.preset == 0) {  // (the diagnostic instantiations exist for the shard's map only)
     unsigned long long h[24];
     static const char* const names[6] = {"outer", "regen", "node_step", "leaf_step", "shade_hit", "walking"};
-    return run_diag(ds, a.stream, [&] { LAUNCH_VOTE(P_SPHERES, true); }, "vote_diag", 10, names, 6, h);
+    return run_diag(ds, a.stream, [&] {
+      if (ring) { LAUNCH_VOTE3(P_SPHERES, true, true, a.sm); } else { LAUNCH_VOTE3(P_SPHERES, true, false, a.sm); }
+    }, "vote_diag", 10, names, 6, h);
   }
-  if (a.preset == 0) { LAUNCH_VOTE(P_SPHERES, false); }
-  else { LAUNCH_VOTE(P_MESH, false); }
+  if (a.preset == 0) { LAUNCH_VOTE(P_SPHERES); }
+  else { LAUNCH_VOTE(P_MESH); }
 #undef LAUNCH_VOTE
 #undef LAUNCH_VOTE2
+#undef LAUNCH_VOTE3
   return RTX_OK;
 }
 
@@ -639,17 +652,18 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   const int family = has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1));
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[family][wide ? 1 : 0]);
   const rt::SceneView& v = ds->view;
-#define LAUNCH_WORLD2(FEAT, WIDEF, DIAGF)                                                                                   \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<FEAT, WIDEF, WORLD_WPS, DIAGF>), dim3(grid), dim3(TRACE_BLOCK), lds, a.stream, \
-                     v, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, v.entries, v.top_level, v.spheres, \
+#define LAUNCH_WORLD3(FEAT, WIDEF, DIAGF, MAP)                                                                               \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<FEAT, WIDEF, WORLD_WPS, DIAGF, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
+                     a.stream, v, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter, v.entries, v.top_level, v.spheres, \
                      v.moving_spheres, v.rects, v.triangles, v.materials, v.textures, v.refs, ds->wide.nodes4, p.desc,     \
                      ds->walk.leaf_weight, ds->sw.world_threshold, levels, p.perlin_lds, p.mat_lds, p.tex_lds,             \
                      DIAGF ? ds->ws.diag : nullptr)
-#define LAUNCH_WORLD(FEAT) do { if (wide) { LAUNCH_WORLD2(FEAT, true, false); } else { LAUNCH_WORLD2(FEAT, false, false); } } while (0)
-  if (ds->sw.kernel == ForcedKernel::world && ds->sw.diag && book2 && wide) {
+#define LAUNCH_WORLD2(FEAT, WIDEF) with_map(a, [&](auto map) { LAUNCH_WORLD3(FEAT, WIDEF, false, map); })
+#define LAUNCH_WORLD(FEAT) do { if (wide) { LAUNCH_WORLD2(FEAT, true); } else { LAUNCH_WORLD2(FEAT, false); } } while (0)
+  if (ds->sw.kernel == ForcedKernel::world && ds->sw.diag && book2 && wide && !a.active) {  // (uniform passes only)
     unsigned long long h[24];
     static const char* const names[8] = {"node_step", "leaf_step", "sweep", "shade(lean)", "regen", "direct_entry(all)", "direct_entry(run)", "shade(rare)"};
-    return run_diag(ds, a.stream, [&] { LAUNCH_WORLD2(P_BOOK2, true, true); }, "world_diag", 18, names, 8, h);
+    return run_diag(ds, a.stream, [&] { LAUNCH_WORLD3(P_BOOK2, true, true, a.sm); }, "world_diag", 18, names, 8, h);
   }
   if (has_gravity) { LAUNCH_WORLD(P_ALL); }  // the bouncing-ball scene: the instantiation that carries GravitySphere code
   else if (book2) { LAUNCH_WORLD(P_BOOK2); }
@@ -657,6 +671,7 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   else { LAUNCH_WORLD(P_ANY); }
 #undef LAUNCH_WORLD
 #undef LAUNCH_WORLD2
+#undef LAUNCH_WORLD3
   return RTX_OK;
 }
 
@@ -726,10 +741,12 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
     // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
     // scenes uploaded earlier (with other LDS sizes) keep launching
     hipError_t ae = hipSuccess;
-#define LDS_ATTR(FEAT, RINGF, MOTIONF) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)k_trace_lds<FEAT, RINGF, MOTIONF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
+#define LDS_ATTR1(K) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
+#define LDS_ATTR(FEAT, RINGF, MOTIONF) LDS_ATTR1((k_trace_lds<FEAT, RINGF, MOTIONF>)); LDS_ATTR1((k_trace_lds<FEAT, RINGF, MOTIONF, ActiveMap>))
     LDS_ATTR(P_SPHERES, true, 0u); LDS_ATTR(P_SPHERES, false, 0u); LDS_ATTR(P_STATIC_SPHERES, true, 0u); LDS_ATTR(P_STATIC_SPHERES, false, 0u);
     LDS_ATTR(P_SPHERES, true, 1u); LDS_ATTR(P_SPHERES, false, 1u); LDS_ATTR(P_SPHERES, true, 3u); LDS_ATTR(P_SPHERES, false, 3u);
 #undef LDS_ATTR
+#undef LDS_ATTR1
     if (ae != hipSuccess) { (void)hipGetLastError(); p.plain.ok = false; }
   }
   if (sw.scene_lds >= 0) {
@@ -753,10 +770,12 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
   const uint32_t grid = grid_size(a.total, LDSK_BLOCK, (uint64_t)ds->n_cu);
   const WalkTuning& wk = ds->walk;
 #define LAUNCH_LDS2(FEAT, RINGF, MOTIONF)                                                                               \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF>), dim3(grid), dim3(LDSK_BLOCK), L.total, a.stream, \
-                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, a.work_counter, wk.leaf_weight,       \
-                     wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,    \
-                     m_t0, m_inv, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1)
+  with_map(a, [&](auto map) {                                                                                           \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, decltype(map)>), dim3(grid), dim3(LDSK_BLOCK), L.total, \
+                       a.stream, ds->view, a.rp, map, a.s_begin, a.total, a.npix, a.samples, a.work_counter, wk.leaf_weight, \
+                       wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,  \
+                       m_t0, m_inv, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1);                        \
+  })
 #define LAUNCH_LDS(FEAT, MOTIONF) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF); } else { LAUNCH_LDS2(FEAT, false, MOTIONF); } } while (0)
   // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
   if ((a.feat & ~P_STATIC_SPHERES) == 0) { LAUNCH_LDS(P_STATIC_SPHERES, 0u); }
@@ -772,16 +791,18 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
 template <bool COUNT>
 static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
-#define LAUNCH_SIMPLE(FEAT)                                                                                             \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT>), dim3(grid), dim3(TRACE_BLOCK), a.stack_lds, a.stream, \
-                     ds->view, a.rp, a.sm, a.s_begin, a.total, a.npix, a.samples, ds->ws.counters)
-  if constexpr (COUNT) { LAUNCH_SIMPLE(P_ALL); }
+#define LAUNCH_SIMPLE2(FEAT, MAP)                                                                                       \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), a.stack_lds, \
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, ds->ws.counters)
+#define LAUNCH_SIMPLE(FEAT) with_map(a, [&](auto map) { LAUNCH_SIMPLE2(FEAT, map); })
+  if constexpr (COUNT) { LAUNCH_SIMPLE2(P_ALL, a.sm); }  // (counting renders are never adaptive)
   else {
     if (a.preset == 0) { LAUNCH_SIMPLE(P_SPHERES); }
     else if (a.preset == 1) { LAUNCH_SIMPLE(P_MESH); }
     else { LAUNCH_SIMPLE(P_ALL); }
   }
 #undef LAUNCH_SIMPLE
+#undef LAUNCH_SIMPLE2
 }
 
 // ------------------------------------------------------------------ wavefront integrator
@@ -843,7 +864,10 @@ static rtx_status wave_pass(DeviceScene* ds, const PassArgs& a) {
   uint32_t check_every = ds->sw.wf_check;
   int it = 0;
   for (;; ++it) {
-    hipLaunchKernelGGL(k_wf_generate, dim3(n_seg), dim3(WF_SEG), 0, stream, pool, a.rp, a.sm, a.s_begin, a.total, a.npix);
+    with_map(a, [&](auto map) {
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_generate<decltype(map)>), dim3(n_seg), dim3(WF_SEG), 0, stream, pool, a.rp, map,
+                         a.s_begin, a.total, a.npix);
+    });
     if ((uint32_t)(it + 1) % check_every == 0u) {
       HIP_TRY(hipMemsetAsync(pool.ctrl, 0, 16, stream));
       hipLaunchKernelGGL(k_wf_count, dim3(256), dim3(256), 0, stream, pool);
@@ -902,10 +926,14 @@ static int32_t choose_trace_kernel(const DeviceScene* ds, int preset, bool count
 // The slice of a frame's samples one call traces (progressive rendering, progressive.inc): the absolute sample indices
 // [first, first + count), added onto the sums already in the accumulator when cont != 0, with the per-pixel sum of
 // squares kept in sumsq when it is not NULL.  A render without one (range == NULL) is the whole frame from sample 0.
+// An adaptive range (active != NULL: the ascending list of the n_active local pixels still active) traces those pixels only;
+// they replace the shard's pixels as the items of every pass (pass_items.inc), and it needs cont and sumsq.
 struct SampleRange {
   uint32_t first, count;
   int cont;
   double* sumsq;
+  const uint32_t* active;
+  uint32_t n_active;
 };
 
 // How one render is cut into passes: samples of every pixel per pass, passes two deep or not, bytes of the sample buffer.
@@ -1016,9 +1044,15 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
 
   const uint32_t s_first = range ? range->first : 0u;
   const uint32_t spp = range ? range->count : (uint32_t)cfg->samples_per_pixel;  // samples of every pixel this call traces
+  const bool adaptive = range && range->active;
+  if (adaptive && (!range->cont || !range->sumsq || d_rgb8_out || range->n_active > npix)) {
+    set_error("render: an adaptive sample range continues S and Q of at most the shard's pixels");
+    return RTX_EINVAL;
+  }
+  const uint64_t nitem = adaptive ? range->n_active : npix;  // pixels of every sample of a pass
   double* accum = d_accum_out;
   PassPlan pp;
-  st = prepare_workspace(ds, cfg, npix, npix_all, spp, COUNT || stats != nullptr, stream, &accum, &pp);
+  st = prepare_workspace(ds, cfg, nitem, npix_all, spp, COUNT || stats != nullptr, stream, &accum, &pp);
   if (st != RTX_OK) return st;
   Workspace& ws = ds->ws;
   if (COUNT) HIP_TRY(hipMemsetAsync(ws.counters, 0, sizeof(rt::TraceCounters), stream));
@@ -1035,12 +1069,12 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   const uint32_t feat = ds->view.features;
   const int preset = ((feat & ~P_SPHERES) == 0) ? 0 : (((feat & ~P_MESH) == 0) ? 1 : 2);
   const int32_t kernel = choose_trace_kernel(ds, preset, COUNT);
-  PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)npix, nullptr, nullptr, stream,
-                preset, feat, stack_levels, stack_bytes(stack_levels)};
+  PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)nitem, nullptr, nullptr, stream,
+                preset, feat, stack_levels, stack_bytes(stack_levels), adaptive ? range->active : nullptr};
 
   float trace_ms = 0.f;
   int passes = 0;
-  if (npix > 0) {
+  if (nitem > 0) {
     // Passes two deep: even passes on the caller's stream, odd ones on ws.aux_stream, each with its own half of the sample
     // buffer and its own work counter.  Within a stream: trace(k), reduce(k), trace(k + 2), ... -- so a half is not overwritten
     // before it has been summed; across streams reduce(k) waits for reduce(k - 1) -- so every pixel's samples are still added in
@@ -1054,9 +1088,9 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       const int half = pp.pipeline ? (passes & 1) : 0;
       const uint32_t s_count = spp - s_off < pp.spp_pass ? spp - s_off : pp.spp_pass;
       a.s_begin = s_first + s_off;  // absolute index of the pass's first sample: the key of its random streams
-      a.total = (uint32_t)((uint64_t)s_count * npix);
+      a.total = (uint32_t)((uint64_t)s_count * nitem);
       a.stream = half ? ws.aux_stream : stream;  // every launch of the pass goes to this stream
-      a.samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)npix * 3u;
+      a.samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)nitem * 3u;
       a.work_counter = ws.work_counter + half;
       if (stats) HIP_TRY(hipEventRecord(ws.ev[0], a.stream));
       switch (kernel) {
@@ -1075,10 +1109,13 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
         HIP_TRY(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]));
         trace_ms += ms;
       }
-      uint32_t pgrid = (uint32_t)((npix + 255) / 256);
+      uint32_t pgrid = (uint32_t)((nitem + 255) / 256);
       if (pp.pipeline && passes > 0) HIP_TRY(hipStreamWaitEvent(a.stream, ws.ev_pass[1 - half], 0));  // the previous pass's sums are in
       const int first_pass = s_off == 0 && !(range && range->cont) ? 1 : 0;
-      if (range && range->sumsq)
+      if (adaptive)
+        hipLaunchKernelGGL(k_reduce_samples_moments_active, dim3(pgrid), dim3(256), 0, a.stream, a.samples, accum, range->sumsq,
+                           range->active, (uint32_t)nitem, s_count);
+      else if (range && range->sumsq)
         hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, a.stream, a.samples, accum, range->sumsq,
                            (uint32_t)npix, s_count, first_pass);
       else
@@ -1100,7 +1137,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
     stats->passes = passes;
     stats->trace_kernel = passes > 0 ? kernel : RTX_KERNEL_SIMPLE;  // (nothing traced: no kernel ran)
     stats->sample_buffer_bytes = pp.sample_bytes;
-    stats->samples = (uint64_t)spp * npix;  // (pixel, sample) paths this call traced; the work counters below only in count mode
+    stats->samples = (uint64_t)spp * nitem;  // (pixel, sample) paths this call traced; the work counters below only in count mode
     if (COUNT) {
       rt::TraceCounters c;
       HIP_TRY(hipMemcpy(&c, ws.counters, sizeof(c), hipMemcpyDeviceToHost));
@@ -1117,6 +1154,15 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
 static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, uint32_t npix, uint32_t spp, hipStream_t stream) {
   if (npix == 0) return RTX_OK;
   hipLaunchKernelGGL(k_tonemap, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, npix, spp);
+  HIP_TRY(hipGetLastError());
+  return RTX_OK;
+}
+
+// The same for an adaptive frame: pixel lp holds counts[lp] samples, or spp where that is 0 (still active).
+static rtx_status tonemap_counts_impl(const double* accum, uint8_t* rgb8, const int32_t* counts, uint32_t npix, uint32_t spp,
+                                      hipStream_t stream) {
+  if (npix == 0) return RTX_OK;
+  hipLaunchKernelGGL(k_tonemap_counts, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, counts, npix, spp);
   HIP_TRY(hipGetLastError());
   return RTX_OK;
 }

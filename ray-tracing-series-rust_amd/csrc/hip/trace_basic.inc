@@ -17,9 +17,9 @@ constexpr uint32_t P_ANY = rt::F_ALL & ~rt::F_GRAVITY_SPHERE;    // any world of
 // Straightforward form: grid-stride over the pass's (sample, pixel) index space (pass_items.inc), one whole
 // path per loop iteration.
 // Kept as the instrumented (COUNT) build and as the plainest kernel to force (RTX_TRACE_KERNEL=simple).
-template <uint32_t F, bool COUNT>
+template <uint32_t F, bool COUNT, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_simple(rt::SceneView sv, rt::RenderParams rp,
-                                                               ShardMap sm, uint32_t s_begin,
+                                                               SM sm, uint32_t s_begin,
                                                                uint32_t total, uint32_t npix,
                                                                double* __restrict__ samples,
                                                                rt::TraceCounters* counters) {

@@ -71,8 +71,8 @@ __host__ __device__ __forceinline__ int32_t ldsk_item(int32_t child) {
 // time s before the slab test.  Only launched when the camera's shutter lies inside that interval (render.hip).
 // MOTION = 1: slopes for every axis; MOTION = 2 + a: every moving sphere of the scene moves along axis a alone (Book-1 at HEAD: y), so only
 // that axis's planes carry slopes -- 4 fmas and 4 LDS dwords per child pair instead of 12 and 12, node records of 27 dwords.
-template <uint32_t F, bool RING, uint32_t MOTION>
-__global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::RenderParams rp, ShardMap sm,
+template <uint32_t F, bool RING, uint32_t MOTION, class SM = ShardMap>
+__global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::RenderParams rp, SM sm,
                                                           uint32_t s_begin, uint32_t total, uint32_t npix,
                                                           double* __restrict__ samples, unsigned int* work_counter,
                                                           uint32_t leaf_weight, uint32_t walk_threshold, uint32_t chunk, uint32_t ring_cap,

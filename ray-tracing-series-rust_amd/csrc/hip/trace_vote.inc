@@ -257,9 +257,9 @@ __device__ __forceinline__ void walk_node_step4(const FlatNode4* __restrict__ no
 // when the ring cannot serve the request does the whole wave run the regeneration code, all lanes at
 // once, to top the ring up.  Which lane traces a sample is invisible in the result.
 // (VoteTop, the plain entries beside the BVH as a kernel argument, is declared in render.hip next to DeviceScene.)
-template <uint32_t F, bool DIAG, bool RING, bool WIDE>
+template <uint32_t F, bool DIAG, bool RING, bool WIDE, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv, rt::RenderParams rp,
-                                                            ShardMap sm, uint32_t s_begin, uint32_t total,
+                                                            SM sm, uint32_t s_begin, uint32_t total,
                                                             uint32_t npix, double* __restrict__ samples,
                                                             unsigned int* work_counter,
                                                             unsigned long long* diag, uint32_t leaf_weight,

@@ -87,7 +87,8 @@ __global__ __launch_bounds__(256) void k_wf_count(WavePool pool) {
 }
 
 // Segment b refills its free slots: its m-th sample is sample ((m / 64) * n_seg + b) * 64 + m % 64 of the pass.
-__global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::RenderParams rp, ShardMap sm, uint32_t s_begin, uint32_t total,
+template <class SM>
+__global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total,
                                                         uint32_t npix) {
   const uint32_t b = blockIdx.x, k = threadIdx.x, n_seg = gridDim.x;
   const uint32_t n_free = pool.n_free[b], cur = pool.cursor[b];

@@ -151,9 +151,9 @@ __device__ __forceinline__ bool direct_closest(const rt::SceneView& sv, const rt
 }
 
 // DIAG: per-region counters (executions by the wave, lanes taking part) -- diagnostic build only (RTX_TRACE_KERNEL=world_diag).
-template <uint32_t F, bool WIDE, int WAVES_PER_SIMD, bool DIAG = false>
+template <uint32_t F, bool WIDE, int WAVES_PER_SIMD, bool DIAG = false, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
-    rt::SceneView sv_in, rt::RenderParams rp, ShardMap sm, uint32_t s_begin, uint32_t total, uint32_t npix,
+    rt::SceneView sv_in, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total, uint32_t npix,
     double* __restrict__ samples, unsigned int* __restrict__ work_counter, const rt::FlatEntry* __restrict__ entries_ro,
     const int32_t* __restrict__ top_level_ro, const rt::FlatSphere* __restrict__ spheres_ro,
     const rt::FlatMovingSphere* __restrict__ msph_ro, const rt::FlatRect* __restrict__ rects_ro,

@@ -12,6 +12,7 @@
 //   get_world_cam(id) -> (world, cam, background)       get_world_cam(s, id)
 //   render_scene(world, cam, background, config)        render_scene(s, world, cam, background, config)
 #pragma once
+#include <cstdio>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -180,8 +181,18 @@ struct Screen {  // screen.rs:6-59, row 0 = bottom row
   int width = 0, height = 0;
   std::vector<uint8_t> rgb8;
   std::vector<double> accum;
+  std::vector<int32_t> spp;  // samples of each pixel (adaptive progressive renders only)
   void write_to_ppm() const { check(rtx_write_ppm(nullptr, width, height, rgb8.data())); }
   void write_to_ppm_file(const char* path) const { check(rtx_write_ppm(path, width, height, rgb8.data())); }
+  // The sample counts as a plain PGM ("P2"), top row first like the PPM, maxval = the budget.
+  void write_spp_pgm_file(const char* path, int32_t budget) const {
+    FILE* f = fopen(path, "w");
+    if (!f) throw Error(RTX_EIO, std::string("cannot open ") + path);
+    fprintf(f, "P2\n%d %d\n%d\n", width, height, budget);
+    for (int j = height - 1; j >= 0; --j)
+      for (int i = 0; i < width; ++i) fprintf(f, "%d\n", spp[(size_t)j * width + i]);
+    if (fclose(f) != 0) throw Error(RTX_EIO, std::string("cannot write ") + path);
+  }
 };
 
 struct WorldCam {
@@ -265,6 +276,38 @@ inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& c
   }
   if (st == RTX_OK) st = rtx_progressive_read(prog, &frame, nullptr);
   if (stats_out) *stats_out = ns;
+  rtx_progressive_destroy(prog);
+  rtx_scene_destroy(scene);
+  check(st);
+  return scr;
+}
+
+// render_scene refined adaptively (rtx_progressive_until_adaptive): rounds of `batch` samples in which the pixels whose relative
+// error is at most target_rel_err (checked from min_spp samples on) stop receiving samples.  The Screen's spp holds each
+// pixel's count.
+inline Screen render_scene_adaptive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
+                                    int batch, int min_spp, double target_rel_err, RtxAdaptiveStats* stats_out = nullptr) {
+  config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
+  rtx_flat* flat = nullptr;
+  check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
+  rtx_scene* scene = nullptr;
+  rtx_status st = rtx_scene_upload(flat, &scene);
+  rtx_flat_destroy(flat);
+  check(st);
+  rtx_progressive* prog = nullptr;
+  st = rtx_progressive_create(scene, &cam.c, &config.c, nullptr, &prog);
+  Screen scr;
+  scr.width = config.c.image_width;
+  scr.height = rtx_image_height(&config.c);
+  scr.rgb8.resize((size_t)scr.width * scr.height * 3);
+  scr.accum.resize((size_t)scr.width * scr.height * 3);
+  scr.spp.resize((size_t)scr.width * scr.height);
+  RtxFrame frame = {scr.accum.data(), scr.rgb8.data()};
+  RtxAdaptiveStats as = {};
+  if (st == RTX_OK) st = rtx_progressive_until_adaptive(prog, batch, min_spp, target_rel_err, &as);
+  if (st == RTX_OK) st = rtx_progressive_read(prog, &frame, nullptr);
+  if (st == RTX_OK) st = rtx_progressive_pixel_spp(prog, scr.spp.data());
+  if (stats_out) *stats_out = as;
   rtx_progressive_destroy(prog);
   rtx_scene_destroy(scene);
   check(st);

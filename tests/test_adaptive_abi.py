@@ -1,0 +1,79 @@
+"""Adaptive sampling's C ABI and Python surface, without a GPU: symbols, struct layout, argument checks, app flags."""
+import ctypes as C
+import math
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+APP = os.path.join(ROOT, "ray-tracing-series-rust_amd", "lib", "rtx_render")
+ADAPTIVE = ["rtx_progressive_add_adaptive", "rtx_progressive_until_adaptive", "rtx_progressive_pixel_spp"]
+
+
+def test_adaptive_symbols_are_declared_exported_and_bound(rtsr):
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rtx_abi.h")).read(), flags=re.S)
+    declared = set(re.findall(r"\b(rtx_[a-z0-9_]+)\s*\(", text))
+    lib = C.CDLL(rtsr.LIB_PATH)
+    for name in ADAPTIVE:
+        assert name in declared and hasattr(lib, name) and name in rtsr.ABI, name
+    assert "} RtxAdaptiveStats;" in text
+    blob = open(rtsr.LIB_PATH, "rb").read()
+    for kernel in (b"k_reduce_samples_moments_active", b"k_noise_stats_counts", b"k_tonemap_counts", b"k_retire_flag",
+                   b"k_retire_scan", b"k_retire_scatter"):
+        assert kernel in blob, kernel
+
+
+def test_adaptive_stats_layout(rtsr):
+    s = rtsr.RtxAdaptiveStats
+    assert C.sizeof(s) == 56
+    assert [(n, getattr(s, n).offset) for n, _ in s._fields_] == [
+        ("spp_done", 0), ("min_spp", 4), ("pixels", 8), ("pixels_active", 12), ("pixels_above", 16), ("reserved", 20),
+        ("samples", 24), ("max_rel_err", 32), ("mean_rel_err", 40), ("target_rel_err", 48)]
+    assert s.samples.size == 8
+
+
+def test_null_handles_are_rejected_without_a_device(rtsr):
+    lib = rtsr.lib
+    st = rtsr.RtxAdaptiveStats()
+    counts = (C.c_int32 * 4)()
+    assert lib.rtx_progressive_add_adaptive(None, 4, 2, 0.1, None, None) == rtsr.RTX_EINVAL
+    assert "NULL handle" in rtsr.last_error()
+    assert lib.rtx_progressive_until_adaptive(None, 8, 2, 0.1, C.byref(st)) == rtsr.RTX_EINVAL
+    assert "NULL handle" in rtsr.last_error()
+    assert lib.rtx_progressive_pixel_spp(None, counts) == rtsr.RTX_EINVAL
+    assert "NULL handle" in rtsr.last_error()
+
+
+@pytest.mark.parametrize("n,min_spp,target", [(0, 2, 0.1), (-1, 2, 0.1), (4, 1, 0.1), (4, 0, 0.1), (4, 2, -0.5),
+                                              (4, 2, float("nan")), (4, 2, -math.inf)])
+def test_bad_adaptive_arguments_on_a_null_handle(rtsr, n, min_spp, target):
+    # a live handle needs a device: here the NULL handle is reported whatever else is wrong; tests/test_gpu_adaptive.py
+    # checks each argument on a live handle and that nothing was traced
+    assert rtsr.lib.rtx_progressive_add_adaptive(None, n, min_spp, target, None, None) == rtsr.RTX_EINVAL
+    st = rtsr.RtxAdaptiveStats()
+    assert rtsr.lib.rtx_progressive_until_adaptive(None, n, min_spp, target, C.byref(st)) == rtsr.RTX_EINVAL
+
+
+def test_python_front_ends_exist(rtsr):
+    for name in ("add_adaptive", "until_adaptive", "pixel_spp"):
+        assert callable(getattr(rtsr.Progressive, name, None)), name
+    import inspect
+    params = inspect.signature(rtsr.render_scene_progressive).parameters
+    assert params["adaptive"].default is False and "min_spp" in params
+
+
+BASE = ["--scene", "10", "--width", "16", "--spp", "8"]
+
+
+@pytest.mark.parametrize("args", [["--adaptive"], ["--adaptive", "--batch", "4"], ["--adaptive", "--target-error", "0.1"],
+                                  ["--adaptive", "--batch", "4", "--target-error", "0.1", "--min-spp", "1"],
+                                  ["--adaptive", "--batch", "4", "--target-error", "0.1", "--min-spp", "9"],
+                                  ["--batch", "4", "--target-error", "0.1", "--min-spp", "4"],
+                                  ["--batch", "4", "--target-error", "0.1", "--spp-map", "x.pgm"],
+                                  ["--adaptive", "--batch", "4", "--target-error", "0.1", "--snapshot-every", "4", "--out", "x.ppm"]])
+def test_app_rejects_incomplete_adaptive_flags(tmp_path, args):
+    assert os.path.exists(APP), "apps/rtx_render was not built (python __graft_entry__.py)"
+    res = subprocess.run([APP] + BASE + args, capture_output=True, text=True, timeout=60, cwd=str(tmp_path))
+    assert res.returncode == 2 and "--" in res.stderr, (res.returncode, res.stderr)
