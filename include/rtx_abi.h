@@ -301,7 +301,8 @@ rtx_status rtx_progressive_add(rtx_progressive* p, int32_t n_samples, void* hip_
  * rtx_render_device's shard layout.  Needs spp_done >= 1. */
 rtx_status rtx_progressive_read(const rtx_progressive* p, RtxFrame* out, double* sumsq_rgb);
 /* Blocking.  Per active pixel and channel, with n = spp_done >= 2:  m = S/n,  var = max(0, (Q - S*S/n) / (n - 1)),
- * se = sqrt(var / n),  r_c = se / (m + 1/256);  the pixel's r = max_c r_c.  Reports max r, mean r and the count of
+ * se = sqrt(var / n),  r_c = se / (m + 1/256);  the pixel's r = max(0, max_c r_c), where a NaN r_c is ignored (a pixel
+ * whose every r_c is NaN has r = 0).  Reports max r, mean r and the count of
  * r > target_rel_err (>= 0), reduced in a fixed order: the same bits on every call.  Once a pixel has retired (adaptive
  * rounds below), each pixel's r is taken at its own count n_p. */
 rtx_status rtx_progressive_stats(rtx_progressive* p, double target_rel_err, RtxNoiseStats* out);
@@ -369,6 +370,18 @@ rtx_status rtx_write_ppm(const char* path, int32_t width, int32_t height, const 
  * (clamp into [y, 3e38] with NaN -> y).  rtx_device_stream: the first n uniforms of the (seed, pixel, sample) stream. */
 rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t n, double* out);
 rtx_status rtx_device_stream(uint64_t seed, uint64_t pixel, uint32_t sample, int32_t n, double* out);
+/* The adaptive retirement check of rtx_progressive_add_adaptive (k_retire_flag / _scan / _scatter) on host arrays, through
+ * the handle's own launch sequence.  S, Q: npix*3; active: n strictly ascending local pixels < npix; counts: npix, in/out
+ * (spp at every pixel of the list with r <= target at n = spp, the rest unchanged); next: n, out (the others in order, the
+ * first *kept valid).  Blocking. */
+rtx_status rtx_device_retire(const double* S, const double* Q, uint32_t npix, const uint32_t* active, uint32_t n,
+                             uint32_t spp, double target, int32_t* counts, uint32_t* next, uint32_t* kept);
+/* The noise reduction of rtx_progressive_stats over npix pixels: k_noise_stats (counts NULL: every pixel at n = spp) or
+ * k_noise_stats_counts (pixel lp at n = counts[lp], or spp where that is 0), then k_noise_stats_final.  Blocking.
+ * Both entries: NULL pointers (counts excepted), spp < 2 and a negative or NaN target are RTX_EINVAL before any device
+ * call; n = 0 or npix = 0 is RTX_OK with nothing kept or reduced. */
+rtx_status rtx_device_noise_reduce(const double* S, const double* Q, const int32_t* counts, uint32_t npix, uint32_t spp,
+                                   double target, double* max_r, double* sum_r, uint64_t* above);
 
 /* Opaque pass-through for the CPU checkers under oracle/ (test infrastructure; not a render path). */
 const void* rtx_builder_graph(const rtx_builder* b);

@@ -163,6 +163,10 @@ ABI = {
     "rtx_write_ppm": (C.c_int32, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rtx_device_math": (C.c_int32, [C.c_int32, _D3, _D3, C.c_int64, _D3]),
     "rtx_device_stream": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _D3]),
+    "rtx_device_retire": (C.c_int32, [_D3, _D3, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_double,
+                                      C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "rtx_device_noise_reduce": (C.c_int32, [_D3, _D3, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_double, _D3, _D3,
+                                            C.POINTER(C.c_uint64)]),
     "rtx_progressive_create": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxShard), C.POINTER(_VP)]),
     "rtx_progressive_destroy": (None, [_VP]),
     "rtx_progressive_spp": (C.c_int32, [_VP]),
@@ -614,6 +618,45 @@ def device_stream(seed, pixel, sample, n):
     out = np.empty(n, dtype=np.float64)
     _check(lib.rtx_device_stream(seed, pixel, sample, n, out.ctypes.data_as(_D3)))
     return out
+
+
+def _moments_arg(S, Q):
+    S = np.ascontiguousarray(S, dtype=np.float64).reshape(-1, 3)
+    Q = np.ascontiguousarray(Q, dtype=np.float64).reshape(-1, 3)
+    if S.shape != Q.shape:
+        raise ValueError("S and Q must have the same shape")
+    return S, Q
+
+
+def device_retire(S, Q, active, spp, target, counts):
+    """One adaptive retirement check on the GPU (see rtx_device_retire) over the pixels of S, Q (npix x 3 or rows x w x 3).
+    -> (the ascending list of the pixels kept active, counts after the check); the inputs are not changed."""
+    S, Q = _moments_arg(S, Q)
+    active = np.ascontiguousarray(active, dtype=np.uint32).ravel()
+    counts = np.array(counts, dtype=np.int32).ravel()  # a copy: written in place
+    if counts.size != S.shape[0]:
+        raise ValueError("counts must hold one entry per pixel")
+    nxt = np.zeros(max(active.size, 1), dtype=np.uint32)
+    kept = C.c_uint32()
+    u32 = C.POINTER(C.c_uint32)
+    _check(lib.rtx_device_retire(S.ctypes.data_as(_D3), Q.ctypes.data_as(_D3), S.shape[0], active.ctypes.data_as(u32),
+                                 active.size, spp, target, counts.ctypes.data_as(C.POINTER(C.c_int32)), nxt.ctypes.data_as(u32),
+                                 C.byref(kept)))
+    return nxt[:kept.value].copy(), counts
+
+
+def device_noise_reduce(S, Q, spp, target, counts=None):
+    """The noise reduction of rtx_progressive_stats on the GPU (see rtx_device_noise_reduce) -> (max r, sum r, count above)."""
+    S, Q = _moments_arg(S, Q)
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, dtype=np.int32).ravel()
+        if counts.size != S.shape[0]:
+            raise ValueError("counts must hold one entry per pixel")
+    max_r, sum_r, above = C.c_double(), C.c_double(), C.c_uint64()
+    _check(lib.rtx_device_noise_reduce(S.ctypes.data_as(_D3), Q.ctypes.data_as(_D3),
+                                       counts.ctypes.data_as(C.POINTER(C.c_int32)) if counts is not None else None,
+                                       S.shape[0], spp, target, C.byref(max_r), C.byref(sum_r), C.byref(above)))
+    return max_r.value, sum_r.value, above.value
 
 
 def shard_rows(cfg, shard):

@@ -92,7 +92,7 @@ __device__ __forceinline__ double pixel_rel_err(const double* __restrict__ S, co
     var = var > 0.0 ? var : 0.0;
     const double se = __dsqrt_rn(__ddiv_rn(var, n));
     const double rc = __ddiv_rn(se, __dadd_rn(m, 1.0 / 256.0));
-    r = rc > r ? rc : r;
+    r = rc > r ? rc : r;  // a NaN rc is ignored
   }
   return r;
 }
@@ -186,7 +186,7 @@ __global__ __launch_bounds__(256) void k_retire_flag(const double* __restrict__ 
   if (k < n) {
     const uint32_t lp = active[k];
     const double r = pixel_rel_err(S, Q, lp, (double)spp);
-    keep = !(r <= target);  // (a NaN r stays active)
+    keep = !(r <= target);  // (r is never NaN: pixel_rel_err ignores a NaN channel, so an all-NaN pixel has r = 0)
     if (!keep) counts[lp] = (int32_t)spp;
   }
   const unsigned long long m = __ballot(keep);
@@ -267,7 +267,8 @@ __global__ __launch_bounds__(256) void k_tonemap_counts(const double* __restrict
   rgb8[3 * (size_t)lp + 2] = (uint8_t)c[2];
 }
 
-// Device self-test kernels (rtx_device_math / rtx_device_stream).
+// Device self-test kernels (rtx_device_math / rtx_device_stream; rtx_device_retire and rtx_device_noise_reduce run the
+// kernels above through progressive.inc's launch helpers).
 __global__ void k_device_math(int fn, const double* x, const double* y, long long n, double* out) {
   long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;

@@ -27,8 +27,7 @@ struct rtx_progressive {
   bool broken;        // a failed add left S / Q partly updated
   double* S;
   double* Q;
-  NoisePartial* partials;  // one per 256 active pixels, then the final result
-  uint32_t n_partials;
+  NoisePartial* partials;  // one per 256 active pixels, then the final result (noise_partials_alloc)
   // adaptive state, allocated by the first adaptive call (a uniform handle keeps its 48 bytes per pixel)
   bool adaptive;
   int cur;                  // active[cur]: the ascending list of the n_active local pixels still active
@@ -71,21 +70,34 @@ rtx_status progressive_add(rtx_progressive* p, int32_t n_samples, hipStream_t st
 
 bool any_retired(const rtx_progressive* p) { return p->adaptive && p->n_active < p->npix; }
 
-// Reduces r over the shard's active pixels into partials[n_partials] (each pixel at its own n_p once one has retired).
+// The noise reduction's partials for npix pixels: one per 256-pixel block, then the final result.
+hipError_t noise_partials_alloc(uint32_t npix, NoisePartial** partials) {
+  return hipMalloc((void**)partials, (((size_t)npix + 255) / 256 + 1) * sizeof(NoisePartial));
+}
+
+// The noise reduction on device arrays, shared by the handle and rtx_device_noise_reduce: k_noise_stats (counts NULL) or
+// k_noise_stats_counts over the npix >= 1 pixels into partials[0, nb), nb = ceil(npix / 256), then k_noise_stats_final
+// into partials[nb] (noise_partials_alloc), copied to *r.  Blocking; runs on the default stream.
+rtx_status noise_reduce_launch(const double* S, const double* Q, const int32_t* counts, uint32_t npix, uint32_t spp,
+                               double target, NoisePartial* partials, NoisePartial* r) {
+  const uint32_t nb = (npix + 255u) / 256u;
+  if (counts)
+    hipLaunchKernelGGL(k_noise_stats_counts, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, S, Q, counts, npix, spp, target,
+                       partials);
+  else
+    hipLaunchKernelGGL(k_noise_stats, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, S, Q, npix, spp, target, partials);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_noise_stats_final, dim3(1), dim3(256), 0, (hipStream_t) nullptr, partials, nb, partials + nb);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(r, partials + nb, sizeof(*r), hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
+// Reduces r over the shard's active pixels (each pixel at its own n_p once one has retired).
 rtx_status noise_reduce(rtx_progressive* p, double target, NoisePartial* r) {
   HIP_TRY(hipDeviceSynchronize());  // the adds ran on the caller's stream
-  if (any_retired(p))
-    hipLaunchKernelGGL(k_noise_stats_counts, dim3(p->n_partials), dim3(256), 0, (hipStream_t) nullptr, p->S, p->Q, p->counts,
-                       p->npix, (uint32_t)p->spp_done, target, p->partials);
-  else
-    hipLaunchKernelGGL(k_noise_stats, dim3(p->n_partials), dim3(256), 0, (hipStream_t) nullptr, p->S, p->Q, p->npix,
-                       (uint32_t)p->spp_done, target, p->partials);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_noise_stats_final, dim3(1), dim3(256), 0, (hipStream_t) nullptr, p->partials, p->n_partials,
-                     p->partials + p->n_partials);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpy(r, p->partials + p->n_partials, sizeof(*r), hipMemcpyDeviceToHost));
-  return RTX_OK;
+  return noise_reduce_launch(p->S, p->Q, any_retired(p) ? p->counts : nullptr, p->npix, (uint32_t)p->spp_done, target,
+                             p->partials, r);
 }
 
 rtx_status progressive_stats(rtx_progressive* p, double target, RtxNoiseStats* out) {
@@ -126,6 +138,37 @@ bool adaptive_args_ok(const rtx_progressive* p, const char* fn, int32_t min_spp,
   return true;
 }
 
+// The retirement check's scratch for lists of up to n pixels (nb = ceil(n / 256) blocks): one ballot per wave (nb * 4, and
+// one spare), the block counts (nb + 1) and their exclusive offsets with the total at [nb] (nb + 1).
+hipError_t retire_scratch_alloc(uint32_t n, unsigned long long** keep_mask, uint32_t** block_count, uint32_t** block_offset) {
+  const uint32_t nb = (n + 255u) / 256u;
+  hipError_t e = hipMalloc((void**)keep_mask, ((size_t)nb * 4 + 1) * 8);
+  if (e == hipSuccess) e = hipMalloc((void**)block_count, ((size_t)nb + 1) * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)block_offset, ((size_t)nb + 1) * 4);
+  return e;
+}
+
+// The retirement check on device arrays, shared by the handle and rtx_device_retire: every pixel of list[0, n) (n >= 1)
+// with r <= target at spp samples gets counts[lp] = spp; the others are compacted, in order, into next[0, *kept).  The
+// scratch comes from retire_scratch_alloc for at least n pixels.  Blocking (the host needs the count).
+rtx_status retire_launch(const double* S, const double* Q, const uint32_t* list, uint32_t n, uint32_t spp, double target,
+                         int32_t* counts, unsigned long long* keep_mask, uint32_t* block_count, uint32_t* block_offset,
+                         uint32_t* next, hipStream_t stream, uint32_t* kept) {
+  const uint32_t nb = (n + 255u) / 256u;
+  hipLaunchKernelGGL(k_retire_flag, dim3(nb), dim3(256), 0, stream, S, Q, list, n, spp, target, counts, keep_mask,
+                     block_count);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(256), 0, stream, block_count, nb, block_offset);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_retire_scatter, dim3(nb), dim3(256), 0, stream, list, n, keep_mask, block_offset, next);
+  HIP_TRY(hipGetLastError());
+  *kept = 0;
+  HIP_TRY(hipMemcpyAsync(kept, block_offset + nb, sizeof(*kept), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (*kept > n) { set_error("progressive: the retirement check counted more pixels than it was given"); return RTX_EHIP; }
+  return RTX_OK;
+}
+
 // Allocates the adaptive buffers on the first adaptive call: every active pixel listed, no count frozen.
 rtx_status adaptive_init(rtx_progressive* p) {
   if (p->adaptive) return RTX_OK;
@@ -134,9 +177,7 @@ rtx_status adaptive_init(rtx_progressive* p) {
   for (uint32_t*& a : p->active)
     if (e == hipSuccess) e = hipMalloc((void**)&a, ((size_t)p->npix + 1) * 4);
   if (e == hipSuccess) e = hipMalloc((void**)&p->counts, ((size_t)p->npix_all + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->keep_mask, ((size_t)nb * 4 + 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->block_count, ((size_t)nb + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->block_offset, ((size_t)nb + 1) * 4);
+  if (e == hipSuccess) e = retire_scratch_alloc(p->npix, &p->keep_mask, &p->block_count, &p->block_offset);
   if (e == hipSuccess) e = hipMemset(p->counts, 0, ((size_t)p->npix_all + 1) * 4);
   if (e == hipSuccess && p->npix) {
     hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, p->active[0], p->npix);
@@ -159,20 +200,11 @@ rtx_status adaptive_init(rtx_progressive* p) {
 // count of every active pixel with r <= target and compacts the list of the others.  Blocking (the host needs the new count).
 rtx_status adaptive_retire_launch(rtx_progressive* p, double target, hipStream_t stream) {
   if (p->n_active == 0) return RTX_OK;
-  const uint32_t n = p->n_active, nb = (n + 255u) / 256u, spp = (uint32_t)p->spp_done;
-  uint32_t* list = p->active[p->cur];
-  uint32_t* next = p->active[1 - p->cur];
-  hipLaunchKernelGGL(k_retire_flag, dim3(nb), dim3(256), 0, stream, p->S, p->Q, list, n, spp, target, p->counts,
-                     p->keep_mask, p->block_count);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(256), 0, stream, p->block_count, nb, p->block_offset);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_retire_scatter, dim3(nb), dim3(256), 0, stream, list, n, p->keep_mask, p->block_offset, next);
-  HIP_TRY(hipGetLastError());
+  const uint32_t n = p->n_active, spp = (uint32_t)p->spp_done;
   uint32_t kept = 0;
-  HIP_TRY(hipMemcpyAsync(&kept, p->block_offset + nb, sizeof(kept), hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  if (kept > n) { set_error("progressive: the retirement check counted more pixels than it was given"); return RTX_EHIP; }
+  const rtx_status st = retire_launch(p->S, p->Q, p->active[p->cur], n, spp, target, p->counts, p->keep_mask, p->block_count,
+                                      p->block_offset, p->active[1 - p->cur], stream, &kept);
+  if (st != RTX_OK) return st;
   p->retired_samples += (uint64_t)(n - kept) * spp;
   p->n_active = kept;
   p->cur = 1 - p->cur;
@@ -228,6 +260,36 @@ rtx_status adaptive_stats(rtx_progressive* p, int32_t min_spp, double target, Rt
   return RTX_OK;
 }
 
+// Device copies of a self-test entry's arrays, freed together.
+struct SelfTestBuffers {
+  std::vector<void*> ptrs;
+  ~SelfTestBuffers() {
+    for (void* d : ptrs) (void)hipFree(d);
+  }
+  template <class T>
+  hipError_t alloc(T** d, size_t count) {
+    *d = nullptr;
+    const hipError_t e = hipMalloc((void**)d, count * sizeof(T) + 8);  // never 0 bytes
+    if (e == hipSuccess) ptrs.push_back((void*)*d);
+    return e;
+  }
+  template <class T>
+  hipError_t upload(T** d, const T* h, size_t count) {
+    hipError_t e = alloc(d, count);
+    if (e == hipSuccess && count) e = hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice);
+    return e;
+  }
+};
+
+// The self-test entries' argument checks (before any device call).
+bool self_test_args_ok(const char* fn, bool pointers, uint32_t npix, uint32_t spp, double target) {
+  if (!pointers) { set_error(std::string(fn) + ": NULL argument"); return false; }
+  if (npix >= (1u << 31)) { set_error(std::string(fn) + ": more than 2^31 pixels"); return false; }
+  if (spp < 2 || spp > (uint32_t)INT32_MAX) { set_error(std::string(fn) + ": spp must be in [2, 2^31)"); return false; }
+  if (!(target >= 0.0)) { set_error(std::string(fn) + ": target must be >= 0"); return false; }
+  return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -250,12 +312,11 @@ rtx_status rtx_progressive_create(const rtx_scene* s, const RtxCamera* cam, cons
   p->shard = sh;
   p->npix_all = (uint32_t)npix_all;
   p->npix = (uint32_t)npix;
-  p->n_partials = (uint32_t)((npix + 255) / 256);
   hipError_t e = hipGetDevice(&p->device);
   const size_t plane = (size_t)npix_all * 24;
   if (e == hipSuccess && plane) e = hipMalloc((void**)&p->S, plane);
   if (e == hipSuccess && plane) e = hipMalloc((void**)&p->Q, plane);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->partials, (p->n_partials + 1) * sizeof(NoisePartial));
+  if (e == hipSuccess) e = noise_partials_alloc(p->npix, &p->partials);
   if (e == hipSuccess && plane) e = hipMemset(p->S, 0, plane);  // rows beyond row_chunk_compat's limit stay zero
   if (e == hipSuccess && plane) e = hipMemset(p->Q, 0, plane);
   if (e != hipSuccess) {
@@ -399,6 +460,73 @@ rtx_status rtx_progressive_pixel_spp(const rtx_progressive* p, int32_t* spp) {
   }
   for (uint32_t lp = 0; lp < p->npix; ++lp)
     if (spp[lp] == 0) spp[lp] = p->spp_done;  // still active
+  return RTX_OK;
+}
+
+rtx_status rtx_device_retire(const double* S, const double* Q, uint32_t npix, const uint32_t* active, uint32_t n,
+                             uint32_t spp, double target, int32_t* counts, uint32_t* next, uint32_t* kept) {
+  const char* fn = "rtx_device_retire";
+  if (!self_test_args_ok(fn, S && Q && active && counts && next && kept, npix, spp, target)) return RTX_EINVAL;
+  *kept = 0;
+  if (n == 0 || npix == 0) return RTX_OK;
+  for (uint32_t k = 0; k < n; ++k)
+    if (active[k] >= npix || (k && active[k] <= active[k - 1])) {
+      set_error(std::string(fn) + ": active must ascend strictly and stay below npix");
+      return RTX_EINVAL;
+    }
+  SelfTestBuffers b;
+  double *dS, *dQ;
+  uint32_t *d_active, *d_next, *block_count = nullptr, *block_offset = nullptr;
+  int32_t* d_counts;
+  unsigned long long* keep_mask = nullptr;
+  const size_t plane = (size_t)npix * 3;
+  hipError_t e = b.upload(&dS, S, plane);
+  if (e == hipSuccess) e = b.upload(&dQ, Q, plane);
+  if (e == hipSuccess) e = b.upload(&d_active, active, n);
+  if (e == hipSuccess) e = b.upload(&d_counts, counts, npix);
+  if (e == hipSuccess) e = b.alloc(&d_next, n);
+  if (e == hipSuccess) {
+    e = retire_scratch_alloc(n, &keep_mask, &block_count, &block_offset);
+    b.ptrs.insert(b.ptrs.end(), {(void*)keep_mask, (void*)block_count, (void*)block_offset});  // (hipFree(NULL) is a no-op)
+  }
+  if (e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  uint32_t got = 0;
+  const rtx_status st = retire_launch(dS, dQ, d_active, n, spp, target, d_counts, keep_mask, block_count, block_offset,
+                                      d_next, (hipStream_t) nullptr, &got);
+  if (st != RTX_OK) return st;
+  if (got) HIP_TRY(hipMemcpy(next, d_next, (size_t)got * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(counts, d_counts, (size_t)npix * 4, hipMemcpyDeviceToHost));
+  *kept = got;
+  return RTX_OK;
+}
+
+rtx_status rtx_device_noise_reduce(const double* S, const double* Q, const int32_t* counts, uint32_t npix, uint32_t spp,
+                                   double target, double* max_r, double* sum_r, uint64_t* above) {
+  const char* fn = "rtx_device_noise_reduce";
+  if (!self_test_args_ok(fn, S && Q && max_r && sum_r && above, npix, spp, target)) return RTX_EINVAL;
+  *max_r = 0.0;
+  *sum_r = 0.0;
+  *above = 0;
+  if (npix == 0) return RTX_OK;
+  SelfTestBuffers b;
+  double *dS, *dQ;
+  int32_t* d_counts = nullptr;
+  NoisePartial* partials = nullptr;
+  const size_t plane = (size_t)npix * 3;
+  hipError_t e = b.upload(&dS, S, plane);
+  if (e == hipSuccess) e = b.upload(&dQ, Q, plane);
+  if (e == hipSuccess && counts) e = b.upload(&d_counts, counts, npix);
+  if (e == hipSuccess) {
+    e = noise_partials_alloc(npix, &partials);
+    b.ptrs.push_back((void*)partials);
+  }
+  if (e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  NoisePartial r;
+  const rtx_status st = noise_reduce_launch(dS, dQ, d_counts, npix, spp, target, partials, &r);
+  if (st != RTX_OK) return st;
+  *max_r = r.max_r;
+  *sum_r = r.sum_r;
+  *above = r.above;
   return RTX_OK;
 }
 

@@ -46,6 +46,37 @@ def test_null_handles_are_rejected_without_a_device(rtsr):
     assert "NULL handle" in rtsr.last_error()
 
 
+def test_post_kernel_self_tests_check_arguments_without_a_device(rtsr):
+    lib, D, U, I = rtsr.lib, C.c_double, C.c_uint32, C.c_int32
+    S, Q = (D * 6)(*[2.0] * 6), (D * 6)(*[1.0] * 6)
+    active, nxt, counts = (U * 2)(0, 1), (U * 2)(), (I * 2)()
+    kept, mx, sm, above = U(7), D(), D(), C.c_uint64()
+    good = [S, Q, 2, active, 2, 4, 0.5, counts, nxt, C.byref(kept)]
+    for k in (0, 1, 3, 7, 8, 9):  # each pointer NULL in turn
+        args = list(good)
+        args[k] = None
+        assert lib.rtx_device_retire(*args) == rtsr.RTX_EINVAL, k
+        assert "NULL" in rtsr.last_error()
+    for spp, target in ((0, 0.5), (1, 0.5), (4, -0.5), (4, float("nan")), (4, -math.inf)):
+        assert lib.rtx_device_retire(S, Q, 2, active, 2, spp, target, counts, nxt, C.byref(kept)) == rtsr.RTX_EINVAL
+        assert lib.rtx_device_noise_reduce(S, Q, None, 2, spp, target, C.byref(mx), C.byref(sm), C.byref(above)) == rtsr.RTX_EINVAL
+    assert lib.rtx_device_retire(S, Q, 2, (U * 2)(1, 1), 2, 4, 0.5, counts, nxt, C.byref(kept)) == rtsr.RTX_EINVAL
+    assert lib.rtx_device_retire(S, Q, 2, (U * 2)(0, 2), 2, 4, 0.5, counts, nxt, C.byref(kept)) == rtsr.RTX_EINVAL
+    good = [S, Q, None, 2, 4, 0.5, C.byref(mx), C.byref(sm), C.byref(above)]
+    for k in (0, 1, 6, 7, 8):
+        args = list(good)
+        args[k] = None
+        assert lib.rtx_device_noise_reduce(*args) == rtsr.RTX_EINVAL, k
+    # nothing to do is not an error, and touches no device
+    assert lib.rtx_device_retire(S, Q, 2, active, 0, 4, 0.5, counts, nxt, C.byref(kept)) == rtsr.RTX_OK and kept.value == 0
+    assert lib.rtx_device_retire(S, Q, 0, active, 0, 4, 0.5, counts, nxt, C.byref(kept)) == rtsr.RTX_OK
+    mx.value = sm.value = 1.0
+    assert lib.rtx_device_noise_reduce(S, Q, None, 0, 4, 0.5, C.byref(mx), C.byref(sm), C.byref(above)) == rtsr.RTX_OK
+    assert (mx.value, sm.value, above.value) == (0.0, 0.0, 0)
+    for name in ("device_retire", "device_noise_reduce"):
+        assert callable(getattr(rtsr, name, None)), name
+
+
 @pytest.mark.parametrize("n,min_spp,target", [(0, 2, 0.1), (-1, 2, 0.1), (4, 1, 0.1), (4, 0, 0.1), (4, 2, -0.5),
                                               (4, 2, float("nan")), (4, 2, -math.inf)])
 def test_bad_adaptive_arguments_on_a_null_handle(rtsr, n, min_spp, target):

@@ -6,7 +6,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_progressive import SPLIT_CASES, _rel_err, _setup, _with
+from test_gpu_progressive import SPLIT_CASES, _noise_tree, _rel_err, _setup, _with
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,7 +94,7 @@ def _check_stats(st, snaps, counts, done, n_active, min_spp, target):
     assert st.pixels_above == int((r > target).sum())
     assert st.samples == int(counts.sum())
     assert st.max_rel_err == r.max()
-    assert st.mean_rel_err == pytest.approx(r.mean(), rel=1e-12, abs=0)
+    assert st.mean_rel_err == _noise_tree(r, target).sum / r.size
 
 
 def _median_target(snaps, spp):

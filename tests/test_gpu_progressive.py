@@ -1,5 +1,6 @@
 """Progressive rendering on the GPU: a frame built from several rtx_progressive_add calls is the one-shot frame at the
 same sample count, bit for bit; the second moment and the noise estimate equal their numpy restatements exactly."""
+import collections
 import os
 import subprocess
 
@@ -37,6 +38,39 @@ def _rel_err(S, Q, n):
     for c in range(3):
         r = np.where(rc[..., c] > r, rc[..., c], r)
     return r
+
+
+NoiseTree = collections.namedtuple("NoiseTree", "max sum above")
+
+
+def _block_tree(x):
+    """noise_block_reduce on rows of 256 lanes: lane 0 of each wave64's xor butterfly (x[:32] + x[32:], then 16, 8, 4, 2, 1;
+    the butterfly's other lanes add the same pairs the other way round, and an IEEE add commutes), then the block's four
+    waves as ((w0 + w1) + w2) + w3."""
+    w = x.reshape(-1, 4, 64)
+    for h in (32, 16, 8, 4, 2, 1):
+        w = w[..., :h] + w[..., h:2 * h]
+    w = w[..., 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+def _noise_tree(r, target):
+    """rtx_progressive_stats' reduction of the per-pixel errors r (>= 0, never NaN; pixel order) in the device's exact order:
+    stage 1 pads r to whole 256-pixel blocks with zeros and reduces each block (_block_tree) to one partial; stage 2 lets
+    thread t add 0.0 + p[t] + p[t + 256] + ... in order and reduces those 256 sums with the same tree.  (Zeros past the last
+    partial change nothing: every sum is >= +0.)  -> NoiseTree(max r, sum r bit for bit, count r > target)."""
+    r = np.ascontiguousarray(r, dtype=np.float64).ravel()
+    nb = -(-r.size // 256)
+    x = np.zeros(nb * 256)
+    x[:r.size] = r
+    part = _block_tree(x)
+    per = -(-nb // 256)
+    p = np.zeros(per * 256)
+    p[:nb] = part
+    t = np.zeros(256)
+    for row in p.reshape(per, 256):
+        t = t + row
+    return NoiseTree(float(r.max()), float(_block_tree(t)[0]), int((r > target).sum()))
 
 
 SPLIT_CASES = [  # (name, scene id, width, aspect, options)
@@ -125,7 +159,7 @@ def test_noise_stats_equal_numpy_restatement_and_converge(rtsr):
             assert (st.spp_done, st.pixels, st.target_rel_err) == (spp, r.size, target)
             assert st.pixels_above == int((r > target).sum())
             assert st.max_rel_err == r.max()
-            assert st.mean_rel_err == pytest.approx(r.mean(), rel=1e-12, abs=0)
+            assert st.mean_rel_err == _noise_tree(r, target).sum / r.size
             again = prog.stats(target)
             assert bytes(again) == bytes(st)
         maxes.append(st.max_rel_err)
