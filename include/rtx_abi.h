@@ -347,6 +347,52 @@ rtx_status rtx_progressive_until_adaptive(rtx_progressive* p, int32_t batch, int
  * still active, and for every pixel of a handle that never ran an adaptive round); rows skipped by row_chunk_compat get 0. */
 rtx_status rtx_progressive_pixel_spp(const rtx_progressive* p, int32_t* spp);
 
+/* ---- denoising a progressive frame ---------------------------------------------------------------------------------- */
+/* An extension: a denoised image is a new, separate output of a handle, STATISTICAL like the f32 mode (no bit-exactness
+ * claim against any reference).  It leaves S, Q, the counts and spp_done untouched: later rtx_progressive_add and
+ * _add_adaptive calls behave exactly as if it had never run.
+ * Features: for each feature sample s in [0, feature_spp), the primary ray of path sample s (the same jitter, lens sample and
+ * shutter time) and its first world hit on that path's stream, averaged per pixel:
+ *   albedo  Lambertian / Isotropic: the texture's colour at the hit (scatter's attenuation); Metal: its albedo;
+ *           Dielectric, DiffuseLight: (1, 1, 1); a miss: the config's background;
+ *   normal  the hit record's face-forwarded normal; (0, 0, 0) for an Isotropic hit and for a miss.
+ * They depend on (scene, camera, config) only; a handle computes them on its first denoise / features call (32 bytes per
+ * pixel, kept while feature_spp stays the same).
+ * Filter: an edge-avoiding a-trous wavelet filter steered by each pixel's variance (Dammertz et al. 2010; Schied et al.
+ * 2017).  Per pixel p at its own count n (spp_done, or n_p once it has retired):
+ *   prepare (f64 -> f32)  m = S/n,  v_c = max(0, (Q - S*S/n)/(n - 1))/n  (rtx_progressive_stats' operations);
+ *                         demodulated (the default): a = max(A, 1e-3) per channel, c0 = m/a, v_c = v_c/a^2, else c0 = m;
+ *                         sigma2 = 0.2126^2 v_r + 0.7152^2 v_g + 0.0722^2 v_b (channel covariances ignored);
+ *                         n^ = N/|N| if |N| >= 1e-3, else 0.
+ *   level k = 0..K-1 (f32), step t = 2^k: taps q = p + t(dx, dy), dx, dy in -2..2, those outside the image skipped,
+ *                         h = (1/16, 1/4, 3/8, 1/4, 1/16), l(c) = 0.2126 r + 0.7152 g + 0.0722 b,
+ *                         w = h_dx h_dy exp(-|l(c_p) - l(c_q)| / (sigma_l sqrt(sigma2_p) + 1e-4) - |A_p - A_q|^2 / sigma_a^2) W_n,
+ *                         W_n = 1 if both n^ are 0, 0 if exactly one is, else max(0, min(1, n^_p . n^_q))^sigma_n;
+ *                         the centre tap's w is (3/8)^2 (its own colour and normal: e = 0, W_n = 1);
+ *                         c' = sum w c_q / sum w,  sigma2' = sum w^2 sigma2_q / (sum w)^2  (taps summed dy outer, dx inner).
+ *   finish                mean = c_K a (demodulated) or c_K; rgb8 = the tone map of a 1-sample sum (sqrt, clamp, * 255.9).
+ * The same inputs give the same bits on every call.  Parameters (0 = the default): iterations K = 5 (1..8), feature_spp = 4
+ * (1..64), sigma_luminance = 4, sigma_normal = 32, sigma_albedo = 0.3 (each in [0, 1e30]), demodulate 0 or 1 = on,
+ * -1 = off.  NULL pointers (outputs excepted), parameters out of range and spp_done < 2 are RTX_EINVAL before any device
+ * call; a sharded handle (shard_count > 1) or one with row_chunk_compat is RTX_EUNSUPPORTED (rows are missing there, and the
+ * filter needs every neighbour). */
+typedef struct RtxDenoiseParams {
+  int32_t iterations, feature_spp, demodulate, reserved; /* 0 = default; reserved is ignored */
+  double sigma_luminance, sigma_normal, sigma_albedo;    /* 0 = default */
+} RtxDenoiseParams;
+/* Blocking.  albedo_rgb, normal_xyz: optional host buffers of rows*w*3 floats in rtx_render_device's layout.  The feature
+ * pass of feature_spp (1..64) samples. */
+rtx_status rtx_progressive_features(rtx_progressive* p, int32_t feature_spp, float* albedo_rgb, float* normal_xyz);
+/* Blocking; waits for adds still running on any stream.  Needs spp_done >= 2; params NULL = the defaults.  mean_rgb
+ * (rows*w*3 doubles): the denoised per-pixel MEAN radiance (not a sum); rgb8 (rows*w*3): its tone map.  Both optional. */
+rtx_status rtx_progressive_denoise(rtx_progressive* p, const RtxDenoiseParams* params, double* mean_rgb, uint8_t* rgb8);
+/* Self-test: the filter above (prepare from m and v, the levels, finish) on host arrays of width*height pixels, through the
+ * handle's own launch sequence.  mean_rgb, var_rgb (the variance of the mean, per channel): doubles; albedo_rgb, normal_xyz:
+ * floats; 3 per pixel, row-major.  out_mean_rgb and out_rgb8 optional.  Blocking. */
+rtx_status rtx_device_denoise(const double* mean_rgb, const double* var_rgb, const float* albedo_rgb, const float* normal_xyz,
+                              int32_t width, int32_t height, const RtxDenoiseParams* params, double* out_mean_rgb,
+                              uint8_t* out_rgb8);
+
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one
  * upload): 500 x 500, 500 spp, depth 50, background (0.7, 0.8, 1), camera (13,2,3) -> (0,0,0), vfov 20, aspect 1,

@@ -97,9 +97,15 @@ class RtxAdaptiveStats(C.Structure):
                 ("max_rel_err", C.c_double), ("mean_rel_err", C.c_double), ("target_rel_err", C.c_double)]
 
 
+class RtxDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("feature_spp", C.c_int32), ("demodulate", C.c_int32), ("reserved", C.c_int32),
+                ("sigma_luminance", C.c_double), ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double)]
+
+
 # Every symbol include/rtx_abi.h declares: (restype, argtypes).  tests/test_abi_symbols.py checks
 # this table against the header and against the loaded library.
 _D3 = C.POINTER(C.c_double)
+_F3 = C.POINTER(C.c_float)
 _VP = C.c_void_p
 _H = C.c_int32
 ABI = {
@@ -177,6 +183,10 @@ ABI = {
     "rtx_progressive_add_adaptive": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_double, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_progressive_until_adaptive": (C.c_int32, [_VP, C.c_int32, C.c_int32, C.c_double, C.POINTER(RtxAdaptiveStats)]),
     "rtx_progressive_pixel_spp": (C.c_int32, [_VP, C.POINTER(C.c_int32)]),
+    "rtx_progressive_features": (C.c_int32, [_VP, C.c_int32, _F3, _F3]),
+    "rtx_progressive_denoise": (C.c_int32, [_VP, C.POINTER(RtxDenoiseParams), _D3, C.POINTER(C.c_uint8)]),
+    "rtx_device_denoise": (C.c_int32, [_D3, _D3, _F3, _F3, C.c_int32, C.c_int32, C.POINTER(RtxDenoiseParams), _D3,
+                                       C.POINTER(C.c_uint8)]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -561,6 +571,23 @@ class Progressive:
         _check(lib.rtx_progressive_pixel_spp(self._p, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
 
+    def features(self, feature_spp=4):
+        """First-hit (albedo, normal) averaged over feature_spp samples: float32 arrays shaped like Screen.accum."""
+        albedo = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        normal = np.zeros_like(albedo)
+        _check(lib.rtx_progressive_features(self._p, feature_spp, albedo.ctypes.data_as(_F3), normal.ctypes.data_as(_F3)))
+        return albedo, normal
+
+    def denoise(self, **params):
+        """The denoised frame (rtx_progressive_denoise; keyword arguments: the fields of RtxDenoiseParams, 0 = default) ->
+        Screen whose accum is the denoised per-pixel MEAN radiance and rgb8 its tone map.  S and Q are not touched."""
+        prm = denoise_params(**params)
+        accum = np.zeros((self.height, self.width, 3), dtype=np.float64)
+        rgb8 = np.zeros((self.height, self.width, 3), dtype=np.uint8)
+        _check(lib.rtx_progressive_denoise(self._p, C.byref(prm), accum.ctypes.data_as(_D3),
+                                           rgb8.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return Screen(self.width, self.height, rgb8, accum)
+
 
 class MultiScene:
     """The scene resident on several GPUs of this process (rtx_multi): row-interleaved shards, one RCCL gather."""
@@ -659,6 +686,40 @@ def device_noise_reduce(S, Q, spp, target, counts=None):
     return max_r.value, sum_r.value, above.value
 
 
+def denoise_params(**params):
+    """RtxDenoiseParams from keyword arguments (iterations, feature_spp, demodulate, sigma_luminance, sigma_normal,
+    sigma_albedo); what is not given is 0, the default."""
+    prm = RtxDenoiseParams()
+    names = [n for n, _ in RtxDenoiseParams._fields_ if n != "reserved"]
+    for k, v in params.items():
+        if k not in names:
+            raise TypeError("unknown denoise parameter %r (expected one of %s)" % (k, ", ".join(names)))
+        setattr(prm, k, v)
+    return prm
+
+
+def device_denoise(mean, var, albedo, normal, **params):
+    """The denoising filter on the GPU for host arrays (see rtx_device_denoise): mean and var (the variance of the mean) per
+    pixel and channel, albedo and normal guides, each rows x width x 3 -> (denoised mean f64, its rgb8)."""
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    if mean.ndim != 3 or mean.shape[2] != 3:
+        raise ValueError("mean must be rows x width x 3")
+    var = np.ascontiguousarray(var, dtype=np.float64)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    for a in (var, albedo, normal):
+        if a.shape != mean.shape:
+            raise ValueError("mean, var, albedo and normal must have the same shape")
+    h, w = mean.shape[:2]
+    prm = denoise_params(**params)
+    out = np.zeros_like(mean)
+    rgb8 = np.zeros(mean.shape, dtype=np.uint8)
+    _check(lib.rtx_device_denoise(mean.ctypes.data_as(_D3), var.ctypes.data_as(_D3), albedo.ctypes.data_as(_F3),
+                                  normal.ctypes.data_as(_F3), w, h, C.byref(prm), out.ctypes.data_as(_D3),
+                                  rgb8.ctypes.data_as(C.POINTER(C.c_uint8))))
+    return out, rgb8
+
+
 def shard_rows(cfg, shard):
     sh = RtxShard(*shard, 0)
     return lib.rtx_shard_rows(C.byref(cfg), C.byref(sh))
@@ -692,19 +753,27 @@ def render_scene(builder, world, cam, background, config, max_leaf=0):
 
 
 def render_scene_progressive(builder, world, cam, background, config, batch, target_rel_err, max_leaf=0, adaptive=False,
-                             min_spp=2):
+                             min_spp=2, denoise=False):
     """render_scene, refined `batch` samples at a time until no pixel's relative error exceeds target_rel_err or
     config.samples_per_pixel is reached.  Returns (Screen, RtxNoiseStats of the last batch).
     adaptive=True: pixels at or below the target stop receiving samples (checked from min_spp samples on); returns
-    (Screen, RtxAdaptiveStats), and Screen.spp holds each pixel's sample count."""
+    (Screen, RtxAdaptiveStats), and Screen.spp holds each pixel's sample count.
+    denoise=True: the Screen is the denoised frame (Progressive.denoise with the default parameters; accum is the MEAN
+    radiance, not a sum) and Screen.noisy holds the frame as accumulated."""
     cfg = RtxConfig.from_buffer_copy(config)
     cfg.background[0], cfg.background[1], cfg.background[2] = background
     scene = builder.flatten(world, max_leaf=max_leaf).upload()
     prog = scene.progressive(cam, cfg)
     if adaptive:
         stats = prog.until_adaptive(batch, min_spp, target_rel_err)
-        screen = prog.screen()
+    else:
+        stats = prog.until(batch, target_rel_err)
+    screen = prog.screen()
+    if adaptive:
         screen.spp = prog.pixel_spp()
-        return screen, stats
-    stats = prog.until(batch, target_rel_err)
-    return prog.screen(), stats
+    if denoise:
+        noisy, screen = screen, prog.denoise()
+        screen.noisy = noisy
+        if adaptive:
+            screen.spp = noisy.spp
+    return screen, stats

@@ -7,6 +7,8 @@
 //              [--scene-seed N] [--out FILE.ppm] [--camera-aspect A] [--ply FILE] [--earth FILE.ppm]
 //              [--row-chunk-compat] [--batch N --target-error E [--snapshot-every K]]
 //              [--batch N --target-error E --adaptive [--min-spp M] [--spp-map FILE.pgm]]
+//              [--batch N --target-error E [--adaptive ...] --denoise [--noisy-out FILE.ppm] [--albedo-out FILE.ppm]
+//               [--normal-out FILE.ppm]]
 //
 // --batch / --target-error render progressively: N samples at a time until no pixel's relative error exceeds E or --spp
 // samples are in (rtx_progressive_until); the spp reached and the final noise stats go to stderr.  --snapshot-every K
@@ -14,12 +16,26 @@
 // --adaptive stops tracing each pixel once its relative error is at most E, checked at every batch boundary from M samples
 // on (default 2; rtx_progressive_until_adaptive); stderr also gets the samples traced against a uniform render's.
 // --spp-map writes each pixel's sample count as a plain PGM (top row first, maxval = --spp).
+// --denoise (with --batch) writes the denoised frame (rtx_progressive_denoise, default parameters) where the frame would go;
+// --noisy-out gets the frame as accumulated, --albedo-out and --normal-out the filter's first-hit guides (albedo clamped to
+// [0, 1], normal mapped to 0.5 + 0.5 n; linear, not tone-mapped).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include "../csrc/host/world.hpp"
+
+// A feature buffer (rows * w * 3 floats, row 0 = bottom) as a PPM: each value v -> 255.9 * clamp(offset + scale * v, 0, 1).
+static void write_feature_ppm(const char* path, int w, int h, const std::vector<float>& v, double offset, double scale) {
+  std::vector<uint8_t> rgb8(v.size());
+  for (size_t k = 0; k < v.size(); ++k) {
+    double x = offset + scale * (double)v[k];
+    x = x < 0.0 ? 0.0 : (x > 1.0 ? 1.0 : x);
+    rgb8[k] = (uint8_t)(int)(255.9 * x);
+  }
+  rtsr::check(rtx_write_ppm(path, w, h, rgb8.data()));
+}
 
 static const size_t THREADS = 11;  // main.rs:4
 static const int SCENE_ID = 11;    // main.rs:5
@@ -38,6 +54,10 @@ int main(int argc, char** argv) {
   double target_error = -1.0;
   bool adaptive = false;
   const char* spp_map = nullptr;
+  bool denoise = false;
+  const char* noisy_out = nullptr;
+  const char* albedo_out = nullptr;
+  const char* normal_out = nullptr;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* flag) -> const char* {
       if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", flag); exit(2); }
@@ -62,6 +82,10 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--adaptive")) adaptive = true;
     else if (!strcmp(argv[i], "--min-spp")) min_spp = atoi(need("--min-spp"));
     else if (!strcmp(argv[i], "--spp-map")) spp_map = need("--spp-map");
+    else if (!strcmp(argv[i], "--denoise")) denoise = true;
+    else if (!strcmp(argv[i], "--noisy-out")) noisy_out = need("--noisy-out");
+    else if (!strcmp(argv[i], "--albedo-out")) albedo_out = need("--albedo-out");
+    else if (!strcmp(argv[i], "--normal-out")) normal_out = need("--normal-out");
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool progressive = batch > 0 || target_error >= 0.0;
@@ -89,6 +113,18 @@ int main(int argc, char** argv) {
     fprintf(stderr, "--snapshot-every and --adaptive do not go together\n");
     return 2;
   }
+  if (denoise && !progressive) {
+    fprintf(stderr, "--denoise needs --batch N (> 0) and --target-error E (>= 0)\n");
+    return 2;
+  }
+  if (denoise && (spp < 2 || compat)) {
+    fprintf(stderr, "--denoise needs --spp >= 2 and every row (no --row-chunk-compat)\n");
+    return 2;
+  }
+  if (!denoise && (noisy_out || albedo_out || normal_out)) {
+    fprintf(stderr, "--noisy-out, --albedo-out and --normal-out need --denoise\n");
+    return 2;
+  }
   try {
     rtsr::Scene scene(scene_seed);
     RtxSceneOptions opt;
@@ -101,9 +137,11 @@ int main(int argc, char** argv) {
     config.c.seed = seed;
     config.c.row_chunk_compat = compat ? 1 : 0;
     rtsr::Screen screen;
+    rtsr::DenoiseOutputs dn;
+    rtsr::DenoiseOutputs* dnp = denoise ? &dn : nullptr;
     if (adaptive) {
       RtxAdaptiveStats as = {};
-      screen = rtsr::render_scene_adaptive(scene, wc.world, wc.cam, wc.background, config, batch, min_spp, target_error, &as);
+      screen = rtsr::render_scene_adaptive(scene, wc.world, wc.cam, wc.background, config, batch, min_spp, target_error, &as, dnp);
       const double uniform = (double)as.spp_done * (double)as.pixels;
       fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", as.spp_done,
               spp, target_error, as.pixels_above, as.pixels, as.max_rel_err, as.mean_rel_err);
@@ -118,12 +156,15 @@ int main(int argc, char** argv) {
         s.write_to_ppm_file(path.c_str());
       };
       screen = rtsr::render_scene_progressive(scene, wc.world, wc.cam, wc.background, config, batch, target_error, &ns,
-                                              snapshot_every, snap);
+                                              snapshot_every, snap, dnp);
       fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", ns.spp_done,
               spp, target_error, ns.pixels_above, ns.pixels, ns.max_rel_err, ns.mean_rel_err);
     } else {
       screen = rtsr::render_scene(scene, wc.world, wc.cam, wc.background, config);  // main.rs:13
     }
+    if (noisy_out) dn.noisy.write_to_ppm_file(noisy_out);
+    if (albedo_out) write_feature_ppm(albedo_out, screen.width, screen.height, dn.albedo, 0.0, 1.0);
+    if (normal_out) write_feature_ppm(normal_out, screen.width, screen.height, dn.normal, 0.5, 0.5);
     if (out) screen.write_to_ppm_file(out);
     else screen.write_to_ppm();
   } catch (const rtsr::Error& e) {

@@ -35,6 +35,10 @@ rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const 
 rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream);
 rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix,
                                   uint32_t spp, void* hip_stream);
+// progressive.inc (denoising): the feature pass (denoise.inc: k_features) of feature_spp first hits per pixel of the whole
+// image into d_albedo4 / d_normal4, 4 floats per pixel each.
+rtx_status rtx_f32_features(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
+                            float* d_albedo4, float* d_normal4, void* hip_stream);
 rtx_status rtx_f32_trim(void* device_scene);
 void rtx_f32_destroy(void* device_scene);
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error

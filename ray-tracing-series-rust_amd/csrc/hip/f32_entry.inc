@@ -53,5 +53,10 @@ rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, co
                                   uint32_t spp, void* hip_stream) {
   return tonemap_counts_impl(d_accum_rgb, d_rgb8, d_counts, npix, spp, (hipStream_t)hip_stream);
 }
+rtx_status rtx_f32_features(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
+                            float* d_albedo4, float* d_normal4, void* hip_stream) {
+  return features_impl((DeviceScene*)device_scene, cam, cfg, feature_spp, (float4*)d_albedo4, (float4*)d_normal4,
+                       (hipStream_t)hip_stream);
+}
 rtx_status rtx_f32_trim(void* device_scene) { return scene_trim_impl((DeviceScene*)device_scene); }
 void rtx_f32_destroy(void* device_scene) { free_device_scene((DeviceScene*)device_scene); }

@@ -15,6 +15,32 @@
 // The handle borrows the scene's render workspace (sample buffer, work counters, pipelining stream): it must not run at the
 // same time as another render of the same scene on another stream, and it must be destroyed before its scene.
 
+// The filter's device buffers for one image (denoise_launch): two (c, sigma2) planes to ping-pong between, n^, and the
+// finished mean and rgb8.
+struct DenoiseBuffers {
+  size_t npix = 0;
+  float4* cv[2] = {nullptr, nullptr};
+  float4* nhat = nullptr;
+  double* mean = nullptr;
+  uint8_t* rgb8 = nullptr;
+  ~DenoiseBuffers() {
+    for (float4* c : cv)
+      if (c) (void)hipFree(c);
+    if (nhat) (void)hipFree(nhat);
+    if (mean) (void)hipFree(mean);
+    if (rgb8) (void)hipFree(rgb8);
+  }
+  hipError_t alloc(size_t n) {
+    npix = n;
+    hipError_t e = hipMalloc((void**)&cv[0], n * 16 + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&cv[1], n * 16 + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&nhat, n * 16 + 16);
+    if (e == hipSuccess) e = hipMalloc((void**)&mean, n * 24 + 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&rgb8, n * 3 + 8);
+    return e;
+  }
+};
+
 struct rtx_progressive {
   const rtx_scene* scene;
   RtxCamera cam;
@@ -38,6 +64,11 @@ struct rtx_progressive {
   uint32_t* block_count;
   uint32_t* block_offset;
   uint64_t retired_samples;  // sum of n_p over the retired pixels
+  // denoising state, allocated by the first features / denoise call (denoise.inc)
+  int32_t feature_spp;       // of the features held (0: none yet)
+  float4* albedo;            // per pixel: the feature pass's albedo, normal
+  float4* normal;
+  DenoiseBuffers* denoise;   // the filter's buffers
 };
 
 namespace {
@@ -52,6 +83,9 @@ void progressive_free(rtx_progressive* p) {
   if (p->keep_mask) (void)hipFree(p->keep_mask);
   if (p->block_count) (void)hipFree(p->block_count);
   if (p->block_offset) (void)hipFree(p->block_offset);
+  if (p->albedo) (void)hipFree(p->albedo);
+  if (p->normal) (void)hipFree(p->normal);
+  delete p->denoise;
   delete p;
 }
 
@@ -288,6 +322,94 @@ bool self_test_args_ok(const char* fn, bool pointers, uint32_t npix, uint32_t sp
   if (spp < 2 || spp > (uint32_t)INT32_MAX) { set_error(std::string(fn) + ": spp must be in [2, 2^31)"); return false; }
   if (!(target >= 0.0)) { set_error(std::string(fn) + ": target must be >= 0"); return false; }
   return true;
+}
+
+// ---- denoising (denoise.inc)
+
+// The filter's parameters with the defaults filled in, checked before any device call; feature_spp gets the feature pass's.
+bool denoise_rule(const RtxDenoiseParams* params, const char* fn, DenoiseRule* r, int32_t* feature_spp) {
+  RtxDenoiseParams d;
+  memset(&d, 0, sizeof(d));
+  if (params) d = *params;
+  const int32_t k = d.iterations ? d.iterations : 5, fs = d.feature_spp ? d.feature_spp : 4;
+  if (k < 1 || k > 8) { set_error(std::string(fn) + ": iterations must be in [1, 8] (0 = 5)"); return false; }
+  if (fs < 1 || fs > 64) { set_error(std::string(fn) + ": feature_spp must be in [1, 64] (0 = 4)"); return false; }
+  if (d.demodulate < -1 || d.demodulate > 1) { set_error(std::string(fn) + ": demodulate must be -1 (off), 0 or 1 (on)"); return false; }
+  const double sig[3] = {d.sigma_luminance, d.sigma_normal, d.sigma_albedo}, dflt[3] = {4.0, 32.0, 0.3};
+  double v[3];
+  for (int c = 0; c < 3; ++c) {
+    if (!(sig[c] >= 0.0 && sig[c] <= 1e30)) { set_error(std::string(fn) + ": sigmas must be in [0, 1e30] (0 = default)"); return false; }
+    v[c] = sig[c] > 0.0 ? sig[c] : dflt[c];
+  }
+  r->iterations = k;
+  r->demodulate = d.demodulate >= 0 ? 1 : 0;
+  r->sigma_l = (float)v[0];
+  r->sigma_n = (float)v[1];
+  const double inv_a2 = 1.0 / (v[2] * v[2]);  // a tiny sigma_a: FLT_MAX, not inf (0 * inf at equal albedos would be NaN)
+  r->inv_sigma_a2 = inv_a2 < (double)FLT_MAX ? (float)inv_a2 : FLT_MAX;
+  if (feature_spp) *feature_spp = fs;
+  return true;
+}
+
+// The filter over a w x h image on the default stream: k_denoise_prepare from S and Q at each pixel's count (moments = 1) or
+// from m and v (moments = 0), then the levels; the last one finishes into b.mean / b.rgb8 where want_mean / want_rgb8.
+// Blocking.
+rtx_status denoise_launch(int32_t w, int32_t h, const DenoiseRule& r, const double* s_or_m, const double* q_or_v,
+                          const int32_t* counts, uint32_t spp, int moments, const float4* albedo, const float4* normal,
+                          DenoiseBuffers& b, bool want_mean, bool want_rgb8) {
+  const uint32_t npix = (uint32_t)((size_t)w * (size_t)h);
+  if (npix == 0) return RTX_OK;
+  hipLaunchKernelGGL(k_denoise_prepare, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, s_or_m, q_or_v, counts,
+                     spp, moments, npix, r.demodulate, albedo, normal, b.cv[0], b.nhat);
+  HIP_TRY(hipGetLastError());
+  const uint32_t nbx = ((uint32_t)w + DENOISE_BX - 1) / DENOISE_BX, nby = ((uint32_t)h + DENOISE_BY - 1) / DENOISE_BY;
+  const dim3 grid(nbx * nby), block(DENOISE_BX, DENOISE_BY);
+  for (int k = 0; k < r.iterations; ++k) {
+    const float4* in = b.cv[k & 1];
+    if (k + 1 < r.iterations)
+      hipLaunchKernelGGL(k_denoise_level<false>, grid, block, 0, (hipStream_t) nullptr, in, albedo, b.nhat, w, h, 1 << k, nbx, r,
+                         b.cv[(k + 1) & 1], nullptr, nullptr);
+    else
+      hipLaunchKernelGGL(k_denoise_level<true>, grid, block, 0, (hipStream_t) nullptr, in, albedo, b.nhat, w, h, 1 << k, nbx, r,
+                         nullptr, want_mean ? b.mean : nullptr, want_rgb8 ? b.rgb8 : nullptr);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipDeviceSynchronize());
+  return RTX_OK;
+}
+
+// Denoising needs every row of the image: a whole-image handle without row_chunk_compat.
+bool denoise_supported(const rtx_progressive* p, const char* fn) {
+  if (p->shard.shard_count == 1 && !p->cfg.row_chunk_compat) return true;
+  set_error(std::string(fn) + ": a sharded or row_chunk_compat handle has rows missing; the spatial filter needs them all");
+  return false;
+}
+
+// The handle's features for feature_spp samples, computed (and the buffers allocated) unless they are already there.  Blocking.
+rtx_status ensure_features(rtx_progressive* p, int32_t feature_spp) {
+  if (p->feature_spp == feature_spp) return RTX_OK;
+  HIP_TRY(hipDeviceSynchronize());  // adds may still run on the caller's stream (the feature pass shares nothing with them)
+  const size_t bytes = (size_t)p->npix_all * 16 + 16;
+  if (!p->albedo) HIP_TRY(hipMalloc((void**)&p->albedo, bytes));
+  if (!p->normal) HIP_TRY(hipMalloc((void**)&p->normal, bytes));
+  p->feature_spp = 0;
+  rtx_status st;
+  if (p->scene->f32)
+    st = rtx_f32_features(p->scene->device_scene, &p->cam, &p->cfg, feature_spp, (float*)p->albedo, (float*)p->normal, nullptr);
+  else
+    st = features_impl(scene_device(p->scene), &p->cam, &p->cfg, feature_spp, p->albedo, p->normal, (hipStream_t) nullptr);
+  if (st != RTX_OK) return st;
+  HIP_TRY(hipDeviceSynchronize());
+  p->feature_spp = feature_spp;
+  return RTX_OK;
+}
+
+// float4 per pixel (device) -> 3 floats per pixel (host).
+rtx_status download_xyz(const float4* d, size_t npix, float* out) {
+  std::vector<float4> h(npix);
+  if (npix) HIP_TRY(hipMemcpy(h.data(), d, npix * 16, hipMemcpyDeviceToHost));
+  for (size_t k = 0; k < npix; ++k) { out[3 * k] = h[k].x; out[3 * k + 1] = h[k].y; out[3 * k + 2] = h[k].z; }
+  return RTX_OK;
 }
 
 }  // namespace
@@ -527,6 +649,84 @@ rtx_status rtx_device_noise_reduce(const double* S, const double* Q, const int32
   *max_r = r.max_r;
   *sum_r = r.sum_r;
   *above = r.above;
+  return RTX_OK;
+}
+
+rtx_status rtx_progressive_features(rtx_progressive* p, int32_t feature_spp, float* albedo_rgb, float* normal_xyz) {
+  const char* fn = "rtx_progressive_features";
+  if (!progressive_usable(p, fn)) return RTX_EINVAL;
+  if (feature_spp < 1 || feature_spp > 64) { set_error(std::string(fn) + ": feature_spp must be in [1, 64]"); return RTX_EINVAL; }
+  if (!denoise_supported(p, fn)) return RTX_EUNSUPPORTED;
+  const rtx_status st = ensure_features(p, feature_spp);
+  if (st != RTX_OK) return st;
+  if (albedo_rgb && download_xyz(p->albedo, p->npix_all, albedo_rgb) != RTX_OK) return RTX_EHIP;
+  if (normal_xyz && download_xyz(p->normal, p->npix_all, normal_xyz) != RTX_OK) return RTX_EHIP;
+  return RTX_OK;
+}
+
+rtx_status rtx_progressive_denoise(rtx_progressive* p, const RtxDenoiseParams* params, double* mean_rgb, uint8_t* rgb8) {
+  const char* fn = "rtx_progressive_denoise";
+  if (!progressive_usable(p, fn)) return RTX_EINVAL;
+  DenoiseRule r;
+  int32_t feature_spp = 0;
+  if (!denoise_rule(params, fn, &r, &feature_spp)) return RTX_EINVAL;
+  if (!denoise_supported(p, fn)) return RTX_EUNSUPPORTED;
+  if (p->spp_done < 2) { set_error(std::string(fn) + ": the variance needs at least 2 samples"); return RTX_EINVAL; }
+  rtx_status st = ensure_features(p, feature_spp);
+  if (st != RTX_OK) return st;
+  if (!p->denoise) {
+    DenoiseBuffers* b = new DenoiseBuffers();
+    const hipError_t e = b->alloc(p->npix_all);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      delete b;
+      set_error(std::string(fn) + ": " + hipGetErrorString(e));
+      return e == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
+    }
+    p->denoise = b;
+  }
+  const int32_t w = p->cfg.image_width, h = (int32_t)(p->npix_all / (uint32_t)w);
+  HIP_TRY(hipDeviceSynchronize());  // the adds ran on the caller's stream: S, Q and the counts must be complete
+  st = denoise_launch(w, h, r, p->S, p->Q, any_retired(p) ? p->counts : nullptr, (uint32_t)p->spp_done, 1, p->albedo,
+                      p->normal, *p->denoise, mean_rgb != nullptr, rgb8 != nullptr);
+  if (st != RTX_OK) return st;
+  if (mean_rgb) HIP_TRY(hipMemcpy(mean_rgb, p->denoise->mean, (size_t)p->npix_all * 24, hipMemcpyDeviceToHost));
+  if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->denoise->rgb8, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
+rtx_status rtx_device_denoise(const double* mean_rgb, const double* var_rgb, const float* albedo_rgb, const float* normal_xyz,
+                              int32_t width, int32_t height, const RtxDenoiseParams* params, double* out_mean_rgb,
+                              uint8_t* out_rgb8) {
+  const char* fn = "rtx_device_denoise";
+  if (!mean_rgb || !var_rgb || !albedo_rgb || !normal_xyz) { set_error(std::string(fn) + ": NULL argument"); return RTX_EINVAL; }
+  if (width < 1 || height < 1 || (uint64_t)width * (uint64_t)height >= (1ull << 31)) {
+    set_error(std::string(fn) + ": width and height must be >= 1, with fewer than 2^31 pixels");
+    return RTX_EINVAL;
+  }
+  DenoiseRule r;
+  if (!denoise_rule(params, fn, &r, nullptr)) return RTX_EINVAL;
+  const size_t npix = (size_t)width * (size_t)height;
+  std::vector<float4> a4(npix), n4(npix);
+  for (size_t k = 0; k < npix; ++k) {
+    a4[k] = make_float4(albedo_rgb[3 * k], albedo_rgb[3 * k + 1], albedo_rgb[3 * k + 2], 0.f);
+    n4[k] = make_float4(normal_xyz[3 * k], normal_xyz[3 * k + 1], normal_xyz[3 * k + 2], 0.f);
+  }
+  SelfTestBuffers t;
+  double *dm, *dv;
+  float4 *da, *dn;
+  DenoiseBuffers b;
+  hipError_t e = t.upload(&dm, mean_rgb, npix * 3);
+  if (e == hipSuccess) e = t.upload(&dv, var_rgb, npix * 3);
+  if (e == hipSuccess) e = t.upload(&da, a4.data(), npix);
+  if (e == hipSuccess) e = t.upload(&dn, n4.data(), npix);
+  if (e == hipSuccess) e = b.alloc(npix);
+  if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  const rtx_status st = denoise_launch(width, height, r, dm, dv, nullptr, 0u, 0, da, dn, b, out_mean_rgb != nullptr,
+                                       out_rgb8 != nullptr);
+  if (st != RTX_OK) return st;
+  if (out_mean_rgb) HIP_TRY(hipMemcpy(out_mean_rgb, b.mean, npix * 24, hipMemcpyDeviceToHost));
+  if (out_rgb8) HIP_TRY(hipMemcpy(out_rgb8, b.rgb8, npix * 3, hipMemcpyDeviceToHost));
   return RTX_OK;
 }
 

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <chrono>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -274,6 +275,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_lds.inc"     // k_trace_lds (the headline kernel)
 #include "trace_wave.inc"    // k_wf_generate / k_wf_trace / k_wf_shade: the split-kernel integrator (path state in HBM)
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
+#include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
 
 // ------------------------------------------------------------------ launcher
 static int shard_row_count(int32_t height, const RtxShard& sh, int32_t row_limit) {
@@ -1163,6 +1165,29 @@ static rtx_status tonemap_counts_impl(const double* accum, uint8_t* rgb8, const 
                                       hipStream_t stream) {
   if (npix == 0) return RTX_OK;
   hipLaunchKernelGGL(k_tonemap_counts, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, counts, npix, spp);
+  HIP_TRY(hipGetLastError());
+  return RTX_OK;
+}
+
+// The feature pass of a whole-image progressive handle (denoise.inc: k_features): feature_spp first hits per pixel into the
+// float4 albedo / normal buffers of w * h pixels.  Asynchronous on stream.
+static rtx_status features_impl(DeviceScene* ds, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
+                                float4* d_albedo, float4* d_normal, hipStream_t stream) {
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("features: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  if ((ds->view.features & rt::F_GRAVITY_SPHERE) && !(cam->time2 <= ds->gravity_time_limit)) {
+    set_error("features: shutter time beyond the GravitySpheres' stored trajectory");
+    return RTX_EINVAL;
+  }
+  const rt::RenderParams rp = make_params(cam, cfg);
+  const uint64_t npix = (uint64_t)rp.image_width * (uint64_t)rp.image_height;
+  if (npix == 0) return RTX_OK;
+  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
+  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("features: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
+  const uint32_t grid = grid_size((uint32_t)npix, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_ALL>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
+                     rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
   HIP_TRY(hipGetLastError());
   return RTX_OK;
 }

@@ -235,13 +235,31 @@ inline Screen render_scene(Scene& s, Hittable world, const Camera& cam, const Co
   return scr;
 }
 
+// What denoising a progressive render (rtx_progressive_denoise, default parameters) hands back besides the denoised frame:
+// the frame as accumulated and the first-hit features of the filter's guides (rows * w * 3 floats each, row 0 = bottom).
+struct DenoiseOutputs {
+  Screen noisy;
+  std::vector<float> albedo, normal;
+};
+
+// Replaces scr (the frame as read from prog) by the denoised one -- accum then holds the MEAN radiance -- and fills dn.
+inline rtx_status denoise_screen(rtx_progressive* prog, Screen& scr, DenoiseOutputs* dn) {
+  dn->noisy = scr;
+  dn->albedo.resize(scr.accum.size());
+  dn->normal.resize(scr.accum.size());
+  rtx_status st = rtx_progressive_denoise(prog, nullptr, scr.accum.data(), scr.rgb8.data());
+  if (st == RTX_OK) st = rtx_progressive_features(prog, 4, dn->albedo.data(), dn->normal.data());  // (cached: no second pass)
+  return st;
+}
+
 // render_scene refined `batch` samples at a time (rtx_progressive_*): stops at the first batch boundary where no pixel's
 // relative error exceeds target_rel_err, or at config's samples_per_pixel.  snapshot(screen, spp), if given, is called
-// with the frame at every multiple of snapshot_every samples that falls on a batch boundary.
+// with the frame at every multiple of snapshot_every samples that falls on a batch boundary.  denoise != NULL: the frame
+// returned is the denoised one (denoise_screen).
 template <class Snapshot = void (*)(const Screen&, int)>
 inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
                                        int batch, double target_rel_err, RtxNoiseStats* stats_out = nullptr,
-                                       int snapshot_every = 0, Snapshot snapshot = nullptr) {
+                                       int snapshot_every = 0, Snapshot snapshot = nullptr, DenoiseOutputs* denoise = nullptr) {
   config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
   rtx_flat* flat = nullptr;
   check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
@@ -275,6 +293,7 @@ inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& c
     }
   }
   if (st == RTX_OK) st = rtx_progressive_read(prog, &frame, nullptr);
+  if (st == RTX_OK && denoise) st = denoise_screen(prog, scr, denoise);
   if (stats_out) *stats_out = ns;
   rtx_progressive_destroy(prog);
   rtx_scene_destroy(scene);
@@ -284,9 +303,10 @@ inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& c
 
 // render_scene refined adaptively (rtx_progressive_until_adaptive): rounds of `batch` samples in which the pixels whose relative
 // error is at most target_rel_err (checked from min_spp samples on) stop receiving samples.  The Screen's spp holds each
-// pixel's count.
+// pixel's count.  denoise != NULL: the frame returned is the denoised one (denoise_screen).
 inline Screen render_scene_adaptive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
-                                    int batch, int min_spp, double target_rel_err, RtxAdaptiveStats* stats_out = nullptr) {
+                                    int batch, int min_spp, double target_rel_err, RtxAdaptiveStats* stats_out = nullptr,
+                                    DenoiseOutputs* denoise = nullptr) {
   config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
   rtx_flat* flat = nullptr;
   check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
@@ -307,6 +327,7 @@ inline Screen render_scene_adaptive(Scene& s, Hittable world, const Camera& cam,
   if (st == RTX_OK) st = rtx_progressive_until_adaptive(prog, batch, min_spp, target_rel_err, &as);
   if (st == RTX_OK) st = rtx_progressive_read(prog, &frame, nullptr);
   if (st == RTX_OK) st = rtx_progressive_pixel_spp(prog, scr.spp.data());
+  if (st == RTX_OK && denoise) st = denoise_screen(prog, scr, denoise);
   if (stats_out) *stats_out = as;
   rtx_progressive_destroy(prog);
   rtx_scene_destroy(scene);

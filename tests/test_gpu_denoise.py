@@ -1,0 +1,304 @@
+"""Denoising a progressive frame on the GPU: the filter against its numpy restatement, the feature pass against analytic
+first hits, the handle path against the self-test path bit for bit, S / Q untouched, and the quality it buys."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import denoise_ref as dr
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+APP = os.path.join(ROOT, "ray-tracing-series-rust_amd", "lib", "rtx_render")
+
+
+def _setup(rtsr, sid, width, aspect, spp, seed=3, f32=False, threads=10, **cfg_fields):
+    b = rtsr.Builder(1)
+    world, cam, bg = b.get_world_cam(sid)
+    cfg = rtsr.Config.new(aspect, width, spp, 50, threads, seed=seed, background=bg, **cfg_fields)
+    flat = b.flatten(world)
+    return b, flat, flat.upload(f32=f32), cam, cfg
+
+
+def _random_inputs(h, w, seed):
+    g = np.random.default_rng(seed)
+    mean = g.uniform(0.0, 2.0, (h, w, 3))
+    var = g.uniform(1e-5, 1e-2, (h, w, 3))
+    albedo = g.uniform(0.0, 1.0, (h, w, 3)).astype(np.float32)
+    albedo[g.uniform(size=(h, w)) < 0.1] = 0.0  # below the demodulation floor
+    normal = g.normal(size=(h, w, 3)).astype(np.float32)
+    normal[g.uniform(size=(h, w)) < 0.2] = 0.0  # misses / media
+    flat = g.uniform(size=(h, w)) < 0.3  # some shared normals, so that W_n = 1 occurs inside the image too
+    normal[flat] = (0.0, 0.6, 0.8)
+    return mean, var, albedo, normal
+
+
+@pytest.mark.parametrize("h,w,params", [(1, 1, {}), (5, 7, {}), (5, 7, dict(iterations=8)), (23, 37, {}),
+                                        (23, 37, dict(iterations=8, demodulate=-1)),
+                                        (16, 20, dict(iterations=3, sigma_luminance=1.5, sigma_normal=16.0, sigma_albedo=0.4)),
+                                        (16, 20, dict(sigma_albedo=1e-20)),  # 1 / sigma_a^2 beyond float: no NaN
+                                        (16, 20, dict(sigma_normal=1e30, sigma_luminance=1e30))])
+def test_device_denoise_matches_the_numpy_rule(rtsr, h, w, params):
+    mean, var, albedo, normal = _random_inputs(h, w, h * 100 + w)
+    out, rgb8 = rtsr.device_denoise(mean, var, albedo, normal, **params)
+    ref = dr.denoise(mean, var, albedo, normal, **params)
+    err = np.abs(out - ref) - (2e-4 * np.abs(ref) + 1e-6)
+    assert err.max() <= 0, (float(np.abs(out - ref).max()), float((np.abs(out - ref) / np.maximum(np.abs(ref), 1e-6)).max()))
+    assert np.array_equal(rgb8, dr.tone_map(out))
+    out2, rgb82 = rtsr.device_denoise(mean, var, albedo, normal, **params)  # the same bits on every call
+    assert np.array_equal(out.view(np.uint64), out2.view(np.uint64)) and np.array_equal(rgb8, rgb82)
+
+
+def _sphere_scene(rtsr, f32=False):
+    b = rtsr.Builder(1)
+    colour = (0.3, 0.6, 0.9)
+    center, radius = np.array([0.0, 0.0, -3.0]), 1.2
+    world = b.hittable_list([b.sphere(tuple(center), radius, b.lambertian(colour))])
+    cam = rtsr.Camera.new((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), (0.0, 1.0, 0.0), 60.0, 1.5, 0.0, 1.0, 0.0, 1.0)
+    cfg = rtsr.Config.new(1.5, 36, 8, 50, 10, seed=5, background=(0.7, 0.8, 1.0))
+    return b, b.flatten(world), cam, cfg, np.float32(colour), center, radius
+
+
+def _analytic_features(rtsr, cam, cfg, center, radius, feature_spp):
+    """Per pixel: how many of the feature samples hit the sphere, and the average of the hit normals (numpy, f64)."""
+    w, h = cfg.image_width, rtsr.image_height(cfg)
+    o = np.array(cam.origin[:])
+    llc, hor, ver = np.array(cam.lower_left_corner[:]), np.array(cam.horizontal[:]), np.array(cam.vertical[:])
+    hits = np.zeros((h, w), dtype=np.int32)
+    nsum = np.zeros((h, w, 3))
+    for j in range(h):
+        for i in range(w):
+            for s in range(feature_spp):
+                ru, rv = rtsr.device_stream(cfg.seed, j * w + i, s, 2)
+                d = llc + ((i + ru) / (w - 1)) * hor + ((j + rv) / (h - 1)) * ver - o
+                oc = o - center
+                a, half_b, c = d @ d, oc @ d, oc @ oc - radius * radius
+                disc = half_b * half_b - a * c
+                if disc < 0:
+                    continue
+                t = (-half_b - np.sqrt(disc)) / a
+                if t < 1e-3:
+                    continue
+                hits[j, i] += 1
+                nsum[j, i] += (o + t * d - center) / radius
+    return hits, nsum / feature_spp
+
+
+def test_features_of_a_lambertian_sphere(rtsr):
+    b, flat, cam, cfg, colour, center, radius = _sphere_scene(rtsr)
+    scene = flat.upload()
+    prog = scene.progressive(cam, cfg)
+    albedo, normal = prog.features(4)
+    hits, nref = _analytic_features(rtsr, cam, cfg, center, radius, 4)
+    full, none = hits == 4, hits == 0
+    assert full.sum() > 50 and none.sum() > 50
+    assert np.array_equal(albedo[full], np.broadcast_to(colour, albedo[full].shape))
+    assert np.abs(normal[full] - nref[full]).max() <= 1e-6
+    assert np.array_equal(albedo[none], np.broadcast_to(np.float32([0.7, 0.8, 1.0]), albedo[none].shape))
+    assert not normal[none].any()
+    # independent of the samples the handle holds
+    prog2 = scene.progressive(cam, cfg)
+    prog2.add(3)
+    a2, n2 = prog2.features(4)
+    assert np.array_equal(a2, albedo) and np.array_equal(n2, normal)
+    # f32 mode
+    scene32 = flat.upload(f32=True)
+    a32, n32 = scene32.progressive(cam, cfg).features(4)
+    ok = full | none
+    assert np.abs(a32[ok] - albedo[ok]).max() <= 1e-5 and np.abs(n32[ok] - normal[ok]).max() <= 1e-5
+    del prog, prog2
+
+
+def _material_scene(rtsr):
+    """Four spheres in a row, one per material kind the feature pass tells apart: Metal, Dielectric, DiffuseLight and a
+    dense ConstantMedium (Isotropic; it scatters within ~1e-3 of its boundary, so every ray that enters it hits it)."""
+    b = rtsr.Builder(1)
+    centers = [np.array([x, 0.0, -4.0]) for x in (-1.5, -0.5, 0.5, 1.5)]
+    radius = 0.4
+    metal, light, medium = (0.8, 0.5, 0.25), (4.0, 3.0, 2.0), (0.25, 0.75, 0.5)
+    objs = [b.sphere(tuple(centers[0]), radius, b.metal(metal, 0.3)),
+            b.sphere(tuple(centers[1]), radius, b.dielectric(1.5)),
+            b.sphere(tuple(centers[2]), radius, b.diffuse_light(light)),
+            b.constant_medium(medium, 1000.0, b.sphere(tuple(centers[3]), radius, b.lambertian((0.5, 0.5, 0.5))))]
+    world = b.hittable_list(objs)
+    cam = rtsr.Camera.new((0.0, 0.0, 0.0), (0.0, 0.0, -1.0), (0.0, 1.0, 0.0), 40.0, 2.0, 0.0, 1.0, 0.0, 1.0)
+    cfg = rtsr.Config.new(2.0, 64, 8, 50, 10, seed=7, background=(0.1, 0.2, 0.3))
+    expect = [np.float32(metal), np.float32([1, 1, 1]), np.float32([1, 1, 1]), np.float32(medium)]
+    return b, b.flatten(world), cam, cfg, centers, radius, expect
+
+
+def test_features_of_each_material(rtsr):
+    b, flat, cam, cfg, centers, radius, expect = _material_scene(rtsr)
+    albedo, normal = flat.upload().progressive(cam, cfg).features(4)
+    per = [_analytic_features(rtsr, cam, cfg, c, radius, 4) for c in centers]
+    for k, (hits, nref) in enumerate(per):
+        full = hits == 4
+        assert full.sum() >= 10, k
+        assert np.array_equal(albedo[full], np.broadcast_to(expect[k], albedo[full].shape)), k
+        if k == 3:
+            assert not normal[full].any()  # Isotropic: no surface normal
+        else:
+            assert np.abs(normal[full] - nref[full]).max() <= 1e-6, k
+    none = sum(h for h, _ in per) == 0
+    assert np.array_equal(albedo[none], np.broadcast_to(np.float32([0.1, 0.2, 0.3]), albedo[none].shape))
+    assert not normal[none].any()
+
+
+def _handle_vs_self_test(rtsr, prog):
+    den = prog.denoise()
+    S, Q = prog.moments()
+    m, v = dr.mean_var(S, Q, prog.pixel_spp())
+    A, N = prog.features(4)
+    out, rgb8 = rtsr.device_denoise(m, v, A, N)
+    assert np.array_equal(out.view(np.uint64), den.accum.view(np.uint64))
+    assert np.array_equal(rgb8, den.rgb8)
+    return den
+
+
+def test_handle_path_is_the_self_test_path(rtsr):
+    b, flat, scene, cam, cfg = _setup(rtsr, 4, 48, 1.0, 16)
+    prog = scene.progressive(cam, cfg)
+    prog.add(8)
+    _handle_vs_self_test(rtsr, prog)
+    ada = scene.progressive(cam, cfg)
+    ada.until_adaptive(4, 4, 0.05)
+    spp = ada.pixel_spp()
+    assert (spp < ada.spp_done).any() and (spp == ada.spp_done).any()
+    _handle_vs_self_test(rtsr, ada)
+    del prog, ada
+
+
+def test_denoise_waits_for_adds_on_another_stream(rtsr):
+    torch = pytest.importorskip("torch")
+    b, flat, scene, cam, cfg = _setup(rtsr, 6, 96, 1.0, 64)
+    prog = scene.progressive(cam, cfg)
+    stream = torch.cuda.Stream()  # a non-blocking stream: the null stream does not wait for it by itself
+    prog.add(4, stream=stream.cuda_stream)
+    prog.denoise()  # features computed and cached
+    for _ in range(3):
+        prog.add(16, stream=stream.cuda_stream)  # asynchronous
+        den = prog.denoise()  # must see every sample of the add
+        S, Q = prog.moments()
+        m, v = dr.mean_var(S, Q, prog.spp_done)
+        A, N = prog.features(4)
+        out, rgb8 = rtsr.device_denoise(m, v, A, N)
+        assert np.array_equal(out.view(np.uint64), den.accum.view(np.uint64))
+    del prog
+
+
+def test_denoising_disturbs_nothing(rtsr):
+    b, flat, scene, cam, cfg = _setup(rtsr, 4, 40, 1.0, 16)
+    prog = scene.progressive(cam, cfg)
+    prog.add(8)
+    first = prog.denoise()
+    again = prog.denoise(iterations=3)  # another rule on the same handle
+    assert not np.array_equal(first.accum, again.accum)
+    assert np.array_equal(prog.denoise().accum, first.accum)
+    prog.add(8)
+    fresh = scene.progressive(cam, cfg)
+    fresh.add(16)
+    for x, y in zip(prog.moments(), fresh.moments()):
+        assert np.array_equal(x.view(np.uint64), y.view(np.uint64))
+    assert prog.spp_done == 16
+    del prog, fresh
+
+
+def _rel_mse(x, ref):
+    return float(np.mean((x - ref) ** 2 / (ref * ref + 1e-2)))
+
+
+def _edge_band(A, N):
+    """Pixels whose albedo or normal differs from one of their 4-neighbours."""
+    band = np.zeros(A.shape[:2], dtype=bool)
+    for g in (A, N):
+        for axis in (0, 1):
+            d = np.abs(np.diff(g, axis=axis)).max(axis=2) > 1e-3
+            if axis == 0:
+                band[1:] |= d
+                band[:-1] |= d
+            else:
+                band[:, 1:] |= d
+                band[:, :-1] |= d
+    return band
+
+
+# denoised / noisy relMSE at 16 spp with the default parameters, measured on an MI355X: Cornell 0.21, Book-2 0.24 (this
+# test prints them); pinned with margin
+QUALITY = {4: 0.3, 6: 0.35}
+
+
+@pytest.mark.parametrize("sid", [4, 6])
+def test_denoising_quality(rtsr, sid):
+    b, flat, scene, cam, cfg = _setup(rtsr, sid, 128, 1.0, 1024)
+    prog = scene.progressive(cam, cfg)
+    prog.add(16)
+    noisy = prog.moments()[0] / 16.0
+    den = prog.denoise().accum
+    A, N = prog.features(4)
+    prog.add(1024 - 16)
+    ref = prog.moments()[0] / 1024.0
+    band = _edge_band(A, N)
+    r_noisy, r_den = _rel_mse(noisy, ref), _rel_mse(den, ref)
+    e_noisy, e_den = _rel_mse(noisy[band], ref[band]), _rel_mse(den[band], ref[band])
+    print("scene %d: relMSE noisy %.5f denoised %.5f (ratio %.3f); edge band (%d px) noisy %.5f denoised %.5f (ratio %.3f)"
+          % (sid, r_noisy, r_den, r_den / r_noisy, band.sum(), e_noisy, e_den, e_den / e_noisy))
+    assert r_den <= QUALITY[sid] * r_noisy
+    assert band.sum() > 100 and e_den <= e_noisy
+    del prog
+
+
+def test_error_cases(rtsr):
+    b, flat, scene, cam, cfg = _setup(rtsr, 4, 32, 1.0, 8)
+    sharded = scene.progressive(cam, cfg, shard=(0, 2, 1))
+    sharded.add(2)
+    for call in (lambda: sharded.denoise(), lambda: sharded.features(4)):
+        with pytest.raises(rtsr.RtxError) as e:
+            call()
+        assert e.value.status == rtsr.RTX_EUNSUPPORTED
+    cfg_c = rtsr.Config.new(1.0, 32, 8, 50, 10, seed=3, background=(0.0, 0.0, 0.0), row_chunk_compat=True)
+    compat = scene.progressive(cam, cfg_c)
+    compat.add(2)
+    with pytest.raises(rtsr.RtxError) as e:
+        compat.denoise()
+    assert e.value.status == rtsr.RTX_EUNSUPPORTED
+    prog = scene.progressive(cam, cfg)
+    for n in (0, 1):
+        with pytest.raises(rtsr.RtxError) as e:
+            prog.denoise()
+        assert e.value.status == rtsr.RTX_EINVAL
+        prog.add(1)
+    S0 = prog.moments()
+    for bad in (dict(iterations=9), dict(feature_spp=65), dict(sigma_normal=-1.0), dict(demodulate=3)):
+        with pytest.raises(rtsr.RtxError) as e:
+            prog.denoise(**bad)
+        assert e.value.status == rtsr.RTX_EINVAL
+    assert prog.spp_done == 2 and all(np.array_equal(x, y) for x, y in zip(S0, prog.moments()))
+    prog.denoise()
+    del sharded, compat, prog
+
+
+def _read_ppm(path):
+    tok = open(path).read().split()
+    assert tok[0] == "P3"
+    w, h = int(tok[1]), int(tok[2])
+    px = np.array(tok[4:], dtype=np.int32).reshape(h, w, 3)
+    return px[::-1].astype(np.uint8)  # top row first -> row 0 = bottom
+
+
+def test_app_writes_the_denoised_frame(rtsr, tmp_path):
+    assert os.path.exists(APP)
+    out, al, nm, noisy = (str(tmp_path / n) for n in ("d.ppm", "a.ppm", "n.ppm", "noisy.ppm"))
+    res = subprocess.run([APP, "--scene", "4", "--width", "64", "--aspect", "1.0", "--spp", "8", "--batch", "4",
+                          "--target-error", "0", "--denoise", "--albedo-out", al, "--normal-out", nm, "--noisy-out", noisy,
+                          "--out", out], capture_output=True, text=True, timeout=300)
+    assert res.returncode == 0, res.stderr
+    b = rtsr.Builder(1)
+    world, cam, bg = b.get_world_cam(4)
+    cfg = rtsr.Config.new(1.0, 64, 8, 50, 11, seed=1, background=bg)
+    screen, _ = rtsr.render_scene_progressive(b, world, cam, bg, cfg, 4, 0.0, denoise=True)
+    assert np.array_equal(_read_ppm(out), screen.rgb8)
+    assert np.array_equal(_read_ppm(noisy), screen.noisy.rgb8)
+    for p in (al, nm):
+        img = _read_ppm(p)
+        assert img.shape == screen.rgb8.shape and img.max() > 0
