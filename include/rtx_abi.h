@@ -219,7 +219,8 @@ enum {
   RTX_KERNEL_LDS = 4,        /* RTX_KERNEL_VOTE with the geometry resident in LDS (sphere worlds that fit) */
   RTX_KERNEL_WQ = 5,         /* retired: workgroup-level path queues in LDS */
   RTX_KERNEL_WORLD = 6,      /* any world: per-lane scan of the world list, walks of every BVH entry carried over */
-  RTX_KERNEL_WAVEFRONT = 7   /* split-kernel integrator: path state in HBM, k_wf_generate / k_wf_trace / k_wf_shade per bounce */
+  RTX_KERNEL_WAVEFRONT = 7,  /* split-kernel integrator: path state in HBM, k_wf_generate / k_wf_trace / k_wf_shade per bounce */
+  RTX_KERNEL_NEE = 8         /* next-event estimation (rtx_render_ex with light_sampling = 1): persistent waves, whole paths per lane */
 };
 const char* rtx_trace_kernel_name(int32_t kernel);
 /* Blocking; host output buffers.  Renders the whole image on the current device. */
@@ -392,6 +393,51 @@ rtx_status rtx_progressive_denoise(rtx_progressive* p, const RtxDenoiseParams* p
 rtx_status rtx_device_denoise(const double* mean_rgb, const double* var_rgb, const float* albedo_rgb, const float* normal_xyz,
                               int32_t width, int32_t height, const RtxDenoiseParams* params, double* out_mean_rgb,
                               uint8_t* out_rgb8);
+
+/* ---- light sampling: next-event estimation with multiple importance sampling ---------------------------------------- */
+/* An extension: a second, opt-in estimator, STATISTICAL like the f32 mode and the denoiser (no bit-exactness claim against
+ * the reference).  The reference's estimator (world.rs:52-93) finds a light only when a scattered ray happens to hit it.
+ * With light_sampling = 1, every Lambertian and Isotropic vertex also connects to a point sampled on a light:
+ *   light table  the top-level slots that are a plain XyRect / XzRect / YzRect or a static Sphere with a DiffuseLight material
+ *                (no transform, no medium around them).  Every other emitter -- in a BVH or a group, wrapped, moving, gravity,
+ *                triangle -- is an unsampled emitter, reached by the material's own sampling with weight 1.  Light k is picked
+ *                with probability proportional to area x the max channel of its emitted colour at its centre (uniform when
+ *                every such product is 0).  Built on the host (rtx_flat_lights reports it), uploaded on first use, freed
+ *                with the scene.
+ *   per vertex   after the material's scatter has drawn (the reference's order), and only when the path may take another
+ *                bounce (depth - 1 >= 0, the rule of world.rs:64-67: the connection counts as the next hit): one uniform
+ *                picks the light, two more a point q on it -- a rectangle uniformly over its area (solid-angle pdf
+ *                d^2 / (|cos theta_l| A), both faces emit), a sphere uniformly over the cone it subtends (pdf 1 / (2 pi
+ *                (1 - cos theta_max)); 0 from inside it).  A shadow ray p -> q (direction q - p, the path's shutter time)
+ *                over t in [0.001, 1 - 1e-6] is occluded by any accepted hit, a ConstantMedium's random hit included (it
+ *                draws from the path's stream).  Unoccluded, the vertex adds product x f x Le x w_light / p_light with
+ *                f = albedo max(0, cos) / pi (Lambertian, about the hit record's normal) or albedo / (4 pi) (Isotropic),
+ *                Le the light's texture at q and w_light = p_light^2 / (p_light^2 + p_bsdf^2) (power heuristic).
+ *   light hits   a scattered ray from a Lambertian / Isotropic vertex that hits a sampled light scales its emitted radiance
+ *                by p_bsdf^2 / (p_bsdf^2 + p_light^2), p_light that light's pdf at that point; emitters reached from the
+ *                camera, from Metal or Dielectric vertices, and unsampled emitters keep weight 1.
+ * With an empty light table the estimator draws and adds exactly what the reference's does: the frame is bit-identical to
+ * rtx_render's.  Results are deterministic and independent of how samples are split into calls or shards.  The f32 mode,
+ * rtx_multi_*, rtx_render_count and the wavefront integrator have no light sampling. */
+typedef struct RtxIntegratorOptions {   /* 16 B */
+  int32_t light_sampling;  /* 0: the reference's estimator (what rtx_render does); 1: next-event estimation + MIS */
+  int32_t reserved[3];     /* must be 0 */
+} RtxIntegratorOptions;
+typedef struct RtxLightInfo {
+  int32_t n_lights, n_rect_lights, n_sphere_lights, n_unsampled_emitters;
+  double total_area;       /* summed area of the sampled lights */
+} RtxLightInfo;
+/* Host only: no GPU needed.  The census of the light table above. */
+rtx_status rtx_flat_lights(const rtx_flat* f, RtxLightInfo* out);
+/* rtx_render with options: opt NULL or light_sampling = 0 is rtx_render exactly.  stats may be NULL.  A light_sampling other
+ * than 0 / 1 or a non-zero reserved word is RTX_EINVAL before any device call; an f32 scene with light_sampling = 1 is
+ * RTX_EUNSUPPORTED.  Blocking, host output buffers. */
+rtx_status rtx_render_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
+                         const RtxIntegratorOptions* opt, RtxFrame* out, RtxRenderStats* stats);
+/* rtx_progressive_create with options (same errors as rtx_render_ex).  A handle made with light sampling uses it for every
+ * add -- uniform, adaptive and until; its stats, read and denoise are unchanged. */
+rtx_status rtx_progressive_create_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
+                                     const RtxShard* shard, const RtxIntegratorOptions* opt, rtx_progressive** out);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

@@ -102,6 +102,19 @@ class RtxDenoiseParams(C.Structure):
                 ("sigma_luminance", C.c_double), ("sigma_normal", C.c_double), ("sigma_albedo", C.c_double)]
 
 
+class RtxIntegratorOptions(C.Structure):
+    _fields_ = [("light_sampling", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class RtxLightInfo(C.Structure):
+    _fields_ = [("n_lights", C.c_int32), ("n_rect_lights", C.c_int32), ("n_sphere_lights", C.c_int32),
+                ("n_unsampled_emitters", C.c_int32), ("total_area", C.c_double)]
+
+
+def _integrator_options(light_sampling):
+    return RtxIntegratorOptions(1 if light_sampling else 0)
+
+
 # Every symbol include/rtx_abi.h declares: (restype, argtypes).  tests/test_abi_symbols.py checks
 # this table against the header and against the loaded library.
 _D3 = C.POINTER(C.c_double)
@@ -187,6 +200,11 @@ ABI = {
     "rtx_progressive_denoise": (C.c_int32, [_VP, C.POINTER(RtxDenoiseParams), _D3, C.POINTER(C.c_uint8)]),
     "rtx_device_denoise": (C.c_int32, [_D3, _D3, _F3, _F3, C.c_int32, C.c_int32, C.POINTER(RtxDenoiseParams), _D3,
                                        C.POINTER(C.c_uint8)]),
+    "rtx_flat_lights": (C.c_int32, [_VP, C.POINTER(RtxLightInfo)]),
+    "rtx_render_ex": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxIntegratorOptions),
+                                  C.POINTER(RtxFrame), C.POINTER(RtxRenderStats)]),
+    "rtx_progressive_create_ex": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxShard),
+                                              C.POINTER(RtxIntegratorOptions), C.POINTER(_VP)]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -421,6 +439,13 @@ class Flat:
         _check(lib.rtx_flat_info(self._p, C.byref(info)))
         return {n: getattr(info, n) for n, _ in RtxFlatInfo._fields_}
 
+    def lights(self):
+        """Census of next-event estimation's light table (rtx_flat_lights): n_lights, n_rect_lights, n_sphere_lights,
+        n_unsampled_emitters, total_area."""
+        info = RtxLightInfo()
+        _check(lib.rtx_flat_lights(self._p, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in RtxLightInfo._fields_}
+
     def top_level_kinds(self):
         """Entry kinds of the flattened world list, in HittableList order (rtx_flat_top_level_kind)."""
         n = self.info()["n_top_level"]
@@ -452,13 +477,22 @@ class Scene:
     def ptr(self):
         return self._p
 
-    def render(self, cam, cfg, want_accum=True):
-        """Whole image on the current device -> Screen (host arrays)."""
+    def render(self, cam, cfg, want_accum=True, light_sampling=False, want_stats=False):
+        """Whole image on the current device -> Screen (host arrays).  light_sampling=True: next-event estimation with MIS
+        (rtx_render_ex; statistical, f64 scenes only).  want_stats=True: Screen.stats holds the RtxRenderStats."""
         w, h = cfg.image_width, image_height(cfg)
         accum = np.zeros((h, w, 3), dtype=np.float64) if want_accum else None
         rgb8 = np.zeros((h, w, 3), dtype=np.uint8)
         frame = RtxFrame(accum.ctypes.data_as(C.POINTER(C.c_double)) if want_accum else None,
                          rgb8.ctypes.data_as(C.POINTER(C.c_uint8)))
+        if light_sampling or want_stats:
+            stats = RtxRenderStats() if want_stats else None
+            opt = _integrator_options(light_sampling)
+            _check(lib.rtx_render_ex(self._p, C.byref(cam), C.byref(cfg), C.byref(opt), C.byref(frame),
+                                     C.byref(stats) if stats else None))
+            screen = Screen(w, h, rgb8, accum)
+            screen.stats = stats
+            return screen
         _check(lib.rtx_render(self._p, C.byref(cam), C.byref(cfg), C.byref(frame)))
         return Screen(w, h, rgb8, accum)
 
@@ -480,9 +514,10 @@ class Scene:
                                      C.byref(stats) if stats else None))
         return stats
 
-    def progressive(self, cam, cfg, shard=None):
-        """A frame accumulated over several calls (rtx_progressive); cfg.samples_per_pixel is the sample budget."""
-        return Progressive(self, cam, cfg, shard)
+    def progressive(self, cam, cfg, shard=None, light_sampling=False):
+        """A frame accumulated over several calls (rtx_progressive); cfg.samples_per_pixel is the sample budget.
+        light_sampling=True: every add traces with next-event estimation (rtx_progressive_create_ex)."""
+        return Progressive(self, cam, cfg, shard, light_sampling=light_sampling)
 
     def render_count(self, cam, cfg, shard=None):
         sh = RtxShard(*shard, 0) if shard is not None else None
@@ -500,13 +535,19 @@ class Progressive:
     that stopped at n_p samples (pixel_spp()) then holds the bits of a one-shot render at n_p spp.
     """
 
-    def __init__(self, scene, cam, cfg, shard=None):
+    def __init__(self, scene, cam, cfg, shard=None, light_sampling=False):
         self.scene = scene  # the handle must be destroyed before its scene
         self.width = cfg.image_width
         self.height = shard_rows(cfg, shard) if shard is not None else image_height(cfg)
         sh = RtxShard(*shard, 0) if shard is not None else None
         p = _VP()
-        _check(lib.rtx_progressive_create(scene.ptr, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None, C.byref(p)))
+        if light_sampling:
+            opt = _integrator_options(True)
+            _check(lib.rtx_progressive_create_ex(scene.ptr, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None,
+                                                 C.byref(opt), C.byref(p)))
+        else:
+            _check(lib.rtx_progressive_create(scene.ptr, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None,
+                                              C.byref(p)))
         self._p = p
 
     def __del__(self):
@@ -753,17 +794,18 @@ def render_scene(builder, world, cam, background, config, max_leaf=0):
 
 
 def render_scene_progressive(builder, world, cam, background, config, batch, target_rel_err, max_leaf=0, adaptive=False,
-                             min_spp=2, denoise=False):
+                             min_spp=2, denoise=False, light_sampling=False):
     """render_scene, refined `batch` samples at a time until no pixel's relative error exceeds target_rel_err or
     config.samples_per_pixel is reached.  Returns (Screen, RtxNoiseStats of the last batch).
     adaptive=True: pixels at or below the target stop receiving samples (checked from min_spp samples on); returns
     (Screen, RtxAdaptiveStats), and Screen.spp holds each pixel's sample count.
     denoise=True: the Screen is the denoised frame (Progressive.denoise with the default parameters; accum is the MEAN
-    radiance, not a sum) and Screen.noisy holds the frame as accumulated."""
+    radiance, not a sum) and Screen.noisy holds the frame as accumulated.
+    light_sampling=True: every batch traces with next-event estimation and MIS (statistical; rtx_progressive_create_ex)."""
     cfg = RtxConfig.from_buffer_copy(config)
     cfg.background[0], cfg.background[1], cfg.background[2] = background
     scene = builder.flatten(world, max_leaf=max_leaf).upload()
-    prog = scene.progressive(cam, cfg)
+    prog = scene.progressive(cam, cfg, light_sampling=light_sampling)
     if adaptive:
         stats = prog.until_adaptive(batch, min_spp, target_rel_err)
     else:

@@ -9,6 +9,7 @@
 //              [--batch N --target-error E --adaptive [--min-spp M] [--spp-map FILE.pgm]]
 //              [--batch N --target-error E [--adaptive ...] --denoise [--noisy-out FILE.ppm] [--albedo-out FILE.ppm]
 //               [--normal-out FILE.ppm]]
+//              [--light-sampling]
 //
 // --batch / --target-error render progressively: N samples at a time until no pixel's relative error exceeds E or --spp
 // samples are in (rtx_progressive_until); the spp reached and the final noise stats go to stderr.  --snapshot-every K
@@ -19,6 +20,8 @@
 // --denoise (with --batch) writes the denoised frame (rtx_progressive_denoise, default parameters) where the frame would go;
 // --noisy-out gets the frame as accumulated, --albedo-out and --normal-out the filter's first-hit guides (albedo clamped to
 // [0, 1], normal mapped to 0.5 + 0.5 n; linear, not tone-mapped).
+// --light-sampling traces with next-event estimation and MIS (rtx_render_ex / rtx_progressive_create_ex; statistical), in
+// every mode above.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -58,6 +61,7 @@ int main(int argc, char** argv) {
   const char* noisy_out = nullptr;
   const char* albedo_out = nullptr;
   const char* normal_out = nullptr;
+  bool light_sampling = false;
   for (int i = 1; i < argc; ++i) {
     auto need = [&](const char* flag) -> const char* {
       if (i + 1 >= argc) { fprintf(stderr, "%s needs a value\n", flag); exit(2); }
@@ -86,6 +90,7 @@ int main(int argc, char** argv) {
     else if (!strcmp(argv[i], "--noisy-out")) noisy_out = need("--noisy-out");
     else if (!strcmp(argv[i], "--albedo-out")) albedo_out = need("--albedo-out");
     else if (!strcmp(argv[i], "--normal-out")) normal_out = need("--normal-out");
+    else if (!strcmp(argv[i], "--light-sampling")) light_sampling = true;
     else { fprintf(stderr, "unknown argument %s\n", argv[i]); return 2; }
   }
   const bool progressive = batch > 0 || target_error >= 0.0;
@@ -139,9 +144,14 @@ int main(int argc, char** argv) {
     rtsr::Screen screen;
     rtsr::DenoiseOutputs dn;
     rtsr::DenoiseOutputs* dnp = denoise ? &dn : nullptr;
+    RtxIntegratorOptions iopt;
+    memset(&iopt, 0, sizeof(iopt));
+    iopt.light_sampling = 1;
+    const RtxIntegratorOptions* integrator = light_sampling ? &iopt : nullptr;
     if (adaptive) {
       RtxAdaptiveStats as = {};
-      screen = rtsr::render_scene_adaptive(scene, wc.world, wc.cam, wc.background, config, batch, min_spp, target_error, &as, dnp);
+      screen = rtsr::render_scene_adaptive(scene, wc.world, wc.cam, wc.background, config, batch, min_spp, target_error, &as, dnp,
+                                           integrator);
       const double uniform = (double)as.spp_done * (double)as.pixels;
       fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", as.spp_done,
               spp, target_error, as.pixels_above, as.pixels, as.max_rel_err, as.mean_rel_err);
@@ -156,11 +166,11 @@ int main(int argc, char** argv) {
         s.write_to_ppm_file(path.c_str());
       };
       screen = rtsr::render_scene_progressive(scene, wc.world, wc.cam, wc.background, config, batch, target_error, &ns,
-                                              snapshot_every, snap, dnp);
+                                              snapshot_every, snap, dnp, integrator);
       fprintf(stderr, "spp reached: %d of %d; pixels above %g: %d of %d; max rel err %.6g, mean rel err %.6g\n", ns.spp_done,
               spp, target_error, ns.pixels_above, ns.pixels, ns.max_rel_err, ns.mean_rel_err);
     } else {
-      screen = rtsr::render_scene(scene, wc.world, wc.cam, wc.background, config);  // main.rs:13
+      screen = rtsr::render_scene(scene, wc.world, wc.cam, wc.background, config, nullptr, integrator);  // main.rs:13
     }
     if (noisy_out) dn.noisy.write_to_ppm_file(noisy_out);
     if (albedo_out) write_feature_ppm(albedo_out, screen.width, screen.height, dn.albedo, 0.0, 1.0);

@@ -510,9 +510,11 @@ RT_HD void xform_record_chain(const FlatXformOp* ops, int nops, const Ray& outer
 // A ConstantMedium asks its boundary twice (rec1 over (-inf, inf), rec2 from rec1.t + 0.0001),
 // then draws one uniform from the path's stream -- inside the intersection, exactly where
 // the reference draws it (hit.rs:969).
-template <uint32_t F, bool COUNT, class STACK>
+// SLOT = true (next-event estimation only, core/integrator.hpp) also reports the top-level slot of the winning entry in
+// *hit_slot; every other caller leaves it false and compiles to the same code as without it.
+template <uint32_t F, bool COUNT, class STACK, bool SLOT = false>
 RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, HitRecord* rec,
-                     Rng& rng, STACK& stack, TraceCounters* cnt) {
+                     Rng& rng, STACK& stack, TraceCounters* cnt, int32_t* hit_slot = nullptr) {
   if (COUNT) cnt->rays++;
   bool hit_anything = false;
   real closest_so_far = t_max;
@@ -586,6 +588,7 @@ RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, 
     }
     hit_anything = true;
     closest_so_far = rec->t;
+    if (SLOT) *hit_slot = i;
   }
   return hit_anything;
 }

@@ -6,6 +6,7 @@
 #include <new>
 #include <string>
 #include "../host/scenes.hpp"
+#include "../host/light_table.hpp"
 #include "abi_internal.hpp"
 
 namespace rtx {
@@ -38,6 +39,7 @@ const char* rtx_trace_kernel_name(int32_t kernel) {
     case RTX_KERNEL_WQ: return "k_trace_wq";
     case RTX_KERNEL_WORLD: return "k_trace_world";
     case RTX_KERNEL_WAVEFRONT: return "k_wf_trace";
+    case RTX_KERNEL_NEE: return "k_trace_nee";
     default: return "?";
   }
 }
@@ -219,6 +221,17 @@ rtx_status rtx_flat_info(const rtx_flat* f, RtxFlatInfo* o) {
   o->max_stack = s.max_stack; o->n_bvh = s.n_bvh; o->sah_cost = s.sah_cost;
   o->bvh_build_ms = s.bvh_build_ms; o->bvh_device_ms = s.bvh_device_ms;
   o->n_gravity_spheres = (int64_t)s.gravity_spheres.size();
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_lights(const rtx_flat* f, RtxLightInfo* o) {
+  if (!f || !o) { set_error("rtx_flat_lights: NULL argument"); return RTX_EINVAL; }
+  const LightTable t = build_light_table(f->scene);
+  o->n_lights = (int32_t)t.lights.size();
+  o->n_rect_lights = t.n_rect;
+  o->n_sphere_lights = t.n_sphere;
+  o->n_unsampled_emitters = t.n_unsampled;
+  o->total_area = t.total_area;
   return RTX_OK;
 }
 

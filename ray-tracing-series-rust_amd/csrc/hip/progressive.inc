@@ -50,6 +50,7 @@ struct rtx_progressive {
   uint32_t npix_all;  // pixels of the shard
   uint32_t npix;      // of which active (row_chunk_compat leaves the rest zero)
   int32_t spp_done;
+  bool light_sampling;  // every add traces with next-event estimation (rtx_progressive_create_ex)
   bool broken;        // a failed add left S / Q partly updated
   double* S;
   double* Q;
@@ -90,7 +91,7 @@ void progressive_free(rtx_progressive* p) {
 }
 
 rtx_status progressive_add(rtx_progressive* p, int32_t n_samples, hipStream_t stream, RtxRenderStats* stats) {
-  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n_samples, p->spp_done > 0 ? 1 : 0, p->Q};
+  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n_samples, p->spp_done > 0 ? 1 : 0, p->Q, nullptr, 0u, p->light_sampling};
   rtx_status st;
   if (p->scene->f32)
     st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
@@ -260,7 +261,7 @@ rtx_status adaptive_trace(rtx_progressive* p, int32_t n, hipStream_t stream, Rtx
     p->spp_done += n;
     return RTX_OK;
   }
-  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n, 1, p->Q, p->active[p->cur], p->n_active};
+  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n, 1, p->Q, p->active[p->cur], p->n_active, p->light_sampling};
   rtx_status st;
   if (p->scene->f32)
     st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
@@ -415,6 +416,18 @@ rtx_status download_xyz(const float4* d, size_t npix, float* out) {
 }  // namespace
 
 extern "C" {
+
+rtx_status rtx_progressive_create_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
+                                     const RtxIntegratorOptions* opt, rtx_progressive** out) {
+  if (!out) { set_error("rtx_progressive_create_ex: NULL out"); return RTX_EINVAL; }
+  *out = nullptr;
+  bool nee = false;
+  rtx_status st = check_integrator_options(s, opt, "rtx_progressive_create_ex", &nee);
+  if (st != RTX_OK) return st;
+  st = rtx_progressive_create(s, cam, cfg, shard, out);
+  if (st == RTX_OK) (*out)->light_sampling = nee;
+  return st;
+}
 
 rtx_status rtx_progressive_create(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
                                   rtx_progressive** out) {

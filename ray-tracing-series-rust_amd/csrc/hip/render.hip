@@ -27,6 +27,7 @@
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
 #include "../host/flat_scene.hpp"
+#include "../host/light_table.hpp"
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
@@ -174,6 +175,7 @@ struct DeviceScene {
   WorldPlan world;
   LdsPlan lds;
   WalkTuning walk;
+  rt::LightView lights = {nullptr, nullptr, 0, 0};  // next-event estimation's light table (k_trace_nee), uploaded with the scene
 };
 
 #define HIP_TRY(expr)                                                                      \
@@ -276,6 +278,9 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_wave.inc"    // k_wf_generate / k_wf_trace / k_wf_shade: the split-kernel integrator (path state in HBM)
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
+#ifndef RTX_F32_TU
+#include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
+#endif
 
 // ------------------------------------------------------------------ launcher
 static int shard_row_count(int32_t height, const RtxShard& sh, int32_t row_limit) {
@@ -807,6 +812,31 @@ static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
 #undef LAUNCH_SIMPLE2
 }
 
+#ifndef RTX_F32_TU
+// ------------------------------------------------------------------ k_trace_nee
+// Three presets cover every world the default launcher accepts: the dragon room exactly, any world without GravitySpheres, and
+// everything.  Persistent: as many blocks as are resident, at most one per TRACE_CHUNK items.
+static rtx_status launch_nee(const DeviceScene* ds, const PassArgs& a) {
+  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
+  const int preset = (a.feat & ~P_MESH_ROOM) == 0 ? 0 : ((a.feat & rt::F_GRAVITY_SPHERE) ? 2 : 1);
+#define LAUNCH_NEE(FEAT, MAP)                                                                                                   \
+  do {                                                                                                                          \
+    const int nb = occupancy(k_trace_nee<FEAT, decltype(MAP)>, a.stack_lds);                                                    \
+    const uint32_t grid = grid_size(a.total, TRACE_CHUNK, (uint64_t)ds->n_cu * (uint64_t)(nb > 0 ? nb : 1) * (TRACE_BLOCK / 64)); \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_nee<FEAT, decltype(MAP)>), dim3((grid + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64)),     \
+                       dim3(TRACE_BLOCK), a.stack_lds, a.stream, ds->view, ds->lights, a.rp, MAP, a.s_begin, a.total, a.npix,     \
+                       a.samples, a.work_counter);                                                                              \
+  } while (0)
+  with_map(a, [&](auto map) {
+    if (preset == 0) LAUNCH_NEE(P_MESH_ROOM, map);
+    else if (preset == 1) LAUNCH_NEE(P_ANY, map);
+    else LAUNCH_NEE(P_ALL, map);
+  });
+#undef LAUNCH_NEE
+  return RTX_OK;
+}
+#endif  // !RTX_F32_TU
+
 // ------------------------------------------------------------------ wavefront integrator
 // One pass (a.total (sample, pixel) items) through the wavefront integrator: iterations of generate -> trace -> shade over the P
 // path slots until every sample of the pass has been written.  It applies where k_trace_vote does (VotePlan::ok).
@@ -930,12 +960,14 @@ static int32_t choose_trace_kernel(const DeviceScene* ds, int preset, bool count
 // squares kept in sumsq when it is not NULL.  A render without one (range == NULL) is the whole frame from sample 0.
 // An adaptive range (active != NULL: the ascending list of the n_active local pixels still active) traces those pixels only;
 // they replace the shard's pixels as the items of every pass (pass_items.inc), and it needs cont and sumsq.
+// light_sampling: trace with next-event estimation (k_trace_nee) instead of the reference's estimator.
 struct SampleRange {
   uint32_t first, count;
   int cont;
   double* sumsq;
   const uint32_t* active;
   uint32_t n_active;
+  bool light_sampling;
 };
 
 // How one render is cut into passes: samples of every pixel per pass, passes two deep or not, bytes of the sample buffer.
@@ -1070,7 +1102,9 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   if (stack_bytes(stack_levels) > 64 * 1024) { set_error("render: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
   const uint32_t feat = ds->view.features;
   const int preset = ((feat & ~P_SPHERES) == 0) ? 0 : (((feat & ~P_MESH) == 0) ? 1 : 2);
-  const int32_t kernel = choose_trace_kernel(ds, preset, COUNT);
+  const bool nee = range && range->light_sampling;
+  if (nee && COUNT) { set_error("render: light sampling has no counting kernel"); return RTX_EUNSUPPORTED; }
+  const int32_t kernel = nee ? (int32_t)RTX_KERNEL_NEE : choose_trace_kernel(ds, preset, COUNT);
   PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)nitem, nullptr, nullptr, stream,
                 preset, feat, stack_levels, stack_bytes(stack_levels), adaptive ? range->active : nullptr};
 
@@ -1100,6 +1134,9 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
         case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam); break;
         case RTX_KERNEL_WAVEFRONT: st = wave_pass(ds, a); break;
         case RTX_KERNEL_VOTE: st = launch_vote(ds, a); break;
+#ifndef RTX_F32_TU
+        case RTX_KERNEL_NEE: st = launch_nee(ds, a); break;
+#endif
         default: st = launch_world(ds, a); break;  // RTX_KERNEL_WORLD
       }
       if (st != RTX_OK) return st;
@@ -1211,6 +1248,19 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   UP(nodes, nodes) UP(nodes32, nodes32) UP(motion32, motion32) UP(refs, refs) UP(entries, entries) UP(top_level, top_level)
   UP(materials, materials) UP(textures, textures) UP(perlins, perlins) UP(images, images) UP(texels, texels)
   UP(top_box32, top_box32) UP(gravity_spheres, gravity_spheres) UP(gravity_y, gravity_y)
+#ifndef RTX_F32_TU
+  {
+    // next-event estimation's light table (host/light_table.hpp): a few records and one int per slot, only when there are lights
+    const LightTable lt = build_light_table(fs);
+    if (!lt.lights.empty()) {
+      if ((st = upload_array(ds, lt.lights, &ds->lights.lights)) != RTX_OK || (st = upload_array(ds, lt.slot_light, &ds->lights.slot_light)) != RTX_OK) {
+        free_device_scene(ds);
+        return st;
+      }
+      ds->lights.n_lights = (int32_t)lt.lights.size();
+    }
+  }
+#endif
 #undef UP
   v.n_top_level = (int32_t)fs.top_level.size();
   v.max_stack = fs.max_stack;
@@ -1372,6 +1422,62 @@ rtx_status rtx_render(const rtx_scene* s, const RtxCamera* cam, const RtxConfig*
     if (e == hipSuccess && out->accum_rgb) e = hipMemcpy(out->accum_rgb, d_accum, npix * 24, hipMemcpyDeviceToHost);
     if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d_rgb, npix * 3, hipMemcpyDeviceToHost);
     if (e != hipSuccess) { set_error(std::string("rtx_render: ") + hipGetErrorString(e)); st = RTX_EHIP; }
+  }
+  (void)hipFree(d_accum);
+  (void)hipFree(d_rgb);
+  return st;
+}
+
+// Argument checks of the *_ex entry points, before any device call.
+static rtx_status check_integrator_options(const rtx_scene* s, const RtxIntegratorOptions* opt, const char* who, bool* light_sampling) {
+  *light_sampling = false;
+  if (!opt) return RTX_OK;
+  if (opt->light_sampling != 0 && opt->light_sampling != 1) {
+    set_error(std::string(who) + ": light_sampling must be 0 or 1");
+    return RTX_EINVAL;
+  }
+  if (opt->reserved[0] || opt->reserved[1] || opt->reserved[2]) {
+    set_error(std::string(who) + ": RtxIntegratorOptions.reserved must be 0");
+    return RTX_EINVAL;
+  }
+  if (opt->light_sampling && s && s->f32) {
+    set_error(std::string(who) + ": light sampling is f64 only (upload the scene with rtx_scene_upload)");
+    return RTX_EUNSUPPORTED;
+  }
+  *light_sampling = opt->light_sampling == 1;
+  return RTX_OK;
+}
+
+rtx_status rtx_render_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, const RtxIntegratorOptions* opt,
+                         RtxFrame* out, RtxRenderStats* stats) {
+  if (!out) { set_error("rtx_render_ex: NULL frame"); return RTX_EINVAL; }
+  bool nee = false;
+  rtx_status st = check_integrator_options(s, opt, "rtx_render_ex", &nee);
+  if (st != RTX_OK) return st;
+  RtxShard sh;
+  st = validate(s, cam, cfg, nullptr, &sh);
+  if (st != RTX_OK) return st;
+  if (!nee && !stats) return rtx_render(s, cam, cfg, out);
+  size_t npix = (size_t)cfg->image_width * (size_t)rtx_image_height(cfg);
+  double* d_accum = nullptr;
+  uint8_t* d_rgb = nullptr;
+  if (hipMalloc((void**)&d_accum, npix * 24) != hipSuccess || hipMalloc((void**)&d_rgb, npix * 3) != hipSuccess) {
+    if (d_accum) (void)hipFree(d_accum);
+    set_error("rtx_render_ex: hipMalloc of the frame failed");
+    return RTX_EHIP;
+  }
+  if (nee) {
+    // the whole frame as one sample range from sample 0: the passes, sums and tone map of a one-shot render
+    const SampleRange range = {0u, (uint32_t)cfg->samples_per_pixel, 0, nullptr, nullptr, 0u, true};
+    st = render_impl<false>(scene_device(s), cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, stats, &range);
+  } else {
+    st = render_any<false>(s, cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, stats);
+  }
+  if (st == RTX_OK) {
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && out->accum_rgb) e = hipMemcpy(out->accum_rgb, d_accum, npix * 24, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d_rgb, npix * 3, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) { set_error(std::string("rtx_render_ex: ") + hipGetErrorString(e)); st = RTX_EHIP; }
   }
   (void)hipFree(d_accum);
   (void)hipFree(d_rgb);

@@ -212,9 +212,10 @@ inline WorldCam get_world_cam(Scene& s, int config_num, const RtxSceneOptions* o
 }
 
 // render_scene(world, cam, background, config) -- world.rs:1181-1247 -- on the current GPU.
-// Returns the Screen; the reference prints it (call write_to_ppm()).
+// Returns the Screen; the reference prints it (call write_to_ppm()).  integrator != NULL: rtx_render_ex with those options
+// (light_sampling = 1: next-event estimation with MIS), stats filled when given.
 inline Screen render_scene(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
-                           RtxRenderStats* stats = nullptr) {
+                           RtxRenderStats* stats = nullptr, const RtxIntegratorOptions* integrator = nullptr) {
   config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
   rtx_flat* flat = nullptr;
   check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
@@ -228,8 +229,7 @@ inline Screen render_scene(Scene& s, Hittable world, const Camera& cam, const Co
   scr.rgb8.resize((size_t)scr.width * scr.height * 3);
   scr.accum.resize((size_t)scr.width * scr.height * 3);
   RtxFrame frame = {scr.accum.data(), scr.rgb8.data()};
-  st = rtx_render(scene, &cam.c, &config.c, &frame);
-  (void)stats;
+  st = integrator ? rtx_render_ex(scene, &cam.c, &config.c, integrator, &frame, stats) : rtx_render(scene, &cam.c, &config.c, &frame);
   rtx_scene_destroy(scene);
   check(st);
   return scr;
@@ -255,11 +255,13 @@ inline rtx_status denoise_screen(rtx_progressive* prog, Screen& scr, DenoiseOutp
 // render_scene refined `batch` samples at a time (rtx_progressive_*): stops at the first batch boundary where no pixel's
 // relative error exceeds target_rel_err, or at config's samples_per_pixel.  snapshot(screen, spp), if given, is called
 // with the frame at every multiple of snapshot_every samples that falls on a batch boundary.  denoise != NULL: the frame
-// returned is the denoised one (denoise_screen).
+// returned is the denoised one (denoise_screen).  integrator: the handle's options (rtx_progressive_create_ex; NULL = the
+// reference's estimator).
 template <class Snapshot = void (*)(const Screen&, int)>
 inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
                                        int batch, double target_rel_err, RtxNoiseStats* stats_out = nullptr,
-                                       int snapshot_every = 0, Snapshot snapshot = nullptr, DenoiseOutputs* denoise = nullptr) {
+                                       int snapshot_every = 0, Snapshot snapshot = nullptr, DenoiseOutputs* denoise = nullptr,
+                                       const RtxIntegratorOptions* integrator = nullptr) {
   config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
   rtx_flat* flat = nullptr;
   check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
@@ -268,7 +270,7 @@ inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& c
   rtx_flat_destroy(flat);
   check(st);
   rtx_progressive* prog = nullptr;
-  st = rtx_progressive_create(scene, &cam.c, &config.c, nullptr, &prog);
+  st = rtx_progressive_create_ex(scene, &cam.c, &config.c, nullptr, integrator, &prog);
   Screen scr;
   scr.width = config.c.image_width;
   scr.height = rtx_image_height(&config.c);
@@ -303,10 +305,11 @@ inline Screen render_scene_progressive(Scene& s, Hittable world, const Camera& c
 
 // render_scene refined adaptively (rtx_progressive_until_adaptive): rounds of `batch` samples in which the pixels whose relative
 // error is at most target_rel_err (checked from min_spp samples on) stop receiving samples.  The Screen's spp holds each
-// pixel's count.  denoise != NULL: the frame returned is the denoised one (denoise_screen).
+// pixel's count.  denoise != NULL: the frame returned is the denoised one (denoise_screen).  integrator: as
+// render_scene_progressive.
 inline Screen render_scene_adaptive(Scene& s, Hittable world, const Camera& cam, const Color& background, Config config,
                                     int batch, int min_spp, double target_rel_err, RtxAdaptiveStats* stats_out = nullptr,
-                                    DenoiseOutputs* denoise = nullptr) {
+                                    DenoiseOutputs* denoise = nullptr, const RtxIntegratorOptions* integrator = nullptr) {
   config.c.background[0] = background.x; config.c.background[1] = background.y; config.c.background[2] = background.z;
   rtx_flat* flat = nullptr;
   check(rtx_flatten(s.builder(), world.h, nullptr, &flat));
@@ -315,7 +318,7 @@ inline Screen render_scene_adaptive(Scene& s, Hittable world, const Camera& cam,
   rtx_flat_destroy(flat);
   check(st);
   rtx_progressive* prog = nullptr;
-  st = rtx_progressive_create(scene, &cam.c, &config.c, nullptr, &prog);
+  st = rtx_progressive_create_ex(scene, &cam.c, &config.c, nullptr, integrator, &prog);
   Screen scr;
   scr.width = config.c.image_width;
   scr.height = rtx_image_height(&config.c);
