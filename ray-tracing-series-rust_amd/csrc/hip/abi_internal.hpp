@@ -12,9 +12,11 @@ struct rtx_builder {
 struct rtx_flat {
   rtx::FlatScene scene;
 };
+struct RtxSceneOps;  // f32_bridge.hpp
 struct rtx_scene {
   void* device_scene;  // rtx::DeviceScene of render.hip, or (f32 != 0) the device scene of its f32 compilation render_f32.hip
-  int32_t f32;
+  const RtxSceneOps* ops;  // what the compilation that owns device_scene does with it: every call on the scene goes through here
+  int32_t f32;  // what rtx_scene_is_f32 answers and the argument checks that reject a precision test; never chooses a callee
 };
 
 namespace rtx {
@@ -25,9 +27,10 @@ void set_error(const std::string& msg);
 
 inline const FlatScene* flat_of(const rtx_flat* f) { return &f->scene; }
 inline DeviceScene* scene_device(const rtx_scene* s) { return (DeviceScene*)s->device_scene; }
-inline rtx_scene* make_scene_handle(DeviceScene* ds, int32_t f32) {
+inline rtx_scene* make_scene_handle(void* ds, const RtxSceneOps* ops, int32_t f32) {
   rtx_scene* s = new rtx_scene;
   s->device_scene = ds;
+  s->ops = ops;
   s->f32 = f32;
   return s;
 }

@@ -3,9 +3,12 @@
 // render.hip is compiled twice: as itself (arithmetic type rt::real = double: the bit-exact path every parity test
 // checks) and through render_f32.hip (rt::real = float, namespaces renamed to rt32 / rtx32: the statistical fast mode of
 // SURVEY.md 8f-4).  The f64 compilation owns the C ABI and its handle types; it hands the f32 compilation byte images of
-// the flat arrays already converted to the f32 layouts (f32_convert.inc) and calls it through the functions below.
+// the flat arrays already converted to the f32 layouts (f32_convert.inc) and gets back a device scene with the table of
+// operations on it.  Each compilation fills one RtxSceneOps from the same lines of render.hip; a scene handle carries its
+// table, so the entry points call s->ops->X(s->device_scene, ...) and never ask which precision a scene has.
 // Nothing here mentions a type of either namespace, so both compilations see the same declarations.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
 #include "../../../include/rtx_abi.h"
@@ -23,22 +26,31 @@ struct RtxF32Blobs {
   uint32_t features;
 };
 
+// A range of the samples of a render (render.hip knows it as SampleRange and says what the fields mean).
+struct RtxSampleRange {
+  uint32_t first, count;
+  int cont;
+  double* sumsq;
+  const uint32_t* active;
+  uint32_t n_active;
+  bool light_sampling;
+};
+
+// What the entry points do with an uploaded scene, whichever compilation owns it.  Every call is asynchronous on stream.
+struct RtxSceneOps {
+  // render_impl<false>: the whole frame (range NULL: sums into d_accum_rgb, tone map into d_rgb8 unless NULL) or a sample range
+  rtx_status (*render)(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard, double* d_accum_rgb,
+                       uint8_t* d_rgb8, hipStream_t stream, RtxRenderStats* stats, const RtxSampleRange* range);
+  // tone map of an accumulator of spp samples per pixel, or (d_counts not NULL) of d_counts[lp] samples, spp where that is 0
+  rtx_status (*tonemap)(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix, uint32_t spp,
+                        hipStream_t stream);
+  // the feature pass (denoise.inc: k_features) of feature_spp first hits per pixel of the whole image
+  rtx_status (*features)(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp, float4* d_albedo,
+                         float4* d_normal, hipStream_t stream);
+  rtx_status (*trim)(void* device_scene);
+  void (*destroy)(void* device_scene);
+};
+
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);
-rtx_status rtx_f32_render(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
-                          double* d_accum_rgb, uint8_t* d_rgb8, void* hip_stream, RtxRenderStats* stats);
-// progressive.inc: trace the absolute samples [first, first + count) onto d_accum_rgb (continuing its sums when cont != 0;
-// d_sumsq_rgb, if not NULL, gets the sums of squares) -- of the n_active local pixels listed in d_active only, when that is
-// not NULL -- and tone-map an accumulator of spp samples, or of d_counts[lp] samples per pixel (spp where that is 0).
-rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
-                                double* d_accum_rgb, double* d_sumsq_rgb, uint32_t first, uint32_t count, int32_t cont,
-                                const uint32_t* d_active, uint32_t n_active, void* hip_stream, RtxRenderStats* stats);
-rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream);
-rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix,
-                                  uint32_t spp, void* hip_stream);
-// progressive.inc (denoising): the feature pass (denoise.inc: k_features) of feature_spp first hits per pixel of the whole
-// image into d_albedo4 / d_normal4, 4 floats per pixel each.
-rtx_status rtx_f32_features(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
-                            float* d_albedo4, float* d_normal4, void* hip_stream);
-rtx_status rtx_f32_trim(void* device_scene);
-void rtx_f32_destroy(void* device_scene);
+const RtxSceneOps* rtx_f32_scene_ops();  // the f32 compilation's table, for the scenes rtx_f32_upload makes
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error

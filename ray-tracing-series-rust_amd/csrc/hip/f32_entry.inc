@@ -35,28 +35,4 @@ rtx_status rtx_f32_upload(const RtxF32Blobs* b, void** device_scene) {
   return RTX_OK;
 }
 
-rtx_status rtx_f32_render(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
-                          double* d_accum_rgb, uint8_t* d_rgb8, void* hip_stream, RtxRenderStats* stats) {
-  return render_impl<false>((DeviceScene*)device_scene, cam, cfg, shard, d_accum_rgb, d_rgb8, (hipStream_t)hip_stream, stats);
-}
-rtx_status rtx_f32_render_range(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
-                                double* d_accum_rgb, double* d_sumsq_rgb, uint32_t first, uint32_t count, int32_t cont,
-                                const uint32_t* d_active, uint32_t n_active, void* hip_stream, RtxRenderStats* stats) {
-  const SampleRange range = {first, count, cont, d_sumsq_rgb, d_active, n_active};
-  return render_impl<false>((DeviceScene*)device_scene, cam, cfg, shard, d_accum_rgb, nullptr, (hipStream_t)hip_stream, stats,
-                            &range);
-}
-rtx_status rtx_f32_tonemap(const double* d_accum_rgb, uint8_t* d_rgb8, uint32_t npix, uint32_t spp, void* hip_stream) {
-  return tonemap_impl(d_accum_rgb, d_rgb8, npix, spp, (hipStream_t)hip_stream);
-}
-rtx_status rtx_f32_tonemap_counts(const double* d_accum_rgb, uint8_t* d_rgb8, const int32_t* d_counts, uint32_t npix,
-                                  uint32_t spp, void* hip_stream) {
-  return tonemap_counts_impl(d_accum_rgb, d_rgb8, d_counts, npix, spp, (hipStream_t)hip_stream);
-}
-rtx_status rtx_f32_features(void* device_scene, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
-                            float* d_albedo4, float* d_normal4, void* hip_stream) {
-  return features_impl((DeviceScene*)device_scene, cam, cfg, feature_spp, (float4*)d_albedo4, (float4*)d_normal4,
-                       (hipStream_t)hip_stream);
-}
-rtx_status rtx_f32_trim(void* device_scene) { return scene_trim_impl((DeviceScene*)device_scene); }
-void rtx_f32_destroy(void* device_scene) { free_device_scene((DeviceScene*)device_scene); }
+const RtxSceneOps* rtx_f32_scene_ops() { return &scene_ops; }

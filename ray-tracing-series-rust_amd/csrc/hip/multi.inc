@@ -69,9 +69,8 @@ struct MultiDevice {
   int device = 0;
   rtx_scene* scene = nullptr;
   hipStream_t stream = nullptr;
-  uint8_t* d_rgb8 = nullptr;     // this shard's tone-mapped rows (max_rows x w x 3)
-  double* d_accum = nullptr;     // this shard's accumulators, when the caller wants them
-  size_t cap_rgb8 = 0, cap_accum = 0;  // capacities (bytes) of the two buffers above
+  DeviceBuffer<uint8_t> d_rgb8;  // this shard's tone-mapped rows (max_rows x w x 3)
+  DeviceBuffer<double> d_accum;  // this shard's accumulators, when the caller wants them
   nccl_comm_t comm = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -83,9 +82,8 @@ struct rtx_multi {
   int n_shards = 1, block_rows = 1;
   bool same_device = false, use_rccl = false;
   int rccl_ranks = 0;                  // ncclCommCount of the communicator (0: no communicator, or the symbol is missing)
-  uint8_t *d_gather8 = nullptr, *d_image8 = nullptr;   // on dev[0]
-  double *d_gather64 = nullptr, *d_image64 = nullptr;  // on dev[0]
-  size_t cap_gather8 = 0, cap_gather64 = 0, cap_image8 = 0, cap_image64 = 0;
+  DeviceBuffer<uint8_t> d_gather8, d_image8;   // on dev[0]
+  DeviceBuffer<double> d_gather64, d_image64;  // on dev[0]
   hipEvent_t ev_gather0 = nullptr, ev_gather1 = nullptr;  // on dev[0]: around gather + un-tiling
 };
 
@@ -101,8 +99,8 @@ static void multi_free(rtx_multi* m) {
     (void)hipSetDevice(d.device);
     if (d.comm && api) (void)api->CommDestroy(d.comm);
     if (d.scene) rtx_scene_destroy(d.scene);
-    if (d.d_rgb8) (void)hipFree(d.d_rgb8);
-    if (d.d_accum) (void)hipFree(d.d_accum);
+    (void)d.d_rgb8.release();  // with its device current
+    (void)d.d_accum.release();
     if (d.ev0) (void)hipEventDestroy(d.ev0);
     if (d.ev1) (void)hipEventDestroy(d.ev1);
     if (d.stream) (void)hipStreamDestroy(d.stream);
@@ -110,20 +108,7 @@ static void multi_free(rtx_multi* m) {
   if (!m->dev.empty()) (void)hipSetDevice(m->dev[0].device);
   if (m->ev_gather0) (void)hipEventDestroy(m->ev_gather0);
   if (m->ev_gather1) (void)hipEventDestroy(m->ev_gather1);
-  if (m->d_gather8) (void)hipFree(m->d_gather8);
-  if (m->d_image8) (void)hipFree(m->d_image8);
-  if (m->d_gather64) (void)hipFree(m->d_gather64);
-  if (m->d_image64) (void)hipFree(m->d_image64);
-  delete m;
-}
-
-template <class T>
-static rtx_status grow(T** p, size_t* cap, size_t need) {
-  if (need <= *cap) return RTX_OK;
-  if (*p) { HIP_TRY(hipFree(*p)); *p = nullptr; *cap = 0; }
-  HIP_TRY(hipMalloc((void**)p, need));
-  *cap = need;
-  return RTX_OK;
+  delete m;  // the gather and image buffers, with dev[0] current
 }
 
 }  // namespace rtx
@@ -235,16 +220,16 @@ rtx_status rtx_multi_render(rtx_multi* m, const RtxCamera* cam, const RtxConfig*
   for (MultiDevice& d : m->dev) {
     HIP_TRY(hipSetDevice(d.device));
     const size_t per = m->same_device ? (size_t)n : 1;  // the rehearsal device holds every shard
-    if ((st = grow(&d.d_rgb8, &d.cap_rgb8, per * shard_px * 3)) != RTX_OK) return st;
-    if (want_accum && (st = grow(&d.d_accum, &d.cap_accum, per * shard_px * 24)) != RTX_OK) return st;
+    HIP_TRY(d.d_rgb8.grow(per * shard_px * 3, d.stream));
+    if (want_accum) HIP_TRY(d.d_accum.grow(per * shard_px * 24, d.stream));
   }
   MultiDevice& root = m->dev[0];
   HIP_TRY(hipSetDevice(root.device));
-  if ((st = grow(&m->d_gather8, &m->cap_gather8, (size_t)n * shard_px * 3)) != RTX_OK) return st;
-  if ((st = grow(&m->d_image8, &m->cap_image8, (size_t)w * h * 3)) != RTX_OK) return st;
+  HIP_TRY(m->d_gather8.grow((size_t)n * shard_px * 3, root.stream));
+  HIP_TRY(m->d_image8.grow((size_t)w * h * 3, root.stream));
   if (want_accum) {
-    if ((st = grow(&m->d_gather64, &m->cap_gather64, (size_t)n * shard_px * 24)) != RTX_OK) return st;
-    if ((st = grow(&m->d_image64, &m->cap_image64, (size_t)w * h * 24)) != RTX_OK) return st;
+    HIP_TRY(m->d_gather64.grow((size_t)n * shard_px * 24, root.stream));
+    HIP_TRY(m->d_image64.grow((size_t)w * h * 24, root.stream));
   }
 
   // ---- render: every device its shard, all at once (launches are asynchronous)
@@ -255,7 +240,7 @@ rtx_status rtx_multi_render(rtx_multi* m, const RtxCamera* cam, const RtxConfig*
     uint8_t* rgb = d.d_rgb8 + (m->same_device ? (size_t)r * shard_px * 3 : 0);
     double* acc = want_accum ? d.d_accum + (m->same_device ? (size_t)r * shard_px * 3 : 0) : nullptr;
     if (r == 0 || !m->same_device) HIP_TRY(hipEventRecord(d.ev0, d.stream));
-    st = render_any<false>(d.scene, cam, cfg, &sh, acc, rgb, d.stream, nullptr);
+    st = render_any(d.scene, cam, cfg, &sh, acc, rgb, d.stream, nullptr);
     if (st != RTX_OK) return st;
     if (r == n - 1 || !m->same_device) HIP_TRY(hipEventRecord(d.ev1, d.stream));
   }

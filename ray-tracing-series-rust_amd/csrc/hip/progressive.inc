@@ -18,27 +18,15 @@
 // The filter's device buffers for one image (denoise_launch): two (c, sigma2) planes to ping-pong between, n^, and the
 // finished mean and rgb8.
 struct DenoiseBuffers {
-  size_t npix = 0;
-  float4* cv[2] = {nullptr, nullptr};
-  float4* nhat = nullptr;
-  double* mean = nullptr;
-  uint8_t* rgb8 = nullptr;
-  ~DenoiseBuffers() {
-    for (float4* c : cv)
-      if (c) (void)hipFree(c);
-    if (nhat) (void)hipFree(nhat);
-    if (mean) (void)hipFree(mean);
-    if (rgb8) (void)hipFree(rgb8);
-  }
-  hipError_t alloc(size_t n) {
-    npix = n;
-    hipError_t e = hipMalloc((void**)&cv[0], n * 16 + 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&cv[1], n * 16 + 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&nhat, n * 16 + 16);
-    if (e == hipSuccess) e = hipMalloc((void**)&mean, n * 24 + 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&rgb8, n * 3 + 8);
-    return e;
-  }
+  DeviceBuffer<float4> cv[2], nhat;
+  DeviceBuffer<double> mean;
+  DeviceBuffer<uint8_t> rgb8;
+};
+
+// The retirement check's compaction scratch (retire_scratch_alloc): one ballot per wave, the block counts, their offsets and total.
+struct RetireScratch {
+  DeviceBuffer<unsigned long long> keep_mask;
+  DeviceBuffer<uint32_t> block_count, block_offset;
 };
 
 struct rtx_progressive {
@@ -52,62 +40,56 @@ struct rtx_progressive {
   int32_t spp_done;
   bool light_sampling;  // every add traces with next-event estimation (rtx_progressive_create_ex)
   bool broken;        // a failed add left S / Q partly updated
-  double* S;
-  double* Q;
-  NoisePartial* partials;  // one per 256 active pixels, then the final result (noise_partials_alloc)
+  DeviceBuffer<double> S, Q;
+  DeviceBuffer<NoisePartial> partials;  // one per 256 active pixels, then the final result (noise_partials_alloc)
   // adaptive state, allocated by the first adaptive call (a uniform handle keeps its 48 bytes per pixel)
   bool adaptive;
   int cur;                  // active[cur]: the ascending list of the n_active local pixels still active
-  uint32_t* active[2];      // (the other one: the compaction's target)
+  DeviceBuffer<uint32_t> active[2];  // (the other one: the compaction's target)
   uint32_t n_active;        // npix until the first pixel retires
-  int32_t* counts;          // per pixel of the shard: n_p of a retired pixel, 0 for an active one (or a row never rendered)
-  unsigned long long* keep_mask;  // compaction scratch: one ballot per wave, the block counts, their offsets and total
-  uint32_t* block_count;
-  uint32_t* block_offset;
+  DeviceBuffer<int32_t> counts;  // per pixel of the shard: n_p of a retired pixel, 0 for an active one (or a row never rendered)
+  RetireScratch scratch;
   uint64_t retired_samples;  // sum of n_p over the retired pixels
   // denoising state, allocated by the first features / denoise call (denoise.inc)
   int32_t feature_spp;       // of the features held (0: none yet)
-  float4* albedo;            // per pixel: the feature pass's albedo, normal
-  float4* normal;
-  DenoiseBuffers* denoise;   // the filter's buffers
+  DeviceBuffer<float4> albedo, normal;  // per pixel: the feature pass's albedo, normal
+  DenoiseBuffers denoise;    // the filter's buffers, allocated by the first denoise call
 };
 
 namespace {
 
-void progressive_free(rtx_progressive* p) {
-  if (p->S) (void)hipFree(p->S);
-  if (p->Q) (void)hipFree(p->Q);
-  if (p->partials) (void)hipFree(p->partials);
-  for (uint32_t* a : p->active)
-    if (a) (void)hipFree(a);
-  if (p->counts) (void)hipFree(p->counts);
-  if (p->keep_mask) (void)hipFree(p->keep_mask);
-  if (p->block_count) (void)hipFree(p->block_count);
-  if (p->block_offset) (void)hipFree(p->block_offset);
-  if (p->albedo) (void)hipFree(p->albedo);
-  if (p->normal) (void)hipFree(p->normal);
-  delete p->denoise;
-  delete p;
-}
+bool any_retired(const rtx_progressive* p) { return p->adaptive && p->n_active < p->npix; }
 
-rtx_status progressive_add(rtx_progressive* p, int32_t n_samples, hipStream_t stream, RtxRenderStats* stats) {
-  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n_samples, p->spp_done > 0 ? 1 : 0, p->Q, nullptr, 0u, p->light_sampling};
-  rtx_status st;
-  if (p->scene->f32)
-    st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
-                              range.cont, nullptr, 0u, (void*)stream, stats);
-  else
-    st = render_impl<false>(scene_device(p->scene), &p->cam, &p->cfg, &p->shard, p->S, nullptr, stream, stats, &range);
+// Traces the samples [spp_done, spp_done + n) onto S and Q: of every pixel, or -- once pixels have retired (adaptive rounds) --
+// of the listed pixels still active; with none active it traces nothing (spp_done still advances).  A failed trace leaves S
+// and Q partly updated: the handle is broken.
+rtx_status progressive_add(rtx_progressive* p, int32_t n, hipStream_t stream, RtxRenderStats* stats) {
+  const bool listed = any_retired(p);
+  if (listed && p->n_active == 0) {
+    if (stats) { memset(stats, 0, sizeof(*stats)); stats->trace_kernel = RTX_KERNEL_SIMPLE; }  // nothing traced
+    p->spp_done += n;
+    return RTX_OK;
+  }
+  // (a pixel retires at spp_done >= 2 at the earliest: a listed range always continues)
+  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n, p->spp_done > 0 ? 1 : 0, p->Q,
+                             listed ? (const uint32_t*)p->active[p->cur] : nullptr, listed ? p->n_active : 0u, p->light_sampling};
+  const rtx_status st = p->scene->ops->render(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, nullptr, stream, stats, &range);
   if (st != RTX_OK) { p->broken = true; return st; }
-  p->spp_done += n_samples;
+  p->spp_done += n;
   return RTX_OK;
 }
 
-bool any_retired(const rtx_progressive* p) { return p->adaptive && p->n_active < p->npix; }
+// The entries' check of a number of samples to add.
+bool n_samples_ok(const rtx_progressive* p, const char* fn, int32_t n_samples) {
+  if (n_samples > 0 && n_samples <= p->cfg.samples_per_pixel - p->spp_done) return true;
+  set_error(std::string(fn) + ": n_samples must be in [1, samples_per_pixel - spp_done] = [1, " +
+            std::to_string(p->cfg.samples_per_pixel - p->spp_done) + "]");
+  return false;
+}
 
 // The noise reduction's partials for npix pixels: one per 256-pixel block, then the final result.
-hipError_t noise_partials_alloc(uint32_t npix, NoisePartial** partials) {
-  return hipMalloc((void**)partials, (((size_t)npix + 255) / 256 + 1) * sizeof(NoisePartial));
+hipError_t noise_partials_alloc(uint32_t npix, DeviceBuffer<NoisePartial>* partials) {
+  return partials->alloc((((size_t)npix + 255) / 256 + 1) * sizeof(NoisePartial));
 }
 
 // The noise reduction on device arrays, shared by the handle and rtx_device_noise_reduce: k_noise_stats (counts NULL) or
@@ -135,12 +117,9 @@ rtx_status noise_reduce(rtx_progressive* p, double target, NoisePartial* r) {
                              p->partials, r);
 }
 
-rtx_status progressive_stats(rtx_progressive* p, double target, RtxNoiseStats* out) {
-  memset(out, 0, sizeof(*out));
-  out->spp_done = p->spp_done;
-  out->pixels = (int32_t)p->npix;
-  out->target_rel_err = target;
-  if (p->npix == 0) return RTX_OK;
+// The error fields of a stats struct (RtxNoiseStats, RtxAdaptiveStats) from the reduction over the handle's npix >= 1 pixels.
+template <class Stats>
+rtx_status error_stats(rtx_progressive* p, double target, Stats* out) {
   NoisePartial r;
   const rtx_status st = noise_reduce(p, target, &r);
   if (st != RTX_OK) return st;
@@ -148,6 +127,19 @@ rtx_status progressive_stats(rtx_progressive* p, double target, RtxNoiseStats* o
   out->max_rel_err = r.max_r;
   out->mean_rel_err = r.sum_r / (double)p->npix;
   return RTX_OK;
+}
+
+// A RtxNoiseStats without its error fields.
+void noise_stats_head(const rtx_progressive* p, double target, RtxNoiseStats* out) {
+  memset(out, 0, sizeof(*out));
+  out->spp_done = p->spp_done;
+  out->pixels = (int32_t)p->npix;
+  out->target_rel_err = target;
+}
+
+rtx_status progressive_stats(rtx_progressive* p, double target, RtxNoiseStats* out) {
+  noise_stats_head(p, target, out);
+  return p->npix == 0 ? RTX_OK : error_stats(p, target, out);
 }
 
 bool progressive_usable(const rtx_progressive* p, const char* fn) {
@@ -175,11 +167,11 @@ bool adaptive_args_ok(const rtx_progressive* p, const char* fn, int32_t min_spp,
 
 // The retirement check's scratch for lists of up to n pixels (nb = ceil(n / 256) blocks): one ballot per wave (nb * 4, and
 // one spare), the block counts (nb + 1) and their exclusive offsets with the total at [nb] (nb + 1).
-hipError_t retire_scratch_alloc(uint32_t n, unsigned long long** keep_mask, uint32_t** block_count, uint32_t** block_offset) {
+hipError_t retire_scratch_alloc(uint32_t n, RetireScratch* s) {
   const uint32_t nb = (n + 255u) / 256u;
-  hipError_t e = hipMalloc((void**)keep_mask, ((size_t)nb * 4 + 1) * 8);
-  if (e == hipSuccess) e = hipMalloc((void**)block_count, ((size_t)nb + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)block_offset, ((size_t)nb + 1) * 4);
+  hipError_t e = s->keep_mask.alloc(((size_t)nb * 4 + 1) * 8);
+  if (e == hipSuccess) e = s->block_count.alloc(((size_t)nb + 1) * 4);
+  if (e == hipSuccess) e = s->block_offset.alloc(((size_t)nb + 1) * 4);
   return e;
 }
 
@@ -187,35 +179,38 @@ hipError_t retire_scratch_alloc(uint32_t n, unsigned long long** keep_mask, uint
 // with r <= target at spp samples gets counts[lp] = spp; the others are compacted, in order, into next[0, *kept).  The
 // scratch comes from retire_scratch_alloc for at least n pixels.  Blocking (the host needs the count).
 rtx_status retire_launch(const double* S, const double* Q, const uint32_t* list, uint32_t n, uint32_t spp, double target,
-                         int32_t* counts, unsigned long long* keep_mask, uint32_t* block_count, uint32_t* block_offset,
-                         uint32_t* next, hipStream_t stream, uint32_t* kept) {
+                         int32_t* counts, const RetireScratch& sc, uint32_t* next, hipStream_t stream, uint32_t* kept) {
   const uint32_t nb = (n + 255u) / 256u;
-  hipLaunchKernelGGL(k_retire_flag, dim3(nb), dim3(256), 0, stream, S, Q, list, n, spp, target, counts, keep_mask,
-                     block_count);
+  hipLaunchKernelGGL(k_retire_flag, dim3(nb), dim3(256), 0, stream, S, Q, list, n, spp, target, counts, sc.keep_mask,
+                     sc.block_count);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(256), 0, stream, block_count, nb, block_offset);
+  hipLaunchKernelGGL(k_retire_scan, dim3(1), dim3(256), 0, stream, sc.block_count, nb, sc.block_offset);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_retire_scatter, dim3(nb), dim3(256), 0, stream, list, n, keep_mask, block_offset, next);
+  hipLaunchKernelGGL(k_retire_scatter, dim3(nb), dim3(256), 0, stream, list, n, sc.keep_mask, sc.block_offset, next);
   HIP_TRY(hipGetLastError());
   *kept = 0;
-  HIP_TRY(hipMemcpyAsync(kept, block_offset + nb, sizeof(*kept), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipMemcpyAsync(kept, sc.block_offset + nb, sizeof(*kept), hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipStreamSynchronize(stream));
   if (*kept > n) { set_error("progressive: the retirement check counted more pixels than it was given"); return RTX_EHIP; }
   return RTX_OK;
 }
 
-// Allocates the adaptive buffers on the first adaptive call: every active pixel listed, no count frozen.
+// Allocates the adaptive buffers on the first adaptive call: every active pixel listed, no count frozen.  The buffers are
+// built in locals and move into the handle together with `adaptive`: a failure frees them all and leaves the handle as it was.
 rtx_status adaptive_init(rtx_progressive* p) {
   if (p->adaptive) return RTX_OK;
   const uint32_t nb = (p->npix + 255u) / 256u;
+  DeviceBuffer<uint32_t> active[2];
+  DeviceBuffer<int32_t> counts;
+  RetireScratch scratch;
   hipError_t e = hipSuccess;
-  for (uint32_t*& a : p->active)
-    if (e == hipSuccess) e = hipMalloc((void**)&a, ((size_t)p->npix + 1) * 4);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->counts, ((size_t)p->npix_all + 1) * 4);
-  if (e == hipSuccess) e = retire_scratch_alloc(p->npix, &p->keep_mask, &p->block_count, &p->block_offset);
-  if (e == hipSuccess) e = hipMemset(p->counts, 0, ((size_t)p->npix_all + 1) * 4);
+  for (DeviceBuffer<uint32_t>& a : active)
+    if (e == hipSuccess) e = a.alloc(((size_t)p->npix + 1) * 4);
+  if (e == hipSuccess) e = counts.alloc(((size_t)p->npix_all + 1) * 4);
+  if (e == hipSuccess) e = retire_scratch_alloc(p->npix, &scratch);
+  if (e == hipSuccess) e = hipMemset(counts, 0, ((size_t)p->npix_all + 1) * 4);
   if (e == hipSuccess && p->npix) {
-    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, p->active[0], p->npix);
+    hipLaunchKernelGGL(k_iota, dim3(nb), dim3(256), 0, (hipStream_t) nullptr, active[0], p->npix);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -224,6 +219,10 @@ rtx_status adaptive_init(rtx_progressive* p) {
     set_error(std::string("progressive: adaptive buffers: ") + hipGetErrorString(e));
     return e == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
   }
+  p->active[0] = std::move(active[0]);
+  p->active[1] = std::move(active[1]);
+  p->counts = std::move(counts);
+  p->scratch = std::move(scratch);
   p->adaptive = true;
   p->cur = 0;
   p->n_active = p->npix;
@@ -237,8 +236,8 @@ rtx_status adaptive_retire_launch(rtx_progressive* p, double target, hipStream_t
   if (p->n_active == 0) return RTX_OK;
   const uint32_t n = p->n_active, spp = (uint32_t)p->spp_done;
   uint32_t kept = 0;
-  const rtx_status st = retire_launch(p->S, p->Q, p->active[p->cur], n, spp, target, p->counts, p->keep_mask, p->block_count,
-                                      p->block_offset, p->active[1 - p->cur], stream, &kept);
+  const rtx_status st = retire_launch(p->S, p->Q, p->active[p->cur], n, spp, target, p->counts, p->scratch,
+                                      p->active[1 - p->cur], stream, &kept);
   if (st != RTX_OK) return st;
   p->retired_samples += (uint64_t)(n - kept) * spp;
   p->n_active = kept;
@@ -250,27 +249,6 @@ rtx_status adaptive_retire(rtx_progressive* p, double target, hipStream_t stream
   const rtx_status st = adaptive_retire_launch(p, target, stream);
   if (st != RTX_OK) p->broken = true;  // counts may be frozen for a list that was not compacted
   return st;
-}
-
-// The tracing half of an adaptive round: samples [spp_done, spp_done + n) of the pixels still active.  With none retired yet
-// that is a uniform add; with none active it traces nothing (spp_done still advances).
-rtx_status adaptive_trace(rtx_progressive* p, int32_t n, hipStream_t stream, RtxRenderStats* stats) {
-  if (p->n_active == p->npix) return progressive_add(p, n, stream, stats);
-  if (p->n_active == 0) {
-    if (stats) { memset(stats, 0, sizeof(*stats)); stats->trace_kernel = RTX_KERNEL_SIMPLE; }  // nothing traced
-    p->spp_done += n;
-    return RTX_OK;
-  }
-  const SampleRange range = {(uint32_t)p->spp_done, (uint32_t)n, 1, p->Q, p->active[p->cur], p->n_active, p->light_sampling};
-  rtx_status st;
-  if (p->scene->f32)
-    st = rtx_f32_render_range(p->scene->device_scene, &p->cam, &p->cfg, &p->shard, p->S, p->Q, range.first, range.count,
-                              range.cont, range.active, range.n_active, (void*)stream, stats);
-  else
-    st = render_impl<false>(scene_device(p->scene), &p->cam, &p->cfg, &p->shard, p->S, nullptr, stream, stats, &range);
-  if (st != RTX_OK) { p->broken = true; return st; }
-  p->spp_done += n;
-  return RTX_OK;
 }
 
 // A retirement check is due at spp_done >= max(2, min_spp); min_spp >= 2 is checked by every entry.
@@ -286,35 +264,11 @@ rtx_status adaptive_stats(rtx_progressive* p, int32_t min_spp, double target, Rt
                              : (uint64_t)p->npix * (uint64_t)p->spp_done;
   out->target_rel_err = target;
   if (p->npix == 0 || p->spp_done < 2) return RTX_OK;
-  NoisePartial r;
-  const rtx_status st = noise_reduce(p, target, &r);
-  if (st != RTX_OK) return st;
-  out->pixels_above = (int32_t)r.above;
-  out->max_rel_err = r.max_r;
-  out->mean_rel_err = r.sum_r / (double)p->npix;
-  return RTX_OK;
+  return error_stats(p, target, out);
 }
 
-// Device copies of a self-test entry's arrays, freed together.
-struct SelfTestBuffers {
-  std::vector<void*> ptrs;
-  ~SelfTestBuffers() {
-    for (void* d : ptrs) (void)hipFree(d);
-  }
-  template <class T>
-  hipError_t alloc(T** d, size_t count) {
-    *d = nullptr;
-    const hipError_t e = hipMalloc((void**)d, count * sizeof(T) + 8);  // never 0 bytes
-    if (e == hipSuccess) ptrs.push_back((void*)*d);
-    return e;
-  }
-  template <class T>
-  hipError_t upload(T** d, const T* h, size_t count) {
-    hipError_t e = alloc(d, count);
-    if (e == hipSuccess && count) e = hipMemcpy(*d, h, count * sizeof(T), hipMemcpyHostToDevice);
-    return e;
-  }
-};
+// Spare bytes behind every device copy of a self-test entry's array: never 0 bytes.
+const size_t SELF_TEST_SPARE = 8;
 
 // The self-test entries' argument checks (before any device call).
 bool self_test_args_ok(const char* fn, bool pointers, uint32_t npix, uint32_t spp, double target) {
@@ -357,7 +311,7 @@ bool denoise_rule(const RtxDenoiseParams* params, const char* fn, DenoiseRule* r
 // Blocking.
 rtx_status denoise_launch(int32_t w, int32_t h, const DenoiseRule& r, const double* s_or_m, const double* q_or_v,
                           const int32_t* counts, uint32_t spp, int moments, const float4* albedo, const float4* normal,
-                          DenoiseBuffers& b, bool want_mean, bool want_rgb8) {
+                          const DenoiseBuffers& b, bool want_mean, bool want_rgb8) {
   const uint32_t npix = (uint32_t)((size_t)w * (size_t)h);
   if (npix == 0) return RTX_OK;
   hipLaunchKernelGGL(k_denoise_prepare, dim3((npix + 255) / 256), dim3(256), 0, (hipStream_t) nullptr, s_or_m, q_or_v, counts,
@@ -372,11 +326,21 @@ rtx_status denoise_launch(int32_t w, int32_t h, const DenoiseRule& r, const doub
                          b.cv[(k + 1) & 1], nullptr, nullptr);
     else
       hipLaunchKernelGGL(k_denoise_level<true>, grid, block, 0, (hipStream_t) nullptr, in, albedo, b.nhat, w, h, 1 << k, nbx, r,
-                         nullptr, want_mean ? b.mean : nullptr, want_rgb8 ? b.rgb8 : nullptr);
+                         nullptr, want_mean ? (double*)b.mean : nullptr, want_rgb8 ? (uint8_t*)b.rgb8 : nullptr);
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(hipDeviceSynchronize());
   return RTX_OK;
+}
+
+// The filter's buffers for an image of n pixels.
+hipError_t denoise_buffers_alloc(size_t n, DenoiseBuffers* b) {
+  hipError_t e = b->cv[0].alloc(n * 16 + 16);
+  if (e == hipSuccess) e = b->cv[1].alloc(n * 16 + 16);
+  if (e == hipSuccess) e = b->nhat.alloc(n * 16 + 16);
+  if (e == hipSuccess) e = b->mean.alloc(n * 24 + 8);
+  if (e == hipSuccess) e = b->rgb8.alloc(n * 3 + 8);
+  return e;
 }
 
 // Denoising needs every row of the image: a whole-image handle without row_chunk_compat.
@@ -391,14 +355,11 @@ rtx_status ensure_features(rtx_progressive* p, int32_t feature_spp) {
   if (p->feature_spp == feature_spp) return RTX_OK;
   HIP_TRY(hipDeviceSynchronize());  // adds may still run on the caller's stream (the feature pass shares nothing with them)
   const size_t bytes = (size_t)p->npix_all * 16 + 16;
-  if (!p->albedo) HIP_TRY(hipMalloc((void**)&p->albedo, bytes));
-  if (!p->normal) HIP_TRY(hipMalloc((void**)&p->normal, bytes));
+  if (!p->albedo) HIP_TRY(p->albedo.alloc(bytes));
+  if (!p->normal) HIP_TRY(p->normal.alloc(bytes));
   p->feature_spp = 0;
-  rtx_status st;
-  if (p->scene->f32)
-    st = rtx_f32_features(p->scene->device_scene, &p->cam, &p->cfg, feature_spp, (float*)p->albedo, (float*)p->normal, nullptr);
-  else
-    st = features_impl(scene_device(p->scene), &p->cam, &p->cfg, feature_spp, p->albedo, p->normal, (hipStream_t) nullptr);
+  const rtx_status st = p->scene->ops->features(p->scene->device_scene, &p->cam, &p->cfg, feature_spp, p->albedo, p->normal,
+                                                 (hipStream_t) nullptr);
   if (st != RTX_OK) return st;
   HIP_TRY(hipDeviceSynchronize());
   p->feature_spp = feature_spp;
@@ -449,15 +410,15 @@ rtx_status rtx_progressive_create(const rtx_scene* s, const RtxCamera* cam, cons
   p->npix = (uint32_t)npix;
   hipError_t e = hipGetDevice(&p->device);
   const size_t plane = (size_t)npix_all * 24;
-  if (e == hipSuccess && plane) e = hipMalloc((void**)&p->S, plane);
-  if (e == hipSuccess && plane) e = hipMalloc((void**)&p->Q, plane);
+  if (e == hipSuccess && plane) e = p->S.alloc(plane);
+  if (e == hipSuccess && plane) e = p->Q.alloc(plane);
   if (e == hipSuccess) e = noise_partials_alloc(p->npix, &p->partials);
   if (e == hipSuccess && plane) e = hipMemset(p->S, 0, plane);  // rows beyond row_chunk_compat's limit stay zero
   if (e == hipSuccess && plane) e = hipMemset(p->Q, 0, plane);
   if (e != hipSuccess) {
     (void)hipGetLastError();
     set_error(std::string("rtx_progressive_create: ") + hipGetErrorString(e));
-    progressive_free(p);
+    delete p;
     return e == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
   }
   *out = p;
@@ -467,18 +428,14 @@ rtx_status rtx_progressive_create(const rtx_scene* s, const RtxCamera* cam, cons
 void rtx_progressive_destroy(rtx_progressive* p) {
   if (!p) return;
   (void)hipDeviceSynchronize();  // an add may still be running on the caller's stream
-  progressive_free(p);
+  delete p;
 }
 
 int32_t rtx_progressive_spp(const rtx_progressive* p) { return p ? p->spp_done : -1; }
 
 rtx_status rtx_progressive_add(rtx_progressive* p, int32_t n_samples, void* hip_stream, RtxRenderStats* stats) {
   if (!progressive_usable(p, "rtx_progressive_add") || !uniform_allowed(p, "rtx_progressive_add")) return RTX_EINVAL;
-  if (n_samples <= 0 || n_samples > p->cfg.samples_per_pixel - p->spp_done) {
-    set_error("rtx_progressive_add: n_samples must be in [1, samples_per_pixel - spp_done] = [1, " +
-              std::to_string(p->cfg.samples_per_pixel - p->spp_done) + "]");
-    return RTX_EINVAL;
-  }
+  if (!n_samples_ok(p, "rtx_progressive_add", n_samples)) return RTX_EINVAL;
   return progressive_add(p, n_samples, (hipStream_t)hip_stream, stats);
 }
 
@@ -491,22 +448,14 @@ rtx_status rtx_progressive_read(const rtx_progressive* p, RtxFrame* out, double*
   if (out->accum_rgb && plane) HIP_TRY(hipMemcpy(out->accum_rgb, p->S, plane, hipMemcpyDeviceToHost));
   if (sumsq_rgb && plane) HIP_TRY(hipMemcpy(sumsq_rgb, p->Q, plane, hipMemcpyDeviceToHost));
   if (out->rgb8 && plane) {
-    uint8_t* d_rgb = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_rgb, (size_t)p->npix_all * 3));
-    rtx_status st = RTX_OK;
-    hipError_t e = hipMemset(d_rgb, 0, (size_t)p->npix_all * 3);
-    if (e == hipSuccess) {
-      if (any_retired(p))  // each pixel by its own count
-        st = p->scene->f32 ? rtx_f32_tonemap_counts(p->S, d_rgb, p->counts, p->npix, (uint32_t)p->spp_done, nullptr)
-                           : tonemap_counts_impl(p->S, d_rgb, p->counts, p->npix, (uint32_t)p->spp_done, (hipStream_t) nullptr);
-      else
-        st = p->scene->f32 ? rtx_f32_tonemap(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, nullptr)
-                           : tonemap_impl(p->S, d_rgb, p->npix, (uint32_t)p->spp_done, (hipStream_t) nullptr);
-      if (st == RTX_OK) e = hipMemcpy(out->rgb8, d_rgb, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost);
-    }
-    (void)hipFree(d_rgb);
+    DeviceBuffer<uint8_t> d_rgb;
+    HIP_TRY(d_rgb.alloc((size_t)p->npix_all * 3));
+    HIP_TRY(hipMemset(d_rgb, 0, (size_t)p->npix_all * 3));
+    // once pixels have retired, each pixel by its own count
+    const rtx_status st = p->scene->ops->tonemap(p->S, d_rgb, any_retired(p) ? (const int32_t*)p->counts : nullptr, p->npix,
+                                                 (uint32_t)p->spp_done, (hipStream_t) nullptr);
     if (st != RTX_OK) return st;
-    if (e != hipSuccess) { set_error(std::string("rtx_progressive_read: ") + hipGetErrorString(e)); return RTX_EHIP; }
+    HIP_TRY(hipMemcpy(out->rgb8, d_rgb, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost));
   }
   return RTX_OK;
 }
@@ -524,10 +473,7 @@ rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double targe
   if (!out) { set_error("rtx_progressive_until: NULL out"); return RTX_EINVAL; }
   if (batch <= 0) { set_error("rtx_progressive_until: batch must be > 0"); return RTX_EINVAL; }
   if (!(target_rel_err >= 0.0)) { set_error("rtx_progressive_until: target_rel_err must be >= 0"); return RTX_EINVAL; }
-  memset(out, 0, sizeof(*out));
-  out->spp_done = p->spp_done;
-  out->pixels = (int32_t)p->npix;
-  out->target_rel_err = target_rel_err;
+  noise_stats_head(p, target_rel_err, out);
   out->pixels_above = (int32_t)p->npix;
   const int32_t budget = p->cfg.samples_per_pixel;
   if (p->spp_done >= 2) {
@@ -549,16 +495,12 @@ rtx_status rtx_progressive_until(rtx_progressive* p, int32_t batch, double targe
 rtx_status rtx_progressive_add_adaptive(rtx_progressive* p, int32_t n_samples, int32_t min_spp, double target_rel_err,
                                         void* hip_stream, RtxRenderStats* stats) {
   if (!progressive_usable(p, "rtx_progressive_add_adaptive")) return RTX_EINVAL;
-  if (n_samples <= 0 || n_samples > p->cfg.samples_per_pixel - p->spp_done) {
-    set_error("rtx_progressive_add_adaptive: n_samples must be in [1, samples_per_pixel - spp_done] = [1, " +
-              std::to_string(p->cfg.samples_per_pixel - p->spp_done) + "]");
-    return RTX_EINVAL;
-  }
+  if (!n_samples_ok(p, "rtx_progressive_add_adaptive", n_samples)) return RTX_EINVAL;
   if (!adaptive_args_ok(p, "rtx_progressive_add_adaptive", min_spp, target_rel_err)) return RTX_EINVAL;
   rtx_status st = adaptive_init(p);
   if (st == RTX_OK && check_due(p, min_spp)) st = adaptive_retire(p, target_rel_err, (hipStream_t)hip_stream);
   if (st != RTX_OK) return st;
-  return adaptive_trace(p, n_samples, (hipStream_t)hip_stream, stats);
+  return progressive_add(p, n_samples, (hipStream_t)hip_stream, stats);
 }
 
 rtx_status rtx_progressive_until_adaptive(rtx_progressive* p, int32_t batch, int32_t min_spp, double target_rel_err,
@@ -578,7 +520,7 @@ rtx_status rtx_progressive_until_adaptive(rtx_progressive* p, int32_t batch, int
     }
     if (p->n_active == 0 || p->spp_done >= budget) break;
     const int32_t n = budget - p->spp_done < batch ? budget - p->spp_done : batch;
-    st = adaptive_trace(p, n, (hipStream_t) nullptr, nullptr);
+    st = progressive_add(p, n, (hipStream_t) nullptr, nullptr);
     if (st != RTX_OK) return st;
   }
   return adaptive_stats(p, min_spp, target_rel_err, out);
@@ -609,25 +551,19 @@ rtx_status rtx_device_retire(const double* S, const double* Q, uint32_t npix, co
       set_error(std::string(fn) + ": active must ascend strictly and stay below npix");
       return RTX_EINVAL;
     }
-  SelfTestBuffers b;
-  double *dS, *dQ;
-  uint32_t *d_active, *d_next, *block_count = nullptr, *block_offset = nullptr;
-  int32_t* d_counts;
-  unsigned long long* keep_mask = nullptr;
+  DeviceBuffer<double> dS, dQ;
+  DeviceBuffer<uint32_t> d_active, d_next;
+  DeviceBuffer<int32_t> d_counts;
+  RetireScratch scratch;
   const size_t plane = (size_t)npix * 3;
-  hipError_t e = b.upload(&dS, S, plane);
-  if (e == hipSuccess) e = b.upload(&dQ, Q, plane);
-  if (e == hipSuccess) e = b.upload(&d_active, active, n);
-  if (e == hipSuccess) e = b.upload(&d_counts, counts, npix);
-  if (e == hipSuccess) e = b.alloc(&d_next, n);
-  if (e == hipSuccess) {
-    e = retire_scratch_alloc(n, &keep_mask, &block_count, &block_offset);
-    b.ptrs.insert(b.ptrs.end(), {(void*)keep_mask, (void*)block_count, (void*)block_offset});  // (hipFree(NULL) is a no-op)
-  }
-  if (e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  HIP_TRY(dS.upload(S, plane, SELF_TEST_SPARE));
+  HIP_TRY(dQ.upload(Q, plane, SELF_TEST_SPARE));
+  HIP_TRY(d_active.upload(active, n, SELF_TEST_SPARE));
+  HIP_TRY(d_counts.upload(counts, npix, SELF_TEST_SPARE));
+  HIP_TRY(d_next.alloc((size_t)n * 4 + SELF_TEST_SPARE));
+  HIP_TRY(retire_scratch_alloc(n, &scratch));
   uint32_t got = 0;
-  const rtx_status st = retire_launch(dS, dQ, d_active, n, spp, target, d_counts, keep_mask, block_count, block_offset,
-                                      d_next, (hipStream_t) nullptr, &got);
+  const rtx_status st = retire_launch(dS, dQ, d_active, n, spp, target, d_counts, scratch, d_next, (hipStream_t) nullptr, &got);
   if (st != RTX_OK) return st;
   if (got) HIP_TRY(hipMemcpy(next, d_next, (size_t)got * 4, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(counts, d_counts, (size_t)npix * 4, hipMemcpyDeviceToHost));
@@ -643,19 +579,14 @@ rtx_status rtx_device_noise_reduce(const double* S, const double* Q, const int32
   *sum_r = 0.0;
   *above = 0;
   if (npix == 0) return RTX_OK;
-  SelfTestBuffers b;
-  double *dS, *dQ;
-  int32_t* d_counts = nullptr;
-  NoisePartial* partials = nullptr;
+  DeviceBuffer<double> dS, dQ;
+  DeviceBuffer<int32_t> d_counts;
+  DeviceBuffer<NoisePartial> partials;
   const size_t plane = (size_t)npix * 3;
-  hipError_t e = b.upload(&dS, S, plane);
-  if (e == hipSuccess) e = b.upload(&dQ, Q, plane);
-  if (e == hipSuccess && counts) e = b.upload(&d_counts, counts, npix);
-  if (e == hipSuccess) {
-    e = noise_partials_alloc(npix, &partials);
-    b.ptrs.push_back((void*)partials);
-  }
-  if (e != hipSuccess) { set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  HIP_TRY(dS.upload(S, plane, SELF_TEST_SPARE));
+  HIP_TRY(dQ.upload(Q, plane, SELF_TEST_SPARE));
+  if (counts) HIP_TRY(d_counts.upload(counts, npix, SELF_TEST_SPARE));
+  HIP_TRY(noise_partials_alloc(npix, &partials));
   NoisePartial r;
   const rtx_status st = noise_reduce_launch(dS, dQ, d_counts, npix, spp, target, partials, &r);
   if (st != RTX_OK) return st;
@@ -687,24 +618,23 @@ rtx_status rtx_progressive_denoise(rtx_progressive* p, const RtxDenoiseParams* p
   if (p->spp_done < 2) { set_error(std::string(fn) + ": the variance needs at least 2 samples"); return RTX_EINVAL; }
   rtx_status st = ensure_features(p, feature_spp);
   if (st != RTX_OK) return st;
-  if (!p->denoise) {
-    DenoiseBuffers* b = new DenoiseBuffers();
-    const hipError_t e = b->alloc(p->npix_all);
+  if (!p->denoise.rgb8) {  // all five buffers or none: rgb8 is the last one allocated
+    DenoiseBuffers b;
+    const hipError_t e = denoise_buffers_alloc(p->npix_all, &b);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      delete b;
       set_error(std::string(fn) + ": " + hipGetErrorString(e));
       return e == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
     }
-    p->denoise = b;
+    p->denoise = std::move(b);
   }
   const int32_t w = p->cfg.image_width, h = (int32_t)(p->npix_all / (uint32_t)w);
   HIP_TRY(hipDeviceSynchronize());  // the adds ran on the caller's stream: S, Q and the counts must be complete
   st = denoise_launch(w, h, r, p->S, p->Q, any_retired(p) ? p->counts : nullptr, (uint32_t)p->spp_done, 1, p->albedo,
-                      p->normal, *p->denoise, mean_rgb != nullptr, rgb8 != nullptr);
+                      p->normal, p->denoise, mean_rgb != nullptr, rgb8 != nullptr);
   if (st != RTX_OK) return st;
-  if (mean_rgb) HIP_TRY(hipMemcpy(mean_rgb, p->denoise->mean, (size_t)p->npix_all * 24, hipMemcpyDeviceToHost));
-  if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->denoise->rgb8, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost));
+  if (mean_rgb) HIP_TRY(hipMemcpy(mean_rgb, p->denoise.mean, (size_t)p->npix_all * 24, hipMemcpyDeviceToHost));
+  if (rgb8) HIP_TRY(hipMemcpy(rgb8, p->denoise.rgb8, (size_t)p->npix_all * 3, hipMemcpyDeviceToHost));
   return RTX_OK;
 }
 
@@ -725,16 +655,14 @@ rtx_status rtx_device_denoise(const double* mean_rgb, const double* var_rgb, con
     a4[k] = make_float4(albedo_rgb[3 * k], albedo_rgb[3 * k + 1], albedo_rgb[3 * k + 2], 0.f);
     n4[k] = make_float4(normal_xyz[3 * k], normal_xyz[3 * k + 1], normal_xyz[3 * k + 2], 0.f);
   }
-  SelfTestBuffers t;
-  double *dm, *dv;
-  float4 *da, *dn;
+  DeviceBuffer<double> dm, dv;
+  DeviceBuffer<float4> da, dn;
   DenoiseBuffers b;
-  hipError_t e = t.upload(&dm, mean_rgb, npix * 3);
-  if (e == hipSuccess) e = t.upload(&dv, var_rgb, npix * 3);
-  if (e == hipSuccess) e = t.upload(&da, a4.data(), npix);
-  if (e == hipSuccess) e = t.upload(&dn, n4.data(), npix);
-  if (e == hipSuccess) e = b.alloc(npix);
-  if (e != hipSuccess) { (void)hipGetLastError(); set_error(std::string(fn) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
+  HIP_TRY(dm.upload(mean_rgb, npix * 3, SELF_TEST_SPARE));
+  HIP_TRY(dv.upload(var_rgb, npix * 3, SELF_TEST_SPARE));
+  HIP_TRY(da.upload(a4.data(), npix, SELF_TEST_SPARE));
+  HIP_TRY(dn.upload(n4.data(), npix, SELF_TEST_SPARE));
+  HIP_TRY(denoise_buffers_alloc(npix, &b));
   const rtx_status st = denoise_launch(width, height, r, dm, dv, nullptr, 0u, 0, da, dn, b, out_mean_rgb != nullptr,
                                        out_rgb8 != nullptr);
   if (st != RTX_OK) return st;

@@ -28,12 +28,13 @@
 #include "../core/integrator.hpp"
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
+#include "device_buffer.hpp"
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
 #else
-// The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports the
-// functions of f32_bridge.hpp and render.hip proper owns the handles.
+// The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports its upload and its
+// table of scene operations (f32_bridge.hpp) and render.hip proper owns the handles.
 namespace rtx { void set_error(const std::string& msg); }
 #endif
 
@@ -92,18 +93,15 @@ struct TraceSwitches {
 // Render workspace, grown on demand by render calls.  Passes of one render run two deep (render_impl): odd passes on aux_stream
 // with their own half of the sample buffer and their own work counter.
 struct Workspace {
-  double* samples = nullptr;
-  size_t samples_bytes = 0;
-  double* accum = nullptr;
-  size_t accum_bytes = 0;
-  rt::TraceCounters* counters = nullptr;
-  unsigned int* work_counter = nullptr;   // two: one per pass stream
-  unsigned long long* diag = nullptr;     // region counters of the diagnostic instantiations (diag_clear / diag_print)
+  DeviceBuffer<double> samples;
+  DeviceBuffer<double> accum;
+  DeviceBuffer<rt::TraceCounters> counters;
+  DeviceBuffer<unsigned int> work_counter;  // two: one per pass stream
+  DeviceBuffer<unsigned long long> diag;    // region counters of the diagnostic instantiations (diag_clear / diag_print)
   hipEvent_t ev[2] = {nullptr, nullptr};  // trace time of a pass (stats)
   hipStream_t aux_stream = nullptr;
   hipEvent_t ev_pass[3] = {nullptr, nullptr, nullptr};  // reduction of an even / odd pass done; start of the render
-  void* wave_mem = nullptr;               // the wavefront integrator's path pool
-  size_t wave_bytes = 0;
+  DeviceBuffer<unsigned char> wave_mem;   // the wavefront integrator's path pool
   uint32_t* wave_host_ctrl = nullptr;     // pinned
 };
 
@@ -163,8 +161,8 @@ struct WalkTuning {
 
 struct DeviceScene {
   int device = -1;
-  std::vector<void*> allocations;
-  rt::SceneView view;   // device pointers
+  std::vector<DeviceBuffer<void>> allocations;  // the uploaded arrays
+  rt::SceneView view;   // device pointers into them (a kernel argument)
   size_t scene_bytes = 0;
   int n_cu = 256;
   double gravity_time_limit = 1e300;  // scenes with GravitySpheres: the largest shutter time a render accepts
@@ -191,26 +189,20 @@ template <class T>
 static rtx_status upload_array(DeviceScene* ds, const std::vector<T>& v, const T** out) {
   *out = nullptr;
   if (v.empty()) return RTX_OK;
-  void* p = nullptr;
+  DeviceBuffer<void> b;
   size_t bytes = v.size() * sizeof(T);
-  HIP_TRY(hipMalloc(&p, bytes));
-  ds->allocations.push_back(p);
-  HIP_TRY(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
+  HIP_TRY(b.alloc(bytes));
+  HIP_TRY(hipMemcpy(b, v.data(), bytes, hipMemcpyHostToDevice));
   ds->scene_bytes += bytes;
-  *out = (const T*)p;
+  *out = (const T*)(void*)b;
+  ds->allocations.push_back(std::move(b));
   return RTX_OK;
 }
 
+// Releases what is not device memory; the buffers go with the DeviceScene.
 static void free_device_scene(DeviceScene* ds) {
   if (!ds) return;
   Workspace& ws = ds->ws;
-  for (void* p : ds->allocations) (void)hipFree(p);
-  if (ws.samples) (void)hipFree(ws.samples);
-  if (ws.accum) (void)hipFree(ws.accum);
-  if (ws.counters) (void)hipFree(ws.counters);
-  if (ws.work_counter) (void)hipFree(ws.work_counter);
-  if (ws.diag) (void)hipFree(ws.diag);
-  if (ws.wave_mem) (void)hipFree(ws.wave_mem);
   if (ws.wave_host_ctrl) (void)hipHostFree(ws.wave_host_ctrl);
   for (int i = 0; i < 2; ++i)
     if (ws.ev[i]) (void)hipEventDestroy(ws.ev[i]);
@@ -368,15 +360,6 @@ static uint32_t grid_size(uint32_t total, uint32_t block, uint64_t resident) {
   return (uint32_t)(want < resident ? want : resident);
 }
 
-// A device buffer grown to `need` bytes (its contents are not kept); the stream's work is finished before the old one is freed.
-static rtx_status grow_buffer(void** p, size_t* bytes, size_t need, hipStream_t stream) {
-  if (need <= *bytes) return RTX_OK;
-  if (*p) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(*p)); *p = nullptr; *bytes = 0; }
-  HIP_TRY(hipMalloc(p, need));
-  *bytes = need;
-  return RTX_OK;
-}
-
 // What every trace launch of one pass takes (render_impl's pass loop).
 struct PassArgs {
   rt::RenderParams rp;
@@ -406,7 +389,7 @@ static void with_map(const PassArgs& a, Launch launch) {
 template <class Launch>
 static rtx_status run_diag(DeviceScene* ds, hipStream_t stream, Launch launch, const char* tag, int width, const char* const* names,
                            int n, unsigned long long (&h)[24]) {
-  if (!ds->ws.diag) HIP_TRY(hipMalloc((void**)&ds->ws.diag, sizeof(h)));
+  if (!ds->ws.diag) HIP_TRY(ds->ws.diag.alloc(sizeof(h)));
   HIP_TRY(hipMemsetAsync(ds->ws.diag, 0, sizeof(h), stream));
   launch();
   HIP_TRY(hipStreamSynchronize(stream));
@@ -849,12 +832,11 @@ static rtx_status wave_pass(DeviceScene* ds, const PassArgs& a) {
   const uint32_t n_seg = P / WF_SEG;
   const size_t R = sizeof(rt::real);
   const size_t bytes = 64 + (size_t)P * (16 + 7 * R + 3 * R + 3 * R + R + 4 + 4 + 4 + 4) + (size_t)n_seg * 8;
-  rtx_status st = grow_buffer(&ws.wave_mem, &ws.wave_bytes, bytes, stream);
-  if (st != RTX_OK) return st;
+  HIP_TRY(ws.wave_mem.grow(bytes, stream));
   if (!ws.wave_host_ctrl) HIP_TRY(hipHostMalloc((void**)&ws.wave_host_ctrl, 4 * sizeof(uint32_t), hipHostMallocDefault));
   WavePool pool;
   {
-    unsigned char* m = (unsigned char*)ws.wave_mem;
+    unsigned char* m = ws.wave_mem;
     pool.ctrl = (uint32_t*)m; m += 64;
     pool.rng = (unsigned long long*)m; m += (size_t)P * 16;
     pool.ray = (rt::real*)m; m += (size_t)P * 7 * R;
@@ -961,14 +943,7 @@ static int32_t choose_trace_kernel(const DeviceScene* ds, int preset, bool count
 // An adaptive range (active != NULL: the ascending list of the n_active local pixels still active) traces those pixels only;
 // they replace the shard's pixels as the items of every pass (pass_items.inc), and it needs cont and sumsq.
 // light_sampling: trace with next-event estimation (k_trace_nee) instead of the reference's estimator.
-struct SampleRange {
-  uint32_t first, count;
-  int cont;
-  double* sumsq;
-  const uint32_t* active;
-  uint32_t n_active;
-  bool light_sampling;
-};
+typedef RtxSampleRange SampleRange;  // (f32_bridge.hpp: one struct for both compilations)
 
 // How one render is cut into passes: samples of every pixel per pass, passes two deep or not, bytes of the sample buffer.
 struct PassPlan {
@@ -991,12 +966,12 @@ static rtx_status prepare_workspace(DeviceScene* ds, const RtxConfig* cfg, uint6
     budget = 24ull << 30;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const uint64_t avail = ((uint64_t)free_b + ws.samples_bytes) / 3;
+      const uint64_t avail = ((uint64_t)free_b + ws.samples.bytes()) / 3;
       if (avail < budget) budget = avail;
     } else {
       (void)hipGetLastError();
     }
-    if (budget < ws.samples_bytes) budget = ws.samples_bytes;  // what is already there can be used
+    if (budget < ws.samples.bytes()) budget = ws.samples.bytes();  // what is already there can be used
   }
   const uint64_t per_sample_plane = npix * 24ull;
   uint32_t spp_pass = spp;
@@ -1015,14 +990,13 @@ static rtx_status prepare_workspace(DeviceScene* ds, const RtxConfig* cfg, uint6
   while (spp_pass > 1 && (uint64_t)spp_pass * npix >= 0xFFFF0000ull) --spp_pass;
   if ((uint64_t)spp_pass * npix >= 0xFFFF0000ull) { set_error("render: shard too large for one pass"); return RTX_EINVAL; }
   size_t need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
-  if (need_samples > ws.samples_bytes) {
-    if (ws.samples) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(ws.samples)); ws.samples = nullptr; ws.samples_bytes = 0; }
+  if (need_samples > ws.samples.bytes()) {
+    if (ws.samples) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(ws.samples.release()); }
     // out of memory: halve the pass until the buffer fits (down to one sample per pass) before giving up
     for (;;) {
-      hipError_t me = hipMalloc((void**)&ws.samples, need_samples);
+      hipError_t me = ws.samples.alloc(need_samples);
       if (me == hipSuccess) break;
       (void)hipGetLastError();
-      ws.samples = nullptr;
       if (me != hipErrorOutOfMemory || spp_pass <= 1) {
         set_error(std::string("render: sample buffer of ") + std::to_string(need_samples) + " bytes: " + hipGetErrorString(me));
         return me == hipErrorOutOfMemory ? RTX_ENOMEM : RTX_EHIP;
@@ -1030,15 +1004,13 @@ static rtx_status prepare_workspace(DeviceScene* ds, const RtxConfig* cfg, uint6
       spp_pass = (spp_pass + 1) / 2;
       need_samples = (size_t)spp_pass * per_sample_plane * (pipeline ? 2 : 1);
     }
-    ws.samples_bytes = need_samples;
   }
   if (!*accum) {
-    const rtx_status st = grow_buffer((void**)&ws.accum, &ws.accum_bytes, (size_t)npix_all * 24, stream);
-    if (st != RTX_OK) return st;
+    HIP_TRY(ws.accum.grow((size_t)npix_all * 24, stream));
     *accum = ws.accum;
   }
-  if (!ws.counters) HIP_TRY(hipMalloc((void**)&ws.counters, sizeof(rt::TraceCounters)));
-  if (!ws.work_counter) HIP_TRY(hipMalloc((void**)&ws.work_counter, 2 * sizeof(unsigned int)));
+  if (!ws.counters) HIP_TRY(ws.counters.alloc(sizeof(rt::TraceCounters)));
+  if (!ws.work_counter) HIP_TRY(ws.work_counter.alloc(2 * sizeof(unsigned int)));
   if (pipeline && !ws.aux_stream) {
     HIP_TRY(hipStreamCreateWithFlags(&ws.aux_stream, hipStreamNonBlocking));
     for (int i = 0; i < 3; ++i) HIP_TRY(hipEventCreateWithFlags(&ws.ev_pass[i], hipEventDisableTiming));
@@ -1104,6 +1076,9 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   const int preset = ((feat & ~P_SPHERES) == 0) ? 0 : (((feat & ~P_MESH) == 0) ? 1 : 2);
   const bool nee = range && range->light_sampling;
   if (nee && COUNT) { set_error("render: light sampling has no counting kernel"); return RTX_EUNSUPPORTED; }
+#ifdef RTX_F32_TU
+  if (nee) { set_error("render: light sampling is f64 only"); return RTX_EUNSUPPORTED; }  // (the *_ex entries reject it first)
+#endif
   const int32_t kernel = nee ? (int32_t)RTX_KERNEL_NEE : choose_trace_kernel(ds, preset, COUNT);
   PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)nitem, nullptr, nullptr, stream,
                 preset, feat, stack_levels, stack_bytes(stack_levels), adaptive ? range->active : nullptr};
@@ -1189,19 +1164,13 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   return RTX_OK;
 }
 
-// Tone map of an accumulator holding spp samples per pixel (progressive.inc reads a frame at any sample count).
-static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, uint32_t npix, uint32_t spp, hipStream_t stream) {
+// Tone map of an accumulator holding spp samples per pixel (progressive.inc reads a frame at any sample count) -- or, for an
+// adaptive frame (counts not NULL), counts[lp] samples in pixel lp, spp where that is 0 (still active).
+static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, const int32_t* counts, uint32_t npix, uint32_t spp,
+                               hipStream_t stream) {
   if (npix == 0) return RTX_OK;
-  hipLaunchKernelGGL(k_tonemap, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, npix, spp);
-  HIP_TRY(hipGetLastError());
-  return RTX_OK;
-}
-
-// The same for an adaptive frame: pixel lp holds counts[lp] samples, or spp where that is 0 (still active).
-static rtx_status tonemap_counts_impl(const double* accum, uint8_t* rgb8, const int32_t* counts, uint32_t npix, uint32_t spp,
-                                      hipStream_t stream) {
-  if (npix == 0) return RTX_OK;
-  hipLaunchKernelGGL(k_tonemap_counts, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, counts, npix, spp);
+  if (counts) hipLaunchKernelGGL(k_tonemap_counts, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, counts, npix, spp);
+  else hipLaunchKernelGGL(k_tonemap, dim3((npix + 255) / 256), dim3(256), 0, stream, accum, rgb8, npix, spp);
   HIP_TRY(hipGetLastError());
   return RTX_OK;
 }
@@ -1291,11 +1260,24 @@ static rtx_status scene_trim_impl(DeviceScene* ds) {
   HIP_TRY(hipGetDevice(&cur));
   if (cur != ds->device) { set_error("rtx_scene_trim: scene lives on a different device than the current one"); return RTX_EINVAL; }
   HIP_TRY(hipDeviceSynchronize());
-  Workspace& ws = ds->ws;
-  if (ws.samples) { HIP_TRY(hipFree(ws.samples)); ws.samples = nullptr; ws.samples_bytes = 0; }
-  if (ws.accum) { HIP_TRY(hipFree(ws.accum)); ws.accum = nullptr; ws.accum_bytes = 0; }
+  HIP_TRY(ds->ws.samples.release());
+  HIP_TRY(ds->ws.accum.release());
   return RTX_OK;
 }
+
+// This compilation's scene operations (f32_bridge.hpp), over the device scene as a void*.  The counting instantiation
+// render_impl<true> is f64 only and stays outside the table.
+static const RtxSceneOps scene_ops = {
+    [](void* ds, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard, double* d_accum_rgb, uint8_t* d_rgb8,
+       hipStream_t stream, RtxRenderStats* stats, const SampleRange* range) {
+      return render_impl<false>((DeviceScene*)ds, cam, cfg, shard, d_accum_rgb, d_rgb8, stream, stats, range);
+    },
+    tonemap_impl,
+    [](void* ds, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp, float4* d_albedo, float4* d_normal,
+       hipStream_t stream) { return features_impl((DeviceScene*)ds, cam, cfg, feature_spp, d_albedo, d_normal, stream); },
+    [](void* ds) { return scene_trim_impl((DeviceScene*)ds); },
+    [](void* ds) { free_device_scene((DeviceScene*)ds); },
+};
 
 }  // namespace rtx
 
@@ -1306,16 +1288,13 @@ using namespace rtx;
 #else
 #include "f32_convert.inc" // f64 flat arrays -> the f32 compilation's layouts
 
-// Every render entry point funnels through here: the scene handle says which compilation owns the device scene.
-template <bool COUNT>
+// Every render entry point but the counting one funnels through here: the scene handle carries the operations of the
+// compilation that owns its device scene.
 static rtx_status render_any(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, const RtxShard* shard,
-                             double* d_accum_rgb, uint8_t* d_rgb8, hipStream_t stream, RtxRenderStats* stats) {
+                             double* d_accum_rgb, uint8_t* d_rgb8, hipStream_t stream, RtxRenderStats* stats,
+                             const SampleRange* range = nullptr) {
   if (!s) { set_error("render: NULL scene, camera or config"); return RTX_EINVAL; }
-  if (s->f32) {
-    if (COUNT) { set_error("rtx_render_count: the work counters belong to the f64 path (upload the scene with rtx_scene_upload)"); return RTX_EUNSUPPORTED; }
-    return rtx_f32_render(s->device_scene, cam, cfg, shard, d_accum_rgb, d_rgb8, (void*)stream, stats);
-  }
-  return render_impl<COUNT>(scene_device(s), cam, cfg, shard, d_accum_rgb, d_rgb8, stream, stats);
+  return s->ops->render(s->device_scene, cam, cfg, shard, d_accum_rgb, d_rgb8, stream, stats, range);
 }
 
 extern "C" {
@@ -1326,7 +1305,7 @@ rtx_status rtx_scene_upload(const rtx_flat* f, rtx_scene** out) {
   DeviceScene* ds = nullptr;
   rtx_status st = scene_upload_impl(*flat_of(f), &ds);
   if (st != RTX_OK) return st;
-  *out = make_scene_handle(ds, 0);
+  *out = make_scene_handle(ds, &scene_ops, 0);
   return RTX_OK;
 }
 
@@ -1336,7 +1315,7 @@ rtx_status rtx_scene_upload_f32(const rtx_flat* f, rtx_scene** out) {
   void* ds32 = nullptr;
   rtx_status st = upload_as_f32(*flat_of(f), &ds32);
   if (st != RTX_OK) return st;
-  *out = make_scene_handle((DeviceScene*)ds32, 1);
+  *out = make_scene_handle(ds32, rtx_f32_scene_ops(), 1);
   return RTX_OK;
 }
 
@@ -1344,88 +1323,80 @@ int32_t rtx_scene_is_f32(const rtx_scene* s) { return s && s->f32 ? 1 : 0; }
 
 rtx_status rtx_scene_trim(rtx_scene* s) {
   if (!s) { set_error("rtx_scene_trim: NULL scene"); return RTX_EINVAL; }
-  if (s->f32) return rtx_f32_trim(s->device_scene);
-  return scene_trim_impl(scene_device(s));
+  return s->ops->trim(s->device_scene);
 }
 
 void rtx_scene_destroy(rtx_scene* s) {
   if (!s) return;
-  if (s->f32) rtx_f32_destroy(s->device_scene);
-  else free_device_scene(scene_device(s));
+  s->ops->destroy(s->device_scene);
   free_scene_handle(s);
 }
 
 rtx_status rtx_render_device(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
                              const RtxShard* shard, double* d_accum_rgb, uint8_t* d_rgb8,
                              void* hip_stream, RtxRenderStats* stats) {
-  return render_any<false>(s, cam, cfg, shard, d_accum_rgb, d_rgb8, (hipStream_t)hip_stream, stats);
+  return render_any(s, cam, cfg, shard, d_accum_rgb, d_rgb8, (hipStream_t)hip_stream, stats);
 }
 
 rtx_status rtx_render_count(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
                             const RtxShard* shard, RtxRenderStats* stats) {
   if (!stats) { set_error("rtx_render_count: stats is NULL"); return RTX_EINVAL; }
-  return render_any<true>(s, cam, cfg, shard, nullptr, nullptr, (hipStream_t) nullptr, stats);
+  if (!s) { set_error("render: NULL scene, camera or config"); return RTX_EINVAL; }
+  if (s->f32) { set_error("rtx_render_count: the work counters belong to the f64 path (upload the scene with rtx_scene_upload)"); return RTX_EUNSUPPORTED; }
+  return render_impl<true>(scene_device(s), cam, cfg, shard, nullptr, nullptr, (hipStream_t) nullptr, stats);
 }
 
 rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t n, double* out) {
   if (!x || !y || !out || n < 0) { set_error("rtx_device_math: bad argument"); return RTX_EINVAL; }
   if (n == 0) return RTX_OK;
-  double *dx = nullptr, *dy = nullptr, *dout = nullptr;
-  size_t bytes = (size_t)n * sizeof(double);
-  rtx_status st = RTX_OK;
-  auto fail = [&](const char* what, hipError_t e) { set_error(std::string(what) + ": " + hipGetErrorString(e)); st = RTX_EHIP; };
-  hipError_t e;
-  if ((e = hipMalloc((void**)&dx, bytes)) != hipSuccess) fail("hipMalloc", e);
-  if (st == RTX_OK && (e = hipMalloc((void**)&dy, bytes)) != hipSuccess) fail("hipMalloc", e);
-  if (st == RTX_OK && (e = hipMalloc((void**)&dout, bytes)) != hipSuccess) fail("hipMalloc", e);
-  if (st == RTX_OK && (e = hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice)) != hipSuccess) fail("hipMemcpy", e);
-  if (st == RTX_OK && (e = hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice)) != hipSuccess) fail("hipMemcpy", e);
-  if (st == RTX_OK) {
-    hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)fn, dx, dy, (long long)n, dout);
-    if ((e = hipGetLastError()) != hipSuccess) fail("k_device_math", e);
-  }
-  if (st == RTX_OK && (e = hipMemcpy(out, dout, bytes, hipMemcpyDeviceToHost)) != hipSuccess) fail("hipMemcpy", e);
-  if (dx) (void)hipFree(dx);
-  if (dy) (void)hipFree(dy);
-  if (dout) (void)hipFree(dout);
-  return st;
+  DeviceBuffer<double> dx, dy, dout;
+  HIP_TRY(dx.upload(x, (size_t)n));
+  HIP_TRY(dy.upload(y, (size_t)n));
+  HIP_TRY(dout.alloc((size_t)n * sizeof(double)));
+  hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)fn, dx, dy, (long long)n, dout);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return RTX_OK;
 }
 
 rtx_status rtx_device_stream(uint64_t seed, uint64_t pixel, uint32_t sample, int32_t n, double* out) {
   if (!out || n < 0) { set_error("rtx_device_stream: bad argument"); return RTX_EINVAL; }
   if (n == 0) return RTX_OK;
-  double* d = nullptr;
-  HIP_TRY(hipMalloc((void**)&d, (size_t)n * sizeof(double)));
+  DeviceBuffer<double> d;
+  HIP_TRY(d.alloc((size_t)n * sizeof(double)));
   hipLaunchKernelGGL(k_device_stream, dim3(1), dim3(64), 0, 0, (unsigned long long)seed, (unsigned long long)pixel, (unsigned int)sample, (int)n, d);
-  hipError_t e = hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-  (void)hipFree(d);
-  if (e != hipSuccess) { set_error(std::string("rtx_device_stream: ") + hipGetErrorString(e)); return RTX_EHIP; }
+  HIP_TRY(hipMemcpy(out, d, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+  return RTX_OK;
+}
+
+// One frame through host memory (rtx_render, rtx_render_ex; who: the entry point's name): allocates the device frame, renders
+// it, waits for it and copies back what `out` asks for.
+static rtx_status render_frame(const char* who, const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
+                               bool light_sampling, RtxFrame* out, RtxRenderStats* stats) {
+  RtxShard sh;
+  rtx_status st = validate(s, cam, cfg, nullptr, &sh);
+  if (st != RTX_OK) return st;
+  size_t npix = (size_t)cfg->image_width * (size_t)rtx_image_height(cfg);
+  DeviceBuffer<double> d_accum;
+  DeviceBuffer<uint8_t> d_rgb;
+  if (d_accum.alloc(npix * 24) != hipSuccess || d_rgb.alloc(npix * 3) != hipSuccess) {
+    set_error(std::string(who) + ": hipMalloc of the frame failed");
+    return RTX_EHIP;
+  }
+  // light sampling: the whole frame as one sample range from sample 0 -- the passes, sums and tone map of a one-shot render
+  const SampleRange range = {0u, (uint32_t)cfg->samples_per_pixel, 0, nullptr, nullptr, 0u, true};
+  st = render_any(s, cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, stats, light_sampling ? &range : nullptr);
+  if (st != RTX_OK) return st;
+  hipError_t e = hipDeviceSynchronize();
+  if (e == hipSuccess && out->accum_rgb) e = hipMemcpy(out->accum_rgb, d_accum, npix * 24, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d_rgb, npix * 3, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { set_error(std::string(who) + ": " + hipGetErrorString(e)); return RTX_EHIP; }
   return RTX_OK;
 }
 
 rtx_status rtx_render(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg, RtxFrame* out) {
   if (!out) { set_error("rtx_render: NULL frame"); return RTX_EINVAL; }
-  RtxShard sh;
-  rtx_status st = validate(s, cam, cfg, nullptr, &sh);
-  if (st != RTX_OK) return st;
-  size_t npix = (size_t)cfg->image_width * (size_t)rtx_image_height(cfg);
-  double* d_accum = nullptr;
-  uint8_t* d_rgb = nullptr;
-  if (hipMalloc((void**)&d_accum, npix * 24) != hipSuccess || hipMalloc((void**)&d_rgb, npix * 3) != hipSuccess) {
-    if (d_accum) (void)hipFree(d_accum);
-    set_error("rtx_render: hipMalloc of the frame failed");
-    return RTX_EHIP;
-  }
-  st = render_any<false>(s, cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, nullptr);
-  if (st == RTX_OK) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && out->accum_rgb) e = hipMemcpy(out->accum_rgb, d_accum, npix * 24, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d_rgb, npix * 3, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { set_error(std::string("rtx_render: ") + hipGetErrorString(e)); st = RTX_EHIP; }
-  }
-  (void)hipFree(d_accum);
-  (void)hipFree(d_rgb);
-  return st;
+  return render_frame("rtx_render", s, cam, cfg, false, out, nullptr);
 }
 
 // Argument checks of the *_ex entry points, before any device call.
@@ -1454,34 +1425,7 @@ rtx_status rtx_render_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConf
   bool nee = false;
   rtx_status st = check_integrator_options(s, opt, "rtx_render_ex", &nee);
   if (st != RTX_OK) return st;
-  RtxShard sh;
-  st = validate(s, cam, cfg, nullptr, &sh);
-  if (st != RTX_OK) return st;
-  if (!nee && !stats) return rtx_render(s, cam, cfg, out);
-  size_t npix = (size_t)cfg->image_width * (size_t)rtx_image_height(cfg);
-  double* d_accum = nullptr;
-  uint8_t* d_rgb = nullptr;
-  if (hipMalloc((void**)&d_accum, npix * 24) != hipSuccess || hipMalloc((void**)&d_rgb, npix * 3) != hipSuccess) {
-    if (d_accum) (void)hipFree(d_accum);
-    set_error("rtx_render_ex: hipMalloc of the frame failed");
-    return RTX_EHIP;
-  }
-  if (nee) {
-    // the whole frame as one sample range from sample 0: the passes, sums and tone map of a one-shot render
-    const SampleRange range = {0u, (uint32_t)cfg->samples_per_pixel, 0, nullptr, nullptr, 0u, true};
-    st = render_impl<false>(scene_device(s), cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, stats, &range);
-  } else {
-    st = render_any<false>(s, cam, cfg, nullptr, d_accum, d_rgb, (hipStream_t) nullptr, stats);
-  }
-  if (st == RTX_OK) {
-    hipError_t e = hipDeviceSynchronize();
-    if (e == hipSuccess && out->accum_rgb) e = hipMemcpy(out->accum_rgb, d_accum, npix * 24, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out->rgb8) e = hipMemcpy(out->rgb8, d_rgb, npix * 3, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { set_error(std::string("rtx_render_ex: ") + hipGetErrorString(e)); st = RTX_EHIP; }
-  }
-  (void)hipFree(d_accum);
-  (void)hipFree(d_rgb);
-  return st;
+  return render_frame("rtx_render_ex", s, cam, cfg, nee, out, stats);
 }
 
 }  // extern "C"
