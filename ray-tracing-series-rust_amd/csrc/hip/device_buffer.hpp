@@ -1,4 +1,4 @@
-// The one owner of device memory on the host side of render.hip (both compilations), progressive.inc and multi.inc.
+// The one owner of device memory on the host side: render.hip (both compilations), progressive.inc, multi.inc and lbvh.hip.
 //
 // A DeviceBuffer<T> holds one hipMalloc'ed allocation and its capacity in bytes.  It is freed exactly once (destructor or
 // release), it cannot be copied, and alloc / grow / upload never overwrite a pointer that is still set.  It reads as its raw

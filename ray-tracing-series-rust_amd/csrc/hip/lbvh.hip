@@ -23,16 +23,31 @@
 #include <vector>
 #include "../core/flat_types.hpp"
 #include "../host/flat_scene.hpp"
+#include "device_buffer.hpp"
 
 namespace rtx {
 
 namespace {
 
+// Inside a function that returns bool and has `err` in scope: a failed call records its text and returns false (the
+// function's DeviceBuffers and events free themselves).
 #define LBVH_TRY(expr)                                                                   \
   do {                                                                                   \
     hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e_); ok = false; goto done; } \
+    if (e_ != hipSuccess) { *err = std::string(#expr) + ": " + hipGetErrorString(e_); return false; } \
   } while (0)
+
+// The two events that time a build; destroyed on every way out.
+struct EventPair {
+  hipEvent_t begin = nullptr, end = nullptr;
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    if (begin) (void)hipEventDestroy(begin);
+    if (end) (void)hipEventDestroy(end);
+  }
+};
 
 struct Box6 { double v[6]; };  // min xyz, max xyz
 
@@ -220,6 +235,75 @@ __global__ __launch_bounds__(256) void k_depth(const int* __restrict__ parent_of
   atomicMax(max_depth, d);
 }
 
+// The device side of build_bvh_gpu: false with *err set when a HIP call fails (*nodes may then have grown; the caller cuts it
+// back).  Every temporary is a local owner, so each return frees them all.
+bool build_on_device(const std::vector<double>& boxes, size_t n, uint32_t cluster, int m, int32_t base,
+                            std::vector<rt::FlatNode>* nodes, std::vector<uint32_t>* order, int32_t* depth, double* device_ms,
+                            std::string* err) {
+  EventPair ev;  // declared first: destroyed after the buffers are freed
+  DeviceBuffer<Box6> d_boxes, d_leaf_box, d_node_box;
+  DeviceBuffer<double> d_bounds;
+  DeviceBuffer<unsigned long long> d_keys, d_keys_sorted;
+  DeviceBuffer<uint32_t> d_prims, d_prims_sorted;
+  DeviceBuffer<int2> d_children;
+  DeviceBuffer<int> d_parent_node, d_parent_leaf, d_depth;
+  DeviceBuffer<unsigned int> d_arrivals;
+  DeviceBuffer<rt::FlatNode> d_nodes;
+  DeviceBuffer<unsigned char> d_temp;
+  size_t temp_bytes = 0;
+  const uint32_t gn = (uint32_t)((n + 255) / 256), gm = (uint32_t)((m + 255) / 256);
+  LBVH_TRY(hipEventCreate(&ev.begin));
+  LBVH_TRY(hipEventCreate(&ev.end));
+  LBVH_TRY(d_boxes.alloc(n * sizeof(Box6)));
+  LBVH_TRY(d_bounds.alloc(6 * sizeof(double)));
+  LBVH_TRY(d_keys.alloc(n * 8));
+  LBVH_TRY(d_keys_sorted.alloc(n * 8));
+  LBVH_TRY(d_prims.alloc(n * 4));
+  LBVH_TRY(d_prims_sorted.alloc(n * 4));
+  LBVH_TRY(d_leaf_box.alloc((size_t)m * sizeof(Box6)));
+  LBVH_TRY(d_node_box.alloc((size_t)m * sizeof(Box6)));
+  LBVH_TRY(d_children.alloc((size_t)m * sizeof(int2)));
+  LBVH_TRY(d_parent_node.alloc((size_t)m * 4));
+  LBVH_TRY(d_parent_leaf.alloc((size_t)m * 4));
+  LBVH_TRY(d_arrivals.alloc((size_t)m * 4));
+  LBVH_TRY(d_depth.alloc(4));
+  LBVH_TRY(d_nodes.alloc((size_t)(m - 1) * sizeof(rt::FlatNode)));
+  // (the owners read as raw pointers; hipcub deduces its key and value types from them, hence the named locals)
+  unsigned long long *const keys = d_keys, *const keys_sorted = d_keys_sorted;
+  uint32_t *const prims = d_prims, *const prims_sorted = d_prims_sorted;
+  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, keys, keys_sorted, prims, prims_sorted, (int)n, 0, 63));
+  LBVH_TRY(d_temp.alloc(temp_bytes));
+  const double init[6] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
+  LBVH_TRY(hipEventRecord(ev.begin, 0));
+  LBVH_TRY(hipMemcpyAsync(d_boxes, boxes.data(), n * sizeof(Box6), hipMemcpyHostToDevice, 0));
+  LBVH_TRY(hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, 0));
+  LBVH_TRY(hipMemsetAsync(d_arrivals, 0, (size_t)m * 4, 0));
+  LBVH_TRY(hipMemsetAsync(d_depth, 0, 4, 0));
+  hipLaunchKernelGGL(k_centroid_bounds, dim3(gn), dim3(256), 0, 0, d_boxes, (uint32_t)n, d_bounds);
+  hipLaunchKernelGGL(k_morton, dim3(gn), dim3(256), 0, 0, d_boxes, (uint32_t)n, d_bounds, keys, prims);
+  LBVH_TRY(hipGetLastError());
+  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, keys, keys_sorted, prims, prims_sorted, (int)n, 0, 63));
+  hipLaunchKernelGGL(k_radix_tree, dim3(gm), dim3(256), 0, 0, keys_sorted, cluster, m, d_children, d_parent_node, d_parent_leaf);
+  hipLaunchKernelGGL(k_leaf_boxes, dim3(gm), dim3(256), 0, 0, d_boxes, prims_sorted, (uint32_t)n, cluster, m, d_leaf_box);
+  hipLaunchKernelGGL(k_refit, dim3(gm), dim3(256), 0, 0, d_children, d_parent_node, d_parent_leaf, d_leaf_box, m, d_node_box, d_arrivals);
+  hipLaunchKernelGGL(k_emit_nodes, dim3(gm), dim3(256), 0, 0, d_children, d_node_box, d_leaf_box, (uint32_t)n, cluster, m, base, d_nodes);
+  hipLaunchKernelGGL(k_depth, dim3(gm), dim3(256), 0, 0, d_parent_node, d_parent_leaf, m, d_depth);
+  LBVH_TRY(hipGetLastError());
+  nodes->resize((size_t)base + (size_t)(m - 1));
+  order->resize(n);
+  LBVH_TRY(hipMemcpyAsync(nodes->data() + base, d_nodes, (size_t)(m - 1) * sizeof(rt::FlatNode), hipMemcpyDeviceToHost, 0));
+  LBVH_TRY(hipMemcpyAsync(order->data(), prims_sorted, n * 4, hipMemcpyDeviceToHost, 0));
+  int h_depth = 0;
+  LBVH_TRY(hipMemcpyAsync(&h_depth, d_depth, 4, hipMemcpyDeviceToHost, 0));
+  LBVH_TRY(hipEventRecord(ev.end, 0));
+  LBVH_TRY(hipEventSynchronize(ev.end));
+  float ms = 0.f;
+  LBVH_TRY(hipEventElapsedTime(&ms, ev.begin, ev.end));
+  if (device_ms) *device_ms += (double)ms;
+  *depth = h_depth;
+  return true;
+}
+
 }  // namespace
 
 // Appends the tree to *nodes (indices are absolute positions in that vector, like the host builders).  Returns the
@@ -233,79 +317,12 @@ int32_t build_bvh_gpu(const std::vector<double>& boxes, int max_leaf, std::vecto
   uint32_t cluster = (uint32_t)(max_leaf < 1 ? 1 : (max_leaf > 8 ? 8 : max_leaf));
   if (n <= cluster) cluster = (uint32_t)(n - 1);  // at least two leaves: the root must be a node
   const int m = (int)((n + cluster - 1) / cluster);
-  bool ok = true;
-  Box6 *d_boxes = nullptr, *d_leaf_box = nullptr, *d_node_box = nullptr;
-  double* d_bounds = nullptr;
-  unsigned long long *d_keys = nullptr, *d_keys_sorted = nullptr;
-  uint32_t *d_prims = nullptr, *d_prims_sorted = nullptr;
-  int2* d_children = nullptr;
-  int *d_parent_node = nullptr, *d_parent_leaf = nullptr, *d_depth = nullptr;
-  unsigned int* d_arrivals = nullptr;
-  rt::FlatNode* d_nodes = nullptr;
-  void* d_temp = nullptr;
-  size_t temp_bytes = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  int32_t root = -1;
-  const uint32_t gn = (uint32_t)((n + 255) / 256), gm = (uint32_t)((m + 255) / 256);
   const int32_t base = (int32_t)nodes->size();
-  {
-    LBVH_TRY(hipEventCreate(&ev0));
-    LBVH_TRY(hipEventCreate(&ev1));
-    LBVH_TRY(hipMalloc((void**)&d_boxes, n * sizeof(Box6)));
-    LBVH_TRY(hipMalloc((void**)&d_bounds, 6 * sizeof(double)));
-    LBVH_TRY(hipMalloc((void**)&d_keys, n * 8));
-    LBVH_TRY(hipMalloc((void**)&d_keys_sorted, n * 8));
-    LBVH_TRY(hipMalloc((void**)&d_prims, n * 4));
-    LBVH_TRY(hipMalloc((void**)&d_prims_sorted, n * 4));
-    LBVH_TRY(hipMalloc((void**)&d_leaf_box, (size_t)m * sizeof(Box6)));
-    LBVH_TRY(hipMalloc((void**)&d_node_box, (size_t)m * sizeof(Box6)));
-    LBVH_TRY(hipMalloc((void**)&d_children, (size_t)m * sizeof(int2)));
-    LBVH_TRY(hipMalloc((void**)&d_parent_node, (size_t)m * 4));
-    LBVH_TRY(hipMalloc((void**)&d_parent_leaf, (size_t)m * 4));
-    LBVH_TRY(hipMalloc((void**)&d_arrivals, (size_t)m * 4));
-    LBVH_TRY(hipMalloc((void**)&d_depth, 4));
-    LBVH_TRY(hipMalloc((void**)&d_nodes, (size_t)(m - 1) * sizeof(rt::FlatNode)));
-    LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_keys, d_keys_sorted, d_prims, d_prims_sorted, (int)n, 0, 63));
-    LBVH_TRY(hipMalloc(&d_temp, temp_bytes));
-    const double init[6] = {__builtin_huge_val(), __builtin_huge_val(), __builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val(), -__builtin_huge_val()};
-    LBVH_TRY(hipEventRecord(ev0, 0));
-    LBVH_TRY(hipMemcpyAsync(d_boxes, boxes.data(), n * sizeof(Box6), hipMemcpyHostToDevice, 0));
-    LBVH_TRY(hipMemcpyAsync(d_bounds, init, sizeof(init), hipMemcpyHostToDevice, 0));
-    LBVH_TRY(hipMemsetAsync(d_arrivals, 0, (size_t)m * 4, 0));
-    LBVH_TRY(hipMemsetAsync(d_depth, 0, 4, 0));
-    hipLaunchKernelGGL(k_centroid_bounds, dim3(gn), dim3(256), 0, 0, d_boxes, (uint32_t)n, d_bounds);
-    hipLaunchKernelGGL(k_morton, dim3(gn), dim3(256), 0, 0, d_boxes, (uint32_t)n, d_bounds, d_keys, d_prims);
-    LBVH_TRY(hipGetLastError());
-    LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_keys, d_keys_sorted, d_prims, d_prims_sorted, (int)n, 0, 63));
-    hipLaunchKernelGGL(k_radix_tree, dim3(gm), dim3(256), 0, 0, d_keys_sorted, cluster, m, d_children, d_parent_node, d_parent_leaf);
-    hipLaunchKernelGGL(k_leaf_boxes, dim3(gm), dim3(256), 0, 0, d_boxes, d_prims_sorted, (uint32_t)n, cluster, m, d_leaf_box);
-    hipLaunchKernelGGL(k_refit, dim3(gm), dim3(256), 0, 0, d_children, d_parent_node, d_parent_leaf, d_leaf_box, m, d_node_box, d_arrivals);
-    hipLaunchKernelGGL(k_emit_nodes, dim3(gm), dim3(256), 0, 0, d_children, d_node_box, d_leaf_box, (uint32_t)n, cluster, m, base, d_nodes);
-    hipLaunchKernelGGL(k_depth, dim3(gm), dim3(256), 0, 0, d_parent_node, d_parent_leaf, m, d_depth);
-    LBVH_TRY(hipGetLastError());
-    nodes->resize((size_t)base + (size_t)(m - 1));
-    order->resize(n);
-    LBVH_TRY(hipMemcpyAsync(nodes->data() + base, d_nodes, (size_t)(m - 1) * sizeof(rt::FlatNode), hipMemcpyDeviceToHost, 0));
-    LBVH_TRY(hipMemcpyAsync(order->data(), d_prims_sorted, n * 4, hipMemcpyDeviceToHost, 0));
-    int h_depth = 0;
-    LBVH_TRY(hipMemcpyAsync(&h_depth, d_depth, 4, hipMemcpyDeviceToHost, 0));
-    LBVH_TRY(hipEventRecord(ev1, 0));
-    LBVH_TRY(hipEventSynchronize(ev1));
-    float ms = 0.f;
-    LBVH_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    if (device_ms) *device_ms += (double)ms;
-    *depth = h_depth;
-    root = base;  // Karras' root is internal node 0
+  if (!build_on_device(boxes, n, cluster, m, base, nodes, order, depth, device_ms, err)) {
+    nodes->resize((size_t)base);
+    return -1;
   }
-done:
-  if (!ok) nodes->resize((size_t)base);
-  for (void* p : {(void*)d_boxes, (void*)d_leaf_box, (void*)d_node_box, (void*)d_bounds, (void*)d_keys, (void*)d_keys_sorted,
-                  (void*)d_prims, (void*)d_prims_sorted, (void*)d_children, (void*)d_parent_node, (void*)d_parent_leaf,
-                  (void*)d_depth, (void*)d_arrivals, (void*)d_nodes, d_temp})
-    if (p) (void)hipFree(p);
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  return ok ? root : -1;
+  return base;  // Karras' root is internal node 0
 }
 
 }  // namespace rtx

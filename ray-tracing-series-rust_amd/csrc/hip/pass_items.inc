@@ -1,5 +1,6 @@
 // A pass's index space as the trace kernels see it (included by render.hip, namespace rtx): item -> pixel and path, the
-// sample store, the chunk size of the persistent kernels' work counter and the size of the per-wave primary-ray ring.
+// sample store, the persistent kernels' work counter (chunk size, claim), a lane's rank in a wave mask and the size of the
+// per-wave primary-ray ring.
 //
 // A pass of `total` items is one index space [0, total): item g = s_local * npix + lp is sample s_begin + s_local of the
 // shard's local pixel lp, so 64 consecutive items are 64 consecutive pixels of one sample: coherent primary rays, coalesced
@@ -57,7 +58,24 @@ __device__ __forceinline__ void store_sample(double* samples, uint32_t g, const 
 // Items a wave claims from the pass's work counter per grab (k_trace_lds: RTX_CHUNK, this by default).
 #define TRACE_CHUNK 512u
 
-// A wave's ring of ready primary rays in LDS (k_trace_vote, k_trace_lds; RTX_RING): f64 [RING_F64][cap] (origin(3),
-// direction(3), time, rng.s0, rng.s1), then u32 [cap] (the item).  Bytes per wave:
+// A lane's rank among the set lanes of a wave mask: the number of set bits below its own lane.  (k_wf_shade spells the pair out:
+// through this function its instructions come out in another order.)
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// The wave claims the next `chunk` items of the pass: lane 0 bumps the work counter, every lane gets the first item.  At or past
+// the pass's total the queue is empty; the caller clamps the chunk's end to the total.  Used where the kernel's code comes out
+// the same as with the lines written in place (k_trace_vote, trace_ring.inc); k_trace_lds without a ring, k_trace_world and
+// k_trace_nee keep them written out, and a form that also does the test and the clamp changed every kernel.
+__device__ __forceinline__ uint32_t queue_claim(unsigned int* work_counter, uint32_t chunk) {
+  uint32_t base = 0;
+  if ((threadIdx.x & 63u) == 0u) base = atomicAdd(work_counter, chunk);
+  return __builtin_amdgcn_readfirstlane(base);
+}
+
+// A wave's ring of ready primary rays in LDS (k_trace_vote, k_trace_lds; RTX_RING): f64 [RING_F64][cap], then u32 [cap] (the
+// item).  trace_ring.inc -- the top-up and the take, included by both kernels -- is the only text that knows the rows.  Bytes
+// per wave:
 #define RING_F64 9u
 __host__ __device__ constexpr uint32_t ring_bytes(uint32_t cap) { return cap * (RING_F64 * 8u + 4u); }

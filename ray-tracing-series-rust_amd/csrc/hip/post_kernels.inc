@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void k_retire_scatter(const uint32_t* __restri
   if (k >= n) return;
   const unsigned long long m = keep_mask[k >> 6];
   if (!((m >> (threadIdx.x & 63u)) & 1ull)) return;
-  const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+  const uint32_t rank = lane_rank(m);
   next[wave_base[threadIdx.x >> 6] + rank] = active[k];
 }
 

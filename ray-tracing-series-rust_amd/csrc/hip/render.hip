@@ -40,7 +40,7 @@ namespace rtx { void set_error(const std::string& msg); }
 
 namespace rtx {
 
-#include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, ring_bytes
+#include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, lane_rank, queue_claim, ring_bytes
 
 // ------------------------------------------------------------------ device scene
 struct FlatNode4;
@@ -263,6 +263,9 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 }
 
 // ------------------------------------------------------------------ kernels
+// The diagnostic instantiations' counters (k_trace_vote and k_trace_world with DIAG; run_diag below prints them): region k of a
+// kernel's `dg` array gets one execution and the lanes of `mask`.  Compiled out of every other instantiation.
+#define DIAG_ADD(region, mask) do { if (DIAG) { dg[2 * (region)] += 1; dg[2 * (region) + 1] += (unsigned long long)__popcll(mask); } } while (0)
 #include "trace_basic.inc"   // feature presets, k_trace_simple
 #include "trace_vote.inc"    // voting walk, 4-wide tree, k_trace_vote
 #include "trace_world.inc"   // k_trace_world: any world, per-lane scan of the world list with carried-over walks

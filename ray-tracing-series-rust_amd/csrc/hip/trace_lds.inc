@@ -197,51 +197,13 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
     const unsigned long long need_mask = wave_ballot(!active);
     if (need_mask != 0ull) {
       const uint32_t n_need = (uint32_t)__popcll(need_mask);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32),
-                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
+      const uint32_t rank = lane_rank(need_mask);
       if (RING) {
-        for (int rep = 0; rep < 2 && ring_n < n_need && !queue_empty; ++rep) {
-          if (chunk_pos >= chunk_end) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(work_counter, chunk);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base >= total) { queue_empty = true; break; }
-            chunk_pos = base;
-            chunk_end = (total - base < chunk) ? total : base + chunk;
-          }
-          const uint32_t room = ring_cap - ring_n, avail = chunk_end - chunk_pos;
-          const uint32_t m = room < avail ? room : avail;
-          if (lane < m) {
-            const uint32_t gg = chunk_pos + lane;
-            rt::PathState fresh;
-            start_path(rp, sm, npix, s_begin, gg, &fresh);
-            const uint32_t slot = ring_n + lane;
-            ring_f[0 * ring_cap + slot] = fresh.ray.origin.x; ring_f[1 * ring_cap + slot] = fresh.ray.origin.y;
-            ring_f[2 * ring_cap + slot] = fresh.ray.origin.z; ring_f[3 * ring_cap + slot] = fresh.ray.direction.x;
-            ring_f[4 * ring_cap + slot] = fresh.ray.direction.y; ring_f[5 * ring_cap + slot] = fresh.ray.direction.z;
-            ring_f[6 * ring_cap + slot] = fresh.ray.time;
-            ring_f[7 * ring_cap + slot] = rt::bits_f64(fresh.rng.s0); ring_f[8 * ring_cap + slot] = rt::bits_f64(fresh.rng.s1);
-            ring_g[slot] = gg;
-          }
-          chunk_pos += m;
-          ring_n += m;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        }
-        const uint32_t take = n_need < ring_n ? n_need : ring_n;
-        if (!active && rank < take) {
-          const uint32_t slot = ring_n - 1u - rank;
-          ps.ray = rt::make_ray(rt::v3(ring_f[0 * ring_cap + slot], ring_f[1 * ring_cap + slot], ring_f[2 * ring_cap + slot]),
-                                rt::v3(ring_f[3 * ring_cap + slot], ring_f[4 * ring_cap + slot], ring_f[5 * ring_cap + slot]),
-                                ring_f[6 * ring_cap + slot]);
-          ps.rng.s0 = rt::f64_bits(ring_f[7 * ring_cap + slot]); ps.rng.s1 = rt::f64_bits(ring_f[8 * ring_cap + slot]);
-          ps.product = rt::v3(1, 1, 1);
-          ps.output = rt::v3(0, 0, 0);
-          ps.depth = rp.max_depth;
-          g = ring_g[slot];
-          active = true;
-        }
-        ring_n -= take;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+#define RING_CAP ring_cap
+#define RING_DIAG(mask)
+#include "trace_ring.inc"
+#undef RING_DIAG
+#undef RING_CAP
       } else {
         if (chunk_pos >= chunk_end && !queue_empty) {
           uint32_t base = 0;

@@ -250,12 +250,9 @@ __device__ __forceinline__ void walk_node_step4(const FlatNode4* __restrict__ no
 // active in it); regions: 0 outer iteration, 1 regenerate, 2 node step, 3 leaf step, 4 shade (hit lanes),
 // 5 shade (all walking lanes).  Diagnostic build only (RTX_TRACE_KERNEL=vote_diag); never timed.
 //
-// RING: primary rays are produced 64 at a time.  Regeneration (Philox seeding, pixel jitter, lens
-// rejection loop, camera ray: ~600 VALU) used to run every outer iteration for just the ~20 lanes
-// whose path had ended.  With RING a wave keeps up to 64 ready primary rays (ray + RNG state + sample
-// index, 76 B each) in its own slice of LDS; a lane whose path ends pops one (10 LDS reads), and only
-// when the ring cannot serve the request does the whole wave run the regeneration code, all lanes at
-// once, to top the ring up.  Which lane traces a sample is invisible in the result.
+// RING: primary rays are produced 64 at a time into the wave's ring in LDS instead of every outer iteration for just the
+// ~20 lanes whose path had ended (trace_ring.inc; layout and size: pass_items.inc).  Which lane traces a sample is
+// invisible in the result.
 // (VoteTop, the plain entries beside the BVH as a kernel argument, is declared in render.hip next to DeviceScene.)
 template <uint32_t F, bool DIAG, bool RING, bool WIDE, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv, rt::RenderParams rp,
@@ -268,7 +265,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
                                                             uint32_t lds_tables, VoteTop top) {
   unsigned long long dg[12];
   if (DIAG) for (int k = 0; k < 12; ++k) dg[k] = 0;
-#define DIAG_ADD(region, mask) do { if (DIAG) { dg[2 * (region)] += 1; dg[2 * (region) + 1] += (unsigned long long)__popcll(mask); } } while (0)
   extern __shared__ int32_t lds_stack[];
   LdsStackB stack;
   stack.base = lds_stack + threadIdx.x;
@@ -290,7 +286,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
   // the launcher packs two thresholds into one argument: walk (low 16 bits) and regeneration (high 16 bits, at least 1)
   const uint32_t regen_min = (walk_threshold >> 16) ? (walk_threshold >> 16) : 1u;
   walk_threshold &= 0xffffu;
-  // this wave's ring of ready primary rays: f64 [RING_F64][64], then u32 [64] (sample index)
+  // this wave's ring of ready primary rays (pass_items.inc)
   double* const ring_f = (double*)((unsigned char*)(lds_stack + stack_levels * TRACE_BLOCK) +
                                    (threadIdx.x >> 6) * ring_bytes(64));
   uint32_t* const ring_g = (uint32_t*)(ring_f + RING_F64 * 64);
@@ -298,6 +294,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
   const rt::FlatEntry& bvh = sv.entries[sv.top_level[bvh_pos]];
   const int32_t root = bvh.a;
   const uint32_t first_ref = (uint32_t)bvh.b;
+  constexpr uint32_t chunk = TRACE_CHUNK;  // items per claim
   uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
   bool queue_empty = false;               // wave-uniform
   bool active = false;
@@ -318,58 +315,16 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
     if (RING) {
       if (need_mask != 0ull) {
         const uint32_t n_need = (uint32_t)__popcll(need_mask);
-        // top the ring up (at most twice: a chunk boundary can cut the first batch short)
-        for (int rep = 0; rep < 2 && ring_n < n_need && !queue_empty; ++rep) {
-          if (chunk_pos >= chunk_end) {
-            uint32_t base = 0;
-            if (lane == 0) base = atomicAdd(work_counter, TRACE_CHUNK);
-            base = __builtin_amdgcn_readfirstlane(base);
-            if (base >= total) { queue_empty = true; break; }
-            chunk_pos = base;
-            chunk_end = (total - base < TRACE_CHUNK) ? total : base + TRACE_CHUNK;
-          }
-          const uint32_t room = 64u - ring_n, avail = chunk_end - chunk_pos;
-          const uint32_t m = room < avail ? room : avail;
-          DIAG_ADD(1, wave_ballot(lane < m));
-          if (lane < m) {
-            const uint32_t gg = chunk_pos + lane;
-            rt::PathState fresh;
-            start_path(rp, sm, npix, s_begin, gg, &fresh);
-            const uint32_t slot = ring_n + lane;
-            ring_f[0 * 64 + slot] = fresh.ray.origin.x; ring_f[1 * 64 + slot] = fresh.ray.origin.y;
-            ring_f[2 * 64 + slot] = fresh.ray.origin.z; ring_f[3 * 64 + slot] = fresh.ray.direction.x;
-            ring_f[4 * 64 + slot] = fresh.ray.direction.y; ring_f[5 * 64 + slot] = fresh.ray.direction.z;
-            ring_f[6 * 64 + slot] = fresh.ray.time;
-            ring_f[7 * 64 + slot] = rt::bits_f64(fresh.rng.s0); ring_f[8 * 64 + slot] = rt::bits_f64(fresh.rng.s1);
-            ring_g[slot] = gg;
-          }
-          chunk_pos += m;
-          ring_n += m;
-          __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");  // LDS executes a wave's accesses in order
-        }
-        const uint32_t take = n_need < ring_n ? n_need : ring_n;
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32),
-                                                        __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
-        if (!active && rank < take) {
-          const uint32_t slot = ring_n - 1u - rank;
-          ps.ray = rt::make_ray(rt::v3(ring_f[0 * 64 + slot], ring_f[1 * 64 + slot], ring_f[2 * 64 + slot]),
-                                rt::v3(ring_f[3 * 64 + slot], ring_f[4 * 64 + slot], ring_f[5 * 64 + slot]),
-                                ring_f[6 * 64 + slot]);
-          ps.rng.s0 = rt::f64_bits(ring_f[7 * 64 + slot]); ps.rng.s1 = rt::f64_bits(ring_f[8 * 64 + slot]);
-          ps.product = rt::v3(1, 1, 1);   // path_begin's constants (core/integrator.hpp)
-          ps.output = rt::v3(0, 0, 0);
-          ps.depth = rp.max_depth;
-          g = ring_g[slot];
-          active = true;
-        }
-        ring_n -= take;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const uint32_t rank = lane_rank(need_mask);
+#define RING_CAP 64u
+#define RING_DIAG(mask) DIAG_ADD(1, mask)
+#include "trace_ring.inc"
+#undef RING_DIAG
+#undef RING_CAP
       }
     } else if ((uint32_t)__popcll(need_mask) >= regen_min) {  // regeneration is ~600 VALU: it waits until enough lanes want it
       if (chunk_pos >= chunk_end && !queue_empty) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(work_counter, TRACE_CHUNK);
-        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t base = queue_claim(work_counter, TRACE_CHUNK);
         if (base >= total) {
           queue_empty = true;
         } else {
@@ -378,8 +333,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
         }
       }
       if (chunk_pos < chunk_end) {
-        uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32),
-                                                  __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
+        uint32_t rank = lane_rank(need_mask);
         uint32_t n_need = (uint32_t)__popcll(need_mask);
         uint32_t avail = chunk_end - chunk_pos;
         DIAG_ADD(1, wave_ballot(!active && rank < avail));
@@ -499,6 +453,5 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
     if (lane == 0)
       for (int k = 0; k < 12; ++k) atomicAdd(&diag[k], dg[k]);
   }
-#undef DIAG_ADD
 }
 

@@ -145,7 +145,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, MIN_BLOCKS) void k_wf_trace(rt::SceneV
     const unsigned long long need_mask = wave_ballot(slot == WF_FREE);
     const uint32_t n_need = (uint32_t)__popcll(need_mask);
     if (!queue_empty && n_need >= refill_min) {
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
+      const uint32_t rank = lane_rank(need_mask);
       const uint32_t avail = WF_DEAL - chunk_pos;
       if (slot == WF_FREE && rank < avail) {
         const uint32_t s = chunk * WF_DEAL + chunk_pos + rank;

@@ -163,7 +163,6 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     uint32_t stack_levels, uint32_t n_perlin_lds, uint32_t n_mat_lds, uint32_t n_tex_lds, unsigned long long* diag = nullptr) {
   unsigned long long dg[16];
   if (DIAG) for (int k = 0; k < 16; ++k) dg[k] = 0;
-#define WDIAG(region, mask) do { if (DIAG) { dg[2 * (region)] += 1; dg[2 * (region) + 1] += (unsigned long long)__popcll(mask); } } while (0)
   rt::SceneView sv = sv_in;  // read-only tables through const __restrict__ parameters: scalar loads where uniform
   sv.entries = entries_ro; sv.top_level = top_level_ro;
   sv.spheres = spheres_ro; sv.moving_spheres = msph_ro; sv.rects = rects_ro; sv.triangles = tris_ro;
@@ -295,13 +294,13 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
       unsigned long long mn = m_node, ml = m_leaf;
       for (;;) {
         if ((uint32_t)__popcll(mn) * leaf_weight >= (uint32_t)__popcll(ml)) {
-          WDIAG(0, mn);
+          DIAG_ADD(0, mn);
           if ((uint32_t)cur < (uint32_t)WALK_DONE) {
             if (WIDE) walk_node_step4(nodes4, q, dir_neg, t_max32, &cur, stack);
             else walk_node_step32(sv.nodes32[cur], q, dir_neg, t_max32, &cur, stack);
           }
         } else if (cur < 0) {
-          WDIAG(1, ml);
+          DIAG_ADD(1, ml);
           const rt::Ray rl = slot_ray();
           walk_leaf_step<F>(sv, first_ref, rl, slot[6 * TRACE_BLOCK], &best, &cur, stack);
           t_max32 = rt::cull_round_up(best.t);
@@ -316,7 +315,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
       // (A split into a lean Lambertian-only class and a "rare materials" class was measured on Book-2 and dropped: 72 % of
       // its hits are on glass, fog or lights -- the r = 5000 glass shell alone catches every escaping ray -- and a fifth
       // class thins every other one out: 631 -> 493 Msamples/s.)
-      WDIAG(3, m_shade);
+      DIAG_ADD(3, m_shade);
       if (stage == WS_SHADE) {
         rt::HitRecord rec;
         if (hit_any) {
@@ -356,7 +355,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
       }
     } else if (n_sweep >= n_need) {
       // ------------------------------------------------------------------ sweep over the world list
-      WDIAG(2, m_sweep);
+      DIAG_ADD(2, m_sweep);
       for (int32_t e = 0; e < n_top; ++e) {
         const bool done_here = stage == WS_WALK && cur == WALK_DONE && ei == e;
         const bool begin_here = stage == WS_ENTRY && ei == e;
@@ -429,8 +428,8 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
             const float hi[3] = {dev_load_uniform(&D->box[3]), dev_load_uniform(&D->box[4]), dev_load_uniform(&D->box[5])};
             may = rt::cull32_may_hit(lo, hi, rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray)), rt::cull_round_up(closest));
           }
-          WDIAG(5, wave_ballot(may));
-          if (wave_ballot(may) != 0ull) WDIAG(6, wave_ballot(may));
+          DIAG_ADD(5, wave_ballot(may));
+          if (wave_ballot(may) != 0ull) DIAG_ADD(6, wave_ballot(may));
           if ((F & rt::F_MEDIUM_SPHERE) && (flags & WD_SPHERE) && (is_medium || (flags & WD_PAIR))) {
             // one static sphere asked more than once: the quadratic is solved once (core/geometry.hpp: sphere_roots)
             if (wave_ballot(may) != 0ull && may) {
@@ -483,7 +482,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     } else {
       // ------------------------------------------------------------------ hand new paths to the lanes without one
       const unsigned long long need_mask = m_need;
-      WDIAG(4, m_need);
+      DIAG_ADD(4, m_need);
       {
         if (chunk_pos >= chunk_end && !queue_empty) {
           uint32_t base = 0;
@@ -493,7 +492,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
           else { chunk_pos = base; chunk_end = (total - base < TRACE_CHUNK) ? total : base + TRACE_CHUNK; }
         }
         if (chunk_pos < chunk_end) {
-          const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(need_mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)need_mask, 0u));
+          const uint32_t rank = lane_rank(need_mask);
           const uint32_t n_want = (uint32_t)__popcll(need_mask);
           const uint32_t avail = chunk_end - chunk_pos;
           if (stage == WS_NEED && rank < avail) {
@@ -508,5 +507,4 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
   }
   if (DIAG && lane == 0)
     for (int k = 0; k < 16; ++k) atomicAdd(&diag[k], dg[k]);
-#undef WDIAG
 }
