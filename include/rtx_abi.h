@@ -459,7 +459,11 @@ rtx_status rtx_write_ppm(const char* path, int32_t width, int32_t height, const 
  * (copied in and out), so tests can prove it is bit-identical to the host's evaluation of the same
  * source.  fn: 0 sin, 1 cos, 2 log, 3 acos, 4 atan2(x,y), 5 tan, 6 sqrt, 7 x/y, 8 x*y+x (must NOT be
  * fused), 9 floor, 10 the sort key of a 4-wide BVH step for entry distance x and t_min y
- * (clamp into [y, 3e38] with NaN -> y).  rtx_device_stream: the first n uniforms of the (seed, pixel, sample) stream. */
+ * (clamp into [y, 3e38] with NaN -> y).  fn >= 32: the building blocks of the f32 fast mode, evaluated by the f32
+ * compilation on (float)x, (float)y, the float result widened: 32 sinf, 33 cosf, 34 logf, 35 acosf, 36 atan2f(x,y), 37 sqrtf,
+ * 38 x/y, 39 the sign rt_sin_sign returns, 43 the capped slope 1/x of the f32 culling ray; 40 / 41 / 42 the float forms of
+ * gen::<f64>() / gen_range(lo..hi) / gen_range(-1..1) from one raw 64-bit draw given as the BITS of x (41: lo and hi as floats
+ * in the low and high word of y).  rtx_device_stream: the first n uniforms of the (seed, pixel, sample) stream. */
 rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t n, double* out);
 rtx_status rtx_device_stream(uint64_t seed, uint64_t pixel, uint32_t sample, int32_t n, double* out);
 /* The adaptive retirement check of rtx_progressive_add_adaptive (k_retire_flag / _scan / _scatter) on host arrays, through

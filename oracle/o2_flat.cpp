@@ -21,6 +21,7 @@
 #include <vector>
 #include "../ray-tracing-series-rust_amd/csrc/core/integrator.hpp"
 #include "../ray-tracing-series-rust_amd/csrc/host/flat_scene.hpp"
+#include "../ray-tracing-series-rust_amd/csrc/host/f32_layout.hpp"
 #include "oracle_abi.h"
 
 namespace {
@@ -284,6 +285,42 @@ double oracle_motion_leaf_area_ratio(const void* flat) {
       a_motion += e[0] * e[1] + e[1] * e[2] + e[2] * e[0];
     }
   return a_static > 0.0 ? a_motion / a_static : 1.0;
+}
+
+// ---- the f64 side of the seam to the float checker (o2_flat_f32.cpp), as csrc/hip/f32_convert.inc is for the device ----
+struct F32Images { std::vector<unsigned char> img[RTX32_N_ARRAYS]; };
+int oracle_f32_images(const void* flat, RtxF32Blobs* blobs, void** keep) {
+  if (!flat || !blobs || !keep) return 1;
+  F32Images* owner = new F32Images;
+  *keep = owner;
+  return rtx::f32_images(*(const rtx::FlatScene*)flat, owner->img, blobs) ? 0 : 2;
+}
+void oracle_f32_images_free(void* keep) { delete (F32Images*)keep; }
+
+// The product's narrowing of n elements of elem64 bytes described by `desc` (host/f32_layout.hpp), for the descriptor tests:
+// returns the f32 element size (0 when desc does not describe elem64 bytes); out (may be NULL) must hold n * that many bytes.
+int64_t oracle_f32_convert(const char* desc, const void* in, int64_t n, int64_t elem64, void* out) {
+  std::vector<unsigned char> img;
+  size_t elem32 = 0;
+  if (!rtx::f32_convert_bytes(in, (size_t)n, (size_t)elem64, desc, &img, &elem32)) return 0;
+  if (out) memcpy(out, img.data(), img.size());
+  return (int64_t)elem32;
+}
+// The descriptor table itself: entry k's array name and descriptor string; NULL past the end.
+const char* oracle_f32_desc(int32_t k, const char** name) {
+  if (k < 0 || k >= (int32_t)(sizeof(rtx::F32_DESCS) / sizeof(rtx::F32_DESCS[0]))) return nullptr;
+  if (name) *name = rtx::F32_DESCS[k].name;
+  return rtx::F32_DESCS[k].desc;
+}
+// The bytes of one flat array of the f64 scene (by the descriptor table's name): pointer, element count and element size.
+const void* oracle_flat_array(const void* flat, const char* name, int64_t* n, int64_t* elem_bytes) {
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+#define ARR(VEC) if (!strcmp(name, #VEC)) { *n = (int64_t)fs.VEC.size(); *elem_bytes = (int64_t)sizeof(fs.VEC[0]); return fs.VEC.data(); }
+  ARR(spheres) ARR(moving_spheres) ARR(rects) ARR(triangles) ARR(nodes) ARR(entries) ARR(materials) ARR(textures)
+  ARR(perlins) ARR(gravity_spheres) ARR(texels) ARR(gravity_y)
+#undef ARR
+  *n = 0; *elem_bytes = 0;
+  return nullptr;
 }
 
 void oracle_philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) { rt::philox4x32_10(ctr, k0, k1); }

@@ -44,6 +44,31 @@ int oracle_o2_render(const void* flat, const OracleCamera* cam, const OracleConf
 int oracle_o2_sample(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t i,
                      int32_t j, int32_t sample, double rgb[3]);
 
+/* O2f: O2 with real = float (oracle/o2_flat_f32.cpp) -- the CPU statement of what the f32 fast mode computes.  Takes the
+ * f64 flat scene and narrows it with the product's converter.  Renders samples first_sample .. first_sample + spp - 1 of
+ * the shard's pixels; accum_rgb is the ordered f64 sum of the widened float samples.  oracle_o2g_*: the same with the five
+ * platform functions computed in double and rounded to float (o2_flat_f32_via_f64.cpp). */
+int oracle_o2f_render(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t shard_index,
+                      int32_t shard_count, int32_t block_rows, int32_t first_sample, double* accum_rgb, uint8_t* rgb8);
+int oracle_o2f_sample(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t i, int32_t j,
+                      int32_t sample, double rgb[3]);
+int oracle_o2g_render(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t shard_index,
+                      int32_t shard_count, int32_t block_rows, int32_t first_sample, double* accum_rgb, uint8_t* rgb8);
+int oracle_o2g_sample(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t i, int32_t j,
+                      int32_t sample, double rgb[3]);
+/* Probes into the float build of the core: one ray through world_hit (t_min < 0: the integrator's own guard), the
+ * non-finite-ray rule of path_bounce_begin, make_ray32's host branch, and the float building blocks under the function
+ * codes of rtx_device_math's float entries. */
+int oracle_core32_world_hit(const void* flat, const double o[3], const double d[3], double time, double t_min,
+                            double t_max, uint64_t rng_seed, double out[10]);
+int oracle_core32_path_ends(const double o[3], const double d[3], int32_t depth);
+void oracle_core32_ray32(const double o[3], const double d[3], double out[8]);
+void oracle_core32_math(int32_t fn, const double* x, const double* y, int64_t n, double* out);
+/* The product's f64 -> f32 scene converter (csrc/host/f32_layout.hpp) and what it is fed. */
+int64_t oracle_f32_convert(const char* desc, const void* in, int64_t n, int64_t elem64, void* out);
+const char* oracle_f32_desc(int32_t k, const char** name);
+const void* oracle_flat_array(const void* flat, const char* name, int64_t* n, int64_t* elem_bytes);
+
 /* Known-answer probes into O1's restated functions. */
 void oracle_o1_vec3_ops(const double a[3], const double b[3], double t, double out[24]);
 void oracle_o1_tone_map(const double sum[3], uint32_t spp, int32_t out[3]);

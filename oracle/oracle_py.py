@@ -93,6 +93,27 @@ def load():
     lib.oracle_sample_stream.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _D]
     lib.oracle_rt_math.restype = None
     lib.oracle_rt_math.argtypes = [C.c_int32, _D, _D, C.c_int64, _D]
+    for side in ("o2f", "o2g"):
+        getattr(lib, "oracle_%s_render" % side).restype = C.c_int
+        getattr(lib, "oracle_%s_render" % side).argtypes = [C.c_void_p, C.POINTER(OracleCamera), C.POINTER(OracleConfig), C.c_int32,
+                                                            C.c_int32, C.c_int32, C.c_int32, _D, C.POINTER(C.c_uint8)]
+        getattr(lib, "oracle_%s_sample" % side).restype = C.c_int
+        getattr(lib, "oracle_%s_sample" % side).argtypes = [C.c_void_p, C.POINTER(OracleCamera), C.POINTER(OracleConfig), C.c_int32,
+                                                            C.c_int32, C.c_int32, _D]
+    lib.oracle_core32_world_hit.restype = C.c_int
+    lib.oracle_core32_world_hit.argtypes = [C.c_void_p, _D, _D, C.c_double, C.c_double, C.c_double, C.c_uint64, _D]
+    lib.oracle_core32_path_ends.restype = C.c_int
+    lib.oracle_core32_path_ends.argtypes = [_D, _D, C.c_int32]
+    lib.oracle_core32_ray32.restype = None
+    lib.oracle_core32_ray32.argtypes = [_D, _D, _D]
+    lib.oracle_core32_math.restype = None
+    lib.oracle_core32_math.argtypes = [C.c_int32, _D, _D, C.c_int64, _D]
+    lib.oracle_f32_convert.restype = C.c_int64
+    lib.oracle_f32_convert.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+    lib.oracle_f32_desc.restype = C.c_char_p
+    lib.oracle_f32_desc.argtypes = [C.c_int32, C.POINTER(C.c_char_p)]
+    lib.oracle_flat_array.restype = C.c_void_p
+    lib.oracle_flat_array.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
     return lib
 
@@ -179,6 +200,105 @@ def o2_sample(flat_arrays_ptr, rtx_cam, rtx_cfg, image_height, i, j, s):
     out = (C.c_double * 3)()
     lib.oracle_o2_sample(flat_arrays_ptr, C.byref(cam), C.byref(cfg), i, j, s, out)
     return np.array(out[:])
+
+
+def o2f_render(flat_arrays_ptr, rtx_cam, rtx_cfg, image_height, shard=(0, 1, 1), threads=None, first_sample=0, accum=None,
+               via_f64=False):
+    """O2 with real = float over the f64 flat scene narrowed by the product's converter: what the f32 fast mode computes.
+    Samples first_sample .. first_sample + spp - 1; with first_sample > 0, `accum` (the sums of the samples before) is
+    continued in a copy.  via_f64: the build whose platform functions are computed in double."""
+    lib = load()
+    cam = camera_from(rtx_cam)
+    cfg = config_from(rtx_cfg, image_height, threads)
+    w = rtx_cfg.image_width
+    rows = [j for j in range(image_height) if (j // shard[2]) % shard[1] == shard[0]]
+    if (first_sample > 0) != (accum is not None):
+        raise ValueError("accum goes with first_sample > 0")
+    accum = np.zeros((len(rows), w, 3), dtype=np.float64) if accum is None else np.array(accum, dtype=np.float64, order="C")
+    assert accum.shape == (len(rows), w, 3)
+    rgb8 = np.zeros((len(rows), w, 3), dtype=np.uint8)
+    fn = lib.oracle_o2g_render if via_f64 else lib.oracle_o2f_render
+    rc = fn(flat_arrays_ptr, C.byref(cam), C.byref(cfg), shard[0], shard[1], shard[2], first_sample,
+            accum.ctypes.data_as(_D), rgb8.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc != 0:
+        raise RuntimeError("oracle_o2f_render failed (%d)" % rc)
+    return accum, rgb8
+
+
+def o2f_sample(flat_arrays_ptr, rtx_cam, rtx_cfg, image_height, i, j, s, via_f64=False):
+    lib = load()
+    cam = camera_from(rtx_cam)
+    cfg = config_from(rtx_cfg, image_height)
+    out = (C.c_double * 3)()
+    rc = (lib.oracle_o2g_sample if via_f64 else lib.oracle_o2f_sample)(flat_arrays_ptr, C.byref(cam), C.byref(cfg), i, j, s, out)
+    if rc != 0:
+        raise RuntimeError("oracle_o2f_sample failed (%d)" % rc)
+    return np.array(out[:])
+
+
+def core32_world_hit(flat_arrays_ptr, o, d, time=0.0, t_min=-1.0, t_max=float("inf"), rng_seed=1):
+    """One float ray through the float build's world_hit (t_min < 0: the integrator's own guard, ray_t_min)."""
+    out = (C.c_double * 10)()
+    return _rec(load().oracle_core32_world_hit(flat_arrays_ptr, _d3(o), _d3(d), time, t_min, t_max, rng_seed, out), out)
+
+
+def core32_path_ends(o, d, depth=50):
+    return bool(load().oracle_core32_path_ends(_d3(o), _d3(d), depth))
+
+
+def core32_ray32(o, d):
+    out = (C.c_double * 8)()
+    load().oracle_core32_ray32(_d3(o), _d3(d), out)
+    return dict(zip(("ix", "iy", "iz", "oix", "oiy", "oiz", "err2", "t_min"), out))
+
+
+# the function codes of rtx_device_math's float entries (api.py: DEVICE_MATH_F32)
+MATH_F32 = {"sinf": 32, "cosf": 33, "logf": 34, "acosf": 35, "atan2f": 36, "sqrtf": 37, "divf": 38, "sin_signf": 39,
+            "rng_f32": 40, "rng_range_f32": 41, "rng_range_pm1_f32": 42, "slope_capf": 43}
+
+
+def core32_math(fn, x, y=None):
+    """The float building blocks as the host build of the core evaluates them; same conventions as rtsr.device_math."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.ascontiguousarray(y if y is not None else np.ones_like(x), dtype=np.float64)
+    out = np.empty_like(x)
+    load().oracle_core32_math(MATH_F32[fn], x.ctypes.data_as(_D), y.ctypes.data_as(_D), x.size, out.ctypes.data_as(_D))
+    return out
+
+
+def f32_descs():
+    """[(array name, descriptor string)] of the product's f64 -> f32 converter."""
+    lib, out, k = load(), [], 0
+    while True:
+        name = C.c_char_p()
+        d = lib.oracle_f32_desc(k, C.byref(name))
+        if d is None:
+            return out
+        out.append((name.value.decode(), d.decode()))
+        k += 1
+
+
+def f32_convert(desc, raw64, elem64):
+    """The product's narrowing of the elements in raw64 (uint8 array, elem64 bytes each) -> (uint8 array, f32 element size);
+    (None, 0) when desc does not describe elem64 bytes."""
+    lib = load()
+    raw64 = np.ascontiguousarray(raw64, dtype=np.uint8)
+    n = raw64.size // elem64
+    e32 = lib.oracle_f32_convert(desc.encode(), raw64.ctypes.data, n, elem64, None)
+    if e32 == 0:
+        return None, 0
+    out = np.zeros(n * e32, dtype=np.uint8)
+    lib.oracle_f32_convert(desc.encode(), raw64.ctypes.data, n, elem64, out.ctypes.data)
+    return out, e32
+
+
+def flat_array(flat_arrays_ptr, name):
+    """The bytes of one array of the f64 flat scene -> (uint8 copy, element size)."""
+    n, e = C.c_int64(0), C.c_int64(0)
+    p = load().oracle_flat_array(flat_arrays_ptr, name.encode(), C.byref(n), C.byref(e))
+    if not p or n.value == 0:
+        return np.zeros(0, dtype=np.uint8), e.value
+    return np.ctypeslib.as_array((C.c_uint8 * (n.value * e.value)).from_address(p)).copy(), e.value
 
 
 def rt_math(fn, x, y=None):

@@ -72,6 +72,14 @@ static int check_scene(int32_t sid, int width, double aspect, int spp, bool refe
     if (oracle_lds_walk_render(&fs, &cam, &cfg, fs.motion32.empty() ? 0 : 1, 1, a3.data(), counts) != 0 ||
         memcmp(a3.data(), a2.data(), n * sizeof(double)) != 0) { fprintf(stderr, "scene %d: the LDS walk differs\n", sid); return 1; }
   }
+  if (!reference_bvh) {  // the float checker, both builds: the converter, the narrowed scene and the float core under the sanitizers
+    std::vector<double> f1(n), f2(n);
+    std::vector<uint8_t> q1(n), q2(n);
+    double one[3];
+    if (oracle_o2f_render(&fs, &cam, &cfg, 0, 1, 1, 0, f1.data(), q1.data()) != 0 ||
+        oracle_o2g_render(&fs, &cam, &cfg, 0, 1, 1, 0, f2.data(), q2.data()) != 0 ||
+        oracle_o2f_sample(&fs, &cam, &cfg, 0, 0, 0, one) != 0) { fprintf(stderr, "scene %d: O2f failed\n", sid); return 1; }
+  }
   printf("scene %3d%s: %zu nodes, %zu entries, %d x %d x %d spp: O1 == O2\n", sid, reference_bvh ? " (reference BVH rule)" : "", fs.nodes.size(),
          fs.entries.size(), cfg.image_width, cfg.image_height, spp);
   return 0;

@@ -672,9 +672,16 @@ def trace_kernel_name(kernel):
     return (lib.rtx_trace_kernel_name(kernel) or b"").decode()
 
 
+# rtx_device_math's float entries: evaluated by the f32 compilation on float(x), float(y), the float result widened.  The
+# three rng_* entries take a raw 64-bit draw as the BITS of x (and, for rng_range_f32, float lo / hi as the low / high word of y).
+DEVICE_MATH_F32 = {"sinf": 32, "cosf": 33, "logf": 34, "acosf": 35, "atan2f": 36, "sqrtf": 37, "divf": 38, "sin_signf": 39,
+                   "rng_f32": 40, "rng_range_f32": 41, "rng_range_pm1_f32": 42, "slope_capf": 43}
+
+
 def device_math(fn, x, y=None):
     """Evaluate one arithmetic building block on the GPU (see rtx_device_math)."""
     names = {"sin": 0, "cos": 1, "log": 2, "acos": 3, "atan2": 4, "tan": 5, "sqrt": 6, "div": 7, "muladd": 8, "floor": 9, "wide_key": 10}
+    names.update(DEVICE_MATH_F32)
     x = np.ascontiguousarray(x, dtype=np.float64)
     y = np.ascontiguousarray(y if y is not None else np.ones_like(x), dtype=np.float64)
     out = np.empty_like(x)

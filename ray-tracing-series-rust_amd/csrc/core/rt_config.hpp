@@ -55,7 +55,7 @@ inline T rt_load_uniform(const T* p) { return *p; }
 
 // The arithmetic type of the path.  double = the parity build (everything above: bit-identical to the CPU oracle);
 // float = the fast mode, compiled as a second translation unit into namespace rt32 (hip/render_f32.hip):
-// same source, `real` = float, judged statistically, never against the oracle's bits.
+// same source, `real` = float, held to the float CPU oracle (oracle/o2_flat_f32.cpp) and statistically to the f64 path.
 #ifndef RT_REAL
 #define RT_REAL double
 #endif

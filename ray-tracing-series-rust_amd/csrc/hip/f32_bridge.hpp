@@ -3,7 +3,7 @@
 // render.hip is compiled twice: as itself (arithmetic type rt::real = double: the bit-exact path every parity test
 // checks) and through render_f32.hip (rt::real = float, namespaces renamed to rt32 / rtx32: the statistical fast mode of
 // SURVEY.md 8f-4).  The f64 compilation owns the C ABI and its handle types; it hands the f32 compilation byte images of
-// the flat arrays already converted to the f32 layouts (f32_convert.inc) and gets back a device scene with the table of
+// the flat arrays already converted to the f32 layouts (host/f32_layout.hpp) and gets back a device scene with the table of
 // operations on it.  Each compilation fills one RtxSceneOps from the same lines of render.hip; a scene handle carries its
 // table, so the entry points call s->ops->X(s->device_scene, ...) and never ask which precision a scene has.
 // Nothing here mentions a type of either namespace, so both compilations see the same declarations.
@@ -12,19 +12,7 @@
 #include <cstddef>
 #include <cstdint>
 #include "../../../include/rtx_abi.h"
-
-enum RtxF32Array : int {
-  RTX32_SPHERES = 0, RTX32_MOVING_SPHERES, RTX32_RECTS, RTX32_TRIANGLES, RTX32_NODES, RTX32_NODES32, RTX32_REFS,
-  RTX32_ENTRIES, RTX32_TOP_LEVEL, RTX32_MATERIALS, RTX32_TEXTURES, RTX32_PERLINS, RTX32_IMAGES, RTX32_TEXELS,
-  RTX32_TOP_BOX32, RTX32_GRAVITY_SPHERES, RTX32_GRAVITY_Y, RTX32_MOTION32, RTX32_N_ARRAYS
-};
-struct RtxF32Blobs {
-  const void* data[RTX32_N_ARRAYS];
-  size_t bytes[RTX32_N_ARRAYS];
-  size_t elem_bytes[RTX32_N_ARRAYS];  // what the converter believes one element occupies; checked against sizeof on the other side
-  int32_t max_stack, n_bvh;
-  uint32_t features;
-};
+#include "../host/f32_blobs.hpp"  // RtxF32Array, RtxF32Blobs: the converted flat arrays as they cross the seam
 
 // A range of the samples of a render (render.hip knows it as SampleRange and says what the fields mean).
 struct RtxSampleRange {
@@ -54,3 +42,6 @@ struct RtxSceneOps {
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);
 const RtxSceneOps* rtx_f32_scene_ops();  // the f32 compilation's table, for the scenes rtx_f32_upload makes
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error
+// rtx_device_math's float entries (fn >= 32): one arithmetic building block as the f32 compilation evaluates it
+// (post_kernels.inc: k_device_math_f32); device pointers, asynchronous on the null stream.
+hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, long long n, double* d_out);

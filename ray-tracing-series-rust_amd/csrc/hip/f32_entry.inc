@@ -24,7 +24,7 @@ rtx_status rtx_f32_upload(const RtxF32Blobs* b, void** device_scene) {
             take_blob(*b, RTX32_IMAGES, &fs.images) && take_blob(*b, RTX32_TEXELS, &fs.texels) &&
             take_blob(*b, RTX32_TOP_BOX32, &fs.top_box32) && take_blob(*b, RTX32_GRAVITY_SPHERES, &fs.gravity_spheres) &&
             take_blob(*b, RTX32_GRAVITY_Y, &fs.gravity_y) && take_blob(*b, RTX32_MOTION32, &fs.motion32);
-  if (!ok) { set_error("rtx_scene_upload_f32: the f32 layout table of f32_convert.inc disagrees with the compiled structs"); return RTX_EINVAL; }
+  if (!ok) { set_error("rtx_scene_upload_f32: the f32 layout table of f32_layout.hpp disagrees with the compiled structs"); return RTX_EINVAL; }
   fs.max_stack = b->max_stack;
   fs.n_bvh = b->n_bvh;
   fs.features = b->features;
@@ -36,3 +36,8 @@ rtx_status rtx_f32_upload(const RtxF32Blobs* b, void** device_scene) {
 }
 
 const RtxSceneOps* rtx_f32_scene_ops() { return &scene_ops; }
+
+hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, long long n, double* d_out) {
+  hipLaunchKernelGGL(k_device_math_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, d_x, d_y, n, d_out);
+  return hipGetLastError();
+}

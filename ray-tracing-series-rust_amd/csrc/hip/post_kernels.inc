@@ -288,6 +288,39 @@ __global__ void k_device_math(int fn, const double* x, const double* y, long lon
   }
   out[k] = r;
 }
+#ifdef RTX_F32_TU
+// rtx_device_math's float entries (fn >= 32): the building blocks as THIS compilation evaluates them -- the five platform
+// functions behind rt_sin ..., the correctly rounded sqrt and division, and the three float RNG forms fed one raw 64-bit
+// draw (the bits of x[k]; for rng_range the bits of y[k] hold lo (low word) and hi (high word) as floats).  The float result
+// is handed back widened, which is exact.
+__global__ void k_device_math_f32(int fn, const double* x, const double* y, long long n, double* out) {
+  long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const float a = (float)x[k], b = (float)y[k];
+  const uint64_t raw = rt::f64_bits(x[k]), yb = rt::f64_bits(y[k]);
+  rt::Rng g;
+  g.s0 = raw; g.s1 = 0;  // rng_next_u64 returns s0 + s1: the next draw IS raw
+  union { uint32_t u; float f; } lo, hi;
+  lo.u = (uint32_t)yb; hi.u = (uint32_t)(yb >> 32);
+  float r;
+  switch (fn) {
+    case 32: r = rt::rt_sin(a); break;
+    case 33: r = rt::rt_cos(a); break;
+    case 34: r = rt::rt_log(a); break;
+    case 35: r = rt::rt_acos(a); break;
+    case 36: r = rt::rt_atan2(a, b); break;
+    case 37: r = rt::rt_sqrt(a); break;
+    case 38: r = a / b; break;
+    case 39: r = (float)rt::rt_sin_sign(a); break;
+    case 40: r = rt::rng_f64(g); break;
+    case 41: r = rt::rng_range(g, lo.f, hi.f); break;
+    case 43: r = rt::make_ray32(rt::make_ray(rt::v3(0, 0, 0), rt::v3(a, 1, 1), 0), rt::real(0.001)).ix; break;  // the slope cap (v_med3_f32) on 1 / a
+    case 42: r = rt::rng_range_pm1(g); break;
+    default: r = 0.0f; break;
+  }
+  out[k] = (double)r;
+}
+#endif
 __global__ void k_device_stream(unsigned long long seed, unsigned long long pixel, unsigned int sample, int n, double* out) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   rt::Rng g = rt::rng_for_sample(seed, pixel, sample);

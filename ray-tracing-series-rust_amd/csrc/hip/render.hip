@@ -1356,7 +1356,8 @@ rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t
   HIP_TRY(dx.upload(x, (size_t)n));
   HIP_TRY(dy.upload(y, (size_t)n));
   HIP_TRY(dout.alloc((size_t)n * sizeof(double)));
-  hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)fn, dx, dy, (long long)n, dout);
+  if (fn >= 32) HIP_TRY(rtx_f32_device_math((int)fn, dx, dy, (long long)n, dout));  // the float entries: the f32 compilation's
+  else hipLaunchKernelGGL(k_device_math, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (int)fn, dx, dy, (long long)n, dout);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return RTX_OK;

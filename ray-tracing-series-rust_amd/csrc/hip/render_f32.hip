@@ -6,10 +6,12 @@
 // adds / multiplies / FMAs issue in 2 clocks instead of 4 (issue-cost table) and sqrt / sin / cos / log in
 // 8 instead of a double-precision expansion.  What does not: the RNG stream (the same counter-based 64-bit generator;
 // a unit float is its top 24 bits), the order samples are added in (k_reduce_samples still sums doubles in sample
-// order), and the scene: the same flatten, converted field by field (f32_convert.inc).
+// order), and the scene: the same flatten, converted field by field (host/f32_layout.hpp).
 //
 // Images of this path are NOT bit-comparable with the reference's: tests/test_gpu_f32.py holds it to a statistical
-// bar against the f64 path instead.  Everything the C ABI promises about bit-exactness is about rtx_scene_upload.
+// bar against the f64 path, and tests/test_gpu_f32_parity.py to the float CPU oracle (oracle/o2_flat_f32.cpp: these
+// four defines in front of the host loop) -- bit for bit where no sample reaches a platform function, DESIGN.md 5.5.
+// Everything the C ABI promises about bit-exactness is about rtx_scene_upload.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
