@@ -136,8 +136,19 @@ struct Flattener {
         if (!collect_prims(c, refs, depth + 1, handles)) return false;
       return true;
     }
-    return fail("unsupported nesting: a Translate / RotateY / ConstantMedium INSIDE a BVH or inside a transformed or medium list "
-                "(an instanced sub-tree); primitives, RectPrisms, lists and BVHs of those may sit there");
+    // What is left is an instanced sub-tree.  Neither kind has an image of the reference's to reproduce that does not depend on
+    // its random split axes (bvh.rs:24; tests/test_instances_oracle.py pins both facts on the literal oracle), so the message
+    // says which spelling does.
+    if (o.kind == H_CONSTANT_MEDIUM)
+      return fail("unsupported nesting: a ConstantMedium INSIDE a BVH or inside a transformed or medium list (an instanced sub-tree). "
+                  "ConstantMedium::hit draws from the path's random stream whenever it is visited with a t_max that still reaches it "
+                  "(hit.rs:955-986), so under a BvhNode the number of draws depends on the visiting order of the reference's random "
+                  "tree: no culling structure reproduces that. List the medium in the world list");
+    return fail("unsupported nesting: a Translate / RotateY INSIDE a BVH or inside a transformed or medium list (an instanced sub-tree); "
+                "primitives, RectPrisms, lists and BVHs of those may sit there. RotateY::new keeps its child's UN-rotated box "
+                "(hit.rs:886) and BvhNode::hit culls by the union of its members' boxes (bvh.rs:99), so which parts of a rotated "
+                "member the reference clips depends on its random split axes (bvh.rs:24): there is no one image to reproduce. "
+                "Wrap the BVH, not its members, or list every wrapped object in the world list");
   }
 
   // Reference bounding boxes (hit.rs bounding_box impls) of one flattened primitive.
