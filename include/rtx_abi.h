@@ -92,6 +92,13 @@ rtx_handle rtx_rect_prism(rtx_builder* b, const double p0[3], const double p1[3]
 rtx_handle rtx_hittable_list_new(rtx_builder* b);                                                       /* hit.rs:646-648 */
 rtx_status rtx_hittable_list_add(rtx_builder* b, rtx_handle list, rtx_handle object);                   /* hit.rs:650-652 */
 rtx_handle rtx_bvh_from_list(rtx_builder* b, rtx_handle list, double time0, double time1);              /* bvh.rs:85-93   */
+/* An extension (no reference type): the HittableList of the list's members -- for every ray the hit of scanning them in
+ * order, later member winning an exact tie (hit.rs:660-690) -- culled by a tree over the members' TRUE boxes (a RotateY
+ * member's rotated box, which hit.rs:886 discards).  May stand where a slot of the world list may: in the world HittableList or
+ * a list nested in it.  Members: primitives, RectPrisms, lists, BvhNodes of those, and up to 4 Translate / RotateY around one;
+ * no ConstantMedium, nothing that holds a Moving- or GravitySphere, no other instance tree (rtx_flatten: RTX_EUNSUPPORTED).
+ * The frame equals, bit for bit, that of the same world with the members written into the list at this position. */
+rtx_handle rtx_instance_bvh_from_list(rtx_builder* b, rtx_handle list);
 rtx_handle rtx_translate(rtx_builder* b, const double offset[3], rtx_handle object);                    /* hit.rs:793-798 */
 rtx_handle rtx_rotate_y(rtx_builder* b, double angle_degrees, rtx_handle object);                       /* hit.rs:843-888 */
 rtx_handle rtx_constant_medium(rtx_builder* b, const double rgb[3], double density, rtx_handle boundary); /* hit.rs:945-951 */
@@ -429,6 +436,15 @@ typedef struct RtxLightInfo {
 } RtxLightInfo;
 /* Host only: no GPU needed.  The census of the light table above. */
 rtx_status rtx_flat_lights(const rtx_flat* f, RtxLightInfo* out);
+/* Host only: the census of a flattened scene's instance trees (rtx_instance_bvh_from_list).  A tree of fewer than two members
+ * leaves no tree behind (its member is a plain slot) and is not counted. */
+typedef struct RtxInstanceInfo {
+  int32_t n_trees;     /* instance trees of two or more members */
+  int32_t n_members;   /* their member slots, summed */
+  int32_t n_nodes;     /* nodes of their culling trees, summed */
+  int32_t max_depth;   /* the deepest of those trees (stack entries its walk can hold) */
+} RtxInstanceInfo;
+rtx_status rtx_flat_instances(const rtx_flat* f, RtxInstanceInfo* out);
 /* rtx_render with options: opt NULL or light_sampling = 0 is rtx_render exactly.  stats may be NULL.  A light_sampling other
  * than 0 / 1 or a non-zero reserved word is RTX_EINVAL before any device call; an f32 scene with light_sampling = 1 is
  * RTX_EUNSUPPORTED.  Blocking, host output buffers. */

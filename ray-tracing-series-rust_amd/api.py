@@ -111,6 +111,10 @@ class RtxLightInfo(C.Structure):
                 ("n_unsampled_emitters", C.c_int32), ("total_area", C.c_double)]
 
 
+class RtxInstanceInfo(C.Structure):
+    _fields_ = [("n_trees", C.c_int32), ("n_members", C.c_int32), ("n_nodes", C.c_int32), ("max_depth", C.c_int32)]
+
+
 def _integrator_options(light_sampling):
     return RtxIntegratorOptions(1 if light_sampling else 0)
 
@@ -150,6 +154,7 @@ ABI = {
     "rtx_hittable_list_new": (_H, [_VP]),
     "rtx_hittable_list_add": (C.c_int32, [_VP, _H, _H]),
     "rtx_bvh_from_list": (_H, [_VP, _H, C.c_double, C.c_double]),
+    "rtx_instance_bvh_from_list": (_H, [_VP, _H]),
     "rtx_translate": (_H, [_VP, _D3, _H]),
     "rtx_rotate_y": (_H, [_VP, C.c_double, _H]),
     "rtx_constant_medium": (_H, [_VP, _D3, C.c_double, _H]),
@@ -201,6 +206,7 @@ ABI = {
     "rtx_device_denoise": (C.c_int32, [_D3, _D3, _F3, _F3, C.c_int32, C.c_int32, C.POINTER(RtxDenoiseParams), _D3,
                                        C.POINTER(C.c_uint8)]),
     "rtx_flat_lights": (C.c_int32, [_VP, C.POINTER(RtxLightInfo)]),
+    "rtx_flat_instances": (C.c_int32, [_VP, C.POINTER(RtxInstanceInfo)]),
     "rtx_render_ex": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxIntegratorOptions),
                                   C.POINTER(RtxFrame), C.POINTER(RtxRenderStats)]),
     "rtx_progressive_create_ex": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxShard),
@@ -378,6 +384,10 @@ class Builder:
     def bvh_from_list(self, lst, time0, time1):
         return _handle(lib.rtx_bvh_from_list(self._p, lst, time0, time1))
 
+    def instance_bvh(self, lst):
+        """An instance tree (rtx_instance_bvh_from_list): the list of lst's members, culled by their true transformed boxes."""
+        return _handle(lib.rtx_instance_bvh_from_list(self._p, lst))
+
     def translate(self, offset, obj):
         return _handle(lib.rtx_translate(self._p, _v3(offset), obj))
 
@@ -445,6 +455,12 @@ class Flat:
         info = RtxLightInfo()
         _check(lib.rtx_flat_lights(self._p, C.byref(info)))
         return {n: getattr(info, n) for n, _ in RtxLightInfo._fields_}
+
+    def instances(self):
+        """Census of the instance trees (rtx_flat_instances): n_trees, n_members, n_nodes, max_depth."""
+        info = RtxInstanceInfo()
+        _check(lib.rtx_flat_instances(self._p, C.byref(info)))
+        return {n: getattr(info, n) for n, _ in RtxInstanceInfo._fields_}
 
     def top_level_kinds(self):
         """Entry kinds of the flattened world list, in HittableList order (rtx_flat_top_level_kind)."""

@@ -23,6 +23,18 @@
 // A zero direction component gives i32 = inf and NaN/inf slab values; fminf/fmaxf ignore NaN so
 // that axis simply stops culling (still conservative).  Host and device need not agree bit for bit
 // here -- any conservative answer gives the same final hit -- so FMA use is fine.
+//
+// Boxes of transformed members (instance trees, host/flatten.cpp: member_world_box).  There the f64 decision is taken in the
+// member's own frame, on a ray that went through up to RT_MAX_XFORM_OPS Translate / RotateY ops, while the box that culls it
+// stands in world space: the rotated corners' min / max plus the offsets, computed in f64.  Two more errors enter:
+//   * the box: each rotation is two products and a sum, each translation a sum: <= 3 * 2^-53 relative to the largest
+//     magnitude M met on the way, per op;
+//   * the ray: xform_ray rounds the same way, so the point the member test accepts lies within about 12 * 2^-53 (|o| + t|d| + M)
+//     of a point of the exact member, mapped to world space.
+// The first is covered on the box: every plane is pushed out by M * 2^-22, at least two f32 ulps of the plane whatever its own
+// value (rounding outward alone gives an exactly representable plane no slack) and 2^31 times the f64 error of the ops.  The
+// second scales with the ray, not with the box, and is covered where the ray's own errors are: the widening above is
+// 2^-21 (|tn| + |tf|) + 2E in t, i.e. at least 2^-21 (|o| + t|d|) in space, 2^29 times larger.
 #pragma once
 #include "flat_types.hpp"
 

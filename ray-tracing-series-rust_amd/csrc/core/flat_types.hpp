@@ -101,13 +101,20 @@ RT_HD int32_t make_leaf(uint32_t first, uint32_t count) {
   return (int32_t)(0x80000000u | (first << 3) | (count - 1u));
 }
 
-// ---- entries: what a HittableList slot can hold ----------------------------------
+// ---- entries: what a HittableList slot can hold (and, last, the record of an instance tree over a run of slots) ----
 enum EntryKind : int32_t {
   ENTRY_PRIM = 0,    // a = PrimRef
   ENTRY_GROUP = 1,   // ordered list semantics (HittableList / RectPrism): a = first ref, b = count
   ENTRY_BVH = 2,     // a = root node, b = first ref of its prim-ref list, c = ref count; f[0], f[1] = time0, time1 of from_list
   ENTRY_XFORM = 3,   // a = child entry (PRIM/GROUP/BVH), b = number of ops (outermost first, <= RT_MAX_XFORM_OPS)
   ENTRY_MEDIUM = 4,  // a = boundary entry (PRIM/GROUP/BVH/XFORM), b = phase material; f[0] = -1/density
+  // An instance tree (rtx_instance_bvh_from_list; an extension, not a reference type): a culling tree over a run of
+  // consecutive top-level slots.  a = root node, b = first slot, c = number of slots.  Never a slot itself: the members are
+  // ordinary slots, in list order, and these records sit at the END of the entry array in ascending order of `b`, closed by
+  // one more record with b = INT32_MAX (SceneView::inst_entries is the index of the first).  The tree's nodes live in
+  // nodes / nodes32 like any BVH's; its leaves hold ONE slot each and leaf_first() of a leaf code is that slot's index in
+  // the world list.  A scan that ignores these records visits every member and finds the same hit.
+  ENTRY_INSTANCE = 5,
 };
 enum XformOp : int32_t { XFORM_TRANSLATE = 0, XFORM_ROTATE_Y = 1 };
 #define RT_MAX_XFORM_OPS 4  // Translate / RotateY wrappers around one object (hit.rs:787-936); deeper chains: RTX_EUNSUPPORTED
@@ -177,8 +184,8 @@ struct SceneView {
   const FlatNode32* nodes32;
   const FlatMotion32* motion32;  // null unless a BVH holds MovingSpheres
   const PrimRef* refs;
-  const FlatEntry* entries;
-  const int32_t* top_level;  // entry indices, in HittableList order
+  const FlatEntry* entries;  // the slots' entries and what they refer to; the ENTRY_INSTANCE records close the array (inst_entries)
+  const int32_t* top_level;  // entry indices, in HittableList order (the members of an instance tree are slots like any other)
   const FlatMaterial* materials;
   const FlatTexture* textures;
   const FlatPerlin* perlins;
@@ -191,9 +198,9 @@ struct SceneView {
   const FlatGravitySphere* gravity_spheres;
   const real* gravity_y;  // the height tables of all gravity spheres, one after another
   int32_t n_top_level;
-  int32_t max_stack;  // deepest traversal stack any BVH of this scene needs
+  int32_t max_stack;  // deepest traversal stack any walk of this scene needs (an instance tree's walk with its deepest member BVH above it)
   uint32_t features;  // Feature bits the scene can reach
-  uint32_t pad;       // padding to a multiple of 8 bytes
+  uint32_t inst_entries;  // index in `entries` of the first ENTRY_INSTANCE record, 0: the world has no instance tree
 };
 
 // Per-render constants.
@@ -218,7 +225,11 @@ enum Feature : uint32_t {
   F_GRAVITY_SPHERE = 1u << 17,
   F_MEDIUM_GENERAL = 1u << 18,  // a medium whose boundary is anything but one plain static sphere (a box, a BVH, a moved object)
   F_MEDIUM_SPHERE = 1u << 19,   // a medium whose boundary is one plain static sphere (Book-2's smoke ball and fog)
-  F_ALL = (1u << 20) - 1u,
+  // The world list holds an instance tree (ENTRY_INSTANCE).  Unlike every other bit this one compiles a FASTER path in, not a
+  // reachable one: code without it scans the members as the plain slots they are.  F_ALL carries it (the CPU checkers and the
+  // host tools walk the trees); the device presets name it explicitly (hip/trace_basic.inc), so that no existing kernel changes.
+  F_INSTANCE = 1u << 20,
+  F_ALL = (1u << 21) - 1u,
 };
 
 // Work counters for the algorithmic-bytes model.

@@ -503,6 +503,80 @@ RT_HD void xform_record_chain(const FlatXformOp* ops, int nops, const Ray& outer
   }
 }
 
+// ---- instance trees (ENTRY_INSTANCE, core/flat_types.hpp) ----------------------------------------------------------
+// A stack handed to a member's own BVH walk while the slot walk's entries lie below it on the same storage: empty means
+// "down to where the slot walk left it", and the member walk's reset() must not drop what lies below.
+template <class STACK>
+struct StackAbove {
+  STACK& s;
+  int floor;
+  RT_HD void reset() {}
+  RT_HD void push(int32_t v) { s.push(v); }
+  RT_HD int32_t pop() { return s.pop(); }
+  RT_HD bool empty() const { return s.n == floor; }
+};
+
+// One member slot offered to the running hit of world_hit: the per-entry code of the list scan for a solid entry (members
+// are never media), with per-lane loads -- the lanes of a wave are at different members -- and the list's tie rule made
+// explicit: the scan accepts t == closest_so_far because a LATER slot wins a tie (hit.rs:676-680); a walk meets the members in
+// any order, so on a tie the higher slot wins, whichever was seen first.
+template <uint32_t F, bool COUNT, class STACK, bool SLOT>
+RT_HD void instance_offer_slot(const SceneView& sv, int32_t slot, const Ray& r, real t_min, real* closest_so_far, bool* hit_anything,
+                               int32_t* win_slot, HitRecord* rec, STACK& stack, TraceCounters* cnt, int32_t* hit_slot) {
+  const FlatEntry* solid = &sv.entries[sv.top_level[slot]];
+  const bool is_xform = (F & F_XFORM) && solid->kind == ENTRY_XFORM;
+  Ray rq = r;
+  const FlatEntry* geom = solid;
+  int nops = 0;
+  if (is_xform) {
+    nops = solid->b;
+    geom = &sv.entries[solid->a];
+    for (int k = 0; k < nops; ++k) rq = xform_ray(solid->ops[k], rq);
+  }
+  Closest best;
+  StackAbove<STACK> above = {stack, stack.n};
+  geom_closest<F, COUNT>(sv, *geom, rq, t_min, *closest_so_far, &best, above, cnt);
+  if (!best.hit) return;
+  if (*hit_anything && best.t == *closest_so_far && slot < *win_slot) return;
+  prim_finalize<F>(sv, best.ref, rq, best.t, rec);
+  if (is_xform) xform_record_chain(solid->ops, nops, r, rq, rec);
+  *hit_anything = true;
+  *closest_so_far = rec->t;
+  *win_slot = slot;
+  if (SLOT) *hit_slot = slot;
+}
+
+// The members of one instance tree offered to the running hit: the tree is walked with the f32 culling ray of the WORLD ray
+// against the members' world-space boxes (near child first), every candidate member goes through instance_offer_slot.  The
+// result is that of scanning the member slots in order (see there); the boxes only decide which members are asked.
+template <uint32_t F, bool COUNT, class STACK, bool SLOT>
+RT_HD void instance_walk(const SceneView& sv, int32_t root, const Ray& r, real t_min, real* closest_so_far, bool* hit_anything,
+                         int32_t* win_slot, HitRecord* rec, STACK& stack, TraceCounters* cnt, int32_t* hit_slot) {
+  const Ray32 q = make_ray32(r, t_min);
+  const uint32_t dir_neg = ray_dir_neg(r);
+  stack.reset();
+  int32_t cur = root;
+  for (;;) {
+    if (!node_child_is_leaf(cur)) {
+      const FlatNode32& n = sv.nodes32[cur];
+      if (COUNT) cnt->box_tests += 2;
+      const int first = (int)((dir_neg >> (uint32_t)n.axis) & 1u);
+      const float t_max32 = cull_round_up(*closest_so_far);
+      const bool hf = cull32_may_hit(n.lo[first], n.hi[first], q, t_max32);
+      const bool hs = cull32_may_hit(n.lo[1 - first], n.hi[1 - first], q, t_max32);
+      const int32_t cf = n.child[first], cs = n.child[1 - first];
+      if (hf) { cur = cf; if (hs) stack.push(cs); continue; }
+      if (hs) { cur = cs; continue; }
+    } else {
+      const uint32_t f = leaf_first(cur), k = leaf_count(cur);
+      for (uint32_t i = 0; i < k; ++i)
+        instance_offer_slot<F, COUNT, STACK, SLOT>(sv, (int32_t)(f + i), r, t_min, closest_so_far, hit_anything, win_slot, rec, stack, cnt, hit_slot);
+    }
+    if (stack.empty()) break;
+    cur = stack.pop();
+  }
+}
+
 // The world: HittableList::hit over the ordered top-level table (hit.rs:660-690), with
 // Translate / RotateY (hit.rs:802-823, 892-931) and ConstantMedium (hit.rs:955-986) handled
 // around ONE geometry query site so the traversal code exists once in the kernel.
@@ -523,7 +597,20 @@ RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, 
   const bool cull_prims = (F & F_PRIM_ENTRY) && sv.top_box32 != nullptr;
   Ray32 q32 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (cull_prims) q32 = make_ray32(r, t_min);
+  // instance trees: the next range of member slots a tree covers (wave-uniform, like the scan itself)
+  int32_t inst_cur = 0, inst_first = 0x7fffffff, win_slot = -1;
+  if ((F & F_INSTANCE) && sv.inst_entries != 0u) {
+    inst_cur = (int32_t)sv.inst_entries;
+    inst_first = rt_load_uniform(&sv.entries[inst_cur].b);
+  }
   for (int32_t i = 0; i < sv.n_top_level; ++i) {
+    if ((F & F_INSTANCE) && i == inst_first) {
+      const int32_t root = rt_load_uniform(&sv.entries[inst_cur].a), n_slots = rt_load_uniform(&sv.entries[inst_cur].c);
+      inst_first = rt_load_uniform(&sv.entries[++inst_cur].b);
+      instance_walk<F, COUNT, STACK, SLOT>(sv, root, r, t_min, &closest_so_far, &hit_anything, &win_slot, rec, stack, cnt, hit_slot);
+      i += n_slots - 1;
+      continue;
+    }
     // the table walk is wave-uniform: entries are fetched once per wave (rt_load_uniform)
     const FlatEntry e_rec = rt_load_uniform(&sv.entries[rt_load_uniform(&sv.top_level[i])]);
     const FlatEntry* e = &e_rec;
@@ -588,6 +675,7 @@ RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, 
     }
     hit_anything = true;
     closest_so_far = rec->t;
+    if (F & F_INSTANCE) win_slot = i;
     if (SLOT) *hit_slot = i;
   }
   return hit_anything;

@@ -95,6 +95,7 @@ rtx_status rtx_hittable_list_add(rtx_builder* b, rtx_handle list, rtx_handle obj
   return RTX_OK;
 }
 rtx_handle rtx_bvh_from_list(rtx_builder* b, rtx_handle list, double t0, double t1) { NEED_BUILDER(b); return checked(b, b->graph.bvh_from_list(list, t0, t1)); }
+rtx_handle rtx_instance_bvh_from_list(rtx_builder* b, rtx_handle list) { NEED_BUILDER(b); return checked(b, b->graph.instance_bvh_from_list(list)); }
 rtx_handle rtx_translate(rtx_builder* b, const double offset[3], rtx_handle obj) { NEED_BUILDER(b); if (!offset) { set_error("NULL offset"); return -1; } return checked(b, b->graph.translate(offset, obj)); }
 rtx_handle rtx_rotate_y(rtx_builder* b, double angle, rtx_handle obj) { NEED_BUILDER(b); return checked(b, b->graph.rotate_y(angle, obj)); }
 rtx_handle rtx_constant_medium(rtx_builder* b, const double rgb[3], double density, rtx_handle boundary) {
@@ -232,6 +233,14 @@ rtx_status rtx_flat_lights(const rtx_flat* f, RtxLightInfo* o) {
   o->n_sphere_lights = t.n_sphere;
   o->n_unsampled_emitters = t.n_unsampled;
   o->total_area = t.total_area;
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_instances(const rtx_flat* f, RtxInstanceInfo* o) {
+  if (!f || !o) { set_error("rtx_flat_instances: NULL argument"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  o->n_trees = s.n_instance_trees; o->n_members = s.n_instance_members;
+  o->n_nodes = s.n_instance_nodes; o->max_depth = s.instance_depth;
   return RTX_OK;
 }
 

@@ -129,7 +129,7 @@ struct WorldPlan {
   const WorldDesc* desc = nullptr;  // per-slot records of the world list
   uint32_t mat_lds = 0, tex_lds = 0;  // material / texture records it copies into LDS
   uint32_t perlin_lds = 0;          // Perlin tables it copies into LDS
-  int blocks_per_cu[4][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}};  // [book2 preset / any / all incl. gravity spheres / no sphere media][binary / wide]
+  int blocks_per_cu[5][2] = {{1, 1}, {1, 1}, {1, 1}, {1, 1}, {1, 1}};  // [book2 preset / any / all incl. gravity spheres / no sphere media / instance trees (binary only)][binary / wide]
 };
 
 // One k_trace_lds variant fitted into the LDS of a block (fit_lds).
@@ -574,6 +574,9 @@ static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
   const bool for_world = !(ds->vote.ok && preset < 2) && preset >= 1;
   bool want_wide = (for_vote && fs.nodes.size() >= 4096) || (for_world && fs.nodes.size() >= 256);
   if (ds->sw.wide >= 0) want_wide = (for_vote || for_world) && ds->sw.wide != 0 && !fs.nodes.empty();
+  // a world with an instance tree keeps the binary tree: the slot walk and the member walks above it share one node format
+  // and one stack (trace_world.inc), and a wide collapse of a slot tree has no leaf format for slots
+  if (fs.features & rt::F_INSTANCE) want_wide = false;
   if (!want_wide) return RTX_OK;
   std::vector<FlatNode4> wide(fs.nodes.size());
   memset(wide.data(), 0, wide.size() * sizeof(FlatNode4));
@@ -627,6 +630,7 @@ static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
 #define WORLD_OCC(I, FEAT) if ((n = occupancy(wd ? k_trace_world<FEAT, true, WORLD_WPS> : k_trace_world<FEAT, false, WORLD_WPS>, wl)) > 0) p.blocks_per_cu[I][wd] = n
     WORLD_OCC(0, P_BOOK2); WORLD_OCC(1, P_ANY); WORLD_OCC(2, P_ALL); WORLD_OCC(3, P_NO_SPHERE_MEDIA);
 #undef WORLD_OCC
+    if (wd == 0 && (n = occupancy(k_trace_world<P_INST, false, WORLD_WPS>, wl)) > 0) p.blocks_per_cu[4][0] = n;
   }
   return RTX_OK;
 }
@@ -642,7 +646,8 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   const size_t lds = stack_bytes(levels) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real) +
                      (size_t)p.perlin_lds * sizeof(rt::FlatPerlin) + (size_t)p.mat_lds * sizeof(rt::FlatMaterial) +
                      (size_t)p.tex_lds * sizeof(rt::FlatTexture);
-  const int family = has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1));
+  const bool inst = (a.feat & rt::F_INSTANCE) != 0;  // (never wide: plan_wide)
+  const int family = inst ? 4 : (has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1)));
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[family][wide ? 1 : 0]);
   const rt::SceneView& v = ds->view;
 #define LAUNCH_WORLD3(FEAT, WIDEF, DIAGF, MAP)                                                                               \
@@ -658,7 +663,11 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
     static const char* const names[8] = {"node_step", "leaf_step", "sweep", "shade(lean)", "regen", "direct_entry(all)", "direct_entry(run)", "shade(rare)"};
     return run_diag(ds, a.stream, [&] { LAUNCH_WORLD3(P_BOOK2, true, true, a.sm); }, "world_diag", 18, names, 8, h);
   }
-  if (has_gravity) { LAUNCH_WORLD(P_ALL); }  // the bouncing-ball scene: the instantiation that carries GravitySphere code
+  if (inst) {
+    if (wide) { set_error("render: a world with an instance tree has no 4-wide tree"); return RTX_EUNSUPPORTED; }
+    LAUNCH_WORLD2(P_INST, false);
+  }
+  else if (has_gravity) { LAUNCH_WORLD(P_ALL); }  // the bouncing-ball scene: the instantiation that carries GravitySphere code
   else if (book2) { LAUNCH_WORLD(P_BOOK2); }
   else if (no_sphere_media) { LAUNCH_WORLD(P_NO_SPHERE_MEDIA); }
   else { LAUNCH_WORLD(P_ANY); }
@@ -788,10 +797,13 @@ static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), a.stack_lds, \
                      a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, ds->ws.counters)
 #define LAUNCH_SIMPLE(FEAT) with_map(a, [&](auto map) { LAUNCH_SIMPLE2(FEAT, map); })
-  if constexpr (COUNT) { LAUNCH_SIMPLE2(P_ALL, a.sm); }  // (counting renders are never adaptive)
-  else {
+  const bool inst = (a.feat & rt::F_INSTANCE) != 0;
+  if constexpr (COUNT) {  // (counting renders are never adaptive)
+    if (inst) { LAUNCH_SIMPLE2(P_INST, a.sm); } else { LAUNCH_SIMPLE2(P_ALL, a.sm); }
+  } else {
     if (a.preset == 0) { LAUNCH_SIMPLE(P_SPHERES); }
     else if (a.preset == 1) { LAUNCH_SIMPLE(P_MESH); }
+    else if (inst) { LAUNCH_SIMPLE(P_INST); }
     else { LAUNCH_SIMPLE(P_ALL); }
   }
 #undef LAUNCH_SIMPLE
@@ -804,7 +816,7 @@ static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
 // everything.  Persistent: as many blocks as are resident, at most one per TRACE_CHUNK items.
 static rtx_status launch_nee(const DeviceScene* ds, const PassArgs& a) {
   HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
-  const int preset = (a.feat & ~P_MESH_ROOM) == 0 ? 0 : ((a.feat & rt::F_GRAVITY_SPHERE) ? 2 : 1);
+  const int preset = (a.feat & rt::F_INSTANCE) ? 3 : ((a.feat & ~P_MESH_ROOM) == 0 ? 0 : ((a.feat & rt::F_GRAVITY_SPHERE) ? 2 : 1));
 #define LAUNCH_NEE(FEAT, MAP)                                                                                                   \
   do {                                                                                                                          \
     const int nb = occupancy(k_trace_nee<FEAT, decltype(MAP)>, a.stack_lds);                                                    \
@@ -816,6 +828,7 @@ static rtx_status launch_nee(const DeviceScene* ds, const PassArgs& a) {
   with_map(a, [&](auto map) {
     if (preset == 0) LAUNCH_NEE(P_MESH_ROOM, map);
     else if (preset == 1) LAUNCH_NEE(P_ANY, map);
+    else if (preset == 3) LAUNCH_NEE(P_INST, map);
     else LAUNCH_NEE(P_ALL, map);
   });
 #undef LAUNCH_NEE
@@ -1195,8 +1208,12 @@ static rtx_status features_impl(DeviceScene* ds, const RtxCamera* cam, const Rtx
   const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
   if (stack_bytes(stack_levels) > 64 * 1024) { set_error("features: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
   const uint32_t grid = grid_size((uint32_t)npix, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_ALL>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
-                     rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
+  if (ds->view.features & rt::F_INSTANCE)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_INST>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
+                       rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_ALL>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
+                       rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
   HIP_TRY(hipGetLastError());
   return RTX_OK;
 }
@@ -1237,6 +1254,7 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   v.n_top_level = (int32_t)fs.top_level.size();
   v.max_stack = fs.max_stack;
   v.features = fs.features;
+  v.inst_entries = fs.view().inst_entries;
   // GravitySphere::get_center (hit.rs:369-391) leaves its stored trajectory for a brute-force loop of (time - time0) / 0.001
   // steps, per sphere test, per ray: a shutter far beyond the table is an effectively unbounded kernel.  Renders are limited to
   // RTX_GRAVITY_SLACK_S seconds past the shortest table (10 000 loop steps); rtx_render* return RTX_EINVAL beyond.

@@ -11,8 +11,12 @@ constexpr uint32_t P_MESH = rt::F_SPHERE | rt::F_RECT | rt::F_TRIANGLE | rt::F_P
                             rt::F_BVH | rt::F_LAMBERTIAN | rt::F_METAL | rt::F_DIELECTRIC | rt::F_LIGHT;
 // P_MESH without spheres, ordered groups and dielectrics: the dragon room exactly.
 constexpr uint32_t P_MESH_ROOM = rt::F_RECT | rt::F_TRIANGLE | rt::F_PRIM_ENTRY | rt::F_BVH | rt::F_LAMBERTIAN | rt::F_METAL | rt::F_LIGHT;
-constexpr uint32_t P_ALL = rt::F_ALL;                            // everything, GravitySphere included (k_trace_simple, scene 8)
-constexpr uint32_t P_ANY = rt::F_ALL & ~rt::F_GRAVITY_SPHERE;    // any world of the catalogue's BASELINE scenes
+constexpr uint32_t P_ALL = rt::F_ALL & ~rt::F_INSTANCE;          // everything, GravitySphere included (k_trace_simple, scene 8)
+constexpr uint32_t P_ANY = P_ALL & ~rt::F_GRAVITY_SPHERE;        // any world of the catalogue's BASELINE scenes
+// P_ALL plus the walk of instance trees: the preset of every world that holds one (a preset without F_INSTANCE scans the
+// members as plain slots -- the same frame, O(members) per ray).  Its own preset so that no P_ALL kernel carries the walk.
+constexpr uint32_t P_INST = rt::F_ALL;
+static_assert(P_ALL == (1u << 20) - 1u, "the presets of worlds without instance trees are what they were before F_INSTANCE");
 
 // Straightforward form: grid-stride over the pass's (sample, pixel) index space (pass_items.inc), one whole
 // path per loop iteration.

@@ -111,6 +111,17 @@ static std::vector<WorldDesc> build_world_desc(const FlatScene& fs) {
       if (memcmp(&sa.cx, &sb.cx, 4 * sizeof(rt::real)) == 0) out[k].flags |= WD_PAIR;  // centre and radius, bit for bit
     }
   }
+  // The instance trees, BEHIND the slots' records: record n_top + k has g_a = first slot, g_b = number of slots, medium_mat =
+  // root node of tree k, in ascending order of first slot; one more with g_a = INT32_MAX closes the table (it is what
+  // core/flat_types.hpp's ENTRY_INSTANCE records say).  Only the P_INST instantiation reads past the slots.
+  if (fs.features & rt::F_INSTANCE)
+    for (const rt::FlatEntry& e : fs.entries)
+      if (e.kind == rt::ENTRY_INSTANCE) {
+        WorldDesc d;
+        memset(&d, 0, sizeof(d));
+        d.g_a = e.b; d.g_b = e.c; d.medium_mat = e.a;
+        out.push_back(d);
+      }
   return out;
 }
 // waves per SIMD k_trace_world is compiled for: 3 (168 VGPRs) measured best in f64 (2: 423, 4: 344 against 573 Msamples/s on
@@ -130,7 +141,8 @@ __device__ __forceinline__ rt::FlatXformOp load_op_uniform(const rt::FlatXformOp
   return o;
 }
 
-template <uint32_t F>
+// UNIFORM: G is the same for every lane (the sweep); false: each lane has its own (a member of an instance tree).
+template <uint32_t F, bool UNIFORM = true>
 __device__ __forceinline__ bool direct_closest(const rt::SceneView& sv, const rt::FlatEntry& G, const rt::Ray& r, rt::real t_min,
                                                rt::real t_max, rt::real* t_out, rt::PrimRef* ref_out) {
   if ((F & rt::F_PRIM_ENTRY) && (G.kind == rt::ENTRY_PRIM || !(F & rt::F_GROUP))) {
@@ -141,7 +153,7 @@ __device__ __forceinline__ bool direct_closest(const rt::SceneView& sv, const rt
   if (F & rt::F_GROUP) {  // HittableList::hit: in order, shrinking closest_so_far, later wins ties
     rt::real best = t_max;
     for (int32_t i = 0; i < G.b; ++i) {
-      const rt::PrimRef ref = dev_load_uniform(&sv.refs[G.a + i]);
+      const rt::PrimRef ref = UNIFORM ? dev_load_uniform(&sv.refs[G.a + i]) : sv.refs[G.a + i];
       rt::real t;
       if (rt::prim_t<F, false>(sv, ref, r, t_min, best, &t, nullptr)) { best = t; hit = true; *ref_out = ref; }
     }
@@ -219,6 +231,15 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
   uint32_t first_ref = 0;
   rt::Closest best;
   best.t = 0.0; best.ref = WALK_NO_REF; best.order = 0; best.hit = false;  // (.hit is not maintained in this kernel: WALK_NO_REF, trace_vote.inc)
+  // Instance trees (P_INST only; DESIGN.md 8.1).  A lane whose scan reaches the first slot of a tree walks the SLOT tree with
+  // the same node steps as any BVH (im = 1: its culling ray is the path's own, `closest` its t_max); a leaf of that tree is one
+  // member slot, which the lane visits on its own: record by a per-lane load, ray transformed per lane, a primitive or group
+  // tested in place, a BVH member walked ABOVE the slot walk on the same stack (im = 2: one WALK_DONE marker between the two, so
+  // the member walk ends like any walk and the lane then pops the slot walk's next item).  Members are met in tree order, so the
+  // list's tie rule is spelled out: on t == closest the higher slot wins (core/geometry.hpp: instance_offer_slot).
+  constexpr bool INST = (F & rt::F_INSTANCE) != 0;
+  static_assert(!(INST && WIDE), "worlds with instance trees walk the binary tree");
+  [[maybe_unused]] uint32_t im = 0u;  // 0: no instance walk, 1: in the slot tree, 2: in a member's BVH (walk_root holds the member's slot)
 
   auto slot_ray = [&]() {
     return rt::make_ray(rt::v3(slot[0 * TRACE_BLOCK], slot[1 * TRACE_BLOCK], slot[2 * TRACE_BLOCK]),
@@ -244,6 +265,56 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     else { closest = RT_INFINITY; hit_any = false; ei = 0; ph = 0; stage = WS_ENTRY; }
   };
 
+  // a member's BVH walk has ended: take its hit by the list's rule, go on with the slot walk
+  auto close_member = [&]() {
+    if constexpr (INST) if (im == 2u && cur == WALK_DONE) {
+      if (best.ref != WALK_NO_REF && !(hit_any && best.t == closest && walk_root < win_e)) { closest = best.t; win_e = walk_root; win_ref = best.ref; hit_any = true; }
+      q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
+      dir_neg = rt::ray_dir_neg(ps.ray);
+      t_max32 = rt::cull_round_up(closest);
+      cur = stack.pop();
+      im = 1u;
+    }
+  };
+  // a leaf of the slot tree: one member, visited by this lane alone
+  auto visit_member = [&]() {
+    if constexpr (INST) {
+    const int32_t ms = (int32_t)rt::leaf_first(cur);
+    const WorldDesc* W = &wdesc[ms];  // per-lane
+    const int32_t wflags = W->flags;
+    const rt::real t_min = rt::ray_t_min(ps.ray);
+    rt::Ray rq = ps.ray;
+    if ((F & rt::F_XFORM) && (wflags & WD_XFORM)) {
+      const int n_ops = W->n_ops;
+      for (int k = 0; k < n_ops; ++k) rq = rt::xform_ray(W->ops[k], rq);
+    }
+    rt::FlatEntry G;
+    G.kind = W->g_kind; G.a = W->g_a; G.b = W->g_b;
+    if ((F & rt::F_BVH) && (wflags & WD_BVH)) {
+      slot[0 * TRACE_BLOCK] = rq.origin.x; slot[1 * TRACE_BLOCK] = rq.origin.y; slot[2 * TRACE_BLOCK] = rq.origin.z;
+      slot[3 * TRACE_BLOCK] = rq.direction.x; slot[4 * TRACE_BLOCK] = rq.direction.y; slot[5 * TRACE_BLOCK] = rq.direction.z;
+      slot[6 * TRACE_BLOCK] = t_min;
+      q = rt::make_ray32(rq, t_min);
+      dir_neg = rt::ray_dir_neg(rq);
+      t_max32 = rt::cull_round_up(closest);
+      best.t = closest; best.ref = WALK_NO_REF; best.order = 0;
+      stack.push(WALK_DONE);
+      cur = G.a;
+      first_ref = (uint32_t)G.b;
+      walk_root = ms;
+      im = 2u;
+    } else {
+      rt::real t;
+      rt::PrimRef ref = 0;
+      if (direct_closest<F, false>(sv, G, rq, t_min, closest, &t, &ref) && !(hit_any && t == closest && ms < win_e)) {
+        closest = t; win_e = ms; win_ref = ref; hit_any = true;
+        t_max32 = rt::cull_round_up(closest);
+      }
+      cur = stack.pop();
+    }
+    }
+  };
+
   // entry 0 a plain BVH (Book-2, the dragon room, every catalogue scene that has a BVH): a new ray enters it at once
   bool e0_plain_bvh = false;
   int32_t e0_root = 0;
@@ -252,6 +323,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     e0_plain_bvh = (F & rt::F_BVH) && dev_load_uniform(&wdesc[0].flags) == WD_BVH;
     e0_root = dev_load_uniform(&wdesc[0].g_a);
     e0_first_ref = (uint32_t)dev_load_uniform(&wdesc[0].g_b);
+    if constexpr (INST) if (dev_load_uniform(&wdesc[n_top].g_a) == 0) e0_plain_bvh = false;  // slot 0 is a member: reached through its tree
   }
   auto begin_bounce_fast = [&]() {
     begin_bounce();
@@ -272,6 +344,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
       ei += 1;
       stage = ei >= n_top ? WS_SHADE : WS_ENTRY;
     }
+    close_member();
     const bool is_leaf = cur < 0;
     const bool is_node = (uint32_t)cur < (uint32_t)WALK_DONE;
     const unsigned long long m_node = wave_ballot(is_node), m_leaf = wave_ballot(is_leaf);
@@ -301,10 +374,17 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
           }
         } else if (cur < 0) {
           DIAG_ADD(1, ml);
-          const rt::Ray rl = slot_ray();
-          walk_leaf_step<F>(sv, first_ref, rl, slot[6 * TRACE_BLOCK], &best, &cur, stack);
-          t_max32 = rt::cull_round_up(best.t);
+          bool at_member = false;
+          if constexpr (INST) at_member = im == 1u;
+          if (at_member) {
+            visit_member();
+          } else {
+            const rt::Ray rl = slot_ray();
+            walk_leaf_step<F>(sv, first_ref, rl, slot[6 * TRACE_BLOCK], &best, &cur, stack);
+            t_max32 = rt::cull_round_up(best.t);
+          }
         }
+        close_member();
         mn = wave_ballot((uint32_t)cur < (uint32_t)WALK_DONE);
         ml = wave_ballot(cur < 0);
         const uint32_t still = (uint32_t)__popcll(mn | ml);
@@ -356,7 +436,27 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
     } else if (n_sweep >= n_need) {
       // ------------------------------------------------------------------ sweep over the world list
       DIAG_ADD(2, m_sweep);
+      // the sweep steps OVER the slots of an instance tree: its members are reached through the tree, by the lanes themselves
+      [[maybe_unused]] int32_t inst_rec = n_top, inst_first = 0x7fffffff;  // wave-uniform cursor in the table behind the slots' records
+      if constexpr (INST) inst_first = dev_load_uniform(&wdesc[inst_rec].g_a);
       for (int32_t e = 0; e < n_top; ++e) {
+        if constexpr (INST) if (e == inst_first) {
+          const int32_t n_slots = dev_load_uniform(&wdesc[inst_rec].g_b), root = dev_load_uniform(&wdesc[inst_rec].medium_mat);
+          inst_first = dev_load_uniform(&wdesc[++inst_rec].g_a);
+          if (stage == WS_WALK && cur == WALK_DONE && ei == e) {  // the slot walk is complete: the scan goes on behind the tree
+            ei = e + n_slots; stage = WS_ENTRY; im = 0u;
+          } else if (stage == WS_ENTRY && ei == e) {
+            q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
+            dir_neg = rt::ray_dir_neg(ps.ray);
+            t_max32 = rt::cull_round_up(closest);
+            stack.reset();
+            cur = root;
+            im = 1u; ph = 0u; walk_plain = false;
+            stage = WS_WALK;
+          }
+          e += n_slots - 1;
+          continue;
+        }
         const bool done_here = stage == WS_WALK && cur == WALK_DONE && ei == e;
         const bool begin_here = stage == WS_ENTRY && ei == e;
         if (wave_ballot(done_here || begin_here) == 0ull) continue;

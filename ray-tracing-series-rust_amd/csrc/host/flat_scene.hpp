@@ -29,6 +29,7 @@ struct FlatScene {
   std::vector<rt::real> gravity_y;
   int32_t max_stack = 0;      // deepest BVH (number of stacked far children a walk can hold)
   int32_t n_bvh = 0;
+  int32_t n_instance_trees = 0, n_instance_members = 0, n_instance_nodes = 0, instance_depth = 0;  // rtx_flat_instances
   uint32_t features = 0;      // rt::Feature bits reachable in this scene
   double sah_cost = 0.0;      // summed SAH cost of all BVHs (diagnostic)
   double bvh_build_ms = 0.0;  // wall time of all BVH builds (host or GPU builder)
@@ -58,7 +59,14 @@ struct FlatScene {
     v.n_top_level = (int32_t)top_level.size();
     v.max_stack = max_stack;
     v.features = features;
-    v.pad = 0;
+    // the instance records are the tail of the entry array (core/flat_types.hpp: ENTRY_INSTANCE); derived from the array
+    // itself so that a scene rebuilt from its byte images (host/f32_layout.hpp) needs nothing more
+    v.inst_entries = 0;
+    if (features & rt::F_INSTANCE) {
+      size_t k = entries.size();
+      while (k > 0 && entries[k - 1].kind == rt::ENTRY_INSTANCE) --k;
+      if (k < entries.size()) v.inst_entries = (uint32_t)k;
+    }
     return v;
   }
   size_t total_bytes() const;

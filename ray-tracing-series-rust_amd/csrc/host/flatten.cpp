@@ -9,6 +9,8 @@
 //   XFORM      := up to RT_MAX_XFORM_OPS nested Translate / RotateY over
 //                 primitive | RECT_PRISM | LIST of primitives | BVH
 //   MEDIUM     := boundary is any of the above except another medium; media only at top level
+//   INSTANCE   := (LIST item only) primitive | RECT_PRISM | LIST (spliced) | BVH | XFORM chain, none holding a Moving- or
+//                 GravitySphere: the members become consecutive slots of the world list, plus a culling tree over them
 // Anything else is reported as unsupported rather than approximated.
 #include <algorithm>
 #include <chrono>
@@ -139,6 +141,11 @@ struct Flattener {
     // What is left is an instanced sub-tree.  Neither kind has an image of the reference's to reproduce that does not depend on
     // its random split axes (bvh.rs:24; tests/test_instances_oracle.py pins both facts on the literal oracle), so the message
     // says which spelling does.
+    if (o.kind == H_INSTANCE_BVH)
+      return fail("unsupported nesting: an instance tree INSIDE a BvhNode or inside a transformed or medium list. An instance tree is the "
+                  "HittableList of its members and stands where a slot of the world list may stand; a BvhNode culls by its members' "
+                  "reference boxes, which for a rotated member are not the boxes the instance tree culls by (hit.rs:886). "
+                  "List the instance tree in the world list");
     if (o.kind == H_CONSTANT_MEDIUM)
       return fail("unsupported nesting: a ConstantMedium INSIDE a BVH or inside a transformed or medium list (an instanced sub-tree). "
                   "ConstantMedium::hit draws from the path's random stream whenever it is visited with a t_max that still reaches it "
@@ -328,6 +335,11 @@ struct Flattener {
       out.n_bvh++;
       return bvh_entry_of[h] = push_entry(e);
     }
+    if (o.kind == H_INSTANCE_BVH) {
+      fail("unsupported nesting: an instance tree UNDER a Translate / RotateY / ConstantMedium. Its culling boxes are its members' "
+           "boxes in world space, and a medium's draw depends on the visiting order (hit.rs:969). Wrap the members, not the tree");
+      return -1;
+    }
     fail("unsupported object where geometry is expected (transform of a transform chain > 2, medium inside a wrapper, ...)");
     return -1;
   }
@@ -369,6 +381,127 @@ struct Flattener {
     return push_entry(e);
   }
 
+  // ---- instance trees (H_INSTANCE_BVH) ----
+  struct InstRec { int32_t root, first_slot, n_slots; };
+  std::vector<InstRec> inst;
+  int32_t inst_depth = 0;
+
+  bool holds_timed_sphere(int32_t h, int depth = 0) const {
+    const GHittable& o = g.hittables[h];
+    if (o.kind == H_MOVING_SPHERE || o.kind == H_GRAVITY_SPHERE) return true;
+    if (depth > 80) return false;
+    for (int32_t c : o.children)
+      if (holds_timed_sphere(c, depth + 1)) return true;
+    return false;
+  }
+  // The members of an instance tree in list order, nested lists spliced in (as emit_top splices them into the world).
+  bool collect_members(int32_t h, std::vector<int32_t>* members, int depth = 0) {
+    if (depth > 64) return fail("hittable lists nested deeper than 64");
+    for (int32_t c : g.hittables[h].children) {
+      const GHittable& o = g.hittables[c];
+      if (o.kind == H_LIST) { if (!collect_members(c, members, depth + 1)) return false; continue; }
+      if (o.kind == H_INSTANCE_BVH)
+        return fail("unsupported nesting: an instance tree INSIDE an instance tree. An instance tree is the list of its members, so "
+                    "the inner tree's members can simply be added to the outer list: one tree over all of them culls better than two");
+      if (o.kind == H_CONSTANT_MEDIUM)
+        return fail("unsupported nesting: a ConstantMedium as a member of an instance tree. ConstantMedium::hit draws from the path's "
+                    "random stream whenever it is visited with a t_max that still reaches it (hit.rs:955-986), so the number of draws "
+                    "depends on the visiting order: no culling structure reproduces the list's. List the medium in the world list, "
+                    "beside the instance tree");
+      if (holds_timed_sphere(c))
+        return fail("unsupported nesting: a MovingSphere or GravitySphere inside a member of an instance tree. Its box only holds "
+                    "inside a time interval (hit.rs:317-327, 430-443) and an instance tree has none: it is culled by boxes that must "
+                    "hold for every ray. List the moving object in the world list, beside the instance tree");
+      members->push_back(c);
+    }
+    return true;
+  }
+  // The true box of one member slot in WORLD space: the union of its primitives' reference boxes taken out through its ops,
+  // innermost first.  RotateY: min / max of the eight rotated corners with the stored sin / cos -- the box hit.rs:857-885 computes
+  // and hit.rs:886 then discards; Translate: the offset added.  Every plane is then pushed OUTWARD by 2^-22 of the largest
+  // magnitude met on the way (coordinates before and after every op, offsets), which is at least two f32 ulps of the plane
+  // itself whatever its own value -- a plane at exactly 0 or at an exactly representable value gets the same slack (see
+  // core/cull32.hpp, "boxes of transformed members", for what this slack has to cover).
+  bool member_world_box(int32_t entry, double* b) {
+    const rt::FlatEntry S = out.entries[(size_t)entry];
+    const rt::FlatEntry G = S.kind == rt::ENTRY_XFORM ? out.entries[(size_t)S.a] : S;
+    for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+    auto grow = [&](rt::PrimRef ref) {
+      double pb[6];
+      prim_box(ref, 0.0, 0.0, pb);
+      for (int a = 0; a < 3; ++a) { b[a] = std::fmin(b[a], pb[a]); b[3 + a] = std::fmax(b[3 + a], pb[3 + a]); }
+    };
+    if (G.kind == rt::ENTRY_PRIM) grow((rt::PrimRef)G.a);
+    else if (G.kind == rt::ENTRY_GROUP) for (int32_t i = 0; i < G.b; ++i) grow(out.refs[(size_t)G.a + i]);
+    else for (int32_t i = 0; i < G.c; ++i) grow(out.refs[(size_t)G.b + i]);
+    double mag = 0.0;
+    auto seen = [&]() { for (int a = 0; a < 6; ++a) mag = std::fmax(mag, std::fabs(b[a])); };
+    seen();
+    const int nops = S.kind == rt::ENTRY_XFORM ? S.b : 0;
+    for (int k = nops - 1; k >= 0; --k) {
+      const rt::FlatXformOp& op = S.ops[k];
+      if (op.op == rt::XFORM_TRANSLATE) {
+        for (int a = 0; a < 3; ++a) { b[a] += op.v[a]; b[3 + a] += op.v[a]; mag = std::fmax(mag, std::fabs(op.v[a])); }
+      } else {
+        const double sin_t = op.v[0], cos_t = op.v[1];
+        double lo[3] = {INFINITY, b[1], INFINITY}, hi[3] = {-INFINITY, b[4], -INFINITY};
+        for (int i = 0; i < 2; ++i)
+          for (int j = 0; j < 2; ++j) {
+            const double x = i ? b[3] : b[0], z = j ? b[5] : b[2];
+            const double nx = cos_t * x + sin_t * z, nz = -sin_t * x + cos_t * z;
+            lo[0] = std::fmin(lo[0], nx); hi[0] = std::fmax(hi[0], nx);
+            lo[2] = std::fmin(lo[2], nz); hi[2] = std::fmax(hi[2], nz);
+          }
+        for (int a = 0; a < 3; ++a) { b[a] = lo[a]; b[3 + a] = hi[a]; }
+      }
+      seen();
+    }
+    const double pad = mag * 0x1.0p-22;
+    for (int a = 0; a < 3; ++a) { b[a] -= pad; b[3 + a] += pad; }
+    for (int a = 0; a < 6; ++a)
+      if (!std::isfinite(b[a])) return fail("instance tree: a member without a finite bounding box");
+    return true;
+  }
+  // H_INSTANCE_BVH in the world list: its members become consecutive slots -- entry for entry what the same objects written
+  // into the list at this position emit -- and a tree over the slots' world boxes is recorded for the scans that use it.
+  bool emit_instance(int32_t h) {
+    std::vector<int32_t> members;
+    if (!collect_members(h, &members)) return false;
+    const int32_t first_slot = (int32_t)out.top_level.size();
+    std::vector<double> boxes(6 * members.size());
+    for (size_t m = 0; m < members.size(); ++m) {
+      const int32_t e = emit_solid_entry(members[m]);
+      if (e < 0) return false;
+      out.top_level.push_back(e);
+      if (!member_world_box(e, &boxes[6 * m])) return false;
+    }
+    if (members.size() < 2) return true;  // no member: no slot; one member: just that slot
+    // one slot per leaf whatever BuildOptions::max_leaf says (that is for primitives: a member is a whole object), SAH on the host
+    BuildOptions bo = opt;
+    bo.max_leaf = 1;
+    const size_t n0 = out.nodes.size();
+    std::vector<uint32_t> order;
+    int32_t depth = 0;
+    double sah = 0.0;
+    const int32_t root = build_bvh(boxes, bo, &out.nodes, &order, &depth, &sah);
+    if (root < 0) return fail("instance tree: the builder returned no tree");
+    // a leaf names its slot of the WORLD list (members stay in list order; the builder's permutation goes into the codes)
+    for (size_t n = n0; n < out.nodes.size(); ++n)
+      for (int c = 0; c < 2; ++c) {
+        const int32_t code = out.nodes[n].child[c];
+        if (!rt::node_child_is_leaf(code)) continue;
+        if (rt::leaf_count(code) != 1u) return fail("instance tree: a leaf of more than one slot");
+        out.nodes[n].child[c] = rt::make_leaf((uint32_t)first_slot + order[rt::leaf_first(code)], 1u);
+      }
+    inst.push_back({root, first_slot, (int32_t)members.size()});
+    inst_depth = std::max(inst_depth, depth);
+    out.n_instance_trees += 1;
+    out.n_instance_members += (int32_t)members.size();
+    out.n_instance_nodes += (int32_t)(out.nodes.size() - n0);
+    out.instance_depth = std::max(out.instance_depth, depth);
+    return true;
+  }
+
   bool emit_top(int32_t h, int depth = 0) {
     if (depth > 64) return fail("hittable lists nested deeper than 64");
     const GHittable& o = g.hittables[h];
@@ -377,6 +510,7 @@ struct Flattener {
         if (!emit_top(c, depth + 1)) return false;
       return true;
     }
+    if (o.kind == H_INSTANCE_BVH) return emit_instance(h);
     int32_t e = emit_entry(h);
     if (e < 0) return false;
     out.top_level.push_back(e);
@@ -427,6 +561,19 @@ struct Flattener {
     }
     // An empty world is legal: HittableList::hit returns None and every path sees the background.
     if (!emit_top(world)) return false;
+    if (!inst.empty()) {
+      // the instance records close the entry array (core/flat_types.hpp: ENTRY_INSTANCE); emit_top met the trees in slot order
+      for (const InstRec& r : inst) {
+        rt::FlatEntry e = blank_entry(rt::ENTRY_INSTANCE);
+        e.a = r.root; e.b = r.first_slot; e.c = r.n_slots;
+        push_entry(e);
+      }
+      rt::FlatEntry end = blank_entry(rt::ENTRY_INSTANCE);
+      end.a = -1; end.b = 0x7fffffff; end.c = 0;
+      push_entry(end);
+      // a member's own BVH is walked ABOVE the slot walk on the same stack, one marker between them (hip/trace_world.inc)
+      out.max_stack = inst_depth + 1 + out.max_stack;
+    }
     uint32_t f = 0;
     if (!out.spheres.empty()) f |= rt::F_SPHERE;
     if (!out.moving_spheres.empty()) f |= rt::F_MOVING_SPHERE;
@@ -438,6 +585,7 @@ struct Flattener {
       else if (e.kind == rt::ENTRY_GROUP) f |= rt::F_GROUP;
       else if (e.kind == rt::ENTRY_BVH) f |= rt::F_BVH;
       else if (e.kind == rt::ENTRY_XFORM) f |= rt::F_XFORM;
+      else if (e.kind == rt::ENTRY_INSTANCE) f |= rt::F_INSTANCE;
       else if (e.kind == rt::ENTRY_MEDIUM) {
         f |= rt::F_MEDIUM;
         const rt::FlatEntry& boundary = out.entries[e.a];

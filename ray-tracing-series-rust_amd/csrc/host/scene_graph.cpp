@@ -6,6 +6,7 @@
 //   H_XY/XZ/YZ_RECT   f[0] x0, f[1] x1, f[2] y0, f[3] y1, f[4] k   (constructor names)
 //   H_RECT_PRISM      f[0..2] p0, f[3..5] p1
 //   H_BVH             f[0] time0, f[1] time1, children = the list's objects at from_list time
+//   H_INSTANCE_BVH    children = the list's objects at construction time
 //   H_TRANSLATE       f[0..2] offset
 //   H_ROTATE_Y        f[0] sin_theta, f[1] cos_theta, f[2] angle in degrees
 //   H_CONSTANT_MEDIUM f[0] neg_inv_density, mat = the Isotropic phase function
@@ -236,6 +237,13 @@ int32_t SceneGraph::bvh_from_list(int32_t list, double time0, double time1) {
   if (hittables[list].children.empty()) { error = "bvh_from_list: empty list (the reference panics)"; return -1; }
   GHittable h = make_h(H_BVH, -1);
   h.f[0] = time0; h.f[1] = time1;
+  h.children = hittables[list].children;
+  hittables.push_back(std::move(h));
+  return (int32_t)hittables.size() - 1;
+}
+int32_t SceneGraph::instance_bvh_from_list(int32_t list) {
+  if (!valid_hittable(list) || hittables[list].kind != H_LIST) { error = "instance_bvh_from_list: not a list"; return -1; }
+  GHittable h = make_h(H_INSTANCE_BVH, -1);
   h.children = hittables[list].children;
   hittables.push_back(std::move(h));
   return (int32_t)hittables.size() - 1;

@@ -29,7 +29,9 @@ enum HittableKind : int32_t {
   H_TRANSLATE = 9,       // Translate::new(offset, obj)                         hit.rs:793-798
   H_ROTATE_Y = 10,       // RotateY::new(angle_deg, obj)                        hit.rs:843-888
   H_CONSTANT_MEDIUM = 11,// ConstantMedium::from_color(color, density, boundary) hit.rs:945-951
-  H_GRAVITY_SPHERE = 12  // GravitySphere::new(start, time0, radius, mat)         hit.rs:340-367
+  H_GRAVITY_SPHERE = 12, // GravitySphere::new(start, time0, radius, mat)         hit.rs:340-367
+  // An extension, not a reference type: the HittableList of its members, culled by their true (transformed) boxes.
+  H_INSTANCE_BVH = 13    // instance_bvh_from_list(list): children = the list's objects at construction time
 };
 
 struct GHittable {
@@ -92,6 +94,7 @@ struct SceneGraph {
   int32_t list_new();
   bool list_add(int32_t list, int32_t obj);
   int32_t bvh_from_list(int32_t list, double time0, double time1);
+  int32_t instance_bvh_from_list(int32_t list);  // may be empty: an empty list hits nothing
   int32_t translate(const double offset[3], int32_t obj);
   int32_t rotate_y(double angle_deg, int32_t obj);
   int32_t constant_medium(const double rgb[3], double density, int32_t boundary);

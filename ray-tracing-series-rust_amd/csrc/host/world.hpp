@@ -140,6 +140,9 @@ struct BvhNode {
     return {list.s, checked(rtx_bvh_from_list(list.s->builder(), list.h, time0, time1))};
   }
 };
+struct InstanceBvh {  // an extension (rtx_instance_bvh_from_list): the list of its members, culled by their true boxes
+  static Hittable from_list(const HittableList& list) { return {list.s, checked(rtx_instance_bvh_from_list(list.s->builder(), list.h))}; }
+};
 struct Translate {
   static Hittable new_(Scene& s, const Vec3& offset, Hittable obj) { double o[3] = {offset.x, offset.y, offset.z}; return {&s, checked(rtx_translate(s.builder(), o, obj.h))}; }
 };
