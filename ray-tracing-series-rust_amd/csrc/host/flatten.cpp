@@ -429,7 +429,9 @@ struct Flattener {
     auto grow = [&](rt::PrimRef ref) {
       double pb[6];
       prim_box(ref, 0.0, 0.0, pb);
-      for (int a = 0; a < 3; ++a) { b[a] = std::fmin(b[a], pb[a]); b[3 + a] = std::fmax(b[3 + a], pb[3 + a]); }
+      // a sphere of negative radius (the hollow-glass idiom) has an INVERTED reference box, centre - r .. centre + r
+      // (hit.rs:239-244): each axis is ordered before the union, or the union -- and every ancestor -- loses the sphere
+      for (int a = 0; a < 3; ++a) { b[a] = std::fmin(b[a], std::fmin(pb[a], pb[3 + a])); b[3 + a] = std::fmax(b[3 + a], std::fmax(pb[a], pb[3 + a])); }
     };
     if (G.kind == rt::ENTRY_PRIM) grow((rt::PrimRef)G.a);
     else if (G.kind == rt::ENTRY_GROUP) for (int32_t i = 0; i < G.b; ++i) grow(out.refs[(size_t)G.a + i]);
@@ -619,11 +621,13 @@ struct Flattener {
       double b[6];
       prim_box(ref, 0.0, 0.0, b);
       for (int a = 0; a < 3; ++a) {
-        float lo = (float)b[a];
-        if ((double)lo > b[a]) lo = std::nextafterf(lo, -INFINITY);
-        float hi = (float)b[3 + a];
-        if ((double)hi < b[3 + a]) hi = std::nextafterf(hi, INFINITY);
-        if (lo == lo && hi == hi) { bx[a] = lo; bx[3 + a] = hi; }
+        // ordered first: a sphere of negative radius has an inverted reference box, and "outward" must mean outward
+        const double blo = std::fmin(b[a], b[3 + a]), bhi = std::fmax(b[a], b[3 + a]);
+        float lo = (float)blo;
+        if ((double)lo > blo) lo = std::nextafterf(lo, -INFINITY);
+        float hi = (float)bhi;
+        if ((double)hi < bhi) hi = std::nextafterf(hi, INFINITY);
+        if (b[a] == b[a] && b[3 + a] == b[3 + a]) { bx[a] = lo; bx[3 + a] = hi; }
       }
     }
     // f32 culling copy of every node: lo rounded down, hi rounded up

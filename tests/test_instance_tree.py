@@ -4,10 +4,16 @@ The one invariant: a world spelled with an instance tree gives, bit for bit, the
 into the world list at that position (the "hoisted" spelling), which O1 -- the literal oracle, which never sees the new node --
 and O2 already agree on.  Every test here fails on a tree without the constructor.
 """
+import ctypes as C
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
-from instance_scenes import box_field, field_cam_cfg, tie_cam_cfg, tie_scene
+from instance_scenes import (ZOO_F32_CAPPED, ZOO_F32_EXACT, ZOO_IMAGE_REGIONS, ZOO_LAYOUTS, ZOO_REFERENCE_ALONE_UNEQUAL, box_field, field_cam_cfg, member_zoo, offset_scene, tie_cam_cfg, tie_scene, zoo_cam_cfg)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 ENTRY_PRIM, ENTRY_GROUP, ENTRY_BVH, ENTRY_XFORM = 0, 1, 2, 3
 
@@ -177,3 +183,415 @@ def test_f32_oracle_instanced_equals_hoisted(rtsr, orc):
     inst, inst8 = orc.o2f_render(fi.arrays_ptr(), cam, cfg, h, threads=8)
     assert hoisted.std() > 0.01
     assert np.array_equal(inst, hoisted) and np.array_equal(inst8, hoisted8)
+
+
+# ---- rays and boxes: the member zoo (tests/instance_scenes.py) in every slot layout ----
+def _vec(rec):
+    """A hit record (or None) as 11 doubles: hit flag, t, p, normal, u, v, front_face."""
+    if rec is None:
+        return [0.0] * 11
+    return [1.0, rec["t"], *rec["p"], *rec["normal"], rec["u"], rec["v"], float(rec["front_face"])]
+
+
+def _same_bits(a, b):
+    """Bit for bit up to the payload of a NaN: equal values with NaN == NaN (numpy.array_equal(equal_nan=True)), and equal signs
+    wherever the value is not a NaN (which tells -0.0 from 0.0)."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    sa, sb = np.signbit(a) & ~np.isnan(a), np.signbit(b) & ~np.isnan(b)
+    return np.array_equal(a, b, equal_nan=True) and np.array_equal(sa, sb)
+
+
+def _random_rays(aim, n, seed, spread=0.45, reach=9.0):
+    """n rays from a fixed seed, each from a point around the scene towards a jittered aim point; every 7th has one zero
+    direction component, every 13th two."""
+    rng = np.random.default_rng(seed)
+    aim = np.asarray(aim, dtype=np.float64)
+    centre = aim.mean(axis=0)
+    rays = []
+    for k in range(n):
+        target = aim[rng.integers(len(aim))] + rng.uniform(-spread, spread, 3)
+        o = centre + rng.uniform(-reach, reach, 3)
+        o[1] = abs(o[1] - centre[1]) * 0.6 + 0.05 + min(aim[:, 1])
+        d = target - o
+        if k % 7 == 0:
+            d[int(rng.integers(3))] = 0.0
+        if k % 13 == 0:
+            keep = int(rng.integers(3))
+            d = np.array([d[a] if a == keep else 0.0 for a in range(3)])
+            if d[keep] == 0.0:
+                d[keep] = 1.0
+        rays.append((tuple(o), tuple(d), 0.001, float("inf")))
+    return rays
+
+
+def _differential(orc, bh, wh, bi, wi, rays, what, image_regions=()):
+    """Every ray through core_world_hit and core32_world_hit of both spellings and through o1_hit of the hoisted graph.
+    image_regions: boxes that hold the scene's image-textured surfaces and no other.
+    -> (rays that hit, rays on which instanced != hoisted in f64, in f32, rays on which hoisted != O1)."""
+    fh, fi = bh.flatten(wh), bi.flatten(wi)
+    rows = {k: [] for k in ("i", "h", "o1", "i32", "h32")}
+    for o, d, t_min, t_max in rays:
+        rows["i"].append(_vec(orc.core_world_hit(fi.arrays_ptr(), o, d, t_min=t_min, t_max=t_max)))
+        rows["h"].append(_vec(orc.core_world_hit(fh.arrays_ptr(), o, d, t_min=t_min, t_max=t_max)))
+        rows["o1"].append(_vec(orc.o1_hit(bh.graph_ptr(), wh, o, d, t_min=t_min, t_max=t_max)))
+        rows["i32"].append(_vec(orc.core32_world_hit(fi.arrays_ptr(), o, d, t_max=t_max)))
+        rows["h32"].append(_vec(orc.core32_world_hit(fh.arrays_ptr(), o, d, t_max=t_max)))
+    rows = {k: np.array(v) for k, v in rows.items()}
+    # u and v against O1: the core computes them for materials with an image texture only and stores 0 elsewhere
+    # (core/geometry.hpp, prim_finalize: "only read by Image textures").  Which hits those are is decided by the scene and
+    # by O1 -- O1's hit point lies in a region of image-textured surfaces -- not by what the core returned: there O1's u
+    # and v are compared as they are, everywhere else the core must hold 0 and O1's pair is set to 0 for the comparison
+    p = rows["o1"][:, 2:5]
+    with_uv = np.zeros(len(p), dtype=bool)
+    for lo, hi in image_regions:
+        with_uv |= (rows["o1"][:, 0] == 1.0) & ((p >= np.array(lo)) & (p <= np.array(hi))).all(axis=1)
+    # (a triangle's record carries the constants u = v = 1 in the reference and in the core alike: kept)
+    with_uv |= (rows["o1"][:, 8] == 1.0) & (rows["o1"][:, 9] == 1.0)
+    # a NaN hit (a ray in a rectangle's plane) has no place: it is on an image-textured rectangle if the RAY lies in the
+    # plane of one (a region thinner than 1e-3 on an axis is a rectangle's)
+    ro, rd = np.array([r[0] for r in rays], dtype=np.float64), np.array([r[1] for r in rays], dtype=np.float64)
+    for lo, hi in image_regions:
+        for a in range(3):
+            if hi[a] - lo[a] < 1e-3:
+                with_uv |= np.isnan(p).any(axis=1) & (ro[:, a] >= lo[a]) & (ro[:, a] <= hi[a]) & (rd[:, a] == 0.0)
+    no_uv = ~with_uv
+    rows["o1"][no_uv, 8:10] = 0.0
+    count = lambda a, b: sum(0 if _same_bits(x, y) else 1 for x, y in zip(rows[a], rows[b]))
+    hits, bad, bad32, bad_o1 = int(rows["h"][:, 0].sum()), count("i", "h"), count("i32", "h32"), count("h", "o1")
+    print("%s: %d rays, %d hit (%d NaN t, %d with u, v); instanced != hoisted: %d (f64), %d (f32); hoisted != O1: %d"
+          % (what, len(rays), hits, int(np.isnan(rows["h"][:, 1]).sum()), int((~no_uv).sum()), bad, bad32, bad_o1))
+    return hits, bad, bad32, bad_o1
+
+
+@pytest.mark.parametrize("layout", ZOO_LAYOUTS)
+def test_zoo_rays_instanced_equals_hoisted_equals_o1(rtsr, orc, layout):
+    """2000 random rays from a fixed seed through the member zoo in one slot layout: core_world_hit(instanced) ==
+    core_world_hit(hoisted) == o1_hit(hoisted graph) and core32_world_hit(instanced) == core32_world_hit(hoisted), over hit or
+    miss, t, p, normal, front_face, u and v (against O1, u and v on the image-textured members, picked by O1's hit point; elsewhere the core holds 0).  The comparison is by bits, not by ==, with NaN equal to NaN: a ray lying in a
+    rectangle's plane gives t = NaN in the reference itself (0 / 0 in hit.rs:476), identically in all three.  The probes return
+    no material; the small frame below, O2(instanced) == O2(hoisted), is what judges it (every member has its own).
+    At least a quarter of the rays must hit."""
+    bh, wh, aim = member_zoo(rtsr, "hoisted", layout, with_aim=True)
+    bi, wi = member_zoo(rtsr, "instanced", layout)
+    rays = _random_rays(aim, 2000, seed=20 + ZOO_LAYOUTS.index(layout))
+    hits, bad, bad32, bad_o1 = _differential(orc, bh, wh, bi, wi, rays, "zoo " + layout, ZOO_IMAGE_REGIONS)
+    assert 4 * hits >= len(rays)
+    assert (bad, bad32, bad_o1) == (0, 0, 0)
+    cam, cfg, h = zoo_cam_cfg(rtsr, spp=4)
+    fh, fi = bh.flatten(wh), bi.flatten(wi)
+    hoisted, hoisted8 = orc.o2_render(fh.arrays_ptr(), cam, cfg, h, threads=8)
+    inst, inst8 = orc.o2_render(fi.arrays_ptr(), cam, cfg, h, threads=8)
+    assert hoisted.std() > 0.01
+    assert np.array_equal(inst, hoisted) and np.array_equal(inst8, hoisted8)
+
+
+def _directed_rays(orc, flat):
+    """The rays the box argument is thinnest for, on the zoo's own coordinates (tests/instance_scenes.py).  A ray with
+    o[a] == k and d[a] == 0 is "in the plane" of EVERY rectangle at k on axis a, however far away, and hits it with t = NaN
+    (0 / 0, and no comparison with NaN rejects); from then on the list accepts whatever comes later.  So the fixed coordinates
+    of the axis-parallel rays are off every plane (+ 0.0137 ...) except where a plane is the point of the ray."""
+    inf = float("inf")
+    rays = []
+    add = lambda o, d, t_min=0.001, t_max=inf: rays.append((o, d, t_min, t_max))
+    for x, z in ((-4.0, 1.0), (1.0, 1.2), (3.4, 0.9), (2.0, -2.2), (-2.4, -2.8), (5.5, -2.6), (-4.2, -4.0), (4.2, -4.0)):
+        add((x + 0.0137, 6.0, z + 0.0071), (0.0, -1.0, 0.0))            # two zero direction components
+        add((x + 0.0137, 6.0, z - 1.5), (0.0, -1.0, 0.25))              # one
+        add((x - 2.0, 0.3137, z + 0.0071), (1.0, 0.0, 0.0))
+    add((-4.0, 0.6137, -0.5), (1.0, 0.013, 0.0))      # in the plane of the XyRect at z = -0.5 (t = NaN) ...
+    add((-2.5, 0.2137, -0.5), (0.0, 1.0, 0.0))
+    add((-2.0137, 0.4, 0.2), (0.003, 0.0, 1.0))       # ... of the XzRect at y = 0.4 ...
+    add((-1.2, 3.0, 0.5137), (0.0, -1.0, 0.01))       # ... of the YzRect at x = -1.2
+    add((3.0, 2.0, 0.9137), (0.0, -1.0, 0.0))         # along a face of the bare prism, along its edge, along its top
+    add((3.0, 2.0, 0.5), (0.0, -1.0, 0.0))
+    add((2.0, 0.9, 0.9137), (1.0, 0.0, 0.0))
+    add((3.8, 0.9, -2.0), (0.0, 0.0, 1.0))
+    add((-4.0, 0.6, 1.0), (0.3, 0.2, 1.0))            # from inside a member, from its surface (outward and inward)
+    add((-4.0, 1.2, 1.0), (0.01, 1.0, 0.02))
+    add((-4.0, 1.2, 1.0), (0.01, -1.0, 0.02))
+    add((3.4, 0.45, 0.9), (1.0, 0.3, 0.2))
+    add((2.0, 0.4, -2.2), (0.2, 0.1, 1.0))            # from inside the wrapped BVH member's row
+    for o, d in (((1.0, 0.7, 1.2), (0.3, 1.0, 0.2)), ((1.0, 1.35, 1.2), (0.01, -1.0, 0.0)), ((1.0, 1.35, 1.2), (1.0, 0.02, 0.0)),
+                 ((1.0137, 5.0, 1.2071), (0.0, -1.0, 0.0)), ((-3.0, 0.7137, 1.2071), (1.0, 0.0, 0.0)), ((1.0, 0.7, 6.0), (0.05, 0.02, -1.0)),
+                 ((1.55, 3.0, 1.2071), (0.0, -1.0, 0.0)), ((1.0, 0.7, 1.2), (-1.0, -0.2, 0.4))):
+        add(o, d)                                     # the negative-radius sphere from inside, between the shells and outside
+    for o, d in (((-4.0137, 6.0, 1.0071), (0.0, -1.0, 0.0)), ((2.3, 5.0, 1.2), (0.01, -1.0, 0.02)), ((3.4137, 4.0, 0.9071), (0.0, -1.0, 0.0)),
+                 ((2.0, 3.0, 2.0), (0.0, -0.6, -1.0))):
+        free = orc.core_world_hit(flat.arrays_ptr(), o, d)
+        assert free is not None and free["t"] == free["t"]
+        add(o, d, 0.001, free["t"])                   # t_max exactly on a member (the reference accepts t == t_max)
+    # vertical and slanted rays over the footprints of the rotated members: their true boxes outside their un-rotated ones
+    for cx, cz in ((-2.4, -2.8), (-1.2, -2.8), (5.5, -2.6), (2.0, -2.2), (4.4, -0.6), (-5.2, 1.9)):
+        for i in range(9):
+            for j in range(9):
+                x, z = cx - 1.0 + 0.25 * i + 0.0037, cz - 1.0 + 0.25 * j + 0.0013
+                add((x, 3.0, z), (0.0, -1.0, 0.0) if (i + j) % 2 else (0.02, -1.0, -0.01))
+    return rays
+
+
+def test_directed_rays_instanced_equals_hoisted_equals_o1(rtsr, orc):
+    """The directed set on the zoo ("middle"): zero direction components, rays in a rectangle's plane and along a prism's face
+    and edge, rays from inside a member, from its surface and with t_max exactly on it, rays over the rotated members'
+    footprints, the negative-radius sphere from inside and outside.  Bit for bit as in the random test (t = NaN occurs)."""
+    bh, wh = member_zoo(rtsr, "hoisted")
+    bi, wi = member_zoo(rtsr, "instanced")
+    flat = bh.flatten(wh)
+    rays = _directed_rays(orc, flat)
+    hits, bad, bad32, bad_o1 = _differential(orc, bh, wh, bi, wi, rays, "directed", ZOO_IMAGE_REGIONS)
+    assert 4 * hits >= len(rays)
+    assert (bad, bad32, bad_o1) == (0, 0, 0)
+
+
+@pytest.mark.parametrize("offset", [0.0, 12345.678, 1e6])
+def test_offset_members_rays(rtsr, orc, offset):
+    """Members carried 0, 12345.678 and 1e6 away: 2000 random rays from nearby, every comparison of the zoo test."""
+    bh, wh, aim = offset_scene(rtsr, "hoisted", offset)
+    bi, wi, _ = offset_scene(rtsr, "instanced", offset)
+    rays = _random_rays(aim, 2000, seed=7, spread=0.5, reach=5.0)
+    hits, bad, bad32, bad_o1 = _differential(orc, bh, wh, bi, wi, rays, "offset %r" % offset)
+    assert 4 * hits >= len(rays)
+    assert (bad, bad32, bad_o1) == (0, 0, 0)
+    _audit_boxes(orc, _host_arrays(), bi.flatten(wi))
+
+
+def test_negative_radius_member_is_seen(rtsr, orc):
+    """A sphere of radius r between two unit-scale neighbours, 1500 random rays: with r = -1 (an inverted reference box,
+    hit.rs:239-244) exactly as with r = +1.  Before member_world_box ordered the box: 1115 rays hit and 288 of them differed
+    from the hoisted spelling in the f64 core, 302 in the f32 core; now 0 and 0 (the figures are printed)."""
+    res = {}
+    for r in (1.0, -1.0):
+        worlds = []
+        for spelling in ("hoisted", "instanced"):
+            b = rtsr.Builder(1)
+            grey = b.lambertian((0.5, 0.5, 0.5))
+            ms = [b.sphere((0.0, 0.0, 0.0), r, grey), b.sphere((2.5, 0.2, 0.0), 0.8, grey), b.sphere((-2.2, -0.3, 0.5), 1.1, grey)]
+            worlds.append((b, b.hittable_list([b.instance_bvh(b.hittable_list(ms))] if spelling == "instanced" else ms)))
+        rays = _random_rays([(0.0, 0.0, 0.0), (2.5, 0.2, 0.0), (-2.2, -0.3, 0.5)], 1500, seed=3, spread=0.8, reach=8.0)
+        res[r] = _differential(orc, worlds[0][0], worlds[0][1], worlds[1][0], worlds[1][1], rays, "radius %+g" % r)
+    assert res[1.0][0] == res[-1.0][0] and 4 * res[1.0][0] >= 1500
+    assert res[1.0][1:] == (0, 0, 0) and res[-1.0][1:] == (0, 0, 0)
+
+
+# ---- the box audit ----
+XFORM_OP = np.dtype([("op", "<i4"), ("pad", "<i4"), ("v", "<f8", (3,))])
+FLAT_ENTRY = np.dtype([("kind", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("f", "<f8", (2,)), ("ops", XFORM_OP, (4,))])
+FLAT_NODE = np.dtype([("bmin", "<f8", (2, 3)), ("bmax", "<f8", (2, 3)), ("child", "<i4", (2,)), ("pad", "<i4", (2,))])
+FLAT_NODE32 = np.dtype([("lo", "<f4", (2, 3)), ("hi", "<f4", (2, 3)), ("child", "<i4", (2,)), ("axis", "<i4"), ("pad", "<i4")])
+FLAT_SPHERE = np.dtype([("c", "<f8", (3,)), ("radius", "<f8"), ("mat", "<i4"), ("pad", "<i4")])
+FLAT_RECT = np.dtype([("a0", "<f8"), ("a1", "<f8"), ("b0", "<f8"), ("b1", "<f8"), ("k", "<f8"), ("axis", "<i4"), ("mat", "<i4")])
+FLAT_TRIANGLE = np.dtype([("v", "<f8", (3, 3)), ("normal", "<f8", (3,)), ("mat", "<i4"), ("pad", "<i4")])
+ENTRY_INSTANCE = 5
+PRIM_SPHERE, PRIM_RECT, PRIM_TRIANGLE = 0, 2, 3
+_HOST = {}
+
+
+def _host_arrays():
+    """tests/instance_host_check.cpp as a shared object: the arrays oracle_flat_array does not name.  It casts arrays_ptr() to
+    rtx::FlatScene* as the oracle does, so it rests on this compiler and the library's sharing one std::vector ABI and one set
+    of defines (real = double); the element-size asserts in _array catch a changed element, not a changed member order."""
+    if "lib" not in _HOST:
+        import tempfile
+        _HOST["dir"] = tempfile.TemporaryDirectory()
+        out = os.path.join(_HOST["dir"].name, "instance_host_check.so")
+        subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wno-unused-function",
+                        "-shared", os.path.join(ROOT, "tests", "instance_host_check.cpp"), "-o", out], check=True)
+        lib = C.CDLL(out)
+        lib.instance_host_array.restype = C.c_void_p
+        lib.instance_host_array.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        _HOST["lib"] = lib
+    return _HOST["lib"]
+
+
+def _array(orc, host, flat, name, dtype):
+    if name in ("top_level", "refs", "nodes32", "top_box32"):
+        n, e = C.c_int64(0), C.c_int64(0)
+        p = host.instance_host_array(flat.arrays_ptr(), name.encode(), C.byref(n), C.byref(e))
+        raw = np.ctypeslib.as_array((C.c_uint8 * (n.value * e.value)).from_address(p)).copy() if p and n.value else np.zeros(0, np.uint8)
+        esize = e.value
+    else:
+        raw, esize = orc.flat_array(flat.arrays_ptr(), name)
+    assert raw.size == 0 or esize == np.dtype(dtype).itemsize, (name, esize)
+    return raw.view(dtype)
+
+
+def _surface_points(ref, spheres, rects, tris):
+    """Points ON one primitive, in numpy.longdouble (n x 3)."""
+    L = np.longdouble
+    kind, idx = int(ref) >> 29, int(ref) & 0x1fffffff
+    if kind == PRIM_SPHERE:
+        c, r = spheres[idx]["c"].astype(L), abs(L(spheres[idx]["radius"]))
+        dirs = [np.eye(3)[a] * s for a in range(3) for s in (1.0, -1.0)]
+        rng = np.random.default_rng(idx)
+        for _ in range(12):
+            v = rng.normal(size=3)
+            dirs.append(v / np.linalg.norm(v))
+        # a unit vector rounded to double is off the unit sphere by an ulp: pull it in by 2^-50, well inside the box's slack
+        return np.array([c + r * (np.asarray(d).astype(L) * (L(1) - L(2) ** -50 * (0 if np.count_nonzero(d) == 1 else 1))) for d in dirs])
+    if kind == PRIM_RECT:
+        q = rects[idx]
+        a0, a1, b0, b1, k = (L(q[n]) for n in ("a0", "a1", "b0", "b1", "k"))
+        flat_pts = [(a0, b0), (a0, b1), (a1, b0), (a1, b1), ((a0 + a1) / 2, (b0 + b1) / 2)]
+        place = {0: lambda a, b: (a, b, k), 1: lambda a, b: (a, k, b), 2: lambda a, b: (k, a, b)}[int(q["axis"])]
+        return np.array([place(a, b) for a, b in flat_pts], dtype=L)
+    assert kind == PRIM_TRIANGLE, kind
+    v = tris[idx]["v"].astype(L)
+    return np.vstack([v, v.mean(axis=0, keepdims=True)])
+
+
+def _to_world(points, entry):
+    """Out through the entry's ops, innermost first, as xform_record maps a hit point (hit.rs:816, 909-914), with the sin / cos
+    the entry stores."""
+    L = np.longdouble
+    pts = points.copy()
+    if entry["kind"] != 3:
+        return pts
+    for k in range(int(entry["b"]) - 1, -1, -1):
+        op = entry["ops"][k]
+        if op["op"] == 0:
+            pts = pts + op["v"].astype(L)
+        else:
+            s, c = L(op["v"][0]), L(op["v"][1])
+            pts = np.stack([c * pts[:, 0] + s * pts[:, 2], pts[:, 1], -s * pts[:, 0] + c * pts[:, 2]], axis=1)
+    return pts
+
+
+def _audit_boxes(orc, host, flat):
+    """Every instance tree of `flat`: boxes ordered, every leaf one slot of the tree's range and every slot named once, and
+    surface points of every member inside its leaf box and every ancestor box, in nodes and in nodes32.  -> points checked."""
+    entries = _array(orc, host, flat, "entries", FLAT_ENTRY)
+    nodes, nodes32 = _array(orc, host, flat, "nodes", FLAT_NODE), _array(orc, host, flat, "nodes32", FLAT_NODE32)
+    top, refs = _array(orc, host, flat, "top_level", "<i4"), _array(orc, host, flat, "refs", "<u4")
+    spheres, rects = _array(orc, host, flat, "spheres", FLAT_SPHERE), _array(orc, host, flat, "rects", FLAT_RECT)
+    tris = _array(orc, host, flat, "triangles", FLAT_TRIANGLE)
+    assert len(nodes) == len(nodes32)
+    assert orc.audit_flat(flat.arrays_ptr())[0] == 0
+    L = np.longdouble
+    checked = 0
+    trees = [e for e in entries if e["kind"] == ENTRY_INSTANCE and e["a"] >= 0]
+    assert len(trees) == flat.instances()["n_trees"]
+    for t in trees:
+        root, first, n_slots = int(t["a"]), int(t["b"]), int(t["c"])
+        named = []
+        stack = [(root, [])]
+        while stack:
+            node, above = stack.pop()
+            assert np.array_equal(nodes[node]["child"], nodes32[node]["child"])
+            for c in range(2):
+                boxes = above + [(nodes[node]["bmin"][c].astype(L), nodes[node]["bmax"][c].astype(L), "nodes[%d][%d]" % (node, c)),
+                                 (nodes32[node]["lo"][c].astype(L), nodes32[node]["hi"][c].astype(L), "nodes32[%d][%d]" % (node, c))]
+                for lo, hi, name in boxes[-2:]:
+                    assert (lo <= hi).all(), "%s is inverted: %s .. %s" % (name, lo, hi)
+                child = int(nodes[node]["child"][c])
+                if child >= 0:
+                    stack.append((child, boxes))
+                    continue
+                slot, count = (child & 0x7fffffff) >> 3, (child & 7) + 1
+                assert count == 1 and first <= slot < first + n_slots, (slot, count, first, n_slots)
+                named.append(slot)
+                S = entries[top[slot]]
+                G = entries[S["a"]] if S["kind"] == 3 else S
+                if G["kind"] == 0:
+                    prims = [np.uint32(G["a"])]
+                elif G["kind"] == 1:
+                    prims = refs[int(G["a"]):int(G["a"]) + int(G["b"])]
+                else:
+                    assert G["kind"] == 2
+                    prims = refs[int(G["b"]):int(G["b"]) + int(G["c"])]
+                assert len(prims) > 0
+                pts = _to_world(np.vstack([_surface_points(r, spheres, rects, tris) for r in prims]), S)
+                for lo, hi, name in boxes:
+                    inside = ((pts >= lo) & (pts <= hi)).all(axis=1)
+                    assert inside.all(), "slot %d: %d of %d surface points outside %s (%s .. %s), e.g. %s" % (
+                        slot, int((~inside).sum()), len(pts), name, lo, hi, pts[~inside][0])
+                checked += len(pts)
+        assert sorted(named) == list(range(first, first + n_slots)), "every slot of the tree in exactly one leaf"
+    return checked
+
+
+@pytest.mark.parametrize("layout", ZOO_LAYOUTS)
+def test_member_boxes_hold_their_members(rtsr, orc, layout):
+    """The box audit on the zoo in every layout: the tree's nodes decoded from the flat arrays with dtypes mirroring
+    core/flat_types.hpp; surface points of every member's primitives taken to world space through its ops in
+    numpy.longdouble (with the stored sin / cos) lie inside the leaf box and every ancestor box, in the f64 and in the f32
+    copy; every box has lo <= hi; every leaf names one slot of [first_slot, first_slot + n_slots) and each slot is named once;
+    audit_flat returns 0.  Also top_box32 -- consumed by a test that sorts the two planes (cull32_may_hit) -- is ordered."""
+    b, w = member_zoo(rtsr, "instanced", layout)
+    flat = b.flatten(w)
+    host = _host_arrays()
+    want_trees = {"two": 2, "one": 0, "empty": 0}.get(layout, 1)
+    assert flat.instances()["n_trees"] == want_trees
+    checked = _audit_boxes(orc, host, flat)
+    print("layout %s: %d trees, %d surface points inside their boxes" % (layout, want_trees, checked))
+    assert (checked > 400) == (want_trees > 0)
+    top_box = _array(orc, host, flat, "top_box32", "<f4").reshape(-1, 6)
+    assert len(top_box) == flat.info()["n_top_level"] and (top_box[:, :3] <= top_box[:, 3:]).all()
+
+
+ENTRY_MEDIUM = 4
+
+
+@pytest.mark.parametrize("layout", ZOO_LAYOUTS)
+def test_layouts_meet_the_conditions_the_scans_branch_on(rtsr, orc, layout):
+    """Each layout is built for a branch of the sweep (hip/trace_world.inc); what that branch tests is read off the flat scene
+    here, so that a changed zoo cannot quietly stop reaching it.  "first": the tree starts at slot 0 and slot 0 is a plain BVH
+    (the e0_plain_bvh guard).  "after_bvh": slot 0 is a plain BVH outside the tree, which starts at slot 1.  "last" / "alone":
+    the tree ends the list / is the list.  "two": two records with plain slots between them.  "pair": the tree's last slot is
+    a plain sphere and the next world slot a medium bounded by a sphere with the same centre and radius, bit for bit -- what
+    build_world_desc sets WD_PAIR on.  "one" / "empty": no record."""
+    b, w = member_zoo(rtsr, "instanced", layout)
+    flat = b.flatten(w)
+    host = _host_arrays()
+    entries, top = _array(orc, host, flat, "entries", FLAT_ENTRY), _array(orc, host, flat, "top_level", "<i4")
+    spheres = _array(orc, host, flat, "spheres", FLAT_SPHERE)
+    kinds = flat.top_level_kinds()
+    trees = [(int(e["b"]), int(e["c"])) for e in entries if e["kind"] == ENTRY_INSTANCE and e["a"] >= 0]
+    n_top = len(top)
+    if layout in ("one", "empty"):
+        assert trees == []
+        return
+    first, n = trees[0]
+    if layout == "middle":
+        assert len(trees) == 1 and first == 1 and first + n == n_top - 1
+    elif layout == "first":
+        assert len(trees) == 1 and first == 0 and kinds[0] == ENTRY_BVH and first + n < n_top
+    elif layout == "after_bvh":
+        assert len(trees) == 1 and first == 1 and kinds[0] == ENTRY_BVH and kinds[1] == ENTRY_BVH
+    elif layout == "last":
+        assert len(trees) == 1 and first == 2 and first + n == n_top
+    elif layout == "alone":
+        assert len(trees) == 1 and first == 0 and n == n_top
+    elif layout == "two":
+        assert len(trees) == 2 and first == 0 and trees[1][0] == n + 2 and trees[1][0] + trees[1][1] == n_top - 1
+    else:
+        assert layout == "pair" and len(trees) == 1
+        last = first + n - 1
+        A, M = entries[top[last]], entries[top[last + 1]]
+        assert A["kind"] == ENTRY_PRIM and int(A["a"]) >> 29 == PRIM_SPHERE and M["kind"] == ENTRY_MEDIUM
+        B = entries[M["a"]]
+        assert B["kind"] == ENTRY_PRIM and int(B["a"]) >> 29 == PRIM_SPHERE
+        sa, sb = spheres[int(A["a"]) & 0x1fffffff], spheres[int(B["a"]) & 0x1fffffff]
+        assert sa["c"].tobytes() == sb["c"].tobytes() and sa["radius"].tobytes() == sb["radius"].tobytes()
+
+
+def _pixels_equal(got, ref, spp):  # tests/test_gpu_f32_parity.py: pixels_equal
+    return (np.abs(got - ref) <= 1e-4 * np.abs(ref) + 1e-5 * spp).all(axis=2)
+
+
+@pytest.mark.parametrize("kind,layout", ZOO_F32_CAPPED + ZOO_F32_EXACT, ids=["%s-%s" % c for c in ZOO_F32_CAPPED + ZOO_F32_EXACT])
+def test_zoo_reference_alone_flip_rate(rtsr, orc, kind, layout):
+    """What the f32 GPU tests of the zoo rest on, measured on the CPU alone as tests/test_oracle_f32.py does for the catalogue:
+    O2f built with glibc's float functions against O2f with the same five computed in double, at the zoo's own frame, in both
+    spellings.  Tier-B cases: the unequal pixels are what ZOO_REFERENCE_ALONE_UNEQUAL records (and below 2 %).  Tier-A cases:
+    no bit of the frame depends on the platform functions."""
+    cam, cfg, h = zoo_cam_cfg(rtsr)
+    for spelling in ("hoisted", "instanced"):
+        b, w = member_zoo(rtsr, spelling, layout, plain=(kind == "plain"))
+        flat = b.flatten(w)
+        f, rf = orc.o2f_render(flat.arrays_ptr(), cam, cfg, h, threads=16)
+        g, rg = orc.o2f_render(flat.arrays_ptr(), cam, cfg, h, threads=16, via_f64=True)
+        unequal = int((~_pixels_equal(g, f, cfg.samples_per_pixel)).sum())
+        print("%s zoo %s %s: %d of %d pixels unequal between the two CPU builds (%d bit-different)"
+              % (kind, layout, spelling, unequal, f.shape[0] * f.shape[1], int((f != g).any(axis=2).sum())))
+        if (kind, layout) in ZOO_F32_EXACT:
+            assert np.array_equal(f, g) and np.array_equal(rf, rg)
+        else:
+            assert unequal == ZOO_REFERENCE_ALONE_UNEQUAL[(kind, layout)] and unequal <= 0.02 * f.shape[0] * f.shape[1]
