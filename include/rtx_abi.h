@@ -455,6 +455,51 @@ rtx_status rtx_render_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConf
 rtx_status rtx_progressive_create_ex(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
                                      const RtxShard* shard, const RtxIntegratorOptions* opt, rtx_progressive** out);
 
+/* ---- ray queries: closest-hit casts of ray batches on a resident scene ------------------------------------------------ */
+/* An extension: the caller's own rays against a resident scene -- picking, depth and visibility maps, occlusion, range
+ * sensors, collision probes.  Ray r of a batch is ONE call
+ *     world_hit(scene, Ray(origin_r, direction_r, time_r), t_min, t_max_r, rng_r)
+ * of the shared core (HittableList::hit, hit.rs:660-690): the call a path's bounce makes.  A ConstantMedium answers with its
+ * random hit, drawn from rng_r = rng_for_sample(seed + r * stream_step, 0, 0): stream_step 0 gives every ray the stream of
+ * the CPU checkers' probe, 1 a stream per ray.  There is no any-hit walk (it would change what a medium draws): an occlusion
+ * query is a cast that asks for `ids` alone.  Rays and results are f64 columns for both kinds of scene; an f32 scene narrows
+ * each ray component, t_min and t_max to float (the conversion of its camera rays) and widens what it writes.
+ * Results are deterministic and do not depend on how a batch is split into calls, provided the seed of a call whose first ray
+ * is ray `first` of the batch is seed + first * stream_step.
+ * On a scene with GravitySpheres a ray whose time lies more than 10 s past the spheres' stored trajectory is not cast (the
+ * reference's brute-force loop is unbounded there) and reports a miss.
+ * RTX_EINVAL before any device call: a NULL scene, batch or hits; n < 0; n > 0 with a NULL origin or direction; a NaN t_min or
+ * t_max_all -- the message names the field.  n = 0 is RTX_OK: nothing is launched, nothing written.  An all-NULL RtxRayHits
+ * with n > 0 is legal (a timing run). */
+typedef struct RtxRayBatch {
+  int64_t n;                 /* rays */
+  const double* origin;      /* [n][3] */
+  const double* direction;   /* [n][3], not normalised, as Ray::new takes it */
+  const double* time;        /* [n] or NULL: every ray at time 0 */
+  const double* t_max;       /* [n] or NULL: every ray to t_max_all */
+  double t_min, t_max_all;   /* the interval world_hit is called with; rtx_ray_batch_defaults: 0.001, +inf */
+  uint64_t seed;             /* rtx_ray_batch_defaults: 1 */
+  uint64_t stream_step;      /* 0: one stream for every ray; 1: a stream per ray */
+} RtxRayBatch;
+typedef struct RtxRayHits {  /* any pointer may be NULL: that column is not written */
+  double* t;                 /* [n]    +inf on a miss */
+  double* p;                 /* [n][3] HitRecord p      (0 on a miss) */
+  double* normal;            /* [n][3] HitRecord normal, face-forwarded as the record holds it (0 on a miss) */
+  double* uv;                /* [n][2] HitRecord u, v   (0 on a miss) */
+  int32_t* ids;              /* [n][4] {hit 0/1, material index of the flat scene, top-level slot, front_face}; miss: {0,-1,-1,0} */
+} RtxRayHits;
+/* Rays staged per slice by the host entry: at most RTX_CAST_HOST_SLICE * 144 bytes of device memory (56 in, 88 out a ray),
+ * whatever n is. */
+#define RTX_CAST_HOST_SLICE 262144
+/* Zeroes *b, then t_min = 0.001, t_max_all = +inf, seed = 1, stream_step = 0. */
+void rtx_ray_batch_defaults(RtxRayBatch* b);
+/* Host pointers, blocking. */
+rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits);
+/* Device pointers, asynchronous on hip_stream: returns after the launch.  uv and ids are stored 16 bytes at a time and must
+ * be 16-byte aligned, every other column 8: RTX_EINVAL naming the column otherwise, before any device call.  A batch of more
+ * than 2^30 rays goes out as several launches, none indexing past 2^31 rays. */
+rtx_status rtx_scene_cast_rays_device(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits, void* hip_stream);
+
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one
  * upload): 500 x 500, 500 spp, depth 50, background (0.7, 0.8, 1), camera (13,2,3) -> (0,0,0), vfov 20, aspect 1,

@@ -115,6 +115,19 @@ class RtxInstanceInfo(C.Structure):
     _fields_ = [("n_trees", C.c_int32), ("n_members", C.c_int32), ("n_nodes", C.c_int32), ("max_depth", C.c_int32)]
 
 
+class RtxRayBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("origin", C.c_void_p), ("direction", C.c_void_p), ("time", C.c_void_p),
+                ("t_max", C.c_void_p), ("t_min", C.c_double), ("t_max_all", C.c_double), ("seed", C.c_uint64),
+                ("stream_step", C.c_uint64)]
+
+
+class RtxRayHits(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("p", C.c_void_p), ("normal", C.c_void_p), ("uv", C.c_void_p), ("ids", C.c_void_p)]
+
+
+RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
+
+
 def _integrator_options(light_sampling):
     return RtxIntegratorOptions(1 if light_sampling else 0)
 
@@ -211,6 +224,9 @@ ABI = {
                                   C.POINTER(RtxFrame), C.POINTER(RtxRenderStats)]),
     "rtx_progressive_create_ex": (C.c_int32, [_VP, C.POINTER(RtxCamera), C.POINTER(RtxConfig), C.POINTER(RtxShard),
                                               C.POINTER(RtxIntegratorOptions), C.POINTER(_VP)]),
+    "rtx_ray_batch_defaults": (None, [C.POINTER(RtxRayBatch)]),
+    "rtx_scene_cast_rays": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits)]),
+    "rtx_scene_cast_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits), _VP]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -540,6 +556,98 @@ class Scene:
         stats = RtxRenderStats()
         _check(lib.rtx_render_count(self._p, C.byref(cam), C.byref(cfg), C.byref(sh) if sh else None, C.byref(stats)))
         return stats
+
+    def cast_rays(self, origins, directions, times=None, t_max=None, *, t_min=0.001, t_max_all=float("inf"), seed=1,
+                  stream_step=0, want=RAY_COLUMNS):
+        """Closest hits of a batch of rays (rtx_scene_cast_rays*): ray r is one world_hit(Ray(origins[r], directions[r],
+        times[r]), t_min, t_max[r]) on the stream of seed + r * stream_step -> RayHits holding the columns named in `want`.
+        numpy arrays go through the host entry and come back as numpy arrays.  torch tensors on the GPU are passed by
+        data_ptr(), without a copy: the results are torch tensors on that device and the call is only ENQUEUED on torch's
+        current stream for it.  Every array is float64 and C-contiguous: origins and directions (n, 3), times and t_max (n,)."""
+        return _cast_rays(self, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want)
+
+
+_RAY_COLUMN_SHAPES = {"t": (), "p": (3,), "normal": (3,), "uv": (2,), "ids": (4,)}
+
+
+class RayHits:
+    """What Scene.cast_rays returns: n and, for each requested column, an attribute of that name (None when not asked for).
+    t (n,) +inf on a miss; p, normal (n, 3); uv (n, 2); ids (n, 4) int32 {hit, material index, top-level slot, front_face},
+    {0, -1, -1, 0} on a miss."""
+
+    def __init__(self, n, columns):
+        self.n = n
+        self.columns = tuple(columns)
+        for name in RAY_COLUMNS:
+            setattr(self, name, columns.get(name))
+
+    @property
+    def hit(self):
+        return self.ids[:, 0] != 0 if self.ids is not None else None
+
+
+def _is_torch(a):
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want):
+    want = tuple(want)
+    for name in want:
+        if name not in RAY_COLUMNS:
+            raise ValueError("want: unknown column %r (expected some of %s)" % (name, ", ".join(RAY_COLUMNS)))
+    given = [("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)]
+    on_device = _is_torch(origins)
+    if on_device:
+        import torch  # only when the caller already holds tensors: the binding loads without torch
+    n = None
+    for name, a, width in given:
+        if a is None:
+            if width:
+                raise ValueError("%s: required" % name)
+            continue
+        if _is_torch(a) != on_device:
+            raise ValueError("%s: torch tensors and numpy arrays cannot be mixed in one call" % name)
+        if on_device:
+            if not a.is_cuda or a.device != origins.device:
+                raise ValueError("%s: must be a tensor on the GPU of origins (%s)" % (name, origins.device))
+            ok_dtype, contiguous = a.dtype == torch.float64, a.is_contiguous()
+        else:
+            if not isinstance(a, np.ndarray):
+                raise ValueError("%s: expected a numpy array or a torch tensor on the GPU" % name)
+            ok_dtype, contiguous = a.dtype == np.float64, a.flags["C_CONTIGUOUS"]
+        if not ok_dtype:
+            raise ValueError("%s: must be float64, not %s" % (name, a.dtype))
+        if not contiguous:
+            raise ValueError("%s: must be contiguous" % name)
+        shape = tuple(a.shape)
+        if len(shape) != (2 if width else 1) or (width and shape[1] != width):
+            raise ValueError("%s: expected shape %s, got %s" % (name, "(n, 3)" if width else "(n,)", shape))
+        if n is None:
+            n = shape[0]
+        elif shape[0] != n:
+            raise ValueError("%s: %d rays, but origins has %d" % (name, shape[0], n))
+    batch = RtxRayBatch()
+    lib.rtx_ray_batch_defaults(C.byref(batch))
+    batch.n, batch.t_min, batch.t_max_all, batch.seed, batch.stream_step = n, t_min, t_max_all, seed, stream_step
+    cols = {}
+    if on_device:
+        ptr = lambda a: a.data_ptr() if a is not None and n else None
+        for name in want:
+            cols[name] = torch.empty((n,) + _RAY_COLUMN_SHAPES[name], device=origins.device,
+                                     dtype=torch.int32 if name == "ids" else torch.float64)
+    else:
+        ptr = lambda a: a.ctypes.data if a is not None and n else None
+        for name in want:
+            cols[name] = np.empty((n,) + _RAY_COLUMN_SHAPES[name], dtype=np.int32 if name == "ids" else np.float64)
+    batch.origin, batch.direction, batch.time, batch.t_max = ptr(origins), ptr(directions), ptr(times), ptr(t_max)
+    hits = RtxRayHits(*[ptr(cols.get(name)) for name in RAY_COLUMNS])
+    if on_device:
+        with torch.cuda.device(origins.device):
+            stream = torch.cuda.current_stream(origins.device).cuda_stream
+            _check(lib.rtx_scene_cast_rays_device(scene.ptr, C.byref(batch), C.byref(hits), _VP(stream or None)))
+    else:
+        _check(lib.rtx_scene_cast_rays(scene.ptr, C.byref(batch), C.byref(hits)))
+    return RayHits(n, cols)
 
 
 class Progressive:

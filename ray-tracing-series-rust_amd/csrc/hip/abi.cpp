@@ -1,5 +1,6 @@
 // Host-only entry points of include/rtx_abi.h: builder (one call per reference constructor),
 // camera/config, scene catalogue, flatten, PPM output.  Device entry points: render.hip.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -12,6 +13,21 @@
 namespace rtx {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
+
+rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits) {
+  const char* bad = nullptr;
+  if (!s) bad = "scene is NULL";
+  else if (!rays) bad = "rays is NULL";
+  else if (!hits) bad = "hits is NULL";
+  else if (rays->n < 0) bad = "rays->n < 0";
+  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
+  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
+  else if (rays->t_min != rays->t_min) bad = "rays->t_min is NaN";
+  else if (rays->t_max_all != rays->t_max_all) bad = "rays->t_max_all is NaN";
+  if (!bad) return RTX_OK;
+  set_error(std::string(who) + ": " + bad);
+  return RTX_EINVAL;
+}
 }  // namespace rtx
 
 using namespace rtx;
@@ -242,6 +258,14 @@ rtx_status rtx_flat_instances(const rtx_flat* f, RtxInstanceInfo* o) {
   o->n_trees = s.n_instance_trees; o->n_members = s.n_instance_members;
   o->n_nodes = s.n_instance_nodes; o->max_depth = s.instance_depth;
   return RTX_OK;
+}
+
+void rtx_ray_batch_defaults(RtxRayBatch* b) {
+  if (!b) return;
+  memset(b, 0, sizeof(*b));
+  b->t_min = 0.001;
+  b->t_max_all = HUGE_VAL;
+  b->seed = 1;
 }
 
 int32_t rtx_flat_top_level_kind(const rtx_flat* f, int32_t index) {

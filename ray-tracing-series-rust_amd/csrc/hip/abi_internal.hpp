@@ -36,4 +36,8 @@ inline rtx_scene* make_scene_handle(void* ds, const RtxSceneOps* ops, int32_t f3
 }
 inline void free_scene_handle(rtx_scene* s) { delete s; }
 
+// The argument checks of rtx_scene_cast_rays and rtx_scene_cast_rays_device (abi.cpp; no device call): RTX_EINVAL with a
+// message that names the entry point `who` and the offending field.
+rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits);
+
 }  // namespace rtx

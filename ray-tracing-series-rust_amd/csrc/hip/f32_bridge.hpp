@@ -37,6 +37,8 @@ struct RtxSceneOps {
                          float4* d_normal, hipStream_t stream);
   rtx_status (*trim)(void* device_scene);
   void (*destroy)(void* device_scene);
+  // ray queries (cast_rays.inc: k_cast_rays): device pointers in both structs, arguments already checked
+  rtx_status (*cast_rays)(void* device_scene, const RtxRayBatch* rays, const RtxRayHits* hits, hipStream_t stream);
 };
 
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);

@@ -273,6 +273,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_wave.inc"    // k_wf_generate / k_wf_trace / k_wf_shade: the split-kernel integrator (path state in HBM)
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
+#include "cast_rays.inc"     // k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
@@ -1218,6 +1219,48 @@ static rtx_status features_impl(DeviceScene* ds, const RtxCamera* cam, const Rtx
   return RTX_OK;
 }
 
+// Ray queries (cast_rays.inc: k_cast_rays): the batch's rays against the scene, the requested columns written.  Device
+// pointers, asynchronous on stream; the arguments were checked by the entry point (check_cast).  A launch indexes rays with
+// 32 bits, so a batch goes out in slices of CAST_LAUNCH_RAYS, ray `first` of a slice on the stream seed + first * stream_step.
+static const int64_t CAST_LAUNCH_RAYS = (int64_t)1 << 30;
+static rtx_status launch_cast_rays(DeviceScene* ds, const RtxRayBatch* b, const RtxRayHits* h, hipStream_t stream) {
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("cast_rays: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
+  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("cast_rays: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
+  const uint32_t feat = ds->view.features;
+  for (int64_t first = 0; first < b->n; first += CAST_LAUNCH_RAYS) {
+    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, b->n - first);
+    CastArgs a;
+    a.origin = b->origin + 3 * first;
+    a.direction = b->direction + 3 * first;
+    a.time = b->time ? b->time + first : nullptr;
+    a.t_max = b->t_max ? b->t_max + first : nullptr;
+    a.t_min = b->t_min;
+    a.t_max_all = b->t_max_all;
+    a.time_limit = (feat & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
+    a.seed = b->seed + (uint64_t)first * b->stream_step;
+    a.stream_step = b->stream_step;
+    a.t = h->t ? h->t + first : nullptr;
+    a.p = h->p ? h->p + 3 * first : nullptr;
+    a.normal = h->normal ? h->normal + 3 * first : nullptr;
+    a.uv = h->uv ? h->uv + 2 * first : nullptr;
+    a.ids = h->ids ? h->ids + 4 * first : nullptr;
+    const uint32_t grid = grid_size(n, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
+#define LAUNCH_CAST(FEAT)                                                                                                     \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cast_rays<FEAT>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, \
+                       ds->view, a, n)
+    // the presets of k_features and k_trace_nee: instance trees, everything (GravitySpheres), any other world
+    if (feat & rt::F_INSTANCE) LAUNCH_CAST(P_INST);
+    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_CAST(P_ALL);
+    else LAUNCH_CAST(P_ANY);
+#undef LAUNCH_CAST
+    HIP_TRY(hipGetLastError());
+  }
+  return RTX_OK;
+}
+
 // Upload one flattened scene to the current device and plan the launches of every kernel family for it.
 static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   *out = nullptr;
@@ -1298,6 +1341,9 @@ static const RtxSceneOps scene_ops = {
        hipStream_t stream) { return features_impl((DeviceScene*)ds, cam, cfg, feature_spp, d_albedo, d_normal, stream); },
     [](void* ds) { return scene_trim_impl((DeviceScene*)ds); },
     [](void* ds) { free_device_scene((DeviceScene*)ds); },
+    [](void* ds, const RtxRayBatch* rays, const RtxRayHits* hits, hipStream_t stream) {
+      return launch_cast_rays((DeviceScene*)ds, rays, hits, stream);
+    },
 };
 
 }  // namespace rtx
@@ -1357,6 +1403,63 @@ rtx_status rtx_render_device(const rtx_scene* s, const RtxCamera* cam, const Rtx
                              const RtxShard* shard, double* d_accum_rgb, uint8_t* d_rgb8,
                              void* hip_stream, RtxRenderStats* stats) {
   return render_any(s, cam, cfg, shard, d_accum_rgb, d_rgb8, (hipStream_t)hip_stream, stats);
+}
+
+// ---- ray queries.  The arguments are checked first (abi.cpp: check_cast), before any device call.
+rtx_status rtx_scene_cast_rays_device(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits, void* hip_stream) {
+  const rtx_status st = check_cast("rtx_scene_cast_rays_device", s, rays, hits);
+  if (st != RTX_OK || rays->n == 0) return st;
+  // the kernel stores uv as double2 and ids as int4, and every other column as doubles
+  const struct { const void* p; uintptr_t mask; const char* name; } cols[] = {
+      {rays->origin, 7, "rays->origin"}, {rays->direction, 7, "rays->direction"}, {rays->time, 7, "rays->time"},
+      {rays->t_max, 7, "rays->t_max"},   {hits->t, 7, "hits->t"},                 {hits->p, 7, "hits->p"},
+      {hits->normal, 7, "hits->normal"}, {hits->uv, 15, "hits->uv"},              {hits->ids, 15, "hits->ids"}};
+  for (const auto& c : cols)
+    if ((uintptr_t)c.p & c.mask) {
+      set_error(std::string("rtx_scene_cast_rays_device: ") + c.name + " is not " + (c.mask == 15 ? "16" : "8") + "-byte aligned");
+      return RTX_EINVAL;
+    }
+  return s->ops->cast_rays(s->device_scene, rays, hits, (hipStream_t)hip_stream);
+}
+
+// Host pointers: slices of RTX_CAST_HOST_SLICE rays staged through device buffers (in: 56 B a ray, out: 88 B), one after the
+// other on the null stream; a slice's seed is advanced as the launcher advances a launch's.
+rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits) {
+  rtx_status st = check_cast("rtx_scene_cast_rays", s, rays, hits);
+  if (st != RTX_OK || rays->n == 0) return st;
+  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_CAST_HOST_SLICE);
+  DeviceBuffer<double> d_o, d_d, d_time, d_tmax, d_t, d_p, d_n, d_uv;
+  DeviceBuffer<int32_t> d_ids;
+  HIP_TRY(d_o.alloc(cap * 24));
+  HIP_TRY(d_d.alloc(cap * 24));
+  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
+  if (rays->t_max) HIP_TRY(d_tmax.alloc(cap * 8));
+  if (hits->t) HIP_TRY(d_t.alloc(cap * 8));
+  if (hits->p) HIP_TRY(d_p.alloc(cap * 24));
+  if (hits->normal) HIP_TRY(d_n.alloc(cap * 24));
+  if (hits->uv) HIP_TRY(d_uv.alloc(cap * 16));
+  if (hits->ids) HIP_TRY(d_ids.alloc(cap * 16));
+  for (int64_t first = 0; first < rays->n; first += RTX_CAST_HOST_SLICE) {
+    const size_t n = (size_t)std::min<int64_t>(RTX_CAST_HOST_SLICE, rays->n - first);
+    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
+    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
+    if (rays->t_max) HIP_TRY(hipMemcpy(d_tmax, rays->t_max + first, n * 8, hipMemcpyHostToDevice));
+    RtxRayBatch b = *rays;
+    b.n = (int64_t)n;
+    b.origin = d_o; b.direction = d_d; b.time = d_time; b.t_max = d_tmax;
+    b.seed = rays->seed + (uint64_t)first * rays->stream_step;
+    const RtxRayHits h = {d_t, d_p, d_n, d_uv, d_ids};
+    if ((st = s->ops->cast_rays(s->device_scene, &b, &h, (hipStream_t) nullptr)) != RTX_OK) return st;
+    // (a blocking copy on the null stream waits for the launch)
+    if (hits->t) HIP_TRY(hipMemcpy(hits->t + first, d_t, n * 8, hipMemcpyDeviceToHost));
+    if (hits->p) HIP_TRY(hipMemcpy(hits->p + 3 * first, d_p, n * 24, hipMemcpyDeviceToHost));
+    if (hits->normal) HIP_TRY(hipMemcpy(hits->normal + 3 * first, d_n, n * 24, hipMemcpyDeviceToHost));
+    if (hits->uv) HIP_TRY(hipMemcpy(hits->uv + 2 * first, d_uv, n * 16, hipMemcpyDeviceToHost));
+    if (hits->ids) HIP_TRY(hipMemcpy(hits->ids + 4 * first, d_ids, n * 16, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxRayHits (a timing run) still returns after its launches
+  return RTX_OK;
 }
 
 rtx_status rtx_render_count(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
