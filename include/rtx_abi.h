@@ -21,6 +21,8 @@
  * render workspace (sample buffer, accumulators, work counter, timers): at most ONE render call may be in flight per
  * rtx_scene at a time -- calls on one handle must come from one thread at a time and, for rtx_render_device, on one
  * stream; concurrent renders of the same scene need one rtx_scene each (rtx_scene_upload is cheap next to a render).
+ * A radiance query (rtx_scene_trace_rays*) uses that workspace and counts as a render call here; a ray query
+ * (rtx_scene_cast_rays*) does not touch it.
  * The workspace is kept until rtx_scene_destroy or rtx_scene_trim (default budget of the sample buffer: 24 GiB).
  */
 #ifndef RTX_ABI_H
@@ -227,7 +229,8 @@ enum {
   RTX_KERNEL_WQ = 5,         /* retired: workgroup-level path queues in LDS */
   RTX_KERNEL_WORLD = 6,      /* any world: per-lane scan of the world list, walks of every BVH entry carried over */
   RTX_KERNEL_WAVEFRONT = 7,  /* split-kernel integrator: path state in HBM, k_wf_generate / k_wf_trace / k_wf_shade per bounce */
-  RTX_KERNEL_NEE = 8         /* next-event estimation (rtx_render_ex with light_sampling = 1): persistent waves, whole paths per lane */
+  RTX_KERNEL_NEE = 8,        /* next-event estimation (rtx_render_ex with light_sampling = 1): persistent waves, whole paths per lane */
+  RTX_KERNEL_RAYS = 9        /* radiance queries (rtx_scene_trace_rays*): RTX_KERNEL_NEE's scheduling, paths that start from the caller's rays */
 };
 const char* rtx_trace_kernel_name(int32_t kernel);
 /* Blocking; host output buffers.  Renders the whole image on the current device. */
@@ -499,6 +502,57 @@ rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, cons
  * be 16-byte aligned, every other column 8: RTX_EINVAL naming the column otherwise, before any device call.  A batch of more
  * than 2^30 rays goes out as several launches, none indexing past 2^31 rays. */
 rtx_status rtx_scene_cast_rays_device(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits, void* hip_stream);
+
+/* ---- radiance queries: the estimator's radiance along a caller's rays on a resident scene ------------------------------ */
+/* An extension: what the path tracer gathers along the caller's own rays -- fisheye, equirectangular or orthographic cameras,
+ * light-map and irradiance-probe bakes, radiance caches, sensor models.  Sample s of ray r is ONE path of the estimator
+ * (ray_color's loop, world.rs:52-93; with light_sampling = 1 the estimator of RtxIntegratorOptions) that starts from
+ * Ray(origin_r, direction_r, time_r) AS GIVEN: no jitter, lens or shutter draw is made, so the first draw of its stream
+ *     rng_for_sample(seed, first_ray + r, first_sample + s)
+ * belongs to the first bounce.  sum_rgb[r] is the sum of the ray's samples added in ascending sample order and sumsq_rgb[r]
+ * the per-channel sum of their squares (Q of the progressive interface; square and add separately rounded).  Rays are f64
+ * columns for both kinds of scene; an f32 scene narrows each ray component to float and its sums add widened floats.
+ * THE CONTRACT: a ray's sums depend only on (scene, ray, first_ray + r, seed, the sample range, max_depth, background,
+ * estimator) -- not on how the batch is cut into calls, staging slices, launches or passes.  With accumulate = 1, two calls
+ * over the samples [0, a) and [a, a + b) leave the bits of one call over [0, a + b).
+ * On a scene with GravitySpheres a ray whose time lies more than 10 s past the spheres' stored trajectory is not traced (the
+ * reference's brute-force loop is unbounded there): every sample of it is NaN, so its sums are NaN -- not a dark ray.
+ * A radiance query uses the scene's render workspace: the one-render-in-flight-per-rtx_scene rule at the top of this header
+ * applies to it (rtx_scene_cast_rays* does not use the workspace and may run beside it).
+ * RTX_EINVAL before any device call, the message naming the field: a NULL scene, struct or sum_rgb; n < 0; n > 0 with a NULL
+ * origin or direction; samples < 1; max_depth < 1; a non-zero reserved; a light_sampling or accumulate other than 0 / 1; a
+ * NaN background; first_sample + samples past 2^32; (device entry) a pointer that is not 8-byte aligned.  An f32 scene with
+ * light_sampling = 1 is RTX_EUNSUPPORTED.  n = 0 is RTX_OK: nothing is launched, nothing written. */
+typedef struct RtxRadianceRays {   /* 104 B */
+  int64_t n;                 /* rays */
+  const double* origin;      /* [n][3] */
+  const double* direction;   /* [n][3], not normalised, as Ray::new takes it */
+  const double* time;        /* [n] or NULL: every ray at time 0 */
+  uint64_t first_ray;        /* index of ray 0 in the caller's whole batch: the stream key's pixel word */
+  uint32_t first_sample;     /* absolute index of the first sample traced by this call */
+  int32_t samples;           /* >= 1 */
+  int32_t max_depth;         /* >= 1, Config::new's rule */
+  int32_t accumulate;        /* 0: sums start at 0; 1: sum_rgb / sumsq_rgb are continued in place */
+  uint64_t seed;
+  double background[3];
+  int32_t light_sampling;    /* RtxIntegratorOptions' meaning; f32 scene with 1: RTX_EUNSUPPORTED */
+  int32_t reserved;          /* must be 0 */
+  uint64_t sample_buffer_bytes; /* RtxConfig's meaning: 0 = the default budget */
+} RtxRadianceRays;
+/* Rays staged per slice by the host entry: at most RTX_TRACE_HOST_SLICE * 104 bytes of device memory (56 in, 48 of sums a ray)
+ * beside the workspace, whatever n is.  Slice k traces with first_ray + its offset. */
+#define RTX_TRACE_HOST_SLICE 262144
+/* Zeroes *r, then samples = 1, max_depth = 50, seed = 1, background = (0.7, 0.8, 1). */
+void rtx_radiance_rays_defaults(RtxRadianceRays* r);
+/* Host pointers, blocking.  sum_rgb [n][3] is required, sumsq_rgb [n][3] and stats are optional.  stats->trace_kernel is
+ * RTX_KERNEL_RAYS, stats->samples = n * samples. */
+rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays, double* sum_rgb, double* sumsq_rgb,
+                                RtxRenderStats* stats);
+/* Device pointers, asynchronous on hip_stream: returns after the launches unless stats is not NULL, which synchronises (as in
+ * rtx_render_device).  A batch of more than 2^30 rays goes out as several launches; a pass's (sample, ray) index space stays
+ * below 0xFFFF0000. */
+rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
+                                       void* hip_stream, RtxRenderStats* stats);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

@@ -125,6 +125,14 @@ class RtxRayHits(C.Structure):
     _fields_ = [("t", C.c_void_p), ("p", C.c_void_p), ("normal", C.c_void_p), ("uv", C.c_void_p), ("ids", C.c_void_p)]
 
 
+class RtxRadianceRays(C.Structure):
+    _fields_ = [("n", C.c_int64), ("origin", C.c_void_p), ("direction", C.c_void_p), ("time", C.c_void_p),
+                ("first_ray", C.c_uint64), ("first_sample", C.c_uint32), ("samples", C.c_int32), ("max_depth", C.c_int32),
+                ("accumulate", C.c_int32), ("seed", C.c_uint64), ("background", C.c_double * 3),
+                ("light_sampling", C.c_int32), ("reserved", C.c_int32), ("sample_buffer_bytes", C.c_uint64)]
+
+
+RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
 
 
@@ -227,6 +235,9 @@ ABI = {
     "rtx_ray_batch_defaults": (None, [C.POINTER(RtxRayBatch)]),
     "rtx_scene_cast_rays": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits)]),
     "rtx_scene_cast_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits), _VP]),
+    "rtx_radiance_rays_defaults": (None, [C.POINTER(RtxRadianceRays)]),
+    "rtx_scene_trace_rays": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_scene_trace_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -566,6 +577,19 @@ class Scene:
         current stream for it.  Every array is float64 and C-contiguous: origins and directions (n, 3), times and t_max (n,)."""
         return _cast_rays(self, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want)
 
+    def trace_rays(self, origins, directions, times=None, *, spp=1, max_depth=50, background=(0.7, 0.8, 1.0), seed=1,
+                   first_sample=0, first_ray=0, light_sampling=False, sumsq=False, out=None, sample_buffer_bytes=0,
+                   want_stats=False):
+        """The estimator's radiance along a batch of rays (rtx_scene_trace_rays*): samples first_sample .. first_sample + spp - 1
+        of every ray, each a whole path that starts from Ray(origins[r], directions[r], times[r]) as given, on the stream of
+        (seed, first_ray + r, sample) -> RadianceSums with .sum (n, 3), .sumsq (n, 3) or None, .spp and .mean.  Arrays as in
+        cast_rays: numpy goes through the host entry; torch tensors on the GPU are passed by data_ptr() and the call is only
+        ENQUEUED on torch's current stream (want_stats=True synchronises).  out=: a RadianceSums of the same rays whose sums
+        are continued in place; first_sample must then be out.spp.  Uses the scene's render workspace: one render or radiance
+        query in flight per Scene."""
+        return _trace_rays(self, origins, directions, times, spp, max_depth, background, seed, first_sample, first_ray,
+                           light_sampling, sumsq, out, sample_buffer_bytes, want_stats)
+
 
 _RAY_COLUMN_SHAPES = {"t": (), "p": (3,), "normal": (3,), "uv": (2,), "ids": (4,)}
 
@@ -590,12 +614,10 @@ def _is_torch(a):
     return type(a).__module__.split(".")[0] == "torch"
 
 
-def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want):
-    want = tuple(want)
-    for name in want:
-        if name not in RAY_COLUMNS:
-            raise ValueError("want: unknown column %r (expected some of %s)" % (name, ", ".join(RAY_COLUMNS)))
-    given = [("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)]
+def _ray_arrays(given):
+    """Checks the arrays of a ray batch -- (name, array or None, width: 3 for an (n, 3) column, 0 for an (n,) one), origins
+    first -- and returns (n, on_device): float64, contiguous, of one kind (numpy, or torch on one GPU) and one length."""
+    origins = given[0][1]
     on_device = _is_torch(origins)
     if on_device:
         import torch  # only when the caller already holds tensors: the binding loads without torch
@@ -626,6 +648,17 @@ def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed,
             n = shape[0]
         elif shape[0] != n:
             raise ValueError("%s: %d rays, but origins has %d" % (name, shape[0], n))
+    return n, on_device
+
+
+def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want):
+    want = tuple(want)
+    for name in want:
+        if name not in RAY_COLUMNS:
+            raise ValueError("want: unknown column %r (expected some of %s)" % (name, ", ".join(RAY_COLUMNS)))
+    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
+    if on_device:
+        import torch
     batch = RtxRayBatch()
     lib.rtx_ray_batch_defaults(C.byref(batch))
     batch.n, batch.t_min, batch.t_max_all, batch.seed, batch.stream_step = n, t_min, t_max_all, seed, stream_step
@@ -648,6 +681,71 @@ def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed,
     else:
         _check(lib.rtx_scene_cast_rays(scene.ptr, C.byref(batch), C.byref(hits)))
     return RayHits(n, cols)
+
+
+class RadianceSums:
+    """What Scene.trace_rays returns: n rays, spp samples summed per ray so far; sum (n, 3) and sumsq (n, 3) or None (numpy
+    arrays, or torch tensors on the rays' device); mean = sum / spp."""
+
+    def __init__(self, n, spp, sum, sumsq, stats=None):
+        self.n, self.spp, self.sum, self.sumsq, self.stats = n, spp, sum, sumsq, stats
+
+    @property
+    def mean(self):
+        return self.sum / self.spp
+
+
+def _trace_rays(scene, origins, directions, times, spp, max_depth, background, seed, first_sample, first_ray, light_sampling,
+                sumsq, out, sample_buffer_bytes, want_stats):
+    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0)])
+    if on_device:
+        import torch
+    for name, v, lo in (("spp", spp, 1), ("max_depth", max_depth, 1), ("first_sample", first_sample, 0), ("first_ray", first_ray, 0)):
+        if int(v) != v or v < lo:
+            raise ValueError("%s: must be an integer >= %d, not %r" % (name, lo, v))
+    if first_sample + spp > 2 ** 32:
+        raise ValueError("first_sample: first_sample + spp is past 2^32")
+    background = tuple(float(c) for c in background)
+    if len(background) != 3 or any(c != c for c in background):
+        raise ValueError("background: three numbers, none a NaN")
+    if out is not None:
+        if not isinstance(out, RadianceSums):
+            raise ValueError("out: expected what an earlier trace_rays call returned")
+        if out.n != n or _is_torch(out.sum) != on_device or (on_device and out.sum.device != origins.device):
+            raise ValueError("out: holds %d rays of another kind or device, the batch has %d" % (out.n, n))
+        if first_sample != out.spp:
+            raise ValueError("out: holds %d samples per ray, so first_sample must be %d, not %d" % (out.spp, out.spp, first_sample))
+        if sumsq and out.sumsq is None:
+            raise ValueError("out: has no sumsq to continue")
+        s_arr, q_arr = out.sum, out.sumsq
+    elif on_device:
+        s_arr = torch.empty((n, 3), device=origins.device, dtype=torch.float64)
+        q_arr = torch.empty((n, 3), device=origins.device, dtype=torch.float64) if sumsq else None
+    else:
+        s_arr = np.empty((n, 3), dtype=np.float64)
+        q_arr = np.empty((n, 3), dtype=np.float64) if sumsq else None
+    q = RtxRadianceRays()
+    lib.rtx_radiance_rays_defaults(C.byref(q))
+    ptr = (lambda a: a.data_ptr() if a is not None and n else None) if on_device else (lambda a: a.ctypes.data if a is not None and n else None)
+    q.n, q.origin, q.direction, q.time = n, ptr(origins), ptr(directions), ptr(times)
+    q.first_ray, q.first_sample, q.samples, q.max_depth = first_ray, first_sample, spp, max_depth
+    q.accumulate, q.seed, q.light_sampling, q.sample_buffer_bytes = 1 if out is not None else 0, seed, 1 if light_sampling else 0, sample_buffer_bytes
+    q.background[:] = background
+    stats = RtxRenderStats() if want_stats else None
+    # (n = 0: the entry still wants a sum pointer; any non-NULL one does, nothing is written)
+    sp = _VP((s_arr.data_ptr() if on_device else s_arr.ctypes.data) or 8)
+    qp = _VP(ptr(q_arr))
+    if on_device:
+        with torch.cuda.device(origins.device):
+            stream = torch.cuda.current_stream(origins.device).cuda_stream
+            _check(lib.rtx_scene_trace_rays_device(scene.ptr, C.byref(q), sp, qp, _VP(stream or None), C.byref(stats) if stats else None))
+    else:
+        _check(lib.rtx_scene_trace_rays(scene.ptr, C.byref(q), sp, qp, C.byref(stats) if stats else None))
+    if out is not None:
+        out.spp += spp
+        out.stats = stats
+        return out
+    return RadianceSums(n, spp, s_arr, q_arr, stats)
 
 
 class Progressive:

@@ -284,4 +284,39 @@ RT_HD Color trace_sample(const SceneView& sv, const RenderParams& rp, uint32_t i
   return ps.output;
 }
 
+// ---- radiance queries: a path that starts from a caller's ray (rtx_scene_trace_rays*) ------------
+// The ray is taken as given: no jitter, lens or shutter draw is made, so the first draw of the stream of
+// (seed, ray_index, sample) belongs to the first bounce.  rp's camera and image size are not read.
+RT_HD void path_begin_ray(const RenderParams& rp, const Ray& ray, uint64_t ray_index, uint32_t sample, PathState* ps) {
+  ps->rng = rng_for_sample(rp.seed, ray_index, sample);
+  ps->ray = ray;
+  ps->product = v3(1, 1, 1);
+  ps->output = v3(0, 0, 0);
+  ps->depth = rp.max_depth;
+}
+
+// Whole sample of a given ray on one thread (the host checker; k_trace_rays runs the same steps).
+template <uint32_t F, bool COUNT, class STACK>
+RT_HD Color trace_ray_sample(const SceneView& sv, const RenderParams& rp, const Ray& ray, uint64_t ray_index, uint32_t sample,
+                             STACK& stack, TraceCounters* cnt) {
+  PathState ps;
+  path_begin_ray(rp, ray, ray_index, sample, &ps);
+  if (COUNT) cnt->samples++;
+  while (!path_step<F, COUNT>(sv, rp, &ps, stack, cnt)) {
+  }
+  return ps.output;
+}
+
+template <uint32_t F, bool COUNT, class STACK>
+RT_HD Color trace_ray_sample_nee(const SceneView& sv, const LightView& lv, const RenderParams& rp, const Ray& ray,
+                                 uint64_t ray_index, uint32_t sample, STACK& stack, TraceCounters* cnt) {
+  PathState ps;
+  path_begin_ray(rp, ray, ray_index, sample, &ps);
+  if (COUNT) cnt->samples++;
+  real last_pdf = real(-1.0);
+  while (!path_step_nee<F, COUNT>(sv, lv, rp, &ps, &last_pdf, stack, cnt)) {
+  }
+  return ps.output;
+}
+
 }  // namespace rt

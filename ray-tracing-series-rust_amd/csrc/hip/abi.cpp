@@ -28,6 +28,26 @@ rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* ra
   set_error(std::string(who) + ": " + bad);
   return RTX_EINVAL;
 }
+rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb) {
+  const char* bad = nullptr;
+  if (!s) bad = "scene is NULL";
+  else if (!rays) bad = "rays is NULL";
+  else if (!sum_rgb) bad = "sum_rgb is NULL";
+  else if (rays->n < 0) bad = "rays->n < 0";
+  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
+  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
+  else if (rays->samples < 1) bad = "rays->samples < 1";
+  else if (rays->max_depth < 1) bad = "rays->max_depth < 1 (Config::new asserts max_depth > 0, world.rs:36-40)";
+  else if (rays->reserved != 0) bad = "rays->reserved is not 0";
+  else if (rays->light_sampling != 0 && rays->light_sampling != 1) bad = "rays->light_sampling is neither 0 nor 1";
+  else if (rays->accumulate != 0 && rays->accumulate != 1) bad = "rays->accumulate is neither 0 nor 1";
+  else if (rays->background[0] != rays->background[0] || rays->background[1] != rays->background[1] ||
+           rays->background[2] != rays->background[2]) bad = "rays->background is NaN";
+  else if ((uint64_t)rays->first_sample + (uint64_t)rays->samples > (1ull << 32)) bad = "rays->first_sample + rays->samples is past 2^32";
+  if (!bad) return RTX_OK;
+  set_error(std::string(who) + ": " + bad);
+  return RTX_EINVAL;
+}
 }  // namespace rtx
 
 using namespace rtx;
@@ -56,6 +76,7 @@ const char* rtx_trace_kernel_name(int32_t kernel) {
     case RTX_KERNEL_WORLD: return "k_trace_world";
     case RTX_KERNEL_WAVEFRONT: return "k_wf_trace";
     case RTX_KERNEL_NEE: return "k_trace_nee";
+    case RTX_KERNEL_RAYS: return "k_trace_rays";
     default: return "?";
   }
 }
@@ -266,6 +287,15 @@ void rtx_ray_batch_defaults(RtxRayBatch* b) {
   b->t_min = 0.001;
   b->t_max_all = HUGE_VAL;
   b->seed = 1;
+}
+
+void rtx_radiance_rays_defaults(RtxRadianceRays* r) {
+  if (!r) return;
+  memset(r, 0, sizeof(*r));
+  r->samples = 1;
+  r->max_depth = 50;
+  r->seed = 1;
+  r->background[0] = 0.7; r->background[1] = 0.8; r->background[2] = 1.0;
 }
 
 int32_t rtx_flat_top_level_kind(const rtx_flat* f, int32_t index) {

@@ -39,5 +39,7 @@ inline void free_scene_handle(rtx_scene* s) { delete s; }
 // The argument checks of rtx_scene_cast_rays and rtx_scene_cast_rays_device (abi.cpp; no device call): RTX_EINVAL with a
 // message that names the entry point `who` and the offending field.
 rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits);
+// The same for rtx_scene_trace_rays and rtx_scene_trace_rays_device.
+rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb);
 
 }  // namespace rtx

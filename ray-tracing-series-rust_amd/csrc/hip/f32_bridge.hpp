@@ -39,6 +39,10 @@ struct RtxSceneOps {
   void (*destroy)(void* device_scene);
   // ray queries (cast_rays.inc: k_cast_rays): device pointers in both structs, arguments already checked
   rtx_status (*cast_rays)(void* device_scene, const RtxRayBatch* rays, const RtxRayHits* hits, hipStream_t stream);
+  // radiance queries (trace_rays.inc: k_trace_rays): device pointers, arguments already checked; stats may be NULL, non-NULL
+  // synchronises.  Uses the scene's render workspace.
+  rtx_status (*trace_rays)(void* device_scene, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
+                           hipStream_t stream, RtxRenderStats* stats);
 };
 
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);

@@ -274,6 +274,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
 #include "cast_rays.inc"     // k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
+#include "trace_rays.inc"    // k_trace_rays: the estimator's radiance along a caller's rays (rtx_scene_trace_rays*)
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
@@ -969,16 +970,17 @@ struct PassPlan {
   size_t sample_bytes;
 };
 
-// Sizes the passes of a render of spp samples of npix pixels and grows the workspace for them (accum: the caller's accumulator,
-// or NULL for the scene's own).  serial: the counting / timing entry points, which synchronise per pass.
-static rtx_status prepare_workspace(DeviceScene* ds, const RtxConfig* cfg, uint64_t npix, uint64_t npix_all, uint32_t spp, bool serial,
-                                    hipStream_t stream, double** accum, PassPlan* pp) {
+// Sizes the passes of a render of spp samples of npix pixels (a radiance query: rays) and grows the workspace for them (accum:
+// the caller's accumulator, or NULL for the scene's own).  sample_buffer_bytes: RtxConfig's field, 0 for the default budget.
+// serial: the counting / timing entry points, which synchronise per pass.
+static rtx_status prepare_workspace(DeviceScene* ds, uint64_t sample_buffer_bytes, uint64_t npix, uint64_t npix_all, uint32_t spp,
+                                    bool serial, hipStream_t stream, double** accum, PassPlan* pp) {
   Workspace& ws = ds->ws;
   // Default budget: 24 GiB (of 288 GB: C5 takes 16 passes instead of 67, C3 10 instead of 40), but never more than a third of the
   // HBM that is free right now plus what this handle already holds -- other scene handles, a second frame in flight, torch's caching
   // allocator or a smaller part shrink it, and a frame then takes more passes instead of failing.  An explicit
-  // cfg->sample_buffer_bytes is taken as given.
-  uint64_t budget = cfg->sample_buffer_bytes;
+  // sample_buffer_bytes is taken as given.
+  uint64_t budget = sample_buffer_bytes;
   if (budget == 0) {
     budget = 24ull << 30;
     size_t free_b = 0, total_b = 0;
@@ -1075,7 +1077,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   const uint64_t nitem = adaptive ? range->n_active : npix;  // pixels of every sample of a pass
   double* accum = d_accum_out;
   PassPlan pp;
-  st = prepare_workspace(ds, cfg, nitem, npix_all, spp, COUNT || stats != nullptr, stream, &accum, &pp);
+  st = prepare_workspace(ds, cfg->sample_buffer_bytes, nitem, npix_all, spp, COUNT || stats != nullptr, stream, &accum, &pp);
   if (st != RTX_OK) return st;
   Workspace& ws = ds->ws;
   if (COUNT) HIP_TRY(hipMemsetAsync(ws.counters, 0, sizeof(rt::TraceCounters), stream));
@@ -1261,6 +1263,126 @@ static rtx_status launch_cast_rays(DeviceScene* ds, const RtxRayBatch* b, const 
   return RTX_OK;
 }
 
+// One pass of a radiance query (trace_rays.inc: k_trace_rays) on `stream`: its work counter zeroed, then the persistent launch --
+// as many blocks as are resident, at most one wave per TRACE_CHUNK items (launch_nee's rule).
+static rtx_status launch_trace_rays_pass(const DeviceScene* ds, const rt::RenderParams& rp, const RadianceArgs& ra, bool nee,
+                                         uint32_t s_begin, uint32_t total, uint32_t n, double* samples, unsigned int* work_counter,
+                                         size_t stack_lds, hipStream_t stream) {
+  HIP_TRY(hipMemsetAsync(work_counter, 0, sizeof(unsigned int), stream));
+  const uint32_t feat = ds->view.features;
+#define LAUNCH_RAYS(FEAT, NEE)                                                                                                   \
+  do {                                                                                                                          \
+    const int nb = occupancy(k_trace_rays<FEAT, NEE>, stack_lds);                                                               \
+    const uint32_t grid = grid_size(total, TRACE_CHUNK, (uint64_t)ds->n_cu * (uint64_t)(nb > 0 ? nb : 1) * (TRACE_BLOCK / 64)); \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_rays<FEAT, NEE>), dim3((grid + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64)),      \
+                       dim3(TRACE_BLOCK), stack_lds, stream, ds->view, ds->lights, rp, ra, s_begin, total, n, samples,          \
+                       work_counter);                                                                                           \
+  } while (0)
+  // the presets of k_cast_rays and k_features: instance trees, everything (GravitySpheres), any other world
+#ifndef RTX_F32_TU
+  if (nee) {
+    if (feat & rt::F_INSTANCE) LAUNCH_RAYS(P_INST, true);
+    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_RAYS(P_ALL, true);
+    else LAUNCH_RAYS(P_ANY, true);
+  } else
+#endif
+  {
+    if (feat & rt::F_INSTANCE) LAUNCH_RAYS(P_INST, false);
+    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_RAYS(P_ALL, false);
+    else LAUNCH_RAYS(P_ANY, false);
+  }
+#undef LAUNCH_RAYS
+  HIP_TRY(hipGetLastError());
+  return RTX_OK;
+}
+
+// Radiance queries (trace_rays.inc: k_trace_rays): q->samples samples of the estimator along every ray of the batch, summed in
+// sample order onto d_sum (and their squares onto d_sumsq unless NULL).  Device pointers, asynchronous on stream unless stats
+// is asked for; the arguments were checked by the entry point (check_trace_rays).  Passes are planned by prepare_workspace and
+// run as a render's do: two deep when the sample buffer does not hold the call, even passes on the caller's stream, odd ones on
+// ws.aux_stream, reductions in pass order.  A launch indexes rays with 32 bits, so a batch goes out in slices of
+// CAST_LAUNCH_RAYS, ray r of a slice that starts at `first` on the stream of first_ray + first + r.
+static rtx_status trace_rays_impl(DeviceScene* ds, const RtxRadianceRays* q, double* d_sum, double* d_sumsq, hipStream_t stream,
+                                  RtxRenderStats* stats) {
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("trace_rays: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
+  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("trace_rays: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
+  const bool nee = q->light_sampling != 0;
+#ifdef RTX_F32_TU
+  if (nee) { set_error("trace_rays: light sampling is f64 only"); return RTX_EUNSUPPORTED; }  // (the entry points reject it first)
+#endif
+  rt::RenderParams rp;
+  memset(&rp, 0, sizeof(rp));  // no camera, no image: path_begin_ray reads neither
+  rp.background = rt::v3(q->background[0], q->background[1], q->background[2]);
+  rp.samples_per_pixel = q->samples;
+  rp.max_depth = q->max_depth;
+  rp.seed = q->seed;
+  const uint32_t spp = (uint32_t)q->samples;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  Workspace& ws = ds->ws;
+  float trace_ms = 0.f;
+  int passes = 0;
+  size_t sample_bytes = 0;
+  for (int64_t first = 0; first < q->n; first += CAST_LAUNCH_RAYS) {
+    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, q->n - first);
+    double* sum = d_sum + 3 * first;
+    double* sumsq = d_sumsq ? d_sumsq + 3 * first : nullptr;
+    PassPlan pp;
+    const rtx_status st = prepare_workspace(ds, q->sample_buffer_bytes, n, n, spp, stats != nullptr, stream, &sum, &pp);
+    if (st != RTX_OK) return st;
+    sample_bytes = std::max(sample_bytes, pp.sample_bytes);
+    RadianceArgs ra;
+    ra.origin = q->origin + 3 * first;
+    ra.direction = q->direction + 3 * first;
+    ra.time = q->time ? q->time + first : nullptr;
+    ra.time_limit = (ds->view.features & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
+    ra.first_ray = q->first_ray + (uint64_t)first;
+    if (pp.pipeline) {
+      HIP_TRY(hipEventRecord(ws.ev_pass[2], stream));
+      HIP_TRY(hipStreamWaitEvent(ws.aux_stream, ws.ev_pass[2], 0));
+    }
+    int k = 0;  // passes of this launch slice
+    for (uint32_t s_off = 0; s_off < spp; s_off += pp.spp_pass, ++k, ++passes) {
+      const int half = pp.pipeline ? (k & 1) : 0;
+      const uint32_t s_count = spp - s_off < pp.spp_pass ? spp - s_off : pp.spp_pass;
+      const uint32_t total = (uint32_t)((uint64_t)s_count * n);
+      const hipStream_t ps = half ? ws.aux_stream : stream;
+      double* samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)n * 3u;
+      if (stats) HIP_TRY(hipEventRecord(ws.ev[0], ps));
+      const rtx_status lst = launch_trace_rays_pass(ds, rp, ra, nee, q->first_sample + s_off, total, n, samples, ws.work_counter + half,
+                                                    stack_bytes(stack_levels), ps);
+      if (lst != RTX_OK) return lst;
+      if (stats) {
+        HIP_TRY(hipEventRecord(ws.ev[1], ps));
+        HIP_TRY(hipEventSynchronize(ws.ev[1]));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]));
+        trace_ms += ms;
+      }
+      const uint32_t pgrid = (n + 255u) / 256u;
+      if (pp.pipeline && k > 0) HIP_TRY(hipStreamWaitEvent(ps, ws.ev_pass[1 - half], 0));  // the previous pass's sums are in
+      const int first_pass = s_off == 0 && !q->accumulate ? 1 : 0;
+      if (sumsq) hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, ps, samples, sum, sumsq, n, s_count, first_pass);
+      else hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, ps, samples, sum, n, s_count, first_pass);
+      HIP_TRY(hipGetLastError());
+      if (pp.pipeline) HIP_TRY(hipEventRecord(ws.ev_pass[half], ps));
+    }
+    if (pp.pipeline && k > 0 && ((k - 1) & 1)) HIP_TRY(hipStreamWaitEvent(stream, ws.ev_pass[1], 0));
+  }
+  if (stats) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    stats->trace_ms = trace_ms;
+    stats->trace_launches = passes;
+    stats->passes = passes;
+    stats->trace_kernel = RTX_KERNEL_RAYS;
+    stats->sample_buffer_bytes = sample_bytes;
+    stats->samples = (uint64_t)spp * (uint64_t)q->n;
+  }
+  return RTX_OK;
+}
+
 // Upload one flattened scene to the current device and plan the launches of every kernel family for it.
 static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
   *out = nullptr;
@@ -1343,6 +1465,9 @@ static const RtxSceneOps scene_ops = {
     [](void* ds) { free_device_scene((DeviceScene*)ds); },
     [](void* ds, const RtxRayBatch* rays, const RtxRayHits* hits, hipStream_t stream) {
       return launch_cast_rays((DeviceScene*)ds, rays, hits, stream);
+    },
+    [](void* ds, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb, hipStream_t stream, RtxRenderStats* stats) {
+      return trace_rays_impl((DeviceScene*)ds, rays, d_sum_rgb, d_sumsq_rgb, stream, stats);
     },
 };
 
@@ -1459,6 +1584,75 @@ rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, cons
     if (hits->ids) HIP_TRY(hipMemcpy(hits->ids + 4 * first, d_ids, n * 16, hipMemcpyDeviceToHost));
   }
   HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxRayHits (a timing run) still returns after its launches
+  return RTX_OK;
+}
+
+// ---- radiance queries.  The arguments are checked first (abi.cpp: check_trace_rays), before any device call.
+rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
+                                       void* hip_stream, RtxRenderStats* stats) {
+  const rtx_status st = check_trace_rays("rtx_scene_trace_rays_device", s, rays, d_sum_rgb);
+  if (st != RTX_OK) return st;
+  const struct { const void* p; const char* name; } cols[] = {{rays->origin, "rays->origin"}, {rays->direction, "rays->direction"},
+                                                              {rays->time, "rays->time"}, {d_sum_rgb, "sum_rgb"}, {d_sumsq_rgb, "sumsq_rgb"}};
+  for (const auto& c : cols)
+    if ((uintptr_t)c.p & 7) {
+      set_error(std::string("rtx_scene_trace_rays_device: ") + c.name + " is not 8-byte aligned");
+      return RTX_EINVAL;
+    }
+  if (rays->n == 0) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    return RTX_OK;
+  }
+  if (rays->light_sampling && s->f32) {
+    set_error("rtx_scene_trace_rays_device: light sampling needs an f64 scene (rtx_scene_upload)");
+    return RTX_EUNSUPPORTED;
+  }
+  return s->ops->trace_rays(s->device_scene, rays, d_sum_rgb, d_sumsq_rgb, (hipStream_t)hip_stream, stats);
+}
+
+// Host pointers: slices of RTX_TRACE_HOST_SLICE rays staged through device buffers (in: 56 B a ray, sums: 48 B), one after the
+// other on the null stream; slice k's first_ray is advanced by its offset, as the launcher advances a launch's.
+rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays, double* sum_rgb, double* sumsq_rgb,
+                                RtxRenderStats* stats) {
+  rtx_status st = check_trace_rays("rtx_scene_trace_rays", s, rays, sum_rgb);
+  if (st != RTX_OK) return st;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (rays->n == 0) return RTX_OK;
+  if (rays->light_sampling && s->f32) {
+    set_error("rtx_scene_trace_rays: light sampling needs an f64 scene (rtx_scene_upload)");
+    return RTX_EUNSUPPORTED;
+  }
+  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_TRACE_HOST_SLICE);
+  DeviceBuffer<double> d_o, d_d, d_time, d_sum, d_sumsq;
+  HIP_TRY(d_o.alloc(cap * 24));
+  HIP_TRY(d_d.alloc(cap * 24));
+  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
+  HIP_TRY(d_sum.alloc(cap * 24));
+  if (sumsq_rgb) HIP_TRY(d_sumsq.alloc(cap * 24));
+  for (int64_t first = 0; first < rays->n; first += RTX_TRACE_HOST_SLICE) {
+    const size_t n = (size_t)std::min<int64_t>(RTX_TRACE_HOST_SLICE, rays->n - first);
+    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
+    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
+    if (rays->accumulate) {
+      HIP_TRY(hipMemcpy(d_sum, sum_rgb + 3 * first, n * 24, hipMemcpyHostToDevice));
+      if (sumsq_rgb) HIP_TRY(hipMemcpy(d_sumsq, sumsq_rgb + 3 * first, n * 24, hipMemcpyHostToDevice));
+    }
+    RtxRadianceRays b = *rays;
+    b.n = (int64_t)n;
+    b.origin = d_o; b.direction = d_d; b.time = d_time;
+    b.first_ray = rays->first_ray + (uint64_t)first;
+    RtxRenderStats one;
+    if ((st = s->ops->trace_rays(s->device_scene, &b, d_sum, d_sumsq, (hipStream_t) nullptr, stats ? &one : nullptr)) != RTX_OK) return st;
+    // (a blocking copy on the null stream waits for the launches; the odd passes were joined to it)
+    HIP_TRY(hipMemcpy(sum_rgb + 3 * first, d_sum, n * 24, hipMemcpyDeviceToHost));
+    if (sumsq_rgb) HIP_TRY(hipMemcpy(sumsq_rgb + 3 * first, d_sumsq, n * 24, hipMemcpyDeviceToHost));
+    if (stats) {
+      stats->samples += one.samples; stats->trace_ms += one.trace_ms; stats->trace_launches += one.trace_launches;
+      stats->passes += one.passes; stats->trace_kernel = one.trace_kernel;
+      stats->sample_buffer_bytes = std::max(stats->sample_buffer_bytes, one.sample_buffer_bytes);
+    }
+  }
   return RTX_OK;
 }
 
