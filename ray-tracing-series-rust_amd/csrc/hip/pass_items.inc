@@ -74,8 +74,4 @@ __device__ __forceinline__ uint32_t queue_claim(unsigned int* work_counter, uint
   return __builtin_amdgcn_readfirstlane(base);
 }
 
-// A wave's ring of ready primary rays in LDS (k_trace_vote, k_trace_lds; RTX_RING): f64 [RING_F64][cap], then u32 [cap] (the
-// item).  trace_ring.inc -- the top-up and the take, included by both kernels -- is the only text that knows the rows.  Bytes
-// per wave:
-#define RING_F64 9u
-__host__ __device__ constexpr uint32_t ring_bytes(uint32_t cap) { return cap * (RING_F64 * 8u + 4u); }
+// (A wave's ring of ready primary rays in LDS -- RING_F64, ring_bytes -- is laid out in lds_layout.inc.)

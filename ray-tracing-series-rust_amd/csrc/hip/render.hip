@@ -40,18 +40,13 @@ namespace rtx { void set_error(const std::string& msg); }
 
 namespace rtx {
 
-#include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, lane_rank, queue_claim, ring_bytes
+#include "lds_layout.inc"    // ring_bytes, LdsSceneDims, ldsk_layout: k_trace_lds's LDS layout (host-compilable: tests/lds_layout_host_check.cpp)
+#include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, lane_rank, queue_claim
 
 // ------------------------------------------------------------------ device scene
 struct FlatNode4;
 typedef const FlatNode4 FlatNode4Dev;
 struct WorldDesc;
-
-struct LdsSceneDims {  // what k_trace_lds (trace_lds.inc) copies into LDS
-  uint32_t n_nodes, n_refs, n_spheres, n_moving;  // n_refs = leaf slots; one record per slot, in slot order: n_spheres or n_moving = n_refs
-  uint32_t node_dwords;  // LDSK_NODE_DWORDS, or LDSK_MOTION_NODE_DWORDS for the time-aware instantiation
-  uint32_t n_uni;        // scenes with moving spheres: how many of the n_moving records are the scene's STATIC spheres, kept as moving spheres that stand still (n_spheres = 0 then; informational: the kernel decides per slot)
-};
 
 // The plain primitive entries beside the BVH in the world list (the dragon room's seven rectangles), as a kernel argument:
 // list position, primitive reference and -- when all of them are rectangles -- the records themselves, for up to 8 entries.
@@ -702,7 +697,7 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   const uint32_t max_end = leaves.max_end, levels = (uint32_t)fs.max_stack + 1u;
   int lds_max = 0;
   (void)hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ds->device);
-  if (lds_max > 160 * 1024) lds_max = 160 * 1024;
+  if (lds_max > (int)LDSK_LDS_MAX) lds_max = (int)LDSK_LDS_MAX;
   // primitive records in LDS: one per leaf slot, in slot order (trace_lds.inc) -- spheres, or moving spheres when the scene has any
   p.plain.levels = levels;
   p.plain.dims = {(uint32_t)fs.nodes32.size(), max_end, max_end, 0u, LDSK_NODE_DWORDS, 0u};
@@ -744,14 +739,26 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   if (p.plain.ok) {
     // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
     // scenes uploaded earlier (with other LDS sizes) keep launching
+    // ... and the kernel addresses its node array absolutely, from LDSK_OFF_NODES = 0: that is where its dynamic LDS block starts as
+    // long as it has no static LDS in front of it.  Asked of the code object here, once; an instantiation that ever grows a static
+    // __shared__ takes k_trace_lds out of the plan (the other kernels render the scene) instead of reading nodes at the wrong place.
     hipError_t ae = hipSuccess;
-#define LDS_ATTR1(K) if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max)
+    bool static_lds = false;
+    hipFuncAttributes fa;
+#define LDS_ATTR1(K)                                                                                                   \
+  if (ae == hipSuccess) ae = hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max); \
+  if (ae == hipSuccess) ae = hipFuncGetAttributes(&fa, (const void*)K);                                                \
+  if (ae == hipSuccess && fa.sharedSizeBytes != 0) static_lds = true
 #define LDS_ATTR(FEAT, RINGF, MOTIONF) LDS_ATTR1((k_trace_lds<FEAT, RINGF, MOTIONF>)); LDS_ATTR1((k_trace_lds<FEAT, RINGF, MOTIONF, ActiveMap>))
     LDS_ATTR(P_SPHERES, true, 0u); LDS_ATTR(P_SPHERES, false, 0u); LDS_ATTR(P_STATIC_SPHERES, true, 0u); LDS_ATTR(P_STATIC_SPHERES, false, 0u);
     LDS_ATTR(P_SPHERES, true, 1u); LDS_ATTR(P_SPHERES, false, 1u); LDS_ATTR(P_SPHERES, true, 3u); LDS_ATTR(P_SPHERES, false, 3u);
 #undef LDS_ATTR
 #undef LDS_ATTR1
-    if (ae != hipSuccess) { (void)hipGetLastError(); p.plain.ok = false; }
+    if (ae != hipSuccess) { (void)hipGetLastError(); p.plain.ok = false; p.motion.ok = false; }
+    if (static_lds) {
+      fprintf(stderr, "[rtx] k_trace_lds has static LDS in front of its node array: not used\n");
+      p.plain.ok = false; p.motion.ok = false;
+    }
   }
   if (sw.scene_lds >= 0) {
     auto bytes = [](const LdsFit& f) { return f.ok ? ldsk_layout(f.levels, f.ring_cap, f.dims).total : 0u; };

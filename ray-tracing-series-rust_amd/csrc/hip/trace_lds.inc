@@ -7,8 +7,9 @@
 // occupancy as 4 x 256) copies that geometry into LDS once and walks it there (~64-cycle ds_read instead of
 // an L1/L2 round trip); the space comes from sharing one copy among 16 waves and from 16-bit stack entries:
 //
-//     [ walk stacks: levels x 1024 x u16 ][ primary-ray rings: 16 waves x ring_cap (64, or 48 / 32 when LDS is tight, else none) x 76 B ]
-//     [ nodes: n x 84 B (156 B with time-aware boxes) ][ refs: n x 4 B ][ spheres: n x 40 B ][ moving spheres: n x 80 B ]   <= 160 KB
+//     [ nodes: n x 84 B (108 / 156 B with time-aware boxes) ][ spheres: n x 40 B ][ moving spheres: n x 80 B ]
+//     [ walk stacks: levels x 1024 x u16 ][ primary-ray rings: 16 waves x ring_cap (64, or 48 when LDS is tight, else none) x 76 B ]   <= 160 KB
+//     (lds_layout.inc: ldsk_layout, the record sizes and the limits)
 //
 // Work items are 16 bits (axis << 13 | node index, index < 0x2000; or 0x8000 | first_slot << 2 | count - 1); the
 // child fields of the LDS copy of the tree are rewritten to that encoding while copying.  A node item carries its
@@ -18,46 +19,46 @@
 // field at a compile-time offset from one per-lane base address).  Everything else -- regeneration through the per-wave ring, cost-weighted node/leaf voting, f32 culling, carry-over of straggler walks,
 // shading -- is k_trace_vote's logic; results are bit-identical (tests/test_gpu_parity.py).
 
-#define LDSK_BLOCK 1024
 #define LDSK_DONE (-1)
 #define LDSK_NO_REF 0xFFFFFFFFu  // "nothing hit yet" in Closest::ref (primitive type 7 does not exist): k_trace_lds keeps no separate flag
-#define LDSK_MAX_SLOTS 8190u    // leaf item: first < 2^13, count <= 4
-#define LDSK_MAX_NODES 8191u     // node item = split axis << 13 | index: the axis travels with the item
-#define LDSK_NODE_DWORDS 21u     // per child and axis [lo, hi, lo] (18) + the two child items + 1 of padding (odd stride: no LDS bank pile-up)
 #ifndef LDSK_NODE_BURST
 #define LDSK_NODE_BURST 1  // node steps per vote (2 measured: see DESIGN.md 4)
 #endif
-#define LDSK_MOTION_NODE_DWORDS 39u  // time-aware boxes: per child 9 planes + 9 slopes + the item (19), twice, + 1 of padding
-#define LDSK_MOTION1_NODE_DWORDS 27u  // ... when everything moves along ONE axis: per child 9 planes + that axis's 3 slopes + the item (13)
-
-struct LdsKernelLayout {
-  uint32_t off_ring, off_nodes, off_refs, off_spheres, off_moving, total;
-};
-// ring_cap: entries of a wave's primary-ray ring (0 = no ring; at most 64 = one per lane)
-__host__ __device__ inline LdsKernelLayout ldsk_layout(uint32_t levels, uint32_t ring_cap, const LdsSceneDims& d) {
-  LdsKernelLayout L;
-  uint32_t o = levels * LDSK_BLOCK * 2u;
-  o = (o + 15u) & ~15u;
-  L.off_ring = o; o += (LDSK_BLOCK / 64u) * ring_bytes(ring_cap);
-  L.off_nodes = o; o += (d.n_nodes * d.node_dwords * 4u + 15u) & ~15u;
-  L.off_refs = o;  // (no reference array since the records are kept in slot order)
-  L.off_spheres = o; o += (d.n_spheres * (uint32_t)sizeof(rt::FlatSphere) + 15u) & ~15u;
-  L.off_moving = o; o += (d.n_moving * (uint32_t)sizeof(rt::FlatMovingSphere) + 15u) & ~15u;
-  L.total = o;
-  return L;
-}
 
 // Slot 0 of every thread holds LDSK_DONE for the whole kernel (init()), and a walk's own entries start at slot 1: popping an
 // "empty" stack returns "done" like any other item -- no emptiness test, no branch (the levels the launcher sizes the stack with
 // are the tree's height + 1: the height is what a walk can hold, the spare one is this slot).
-struct LdsStack16 {  // slot (level, thread) at base[level * LDSK_BLOCK]
-  unsigned short* base;
-  int n;
-  __device__ __forceinline__ void init() { base[0] = 0xFFFFu; n = 1; }  // 0xFFFF sign-extends to LDSK_DONE
-  __device__ __forceinline__ void reset() { n = 1; }
-  __device__ __forceinline__ void push(int32_t v) { base[n * LDSK_BLOCK] = (unsigned short)v; ++n; }
-  __device__ __forceinline__ int32_t pop() { --n; return (int32_t)(short)base[n * LDSK_BLOCK]; }  // ds_read_i16: sign-extending
-  __device__ __forceinline__ int32_t top() const { return (int32_t)(short)base[(n - 1) * LDSK_BLOCK]; }
+//
+// LDS by absolute address.  The kernel has no static LDS, so its dynamic block starts at address 0 (the launcher asks the code
+// object: plan_lds in render.hip): an address built from integers lets the compiler fold the node array's fixed offset into the index multiply and
+// every field into the DS instruction's immediate offset -- through `ldsk + ...` the base is a symbol that is resolved (to 0)
+// only after instruction selection, and stays behind as an add of its own.
+typedef __attribute__((address_space(3))) unsigned char LdsByte;
+typedef __attribute__((address_space(3))) float LdsF32;
+typedef __attribute__((address_space(3))) int32_t LdsI32;
+typedef __attribute__((address_space(3))) short LdsI16;
+typedef __attribute__((address_space(3))) unsigned short LdsU16;
+__device__ __forceinline__ const LdsByte* lds_at(uint32_t addr) { return (const LdsByte*)(uintptr_t)addr; }
+// What a walk carries is the BYTE ADDRESS of its top entry (`sp`), not a depth: the top is read at that address, a pop reads it
+// and steps down by the constant LDSK_LEVEL_BYTES, a push steps up and stores -- no address is rebuilt from a depth in any
+// step.  The thread's slot 0 (`bottom`) has the stacks' runtime base folded in once.
+struct LdsStack16 {  // slot (level, thread) at bottom + level * LDSK_LEVEL_BYTES
+  uint32_t bottom, sp;
+  __device__ __forceinline__ void init() { *(LdsU16*)lds_at(bottom) = 0xFFFFu; sp = bottom; }  // 0xFFFF sign-extends to LDSK_DONE
+  __device__ __forceinline__ void reset() { sp = bottom; }
+  __device__ __forceinline__ void set_top(int32_t v) { *(LdsU16*)lds_at(sp) = (unsigned short)v; }
+  __device__ __forceinline__ void push(int32_t v) { sp += LDSK_LEVEL_BYTES; set_top(v); }
+  __device__ __forceinline__ int32_t top() const { return (int32_t)*(const LdsI16*)lds_at(sp); }  // ds_read_i16: sign-extending
+  __device__ __forceinline__ int32_t pop() { const int32_t v = top(); sp -= LDSK_LEVEL_BYTES; return v; }
+  // a node step's net effect: one level up when both children may be hit (the caller then stores the far one with set_top), one
+  // down when neither: hf + hs - 1 levels.  Written as two adds of a bool so that a compare's lane mask goes in as the carry of
+  // an add / subtract (v_addc_co / v_subbrev_co) instead of through a 0 / 1 select of its own.
+  __device__ __forceinline__ void move(bool hf, bool hs) {
+    int32_t d = -1;
+    d += (int32_t)hf;
+    d += (int32_t)hs;
+    sp += (uint32_t)d * LDSK_LEVEL_BYTES;
+  }
 };
 // A work item is a 16-bit value kept sign-extended in a register: node >= 0 (split axis << 13 | index), leaf < -1
 // (0x8000 | first_slot << 2 | count - 1: at most 0xFFF7 = -9), done = -1 -- so "is a node" and "is a leaf" are one signed compare each.
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   const uint32_t first_ref = (uint32_t)bvh.b;
 
   // ---- geometry -> LDS
-  uint32_t* const lds_nodes = (uint32_t*)(ldsk + L.off_nodes);  // [n_nodes][21], see the copy loop below
+  uint32_t* const lds_nodes = (uint32_t*)(ldsk + LDSK_OFF_NODES);  // [n_nodes][21], see the copy loop below (L.off_nodes is this constant)
   rt::FlatSphere* const lds_spheres = (rt::FlatSphere*)(ldsk + L.off_spheres);
   rt::FlatMovingSphere* const lds_moving = (rt::FlatMovingSphere*)(ldsk + L.off_moving);
   {
@@ -170,7 +171,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   lsv.moving_spheres = lds_moving;
 
   LdsStack16 stack;
-  stack.base = (unsigned short*)ldsk + threadIdx.x;
+  stack.bottom = (uint32_t)(uintptr_t)(LdsByte*)ldsk + L.off_stacks + threadIdx.x * 2u;
   stack.init();
   double* const ring_f = (double*)(ldsk + L.off_ring + (threadIdx.x >> 6) * ring_bytes(ring_cap));
   uint32_t* const ring_g = (uint32_t*)(ring_f + RING_F64 * ring_cap);
@@ -252,18 +253,18 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
     auto node_step = [&]() {
       // the child that is near along the node's split axis is tested and queued first; which block that is is decided in
       // the ADDRESS (block 1 starts 40 bytes after block 0), not by selecting results afterwards
-      const unsigned char* nd = (const unsigned char*)(lds_nodes + ((uint32_t)cur & 0x1FFFu) * ND);
+      const LdsByte* nd = lds_at(LDSK_OFF_NODES + ((uint32_t)cur & 0x1FFFu) * (ND * 4u));
       const uint32_t first_b = __builtin_amdgcn_ubfe(flip_b, ((uint32_t)cur >> 10) & 0x18u, 8u);  // byte `axis` of flip_b: 0 or CB
-      const unsigned char* bf = nd + first_b;         // near child's block
-      const unsigned char* bs = nd + (CB - first_b);  // far child's block
-      const float *fx = (const float*)(bf + off_x), *fy = (const float*)(bf + off_y), *fz = (const float*)(bf + off_z);
-      const float *sx = (const float*)(bs + off_x), *sy = (const float*)(bs + off_y), *sz = (const float*)(bs + off_z);
-      const int32_t top = stack.top();
+      const LdsByte* bf = nd + first_b;         // near child's block
+      const LdsByte* bs = nd + (CB - first_b);  // far child's block
+      const LdsF32 *fx = (const LdsF32*)(bf + off_x), *fy = (const LdsF32*)(bf + off_y), *fz = (const LdsF32*)(bf + off_z);
+      const LdsF32 *sx = (const LdsF32*)(bs + off_x), *sy = (const LdsF32*)(bs + off_y), *sz = (const LdsF32*)(bs + off_z);
+      int32_t top = stack.top();
       bool hf, hs;
       if (MOTION >= 2u) {  // one moving axis: its slope pair sits at dword 9 of the block, i.e. 9 - 3 MA dwords after its plane pair
         constexpr uint32_t SO = 9u - 3u * MA;
-        const float* fm = MA == 0u ? fx : (MA == 1u ? fy : fz);
-        const float* sm = MA == 0u ? sx : (MA == 1u ? sy : sz);
+        const auto* fm = MA == 0u ? fx : (MA == 1u ? fy : fz);
+        const auto* sm = MA == 0u ? sx : (MA == 1u ? sy : sz);
         const float fn = __builtin_fmaf(s32, fm[SO], fm[0]), ff = __builtin_fmaf(s32, fm[SO + 1u], fm[1]);
         const float sn = __builtin_fmaf(s32, sm[SO], sm[0]), sf = __builtin_fmaf(s32, sm[SO + 1u], sm[1]);
         hf = rt::cull32_may_hit_nf_pos(MA == 0u ? fn : fx[0], MA == 0u ? ff : fx[1], MA == 1u ? fn : fy[0], MA == 1u ? ff : fy[1],
@@ -279,13 +280,18 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
         hf = rt::cull32_may_hit_nf_pos(fx[0], fx[1], fy[0], fy[1], fz[0], fz[1], q, t_max32);
         hs = rt::cull32_may_hit_nf_pos(sx[0], sx[1], sy[0], sy[1], sz[0], sz[1], q, t_max32);
       }
-      const int32_t cf = *(const int32_t*)(bf + ITEM_OFF), cs = *(const int32_t*)(bs + ITEM_OFF);
+      int32_t cf = *(const LdsI32*)(bf + ITEM_OFF), cs = *(const LdsI32*)(bs + ITEM_OFF);
+      // the three candidates for the next item are READ AHEAD, beside the planes: an empty statement that "uses" them keeps the
+      // compiler from sinking each read behind the compare that selects it (a dependent LDS round trip at the end of every step)
+      asm volatile("" : "+v"(top), "+v"(cf), "+v"(cs));
       // next item without a branch: the near child if it may be hit (the far one is stacked if it may be too), else the
       // far child, else the top of the stack -- read ahead of the tests, and LDSK_DONE when the walk's own entries are used up
       const bool both = hf && hs;
-      if (both) stack.base[stack.n * LDSK_BLOCK] = (unsigned short)cs;
+      // (selects and pointer update in the block of the compares, the one predicated store behind them: the sign extension of
+      // `top` folds into its read and the two masks into the pointer arithmetic only where the compiler sees them side by side)
       cur = hf ? cf : (hs ? cs : top);
-      stack.n += (int)both - (int)!(hf || hs);
+      stack.move(hf, hs);
+      if (both) stack.set_top(cs);
     };
     auto leaf_test = [&](uint32_t slot) {
       const rt::PrimRef ref = rt::make_primref(UNI ? rt::PRIM_MOVING_SPHERE : rt::PRIM_SPHERE, slot);  // record k = slot k (see the copy)
@@ -305,29 +311,39 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
       // hit, and no slot is below 0 -- one loop-carried lane mask less for every step of the walk
       if (ok && !(t == best.t && slot < best.order)) { best.t = t; best.ref = ref; best.order = slot; }
     };
-    for (;;) {
+    // The vote closes the loop instead of opening it: the ballots are convergent operations, which the compiler will not duplicate
+    // to rotate the loop itself, and an exit test at the head of a loop with divergent regions inside becomes a "stop" lane mask
+    // carried to the latch.  At the latch the wave-uniform compare is the back edge's own condition (s_cmp + s_cbranch_scc).
+    {
       // cur == LDSK_DONE whenever a lane is not in a walk, so the item alone tells the lane's state
-      const bool is_node = cur >= 0;
-      const bool is_leaf = cur < -1;
-      const uint32_t n_node = (uint32_t)__popcll(wave_ballot(is_node)), n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
-      if (n_node + n_leaf < threshold) break;
-      if (n_node * leaf_weight >= n_leaf) {
-        if (is_node) node_step();
+      bool is_node = cur >= 0;
+      bool is_leaf = cur < -1;
+      uint32_t n_node = (uint32_t)__popcll(wave_ballot(is_node)), n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
+      if (n_node + n_leaf >= threshold) {
+        do {
+          if (n_node * leaf_weight >= n_leaf) {
+            if (is_node) node_step();
 #if LDSK_NODE_BURST >= 2
-        if (cur >= 0) node_step();  // a second node step without a vote in between (the lanes that left for a leaf sit it out)
+            if (cur >= 0) node_step();  // a second node step without a vote in between (the lanes that left for a leaf sit it out)
 #endif
-      } else {
-        if (is_leaf) {
-          const uint32_t f = ((uint32_t)cur & 0x7FFFu) >> 2;
-          if (single_leaf) {  // wave-uniform: every leaf of this tree holds one primitive -- no loop
-            leaf_test(f);
           } else {
-            const uint32_t k = ((uint32_t)cur & 3u) + 1u;
-            for (uint32_t i = 0; i < k; ++i) leaf_test(f + i);
+            if (is_leaf) {
+              const uint32_t f = ((uint32_t)cur & 0x7FFFu) >> 2;
+              if (single_leaf) {  // wave-uniform: every leaf of this tree holds one primitive -- no loop
+                leaf_test(f);
+              } else {
+                const uint32_t k = ((uint32_t)cur & 3u) + 1u;
+                for (uint32_t i = 0; i < k; ++i) leaf_test(f + i);
+              }
+              t_max32 = rt::cull_round_up(best.t);
+              cur = stack.pop();
+            }
           }
-          t_max32 = rt::cull_round_up(best.t);
-          cur = stack.pop();
-        }
+          is_node = cur >= 0;
+          is_leaf = cur < -1;
+          n_node = (uint32_t)__popcll(wave_ballot(is_node));
+          n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
+        } while (n_node + n_leaf >= threshold);
       }
     }
     // ---- shade the lanes whose walk is complete
