@@ -165,10 +165,40 @@ int oracle_core_world_hit(const void* flat, const double o[3], const double d[3]
   out[7] = rec.u; out[8] = rec.v; out[9] = rec.front_face ? 1.0 : 0.0;
   return 1;
 }
-// Structural audit of a flattened scene (used by tests/test_host_logic.py): checks that every BVH
-// node box encloses its subtree's primitive boxes and every primitive sits in exactly one leaf.
-// Returns 0 when consistent, else a positive error code.
-static int audit_node(const rtx::FlatScene& fs, const rt::FlatEntry& e, int32_t child, const double* mn, const double* mx,
+// oracle_core_world_hit plus the material index of the hit (-1 on a miss): which of several primitives tied at one t was taken
+int oracle_core_world_hit_mat(const void* flat, const double o[3], const double d[3], double time, double t_min,
+                              double t_max, uint64_t rng_seed, double out[10], int32_t* mat) {
+  if (!flat || !mat) return -1;
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+  const rt::SceneView sv = fs.view();
+  rt::LocalStack<128> stack;
+  stack.n = 0;
+  rt::Rng rng = rt::rng_for_sample(rng_seed, 0, 0);
+  rt::HitRecord rec;
+  rt::Ray r = rt::make_ray(rt::v3(o[0], o[1], o[2]), rt::v3(d[0], d[1], d[2]), time);
+  *mat = -1;
+  if (!rt::world_hit<rt::F_ALL, false>(sv, r, t_min, t_max, &rec, rng, stack, nullptr)) return 0;
+  out[0] = rec.t; out[1] = rec.p.x; out[2] = rec.p.y; out[3] = rec.p.z;
+  out[4] = rec.normal.x; out[5] = rec.normal.y; out[6] = rec.normal.z;
+  out[7] = rec.u; out[8] = rec.v; out[9] = rec.front_face ? 1.0 : 0.0;
+  *mat = (int32_t)rec.mat;
+  return 1;
+}
+// Structural audits of a flattened scene (tests/test_host_logic.py, tests/test_gpu_lbvh_edges.py); 0 when consistent, else the
+// code of the first property that fails.
+//   oracle_audit_flat: 2 a leaf's range leaves the BVH's references; 3 a child index leaves the node array (or the tree is
+//     deeper than 4096: a cycle); 4 a child box of a node leaves the box its parent stores for that node; 5 a primitive sits in
+//     no leaf or in several; 6 the tree is deeper than max_stack + 1.  It compares stored boxes with stored boxes only: a tree
+//     whose boxes all miss their primitives passes.
+//   oracle_audit_flat_exact: all of the above, then 7 a leaf count outside 1..8; 8 a split axis (pad[0]) outside 0..2 -- or, with flag
+//     ORACLE_AUDIT_ASK_FIRST, neither that nor the host SAH builder's 3 ("ask child 0 first", bvh_build.cpp) on a node whose child 0 is
+//     a leaf of one primitive; 9 a
+//     child box that is not BIT-equal to the fmin / fmax union of the reference boxes (hit.rs bounding_box, restated in
+//     exact_prim_box below from the flat primitive arrays) of the primitives under it; 10 (flag ORACLE_AUDIT_LEAF_ORDER) a left-to-right
+//     depth-first walk does not meet the leaves with leaf_first ascending and contiguous from 0; 11 (cluster > 0) a leaf other
+//     than the last in leaf order that does not hold exactly `cluster` primitives; 12 a primitive type without a box rule.
+//     `nodes` (may be NULL: the scene's own) lets a test audit an edited copy of the node array.
+static int audit_node(const rt::FlatNode* nodes, size_t n_nodes, const rt::FlatEntry& e, int32_t child, const double* mn, const double* mx,
                       std::vector<int>& seen, int depth, int* max_depth) {
   if (depth > *max_depth) *max_depth = depth;
   if (rt::node_child_is_leaf(child)) {
@@ -177,25 +207,23 @@ static int audit_node(const rtx::FlatScene& fs, const rt::FlatEntry& e, int32_t 
     for (uint32_t i = 0; i < k; ++i) seen[f + i]++;
     return 0;
   }
-  if (child < 0 || (size_t)child >= fs.nodes.size()) return 3;
-  const rt::FlatNode& n = fs.nodes[child];
+  if (child < 0 || (size_t)child >= n_nodes || depth > 4096) return 3;
+  const rt::FlatNode& n = nodes[child];
   for (int c = 0; c < 2; ++c) {
     for (int a = 0; a < 3; ++a)
       if (mn && (n.bmin[c][a] < mn[a] || n.bmax[c][a] > mx[a])) return 4;
-    int rc = audit_node(fs, e, n.child[c], n.bmin[c], n.bmax[c], seen, depth + 1, max_depth);
+    int rc = audit_node(nodes, n_nodes, e, n.child[c], n.bmin[c], n.bmax[c], seen, depth + 1, max_depth);
     if (rc) return rc;
   }
   return 0;
 }
-int oracle_audit_flat(const void* flat, int32_t* max_depth_out) {
-  if (!flat) return -1;
-  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+static int audit_flat_nodes(const rtx::FlatScene& fs, const rt::FlatNode* nodes, size_t n_nodes, int32_t* max_depth_out) {
   int max_depth = 0;
   for (const rt::FlatEntry& e : fs.entries) {
     if (e.kind != rt::ENTRY_BVH) continue;
     std::vector<int> seen((size_t)e.c, 0);
     int d = 0;
-    int rc = audit_node(fs, e, e.a, nullptr, nullptr, seen, 1, &d);
+    int rc = audit_node(nodes, n_nodes, e, e.a, nullptr, nullptr, seen, 1, &d);
     if (rc) return rc;
     for (int v : seen)
       if (v != 1) return 5;
@@ -203,6 +231,120 @@ int oracle_audit_flat(const void* flat, int32_t* max_depth_out) {
   }
   if (max_depth_out) *max_depth_out = max_depth;
   return max_depth <= fs.max_stack + 1 ? 0 : 6;
+}
+int oracle_audit_flat(const void* flat, int32_t* max_depth_out) {
+  if (!flat) return -1;
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+  return audit_flat_nodes(fs, fs.nodes.data(), fs.nodes.size(), max_depth_out);
+}
+
+// The reference's bounding_box of one flat primitive over [t0, t1] (hit.rs:239-244, 317-327, 430-443, 503-508 / 568-573 /
+// 633-638, 164-177), restated here: the audit must not share code with the builders it judges.
+static bool exact_prim_box(const rtx::FlatScene& fs, rt::PrimRef ref, double t0, double t1, double* b) {
+  const uint32_t idx = rt::primref_index(ref);
+  auto two_instants = [&](const rt::Vec3& ca, const rt::Vec3& cb, double r) {
+    const double a3[3] = {ca.x, ca.y, ca.z}, b3[3] = {cb.x, cb.y, cb.z};
+    for (int a = 0; a < 3; ++a) {
+      b[a] = std::fmin(a3[a] - r, b3[a] - r);
+      b[3 + a] = std::fmax(a3[a] + r, b3[a] + r);
+    }
+  };
+  switch (rt::primref_type(ref)) {
+    case rt::PRIM_SPHERE: {
+      if (idx >= fs.spheres.size()) return false;
+      const rt::FlatSphere& s = fs.spheres[idx];
+      const double c[3] = {s.cx, s.cy, s.cz};
+      const double r = std::fabs(s.radius);  // |r|: the reference's c - r .. c + r for r >= 0, ordered for the hollow-glass idiom (flatten.cpp: prim_box)
+      for (int a = 0; a < 3; ++a) { b[a] = c[a] - r; b[3 + a] = c[a] + r; }
+      return true;
+    }
+    case rt::PRIM_MOVING_SPHERE: {
+      if (idx >= fs.moving_spheres.size()) return false;
+      const rt::FlatMovingSphere& s = fs.moving_spheres[idx];
+      two_instants(rt::moving_sphere_center(s, t0), rt::moving_sphere_center(s, t1), std::fabs(s.radius));
+      return true;
+    }
+    case rt::PRIM_GRAVITY_SPHERE: {
+      if (idx >= fs.gravity_spheres.size()) return false;
+      const rt::FlatGravitySphere& s = fs.gravity_spheres[idx];
+      two_instants(rt::gravity_sphere_center(s, fs.gravity_y.data(), t0), rt::gravity_sphere_center(s, fs.gravity_y.data(), t1), std::fabs(s.radius));
+      return true;
+    }
+    case rt::PRIM_RECT: {
+      if (idx >= fs.rects.size()) return false;
+      const rt::FlatRect& q = fs.rects[idx];
+      // (a, b) are the rectangle's own two axes in the order of its constructor, k the thin one
+      const int thin = q.axis == rt::RECT_XY ? 2 : (q.axis == rt::RECT_XZ ? 1 : 0);
+      const int ua = q.axis == rt::RECT_YZ ? 1 : 0, ub = q.axis == rt::RECT_XY ? 1 : 2;
+      b[ua] = q.a0; b[3 + ua] = q.a1;
+      b[ub] = q.b0; b[3 + ub] = q.b1;
+      b[thin] = q.k - 0.0001; b[3 + thin] = q.k + 0.0001;
+      return true;
+    }
+    case rt::PRIM_TRIANGLE: {
+      if (idx >= fs.triangles.size()) return false;
+      const rt::FlatTriangle& t = fs.triangles[idx];
+      for (int a = 0; a < 3; ++a) {
+        b[a] = std::fmin(std::fmin(t.v0[a], t.v1[a]), t.v2[a]);
+        b[3 + a] = std::fmax(std::fmax(t.v0[a], t.v1[a]), t.v2[a]);
+      }
+      return true;
+    }
+    default: return false;
+  }
+}
+struct ExactWalk {
+  const rtx::FlatScene& fs;
+  const rt::FlatNode* nodes;
+  const rt::FlatEntry& e;
+  bool leaf_order, ask_first;
+  uint32_t cluster, next_first;
+};
+// the union of the reference boxes under `child` into u[6]; 0 or the code of the first failed property
+static int exact_node(ExactWalk& w, int32_t child, double* u) {
+  for (int a = 0; a < 3; ++a) { u[a] = INFINITY; u[3 + a] = -INFINITY; }
+  if (rt::node_child_is_leaf(child)) {
+    const uint32_t f = rt::leaf_first(child), k = rt::leaf_count(child);
+    if (k < 1u || k > 8u) return 7;
+    if (w.leaf_order && f != w.next_first) return 10;
+    w.next_first = f + k;
+    if (w.cluster && (f + k < (uint32_t)w.e.c ? k != w.cluster : k > w.cluster)) return 11;
+    for (uint32_t i = 0; i < k; ++i) {
+      double b[6];
+      if (!exact_prim_box(w.fs, w.fs.refs[(size_t)w.e.b + f + i], w.e.f[0], w.e.f[1], b)) return 12;
+      for (int a = 0; a < 3; ++a) { u[a] = std::fmin(u[a], b[a]); u[3 + a] = std::fmax(u[3 + a], b[3 + a]); }
+    }
+    return 0;
+  }
+  const rt::FlatNode& n = w.nodes[child];
+  const bool asks_first = w.ask_first && n.pad[0] == 3 && rt::node_child_is_leaf(n.child[0]) && rt::leaf_count(n.child[0]) == 1u;
+  if ((n.pad[0] < 0 || n.pad[0] > 2) && !asks_first) return 8;
+  for (int c = 0; c < 2; ++c) {
+    double cb[6];
+    const int rc = exact_node(w, n.child[c], cb);
+    if (rc) return rc;
+    if (memcmp(cb, n.bmin[c], 3 * sizeof(double)) != 0 || memcmp(cb + 3, n.bmax[c], 3 * sizeof(double)) != 0) return 9;
+    for (int a = 0; a < 3; ++a) { u[a] = std::fmin(u[a], cb[a]); u[3 + a] = std::fmax(u[3 + a], cb[3 + a]); }
+  }
+  return 0;
+}
+int oracle_audit_flat_exact(const void* flat, const void* nodes, int64_t n_nodes, int32_t flags, int32_t cluster, int32_t* max_depth_out) {
+  if (!flat || cluster < 0 || cluster > 8) return -1;
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+  const rt::FlatNode* nd = nodes ? (const rt::FlatNode*)nodes : fs.nodes.data();
+  const size_t nn = nodes ? (size_t)n_nodes : fs.nodes.size();
+  int rc = audit_flat_nodes(fs, nd, nn, max_depth_out);  // (every index and range is in bounds past this point)
+  if (rc) return rc;
+  for (const rt::FlatEntry& e : fs.entries) {
+    if (e.kind != rt::ENTRY_BVH) continue;
+    if (e.b < 0 || (size_t)e.b + (size_t)e.c > fs.refs.size()) return 2;
+    ExactWalk w{fs, nd, e, (flags & ORACLE_AUDIT_LEAF_ORDER) != 0, (flags & ORACLE_AUDIT_ASK_FIRST) != 0, (uint32_t)cluster, 0u};
+    double u[6];
+    rc = exact_node(w, e.a, u);
+    if (rc) return rc;
+    if (w.leaf_order && w.next_first != (uint32_t)e.c) return 10;
+  }
+  return 0;
 }
 
 // Audit of the time-aware culling boxes (FlatMotion32): for every BVH that carries them and `n_times` instants of its interval
@@ -317,7 +459,7 @@ const void* oracle_flat_array(const void* flat, const char* name, int64_t* n, in
   const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
 #define ARR(VEC) if (!strcmp(name, #VEC)) { *n = (int64_t)fs.VEC.size(); *elem_bytes = (int64_t)sizeof(fs.VEC[0]); return fs.VEC.data(); }
   ARR(spheres) ARR(moving_spheres) ARR(rects) ARR(triangles) ARR(nodes) ARR(entries) ARR(materials) ARR(textures)
-  ARR(perlins) ARR(gravity_spheres) ARR(texels) ARR(gravity_y)
+  ARR(perlins) ARR(gravity_spheres) ARR(texels) ARR(gravity_y) ARR(refs)
 #undef ARR
   *n = 0; *elem_bytes = 0;
   return nullptr;

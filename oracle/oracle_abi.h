@@ -92,7 +92,14 @@ int oracle_core_aabb_hit(const double mn[3], const double mx[3], const double o[
                          double t_min, double t_max);
 int oracle_core_world_hit(const void* flat, const double o[3], const double d[3], double time, double t_min,
                           double t_max, uint64_t rng_seed, double out[10]);
+int oracle_core_world_hit_mat(const void* flat, const double o[3], const double d[3], double time, double t_min,
+                              double t_max, uint64_t rng_seed, double out[10], int32_t* mat);
 int oracle_audit_flat(const void* flat, int32_t* max_depth_out);
+/* The exact audit (o2_flat.cpp): nodes == NULL audits the scene's own node array; cluster > 0 asks for full leaves. */
+#define ORACLE_AUDIT_LEAF_ORDER 1 /* leaves ascend contiguously in a depth-first walk (GPU-built trees) */
+#define ORACLE_AUDIT_ASK_FIRST 2  /* split "axis" 3 is legal on a node whose child 0 is a one-primitive leaf (host SAH trees) */
+int oracle_audit_flat_exact(const void* flat, const void* nodes, int64_t n_nodes, int32_t flags, int32_t cluster,
+                            int32_t* max_depth_out);
 int oracle_audit_motion(const void* flat, int32_t n_times, int64_t* checked);
 double oracle_motion_leaf_area_ratio(const void* flat);
 int oracle_lds_walk_render(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t use_motion,

@@ -79,8 +79,12 @@ def load():
         getattr(lib, "oracle_%s_aabb_hit" % side).argtypes = [_D, _D, _D, _D, C.c_double, C.c_double]
     lib.oracle_core_world_hit.restype = C.c_int
     lib.oracle_core_world_hit.argtypes = [C.c_void_p, _D, _D, C.c_double, C.c_double, C.c_double, C.c_uint64, _D]
+    lib.oracle_core_world_hit_mat.restype = C.c_int
+    lib.oracle_core_world_hit_mat.argtypes = [C.c_void_p, _D, _D, C.c_double, C.c_double, C.c_double, C.c_uint64, _D, C.POINTER(C.c_int32)]
     lib.oracle_audit_flat.restype = C.c_int
     lib.oracle_audit_flat.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    lib.oracle_audit_flat_exact.restype = C.c_int
+    lib.oracle_audit_flat_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
     lib.oracle_audit_motion.restype = C.c_int
     lib.oracle_audit_motion.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int64)]
     lib.oracle_motion_leaf_area_ratio.restype = C.c_double
@@ -371,6 +375,16 @@ def core_world_hit(flat_arrays_ptr, o, d, time=0.0, t_min=0.001, t_max=float("in
     return _rec(load().oracle_core_world_hit(flat_arrays_ptr, _d3(o), _d3(d), time, t_min, t_max, rng_seed, out), out)
 
 
+def core_world_hit_mat(flat_arrays_ptr, o, d, time=0.0, t_min=0.001, t_max=float("inf"), rng_seed=1):
+    """core_world_hit with the hit's material index under "mat": which of several primitives tied at one t was taken."""
+    out = (C.c_double * 10)()
+    mat = C.c_int32(-1)
+    rec = _rec(load().oracle_core_world_hit_mat(flat_arrays_ptr, _d3(o), _d3(d), time, t_min, t_max, rng_seed, out, C.byref(mat)), out)
+    if rec is not None:
+        rec["mat"] = mat.value
+    return rec
+
+
 def audit_motion(flat_arrays_ptr, n_times=16):
     """(code, triples checked): the time-aware boxes contain every sphere below them at n_times instants (0 = consistent)."""
     n = C.c_int64(0)
@@ -401,4 +415,30 @@ def motion_leaf_area_ratio(flat_arrays_ptr):
 def audit_flat(flat_arrays_ptr):
     depth = C.c_int32(0)
     rc = load().oracle_audit_flat(flat_arrays_ptr, C.byref(depth))
+    return rc, depth.value
+
+
+# rt::FlatNode (core/flat_types.hpp), for tests that look into or edit a copy of the node array
+FLAT_NODE = np.dtype([("bmin", np.float64, (2, 3)), ("bmax", np.float64, (2, 3)), ("child", np.int32, (2,)), ("pad", np.int32, (2,))])
+
+
+def flat_nodes(flat_arrays_ptr):
+    """A copy of the scene's node array as a structured array of FLAT_NODE."""
+    raw, e = flat_array(flat_arrays_ptr, "nodes")
+    assert e == FLAT_NODE.itemsize
+    return raw.view(FLAT_NODE)
+
+
+def audit_flat_exact(flat_arrays_ptr, leaf_order=False, full_leaves=0, ask_first=False, nodes=None):
+    """(code, depth) of oracle_audit_flat_exact: audit_flat's checks, then every child box bit-equal to the union of the
+    reference boxes below it, leaf counts and split axes in range.  leaf_order: leaves ascend contiguously in a depth-first
+    walk; full_leaves = the cluster size: every leaf but the last holds exactly that many (both hold for GPU-built trees).
+    ask_first: split "axis" 3, the host SAH builder's "ask child 0 first", is legal where child 0 is a one-primitive leaf.
+    nodes: a FLAT_NODE array audited in place of the scene's own."""
+    depth = C.c_int32(0)
+    p, n = None, 0
+    if nodes is not None:
+        nodes = np.ascontiguousarray(nodes, dtype=FLAT_NODE)
+        p, n = nodes.ctypes.data, nodes.size
+    rc = load().oracle_audit_flat_exact(flat_arrays_ptr, p, n, (1 if leaf_order else 0) | (2 if ask_first else 0), int(full_leaves), C.byref(depth))
     return rc, depth.value

@@ -13,6 +13,8 @@
 #include "oracle_abi.h"
 
 extern "C" int oracle_audit_flat(const void* flat, int32_t* max_depth_out);
+extern "C" int oracle_audit_flat_exact(const void* flat, const void* nodes, int64_t n_nodes, int32_t flags, int32_t cluster,
+                                       int32_t* max_depth_out);
 extern "C" int oracle_audit_motion(const void* flat, int32_t n_times, int64_t* checked);
 extern "C" int oracle_lds_walk_render(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t use_motion,
                                       int32_t row_stride, double* accum_rgb, uint64_t counts[3]);
@@ -42,6 +44,7 @@ static int check_scene(int32_t sid, int width, double aspect, int spp, bool refe
   int32_t depth = 0;
   // (the reference's build rule stores a span of one object twice, bvh.rs:53-55: "every primitive in exactly one leaf" does not hold there)
   if (!reference_bvh && oracle_audit_flat(&fs, &depth) != 0) { fprintf(stderr, "scene %d: audit_flat failed\n", sid); return 1; }
+  if (!reference_bvh && oracle_audit_flat_exact(&fs, nullptr, 0, ORACLE_AUDIT_ASK_FIRST, 0, &depth) != 0) { fprintf(stderr, "scene %d: audit_flat_exact failed\n", sid); return 1; }
   int64_t checked = 0;
   if (oracle_audit_motion(&fs, 8, &checked) != 0) { fprintf(stderr, "scene %d: audit_motion failed\n", sid); return 1; }
   OracleCamera cam;

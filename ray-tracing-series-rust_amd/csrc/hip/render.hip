@@ -473,7 +473,7 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
   const WidePlan& wt = ds->wide;
   uint32_t lds_tables = 0;
   size_t lds = stack_bytes((uint32_t)wt.levels);
-  if (p.tables_bytes > 0 && (lds + p.tables_bytes) * (size_t)wt.vote_blocks_per_cu <= 160 * 1024) {
+  if (p.tables_bytes > 0 && lds + p.tables_bytes <= 64 * 1024 && (lds + p.tables_bytes) * (size_t)wt.vote_blocks_per_cu <= 160 * 1024) {
     lds_tables = p.tables;
     lds += p.tables_bytes;
   }
@@ -643,7 +643,10 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   const size_t lds = stack_bytes(levels) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real) +
                      (size_t)p.perlin_lds * sizeof(rt::FlatPerlin) + (size_t)p.mat_lds * sizeof(rt::FlatMaterial) +
                      (size_t)p.tex_lds * sizeof(rt::FlatTexture);
-  const bool inst = (a.feat & rt::F_INSTANCE) != 0;  // (never wide: plan_wide)
+  // the footprint plan_world refused to fit (it skipped the tree: no tables, no occupancy) is not launched either: the per-lane
+  // slot behind the stacks leaves this kernel 50 levels where the others have 64
+  if (lds > 64 * 1024) { set_error("render: BVH too deep for the LDS traversal stack of k_trace_world (stacks and per-lane slots)"); return RTX_EUNSUPPORTED; }
+  const bool inst =(a.feat & rt::F_INSTANCE) != 0;  // (never wide: plan_wide)
   const int family = inst ? 4 : (has_gravity ? 2 : (book2 ? 0 : (no_sphere_media ? 3 : 1)));
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[family][wide ? 1 : 0]);
   const rt::SceneView& v = ds->view;

@@ -61,6 +61,11 @@ struct Builder {
     if ((int)n <= opt.max_leaf) {
       *depth = 0;
       sah += bb.half_area() * n;
+      // Slots of a leaf in list order: an exact tie inside one BVH goes to the higher slot (core/geometry.hpp: offer_prim), and
+      // primitives that COINCIDE (one centroid: no split below ever parts them except the median fallback, which parts them by
+      // index) must tie the same way whatever the leaf size -- the later one in the list wins, as in a HittableList and as in
+      // a tree from the GPU builder, whose stable sort keeps equal Morton codes in list order.
+      std::sort(order.begin() + begin, order.begin() + end);
       return rt::make_leaf(begin, n);
     }
     // ---- binned SAH over the three axes

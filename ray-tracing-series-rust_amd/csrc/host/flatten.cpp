@@ -158,20 +158,26 @@ struct Flattener {
                 "Wrap the BVH, not its members, or list every wrapped object in the world list");
   }
 
-  // Reference bounding boxes (hit.rs bounding_box impls) of one flattened primitive.
+  // Reference bounding boxes (hit.rs bounding_box impls) of one flattened primitive -- with one delta: a sphere's box is taken
+  // with |radius|.  The reference's centre - r .. centre + r is INVERTED for a negative radius (the hollow-glass idiom), unions
+  // keep it inverted, and a box that does not hold its primitive makes the closest hit depend on leaf size, topology and on how
+  // a walker reads such a box (min / max of the planes, or near / far by the ray's signs): DESIGN.md 2.  For r >= 0 the bits
+  // are the reference's.
   void prim_box(rt::PrimRef ref, double time0, double time1, double* b) const {
     uint32_t idx = rt::primref_index(ref);
     switch (rt::primref_type(ref)) {
       case rt::PRIM_SPHERE: {  // hit.rs:239-244
         const rt::FlatSphere& s = out.spheres[idx];
-        Vec3 c = rt::v3(s.cx, s.cy, s.cz), r = rt::v3(s.radius, s.radius, s.radius);
+        const double ar = std::fabs(s.radius);
+        Vec3 c = rt::v3(s.cx, s.cy, s.cz), r = rt::v3(ar, ar, ar);
         Vec3 lo = c - r, hi = c + r;
         b[0] = lo.x; b[1] = lo.y; b[2] = lo.z; b[3] = hi.x; b[4] = hi.y; b[5] = hi.z;
         break;
       }
       case rt::PRIM_MOVING_SPHERE: {  // hit.rs:317-327
         const rt::FlatMovingSphere& s = out.moving_spheres[idx];
-        Vec3 r = rt::v3(s.radius, s.radius, s.radius);
+        const double ar = std::fabs(s.radius);
+        Vec3 r = rt::v3(ar, ar, ar);
         Vec3 ca = rt::moving_sphere_center(s, time0), cb = rt::moving_sphere_center(s, time1);
         Vec3 lo0 = ca - r, hi0 = ca + r, lo1 = cb - r, hi1 = cb + r;
         b[0] = std::fmin(lo0.x, lo1.x); b[1] = std::fmin(lo0.y, lo1.y); b[2] = std::fmin(lo0.z, lo1.z);
@@ -180,7 +186,8 @@ struct Flattener {
       }
       case rt::PRIM_GRAVITY_SPHERE: {  // hit.rs:430-443: union of the boxes at time0 and time1 (NOT of the trajectory between)
         const rt::FlatGravitySphere& s = out.gravity_spheres[idx];
-        Vec3 r = rt::v3(s.radius, s.radius, s.radius);
+        const double ar = std::fabs(s.radius);
+        Vec3 r = rt::v3(ar, ar, ar);
         Vec3 ca = rt::gravity_sphere_center(s, out.gravity_y.data(), time0), cb = rt::gravity_sphere_center(s, out.gravity_y.data(), time1);
         Vec3 lo0 = ca - r, hi0 = ca + r, lo1 = cb - r, hi1 = cb + r;
         b[0] = std::fmin(lo0.x, lo1.x); b[1] = std::fmin(lo0.y, lo1.y); b[2] = std::fmin(lo0.z, lo1.z);

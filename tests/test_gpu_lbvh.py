@@ -94,16 +94,23 @@ def test_ply_mesh_through_the_gpu_builder(rtsr, orc, tmp_path):
 
 
 def test_full_size_mesh_build_time(rtsr, orc):
-    """871 200 triangles (BASELINE configs[3]): the device part of the build under 100 ms; spot rows of the 1920x1080 frame
-    traced through the GPU-built tree equal the oracle's."""
+    """871 200 triangles (BASELINE configs[3]): the device part of the build under 100 ms; the tree passes the exact audit and is the
+    same bytes in two builds; spot rows of the 1920x1080 frame traced through the GPU-built tree equal the oracle's."""
     b = rtsr.Builder(1)
     world, cam, bg = b.get_world_cam(rtsr.SCENE_STANFORD_DRAGON, mesh_triangles=871200)
-    b.flatten(world, gpu_builder=True)  # first call pays one-time costs (code object load, rocPRIM kernel selection)
+    first = b.flatten(world, gpu_builder=True)  # first call pays one-time costs (code object load, rocPRIM kernel selection)
     t0 = time.perf_counter()
     flat = b.flatten(world, gpu_builder=True)
     wall = time.perf_counter() - t0
     info = flat.info()
     assert info["n_triangles"] == 871200
+    # the one build that spreads k_refit over the whole device: every box bit-equal to the union of the triangles under it, leaves
+    # in order and full (two triangles each), the reported depth exact, and the two builds the same bytes
+    rc, depth = orc.audit_flat_exact(flat.arrays_ptr(), leaf_order=True, full_leaves=2)
+    assert rc == 0, "exact audit code %d" % rc
+    assert depth == info["max_stack"] + 1
+    assert np.array_equal(orc.flat_array(first.arrays_ptr(), "nodes")[0], orc.flat_array(flat.arrays_ptr(), "nodes")[0])
+    del first
     print("\n[lbvh] 871200 triangles: device %.1f ms, builder wall %.1f ms, whole flatten %.0f ms, depth %d" % (
         info["bvh_device_ms"], info["bvh_build_ms"], wall * 1e3, info["max_stack"]))
     assert info["bvh_device_ms"] < 100.0

@@ -43,6 +43,11 @@ def test_bvh_structure(rtsr, orc, sid, opts, leaf):
     rc, depth = orc.audit_flat(flat.arrays_ptr())
     assert rc == 0, "audit code %d" % rc
     assert depth <= flat.info()["max_stack"] + 1
+    # ... and every child box is bit for bit the union of the reference boxes under it (the host SAH builder's "axis" 3, ask
+    # child 0 first, is legal where child 0 is a one-primitive leaf: bvh_build.cpp)
+    rc, depth2 = orc.audit_flat_exact(flat.arrays_ptr(), ask_first=True)
+    assert rc == 0, "exact audit code %d" % rc
+    assert depth2 == depth
 
 
 def test_bvh_degenerate_inputs(rtsr, orc):
@@ -57,9 +62,58 @@ def test_bvh_degenerate_inputs(rtsr, orc):
     for world in (same, one, two):
         flat = b.flatten(world)
         assert orc.audit_flat(flat.arrays_ptr())[0] == 0
+        assert orc.audit_flat_exact(flat.arrays_ptr(), ask_first=True)[0] == 0
         a1, _ = orc.o1_render(b.graph_ptr(), world, cam, cfg, 12)
         a2, _ = orc.o2_render(flat.arrays_ptr(), cam, cfg, 12)
         assert np.array_equal(a1, a2)
+
+
+def test_exact_audit_can_fail(rtsr, orc):
+    """The exact audit on edited copies of a host-built node array: each corruption gives its own code."""
+    b = rtsr.Builder(3)
+    world, _, _ = b.get_world_cam(6)
+    flat = b.flatten(world, max_leaf=2)
+    ptr = flat.arrays_ptr()
+    nodes = orc.flat_nodes(ptr)
+    assert orc.audit_flat_exact(ptr, leaf_order=True, ask_first=True, nodes=nodes)[0] == 0  # the copy as it is: clean
+    leaves = [(i, c) for i in range(len(nodes)) for c in range(2) if nodes["child"][i][c] < 0]
+    inner = [i for i in range(len(nodes)) if nodes["child"][i][0] >= 0]
+    # 1. one plane of one child box moved INWARD by one ulp.  Over a leaf only the exact audit sees it (9; the nesting audit
+    # compares stored boxes with stored boxes); over a subtree the boxes stored below stick out of it, which is nesting's code 4
+    for (i, c), code in ((leaves[3], 9), ((inner[0], 0), 4)):
+        for plane, toward in (("bmin", np.inf), ("bmax", -np.inf)):
+            bad = nodes.copy()
+            bad[plane][i][c][1] = np.nextafter(bad[plane][i][c][1], toward)
+            assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == code
+    # ... and one ulp OUTWARD over a subtree still nests: only exactness objects
+    bad = nodes.copy()
+    bad["bmax"][inner[0]][0][1] = np.nextafter(bad["bmax"][inner[0]][0][1], np.inf)
+    assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == 9
+    # 2. two sibling leaves swapped, boxes and all: still a sound tree (exact boxes, every primitive in one leaf), out of leaf order
+    i = [i for i in range(len(nodes)) if nodes["child"][i][0] < 0 and nodes["child"][i][1] < 0][0]
+    bad = nodes.copy()
+    for f in ("bmin", "bmax", "child"):
+        bad[f][i][0], bad[f][i][1] = nodes[f][i][1], nodes[f][i][0]
+    assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == 0
+    assert orc.audit_flat_exact(ptr, leaf_order=True, ask_first=True, nodes=bad)[0] == 10
+    # ... and the codes alone of two leaves far apart swapped: each now sits under the other's box
+    (i, c), (j, d) = leaves[1], leaves[6]
+    bad = nodes.copy()
+    bad["child"][i][c], bad["child"][j][d] = nodes["child"][j][d], nodes["child"][i][c]
+    assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == 9
+    # 3. split axis 3 where child 0 is a subtree (nothing to ask first), and on any node for a builder that never writes 3
+    bad = nodes.copy()
+    bad["pad"][inner[0]][0] = 3
+    assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == 8
+    bad = nodes.copy()
+    bad["pad"][leaves[0][0]][0] = 3
+    assert orc.audit_flat_exact(ptr, nodes=bad)[0] == 8
+    # 4. a leaf one primitive short: that primitive is in no leaf (audit_flat's own code), and a cluster that is not full
+    bad = nodes.copy()
+    two = [(i, c) for (i, c) in leaves if (int(nodes["child"][i][c]) & 7) == 1][0]
+    bad["child"][two[0]][two[1]] -= 1
+    assert orc.audit_flat_exact(ptr, ask_first=True, nodes=bad)[0] == 5
+    assert orc.audit_flat_exact(ptr, ask_first=True, full_leaves=1, nodes=nodes)[0] == 11
 
 
 def test_ppm_writer_format(rtsr, tmp_path):  # screen.rs:40-48, vec3.rs:109-114
