@@ -554,6 +554,59 @@ rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays,
 rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
                                        void* hip_stream, RtxRenderStats* stats);
 
+/* ---- moving objects: new parameters for the Translate / RotateY chains of top-level slots --------------------------------
+ * Setting the ops of top-level slots on a flattened or a resident scene gives the scene that rtx_flatten (and rtx_scene_upload)
+ * build from scratch with those rtx_translate offsets and rtx_rotate_y angles: every entry point answers bit for bit as it
+ * does on that scene.  Three device arrays depend on a transform -- the slot's entry, its record in k_trace_world's slot table
+ * and the boxes of the instance tree it is a member of -- and only those are touched: no primitive, texture or BVH is re-sent.
+ *   * The chain's SHAPE is fixed: a slot's number of ops and the kind of each stay what the flattener emitted (ask
+ *     rtx_flat_slot_chain); only the parameters change.  An update names ALL ops of its slot.
+ *   * The instance tree's TOPOLOGY is fixed: its boxes are refitted bottom-up, nothing is rebuilt.  A refitted tree culls
+ *     less well than a rebuilt one once members have moved far, and RtxFlatInfo::sah_cost is NOT recomputed: it goes stale.
+ *   * A slot can be moved when its entry is a Translate / RotateY chain (rtx_flat_top_level_kind 3) or a ConstantMedium whose
+ *     boundary is such a chain (kind 4), inside or outside an instance tree.
+ * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, a slot out of
+ * range, a slot without a chain, a wrong n_ops, a wrong op kind, a slot named twice, a value that is not finite, a member whose
+ * new bounding box is not finite.  n = 0 is RTX_OK and nothing is launched. */
+#define RTX_XFORM_TRANSLATE 0
+#define RTX_XFORM_ROTATE_Y 1
+typedef struct RtxSlotOps {
+  int32_t slot;   /* index in the world list */
+  int32_t n_ops;  /* must equal the slot's chain length */
+  struct {
+    int32_t op;   /* RTX_XFORM_TRANSLATE / RTX_XFORM_ROTATE_Y: must equal the kind the chain has at this place */
+    int32_t pad;
+    double v[3];  /* translate: the offset; rotate_y: v[0] = the angle in DEGREES (v[1], v[2] ignored), turned into sin / cos on
+                     the host exactly as rtx_rotate_y does, which is what makes the result bit-equal to a fresh build */
+  } ops[4];       /* outermost first, as the wrappers are nested: Translate(RotateY(x)) is {translate, rotate_y} */
+} RtxSlotOps;
+/* Number of ops of the slot's chain, their kinds into kinds[0..n); 0 for a slot with no chain, -1 when the slot is out of range
+ * (or f or kinds is NULL). */
+int32_t rtx_flat_slot_chain(const rtx_flat* f, int32_t slot, int32_t kinds[4]);
+/* Instance tree k (0 <= k < RtxInstanceInfo::n_trees, in the order of their first slots): its members are the n_slots
+ * consecutive slots from first_slot, in list order with nested lists spliced in. */
+typedef struct RtxInstanceTree {
+  int32_t first_slot, n_slots, n_nodes, depth;
+} RtxInstanceTree;
+rtx_status rtx_flat_instance_tree(const rtx_flat* f, int32_t k, RtxInstanceTree* out);
+/* Host only.  Edits the flat scene in place (entries, and nodes / nodes32 / the static boxes of the time-aware copy of every
+ * tree that holds an updated member); it can then be uploaded, or handed to rtx_multi_create, without flattening again. */
+rtx_status rtx_flat_set_transforms(rtx_flat* f, const RtxSlotOps* updates, int64_t n);
+/* The same on a resident scene of either precision (an f32 scene takes the ops through the converter's (float) cast and its
+ * boxes rounded outward, as rtx_scene_upload_f32 does).  `updates` is a HOST array, free for reuse on return; the work -- one
+ * small copy, k_set_slot_ops, and k_refit_instance_tree once per tree that holds an updated member -- is asynchronous on
+ * hip_stream.  Ordering against renders and casts on OTHER streams is the caller's business; two updates of one scene may not
+ * run concurrently (issue them on one stream, or synchronise).  A progressive handle made before an update holds samples of
+ * the old pose: make a new one.  rtx_multi_* scenes are not covered: set the flat scene and create the handle again. */
+rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int64_t n, void* hip_stream);
+/* Test hook: copies one resident array of the scene back to the host, after everything enqueued on the device.  which:
+ * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table.  bytes must be the array's size (elements
+ * as the scene's precision lays them out); RTX_EINVAL naming the size otherwise. */
+rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
+/* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
+ * instance tree, the box before the ops). */
+rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
+
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one
  * upload): 500 x 500, 500 spp, depth 50, background (0.7, 0.8, 1), camera (13,2,3) -> (0,0,0), vfov 20, aspect 1,

@@ -11,6 +11,7 @@ if no GPU is present, upload/render raise RtxError(RTX_EHIP).
 """
 import ctypes as C
 import os
+import re
 import sys
 
 import numpy as np
@@ -132,6 +133,24 @@ class RtxRadianceRays(C.Structure):
                 ("light_sampling", C.c_int32), ("reserved", C.c_int32), ("sample_buffer_bytes", C.c_uint64)]
 
 
+class _RtxSlotOp(C.Structure):
+    _fields_ = [("op", C.c_int32), ("pad", C.c_int32), ("v", C.c_double * 3)]
+
+
+class RtxSlotOps(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n_ops", C.c_int32), ("ops", _RtxSlotOp * 4)]
+
+
+class RtxInstanceTree(C.Structure):
+    _fields_ = [("first_slot", C.c_int32), ("n_slots", C.c_int32), ("n_nodes", C.c_int32), ("depth", C.c_int32)]
+
+
+RTX_XFORM_TRANSLATE, RTX_XFORM_ROTATE_Y = 0, 1
+_XFORM_NAMES = ("translate", "rotate_y")
+# rtx_flat_array / rtx_device_scene_array: `which` and the element size in an f64 and in an f32 scene
+SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
+                "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8)}
+
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
 
@@ -238,6 +257,12 @@ ABI = {
     "rtx_radiance_rays_defaults": (None, [C.POINTER(RtxRadianceRays)]),
     "rtx_scene_trace_rays": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_scene_trace_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_flat_slot_chain": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_int32)]),
+    "rtx_flat_instance_tree": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxInstanceTree)]),
+    "rtx_flat_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64]),
+    "rtx_scene_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64, _VP]),
+    "rtx_device_scene_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
+    "rtx_flat_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_builder_graph": (_VP, [_VP]),
     "rtx_flat_arrays": (_VP, [_VP]),
 }
@@ -494,9 +519,89 @@ class Flat:
         n = self.info()["n_top_level"]
         return [lib.rtx_flat_top_level_kind(self._p, i) for i in range(n)]
 
+    def slot_chain(self, slot):
+        """The Translate / RotateY chain of a top-level slot, outermost first (rtx_flat_slot_chain): a list of "translate" /
+        "rotate_y", [] for a slot without a chain.  IndexError when the slot is out of range."""
+        kinds = (C.c_int32 * 4)()
+        n = lib.rtx_flat_slot_chain(self._p, int(slot), kinds)
+        if n < 0:
+            raise IndexError("slot %r is out of range" % (slot,))
+        return [_XFORM_NAMES[kinds[k]] for k in range(n)]
+
+    def instance_tree(self, k):
+        """Instance tree k (rtx_flat_instance_tree): first_slot, n_slots, n_nodes, depth.  Its members are the n_slots
+        consecutive slots from first_slot."""
+        info = RtxInstanceTree()
+        _check(lib.rtx_flat_instance_tree(self._p, int(k), C.byref(info)))
+        return {n: getattr(info, n) for n, _ in RtxInstanceTree._fields_}
+
+    def set_transforms(self, updates):
+        """New parameters for the chains of top-level slots, in place (rtx_flat_set_transforms): the flat scene becomes the one
+        flattened from scratch with these offsets and angles.  updates: {slot: [("translate", (x, y, z)) | ("rotate_y",
+        degrees), ...]}, every op of the slot's chain, outermost first.  ValueError for input the chain does not admit."""
+        arr = _slot_ops(self, updates)
+        _check(lib.rtx_flat_set_transforms(self._p, arr, len(arr)))
+
+    def array(self, name):
+        """A copy of one host array as bytes (rtx_flat_array; a test hook): a name of SCENE_ARRAYS but "world_desc"."""
+        return _scene_array(lambda out, n: lib.rtx_flat_array(self._p, SCENE_ARRAYS[name][0], out, n), self, name, False)
+
     def upload(self, f32=False):
         """f32=True: the statistical fast mode (rtx_scene_upload_f32): float arithmetic, no bit-exactness claim."""
         return Scene(self, f32=f32)
+
+
+def _slot_ops(flat, updates):
+    """updates of Flat.set_transforms / Scene.set_transforms -> a ctypes array of RtxSlotOps, checked against the chains of
+    `flat`.  Raises ValueError before the library sees anything."""
+    if not isinstance(updates, dict):
+        raise ValueError("updates must be a dict {slot: [op, ...]}")
+    arr = (RtxSlotOps * max(len(updates), 1))()
+    n_top = flat.info()["n_top_level"]
+    for i, (slot, ops) in enumerate(updates.items()):
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)):
+            raise ValueError("slot %r is not an integer" % (slot,))
+        if not 0 <= slot < n_top:
+            raise ValueError("slot %d is out of range (the world list has %d slots)" % (slot, n_top))
+        chain = flat.slot_chain(slot)
+        if not chain:
+            raise ValueError("slot %d has no Translate / RotateY chain" % slot)
+        ops = list(ops)
+        if len(ops) != len(chain):
+            raise ValueError("slot %d: %d ops given, its chain has %d (%s)" % (slot, len(ops), len(chain), ", ".join(chain)))
+        arr[i].slot, arr[i].n_ops = int(slot), len(ops)
+        for k, op in enumerate(ops):
+            if not isinstance(op, (tuple, list)) or len(op) != 2 or op[0] not in _XFORM_NAMES:
+                raise ValueError('slot %d, op %d: expected ("translate", (x, y, z)) or ("rotate_y", degrees), got %r' % (slot, k, op))
+            if op[0] != chain[k]:
+                raise ValueError("slot %d, op %d is a %s in the scene, not a %s" % (slot, k, chain[k], op[0]))
+            try:
+                vals = [float(x) for x in op[1]] if op[0] == "translate" else [float(op[1])]
+            except (TypeError, ValueError):
+                raise ValueError("slot %d, op %d: %r is not %s" % (slot, k, op[1], "three numbers" if op[0] == "translate" else "a number"))
+            if len(vals) != (3 if op[0] == "translate" else 1) or not all(np.isfinite(vals)):
+                raise ValueError("slot %d, op %d: %r is not %s" % (slot, k, op[1], "three finite numbers" if op[0] == "translate" else "a finite number"))
+            arr[i].ops[k].op = _XFORM_NAMES.index(op[0])
+            for a, x in enumerate(vals):
+                arr[i].ops[k].v[a] = x
+    return (RtxSlotOps * len(updates)).from_buffer(arr) if len(updates) else (RtxSlotOps * 0)()
+
+
+def _scene_array(call, flat, name, f32):
+    """One array through rtx_flat_array / rtx_device_scene_array as a uint8 numpy array; the size comes from Flat.info()."""
+    info = flat.info()
+    elem = SCENE_ARRAYS[name][2 if f32 else 1]
+    count = {"entries": info["n_entries"], "nodes": info["n_nodes"], "nodes32": info["n_nodes"], "top_level": info["n_top_level"]}.get(name)
+    if count is None:  # motion32 (n_nodes or none), world_desc, member_local_box: ask with 0 bytes, the refusal names the size
+        if call(None, 0) == RTX_OK:
+            return np.zeros(0, dtype=np.uint8)
+        m = re.search(r"holds (\d+) bytes", last_error())
+        if not m:
+            raise RtxError(RTX_EINVAL, last_error())
+        count = int(m.group(1)) // elem
+    out = np.zeros(count * elem, dtype=np.uint8)
+    _check(call(out.ctypes.data_as(_VP), out.size))
+    return out
 
 
 class Scene:
@@ -506,6 +611,7 @@ class Scene:
         p = _VP()
         _check((lib.rtx_scene_upload_f32 if f32 else lib.rtx_scene_upload)(flat.ptr, C.byref(p)))
         self._p = p
+        self._flat = flat  # set_transforms checks its input against the slots' chains, whose shape never changes
 
     @property
     def is_f32(self):
@@ -538,6 +644,20 @@ class Scene:
             return screen
         _check(lib.rtx_render(self._p, C.byref(cam), C.byref(cfg), C.byref(frame)))
         return Screen(w, h, rgb8, accum)
+
+    def set_transforms(self, updates, stream=None):
+        """New parameters for the chains of top-level slots of the RESIDENT scene (rtx_scene_set_transforms): every later call
+        answers as on a scene flattened and uploaded from scratch with these offsets and angles.  updates as in
+        Flat.set_transforms.  Enqueued on `stream` (a raw hipStream_t, an object with .cuda_stream such as a torch stream, or
+        None for the default stream); ordering against work on other streams is the caller's."""
+        arr = _slot_ops(self._flat, updates)
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(lib.rtx_scene_set_transforms(self._p, arr, len(arr), _VP(raw or None)))
+
+    def array(self, name):
+        """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
+        "nodes", "nodes32", "motion32" or "world_desc"."""
+        return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)
 
     def trim(self):
         """Release the render workspace (sample buffer, accumulators); the geometry stays resident."""

@@ -6,8 +6,11 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
+#include <vector>
 #include "../host/scenes.hpp"
 #include "../host/light_table.hpp"
+#include "../host/set_transforms.hpp"
 #include "abi_internal.hpp"
 
 namespace rtx {
@@ -47,6 +50,18 @@ rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadian
   if (!bad) return RTX_OK;
   set_error(std::string(who) + ": " + bad);
   return RTX_EINVAL;
+}
+rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved) {
+  std::string err;
+  if (!check_slot_ops_shape(who, s, updates, n, &err)) { set_error(err); return RTX_EINVAL; }
+  *resolved = resolve_slot_ops(updates, n);
+  return RTX_OK;
+}
+// The size check of the test hook rtx_flat_array.
+static rtx_status check_array_bytes(const char* who, size_t have, const void* out, size_t bytes) {
+  if (bytes != have) { set_error(std::string(who) + ": the array holds " + std::to_string(have) + " bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
+  if (have && !out) { set_error(std::string(who) + ": out is NULL"); return RTX_EINVAL; }
+  return RTX_OK;
 }
 }  // namespace rtx
 
@@ -279,6 +294,62 @@ rtx_status rtx_flat_instances(const rtx_flat* f, RtxInstanceInfo* o) {
   o->n_trees = s.n_instance_trees; o->n_members = s.n_instance_members;
   o->n_nodes = s.n_instance_nodes; o->max_depth = s.instance_depth;
   return RTX_OK;
+}
+
+int32_t rtx_flat_slot_chain(const rtx_flat* f, int32_t slot, int32_t kinds[4]) {
+  if (!f || !kinds || slot < 0 || (size_t)slot >= f->scene.top_level.size()) return -1;
+  const FlatScene& s = f->scene;
+  const rt::FlatEntry* E = &s.entries[(size_t)s.top_level[(size_t)slot]];
+  if (E->kind == rt::ENTRY_MEDIUM) E = &s.entries[(size_t)E->a];
+  if (E->kind != rt::ENTRY_XFORM) return 0;
+  for (int k = 0; k < E->b; ++k) kinds[k] = E->ops[k].op;
+  return E->b;
+}
+
+rtx_status rtx_flat_instance_tree(const rtx_flat* f, int32_t k, RtxInstanceTree* o) {
+  if (!f || !o) { set_error("rtx_flat_instance_tree: NULL argument"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  int32_t seen = 0;
+  for (const rt::FlatEntry& e : s.entries) {
+    if (e.kind != rt::ENTRY_INSTANCE || e.a < 0 || seen++ != k) continue;
+    o->first_slot = e.b; o->n_slots = e.c; o->n_nodes = e.c - 1;
+    // the height in nodes, as the builder counts it: the stack entries a walk of the tree can hold
+    int32_t depth = 0;
+    std::vector<std::pair<int32_t, int32_t>> todo{{e.a, 1}};
+    while (!todo.empty()) {
+      const std::pair<int32_t, int32_t> n = todo.back();
+      todo.pop_back();
+      depth = std::max(depth, n.second);
+      for (int c = 0; c < 2; ++c)
+        if (!rt::node_child_is_leaf(s.nodes[(size_t)n.first].child[c])) todo.push_back({s.nodes[(size_t)n.first].child[c], n.second + 1});
+    }
+    o->depth = depth;
+    return RTX_OK;
+  }
+  set_error("rtx_flat_instance_tree: k is out of range (the scene has " + std::to_string(s.n_instance_trees) + " instance trees)");
+  return RTX_EINVAL;
+}
+
+rtx_status rtx_flat_set_transforms(rtx_flat* f, const RtxSlotOps* updates, int64_t n) {
+  std::string err;
+  if (!flat_set_transforms("rtx_flat_set_transforms", f ? &f->scene : nullptr, updates, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes) {
+  if (!f) { set_error("rtx_flat_array: NULL flat"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  const void* p = nullptr;
+  size_t have = 0;
+#define ARR(W, VEC) case W: p = s.VEC.data(); have = s.VEC.size() * sizeof(s.VEC[0]); break;
+  switch (which) {
+    ARR(0, entries) ARR(1, nodes) ARR(2, nodes32) ARR(3, motion32) ARR(5, top_level) ARR(6, member_local_box)
+    default: set_error("rtx_flat_array: which names no host array"); return RTX_EINVAL;
+  }
+#undef ARR
+  const rtx_status st = check_array_bytes("rtx_flat_array", have, out, bytes);
+  if (st == RTX_OK && have) memcpy(out, p, have);
+  return st;
 }
 
 void rtx_ray_batch_defaults(RtxRayBatch* b) {

@@ -1,6 +1,7 @@
 // Glue shared by abi.cpp (host-only entry points) and render.hip (device entry points).
 #pragma once
 #include <string>
+#include <vector>
 #include "../../../include/rtx_abi.h"
 #include "../host/flat_scene.hpp"
 #include "../host/scene_graph.hpp"
@@ -41,5 +42,8 @@ inline void free_scene_handle(rtx_scene* s) { delete s; }
 rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits);
 // The same for rtx_scene_trace_rays and rtx_scene_trace_rays_device.
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb);
+// The checks of rtx_scene_set_transforms that need no scene (host/set_transforms.hpp: check_slot_ops_shape; s is compared with
+// NULL and not read), then *resolved = the updates with every angle turned into sin / cos as the flat arrays hold them.
+rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved);
 
 }  // namespace rtx

@@ -43,6 +43,11 @@ struct RtxSceneOps {
   // synchronises.  Uses the scene's render workspace.
   rtx_status (*trace_rays)(void* device_scene, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
                            hipStream_t stream, RtxRenderStats* stats);
+  // rtx_scene_set_transforms (scene_update.inc): n > 0 updates in host memory, already through the checks that need no scene
+  // and RESOLVED (a rotate_y holds v[0] = sin, v[1] = cos); checks the rest against the scene, then enqueues
+  rtx_status (*set_transforms)(void* device_scene, const RtxSlotOps* resolved, int64_t n, hipStream_t stream);
+  // rtx_device_scene_array: one resident array copied to the host (blocking)
+  rtx_status (*read_array)(void* device_scene, int32_t which, void* out, size_t bytes);
 };
 
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);

@@ -23,7 +23,8 @@ rtx_status rtx_f32_upload(const RtxF32Blobs* b, void** device_scene) {
             take_blob(*b, RTX32_TEXTURES, &fs.textures) && take_blob(*b, RTX32_PERLINS, &fs.perlins) &&
             take_blob(*b, RTX32_IMAGES, &fs.images) && take_blob(*b, RTX32_TEXELS, &fs.texels) &&
             take_blob(*b, RTX32_TOP_BOX32, &fs.top_box32) && take_blob(*b, RTX32_GRAVITY_SPHERES, &fs.gravity_spheres) &&
-            take_blob(*b, RTX32_GRAVITY_Y, &fs.gravity_y) && take_blob(*b, RTX32_MOTION32, &fs.motion32);
+            take_blob(*b, RTX32_GRAVITY_Y, &fs.gravity_y) && take_blob(*b, RTX32_MOTION32, &fs.motion32) &&
+            take_blob(*b, RTX32_MEMBER_LOCAL_BOX, &fs.member_local_box) && take_blob(*b, RTX32_SLOT_OPS64, &fs.slot_ops64);
   if (!ok) { set_error("rtx_scene_upload_f32: the f32 layout table of f32_layout.hpp disagrees with the compiled structs"); return RTX_EINVAL; }
   fs.max_stack = b->max_stack;
   fs.n_bvh = b->n_bvh;

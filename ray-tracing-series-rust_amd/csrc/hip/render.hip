@@ -28,6 +28,7 @@
 #include "../core/integrator.hpp"
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
+#include "../host/update_shadow.hpp"
 #include "device_buffer.hpp"
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
@@ -154,6 +155,21 @@ struct WalkTuning {
   bool single_leaf = false;       // every BVH leaf holds one primitive (k_trace_lds tests it without a loop)
 };
 
+// rtx_scene_set_transforms (scene_update.inc): what an update needs beside the scene's arrays, kept from the upload.
+struct SceneUpdate {
+  UpdateShadow shadow;              // host: the slots' chains, the instance trees and their parent tables
+  std::vector<double> local_box;    // host: FlatScene::member_local_box (an update's new boxes are checked before anything is enqueued)
+  size_t n_entries = 0, n_nodes = 0, n_motion = 0, n_desc = 0;  // element counts of the arrays an update writes (rtx_device_scene_array)
+  DeviceBuffer<double> d_local_box;
+  DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
+  DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
+  DeviceBuffer<rt::XformOp64> d_slot_ops64;     // the f32 compilation only: the slots' ops in f64
+  DeviceBuffer<unsigned char> d_staging;        // the update records of one call
+  void* h_staging = nullptr;                    // pinned; `staged` marks the end of the copy out of it
+  size_t h_staging_bytes = 0;
+  hipEvent_t staged = nullptr;
+};
+
 struct DeviceScene {
   int device = -1;
   std::vector<DeviceBuffer<void>> allocations;  // the uploaded arrays
@@ -169,6 +185,7 @@ struct DeviceScene {
   LdsPlan lds;
   WalkTuning walk;
   rt::LightView lights = {nullptr, nullptr, 0, 0};  // next-event estimation's light table (k_trace_nee), uploaded with the scene
+  SceneUpdate upd;
 };
 
 #define HIP_TRY(expr)                                                                      \
@@ -195,8 +212,10 @@ static rtx_status upload_array(DeviceScene* ds, const std::vector<T>& v, const T
 }
 
 // Releases what is not device memory; the buffers go with the DeviceScene.
+static void free_scene_update(SceneUpdate* u);
 static void free_device_scene(DeviceScene* ds) {
   if (!ds) return;
+  free_scene_update(&ds->upd);
   Workspace& ws = ds->ws;
   if (ws.wave_host_ctrl) (void)hipHostFree(ws.wave_host_ctrl);
   for (int i = 0; i < 2; ++i)
@@ -273,6 +292,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
+#include "scene_update.inc"  // k_set_slot_ops, k_refit_instance_tree: new Translate / RotateY parameters on a resident scene
 
 // ------------------------------------------------------------------ launcher
 static int shard_row_count(int32_t height, const RtxShard& sh, int32_t row_limit) {
@@ -1447,6 +1467,10 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
     return st;
   }
   plan_walk(ds, leaves);
+  if ((st = build_scene_update(ds, fs)) != RTX_OK) {
+    free_device_scene(ds);
+    return st;
+  }
   *out = ds;
   return RTX_OK;
 }
@@ -1479,6 +1503,10 @@ static const RtxSceneOps scene_ops = {
     [](void* ds, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb, hipStream_t stream, RtxRenderStats* stats) {
       return trace_rays_impl((DeviceScene*)ds, rays, d_sum_rgb, d_sumsq_rgb, stream, stats);
     },
+    [](void* ds, const RtxSlotOps* resolved, int64_t n, hipStream_t stream) {
+      return scene_set_transforms_impl((DeviceScene*)ds, resolved, n, stream);
+    },
+    [](void* ds, int32_t which, void* out, size_t bytes) { return scene_read_array_impl((DeviceScene*)ds, which, out, bytes); },
 };
 
 }  // namespace rtx
@@ -1595,6 +1623,20 @@ rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, cons
   }
   HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxRayHits (a timing run) still returns after its launches
   return RTX_OK;
+}
+
+// ---- moving objects.  What needs no scene is checked first (abi.cpp: check_set_transforms), then the scene's own compilation
+// checks the rest against its shadow of the upload and enqueues (scene_update.inc).
+rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int64_t n, void* hip_stream) {
+  std::vector<RtxSlotOps> resolved;
+  const rtx_status st = check_set_transforms("rtx_scene_set_transforms", s, updates, n, &resolved);
+  if (st != RTX_OK || n == 0) return st;
+  return s->ops->set_transforms(s->device_scene, resolved.data(), n, (hipStream_t)hip_stream);
+}
+
+rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes) {
+  if (!s) { set_error("rtx_device_scene_array: NULL scene"); return RTX_EINVAL; }
+  return s->ops->read_array(s->device_scene, which, out, bytes);
 }
 
 // ---- radiance queries.  The arguments are checked first (abi.cpp: check_trace_rays), before any device call.

@@ -1,0 +1,239 @@
+// rtx_scene_set_transforms on a resident scene (included by render.hip, namespace rtx; compiled by both compilations).
+//
+// New parameters for the Translate / RotateY chains of top-level slots reach three device arrays and no other:
+//   entries[xform].ops      what every scan transforms a ray by (core/geometry.hpp)
+//   WorldDesc[slot].ops     k_trace_world's copy of the same ops (trace_world.inc)
+//   nodes / nodes32 / motion32 of the instance tree the slot is a member of: the members' boxes in WORLD space
+// k_set_slot_ops scatters the first two; k_refit_instance_tree recomputes the third for one tree, bottom-up, with the
+// arithmetic the flattener used (core/member_box.hpp), so that the arrays equal those of a scene flattened and uploaded from
+// scratch with the new parameters -- the judge of tests/test_gpu_set_transforms.py.  Topology is not touched: child codes,
+// split axes and every other array stay as uploaded, and no existing kernel changes.
+//
+// The boxes are computed in f64 in BOTH compilations and narrowed last: an f32 scene's node planes are the f64 planes rounded
+// down / up (host/f32_layout.hpp: "d6 u6"), so its refit starts from the f64 ops it keeps in SceneUpdate::slot_ops64 -- the
+// ops in its own entries went through a (float) cast.  Min and max commute with a monotone rounding, so above the leaves the
+// f32 compilation unites the narrowed planes and still gets the narrowed unions.
+
+// One update as the device takes it: the slot, its ENTRY_XFORM and the resolved ops (a rotate_y as sin, cos).
+struct SlotOpsRecord {  // 144 B
+  int32_t slot, xform, n_ops, pad;
+  rt::XformOp64 ops[RT_MAX_XFORM_OPS];
+};
+
+// One thread per update.  The host has checked slot, xform and n_ops against the scene (host/update_shadow.hpp).
+__global__ __launch_bounds__(256) void k_set_slot_ops(const SlotOpsRecord* __restrict__ rec, int n, rt::FlatEntry* __restrict__ entries,
+                                                     WorldDesc* __restrict__ desc, rt::XformOp64* __restrict__ slot_ops64) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i >= n) return;
+  const int32_t slot = rec[i].slot, xform = rec[i].xform;
+  const int n_ops = rec[i].n_ops < RT_MAX_XFORM_OPS ? rec[i].n_ops : RT_MAX_XFORM_OPS;
+  for (int k = 0; k < n_ops; ++k) {
+    const rt::XformOp64 in = rec[i].ops[k];
+    rt::FlatXformOp o;
+    o.op = in.op; o.pad = 0;
+    for (int a = 0; a < 3; ++a) o.v[a] = (rt::real)in.v[a];  // the converter's cast (host/f32_layout.hpp: 'r')
+    entries[xform].ops[k] = o;
+    desc[slot].ops[k] = o;
+    if (slot_ops64) slot_ops64[(size_t)slot * RT_MAX_XFORM_OPS + k] = in;
+  }
+}
+
+struct RefitArgs {
+  const rt::FlatEntry* entries;
+  const int32_t* top_level;
+  rt::FlatNode* nodes;
+  rt::FlatNode32* nodes32;
+  rt::FlatMotion32* motion32;         // NULL: the scene has no time-aware boxes
+  const double* local_box;            // 6 per member, this tree's first member first
+  const int32_t* leaf_parent;         // 2 per member: node, child index
+  const int32_t* node_parent;         // 2 per node of this tree, by node - node_base: parent (-1: root), child index
+  unsigned int* arrivals;             // 1 per node of this tree, zero at launch
+  const rt::XformOp64* slot_ops64;    // the f32 compilation's f64 ops, RT_MAX_XFORM_OPS per slot; NULL in the f64 compilation
+  int32_t first_slot, n_slots, node_base;
+};
+
+__device__ __forceinline__ rt::real refit_plane_down(double x) {
+#ifdef RT_F32
+  return rt::f32_narrow_down(x);
+#else
+  return x;
+#endif
+}
+__device__ __forceinline__ rt::real refit_plane_up(double x) {
+#ifdef RT_F32
+  return rt::f32_narrow_up(x);
+#else
+  return x;
+#endif
+}
+
+// One thread per member slot of ONE tree -- every member, not only the moved ones: the thread recomputes the member's world box,
+// writes it where its parent node keeps it and climbs.  Of the two threads that reach a node the first leaves; the second
+// unites the node's two child boxes into the node's place in ITS parent.  lbvh.hip's k_refit recipe for visibility across
+// workgroups: the box stores, a fence, an agent-scope atomic arrival, a fence, agent-scope loads of the sibling's box.  Unions
+// are exact min / max, so the result does not depend on who arrives first.
+__global__ __launch_bounds__(256) void k_refit_instance_tree(RefitArgs a) {
+  const int m = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (m >= a.n_slots) return;
+  const int32_t slot = a.first_slot + m;
+  rt::XformOp64 ops[RT_MAX_XFORM_OPS];
+  int n_ops = 0;
+  const rt::FlatEntry* S = &a.entries[a.top_level[slot]];
+  if (S->kind == rt::ENTRY_XFORM) {
+    n_ops = S->b < RT_MAX_XFORM_OPS ? S->b : RT_MAX_XFORM_OPS;
+    for (int k = 0; k < n_ops; ++k) {
+#ifdef RT_F32
+      ops[k] = a.slot_ops64[(size_t)slot * RT_MAX_XFORM_OPS + k];
+#else
+      ops[k].op = S->ops[k].op; ops[k].pad = 0;
+      for (int x = 0; x < 3; ++x) ops[k].v[x] = S->ops[k].v[x];
+#endif
+    }
+  }
+  double local[6], b[6];
+  for (int x = 0; x < 6; ++x) local[x] = a.local_box[6 * (size_t)m + x];
+  rt::member_box_through_ops(local, ops, n_ops, b);
+  rt::real lo[3], hi[3];
+  for (int x = 0; x < 3; ++x) { lo[x] = refit_plane_down(b[x]); hi[x] = refit_plane_up(b[3 + x]); }
+  int32_t node = a.leaf_parent[2 * (size_t)m], c = a.leaf_parent[2 * (size_t)m + 1];
+  for (;;) {
+    rt::FlatNode* nd = &a.nodes[node];
+    for (int x = 0; x < 3; ++x) {
+      // a sibling's climber on another CU reads these: agent-scope stores, as in k_refit
+      __hip_atomic_store(&nd->bmin[c][x], lo[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&nd->bmax[c][x], hi[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float l32 = rt::f32_narrow_down((double)lo[x]), h32 = rt::f32_narrow_up((double)hi[x]);
+      a.nodes32[node].lo[c][x] = l32;
+      a.nodes32[node].hi[c][x] = h32;
+      if (a.motion32) {  // an instance tree has no time interval: its static box, no slope
+        a.motion32[node].lo0[c][x] = l32; a.motion32[node].hi0[c][x] = h32;
+        a.motion32[node].dlo[c][x] = 0.0f; a.motion32[node].dhi[c][x] = 0.0f;
+      }
+    }
+    const int32_t rel = node - a.node_base;
+    const int32_t parent = a.node_parent[2 * (size_t)rel], pc = a.node_parent[2 * (size_t)rel + 1];
+    if (parent < 0) return;  // the root: its two child boxes are the whole tree
+    __threadfence();
+    if (atomicAdd(&a.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
+    __threadfence();
+    for (int x = 0; x < 3; ++x) {
+      const rt::real slo = __hip_atomic_load(&nd->bmin[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const rt::real shi = __hip_atomic_load(&nd->bmax[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      lo[x] = rt::rt_fmin(lo[x], slo);
+      hi[x] = rt::rt_fmax(hi[x], shi);
+    }
+    node = parent;
+    c = pc;
+  }
+}
+
+// ------------------------------------------------------------------ host side
+// What an update needs beside the scene's arrays, built once at upload (scene_upload_impl).
+static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
+  SceneUpdate& u = ds->upd;
+  u.shadow = build_update_shadow(fs);
+  u.local_box = fs.member_local_box;
+  u.n_entries = fs.entries.size(); u.n_nodes = fs.nodes.size(); u.n_motion = fs.motion32.size();
+  u.n_desc = fs.top_level.size();
+  if (fs.features & rt::F_INSTANCE)
+    for (const rt::FlatEntry& e : fs.entries) u.n_desc += e.kind == rt::ENTRY_INSTANCE ? 1 : 0;
+  if (!u.shadow.broken.empty() || u.shadow.trees.empty()) return RTX_OK;
+  HIP_TRY(u.d_local_box.upload(u.local_box.data(), u.local_box.size()));
+  HIP_TRY(u.d_leaf_parent.upload(u.shadow.leaf_parent.data(), u.shadow.leaf_parent.size()));
+  HIP_TRY(u.d_node_parent.upload(u.shadow.node_parent.data(), u.shadow.node_parent.size()));
+  HIP_TRY(u.d_arrivals.alloc(u.shadow.node_parent.size() / 2 * sizeof(unsigned int)));
+#ifdef RT_F32
+  if (fs.slot_ops64.size() != fs.top_level.size() * RT_MAX_XFORM_OPS) {
+    u.shadow.broken = "the f32 scene did not receive the f64 ops of its slots";
+    return RTX_OK;
+  }
+  HIP_TRY(u.d_slot_ops64.upload(fs.slot_ops64.data(), fs.slot_ops64.size()));
+#endif
+  return RTX_OK;
+}
+
+static void free_scene_update(SceneUpdate* u) {
+  if (u->h_staging) (void)hipHostFree(u->h_staging);
+  if (u->staged) (void)hipEventDestroy(u->staged);
+  u->h_staging = nullptr;
+  u->staged = nullptr;
+}
+
+// `resolved` (host memory, n > 0) has passed check_slot_ops_shape.  Every check against the scene comes first; then one copy,
+// k_set_slot_ops and one k_refit_instance_tree per tree that holds an updated member, all on `stream`.
+static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* resolved, int64_t n, hipStream_t stream) {
+  SceneUpdate& u = ds->upd;
+  std::string err;
+  if (!check_slot_ops_scene("rtx_scene_set_transforms", u.shadow, u.local_box.data(), resolved, n, &err)) { set_error(err); return RTX_EINVAL; }
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("rtx_scene_set_transforms: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  // the pinned staging buffer is this scene's own: the copy of the previous update must have left it
+  if (!u.staged) HIP_TRY(hipEventCreateWithFlags(&u.staged, hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(u.staged));
+  const size_t bytes = (size_t)n * sizeof(SlotOpsRecord);
+  if (bytes > u.h_staging_bytes) {
+    if (u.h_staging) HIP_TRY(hipHostFree(u.h_staging));
+    u.h_staging = nullptr;
+    u.h_staging_bytes = 0;
+    HIP_TRY(hipHostMalloc(&u.h_staging, bytes, hipHostMallocDefault));
+    u.h_staging_bytes = bytes;
+  }
+  HIP_TRY(u.d_staging.grow(bytes, stream));
+  SlotOpsRecord* rec = (SlotOpsRecord*)u.h_staging;
+  std::vector<char> touched(u.shadow.trees.size(), 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const SlotChain& c = u.shadow.slots[(size_t)resolved[i].slot];
+    memset(&rec[i], 0, sizeof(SlotOpsRecord));
+    rec[i].slot = resolved[i].slot; rec[i].xform = c.xform; rec[i].n_ops = c.n_ops;
+    static_assert(sizeof(rec[i].ops) == sizeof(resolved[i].ops), "RtxSlotOps::ops is rt::XformOp64");
+    memcpy(rec[i].ops, resolved[i].ops, sizeof(rec[i].ops));
+    if (c.tree >= 0) touched[(size_t)c.tree] = 1;
+  }
+  HIP_TRY(hipMemcpyAsync((void*)(unsigned char*)u.d_staging, u.h_staging, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(u.staged, stream));
+  hipLaunchKernelGGL(k_set_slot_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const SlotOpsRecord*)(unsigned char*)u.d_staging,
+                     (int)n, (rt::FlatEntry*)ds->view.entries, (WorldDesc*)ds->world.desc, (rt::XformOp64*)u.d_slot_ops64);
+  HIP_TRY(hipGetLastError());
+  for (size_t k = 0; k < u.shadow.trees.size(); ++k) {
+    if (!touched[k]) continue;
+    const TreeShadow& t = u.shadow.trees[k];
+    RefitArgs a;
+    a.entries = ds->view.entries; a.top_level = ds->view.top_level;
+    a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
+    a.local_box = u.d_local_box + 6 * (size_t)t.member_first;
+    a.leaf_parent = u.d_leaf_parent + 2 * (size_t)t.member_first;
+    a.node_parent = u.d_node_parent + 2 * (size_t)t.node_first;
+    a.arrivals = u.d_arrivals + (size_t)t.node_first;
+    a.slot_ops64 = u.d_slot_ops64;
+    a.first_slot = t.first_slot; a.n_slots = t.n_slots; a.node_base = t.node_base;
+    HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)t.n_nodes * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_refit_instance_tree, dim3((unsigned)((t.n_slots + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return RTX_OK;
+}
+
+// rtx_device_scene_array: one resident array back to the host, after everything enqueued on the device.
+static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* out, size_t bytes) {
+  const SceneUpdate& u = ds->upd;
+  const void* p = nullptr;
+  size_t have = 0;
+  switch (which) {
+    case 0: p = ds->view.entries; have = u.n_entries * sizeof(rt::FlatEntry); break;
+    case 1: p = ds->view.nodes; have = u.n_nodes * sizeof(rt::FlatNode); break;
+    case 2: p = ds->view.nodes32; have = u.n_nodes * sizeof(rt::FlatNode32); break;
+    case 3: p = ds->view.motion32; have = u.n_motion * sizeof(rt::FlatMotion32); break;
+    case 4: p = ds->world.desc; have = u.n_desc * sizeof(WorldDesc); break;
+    default: set_error("rtx_device_scene_array: which names no resident array"); return RTX_EINVAL;
+  }
+  if (bytes != have) { set_error("rtx_device_scene_array: the array holds " + std::to_string(have) + " bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
+  if (have == 0) return RTX_OK;
+  if (!out) { set_error("rtx_device_scene_array: out is NULL"); return RTX_EINVAL; }
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("rtx_device_scene_array: scene lives on a different device than the current one"); return RTX_EINVAL; }
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, p, have, hipMemcpyDeviceToHost));
+  return RTX_OK;
+}

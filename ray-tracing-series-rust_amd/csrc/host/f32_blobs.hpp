@@ -9,7 +9,9 @@
 enum RtxF32Array : int {
   RTX32_SPHERES = 0, RTX32_MOVING_SPHERES, RTX32_RECTS, RTX32_TRIANGLES, RTX32_NODES, RTX32_NODES32, RTX32_REFS,
   RTX32_ENTRIES, RTX32_TOP_LEVEL, RTX32_MATERIALS, RTX32_TEXTURES, RTX32_PERLINS, RTX32_IMAGES, RTX32_TEXELS,
-  RTX32_TOP_BOX32, RTX32_GRAVITY_SPHERES, RTX32_GRAVITY_Y, RTX32_MOTION32, RTX32_N_ARRAYS
+  RTX32_TOP_BOX32, RTX32_GRAVITY_SPHERES, RTX32_GRAVITY_Y, RTX32_MOTION32,
+  // what a refit of an f32 scene starts from, in f64 (FlatScene::member_local_box, ::slot_ops64)
+  RTX32_MEMBER_LOCAL_BOX, RTX32_SLOT_OPS64, RTX32_N_ARRAYS
 };
 struct RtxF32Blobs {
   const void* data[RTX32_N_ARRAYS];

@@ -124,6 +124,25 @@ static bool f32_images(const FlatScene& fs, std::vector<unsigned char> img[RTX32
   SHARE(RTX32_TOP_LEVEL, top_level);
   SHARE(RTX32_IMAGES, images);
   SHARE(RTX32_TOP_BOX32, top_box32);
+  SHARE(RTX32_MEMBER_LOCAL_BOX, member_local_box);
+  {
+    // the ops of every slot's chain as they are BEFORE the (float) cast above: a refit on the f32 side computes a member's box
+    // in f64 from these, as the flattener did, and narrows the box -- never a box from narrowed ops
+    std::vector<unsigned char>& im = img[RTX32_SLOT_OPS64];
+    im.assign(fs.top_level.size() * RT_MAX_XFORM_OPS * sizeof(rt::XformOp64), 0);
+    for (size_t k = 0; k < fs.top_level.size(); ++k) {
+      const rt::FlatEntry* E = &fs.entries[(size_t)fs.top_level[k]];
+      if (E->kind == rt::ENTRY_MEDIUM) E = &fs.entries[(size_t)E->a];
+      if (E->kind != rt::ENTRY_XFORM) continue;
+      for (int i = 0; i < E->b; ++i) {
+        rt::XformOp64 op;
+        op.op = E->ops[i].op; op.pad = 0;
+        for (int a = 0; a < 3; ++a) op.v[a] = E->ops[i].v[a];
+        memcpy(im.data() + (k * RT_MAX_XFORM_OPS + (size_t)i) * sizeof(op), &op, sizeof(op));
+      }
+    }
+    b->data[RTX32_SLOT_OPS64] = im.data(); b->bytes[RTX32_SLOT_OPS64] = im.size(); b->elem_bytes[RTX32_SLOT_OPS64] = sizeof(rt::XformOp64);
+  }
 #undef CONVERT
 #undef SHARE
   b->max_stack = fs.max_stack;

@@ -4,6 +4,7 @@
 #include <string>
 #include <vector>
 #include "../core/flat_types.hpp"
+#include "../core/member_box.hpp"
 #include "scene_graph.hpp"
 
 namespace rtx {
@@ -34,6 +35,13 @@ struct FlatScene {
   double sah_cost = 0.0;      // summed SAH cost of all BVHs (diagnostic)
   double bvh_build_ms = 0.0;  // wall time of all BVH builds (host or GPU builder)
   double bvh_device_ms = 0.0; // GPU builder only: device time (HIP events), uploads and downloads included
+  // What rtx_flat_set_transforms / rtx_scene_set_transforms refit an instance tree from (host/set_transforms.hpp): the box of
+  // every member slot BEFORE its ops -- the ordered union of its primitives' boxes, lo xyz then hi xyz -- 6 doubles per member,
+  // tree after tree in the order of the ENTRY_INSTANCE records, members in slot order.
+  std::vector<double> member_local_box;
+  // The f32 side of the seam only (host/f32_layout.hpp fills it, an f64 flat leaves it empty): the ops of every top-level slot in
+  // f64, RT_MAX_XFORM_OPS per slot, because the f32 scene's own entries hold them narrowed and its refit must start from doubles.
+  std::vector<rt::XformOp64> slot_ops64;
 
   // pointers into the vectors above (host memory)
   rt::SceneView view() const {

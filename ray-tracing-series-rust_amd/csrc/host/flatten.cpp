@@ -17,6 +17,7 @@
 #include <cmath>
 #include <cstring>
 #include "../core/geometry.hpp"
+#include "../core/member_box.hpp"
 #include "../core/shading.hpp"
 #include "flat_scene.hpp"
 
@@ -429,46 +430,27 @@ struct Flattener {
   // magnitude met on the way (coordinates before and after every op, offsets), which is at least two f32 ulps of the plane
   // itself whatever its own value -- a plane at exactly 0 or at an exactly representable value gets the same slack (see
   // core/cull32.hpp, "boxes of transformed members", for what this slack has to cover).
-  bool member_world_box(int32_t entry, double* b) {
+  // (The ops and the pad are core/member_box.hpp: member_box_through_ops, shared with the refits of rtx_*_set_transforms.
+  // local receives the box BEFORE the ops, which FlatScene::member_local_box keeps for them.)
+  bool member_world_box(int32_t entry, double* local, double* b) {
     const rt::FlatEntry S = out.entries[(size_t)entry];
     const rt::FlatEntry G = S.kind == rt::ENTRY_XFORM ? out.entries[(size_t)S.a] : S;
-    for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+    for (int a = 0; a < 3; ++a) { local[a] = INFINITY; local[3 + a] = -INFINITY; }
     auto grow = [&](rt::PrimRef ref) {
       double pb[6];
       prim_box(ref, 0.0, 0.0, pb);
       // a sphere of negative radius (the hollow-glass idiom) has an INVERTED reference box, centre - r .. centre + r
       // (hit.rs:239-244): each axis is ordered before the union, or the union -- and every ancestor -- loses the sphere
-      for (int a = 0; a < 3; ++a) { b[a] = std::fmin(b[a], std::fmin(pb[a], pb[3 + a])); b[3 + a] = std::fmax(b[3 + a], std::fmax(pb[a], pb[3 + a])); }
+      for (int a = 0; a < 3; ++a) { local[a] = std::fmin(local[a], std::fmin(pb[a], pb[3 + a])); local[3 + a] = std::fmax(local[3 + a], std::fmax(pb[a], pb[3 + a])); }
     };
     if (G.kind == rt::ENTRY_PRIM) grow((rt::PrimRef)G.a);
     else if (G.kind == rt::ENTRY_GROUP) for (int32_t i = 0; i < G.b; ++i) grow(out.refs[(size_t)G.a + i]);
     else for (int32_t i = 0; i < G.c; ++i) grow(out.refs[(size_t)G.b + i]);
-    double mag = 0.0;
-    auto seen = [&]() { for (int a = 0; a < 6; ++a) mag = std::fmax(mag, std::fabs(b[a])); };
-    seen();
     const int nops = S.kind == rt::ENTRY_XFORM ? S.b : 0;
-    for (int k = nops - 1; k >= 0; --k) {
-      const rt::FlatXformOp& op = S.ops[k];
-      if (op.op == rt::XFORM_TRANSLATE) {
-        for (int a = 0; a < 3; ++a) { b[a] += op.v[a]; b[3 + a] += op.v[a]; mag = std::fmax(mag, std::fabs(op.v[a])); }
-      } else {
-        const double sin_t = op.v[0], cos_t = op.v[1];
-        double lo[3] = {INFINITY, b[1], INFINITY}, hi[3] = {-INFINITY, b[4], -INFINITY};
-        for (int i = 0; i < 2; ++i)
-          for (int j = 0; j < 2; ++j) {
-            const double x = i ? b[3] : b[0], z = j ? b[5] : b[2];
-            const double nx = cos_t * x + sin_t * z, nz = -sin_t * x + cos_t * z;
-            lo[0] = std::fmin(lo[0], nx); hi[0] = std::fmax(hi[0], nx);
-            lo[2] = std::fmin(lo[2], nz); hi[2] = std::fmax(hi[2], nz);
-          }
-        for (int a = 0; a < 3; ++a) { b[a] = lo[a]; b[3 + a] = hi[a]; }
-      }
-      seen();
-    }
-    const double pad = mag * 0x1.0p-22;
-    for (int a = 0; a < 3; ++a) { b[a] -= pad; b[3 + a] += pad; }
-    for (int a = 0; a < 6; ++a)
-      if (!std::isfinite(b[a])) return fail("instance tree: a member without a finite bounding box");
+    rt::XformOp64 ops[RT_MAX_XFORM_OPS];
+    for (int k = 0; k < nops; ++k) { ops[k].op = S.ops[k].op; ops[k].pad = 0; for (int a = 0; a < 3; ++a) ops[k].v[a] = S.ops[k].v[a]; }
+    rt::member_box_through_ops(local, ops, nops, b);
+    if (!rt::box_is_finite(b)) return fail("instance tree: a member without a finite bounding box");
     return true;
   }
   // H_INSTANCE_BVH in the world list: its members become consecutive slots -- entry for entry what the same objects written
@@ -477,14 +459,15 @@ struct Flattener {
     std::vector<int32_t> members;
     if (!collect_members(h, &members)) return false;
     const int32_t first_slot = (int32_t)out.top_level.size();
-    std::vector<double> boxes(6 * members.size());
+    std::vector<double> boxes(6 * members.size()), local(6 * members.size());
     for (size_t m = 0; m < members.size(); ++m) {
       const int32_t e = emit_solid_entry(members[m]);
       if (e < 0) return false;
       out.top_level.push_back(e);
-      if (!member_world_box(e, &boxes[6 * m])) return false;
+      if (!member_world_box(e, &local[6 * m], &boxes[6 * m])) return false;
     }
     if (members.size() < 2) return true;  // no member: no slot; one member: just that slot
+    out.member_local_box.insert(out.member_local_box.end(), local.begin(), local.end());
     // one slot per leaf whatever BuildOptions::max_leaf says (that is for primitives: a member is a whole object), SAH on the host
     BuildOptions bo = opt;
     bo.max_leaf = 1;
