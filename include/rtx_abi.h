@@ -597,7 +597,9 @@ rtx_status rtx_flat_set_transforms(rtx_flat* f, const RtxSlotOps* updates, int64
  * small copy, k_set_slot_ops, and k_refit_instance_tree once per tree that holds an updated member -- is asynchronous on
  * hip_stream.  Ordering against renders and casts on OTHER streams is the caller's business; two updates of one scene may not
  * run concurrently (issue them on one stream, or synchronise).  A progressive handle made before an update holds samples of
- * the old pose: make a new one.  rtx_multi_* scenes are not covered: set the flat scene and create the handle again. */
+ * the old pose, and the features it has already computed (rtx_progressive_features / _denoise keep those
+ * of the last feature_spp asked for, and compute them again only when another count is asked for) are those of the old pose
+ * too: make a new one.  rtx_multi_* scenes are not covered: set the flat scene and create the handle again. */
 rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int64_t n, void* hip_stream);
 /* Test hook: copies one resident array of the scene back to the host, after everything enqueued on the device.  which:
  * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table.  bytes must be the array's size (elements

@@ -3,7 +3,8 @@
 // checkers (O1 literal, O2 flat), compiled by g++ with -fsanitize=address,undefined into one program (`make -C oracle sanitize`;
 // GPU AddressSanitizer is not available on this pool).  It builds catalogue scenes and nested worlds, flattens them
 // with every builder, renders small frames with O1 and O2 and insists that they agree bit for bit; any sanitizer report aborts
-// the run with a non-zero status (tests/test_sanitizers.py).
+// the run with a non-zero status (tests/test_sanitizers.py).  The host checker of the denoiser's feature pass
+// (tests/features_host_check.cpp, both builds) runs here too, on scenes with media, textures, a BVH and moving spheres.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -18,6 +19,12 @@ extern "C" int oracle_audit_flat_exact(const void* flat, const void* nodes, int6
 extern "C" int oracle_audit_motion(const void* flat, int32_t n_times, int64_t* checked);
 extern "C" int oracle_lds_walk_render(const void* flat, const OracleCamera* cam, const OracleConfig* cfg, int32_t use_motion,
                                       int32_t row_stride, double* accum_rgb, uint64_t counts[3]);
+
+// tests/features_host_check.cpp: the f64 build and the float judge
+extern "C" int features_host(const void* flat, const double* camera24, const double* background3, int32_t width, int32_t height,
+                             int32_t feature_spp, int32_t max_depth, uint64_t seed, float* albedo_rgb, float* normal_xyz, int32_t* hits);
+extern "C" int features_host_f32(const void* flat, const double* camera24, const double* background3, int32_t width, int32_t height,
+                                 int32_t feature_spp, int32_t max_depth, uint64_t seed, float* albedo_rgb, float* normal_xyz, int32_t* hits);
 
 namespace rtx {
 // the GPU builder lives in csrc/hip/lbvh.hip: not part of a CPU-only program
@@ -88,12 +95,48 @@ static int check_scene(int32_t sid, int width, double aspect, int spp, bool refe
   return 0;
 }
 
+// The feature checker on a catalogue scene, three samples per pixel: both builds run, every pixel's hit count is within
+// [0, 3], the two builds agree on nearly all of them, and a pixel no sample hit has no normal.
+static int check_features(int32_t sid) {
+  rtx::SceneGraph g(1);
+  rtx::SceneOptions opt;
+  opt.mesh_triangles = 2000;
+  opt.book2_boxes_per_side = 4;
+  opt.book2_spheres = 50;
+  rtx::WorldCam wc;
+  std::string err;
+  if (!rtx::get_world_cam(g, sid, opt, &wc, &err)) { fprintf(stderr, "features, scene %d: %s\n", sid, err.c_str()); return 1; }
+  rtx::BuildOptions bo;
+  rtx::FlatScene fs;
+  if (!rtx::flatten_scene(g, wc.world, bo, &fs, &err)) { fprintf(stderr, "features, scene %d: flatten: %s\n", sid, err.c_str()); return 1; }
+  const int w = 33, h = 17, spp = 3;
+  std::vector<float> a64(3 * w * h), n64(3 * w * h), a32(3 * w * h), n32(3 * w * h);
+  std::vector<int32_t> h64(w * h), h32(w * h);
+  if (features_host(&fs, (const double*)&wc.cam, wc.background, w, h, spp, 12, 7, a64.data(), n64.data(), h64.data()) != 0 ||
+      features_host_f32(&fs, (const double*)&wc.cam, wc.background, w, h, spp, 12, 7, a32.data(), n32.data(), h32.data()) != 0) {
+    fprintf(stderr, "features, scene %d: the checker failed\n", sid);
+    return 1;
+  }
+  int same = 0, hit = 0;
+  for (int p = 0; p < w * h; ++p) {
+    if (h64[p] < 0 || h64[p] > spp || h32[p] < 0 || h32[p] > spp) { fprintf(stderr, "features, scene %d: hit count out of range\n", sid); return 1; }
+    if (h64[p] == 0 && (n64[3 * p] != 0.f || n64[3 * p + 1] != 0.f || n64[3 * p + 2] != 0.f)) { fprintf(stderr, "features, scene %d: a normal without a hit\n", sid); return 1; }
+    same += h64[p] == h32[p];
+    hit += h64[p];
+  }
+  if (10 * same < 8 * w * h) { fprintf(stderr, "features, scene %d: the float judge disagrees on %d of %d pixels\n", sid, w * h - same, w * h); return 1; }
+  printf("scene %3d: features of %d x %d x %d samples, %d hits, f32 and f64 counts agree on %d pixels\n", sid, w, h, spp, hit, same);
+  return 0;
+}
+
 int main() {
   int bad = 0;
+  for (int32_t sid : {2, 5, 6, 7, 11}) bad += check_features(sid);  // image texture; box media; Book-2; moving spheres + lens; mesh
   const int32_t scenes[] = {0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 100, 101};
   for (int32_t sid : scenes) bad += check_scene(sid, 40, sid == 4 || sid == 5 || sid == 6 || sid == 12 ? 1.0 : 1.6, 2, false);
   for (int32_t sid : {6, 13, 100}) bad += check_scene(sid, 32, 1.0, 2, true);
   if (bad) { fprintf(stderr, "%d scene(s) failed\n", bad); return 1; }
+  printf("feature checker clean\n");
   printf("sanitizer run clean\n");
   return 0;
 }

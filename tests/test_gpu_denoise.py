@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import denoise_ref as dr
+from features_cases import analytic_features
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,13 +35,33 @@ def _random_inputs(h, w, seed):
     return mean, var, albedo, normal
 
 
+def _seam_inputs(h, w):
+    """_random_inputs; an image wider than one block (64 x 4 pixels) also gets a column of zero normals at x = 63 and a column
+    of albedo below the demodulation floor at x = 64: the filter's special cases on either side of the first block seam."""
+    mean, var, albedo, normal = _random_inputs(h, w, h * 100 + w)
+    if w > 64:
+        normal[:, 63] = 0.0
+        albedo[:, 64] = 5e-4
+    return mean, var, albedo, normal
+
+
+# More than one block across or down (a block is 64 x 4 pixels: nbx = 1, 2, 3, 5, one block column of 33 bands, and exactly 2 blocks), each at the
+# default rule and at 8 levels, whose last two steps (64 and 128) reach across whole blocks.  The tolerance is the one the
+# narrow shapes were measured with, 2e-4 |ref| + 1e-6: on an MI355X the wide shapes stay inside it (at 9 x 130 the largest
+# |out - ref| after levels 1 .. 7 is 4.6e-7 .. 8.7e-7, every one below the bound's constant term alone), so it is not widened.
+# (5, 128) is exactly two blocks wide: its last column is the last lane of the last block, the one pixel a block stride of 63
+# in place of 64 would leave unwritten (at the other widths overlapping blocks still cover every pixel, with equal values).
+BLOCK_SHAPES = [(4, 64), (5, 65), (9, 130), (3, 257), (130, 9), (5, 128)]
+
+
 @pytest.mark.parametrize("h,w,params", [(1, 1, {}), (5, 7, {}), (5, 7, dict(iterations=8)), (23, 37, {}),
                                         (23, 37, dict(iterations=8, demodulate=-1)),
                                         (16, 20, dict(iterations=3, sigma_luminance=1.5, sigma_normal=16.0, sigma_albedo=0.4)),
                                         (16, 20, dict(sigma_albedo=1e-20)),  # 1 / sigma_a^2 beyond float: no NaN
-                                        (16, 20, dict(sigma_normal=1e30, sigma_luminance=1e30))])
+                                        (16, 20, dict(sigma_normal=1e30, sigma_luminance=1e30))] +
+                         [(h, w, p) for h, w in BLOCK_SHAPES for p in ({}, dict(iterations=8))])
 def test_device_denoise_matches_the_numpy_rule(rtsr, h, w, params):
-    mean, var, albedo, normal = _random_inputs(h, w, h * 100 + w)
+    mean, var, albedo, normal = _seam_inputs(h, w)
     out, rgb8 = rtsr.device_denoise(mean, var, albedo, normal, **params)
     ref = dr.denoise(mean, var, albedo, normal, **params)
     err = np.abs(out - ref) - (2e-4 * np.abs(ref) + 1e-6)
@@ -48,6 +69,29 @@ def test_device_denoise_matches_the_numpy_rule(rtsr, h, w, params):
     assert np.array_equal(rgb8, dr.tone_map(out))
     out2, rgb82 = rtsr.device_denoise(mean, var, albedo, normal, **params)  # the same bits on every call
     assert np.array_equal(out.view(np.uint64), out2.view(np.uint64)) and np.array_equal(rgb8, rgb82)
+
+
+@pytest.fixture(scope="module")
+def levels_9x130():
+    """The inputs at 9 x 130 (three blocks across, three bands) and the reference's remodulated colour after every level."""
+    mean, var, albedo, normal = _seam_inputs(9, 130)
+    levels = []
+    dr.denoise(mean, var, albedo, normal, levels_out=levels, iterations=7)
+    a = dr.prepare(mean, var, albedo, normal)[3]
+    return (mean, var, albedo, normal), [c * a for c, _ in levels]
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 4, 5, 6, 7])
+def test_device_denoise_matches_the_numpy_rule_level_by_level(rtsr, levels_9x130, k):
+    """The filter stopped after k levels against the reference's colour after level k, remodulated as the last level does.  A
+    wrong step or a wrong ping-pong buffer shows at the level where it happens."""
+    (mean, var, albedo, normal), refs = levels_9x130
+    ref = refs[k]
+    out, rgb8 = rtsr.device_denoise(mean, var, albedo, normal, iterations=k)
+    err = np.abs(out - ref) - (2e-4 * np.abs(ref) + 1e-6)
+    print("level %d: largest |out - ref| %.3e, largest excess over the bound %.3e" % (k, float(np.abs(out - ref).max()), float(err.max())))
+    assert err.max() <= 0, (k, float(np.abs(out - ref).max()), float((np.abs(out - ref) / np.maximum(np.abs(ref), 1e-6)).max()))
+    assert np.array_equal(rgb8, dr.tone_map(out))
 
 
 def _sphere_scene(rtsr, f32=False):
@@ -60,37 +104,12 @@ def _sphere_scene(rtsr, f32=False):
     return b, b.flatten(world), cam, cfg, np.float32(colour), center, radius
 
 
-def _analytic_features(rtsr, cam, cfg, center, radius, feature_spp):
-    """Per pixel: how many of the feature samples hit the sphere, and the average of the hit normals (numpy, f64)."""
-    w, h = cfg.image_width, rtsr.image_height(cfg)
-    o = np.array(cam.origin[:])
-    llc, hor, ver = np.array(cam.lower_left_corner[:]), np.array(cam.horizontal[:]), np.array(cam.vertical[:])
-    hits = np.zeros((h, w), dtype=np.int32)
-    nsum = np.zeros((h, w, 3))
-    for j in range(h):
-        for i in range(w):
-            for s in range(feature_spp):
-                ru, rv = rtsr.device_stream(cfg.seed, j * w + i, s, 2)
-                d = llc + ((i + ru) / (w - 1)) * hor + ((j + rv) / (h - 1)) * ver - o
-                oc = o - center
-                a, half_b, c = d @ d, oc @ d, oc @ oc - radius * radius
-                disc = half_b * half_b - a * c
-                if disc < 0:
-                    continue
-                t = (-half_b - np.sqrt(disc)) / a
-                if t < 1e-3:
-                    continue
-                hits[j, i] += 1
-                nsum[j, i] += (o + t * d - center) / radius
-    return hits, nsum / feature_spp
-
-
 def test_features_of_a_lambertian_sphere(rtsr):
     b, flat, cam, cfg, colour, center, radius = _sphere_scene(rtsr)
     scene = flat.upload()
     prog = scene.progressive(cam, cfg)
     albedo, normal = prog.features(4)
-    hits, nref = _analytic_features(rtsr, cam, cfg, center, radius, 4)
+    hits, nref = analytic_features(rtsr, cam, cfg, center, radius, 4)
     full, none = hits == 4, hits == 0
     assert full.sum() > 50 and none.sum() > 50
     assert np.array_equal(albedo[full], np.broadcast_to(colour, albedo[full].shape))
@@ -131,7 +150,7 @@ def _material_scene(rtsr):
 def test_features_of_each_material(rtsr):
     b, flat, cam, cfg, centers, radius, expect = _material_scene(rtsr)
     albedo, normal = flat.upload().progressive(cam, cfg).features(4)
-    per = [_analytic_features(rtsr, cam, cfg, c, radius, 4) for c in centers]
+    per = [analytic_features(rtsr, cam, cfg, c, radius, 4) for c in centers]
     for k, (hits, nref) in enumerate(per):
         full = hits == 4
         assert full.sum() >= 10, k

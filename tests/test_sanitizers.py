@@ -15,6 +15,8 @@ def test_host_code_and_oracles_are_clean_under_asan_and_ubsan():
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     assert "sanitizer run clean" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
     assert out.stdout.count("O1 == O2") == 18  # 15 catalogue scenes + 3 with the reference's BVH rule
+    # tests/features_host_check.cpp, both builds, on five catalogue scenes
+    assert "feature checker clean" in out.stdout and out.stdout.count("features of") == 5
 
 
 def test_instance_trees_are_clean_under_asan_and_ubsan(tmp_path):
