@@ -602,8 +602,10 @@ rtx_status rtx_flat_set_transforms(rtx_flat* f, const RtxSlotOps* updates, int64
  * too: make a new one.  rtx_multi_* scenes are not covered: set the flat scene and create the handle again. */
 rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int64_t n, void* hip_stream);
 /* Test hook: copies one resident array of the scene back to the host, after everything enqueued on the device.  which:
- * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table.  bytes must be the array's size (elements
- * as the scene's precision lays them out); RTX_EINVAL naming the size otherwise. */
+ * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table, 7 the 4-wide culling tree (128 bytes per
+ * node, indexed like nodes; 0 bytes when the scene walks its binary tree), 8 the stack levels its walks are launched with (one
+ * int32, 0 without a wide tree).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
+ * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
  * instance tree, the box before the ops). */
@@ -636,6 +638,42 @@ rtx_status rtx_write_ppm(const char* path, int32_t width, int32_t height, const 
  * in the low and high word of y).  rtx_device_stream: the first n uniforms of the (seed, pixel, sample) stream. */
 rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t n, double* out);
 rtx_status rtx_device_stream(uint64_t seed, uint64_t pixel, uint32_t sample, int32_t n, double* out);
+/* The f32 box tests that let every trace kernel skip subtrees (core/cull32.hpp, trace_vote.inc), asked directly.  f32: 0 the
+ * f64 compilation's code, 1 the fast mode's.  Item k: box[6k..] = lo xyz, hi xyz in f64, narrowed by the host with the product's
+ * outward rounding (lo down, hi up); ray[8k..] = origin xyz, direction xyz, t_min, t_max in f64 (f32 = 1: converted with a
+ * (float) cast, so give it float-representable numbers).  The device builds the culling ray as a bounce does (make_ray32:
+ * v_rcp_f32, and the slope cap under f32 = 1; t_max through cull_round_up) and returns
+ *   ray32[8k..]  ix iy iz, oix oiy oiz, err2, t_min
+ *   key[k]       the clamped entry distance a wide step sorts the child by
+ *   verdict[k]   bit 0 cull32_may_hit, 1 cull32_may_hit_nf, 2 cull32_may_hit_nf_pos (bit 6 says it was asked: t_min > 0),
+ *                3 and 4 the two outputs of cull32_may_hit2 for this box as both children, 5 the wide step's slab_interval_nf;
+ *                a set bit = "may hit".  The near / far planes are picked as the kernels pick them (ray32_dir_neg,
+ *                wide_sign_pack).
+ * n <= 65536.  Blocking. */
+rtx_status rtx_device_cull_verdicts(int32_t f32, int64_t n, const double* box, const double* ray, float* ray32, float* key,
+                                    uint32_t* verdict);
+/* One node step of a walk per item, as a lane of a 256-thread block takes it with its stack in LDS.  kind: 0 walk_node_step32
+ * on FlatNode32 records (64 bytes), 1 walk_node_step4 on 4-wide records (128 bytes); bottom: 0 LdsStack, 1 LdsStackB (slot 0
+ * holds "walk done" and a walk starts at n = 1).  nodes: n_nodes records in host memory.  Each lane's stack has `levels` slots
+ * and four guard slots above them: a step stores into slot n + 3 at the most and n_stack + bottom <= levels is required, so no
+ * item can make a store leave the block's allocation; 1 <= levels <= 60.
+ * An item: the node to step at; the culling ray as DATA (no reciprocal enters); the f64 direction, which decides the binary
+ * step's child order and, by its sign bits, the wide step's plane picks; t_max32; n_stack entries already on the stack -- the
+ * top min(4, n_stack) of them are stack[0..], lowest first, and entry k below those holds 0x40000000 | k.  second_node >= 0:
+ * after the step the lane resets its stack, as a new walk does, and takes one more step at that node.
+ * out: 2 + levels + 4 words per item -- the new current item, the new n, then every slot; a slot no step wrote holds 0x0badf00d,
+ * a guard slot 0x5ca1ab1e.  n <= 65536.  Blocking. */
+typedef struct RtxWalkStepItem {
+  int32_t node;
+  int32_t second_node;
+  float q[8];      /* ix iy iz, oix oiy oiz, err2, t_min */
+  double dir[3];
+  float t_max32;
+  int32_t n_stack;
+  int32_t stack[4];
+} RtxWalkStepItem;
+rtx_status rtx_device_walk_steps(int32_t f32, int32_t kind, int32_t bottom, const void* nodes, int64_t n_nodes, int32_t levels,
+                                 int64_t n, const RtxWalkStepItem* items, int32_t* out);
 /* The adaptive retirement check of rtx_progressive_add_adaptive (k_retire_flag / _scan / _scatter) on host arrays, through
  * the handle's own launch sequence.  S, Q: npix*3; active: n strictly ascending local pixels < npix; counts: npix, in/out
  * (spp at every pixel of the list with r <= target at n = spp, the rest unchanged); next: n, out (the others in order, the

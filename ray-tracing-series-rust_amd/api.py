@@ -149,7 +149,7 @@ RTX_XFORM_TRANSLATE, RTX_XFORM_ROTATE_Y = 0, 1
 _XFORM_NAMES = ("translate", "rotate_y")
 # rtx_flat_array / rtx_device_scene_array: `which` and the element size in an f64 and in an f32 scene
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
-                "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8)}
+                "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
@@ -227,6 +227,8 @@ ABI = {
     "rtx_write_ppm": (C.c_int32, [C.c_char_p, C.c_int32, C.c_int32, C.POINTER(C.c_uint8)]),
     "rtx_device_math": (C.c_int32, [C.c_int32, _D3, _D3, C.c_int64, _D3]),
     "rtx_device_stream": (C.c_int32, [C.c_uint64, C.c_uint64, C.c_uint32, C.c_int32, _D3]),
+    "rtx_device_cull_verdicts": (C.c_int32, [C.c_int32, C.c_int64, _D3, _D3, _F3, _F3, C.POINTER(C.c_uint32)]),
+    "rtx_device_walk_steps": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, _VP, C.c_int64, C.c_int32, C.c_int64, _VP, C.POINTER(C.c_int32)]),
     "rtx_device_retire": (C.c_int32, [_D3, _D3, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.c_double,
                                       C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "rtx_device_noise_reduce": (C.c_int32, [_D3, _D3, C.POINTER(C.c_int32), C.c_uint32, C.c_uint32, C.c_double, _D3, _D3,
@@ -656,8 +658,14 @@ class Scene:
 
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
-        "nodes", "nodes32", "motion32" or "world_desc"."""
+        "nodes", "nodes32", "motion32", "world_desc" or "nodes4" (the 4-wide tree; empty when the scene has none)."""
         return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)
+
+    def wide_levels(self):
+        """Stack levels the scene's 4-wide walks are launched with; 0 when it walks its binary tree (rtx_device_scene_array 8)."""
+        v = C.c_int32(0)
+        _check(lib.rtx_device_scene_array(self._p, 8, C.byref(v), 4))
+        return v.value
 
     def trim(self):
         """Release the render workspace (sample buffer, accumulators); the geometry stays resident."""
@@ -1029,6 +1037,41 @@ def device_math(fn, x, y=None):
     out = np.empty_like(x)
     _check(lib.rtx_device_math(names[fn], x.ctypes.data_as(_D3), y.ctypes.data_as(_D3), x.size, out.ctypes.data_as(_D3)))
     return out
+
+
+# rtx_device_walk_steps: RtxWalkStepItem as a numpy record (88 bytes)
+WALK_STEP_ITEM = np.dtype([("node", "<i4"), ("second_node", "<i4"), ("q", "<f4", (8,)), ("dir", "<f8", (3,)), ("t_max32", "<f4"),
+                           ("n_stack", "<i4"), ("stack", "<i4", (4,))])
+WALK_GUARD_SLOTS, WALK_CANARY, WALK_UNWRITTEN = 4, 0x5CA1AB1E, 0x0BADF00D
+CULL_VERDICT_BITS = ("may_hit", "nf", "nf_pos", "hit2_a", "hit2_b", "wide")  # bit 6: nf_pos was asked (t_min > 0)
+
+
+def device_cull_verdicts(box, ray, f32=False):
+    """The f32 box tests on the GPU (rtx_device_cull_verdicts): box (n, 6) lo / hi in f64, ray (n, 8) origin, direction, t_min,
+    t_max in f64 -> (ray32 (n, 8) float32, key (n,) float32, verdict (n,) uint32)."""
+    box = np.ascontiguousarray(box, dtype=np.float64).reshape(-1, 6)
+    ray = np.ascontiguousarray(ray, dtype=np.float64).reshape(-1, 8)
+    n = box.shape[0]
+    if ray.shape[0] != n:
+        raise ValueError("%d boxes, %d rays" % (n, ray.shape[0]))
+    q, key, v = np.zeros((n, 8), dtype=np.float32), np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.uint32)
+    _check(lib.rtx_device_cull_verdicts(1 if f32 else 0, n, box.ctypes.data_as(_D3), ray.ctypes.data_as(_D3), q.ctypes.data_as(_F3),
+                                        key.ctypes.data_as(_F3), v.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return q, key, v
+
+
+def device_walk_steps(kind, bottom, nodes, levels, items, f32=False):
+    """One walk step per item on the GPU (rtx_device_walk_steps).  kind "step32" / "step4"; nodes: the records as a numpy array
+    of 64- / 128-byte elements; items: WALK_STEP_ITEM records -> (cur (n,), n (n,), slots (n, levels + WALK_GUARD_SLOTS))."""
+    k = {"step32": 0, "step4": 1}[kind]
+    nodes = np.ascontiguousarray(nodes)
+    if nodes.dtype.itemsize != (128 if k else 64):
+        raise ValueError("%s takes %d-byte records" % (kind, 128 if k else 64))
+    items = np.ascontiguousarray(items, dtype=WALK_STEP_ITEM)
+    out = np.zeros((len(items), 2 + levels + WALK_GUARD_SLOTS), dtype=np.int32)
+    _check(lib.rtx_device_walk_steps(1 if f32 else 0, k, 1 if bottom else 0, nodes.ctypes.data_as(_VP), len(nodes), levels, len(items),
+                                     items.ctypes.data_as(_VP), out.ctypes.data_as(C.POINTER(C.c_int32))))
+    return out[:, 0], out[:, 1], out[:, 2:]
 
 
 def device_stream(seed, pixel, sample, n):

@@ -47,6 +47,18 @@ struct Ray32 {
   float t_min;          // rounded down
 };
 
+// Which plane of an axis is the near one, for the forms below that take the planes already picked (cull32_may_hit_nf,
+// cull32_may_hit_nf_pos; the wide step's slab_interval_nf gets the same answer from the direction's sign bit, trace_vote.inc:
+// wide_sign_pack): bit a set = the hi plane of axis a is the near one.  The sign is
+// taken from the SLOPE the planes are multiplied by, not from the f64 direction: for every direction but -0.0 the two agree
+// (a reciprocal keeps the sign, also where the narrowing underflows to -0.0f; an infinite component has a slope of +-0,
+// whose planes all lie at +-0 or NaN whichever is picked), and for -0.0 -- slope -inf, or
+// -2^60 under RT_F32 -- `d < 0` is false and picked lo as the near plane, whose distance then came out as +inf: a miss for a
+// ray that runs inside the slab.  With the slope's sign near / far are min / max of the two plane distances for every input.
+RT_HD uint32_t ray32_dir_neg(const Ray32& q) {
+  return (q.ix < 0.0f ? 1u : 0u) | (q.iy < 0.0f ? 2u : 0u) | (q.iz < 0.0f ? 4u : 0u);
+}
+
 RT_HD float cull_round_up(real x) {  // an f32 >= x (inf stays inf)
   return (float)x * (x >= 0.0 ? 1.00000012f : 0.99999988f);
 }
@@ -67,27 +79,34 @@ RT_HD Ray32 make_ray32(const Ray& r, real t_min) {
   // Single-precision rays do have direction components of exactly 0 (a cancellation leaves nothing below one ulp), a few in
   // every 10^8 rays.  With 1/d = inf the planes of that axis come out as +-inf or NaN, the widening below becomes inf and no
   // box can be ruled out any more: such a ray walked the WHOLE tree, alone in its wave (the dragon room: 4 rays, 0.4 s).
-  // The fast mode gives the axis a finite slope of 2^-60 instead: a ray outside the slab sees both planes at the same huge
+  // The fast mode gives such an axis a finite slope of 2^60 instead: a ray outside the slab sees both planes at the same huge
   // distance and is culled, a ray inside sees (-huge, +huge).  The axis is left out of the error term like an infinite one
-  // (its distances only matter through their sign).
+  // (its distances only matter through their sign; 2^60 is a power of two, so its products are exact).
+  // Only a slope that is NOT finite is replaced (d = +-0, a denormal d, NaN -> -2^60): a finite slope, however steep, is the
+  // ray's own and stays -- capping it too (as a clamp into +-2^60 did) shortened every plane distance of a component below
+  // 2^-60 and culled boxes such a ray enters.  A steep finite slope counts in the error term like any other, which switches
+  // culling off for that ray (|o| 2^60 2^-20 and more): rarer than the zeros, and correct.
+  // What the replacement gives up: an origin EXACTLY on a plane of a zero-component axis sees that plane at t = 0
+  // (fma(p, 2^60, -p 2^60) = 0) instead of "inside for all t", so a ray that runs in a face of the box (closed box: a touch) is
+  // culled when the plane is the far one and t_min > 0.  A touch of measure zero; the float CPU oracle shares this code and
+  // the verdict (tests/test_cull_conservative.py counts the class and excepts nothing else).
+  // (Two compares and two selects per axis and bounce.  Not free: the fast mode's C2 is 1.3 % slower for it, Book-2 0.6 %; a clamp
+  // taken only where the slope is not finite measured worse on C2, -1.9 %.  DESIGN.md 5.6.)
   const float slope_cap = 0x1.0p60f;
-#if defined(__HIP_DEVICE_COMPILE__)
-  q.ix = __builtin_amdgcn_fmed3f(q.ix, -slope_cap, slope_cap);
-  q.iy = __builtin_amdgcn_fmed3f(q.iy, -slope_cap, slope_cap);
-  q.iz = __builtin_amdgcn_fmed3f(q.iz, -slope_cap, slope_cap);
-#else
-  q.ix = __builtin_fminf(__builtin_fmaxf(q.ix, -slope_cap), slope_cap);
-  q.iy = __builtin_fminf(__builtin_fmaxf(q.iy, -slope_cap), slope_cap);
-  q.iz = __builtin_fminf(__builtin_fmaxf(q.iz, -slope_cap), slope_cap);
-#endif
-  const float finite_slope = 0x1.0p60f;
+  q.ix = __builtin_fabsf(q.ix) < __builtin_huge_valf() ? q.ix : (q.ix > 0.0f ? slope_cap : -slope_cap);
+  q.iy = __builtin_fabsf(q.iy) < __builtin_huge_valf() ? q.iy : (q.iy > 0.0f ? slope_cap : -slope_cap);
+  q.iz = __builtin_fabsf(q.iz) < __builtin_huge_valf() ? q.iz : (q.iz > 0.0f ? slope_cap : -slope_cap);
+  q.oix = ox * q.ix; q.oiy = oy * q.iy; q.oiz = oz * q.iz;
+  float ax = __builtin_fabsf(q.ix) != slope_cap ? __builtin_fabsf(q.oix) : 0.0f;
+  float ay = __builtin_fabsf(q.iy) != slope_cap ? __builtin_fabsf(q.oiy) : 0.0f;
+  float az = __builtin_fabsf(q.iz) != slope_cap ? __builtin_fabsf(q.oiz) : 0.0f;
 #else
   const float finite_slope = 1e30f;
-#endif
   q.oix = ox * q.ix; q.oiy = oy * q.iy; q.oiz = oz * q.iz;
   float ax = __builtin_fabsf(q.ix) < finite_slope ? __builtin_fabsf(q.oix) : 0.0f;
   float ay = __builtin_fabsf(q.iy) < finite_slope ? __builtin_fabsf(q.oiy) : 0.0f;
   float az = __builtin_fabsf(q.iz) < finite_slope ? __builtin_fabsf(q.oiz) : 0.0f;
+#endif
   q.err2 = __builtin_fmaxf(ax, __builtin_fmaxf(ay, az)) * 0x1.0p-20f;
   // rounded DOWN whatever the sign (a medium's second boundary query may start at a negative t)
   q.t_min = (float)t_min * (t_min >= 0.0 ? 0.99999988f : 1.00000012f);
@@ -106,8 +125,8 @@ RT_HD bool cull32_may_hit(const float* lo, const float* hi, const Ray32& q, floa
   return !(tn - tf > __builtin_fmaf(__builtin_fabsf(tn) + __builtin_fabsf(tf), 0x1.0p-21f, q.err2));
 }
 
-// The same test with the near / far plane of every axis already picked by the sign of the ray's direction (near = lo
-// where the ray travels towards +axis, hi otherwise).  For a finite slope the near value IS min(a, b) and the far value
+// The same test with the near / far plane of every axis already picked by the sign of the ray's slope (ray32_dir_neg: near =
+// lo where the ray travels towards +axis, hi otherwise).  For a finite slope the near value IS min(a, b) and the far value
 // max(a, b) of cull32_may_hit, so tn / tf -- and the verdict -- are the same numbers; for a zero direction component
 // both are NaN and fmaxf / fminf drop them, exactly as there.  What it saves is the six min / max per box that only
 // sorted the two planes: on gfx950 v_min_f32 / v_max_f32 issue in 4 clocks, twice a v_fma_f32.

@@ -77,6 +77,10 @@ RT_HD double f64_from_words(uint32_t hi, uint32_t lo) {
   return bits_f64(((uint64_t)hi << 32) | (uint64_t)lo);
 }
 
+// 1 where the sign bit is set (-0.0 included), else 0
+RT_HD uint32_t real_sign_bit(double x) { return f64_hi(x) >> 31; }
+RT_HD uint32_t real_sign_bit(float x) { union { float f; uint32_t u; } c; c.f = x; return c.u >> 31; }
+
 #define RT_INFINITY ((::rt::real)__builtin_huge_val())
 
 // IEEE-exact primitives used by the core.  sqrt/fabs/floor are correctly

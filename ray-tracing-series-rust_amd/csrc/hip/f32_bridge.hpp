@@ -56,3 +56,7 @@ void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: bot
 // rtx_device_math's float entries (fn >= 32): one arithmetic building block as the f32 compilation evaluates it
 // (post_kernels.inc: k_device_math_f32); device pointers, asynchronous on the null stream.
 hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, long long n, double* d_out);
+// rtx_device_cull_verdicts / rtx_device_walk_steps with f32 = 1 (cull_hooks.inc as the f32 compilation has it); host pointers
+rtx_status rtx_f32_cull_verdicts(int64_t n, const double* box, const double* ray, float* ray32, float* key, uint32_t* verdict);
+rtx_status rtx_f32_walk_steps(int32_t kind, int32_t bottom, const void* nodes, int64_t n_nodes, int32_t levels, int64_t n,
+                              const RtxWalkStepItem* items, int32_t* out);

@@ -42,3 +42,12 @@ hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, lon
   hipLaunchKernelGGL(k_device_math_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, fn, d_x, d_y, n, d_out);
   return hipGetLastError();
 }
+
+rtx_status rtx_f32_cull_verdicts(int64_t n, const double* box, const double* ray, float* ray32, float* key, uint32_t* verdict) {
+  return cull_verdicts_impl(n, box, ray, ray32, key, verdict);
+}
+
+rtx_status rtx_f32_walk_steps(int32_t kind, int32_t bottom, const void* nodes, int64_t n_nodes, int32_t levels, int64_t n,
+                              const RtxWalkStepItem* items, int32_t* out) {
+  return walk_steps_impl(kind, bottom, nodes, n_nodes, levels, n, items, out);
+}

@@ -29,6 +29,7 @@
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
 #include "../host/update_shadow.hpp"
+#include "../host/wide_tree.hpp"
 #include "device_buffer.hpp"
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
@@ -45,8 +46,7 @@ namespace rtx {
 #include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, lane_rank, queue_claim
 
 // ------------------------------------------------------------------ device scene
-struct FlatNode4;
-typedef const FlatNode4 FlatNode4Dev;
+typedef const FlatNode4 FlatNode4Dev;  // host/wide_tree.hpp
 struct WorldDesc;
 
 // The plain primitive entries beside the BVH in the world list (the dragon room's seven rectangles), as a kernel argument:
@@ -293,6 +293,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
 #include "scene_update.inc"  // k_set_slot_ops, k_refit_instance_tree: new Translate / RotateY parameters on a resident scene
+#include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
 // ------------------------------------------------------------------ launcher
 static int shard_row_count(int32_t height, const RtxShard& sh, int32_t row_limit) {
@@ -595,12 +596,11 @@ static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
   // and one stack (trace_world.inc), and a wide collapse of a slot tree has no leaf format for slots
   if (fs.features & rt::F_INSTANCE) want_wide = false;
   if (!want_wide) return RTX_OK;
-  std::vector<FlatNode4> wide(fs.nodes.size());
-  memset(wide.data(), 0, wide.size() * sizeof(FlatNode4));
-  int peak = 0;
+  std::vector<FlatNode4> wide;
+  std::vector<int32_t> roots;
   for (const rt::FlatEntry& e : fs.entries)
-    if (e.kind == rt::ENTRY_BVH) peak = std::max(peak, build_wide_nodes(fs.nodes, e.a, &wide));
-  p.levels = peak + 1;  // (the spare level is the bottom slot of LdsStackB; walk_node_step4 needs none of its own)
+    if (e.kind == rt::ENTRY_BVH) roots.push_back(e.a);
+  p.levels = build_wide_tree(fs.nodes, roots, &wide);  // (peak + 1: the spare level is the bottom slot of LdsStackB)
   const size_t lds = stack_bytes((uint32_t)p.levels);
   bool ok = lds <= 64 * 1024;
   if (ok && for_vote) {
@@ -1728,6 +1728,18 @@ rtx_status rtx_device_math(int32_t fn, const double* x, const double* y, int64_t
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, dout, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
   return RTX_OK;
+}
+
+rtx_status rtx_device_cull_verdicts(int32_t f32, int64_t n, const double* box, const double* ray, float* ray32, float* key, uint32_t* verdict) {
+  if (f32 != 0 && f32 != 1) { set_error("rtx_device_cull_verdicts: f32 must be 0 or 1"); return RTX_EINVAL; }
+  return f32 ? rtx_f32_cull_verdicts(n, box, ray, ray32, key, verdict) : cull_verdicts_impl(n, box, ray, ray32, key, verdict);
+}
+
+rtx_status rtx_device_walk_steps(int32_t f32, int32_t kind, int32_t bottom, const void* nodes, int64_t n_nodes, int32_t levels, int64_t n,
+                                 const RtxWalkStepItem* items, int32_t* out) {
+  if (f32 != 0 && f32 != 1) { set_error("rtx_device_walk_steps: f32 must be 0 or 1"); return RTX_EINVAL; }
+  return f32 ? rtx_f32_walk_steps(kind, bottom, nodes, n_nodes, levels, n, items, out)
+             : walk_steps_impl(kind, bottom, nodes, n_nodes, levels, n, items, out);
 }
 
 rtx_status rtx_device_stream(uint64_t seed, uint64_t pixel, uint32_t sample, int32_t n, double* out) {

@@ -225,6 +225,11 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 2: p = ds->view.nodes32; have = u.n_nodes * sizeof(rt::FlatNode32); break;
     case 3: p = ds->view.motion32; have = u.n_motion * sizeof(rt::FlatMotion32); break;
     case 4: p = ds->world.desc; have = u.n_desc * sizeof(WorldDesc); break;
+    case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
+    case 8:  // the stack levels of a wide walk: host memory, one int32
+      if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
+      *(int32_t*)out = ds->wide.nodes4 ? (int32_t)ds->wide.levels : 0;
+      return RTX_OK;
     default: set_error("rtx_device_scene_array: which names no resident array"); return RTX_EINVAL;
   }
   if (bytes != have) { set_error("rtx_device_scene_array: the array holds " + std::to_string(have) + " bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
         active = false;
       } else {
         q = rt::make_ray32(ps.ray, rt::ray_t_min(ps.ray));
-        dir_neg = rt::ray_dir_neg(ps.ray);
+        dir_neg = rt::ray32_dir_neg(q);  // the planes are picked by it: the slope's sign (core/cull32.hpp)
         off_x = (dir_neg & 1u) << 2; off_y = 12u + ((dir_neg & 2u) << 1); off_z = 24u + (dir_neg & 4u);
         flip_b = ((dir_neg & 1u) * CB) | (((dir_neg >> 1) & 1u) * (CB << 8)) | (((dir_neg >> 2) & 1u) * (CB << 16));
         t_max32 = __builtin_huge_valf();

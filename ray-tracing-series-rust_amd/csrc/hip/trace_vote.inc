@@ -81,91 +81,7 @@ __device__ __forceinline__ void walk_leaf_step(const rt::SceneView& sv, uint32_t
 }
 
 // ------------------------------------------------------------------ 4-wide culling tree (big meshes)
-// On the dragon room the walk is bound by the latency of dependent node fetches (28 MB of culling tree: every step
-// waits for L2 / MALL), not by VALU.  A 4-wide tree halves the length of that chain: built at upload by collapsing the
-// binary SAH tree (the child with the largest area is opened until four slots are used), one 128-byte record = one
-// cache line per step, boxes rounded outward to f32 exactly like FlatNode32.  Wide node i is binary node i opened
-// up, so child codes (node index >= 0, leaf code < 0) are the binary tree's and leaves are untouched.  Culling
-// structure only: every hit is still decided by the f64 primitive tests, so results do not change.
-struct FlatNode4 {  // 128 B, field-major so that one child's six planes are six scalar picks from float4 loads
-  float lo[3][4];
-  float hi[3][4];
-  int32_t child[4];  // WALK_DONE marks an empty slot (its box is empty too)
-  int32_t pad[4];
-};
-static_assert(sizeof(FlatNode4) == 128, "one cache line per wide node");
-
-// Host: collapse fs.nodes below `root` into `out` (indexed like fs.nodes); returns the peak stack use of a walk.
-static int build_wide_nodes(const std::vector<rt::FlatNode>& nodes, int32_t root, std::vector<FlatNode4>* out) {
-  struct Slot { int32_t code; double mn[3], mx[3]; };
-  auto half_area = [](const Slot& s) {
-    double dx = s.mx[0] - s.mn[0], dy = s.mx[1] - s.mn[1], dz = s.mx[2] - s.mn[2];
-    return dx * dy + dy * dz + dz * dx;
-  };
-  auto slots_of = [&](int32_t n, Slot* dst) {
-    for (int c = 0; c < 2; ++c) {
-      dst[c].code = nodes[n].child[c];
-      for (int a = 0; a < 3; ++a) { dst[c].mn[a] = nodes[n].bmin[c][a]; dst[c].mx[a] = nodes[n].bmax[c][a]; }
-    }
-  };
-  struct Frame { int32_t node; int next; int nslots; int32_t kids[4]; int peak_kids; };
-  std::vector<Frame> stack;
-  std::vector<int> peak(nodes.size(), 0);
-  auto open = [&](int32_t n) {
-    Slot sl[4];
-    int ns = 2;
-    slots_of(n, sl);
-    while (ns < 4) {
-      int best = -1;
-      double best_area = -1.0;
-      for (int k = 0; k < ns; ++k)
-        if (sl[k].code >= 0 && half_area(sl[k]) > best_area) { best_area = half_area(sl[k]); best = k; }
-      if (best < 0) break;
-      Slot two[2];
-      slots_of(sl[best].code, two);
-      sl[best] = two[0];
-      sl[ns++] = two[1];
-    }
-    FlatNode4& w = (*out)[n];
-    Frame f;
-    f.node = n; f.next = 0; f.nslots = ns; f.peak_kids = 0;
-    for (int k = 0; k < 4; ++k) {
-      f.kids[k] = -1;
-      if (k < ns) {
-        for (int a = 0; a < 3; ++a) {
-          float lo = (float)sl[k].mn[a];
-          if ((double)lo > sl[k].mn[a]) lo = std::nextafterf(lo, -INFINITY);
-          float hi = (float)sl[k].mx[a];
-          if ((double)hi < sl[k].mx[a]) hi = std::nextafterf(hi, INFINITY);
-          w.lo[a][k] = lo; w.hi[a][k] = hi;
-        }
-        w.child[k] = sl[k].code;
-        if (sl[k].code >= 0) f.kids[k] = sl[k].code;
-      } else {
-        for (int a = 0; a < 3; ++a) { w.lo[a][k] = INFINITY; w.hi[a][k] = -INFINITY; }
-        w.child[k] = 0x7fffffff;
-      }
-      w.pad[k] = 0;
-    }
-    stack.push_back(f);
-  };
-  open(root);
-  while (!stack.empty()) {
-    Frame& f = stack.back();
-    if (f.next < 4) {
-      int32_t kid = f.kids[f.next++];
-      if (kid >= 0) open(kid);
-      continue;
-    }
-    // all wide children done: a walk pushes up to nslots items here, pops one and descends with nslots - 1 left
-    int pk = f.nslots;
-    for (int k = 0; k < 4; ++k)
-      if (f.kids[k] >= 0) pk = std::max(pk, f.nslots - 1 + peak[f.kids[k]]);
-    peak[f.node] = pk;
-    stack.pop_back();
-  }
-  return peak[root];
-}
+// FlatNode4, the host collapse that builds it (build_wide_nodes) and the stack sizing live in host/wide_tree.hpp.
 
 // One wide step: test the four child boxes, push the hit ones so that the nearest ends on top, pop it.
 // The near / far plane of every axis is picked by the sign of the ray's direction THROUGH THE ADDRESS: `sign_pack` holds, per
@@ -173,8 +89,11 @@ static int build_wide_nodes(const std::vector<rt::FlatNode>& nodes, int32_t root
 // planes sit at 48 - x, 80 - y, 112 - z).  For a finite slope near = min and far = max of the two plane distances, so tn / tf
 // are the numbers the min / max form computes (and NaNs of a zero slope are dropped by fmaxf / fminf either way): same
 // verdicts, same order, same walk -- without the six v_min / v_max per box that only sorted the planes (4 clocks each on gfx950).
+// The sign is the direction's SIGN BIT, which is the sign bit of the slope the planes are multiplied by (narrowing to f32 and a
+// reciprocal both keep it; rt::ray32_dir_neg says why `d < 0` is not enough: -0.0).  Taken from the direction rather than from
+// the Ray32 because that is what cost nothing: a compare on the slope made k_trace_world 0.7 % slower on Book-2 (DESIGN.md 5.6).
 __device__ __forceinline__ uint32_t wide_sign_pack(const rt::Ray& r) {
-  const uint32_t nx = r.direction.x < 0.0 ? 48u : 0u, ny = r.direction.y < 0.0 ? 64u : 16u, nz = r.direction.z < 0.0 ? 80u : 32u;
+  const uint32_t nx = rt::real_sign_bit(r.direction.x) * 48u, ny = 16u + rt::real_sign_bit(r.direction.y) * 48u, nz = 32u + rt::real_sign_bit(r.direction.z) * 48u;
   return nx | (ny << 8) | (nz << 16);
 }
 // The key a wide step sorts a child by: the slab entry distance clamped into [t_min, 3e38].  The clamp is what keeps the

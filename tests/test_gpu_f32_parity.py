@@ -360,14 +360,17 @@ def test_f32_rng_forms_equal_numpy_restatements(rtsr):
         assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (lo, hi)
 
 
-SLOPE_CAP_IN = np.float32([0.0, -0.0, np.nan, np.inf, -np.inf, 1e-30, -1e-30, 1e-45, -1e-45, 2.0 ** -60, 2.0 ** -61, 0.5, -4.0])
-SLOPE_CAP_OUT = [2.0 ** 60, -2.0 ** 60, -2.0 ** 60, 0.0, -0.0, 2.0 ** 60, -2.0 ** 60, 2.0 ** 60, -2.0 ** 60, 2.0 ** 60, 2.0 ** 60, 2.0, -0.25]
+# (finite slopes are powers of two here: the device's v_rcp_f32 is exact on them, so host and device can be held to one table)
+SLOPE_CAP_IN = np.float32([0.0, -0.0, np.nan, np.inf, -np.inf, 2.0 ** -100, -2.0 ** -100, 1e-45, -1e-45, 2.0 ** -60, 2.0 ** -61, 0.5, -4.0])
+SLOPE_CAP_OUT = [2.0 ** 60, -2.0 ** 60, -2.0 ** 60, 0.0, -0.0, 2.0 ** 100, -2.0 ** 100, 2.0 ** 60, -2.0 ** 60, 2.0 ** 60, 2.0 ** 61, 2.0, -0.25]
 
 
 def test_f32_slope_cap_is_the_same_on_host_and_device(rtsr, orc):
-    """core/cull32.hpp caps 1 / d at +-2^60 with v_med3_f32 on the device and fminf(fmaxf()) on the host.  The two must agree
-    where they are not plain arithmetic: d = +-0 (1 / d = +-inf -> +-cap), NaN (v_med3_f32 returns the minimum of its
-    operands, fmaxf drops the NaN: both -cap), +-inf (a zero slope keeps its sign), denormal d, and the cap itself."""
+    """core/cull32.hpp replaces a slope 1 / d that is not finite by +-2^60 and keeps every finite one, however steep (a clamp
+    into +-2^60 culled boxes a ray with a component below 2^-60 enters: tests/test_cull_conservative.py).  Host and device must
+    agree where that is not plain arithmetic: d = +-0 (+-inf -> +-2^60), NaN (-2^60), +-inf (a zero slope keeps its sign), a
+    denormal d (its reciprocal overflows on the host and is flushed on the device: +-2^60 both), 2^-60, and 2^-61 and 2^-100,
+    which stay 2^61 and 2^100."""
     want = np.float32(SLOPE_CAP_OUT)
     host = orc.core32_math("slope_capf", SLOPE_CAP_IN).astype(np.float32)
     dev = rtsr.device_math("slope_capf", SLOPE_CAP_IN).astype(np.float32)

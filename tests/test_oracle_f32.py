@@ -214,9 +214,9 @@ def test_host_rng_forms_equal_numpy_restatements(orc):
 
 
 def test_host_slope_cap_handles_nan_and_infinities_like_v_med3(orc):
-    """core/cull32.hpp's host branch of the slope cap, fminf(fmaxf(1 / d, -2^60), 2^60), on the inputs where it could part
-    from the device's v_med3_f32 (which returns the smallest operand when one is a NaN); tests/test_gpu_f32_parity.py
-    holds the device to the same table."""
+    """core/cull32.hpp's replacement of a slope that is not finite by +-2^60 (finite slopes stay, however steep), on the host, on
+    the inputs where it could part from the device: +-0, NaN, +-inf, denormals, 2^-60, 2^-61, 2^-100;
+    tests/test_gpu_f32_parity.py holds the device to the same table."""
     from test_gpu_f32_parity import SLOPE_CAP_IN, SLOPE_CAP_OUT
     got = orc.core32_math("slope_capf", SLOPE_CAP_IN).astype(np.float32)
     assert got.view(np.uint32).tolist() == np.float32(SLOPE_CAP_OUT).view(np.uint32).tolist()
