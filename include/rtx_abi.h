@@ -561,8 +561,10 @@ rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays
  * and the boxes of the instance tree it is a member of -- and only those are touched: no primitive, texture or BVH is re-sent.
  *   * The chain's SHAPE is fixed: a slot's number of ops and the kind of each stay what the flattener emitted (ask
  *     rtx_flat_slot_chain); only the parameters change.  An update names ALL ops of its slot.
- *   * The instance tree's TOPOLOGY is fixed: its boxes are refitted bottom-up, nothing is rebuilt.  A refitted tree culls
- *     less well than a rebuilt one once members have moved far, and RtxFlatInfo::sah_cost is NOT recomputed: it goes stale.
+ *   * The instance tree's TOPOLOGY is kept: its boxes are refitted bottom-up.  A refitted tree culls less well than a rebuilt
+ *     one once members have moved far: rtx_*_instance_tree_cost reports how well a tree culls as it stands, and
+ *     rtx_*_rebuild_instance_trees (below) gives it a new topology for the current pose.  RtxFlatInfo::sah_cost covers the
+ *     members' own BVHs only and does not depend on a pose.
  *   * A slot can be moved when its entry is a Translate / RotateY chain (rtx_flat_top_level_kind 3) or a ConstantMedium whose
  *     boundary is such a chain (kind 4), inside or outside an instance tree.
  * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, a slot out of
@@ -604,12 +606,60 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
 /* Test hook: copies one resident array of the scene back to the host, after everything enqueued on the device.  which:
  * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table, 7 the 4-wide culling tree (128 bytes per
  * node, indexed like nodes; 0 bytes when the scene walks its binary tree), 8 the stack levels its walks are launched with (one
- * int32, 0 without a wide tree).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
+ * int32, 0 without a wide tree), 9 the scene's max_stack as its binary walks are now launched with (one int32; a rebuild of
+ * an instance tree changes it).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
  * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
  * instance tree, the box before the ops). */
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
+
+/* ---- instance trees: the quality of a tree as it stands, and a rebuild for the current pose ---------------------------------
+ * Cost of instance tree k (0 <= k < RtxInstanceInfo::n_trees): the sum, over the tree's nodes in ascending node index, of the
+ * surface areas 2 (dx dy + dy dz + dz dx) of the node's two child boxes, divided by the area of the union of the root's two
+ * child boxes -- the expected number of child boxes a random ray through the tree's box meets, up to a constant.  Areas are f64
+ * from the planes as the scene stores them (an f32 scene's planes are widened first).  The resident version computes the
+ * per-node terms in a kernel and adds them on the host in the same order, so it equals the flat version bit for bit on equal
+ * planes; it BLOCKS: it waits for everything enqueued on the device, like rtx_device_scene_array.  RTX_EINVAL for a NULL
+ * argument or k out of range. */
+rtx_status rtx_flat_instance_tree_cost(const rtx_flat* f, int32_t k, double* cost);
+rtx_status rtx_scene_instance_tree_cost(const rtx_scene* s, int32_t k, double* cost);
+/* Rebuilding instance tree k replaces its TOPOLOGY with one built from the members' world boxes at their current ops.  The
+ * members stay the same n_slots consecutive slots and the tree keeps its piece of n_slots - 1 nodes: no array grows or moves.
+ * Every leaf holds one slot, every child box is the exact union of the member boxes under it, nodes32 is the narrowing of nodes,
+ * the time-aware copy (where present) the static one a refit writes, and every entry point answers bit for bit as on a fresh
+ * upload of that pose (a frame does not depend on a tree's topology).  rtx_*_set_transforms keeps working on a rebuilt tree.
+ * The scene's max_stack is the members' part + 1 + the deepest instance tree as the trees now stand: it can rise or fall.
+ *   RTX_REBUILD_MORTON  what the device does, restated on the host: 63-bit Morton codes of the box centroids, a stable sort,
+ *                       Karras' radix tree.  A flat scene rebuilt this way equals the resident arrays of a scene rebuilt on
+ *                       the device, byte for byte, in both precisions.
+ *   RTX_REBUILD_SAH     the flattener's own builder on the current boxes: the flat scene then equals a fresh rtx_flatten of
+ *                       that pose byte for byte in every array, and so does rtx_flat_info (build times aside).
+ * trees: n tree indices, or NULL for every tree (n is then ignored unless negative).  RTX_EINVAL, the message naming the
+ * field, nothing enqueued and the scene unchanged: a NULL scene, n < 0, a tree index out of range or named twice, an unknown
+ * builder, a non-zero reserved word of *out, a scene on another device.  RTX_OK with nothing launched: a scene without instance
+ * trees when trees is NULL, and n = 0 with a list.  RTX_EUNSUPPORTED, the scene unchanged: the Morton trees would need a walk
+ * stack of more than 64 levels (64 KB of LDS), which no launcher accepts. */
+#define RTX_REBUILD_MORTON 0
+#define RTX_REBUILD_SAH 1
+typedef struct RtxRebuildStats {
+  int32_t trees_rebuilt;     /* trees this call rebuilt */
+  int32_t max_depth;         /* the deepest of them, in nodes */
+  int32_t max_stack_before;  /* the scene's max_stack before and after the call */
+  int32_t max_stack_after;
+  int32_t reserved[4];       /* must be 0 on entry */
+} RtxRebuildStats;
+/* Host only.  Edits the flat scene in place. */
+rtx_status rtx_flat_rebuild_instance_trees(rtx_flat* f, const int32_t* trees, int32_t n, int32_t builder);
+/* A resident scene of either precision, with the Morton builder on the device (k_member_boxes, k_member_morton, a radix sort,
+ * k_rebuild_radix, k_rebuild_emit per tree, into scratch memory of the scene; then device-to-device copies into the tree's
+ * piece).  The kernels run on hip_stream.  Unlike rtx_scene_set_transforms this call BLOCKS: it waits on hip_stream once, for
+ * the read-back of the new depths (4 bytes per tree, and the new parent tables with them), because the stack budget of every
+ * later launch depends on them and a tree that is too deep must be refused before it is committed.  out may be NULL.
+ * Concurrency as for rtx_scene_set_transforms: one update or rebuild of a scene at a time, ordering against work on other
+ * streams is the caller's, progressive handles made earlier hold the old pose's samples.  rtx_multi_* scenes are not covered:
+ * rebuild the flat scene and create the handle again. */
+rtx_status rtx_scene_rebuild_instance_trees(rtx_scene* s, const int32_t* trees, int32_t n, void* hip_stream, RtxRebuildStats* out);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

@@ -145,6 +145,13 @@ class RtxInstanceTree(C.Structure):
     _fields_ = [("first_slot", C.c_int32), ("n_slots", C.c_int32), ("n_nodes", C.c_int32), ("depth", C.c_int32)]
 
 
+class RtxRebuildStats(C.Structure):
+    _fields_ = [("trees_rebuilt", C.c_int32), ("max_depth", C.c_int32), ("max_stack_before", C.c_int32), ("max_stack_after", C.c_int32),
+                ("reserved", C.c_int32 * 4)]
+
+
+RTX_REBUILD_MORTON, RTX_REBUILD_SAH = 0, 1
+_REBUILD_NAMES = ("morton", "sah")
 RTX_XFORM_TRANSLATE, RTX_XFORM_ROTATE_Y = 0, 1
 _XFORM_NAMES = ("translate", "rotate_y")
 # rtx_flat_array / rtx_device_scene_array: `which` and the element size in an f64 and in an f32 scene
@@ -263,6 +270,10 @@ ABI = {
     "rtx_flat_instance_tree": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxInstanceTree)]),
     "rtx_flat_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64]),
     "rtx_scene_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64, _VP]),
+    "rtx_flat_instance_tree_cost": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_double)]),
+    "rtx_scene_instance_tree_cost": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_double)]),
+    "rtx_flat_rebuild_instance_trees": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    "rtx_scene_rebuild_instance_trees": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int32, _VP, C.POINTER(RtxRebuildStats)]),
     "rtx_device_scene_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_flat_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_builder_graph": (_VP, [_VP]),
@@ -544,6 +555,23 @@ class Flat:
         arr = _slot_ops(self, updates)
         _check(lib.rtx_flat_set_transforms(self._p, arr, len(arr)))
 
+    def rebuild_instance_trees(self, trees=None, builder="morton"):
+        """A new topology for instance trees from their members' boxes at the current pose, in place
+        (rtx_flat_rebuild_instance_trees).  trees: tree indices, None for every tree.  builder: "morton" -- what
+        Scene.rebuild_instance_trees does on the device, restated on the host -- or "sah", the flattener's own builder: the
+        flat scene then equals a fresh flatten of the pose."""
+        if builder not in _REBUILD_NAMES:
+            raise ValueError('builder must be "morton" or "sah", not %r' % (builder,))
+        arr, n = _tree_list(trees)
+        _check(lib.rtx_flat_rebuild_instance_trees(self._p, arr, n, _REBUILD_NAMES.index(builder)))
+
+    def instance_tree_cost(self, k):
+        """How well instance tree k culls as it stands (rtx_flat_instance_tree_cost): the summed surface area of every node's
+        two child boxes over the area of the tree's box.  Smaller is better; compare a refitted tree with a rebuilt one."""
+        cost = C.c_double(0.0)
+        _check(lib.rtx_flat_instance_tree_cost(self._p, int(k), C.byref(cost)))
+        return cost.value
+
     def array(self, name):
         """A copy of one host array as bytes (rtx_flat_array; a test hook): a name of SCENE_ARRAYS but "world_desc"."""
         return _scene_array(lambda out, n: lib.rtx_flat_array(self._p, SCENE_ARRAYS[name][0], out, n), self, name, False)
@@ -551,6 +579,14 @@ class Flat:
     def upload(self, f32=False):
         """f32=True: the statistical fast mode (rtx_scene_upload_f32): float arithmetic, no bit-exactness claim."""
         return Scene(self, f32=f32)
+
+
+def _tree_list(trees):
+    """trees of rebuild_instance_trees -> (ctypes int32 array or None, n)."""
+    if trees is None:
+        return None, 0
+    trees = [int(k) for k in trees]
+    return (C.c_int32 * max(len(trees), 1))(*trees), len(trees)
 
 
 def _slot_ops(flat, updates):
@@ -655,6 +691,30 @@ class Scene:
         arr = _slot_ops(self._flat, updates)
         raw = getattr(stream, "cuda_stream", stream)
         _check(lib.rtx_scene_set_transforms(self._p, arr, len(arr), _VP(raw or None)))
+
+    def rebuild_instance_trees(self, trees=None, stream=None):
+        """A new topology for instance trees of the RESIDENT scene from their members' boxes at the current pose
+        (rtx_scene_rebuild_instance_trees; Morton codes, a radix sort and Karras' tree on the device).  trees: tree indices,
+        None for every tree.  The kernels run on `stream` (as in set_transforms) and the call waits on it once, for the new
+        depths.  -> {"trees_rebuilt", "max_depth", "max_stack_before", "max_stack_after"}."""
+        arr, n = _tree_list(trees)
+        raw = getattr(stream, "cuda_stream", stream)
+        stats = RtxRebuildStats()
+        _check(lib.rtx_scene_rebuild_instance_trees(self._p, arr, n, _VP(raw or None), C.byref(stats)))
+        return {k: getattr(stats, k) for k in ("trees_rebuilt", "max_depth", "max_stack_before", "max_stack_after")}
+
+    def instance_tree_cost(self, k):
+        """Flat.instance_tree_cost of the resident tree k as it stands (rtx_scene_instance_tree_cost; blocking)."""
+        cost = C.c_double(0.0)
+        _check(lib.rtx_scene_instance_tree_cost(self._p, int(k), C.byref(cost)))
+        return cost.value
+
+    def max_stack(self):
+        """The max_stack the scene's binary walks are now launched with (rtx_device_scene_array 9): Flat.info()["max_stack"]
+        at upload, changed by rebuild_instance_trees."""
+        v = C.c_int32(0)
+        _check(lib.rtx_device_scene_array(self._p, 9, C.byref(v), 4))
+        return v.value
 
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",

@@ -11,6 +11,7 @@
 #include "../host/scenes.hpp"
 #include "../host/light_table.hpp"
 #include "../host/set_transforms.hpp"
+#include "../host/rebuild_instances.hpp"
 #include "abi_internal.hpp"
 
 namespace rtx {
@@ -255,6 +256,7 @@ rtx_status rtx_flatten(const rtx_builder* b, rtx_handle world, const RtxBuildOpt
     set_error(err);
     return RTX_EUNSUPPORTED;
   }
+  f->options = opt;
   *out = f;
   return RTX_OK;
 }
@@ -333,6 +335,26 @@ rtx_status rtx_flat_instance_tree(const rtx_flat* f, int32_t k, RtxInstanceTree*
 rtx_status rtx_flat_set_transforms(rtx_flat* f, const RtxSlotOps* updates, int64_t n) {
   std::string err;
   if (!flat_set_transforms("rtx_flat_set_transforms", f ? &f->scene : nullptr, updates, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_rebuild_instance_trees(rtx_flat* f, const int32_t* trees, int32_t n, int32_t builder) {
+  std::string err;
+  const rtx_status st = flat_rebuild_instance_trees("rtx_flat_rebuild_instance_trees", f ? &f->scene : nullptr, f ? f->options : BuildOptions(),
+                                                    trees, n, builder, &err);
+  if (st != RTX_OK) set_error(err);
+  return st;
+}
+
+rtx_status rtx_flat_instance_tree_cost(const rtx_flat* f, int32_t k, double* cost) {
+  if (!f || !cost) { set_error("rtx_flat_instance_tree_cost: NULL argument"); return RTX_EINVAL; }
+  const UpdateShadow sh = build_update_shadow(f->scene);
+  if (!sh.broken.empty()) { set_error("rtx_flat_instance_tree_cost: " + sh.broken); return RTX_EINVAL; }
+  if (k < 0 || (size_t)k >= sh.trees.size()) {
+    set_error("rtx_flat_instance_tree_cost: k is out of range (the scene has " + std::to_string(sh.trees.size()) + " instance trees)");
+    return RTX_EINVAL;
+  }
+  *cost = flat_instance_tree_cost(f->scene, sh.trees[(size_t)k]);
   return RTX_OK;
 }
 

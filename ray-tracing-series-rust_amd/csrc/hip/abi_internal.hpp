@@ -12,6 +12,7 @@ struct rtx_builder {
 };
 struct rtx_flat {
   rtx::FlatScene scene;
+  rtx::BuildOptions options;  // what rtx_flatten built it with: RTX_REBUILD_SAH builds with the same
 };
 struct RtxSceneOps;  // f32_bridge.hpp
 struct rtx_scene {

@@ -48,8 +48,16 @@ struct RtxSceneOps {
   rtx_status (*set_transforms)(void* device_scene, const RtxSlotOps* resolved, int64_t n, hipStream_t stream);
   // rtx_device_scene_array: one resident array copied to the host (blocking)
   rtx_status (*read_array)(void* device_scene, int32_t which, void* out, size_t bytes);
+  // rtx_scene_rebuild_instance_trees (scene_rebuild.inc): the list already checked for NULL / n < 0 / reserved words; blocks once
+  rtx_status (*rebuild_instance_trees)(void* device_scene, const int32_t* trees, int32_t n, hipStream_t stream, RtxRebuildStats* out);
+  // rtx_scene_instance_tree_cost (blocking)
+  rtx_status (*instance_tree_cost)(void* device_scene, int32_t k, double* cost);
 };
 
+// A stable radix sort of (64-bit key, 32-bit value) pairs on `stream` (lbvh.hip, which already carries rocPRIM's sort: neither
+// compilation of render.hip instantiates it).  temp == NULL: *temp_bytes = the temporary storage n pairs need.
+hipError_t rtx_sort_pairs_u64_u32(void* temp, size_t* temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                                  const uint32_t* vals_in, uint32_t* vals_out, int n, hipStream_t stream);
 rtx_status rtx_f32_upload(const RtxF32Blobs* blobs, void** device_scene);
 const RtxSceneOps* rtx_f32_scene_ops();  // the f32 compilation's table, for the scenes rtx_f32_upload makes
 void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: both report through rtx_last_error

@@ -24,6 +24,7 @@
 #include "../core/flat_types.hpp"
 #include "../host/flat_scene.hpp"
 #include "device_buffer.hpp"
+#include "f32_bridge.hpp"
 
 namespace rtx {
 
@@ -326,3 +327,9 @@ int32_t build_bvh_gpu(const std::vector<double>& boxes, int max_leaf, std::vecto
 }
 
 }  // namespace rtx
+
+// f32_bridge.hpp: the sort of scene_rebuild.inc, for both compilations of render.hip.
+hipError_t rtx_sort_pairs_u64_u32(void* temp, size_t* temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                                  const uint32_t* vals_in, uint32_t* vals_out, int n, hipStream_t stream) {
+  return hipcub::DeviceRadixSort::SortPairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, 63, stream);
+}

@@ -26,6 +26,7 @@
 #include "../../../include/rtx_abi.h"
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
+#include "../core/karras.hpp"
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
 #include "../host/update_shadow.hpp"
@@ -168,6 +169,19 @@ struct SceneUpdate {
   void* h_staging = nullptr;                    // pinned; `staged` marks the end of the copy out of it
   size_t h_staging_bytes = 0;
   hipEvent_t staged = nullptr;
+  // rtx_scene_rebuild_instance_trees (scene_rebuild.inc).  max_stack = member_stack + 1 + the deepest of tree_depth.
+  int32_t member_stack = 0;                     // host: the members' own part of max_stack (their deepest BVH)
+  std::vector<int32_t> tree_depth;              // host: per instance tree, as the trees now stand
+  size_t n_perlins = 0, n_materials = 0, n_textures = 0;  // what plan_world_stacks fits into LDS beside the stacks
+  // scratch of a rebuild, laid out like the shadow's per-member / per-node tables; allocated by the first rebuild
+  DeviceBuffer<double> r_boxes, r_bounds, r_box64, r_terms;
+  DeviceBuffer<unsigned long long> r_keys, r_keys_sorted;
+  DeviceBuffer<uint32_t> r_vals, r_vals_sorted;
+  DeviceBuffer<int32_t> r_children, r_parent_node, r_parent_leaf, r_leaf_parent, r_node_parent, r_depth;
+  DeviceBuffer<rt::FlatNode> r_nodes;
+  DeviceBuffer<rt::FlatNode32> r_nodes32;
+  DeviceBuffer<rt::FlatMotion32> r_motion32;
+  DeviceBuffer<unsigned char> r_sort_temp;      // the radix sort's temporary storage, grown on demand
 };
 
 struct DeviceScene {
@@ -293,6 +307,9 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
 #include "scene_update.inc"  // k_set_slot_ops, k_refit_instance_tree: new Translate / RotateY parameters on a resident scene
+static size_t stack_bytes(uint32_t levels);
+static void plan_world_stacks(DeviceScene* ds);
+#include "scene_rebuild.inc" // k_member_boxes .. k_rebuild_emit: a new topology for an instance tree of a resident scene; its cost
 #include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
 // ------------------------------------------------------------------ launcher
@@ -619,27 +636,29 @@ static rtx_status plan_wide(DeviceScene* ds, const FlatScene& fs) {
 
 // ------------------------------------------------------------------ k_trace_world
 // Needs WidePlan: the LDS tables go with the stacks of the tree the kernel walks.
-static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
+// What of k_trace_world's plan depends on the stack levels: the LDS tables that fit beside the stacks and the resident blocks.
+// From ds->view.max_stack, so that a rebuild of an instance tree (scene_rebuild.inc), which changes it, plans again.
+static void plan_world_stacks(DeviceScene* ds) {
   WorldPlan& p = ds->world;
   const TraceSwitches& sw = ds->sw;
-  rtx_status st = upload_array(ds, build_world_desc(fs), &p.desc);
-  if (st != RTX_OK) return st;
+  const SceneUpdate& u = ds->upd;
+  p.perlin_lds = p.mat_lds = p.tex_lds = 0;
   for (int wd = 0; wd < 2; ++wd) {
-    const uint32_t levels = (uint32_t)(wd ? ds->wide.levels : fs.max_stack + 1);
+    const uint32_t levels = (uint32_t)(wd ? ds->wide.levels : ds->view.max_stack + 1);
     size_t wl = stack_bytes(levels) + (size_t)WORLD_SLOT_F64 * TRACE_BLOCK * sizeof(rt::real);
     if (wl > 64 * 1024) continue;
     // Perlin tables in LDS when that costs no resident block (3 per CU at 168 VGPRs: up to 53 KB each)
     if ((wd != 0) == (ds->wide.nodes4 != nullptr)) {
-      const size_t n_p = fs.perlins.size();
+      const size_t n_p = u.n_perlins;
       if (n_p >= 1 && n_p <= 2 && sw.perlin_lds && wl + n_p * sizeof(rt::FlatPerlin) <= 52 * 1024) {
         p.perlin_lds = (uint32_t)n_p;
         wl += n_p * sizeof(rt::FlatPerlin);
       }
-      const size_t mt = fs.materials.size() * sizeof(rt::FlatMaterial) + fs.textures.size() * sizeof(rt::FlatTexture);
-      if (!fs.materials.empty() && !fs.textures.empty() && fs.materials.size() <= 64 && fs.textures.size() <= 64 && sw.mat_lds &&
+      const size_t mt = u.n_materials * sizeof(rt::FlatMaterial) + u.n_textures * sizeof(rt::FlatTexture);
+      if (u.n_materials != 0 && u.n_textures != 0 && u.n_materials <= 64 && u.n_textures <= 64 && sw.mat_lds &&
           wl + mt <= 52 * 1024) {
-        p.mat_lds = (uint32_t)fs.materials.size();
-        p.tex_lds = (uint32_t)fs.textures.size();
+        p.mat_lds = (uint32_t)u.n_materials;
+        p.tex_lds = (uint32_t)u.n_textures;
         wl += mt;
       }
     }
@@ -649,6 +668,12 @@ static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
 #undef WORLD_OCC
     if (wd == 0 && (n = occupancy(k_trace_world<P_INST, false, WORLD_WPS>, wl)) > 0) p.blocks_per_cu[4][0] = n;
   }
+}
+static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
+  const rtx_status st = upload_array(ds, build_world_desc(fs), &ds->world.desc);
+  if (st != RTX_OK) return st;
+  ds->upd.n_perlins = fs.perlins.size(); ds->upd.n_materials = fs.materials.size(); ds->upd.n_textures = fs.textures.size();
+  plan_world_stacks(ds);
   return RTX_OK;
 }
 
@@ -1507,6 +1532,10 @@ static const RtxSceneOps scene_ops = {
       return scene_set_transforms_impl((DeviceScene*)ds, resolved, n, stream);
     },
     [](void* ds, int32_t which, void* out, size_t bytes) { return scene_read_array_impl((DeviceScene*)ds, which, out, bytes); },
+    [](void* ds, const int32_t* trees, int32_t n, hipStream_t stream, RtxRebuildStats* out) {
+      return scene_rebuild_impl((DeviceScene*)ds, trees, n, stream, out);
+    },
+    [](void* ds, int32_t k, double* cost) { return scene_tree_cost_impl((DeviceScene*)ds, k, cost); },
 };
 
 }  // namespace rtx
@@ -1632,6 +1661,23 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
   const rtx_status st = check_set_transforms("rtx_scene_set_transforms", s, updates, n, &resolved);
   if (st != RTX_OK || n == 0) return st;
   return s->ops->set_transforms(s->device_scene, resolved.data(), n, (hipStream_t)hip_stream);
+}
+
+// ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands
+// (scene_rebuild.inc).  What needs no device is checked here; the scene's own compilation checks the rest.
+rtx_status rtx_scene_rebuild_instance_trees(rtx_scene* s, const int32_t* trees, int32_t n, void* hip_stream, RtxRebuildStats* out) {
+  const char* who = "rtx_scene_rebuild_instance_trees";
+  if (!s) { set_error(std::string(who) + ": the scene is NULL"); return RTX_EINVAL; }
+  if (n < 0) { set_error(std::string(who) + ": n < 0"); return RTX_EINVAL; }
+  if (out)
+    for (int i = 0; i < 4; ++i)
+      if (out->reserved[i] != 0) { set_error(std::string(who) + ": out->reserved[" + std::to_string(i) + "] is not 0"); return RTX_EINVAL; }
+  return s->ops->rebuild_instance_trees(s->device_scene, trees, n, (hipStream_t)hip_stream, out);
+}
+
+rtx_status rtx_scene_instance_tree_cost(const rtx_scene* s, int32_t k, double* cost) {
+  if (!s || !cost) { set_error("rtx_scene_instance_tree_cost: NULL argument"); return RTX_EINVAL; }
+  return s->ops->instance_tree_cost(s->device_scene, k, cost);
 }
 
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes) {

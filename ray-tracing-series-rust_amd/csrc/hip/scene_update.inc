@@ -138,6 +138,9 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   if (fs.features & rt::F_INSTANCE)
     for (const rt::FlatEntry& e : fs.entries) u.n_desc += e.kind == rt::ENTRY_INSTANCE ? 1 : 0;
   if (!u.shadow.broken.empty() || u.shadow.trees.empty()) return RTX_OK;
+  // the parts of max_stack (flatten.cpp: inst_depth + 1 + the members' deepest BVH), kept apart for a rebuild
+  for (const TreeShadow& t : u.shadow.trees) u.tree_depth.push_back(instance_tree_depth(fs.nodes.data(), t.root));
+  u.member_stack = fs.max_stack - instance_max_stack(0, u.tree_depth);
   HIP_TRY(u.d_local_box.upload(u.local_box.data(), u.local_box.size()));
   HIP_TRY(u.d_leaf_parent.upload(u.shadow.leaf_parent.data(), u.shadow.leaf_parent.size()));
   HIP_TRY(u.d_node_parent.upload(u.shadow.node_parent.data(), u.shadow.node_parent.size()));
@@ -226,6 +229,10 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 3: p = ds->view.motion32; have = u.n_motion * sizeof(rt::FlatMotion32); break;
     case 4: p = ds->world.desc; have = u.n_desc * sizeof(WorldDesc); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
+    case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
+      if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
+      *(int32_t*)out = ds->view.max_stack;
+      return RTX_OK;
     case 8:  // the stack levels of a wide walk: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
       *(int32_t*)out = ds->wide.nodes4 ? (int32_t)ds->wide.levels : 0;

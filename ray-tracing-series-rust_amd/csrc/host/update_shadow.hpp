@@ -4,8 +4,10 @@
 // fly and a device scene keeps it from its upload.  Pure host code, compiled by both compilations of render.hip: nothing here
 // reads a `real`.
 #pragma once
+#include <algorithm>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../../include/rtx_abi.h"
 #include "../core/member_box.hpp"
@@ -122,4 +124,64 @@ inline bool check_slot_ops_scene(const char* who, const UpdateShadow& sh, const 
   return true;
 }
 
+// ---- what a rebuild of an instance tree shares between the host (host/rebuild_instances.hpp) and the device
+// (hip/scene_rebuild.inc): the stack rule, the depth walk, the check of the tree list and the sum of the cost.
+// The launchers accept stack_bytes(max_stack + 1) <= 64 KB of LDS, one KB per level (render.hip: stack_bytes).
+constexpr int32_t kMaxWalkStack = 63;
+
+// The scene's max_stack from its parts (flatten.cpp: inst_depth + 1 + out.max_stack): a member's own BVH is walked above the
+// slot walk on one stack, one marker between them.
+inline int32_t instance_max_stack(int32_t member_stack, const std::vector<int32_t>& tree_depth) {
+  int32_t deepest = 0;
+  for (int32_t d : tree_depth) deepest = std::max(deepest, d);
+  return deepest + 1 + member_stack;
+}
+
+// The height of a tree in nodes, as the builders count it (the stack entries a walk can hold).  NODE: FlatNode of either
+// precision.
+template <class NODE>
+inline int32_t instance_tree_depth(const NODE* nodes, int32_t root) {
+  int32_t depth = 0;
+  std::vector<std::pair<int32_t, int32_t>> todo{{root, 1}};
+  while (!todo.empty()) {
+    const std::pair<int32_t, int32_t> n = todo.back();
+    todo.pop_back();
+    depth = std::max(depth, n.second);
+    for (int c = 0; c < 2; ++c)
+      if (!rt::node_child_is_leaf(nodes[(size_t)n.first].child[c])) todo.push_back({nodes[(size_t)n.first].child[c], n.second + 1});
+  }
+  return depth;
+}
+
+// The list of trees of one rebuild call -> *out (ascending as given; every tree when trees is NULL).  false with *err naming
+// the field: NULL scene, n < 0, an index out of range or named twice.
+inline bool check_rebuild_list(const char* who, const void* scene, size_t n_trees, const int32_t* trees, int32_t n, std::vector<int32_t>* out,
+                               std::string* err) {
+  out->clear();
+  if (!scene) { *err = std::string(who) + ": the scene is NULL"; return false; }
+  if (n < 0) { *err = std::string(who) + ": n < 0"; return false; }
+  if (!trees) {
+    for (size_t k = 0; k < n_trees; ++k) out->push_back((int32_t)k);
+    return true;
+  }
+  std::vector<char> seen(n_trees, 0);
+  for (int32_t i = 0; i < n; ++i) {
+    if (trees[i] < 0 || (size_t)trees[i] >= n_trees) {
+      *err = std::string(who) + ": trees[" + std::to_string(i) + "] is out of range (the scene has " + std::to_string(n_trees) + " instance trees)";
+      return false;
+    }
+    if (seen[(size_t)trees[i]]) { *err = std::string(who) + ": trees names tree " + std::to_string(trees[i]) + " twice"; return false; }
+    seen[(size_t)trees[i]] = 1;
+    out->push_back(trees[i]);
+  }
+  return true;
+}
+
+// rtx_*_instance_tree_cost from f64 planes: the sum, over the tree's nodes in ascending node index, of the areas of the node's
+// two child boxes, over the area of the union of the root's two child boxes.  term[i] is node node_base + i's.
+inline double instance_tree_cost_from_terms(const double* term, int32_t n_nodes, double root_area) {
+  double sum = 0.0;
+  for (int32_t i = 0; i < n_nodes; ++i) sum += term[i];
+  return sum / root_area;
+}
 }  // namespace rtx
