@@ -216,8 +216,14 @@ typedef struct RtxRenderStats {
   int32_t trace_launches, passes;
   uint64_t sample_buffer_bytes;
   int32_t trace_kernel; /* which trace kernel the launcher chose: RTX_KERNEL_* (rtx_trace_kernel_name) */
-  int32_t reserved;
+  int32_t trace_variant; /* RTX_KERNEL_LDS: which instantiation ran, RTX_LDS_VARIANT_* bits; 0 for every other kernel */
 } RtxRenderStats;
+/* RtxRenderStats.trace_variant (all variants produce identical results; a frame cannot tell which ran, this word can) */
+enum {
+  RTX_LDS_VARIANT_TIME_BOXES = 1,   /* time-aware boxes: the shutter lies inside the (ordered) interval of the world's BVH */
+  RTX_LDS_VARIANT_ONE_AXIS = 2,     /* ... whose slopes are zero except along y */
+  RTX_LDS_VARIANT_COMMON_RATIO = 4  /* every MovingSphere has the same non-empty (time0, time1): one time ratio per bounce */
+};
 /* Trace kernels (all produce identical results; the launcher picks by world shape and LDS budget).  Ids 1, 2 and 5 are retired:
    their kernels were removed and the launcher never reports them; the ids and names stay reserved. */
 enum {

@@ -74,7 +74,7 @@ class RtxRenderStats(C.Structure):
                                           "rect_tests", "triangle_tests", "scatters", "texels", "perlin_calls")] + \
                [("trace_ms", C.c_double), ("reduce_ms", C.c_double), ("tonemap_ms", C.c_double),
                 ("trace_launches", C.c_int32), ("passes", C.c_int32), ("sample_buffer_bytes", C.c_uint64),
-                ("trace_kernel", C.c_int32), ("reserved", C.c_int32)]
+                ("trace_kernel", C.c_int32), ("trace_variant", C.c_int32)]
 
 
 class RtxMultiStats(C.Structure):
@@ -159,6 +159,8 @@ SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 
                 "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
+# RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
+RTX_LDS_VARIANT_TIME_BOXES, RTX_LDS_VARIANT_ONE_AXIS, RTX_LDS_VARIANT_COMMON_RATIO = 1, 2, 4
 RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
 
 

@@ -1,0 +1,38 @@
+// Which k_trace_lds a render launches, decided on the host from the scene's time intervals: the MovingSpheres' own
+// (time0, time1), the interval of the BVH above them and the camera's shutter.  plan_lds and launch_lds (render.hip) take
+// every such decision from here and report it in RtxRenderStats.trace_variant.  Included inside namespace rtx; host-compilable
+// on its own (tests/lds_variant_host_check.cpp).
+
+// bits of RtxRenderStats.trace_variant
+enum : int32_t {
+  LDSV_TIME_BOXES = 1,    // the time-aware boxes (MOTION bit 0 of k_trace_lds)
+  LDSV_ONE_AXIS = 2,      // ... with slopes along y only (MOTION bit 1)
+  LDSV_COMMON_RATIO = 4,  // one (time - mv_t0) / (mv_t1 - mv_t0) per bounce for every primitive record
+};
+
+// One ratio per bounce serves every record when all MovingSpheres share one interval -- and that interval is not empty:
+// static spheres ride along as movers with c1 = c0, and with time0 == time1 the shared ratio is x / 0, its product with
+// their c1 - c0 = 0 a NaN, so every STATIC sphere of the scene would take a NaN centre (Sphere::hit never reads the time).
+// Records of such a scene are tested with their own intervals instead (a static sphere's is (0, 1)).
+// MS: any record with time0 and time1.
+template <class MS>
+inline bool lds_common_interval(const MS* ms, size_t n, double* t0, double* t1) {
+  if (n == 0 || (double)ms[0].time0 == (double)ms[0].time1) return false;
+  for (size_t k = 1; k < n; ++k)
+    if (ms[k].time0 != ms[0].time0 || ms[k].time1 != ms[0].time1) return false;
+  *t0 = (double)ms[0].time0;
+  *t1 = (double)ms[0].time1;
+  return true;
+}
+
+// A BVH's interval admits time-aware boxes when it is ordered: the boxes are lerps between its two ends (flatten.cpp).
+inline bool lds_motion_interval_ok(double bvh_t0, double bvh_t1) { return bvh_t0 < bvh_t1; }
+
+// The variant of one render.  time_boxes: the scene has a time-aware instantiation that fits (LdsPlan::motion.ok) over
+// [bvh_t0, bvh_t1]; it is taken when every ray time of the render, [shutter1, shutter2) (camera.rs:69), lies inside that interval --
+// outside it a lerped box is no bound.  motion_axis: LdsPlan::motion_axis.
+inline int32_t lds_trace_variant(bool time_boxes, double bvh_t0, double bvh_t1, double shutter1, double shutter2, int motion_axis,
+                                 bool mv_common) {
+  const bool motion = time_boxes && lds_motion_interval_ok(bvh_t0, bvh_t1) && shutter1 >= bvh_t0 && shutter2 <= bvh_t1;
+  return (motion ? LDSV_TIME_BOXES : 0) | (motion && motion_axis == 1 ? LDSV_ONE_AXIS : 0) | (mv_common ? LDSV_COMMON_RATIO : 0);
+}

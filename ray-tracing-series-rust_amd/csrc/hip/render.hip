@@ -44,6 +44,9 @@ namespace rtx { void set_error(const std::string& msg); }
 namespace rtx {
 
 #include "lds_layout.inc"    // ring_bytes, LdsSceneDims, ldsk_layout: k_trace_lds's LDS layout (host-compilable: tests/lds_layout_host_check.cpp)
+#include "lds_variant.inc"   // lds_common_interval, lds_trace_variant: which k_trace_lds a render launches (host-compilable: tests/lds_variant_host_check.cpp)
+static_assert(LDSV_TIME_BOXES == RTX_LDS_VARIANT_TIME_BOXES && LDSV_ONE_AXIS == RTX_LDS_VARIANT_ONE_AXIS &&
+              LDSV_COMMON_RATIO == RTX_LDS_VARIANT_COMMON_RATIO, "RtxRenderStats.trace_variant");
 #include "pass_items.inc"    // ShardMap, item_pixel, start_path, store_sample, TRACE_CHUNK, lane_rank, queue_claim
 
 // ------------------------------------------------------------------ device scene
@@ -749,12 +752,7 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   // primitive records in LDS: one per leaf slot, in slot order (trace_lds.inc) -- spheres, or moving spheres when the scene has any
   p.plain.levels = levels;
   p.plain.dims = {(uint32_t)fs.nodes32.size(), max_end, max_end, 0u, LDSK_NODE_DWORDS, 0u};
-  if (!fs.moving_spheres.empty()) {
-    bool same = sw.mv_common;
-    for (const rt::FlatMovingSphere& ms : fs.moving_spheres)
-      same = same && ms.time0 == fs.moving_spheres[0].time0 && ms.time1 == fs.moving_spheres[0].time1;
-    if (same) { p.mv_common = true; p.mv_t0 = (double)fs.moving_spheres[0].time0; p.mv_t1 = (double)fs.moving_spheres[0].time1; }
-  }
+  p.mv_common = sw.mv_common && lds_common_interval(fs.moving_spheres.data(), fs.moving_spheres.size(), &p.mv_t0, &p.mv_t1);
   if (fs.features & rt::F_MOVING_SPHERE) {  // k_trace_lds<P_SPHERES>: one kind of primitive in LDS (trace_lds.inc: UNI)
     p.plain.dims.n_uni = (uint32_t)fs.spheres.size();
     p.plain.dims.n_moving = max_end;
@@ -779,7 +777,7 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
     fit_lds(&p.plain, want_ring, (uint32_t)lds_max);
     const rt::FlatEntry& be = fs.entries[fs.top_level[0]];
     // the time-aware instantiation: the world's one BVH holds moving spheres and came with an interval
-    if (p.plain.ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && (double)be.f[0] < (double)be.f[1] && sw.motion) {
+    if (p.plain.ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && lds_motion_interval_ok((double)be.f[0], (double)be.f[1]) && sw.motion) {
       p.motion_t0 = (double)be.f[0]; p.motion_t1 = (double)be.f[1];
       fit_lds(&p.motion, want_ring, (uint32_t)lds_max);
     }
@@ -817,11 +815,13 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   return RTX_OK;
 }
 
-static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera* cam) {
+// *variant: the instantiation launched, as RtxRenderStats.trace_variant reports it (lds_variant.inc).
+static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera* cam, int32_t* variant) {
   const LdsPlan& p = ds->lds;
   HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
-  const bool motion = p.motion.ok && (double)cam->time1 >= p.motion_t0 && (double)cam->time2 <= p.motion_t1;
+  *variant = lds_trace_variant(p.motion.ok, p.motion_t0, p.motion_t1, (double)cam->time1, (double)cam->time2, p.motion_axis, p.mv_common);
+  const bool motion = (*variant & LDSV_TIME_BOXES) != 0;
   const LdsFit& f = motion ? p.motion : p.plain;
   const bool ring = f.ring_cap != 0u;
   const rt::real m_t0 = (rt::real)p.motion_t0, m_inv = (rt::real)(1.0 / (p.motion_t1 - p.motion_t0));
@@ -838,7 +838,7 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
 #define LAUNCH_LDS(FEAT, MOTIONF) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF); } else { LAUNCH_LDS2(FEAT, false, MOTIONF); } } while (0)
   // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
   if ((a.feat & ~P_STATIC_SPHERES) == 0) { LAUNCH_LDS(P_STATIC_SPHERES, 0u); }
-  else if (motion && p.motion_axis == 1) { LAUNCH_LDS(P_SPHERES, 3u); }  // slopes along y only (Book-1 at HEAD)
+  else if (*variant & LDSV_ONE_AXIS) { LAUNCH_LDS(P_SPHERES, 3u); }  // slopes along y only (Book-1 at HEAD)
   else if (motion) { LAUNCH_LDS(P_SPHERES, 1u); }
   else { LAUNCH_LDS(P_SPHERES, 0u); }
 #undef LAUNCH_LDS
@@ -1159,6 +1159,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
 
   float trace_ms = 0.f;
   int passes = 0;
+  int32_t variant = 0;  // of k_trace_lds (launch_lds); every other kernel has one form
   if (nitem > 0) {
     // Passes two deep: even passes on the caller's stream, odd ones on ws.aux_stream, each with its own half of the sample
     // buffer and its own work counter.  Within a stream: trace(k), reduce(k), trace(k + 2), ... -- so a half is not overwritten
@@ -1180,7 +1181,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       if (stats) HIP_TRY(hipEventRecord(ws.ev[0], a.stream));
       switch (kernel) {
         case RTX_KERNEL_SIMPLE: launch_simple<COUNT>(ds, a); break;
-        case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam); break;
+        case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam, &variant); break;
         case RTX_KERNEL_WAVEFRONT: st = wave_pass(ds, a); break;
         case RTX_KERNEL_VOTE: st = launch_vote(ds, a); break;
 #ifndef RTX_F32_TU
@@ -1224,6 +1225,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
     stats->trace_launches = passes;
     stats->passes = passes;
     stats->trace_kernel = passes > 0 ? kernel : RTX_KERNEL_SIMPLE;  // (nothing traced: no kernel ran)
+    stats->trace_variant = variant;
     stats->sample_buffer_bytes = pp.sample_bytes;
     stats->samples = (uint64_t)spp * nitem;  // (pixel, sample) paths this call traced; the work counters below only in count mode
     if (COUNT) {

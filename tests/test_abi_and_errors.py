@@ -134,6 +134,24 @@ def test_trace_kernel_names_retired_ids(rtsr):
         assert "RTX_KERNEL_PERSISTENT" not in src and "RTX_KERNEL_STREAM" not in src and "RTX_KERNEL_WQ" not in src
 
 
+def test_render_stats_layout_and_the_variant_word(rtsr):
+    """RtxRenderStats (rtx_abi.h): 128 bytes, trace_kernel at 120 and trace_variant -- the output word that used to be `reserved`
+    -- at 124; the variant bits are the header's."""
+    import ctypes as C
+    s = rtsr.RtxRenderStats()
+    assert C.sizeof(s) == 128
+    offsets = [(n, getattr(rtsr.RtxRenderStats, n).offset) for n, _ in rtsr.RtxRenderStats._fields_]
+    assert offsets[:10] == [(n, 8 * k) for k, n in enumerate(("samples", "rays", "box_tests", "sphere_tests", "moving_sphere_tests",
+                                                             "rect_tests", "triangle_tests", "scatters", "texels", "perlin_calls"))]
+    assert offsets[10:] == [("trace_ms", 80), ("reduce_ms", 88), ("tonemap_ms", 96), ("trace_launches", 104), ("passes", 108),
+                            ("sample_buffer_bytes", 112), ("trace_kernel", 120), ("trace_variant", 124)]
+    assert (rtsr.RTX_LDS_VARIANT_TIME_BOXES, rtsr.RTX_LDS_VARIANT_ONE_AXIS, rtsr.RTX_LDS_VARIANT_COMMON_RATIO) == (1, 2, 4)
+    header = open(os.path.join(ROOT, "include", "rtx_abi.h")).read()
+    for name, bit in (("TIME_BOXES", 1), ("ONE_AXIS", 2), ("COMMON_RATIO", 4)):
+        assert "RTX_LDS_VARIANT_%s = %d" % (name, bit) in header
+    assert "int32_t trace_variant;" in header.split("} RtxRenderStats;")[0].rsplit("typedef struct RtxRenderStats", 1)[1]
+
+
 def test_product_never_touches_the_oracle():
     """oracle/ is test infrastructure: nothing under the product package may reference it."""
     pkg = os.path.join(ROOT, "ray-tracing-series-rust_amd")
