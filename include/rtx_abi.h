@@ -67,6 +67,9 @@ double rtx_builder_random(rtx_builder* b);
 
 /* Textures -- src/texture.rs */
 rtx_handle rtx_solid_color(rtx_builder* b, const double rgb[3]);                 /* SolidColor::new            texture.rs:16-20  */
+/* rtx_checker: checkers may nest, as in the reference, but a chain of at most 16 of them is followed when a texture is
+ * evaluated (the reference recurses without limit).  Building a deeper texture succeeds; rtx_flatten refuses, with
+ * RTX_EUNSUPPORTED and the depth in the message, a world in which a material reaches one. */
 rtx_handle rtx_checker(rtx_builder* b, rtx_handle even, rtx_handle odd);        /* Checker::new               texture.rs:39-44  */
 rtx_handle rtx_noise(rtx_builder* b, double scale);                             /* Noise::new (+Perlin::new)  texture.rs:72-77  */
 rtx_handle rtx_image_from_ppm(rtx_builder* b, const char* path);                /* Image::from_ppm            texture.rs:95-99  */

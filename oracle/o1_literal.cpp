@@ -1064,5 +1064,16 @@ int oracle_o1_hit(const void* graph_ptr, int32_t handle, const double o[3], cons
   out[7] = rec.u; out[8] = rec.v; out[9] = rec.front_face ? 1.0 : 0.0;
   return 1;
 }
+// Texture::value of one texture of a graph (recursing as texture.rs does, to any depth): out = the colour.  -1: bad handle.
+int oracle_o1_texture_value(const void* graph_ptr, int32_t texture_handle, double u, double v, const double p[3], double out[3]) {
+  const rtx::SceneGraph* g = (const rtx::SceneGraph*)graph_ptr;
+  if (!g || !g->valid_texture(texture_handle)) return -1;
+  World wb;
+  wb.g = g;
+  wb.textures.resize(g->textures.size());
+  const Color c = wb.texture(texture_handle)->value(u, v, Point3(p[0], p[1], p[2]));
+  out[0] = c.x(); out[1] = c.y(); out[2] = c.z();
+  return 1;
+}
 
 }  // extern "C"

@@ -184,6 +184,16 @@ int oracle_core_world_hit_mat(const void* flat, const double o[3], const double 
   *mat = (int32_t)rec.mat;
   return 1;
 }
+// texture_value of one texture record of a flattened scene: out = the colour.  -1: no such record.
+int oracle_core_texture_value(const void* flat, int32_t texture_index, double u, double v, const double p[3], double out[3]) {
+  if (!flat) return -1;
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+  if (texture_index < 0 || (size_t)texture_index >= fs.textures.size()) return -1;
+  const rt::SceneView sv = fs.view();
+  const rt::Color c = rt::texture_value<rt::F_ALL, false>(sv, texture_index, u, v, rt::v3(p[0], p[1], p[2]), nullptr);
+  out[0] = c.x; out[1] = c.y; out[2] = c.z;
+  return 1;
+}
 // Structural audits of a flattened scene (tests/test_host_logic.py, tests/test_gpu_lbvh_edges.py); 0 when consistent, else the
 // code of the first property that fails.
 //   oracle_audit_flat: 2 a leaf's range leaves the BVH's references; 3 a child index leaves the node array (or the tree is
@@ -459,11 +469,13 @@ const void* oracle_flat_array(const void* flat, const char* name, int64_t* n, in
   const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
 #define ARR(VEC) if (!strcmp(name, #VEC)) { *n = (int64_t)fs.VEC.size(); *elem_bytes = (int64_t)sizeof(fs.VEC[0]); return fs.VEC.data(); }
   ARR(spheres) ARR(moving_spheres) ARR(rects) ARR(triangles) ARR(nodes) ARR(entries) ARR(materials) ARR(textures)
-  ARR(perlins) ARR(gravity_spheres) ARR(texels) ARR(gravity_y) ARR(refs)
+  ARR(perlins) ARR(gravity_spheres) ARR(texels) ARR(gravity_y) ARR(refs) ARR(images)
 #undef ARR
   *n = 0; *elem_bytes = 0;
   return nullptr;
 }
+// The feature word the flattener derived (core/flat_types.hpp: F_*), which picks the kernels' instantiations.
+uint32_t oracle_flat_features(const void* flat) { return flat ? ((const rtx::FlatScene*)flat)->features : 0u; }
 
 void oracle_philox4x32_10(uint32_t ctr[4], uint32_t k0, uint32_t k1) { rt::philox4x32_10(ctr, k0, k1); }
 uint64_t oracle_splitmix64_next(uint64_t* state) {

@@ -192,6 +192,18 @@ int oracle_core32_world_hit(const void* flat, const double o[3], const double d[
   return 1;
 }
 
+// texture_value of one texture record of the narrowed scene at (u, v, p) narrowed: out = the float colour widened.
+int oracle_core32_texture_value(const void* flat, int32_t texture_index, double u, double v, const double p[3], double out[3]) {
+  if (!flat) return -1;
+  rtx::FlatScene fs;
+  if (!narrow_scene(flat, &fs)) return -1;
+  if (texture_index < 0 || (size_t)texture_index >= fs.textures.size()) return -1;
+  const rt::SceneView sv = fs.view();
+  const rt::Color c = rt::texture_value<rt::F_ALL, false>(sv, texture_index, (float)u, (float)v, rt::v3((float)p[0], (float)p[1], (float)p[2]), nullptr);
+  out[0] = c.x; out[1] = c.y; out[2] = c.z;
+  return 1;
+}
+
 // path_bounce_begin on a ray given as six doubles (narrowed) with `depth` bounces left: 1 when the path ends there.
 int oracle_core32_path_ends(const double o[3], const double d[3], int32_t depth) {
   rt::PathState ps;

@@ -64,10 +64,12 @@ int oracle_core32_world_hit(const void* flat, const double o[3], const double d[
 int oracle_core32_path_ends(const double o[3], const double d[3], int32_t depth);
 void oracle_core32_ray32(const double o[3], const double d[3], double out[8]);
 void oracle_core32_math(int32_t fn, const double* x, const double* y, int64_t n, double* out);
+int oracle_core32_texture_value(const void* flat, int32_t texture_index, double u, double v, const double p[3], double out[3]);
 /* The product's f64 -> f32 scene converter (csrc/host/f32_layout.hpp) and what it is fed. */
 int64_t oracle_f32_convert(const char* desc, const void* in, int64_t n, int64_t elem64, void* out);
 const char* oracle_f32_desc(int32_t k, const char** name);
 const void* oracle_flat_array(const void* flat, const char* name, int64_t* n, int64_t* elem_bytes);
+uint32_t oracle_flat_features(const void* flat);
 
 /* Known-answer probes into O1's restated functions. */
 void oracle_o1_vec3_ops(const double a[3], const double b[3], double t, double out[24]);
@@ -80,6 +82,10 @@ int oracle_o1_aabb_hit(const double mn[3], const double mx[3], const double o[3]
                        double t_min, double t_max);
 int oracle_o1_hit(const void* graph, int32_t handle, const double o[3], const double d[3], double time,
                   double t_min, double t_max, uint64_t rng_seed, double out[10]);
+/* Texture::value of one texture: the graph's (recursing to any depth), and texture_value over the flat record of the same
+ * index (a graph texture handle IS its flat index) in the f64 core; oracle_core32_texture_value is the float build's. */
+int oracle_o1_texture_value(const void* graph, int32_t texture_handle, double u, double v, const double p[3], double out[3]);
+int oracle_core_texture_value(const void* flat, int32_t texture_index, double u, double v, const double p[3], double out[3]);
 
 /* The same probes into the product's shared core (ray-tracing-series-rust_amd/csrc/core). */
 void oracle_core_vec3_ops(const double a[3], const double b[3], double t, double out[24]);

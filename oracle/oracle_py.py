@@ -116,6 +116,9 @@ def load():
     lib.oracle_f32_convert.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
     lib.oracle_f32_desc.restype = C.c_char_p
     lib.oracle_f32_desc.argtypes = [C.c_int32, C.POINTER(C.c_char_p)]
+    for name in ("oracle_o1_texture_value", "oracle_core_texture_value", "oracle_core32_texture_value"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, _D, _D]
     lib.oracle_flat_array.restype = C.c_void_p
     lib.oracle_flat_array.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
@@ -305,6 +308,17 @@ def flat_array(flat_arrays_ptr, name):
     return np.ctypeslib.as_array((C.c_uint8 * (n.value * e.value)).from_address(p)).copy(), e.value
 
 
+# core/flat_types.hpp: the texture bits of the feature word
+F_CHECKER, F_NOISE, F_IMAGE = 1 << 14, 1 << 15, 1 << 16
+
+
+def flat_features(flat_arrays_ptr):
+    """The feature word of a flat scene (F_* of core/flat_types.hpp)."""
+    lib = load()
+    lib.oracle_flat_features.restype, lib.oracle_flat_features.argtypes = C.c_uint32, [C.c_void_p]
+    return int(lib.oracle_flat_features(flat_arrays_ptr))
+
+
 def rt_math(fn, x, y=None):
     lib = load()
     names = {"sin": 0, "cos": 1, "log": 2, "acos": 3, "atan2": 4, "tan": 5, "sqrt": 6, "sin_sign": 10}
@@ -383,6 +397,25 @@ def core_world_hit_mat(flat_arrays_ptr, o, d, time=0.0, t_min=0.001, t_max=float
     if rec is not None:
         rec["mat"] = mat.value
     return rec
+
+
+def _texture_value(name, ptr, tex, u, v, p):
+    out = (C.c_double * 3)()
+    rc = getattr(load(), name)(ptr, int(tex), float(u), float(v), _d3(p), out)
+    if rc != 1:
+        raise ValueError("%s: no texture %r" % (name, tex))
+    return np.array(out[:])
+
+
+def o1_texture_value(graph_ptr, texture_handle, u, v, p):
+    """Texture::value(u, v, p) of a graph's texture by the literal restatement, which recurses to any depth -> rgb (3,)."""
+    return _texture_value("oracle_o1_texture_value", graph_ptr, texture_handle, u, v, p)
+
+
+def core_texture_value(flat_arrays_ptr, texture_index, u, v, p, f32=False):
+    """texture_value of the product's core over a flat scene's texture record (a graph texture handle is its index); f32: the
+    float build over the narrowed scene, (u, v, p) narrowed, the float colour widened."""
+    return _texture_value("oracle_core32_texture_value" if f32 else "oracle_core_texture_value", flat_arrays_ptr, texture_index, u, v, p)
 
 
 def audit_motion(flat_arrays_ptr, n_times=16):

@@ -129,8 +129,59 @@ static int check_features(int32_t sid) {
   return 0;
 }
 
+// The texture probes on a tree of every kind: a chain of 16 checkers (the longest the flattener admits) whose leaves are a
+// 3 x 2 image, a noise texture and a solid colour.  O1, the f64 core and the float core are asked at points of both
+// parities, at far and non-finite coordinates and at (u, v) on, beyond and not on the unit square; O1 and the f64 core must
+// agree bit for bit.  One more checker on top must be refused once a sphere of the world wears it.
+static int check_textures() {
+  rtx::SceneGraph g(1);
+  std::vector<double> texels;
+  for (int k = 0; k < 3 * 2 * 3; ++k) texels.push_back((double)(10 * k + 1));
+  const int32_t image = g.image_from_texels(3, 2, texels.data());
+  const int32_t noise = g.noise(4.0);
+  const double red[3] = {0.9, 0.1, 0.2};
+  const int32_t solid = g.solid_color(red);
+  int32_t t = g.checker(image, noise);
+  for (int k = 1; k < 16; ++k) t = g.checker(k % 2 ? t : solid, k % 2 ? solid : t);
+  const int32_t deep = g.checker(t, t);
+  if (image < 0 || noise < 0 || solid < 0 || t < 0 || deep < 0) { fprintf(stderr, "textures: construction failed: %s\n", g.error.c_str()); return 1; }
+  const double c[3] = {0.0, 0.0, 0.0};
+  const int32_t world = g.list_new();
+  g.list_add(world, g.sphere(c, 1.0, g.diffuse_light(t)));
+  g.diffuse_light(deep);  // a material nothing wears: allowed
+  rtx::BuildOptions bo;
+  rtx::FlatScene fs;
+  std::string err;
+  if (!rtx::flatten_scene(g, world, bo, &fs, &err)) { fprintf(stderr, "textures: flatten: %s\n", err.c_str()); return 1; }
+  const double big = 3.0e9, inf = 1.0 / 0.0, nan = inf - inf;
+  const double pts[][3] = {{0.1, 0.2, 0.3}, {-0.1, 0.2, 0.3}, {0.4, -0.7, 12.5}, {big, -big, 0.5}, {1e15, 2.5, -1e15}, {inf, 0.0, 1.0}, {nan, 1.0, 1.0}, {0.0, -0.0, 5.0}};
+  const double uvs[][2] = {{0.0, 0.0}, {1.0, 1.0}, {0.5, 0.34}, {-3.0, 7.0}, {nan, nan}, {inf, -inf}};
+  int n = 0;
+  for (const auto& p : pts)
+    for (const auto& uv : uvs)
+      for (int32_t tex : {image, noise, solid, t}) {
+        double a[3], b[3], f[3];
+        if (oracle_o1_texture_value(&g, tex, uv[0], uv[1], p, a) != 1 || oracle_core_texture_value(&fs, tex, uv[0], uv[1], p, b) != 1 ||
+            oracle_core32_texture_value(&fs, tex, uv[0], uv[1], p, f) != 1) { fprintf(stderr, "textures: a probe failed\n"); return 1; }
+        if (memcmp(a, b, sizeof(a)) != 0) { fprintf(stderr, "textures: O1 and the core differ on texture %d\n", tex); return 1; }
+        ++n;
+      }
+  double out[3];
+  if (oracle_o1_texture_value(&g, -1, 0, 0, c, out) != -1 || oracle_core_texture_value(&fs, (int32_t)fs.textures.size(), 0, 0, c, out) != -1) {
+    fprintf(stderr, "textures: a bad index was not refused\n");
+    return 1;
+  }
+  const int32_t world17 = g.list_new();
+  g.list_add(world17, g.sphere(c, 1.0, g.diffuse_light(deep)));
+  rtx::FlatScene fs17;
+  if (rtx::flatten_scene(g, world17, bo, &fs17, &err) || err.find("17 deep") == std::string::npos) { fprintf(stderr, "textures: 17 checkers were not refused\n"); return 1; }
+  printf("textures: %d probes, O1 == core; 17 checkers refused\n", n);
+  return 0;
+}
+
 int main() {
   int bad = 0;
+  bad += check_textures();
   for (int32_t sid : {2, 5, 6, 7, 11}) bad += check_features(sid);  // image texture; box media; Book-2; moving spheres + lens; mesh
   const int32_t scenes[] = {0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 100, 101};
   for (int32_t sid : scenes) bad += check_scene(sid, 40, sid == 4 || sid == 5 || sid == 6 || sid == 12 ? 1.0 : 1.6, 2, false);

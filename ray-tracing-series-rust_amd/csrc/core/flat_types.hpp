@@ -216,6 +216,11 @@ struct RenderParams {
 // scene; the kernels are compiled for a few preset masks so that, e.g., a sphere-only scene
 // does not carry triangle / medium / Perlin code (and registers).  A path is only ever
 // compiled OUT when the scene cannot reach it, so results do not depend on the preset.
+// The longest chain of nested Checker textures texture_value (shading.hpp) follows; the reference recurses without limit
+// (texture.rs:54-64).  The flattener refuses a world in which a material reaches a longer one (host/flatten.cpp:
+// check_checker_chains), include/rtx_abi.h states it at rtx_checker, tests/texture_cases.py holds both sides of it.
+constexpr int RT_MAX_CHECKER_CHAIN = 16;
+
 enum Feature : uint32_t {
   F_SPHERE = 1u << 0, F_MOVING_SPHERE = 1u << 1, F_RECT = 1u << 2, F_TRIANGLE = 1u << 3,
   F_PRIM_ENTRY = 1u << 4, F_GROUP = 1u << 5, F_BVH = 1u << 6, F_XFORM = 1u << 7, F_MEDIUM = 1u << 8,

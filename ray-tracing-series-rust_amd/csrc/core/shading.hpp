@@ -124,7 +124,7 @@ template <uint32_t F, bool COUNT>
 RT_HD Color texture_value(const SceneView& sv, int32_t tex, real u, real v, Point3 p,
                           TraceCounters* cnt) {
   if (F & F_CHECKER) {
-    for (int guard = 0; guard < 16; ++guard) {
+    for (int guard = 0; guard < RT_MAX_CHECKER_CHAIN; ++guard) {  // (flat_types.hpp; a longer chain never gets here: the flattener refuses it)
       const FlatTexture& t = sv.textures[tex];
       if (t.kind != TEX_CHECKER) break;
       // texture.rs:56-62: sines = sin(10x) sin(10y) sin(10z); sines < 0 -> odd.  Only the sign is used, and

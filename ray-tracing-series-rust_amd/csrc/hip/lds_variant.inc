@@ -25,6 +25,21 @@ inline bool lds_common_interval(const MS* ms, size_t n, double* t0, double* t1) 
   return true;
 }
 
+// Which primitive record k_trace_lds keeps in LDS.  static_preset: the feature mask of the lean instantiation
+// (P_STATIC_SPHERES: static spheres, no checker).  A world with any feature beyond it -- moving spheres, or static spheres
+// under a checker texture -- runs k_trace_lds<P_SPHERES>, which keeps EVERY sphere as an 80-byte moving-sphere record
+// (trace_lds.inc: UNI).  plan_lds sizes the LDS and launch_lds picks the instantiation from this one answer: asked of the
+// scene's primitives instead, a static world with a checker got room for 40-byte sphere records under a kernel that writes
+// moving-sphere records.
+inline bool lds_records_are_moving(uint32_t features, uint32_t static_preset) { return (features & ~static_preset) != 0u; }
+// The record counts of the plan for a BVH of max_end leaf slots over n_static static spheres: {n_spheres, n_moving, n_uni}.
+inline void lds_record_counts(uint32_t features, uint32_t static_preset, uint32_t n_static, uint32_t max_end, uint32_t out[3]) {
+  const bool moving = lds_records_are_moving(features, static_preset);
+  out[0] = moving ? 0u : max_end;
+  out[1] = moving ? max_end : 0u;
+  out[2] = moving ? n_static : 0u;
+}
+
 // A BVH's interval admits time-aware boxes when it is ordered: the boxes are lerps between its two ends (flatten.cpp).
 inline bool lds_motion_interval_ok(double bvh_t0, double bvh_t1) { return bvh_t0 < bvh_t1; }
 

@@ -753,11 +753,10 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   p.plain.levels = levels;
   p.plain.dims = {(uint32_t)fs.nodes32.size(), max_end, max_end, 0u, LDSK_NODE_DWORDS, 0u};
   p.mv_common = sw.mv_common && lds_common_interval(fs.moving_spheres.data(), fs.moving_spheres.size(), &p.mv_t0, &p.mv_t1);
-  if (fs.features & rt::F_MOVING_SPHERE) {  // k_trace_lds<P_SPHERES>: one kind of primitive in LDS (trace_lds.inc: UNI)
-    p.plain.dims.n_uni = (uint32_t)fs.spheres.size();
-    p.plain.dims.n_moving = max_end;
-    p.plain.dims.n_spheres = 0u;
-  }
+  // the record kind follows the instantiation launch_lds picks, not the scene's primitives (lds_variant.inc)
+  uint32_t counts[3];
+  lds_record_counts(fs.features, P_STATIC_SPHERES, (uint32_t)fs.spheres.size(), max_end, counts);
+  p.plain.dims.n_spheres = counts[0]; p.plain.dims.n_moving = counts[1]; p.plain.dims.n_uni = counts[2];
   p.motion.levels = levels;
   p.motion.dims = p.plain.dims;
   p.motion.dims.node_dwords = LDSK_MOTION_NODE_DWORDS;
@@ -837,7 +836,7 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
   })
 #define LAUNCH_LDS(FEAT, MOTIONF) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF); } else { LAUNCH_LDS2(FEAT, false, MOTIONF); } } while (0)
   // static spheres without checker textures (the Book-1 final scene): the leaner instantiation
-  if ((a.feat & ~P_STATIC_SPHERES) == 0) { LAUNCH_LDS(P_STATIC_SPHERES, 0u); }
+  if (!lds_records_are_moving(a.feat, P_STATIC_SPHERES)) { LAUNCH_LDS(P_STATIC_SPHERES, 0u); }
   else if (*variant & LDSV_ONE_AXIS) { LAUNCH_LDS(P_SPHERES, 3u); }  // slopes along y only (Book-1 at HEAD)
   else if (motion) { LAUNCH_LDS(P_SPHERES, 1u); }
   else { LAUNCH_LDS(P_SPHERES, 0u); }

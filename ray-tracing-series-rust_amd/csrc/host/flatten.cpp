@@ -509,15 +509,51 @@ struct Flattener {
     return true;
   }
 
-  bool texture_has_image(int32_t t, int depth = 0) const {
-    if (t < 0 || depth > 16) return false;
-    const GTexture& tx = g.textures[t];
-    if (tx.kind == rt::TEX_IMAGE) return true;
-    if (tx.kind == rt::TEX_CHECKER) return texture_has_image(tx.a, depth + 1) || texture_has_image(tx.b, depth + 1);
-    return false;
+  // Per texture, bottom-up in one pass (a handle names an EARLIER texture: SceneGraph::checker takes valid handles only):
+  // tex_chain = the checkers on the longest way down from it (0 for a leaf kind), tex_image = an Image texture below it.
+  // texture_value (core/shading.hpp) follows a checker chain for rt::RT_MAX_CHECKER_CHAIN steps (core/flat_types.hpp), so a longer one is refused
+  // (check_checker_chains) rather than rendered as the colour field of a checker record.
+  std::vector<int32_t> tex_chain;
+  std::vector<uint8_t> tex_image;
+  bool survey_textures() {
+    const size_t n = g.textures.size();
+    tex_chain.assign(n, 0);
+    tex_image.assign(n, 0);
+    for (size_t t = 0; t < n; ++t) {
+      const GTexture& tx = g.textures[t];
+      if (tx.kind == rt::TEX_IMAGE) tex_image[t] = 1;
+      if (tx.kind != rt::TEX_CHECKER) continue;
+      if (tx.a < 0 || tx.b < 0 || (size_t)tx.a >= t || (size_t)tx.b >= t) return fail("a checker texture whose child is not an earlier texture");
+      tex_chain[t] = 1 + std::max(tex_chain[(size_t)tx.a], tex_chain[(size_t)tx.b]);
+      tex_image[t] = tex_image[(size_t)tx.a] | tex_image[(size_t)tx.b];
+    }
+    return true;
+  }
+  // Every material a primitive or a medium of the flattened world names: its texture's checker chain must fit.  A deep texture
+  // that nothing in the world reaches is never evaluated and stays allowed.
+  bool check_checker_chains() {
+    std::vector<int32_t> mats;
+    for (const auto& p : out.spheres) mats.push_back(p.mat);
+    for (const auto& p : out.moving_spheres) mats.push_back(p.mat);
+    for (const auto& p : out.gravity_spheres) mats.push_back(p.mat);
+    for (const auto& p : out.rects) mats.push_back(p.mat);
+    for (const auto& p : out.triangles) mats.push_back(p.mat);
+    for (const rt::FlatEntry& e : out.entries)
+      if (e.kind == rt::ENTRY_MEDIUM) mats.push_back(e.b);
+    for (int32_t m : mats) {
+      if (m < 0 || (size_t)m >= g.materials.size()) continue;
+      const int32_t t = g.materials[(size_t)m].tex;
+      if (t < 0 || (size_t)t >= tex_chain.size() || tex_chain[(size_t)t] <= rt::RT_MAX_CHECKER_CHAIN) continue;
+      return fail("unsupported texture: checker textures nested " + std::to_string(tex_chain[(size_t)t]) + " deep under material " +
+                  std::to_string(m) + ". A chain of at most " + std::to_string(rt::RT_MAX_CHECKER_CHAIN) +
+                  " checkers is followed (the reference recurses without limit, texture.rs:54-64); a deeper one would be cut short "
+                  "and shade with the wrong texture");
+    }
+    return true;
   }
 
   bool run(int32_t world) {
+    if (!survey_textures()) return false;
     for (const GTexture& t : g.textures) {
       rt::FlatTexture f;
       memset(&f, 0, sizeof(f));
@@ -532,7 +568,7 @@ struct Flattener {
       f.kind = m.kind; f.tex = m.tex;
       f.albedo[0] = m.albedo[0]; f.albedo[1] = m.albedo[1]; f.albedo[2] = m.albedo[2];
       f.param = m.param;
-      f.needs_uv = texture_has_image(m.tex) ? 1 : 0;
+      f.needs_uv = (m.tex >= 0 && (size_t)m.tex < tex_image.size() && tex_image[(size_t)m.tex]) ? 1 : 0;
       // SolidColor::value (texture.rs:27-31) resolved here: kernels compiled for scenes without checker / noise / image
       // textures read the colour from the material record and never fetch the texture record behind it
       if ((m.kind == rt::MAT_LAMBERTIAN || m.kind == rt::MAT_DIFFUSE_LIGHT || m.kind == rt::MAT_ISOTROPIC) && m.tex >= 0 &&
@@ -553,6 +589,7 @@ struct Flattener {
     }
     // An empty world is legal: HittableList::hit returns None and every path sees the background.
     if (!emit_top(world)) return false;
+    if (!check_checker_chains()) return false;
     if (!inst.empty()) {
       // the instance records close the entry array (core/flat_types.hpp: ENTRY_INSTANCE); emit_top met the trees in slot order
       for (const InstRec& r : inst) {

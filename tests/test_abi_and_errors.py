@@ -93,6 +93,24 @@ def test_unsupported_shapes_are_reported_not_approximated(rtsr):
     assert e.value.status == rtsr.RTX_EUNSUPPORTED
 
 
+def test_checker_chains_deeper_than_sixteen_are_refused(rtsr):
+    """texture_value follows a checker chain for 16 steps (rtx_abi.h: rtx_checker): a world that wears a longer one is refused
+    with the depth in the message; building the texture, or leaving it unworn, is not an error."""
+    b = rtsr.Builder(1)
+    t = b.solid_color((0.9, 0.1, 0.1))
+    other = b.solid_color((0.1, 0.1, 0.9))
+    for k in range(16):
+        t = b.checker(t, other) if k % 2 else b.checker(other, t)  # the chain runs through either child
+    sixteen = b.sphere((0, 0, 0), 1.0, b.lambertian(t))
+    seventeen = b.sphere((3, 0, 0), 1.0, b.diffuse_light(b.checker(other, t)))
+    assert b.flatten(b.hittable_list([sixteen])).info()["n_spheres"] == 1
+    for world in (b.hittable_list([sixteen, seventeen]), b.bvh_from_list(b.hittable_list([sixteen, seventeen]), 0, 1),
+                  b.hittable_list([b.constant_medium((1, 1, 1), 0.1, sixteen), b.translate((1, 0, 0), seventeen)])):
+        with pytest.raises(rtsr.RtxError) as e:
+            b.flatten(world)
+        assert e.value.status == rtsr.RTX_EUNSUPPORTED and "nested 17 deep" in str(e.value) and "16" in str(e.value)
+
+
 def test_missing_files(rtsr, tmp_path):
     b = rtsr.Builder(1)
     with pytest.raises(rtsr.RtxError):
