@@ -616,11 +616,11 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
  * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table, 7 the 4-wide culling tree (128 bytes per
  * node, indexed like nodes; 0 bytes when the scene walks its binary tree), 8 the stack levels its walks are launched with (one
  * int32, 0 without a wide tree), 9 the scene's max_stack as its binary walks are now launched with (one int32; a rebuild of
- * an instance tree changes it).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
+ * an instance tree changes it), 10 triangles, 11 top_box32 (6 floats per slot).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
  * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
- * instance tree, the box before the ops). */
+ * instance tree, the box before the ops), 12: triangle_id (one int32 per flat triangle). */
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
 
 /* ---- instance trees: the quality of a tree as it stands, and a rebuild for the current pose ---------------------------------
@@ -669,6 +669,53 @@ rtx_status rtx_flat_rebuild_instance_trees(rtx_flat* f, const int32_t* trees, in
  * streams is the caller's, progressive handles made earlier hold the old pose's samples.  rtx_multi_* scenes are not covered:
  * rebuild the flat scene and create the handle again. */
 rtx_status rtx_scene_rebuild_instance_trees(rtx_scene* s, const int32_t* trees, int32_t n, void* hip_stream, RtxRebuildStats* out);
+
+/* ---- deforming meshes: new vertices for triangles of a flat scene or of a resident f64 scene (an extension) -----------------
+ * The flattener stores a BVH's triangles in leaf order and gives a shared triangle private copies, so a flat triangle is not
+ * named by position but by its ID: the ordinal of its first emission by the flattener, 0, 1, 2, ... in the order the world is
+ * walked.  A triangle handle listed twice has one id; a private copy carries the id of its original.
+ *
+ * rtx_flat_triangle_ids: the ids of the triangles below `object` (a triangle, a list such as rtx_triangle_mesh returns, a
+ * BvhNode, a wrapper or medium around those), in list order, a mesh's faces in face order.  Writes min(count, cap) ids,
+ * returns count; -1 (and rtx_last_error) for a NULL argument, a bad handle or an object this flat scene did not flatten. */
+int64_t rtx_flat_triangle_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap);
+/* vertices: n x 9 doubles, v0 v1 v2 of triangle ids[i].  ids: a HOST array in all three entries, free for reuse on return.
+ *
+ * Meaning: the scene then answers every entry point -- rtx_render* through every walker, light sampling, progressive handles
+ * made afterwards and their feature pass, rtx_scene_cast_rays*, rtx_scene_trace_rays* -- bit for bit as the scene built from
+ * scratch with those vertices.  One class of ray is exempt, and it is open for a fresh build too: an exact tie between two
+ * primitives of different centroids inside one BVH goes by leaf order ("Not covered"), and a fresh build
+ * may order leaves differently.
+ *
+ * What is written, and nothing else: v0 v1 v2 and normal = unit(cross(v1 - v0, v2 - v0)) of every flat copy of each id (mat is
+ * untouched; a zero-area triangle gets the NaN normal a fresh build gives it); the boxes of every BVH that holds an updated
+ * triangle, refitted whole and bottom-up in nodes, nodes32 and the static copy of the time-aware boxes (child codes, split axes
+ * and pads stay: the TOPOLOGY is kept, where a fresh build might choose another -- culling only); on a resident scene with a
+ * 4-wide tree the planes of its slots (which nodes the collapse opened is kept, so the stack levels and every launch plan
+ * stand); member_local_box and the instance tree above a touched member; top_box32 and the slot record's box of a plain
+ * top-level triangle.  RtxFlatInfo::sah_cost is not updated.
+ *
+ * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, an id out of
+ * range or named twice; host entries: a vertex that is not finite; device entry: a pointer that is not 8-byte aligned.  n = 0
+ * is RTX_OK with nothing launched.  RTX_EUNSUPPORTED, the scene unchanged, checked before anything is enqueued: a touched BVH
+ * that holds a MovingSphere or GravitySphere (its time-aware slopes would have to be derived again), and a resident f32 scene,
+ * which does not hold the f64 vertices of the untouched triangles in touched leaves: update the flat scene with
+ * rtx_flat_set_triangles and upload it again with rtx_scene_upload_f32. */
+rtx_status rtx_flat_set_triangles(rtx_flat* f, const int32_t* ids, int64_t n, const double* vertices);
+/* A resident f64 scene; vertices is a HOST array, staged with one copy.  Asynchronous on hip_stream, as
+ * rtx_scene_set_transforms: k_set_triangles, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
+ * k_refit_instance_tree per touched instance tree, k_top_triangle_boxes.  One update of a scene at a time; ordering against
+ * work on other streams is the caller's; progressive handles made earlier hold the old shape.  rtx_multi_* scenes are not
+ * covered: update the flat scene and create the handle again.
+ * After an update (through either resident entry) that touched a member of an instance tree, the FIRST
+ * rtx_scene_set_transforms that follows waits for the device once and reads the members' new local boxes back (48 bytes a
+ * member) before it checks the new pose against them; that one call is not asynchronous.  Later ones are again. */
+rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream);
+/* d_vertices: a DEVICE pointer (8-byte aligned), e.g. the output of the caller's own skinning kernel on hip_stream; it is read
+ * by work enqueued on hip_stream and must stay valid until that work is done.  Finiteness cannot be checked without a
+ * read-back: a vertex that is not finite gives that triangle and the boxes above it unspecified culling.  No index is derived
+ * from a vertex, so nothing can leave an allocation. */
+rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

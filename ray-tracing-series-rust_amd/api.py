@@ -156,7 +156,8 @@ RTX_XFORM_TRANSLATE, RTX_XFORM_ROTATE_Y = 0, 1
 _XFORM_NAMES = ("translate", "rotate_y")
 # rtx_flat_array / rtx_device_scene_array: `which` and the element size in an f64 and in an f32 scene
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
-                "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128)}
+                "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128),
+                "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
@@ -276,6 +277,10 @@ ABI = {
     "rtx_scene_instance_tree_cost": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_double)]),
     "rtx_flat_rebuild_instance_trees": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
     "rtx_scene_rebuild_instance_trees": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int32, _VP, C.POINTER(RtxRebuildStats)]),
+    "rtx_flat_triangle_ids": (C.c_int64, [_VP, _VP, _H, C.POINTER(C.c_int32), C.c_int64]),
+    "rtx_flat_set_triangles": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
+    "rtx_scene_set_triangles": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
+    "rtx_scene_set_triangles_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
     "rtx_device_scene_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_flat_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_builder_graph": (_VP, [_VP]),
@@ -557,6 +562,25 @@ class Flat:
         arr = _slot_ops(self, updates)
         _check(lib.rtx_flat_set_transforms(self._p, arr, len(arr)))
 
+    def triangle_ids(self, builder, handle):
+        """The ids of the triangles below `handle` (a triangle, a mesh's list, a BvhNode, a wrapper or medium around those) in
+        list order, a mesh's faces in face order (rtx_flat_triangle_ids) -> int32 array.  A triangle's id is the ordinal of its
+        first emission by the flattener; Flat.array("triangle_id") holds the id of every flat triangle."""
+        n = lib.rtx_flat_triangle_ids(self._p, builder.ptr, int(handle), None, 0)
+        if n < 0:
+            raise RtxError(RTX_EINVAL, last_error())
+        out = np.zeros(n, dtype=np.int32)
+        if n and lib.rtx_flat_triangle_ids(self._p, builder.ptr, int(handle), out.ctypes.data_as(C.POINTER(C.c_int32)), n) != n:
+            raise RtxError(RTX_EINVAL, last_error())
+        return out
+
+    def set_triangles(self, ids, vertices):
+        """New vertices for the triangles `ids`, in place (rtx_flat_set_triangles): the flat scene becomes the one flattened from
+        scratch with these vertices, its BVHs refitted with their topology kept.  vertices: n x 9 (or n x 3 x 3) doubles, v0 v1 v2
+        of ids[i]."""
+        ids, vertices = _triangle_update(ids, vertices)
+        _check(lib.rtx_flat_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3)))
+
     def rebuild_instance_trees(self, trees=None, builder="morton"):
         """A new topology for instance trees from their members' boxes at the current pose, in place
         (rtx_flat_rebuild_instance_trees).  trees: tree indices, None for every tree.  builder: "morton" -- what
@@ -575,12 +599,23 @@ class Flat:
         return cost.value
 
     def array(self, name):
-        """A copy of one host array as bytes (rtx_flat_array; a test hook): a name of SCENE_ARRAYS but "world_desc"."""
+        """A copy of one host array as bytes (rtx_flat_array; a test hook): a name of SCENE_ARRAYS but "world_desc" and "nodes4"."""
         return _scene_array(lambda out, n: lib.rtx_flat_array(self._p, SCENE_ARRAYS[name][0], out, n), self, name, False)
 
     def upload(self, f32=False):
         """f32=True: the statistical fast mode (rtx_scene_upload_f32): float arithmetic, no bit-exactness claim."""
         return Scene(self, f32=f32)
+
+
+def _triangle_update(ids, vertices):
+    """ids, vertices of set_triangles -> (contiguous int32 array of n ids, contiguous float64 array of 9 n values)."""
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+    vertices = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1))
+    if vertices.size != 9 * ids.size:
+        raise ValueError("vertices holds %d values, %d ids need %d (v0 v1 v2 each)" % (vertices.size, ids.size, 9 * ids.size))
+    if ids.size == 0:  # a pointer the library may compare with NULL
+        return np.zeros(1, dtype=np.int32)[:0], np.zeros(1, dtype=np.float64)[:0]
+    return ids, vertices
 
 
 def _tree_list(trees):
@@ -694,6 +729,29 @@ class Scene:
         raw = getattr(stream, "cuda_stream", stream)
         _check(lib.rtx_scene_set_transforms(self._p, arr, len(arr), _VP(raw or None)))
 
+    def set_triangles(self, ids, vertices, stream=None):
+        """New vertices for the triangles `ids` of the RESIDENT f64 scene: every later call answers as on the scene built from
+        scratch with these vertices (its BVHs are refitted on the device, their topology kept).  vertices: n x 9 doubles as a
+        numpy array (rtx_scene_set_triangles, staged with one copy) or as a torch float64 tensor on the GPU
+        (rtx_scene_set_triangles_device: e.g. the output of a skinning kernel on `stream`).  ids: host integers either way.
+        Enqueued on `stream` as in set_transforms."""
+        raw = getattr(stream, "cuda_stream", stream)
+        if hasattr(vertices, "data_ptr"):  # a torch tensor
+            import torch
+            if not vertices.is_cuda or vertices.dtype != torch.float64 or not vertices.is_contiguous():
+                raise ValueError("a tensor of vertices must be a contiguous float64 tensor on the GPU")
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+            if vertices.numel() != 9 * ids.size:
+                raise ValueError("vertices holds %d values, %d ids need %d (v0 v1 v2 each)" % (vertices.numel(), ids.size, 9 * ids.size))
+            if ids.size == 0:
+                return  # n = 0 is RTX_OK with nothing launched; an empty tensor has no pointer to hand over
+            _check(lib.rtx_scene_set_triangles_device(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
+                                                      _VP(vertices.data_ptr() or None), _VP(raw or None)))
+            return
+        ids, vertices = _triangle_update(ids, vertices)
+        _check(lib.rtx_scene_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3),
+                                           _VP(raw or None)))
+
     def rebuild_instance_trees(self, trees=None, stream=None):
         """A new topology for instance trees of the RESIDENT scene from their members' boxes at the current pose
         (rtx_scene_rebuild_instance_trees; Morton codes, a radix sort and Karras' tree on the device).  trees: tree indices,
@@ -720,7 +778,8 @@ class Scene:
 
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
-        "nodes", "nodes32", "motion32", "world_desc" or "nodes4" (the 4-wide tree; empty when the scene has none)."""
+        "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32" or "nodes4" (the 4-wide tree; empty when the
+        scene has none)."""
         return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)
 
     def wide_levels(self):

@@ -1,0 +1,259 @@
+// rtx_scene_set_triangles / rtx_scene_set_triangles_device on a resident f64 scene (included by render.hip, namespace rtx; the
+// f64 compilation only: an f32 scene does not hold the f64 vertices of the untouched triangles in a touched leaf).
+//
+// New vertices for named triangles reach these device arrays and no other:
+//   triangles                       v0 v1 v2 and the normal of every flat copy of an id (k_set_triangles)
+//   nodes / nodes32 / motion32      every BVH that holds an updated triangle, refitted whole and bottom-up (k_refit_bvh)
+//   nodes4                          the planes of every slot of those BVHs' wide records; which nodes the collapse opened is kept,
+//                                   so WidePlan::levels and every launch plan stand (k_refit_wide)
+//   d_local_box, then the instance tree above a touched member (k_member_local_boxes, k_refit_instance_tree of scene_update.inc)
+//   top_box32 / WorldDesc::box      a plain top-level triangle slot (k_top_triangle_boxes)
+// with the arithmetic of the flattener (core/prim_box.hpp, host/set_triangles.hpp), so that the arrays equal those of the
+// host-updated flat scene uploaded afresh -- the judge of tests/test_gpu_set_triangles.py.  Topology is not touched: child
+// codes, split axes, refs, entries; SceneView, the trace kernels and their arguments do not change.
+//
+// No index is derived from a vertex.  Every index a kernel forms comes from a table the host built from the caller's ids and
+// the upload's shadow, both checked against the array sizes (host/set_triangles.hpp: build_mesh_shadow, check_triangle_ids);
+// a vertex is only ever stored or compared.  A non-finite vertex through the device entry therefore cannot leave an
+// allocation: it gives its triangle and the boxes above it unspecified culling.
+
+// One thread per (flat triangle, vertex triple): pairs[2 i] = flat index, pairs[2 i + 1] = index of the triple in `vertices`.
+__global__ __launch_bounds__(256) void k_set_triangles(const int32_t* __restrict__ pairs, int n_pairs, const double* __restrict__ vertices,
+                                                      rt::FlatTriangle* __restrict__ triangles) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i >= n_pairs) return;
+  double v[9];
+  const double* src = vertices + 9 * (size_t)pairs[2 * (size_t)i + 1];
+  for (int k = 0; k < 9; ++k) v[k] = src[k];
+  rt::set_triangle_vertices(&triangles[pairs[2 * (size_t)i]], v);
+}
+
+struct BvhRefitArgs {
+  rt::FlatNode* nodes;
+  rt::FlatNode32* nodes32;
+  rt::FlatMotion32* motion32;       // NULL: the scene has no time-aware boxes
+  const rt::PrimRef* refs;          // this BVH's first reference first
+  const rt::FlatSphere* spheres;
+  const rt::FlatRect* rects;
+  const rt::FlatTriangle* triangles;
+  const int32_t* leaves;            // 3 per leaf of this BVH: leaf code, node, child index
+  const int32_t* node_parent;       // 2 per node of this BVH, by node - node_base: parent (-1: root), child index
+  unsigned int* arrivals;           // 1 per node of this BVH, zero at launch
+  int32_t n_leaves, node_base;
+};
+
+// One thread per leaf of ONE BVH -- every leaf, not only the touched ones: the thread unites its primitives' boxes, writes the
+// box where the leaf's parent keeps it and climbs.  The hand-off is k_refit_instance_tree's (scene_update.inc), which is
+// lbvh.hip's k_refit recipe: agent-scope stores of the f64 planes, a fence, an agent-scope arrival, a fence, agent-scope loads
+// of the sibling's planes -- a plain load of a box another CU stored can be served stale from this CU's L1.  Of the two threads
+// that reach a node the first leaves; unions are exact min / max, so the result does not depend on who arrives first.
+__global__ __launch_bounds__(256) void k_refit_bvh(BvhRefitArgs a) {
+  const int l = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (l >= a.n_leaves) return;
+  double b[6];
+  bvh_leaf_box(a.leaves[3 * (size_t)l], a.refs, a.spheres, a.rects, a.triangles, b);
+  double lo[3], hi[3];
+  for (int x = 0; x < 3; ++x) { lo[x] = b[x]; hi[x] = b[3 + x]; }
+  int32_t node = a.leaves[3 * (size_t)l + 1], c = a.leaves[3 * (size_t)l + 2];
+  for (;;) {
+    rt::FlatNode* nd = &a.nodes[node];
+    for (int x = 0; x < 3; ++x) {
+      __hip_atomic_store(&nd->bmin[c][x], lo[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&nd->bmax[c][x], hi[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float l32 = rt::f32_narrow_down(lo[x]), h32 = rt::f32_narrow_up(hi[x]);
+      a.nodes32[node].lo[c][x] = l32;
+      a.nodes32[node].hi[c][x] = h32;
+      if (a.motion32) {  // a BVH without a moving sphere: its static box, no slope (flatten.cpp: build_motion_boxes)
+        a.motion32[node].lo0[c][x] = l32; a.motion32[node].hi0[c][x] = h32;
+        a.motion32[node].dlo[c][x] = 0.0f; a.motion32[node].dhi[c][x] = 0.0f;
+      }
+    }
+    const int32_t rel = node - a.node_base;
+    const int32_t parent = a.node_parent[2 * (size_t)rel], pc = a.node_parent[2 * (size_t)rel + 1];
+    if (parent < 0) return;  // the root: its two child boxes are the whole tree
+    __threadfence();
+    if (atomicAdd(&a.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
+    __threadfence();
+    for (int x = 0; x < 3; ++x) {
+      const double slo = __hip_atomic_load(&nd->bmin[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const double shi = __hip_atomic_load(&nd->bmax[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      lo[x] = rt::rt_fmin(lo[x], slo);
+      hi[x] = rt::rt_fmax(hi[x], shi);
+    }
+    node = parent;
+    c = pc;
+  }
+}
+
+// The f64 box the binary tree keeps for child code `code` below node i: the collapse (host/wide_tree.hpp) opens at most two
+// nodes, so a slot's code is a child of i, of a child of i, or of a grandchild of i.  false: not there (a record no walk reaches).
+__device__ __forceinline__ bool wide_slot_box(const rt::FlatNode* __restrict__ nodes, int32_t i, int32_t code, const rt::FlatNode** at, int* which) {
+  for (int c0 = 0; c0 < 2; ++c0)
+    if (nodes[i].child[c0] == code) { *at = &nodes[i]; *which = c0; return true; }
+  for (int c0 = 0; c0 < 2; ++c0) {
+    const int32_t n1 = nodes[i].child[c0];
+    if (rt::node_child_is_leaf(n1)) continue;
+    for (int c1 = 0; c1 < 2; ++c1)
+      if (nodes[n1].child[c1] == code) { *at = &nodes[n1]; *which = c1; return true; }
+  }
+  for (int c0 = 0; c0 < 2; ++c0) {
+    const int32_t n1 = nodes[i].child[c0];
+    if (rt::node_child_is_leaf(n1)) continue;
+    for (int c1 = 0; c1 < 2; ++c1) {
+      const int32_t n2 = nodes[n1].child[c1];
+      if (rt::node_child_is_leaf(n2)) continue;
+      for (int c2 = 0; c2 < 2; ++c2)
+        if (nodes[n2].child[c2] == code) { *at = &nodes[n2]; *which = c2; return true; }
+    }
+  }
+  return false;
+}
+
+// One thread per node of ONE BVH, its own launch after the binary refit (plain loads: the kernel boundary made the boxes
+// visible).  Every occupied slot of the node's wide record gets the outward-narrowed box of its child code; child codes, empty
+// slots (+inf, -inf) and the all-zero records of nodes no wide walk reaches stay as they are.  Child indices read from `nodes`
+// are the upload's own (validated by build_mesh_shadow: every one lies inside this BVH's piece).
+__global__ __launch_bounds__(256) void k_refit_wide(const rt::FlatNode* __restrict__ nodes, FlatNode4* __restrict__ wide, int32_t node_base, int32_t n_nodes) {
+  const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (t >= n_nodes) return;
+  const int32_t i = node_base + t;
+  FlatNode4* w = &wide[i];
+  if (w->child[0] == 0 && w->child[1] == 0 && w->child[2] == 0 && w->child[3] == 0) return;  // never opened
+  for (int k = 0; k < 4; ++k) {
+    const int32_t code = w->child[k];
+    if (code == 0x7fffffff) continue;
+    const rt::FlatNode* at;
+    int c;
+    if (!wide_slot_box(nodes, i, code, &at, &c)) continue;
+    for (int x = 0; x < 3; ++x) {
+      w->lo[x][k] = rt::f32_narrow_down(at->bmin[c][x]);
+      w->hi[x][k] = rt::f32_narrow_up(at->bmax[c][x]);
+    }
+  }
+}
+
+// One thread per touched member of an instance tree: list[2 i] = the member's index in d_local_box, list[2 i + 1] = its PRIM /
+// GROUP / BVH entry.  After the BVH refits on the same stream.
+__global__ __launch_bounds__(256) void k_member_local_boxes(const int32_t* __restrict__ list, int n, const rt::FlatEntry* __restrict__ entries,
+                                                           const rt::FlatNode* __restrict__ nodes, const rt::PrimRef* __restrict__ refs,
+                                                           const rt::FlatSphere* __restrict__ spheres, const rt::FlatRect* __restrict__ rects,
+                                                           const rt::FlatTriangle* __restrict__ triangles, double* __restrict__ local_box) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i >= n) return;
+  double b[6];
+  member_local_box_of(entries[list[2 * (size_t)i + 1]], nodes, refs, spheres, rects, triangles, b);
+  for (int x = 0; x < 6; ++x) local_box[6 * (size_t)list[2 * (size_t)i] + x] = b[x];
+}
+
+// One block: the touched plain triangle slots.  top_box32 and the box (and the flag that says it is finite) of the slot's
+// WorldDesc record, as build_world_desc derives them.
+__global__ __launch_bounds__(256) void k_top_triangle_boxes(const int32_t* __restrict__ slots, int n, const rt::FlatEntry* __restrict__ entries,
+                                                           const int32_t* __restrict__ top_level, const rt::FlatTriangle* __restrict__ triangles,
+                                                           float* __restrict__ top_box32, WorldDesc* __restrict__ desc) {
+  for (int i = (int)threadIdx.x; i < n; i += 256) {
+    const int32_t slot = slots[i];
+    float bx[6];
+    top_triangle_box32(triangles, (rt::PrimRef)entries[top_level[slot]].a, bx);
+    bool finite = true;
+    for (int x = 0; x < 6; ++x) {
+      top_box32[6 * (size_t)slot + x] = bx[x];
+      if (desc) desc[slot].box[x] = bx[x];
+      finite = finite && rt::rt_fabs(bx[x]) < __builtin_huge_valf();
+    }
+    if (desc) desc[slot].flags = finite ? (desc[slot].flags | WD_BOXED_PRIM) : (desc[slot].flags & ~WD_BOXED_PRIM);
+  }
+}
+
+// ------------------------------------------------------------------ host side
+// ids (host memory) have passed check_triangle_ids against ds->mesh.shadow.  vertices: host memory (staged here, one copy) when
+// host_vertices, else a device pointer.  Everything that can refuse comes first; then one copy and the launches, all on `stream`.
+static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, const int32_t* ids, int64_t n, const double* vertices, bool host_vertices,
+                                           hipStream_t stream) {
+  MeshUpdate& mu = ds->mesh;
+  SceneUpdate& u = ds->upd;
+  const MeshShadow& sh = mu.shadow;
+  std::string err;
+  TrianglePlan plan;
+  const rtx_status pst = plan_triangle_update(who, sh, ids, n, &plan, &err);
+  if (pst != RTX_OK) { set_error(err); return pst; }
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error(std::string(who) + ": scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  if (!mu.uploaded) {
+    if (!sh.leaves.empty()) HIP_TRY(mu.d_leaves.upload(sh.leaves.data(), sh.leaves.size()));
+    if (!sh.node_parent.empty()) {
+      HIP_TRY(mu.d_node_parent.upload(sh.node_parent.data(), sh.node_parent.size()));
+      HIP_TRY(mu.d_arrivals.alloc(sh.node_parent.size() / 2 * sizeof(unsigned int)));
+    }
+    mu.uploaded = true;
+  }
+  // the pinned staging buffer is this scene's own: the copy of the previous update must have left it
+  if (!mu.staged) HIP_TRY(hipEventCreateWithFlags(&mu.staged, hipEventDisableTiming));
+  else HIP_TRY(hipEventSynchronize(mu.staged));
+  // staging layout: [vertices, 72 B each (host entry only)] [pairs] [members: index, entry] [slots]
+  const size_t vert_bytes = host_vertices ? (size_t)n * 9 * sizeof(double) : 0;
+  const size_t n_pairs = plan.pairs.size() / 2, n_members = plan.members.size(), n_slots = plan.slots.size();
+  const size_t bytes = vert_bytes + (2 * n_pairs + 2 * n_members + n_slots) * sizeof(int32_t);
+  if (bytes > mu.h_staging_bytes) {
+    if (mu.h_staging) HIP_TRY(hipHostFree(mu.h_staging));
+    mu.h_staging = nullptr;
+    mu.h_staging_bytes = 0;
+    HIP_TRY(hipHostMalloc(&mu.h_staging, bytes, hipHostMallocDefault));
+    mu.h_staging_bytes = bytes;
+  }
+  HIP_TRY(mu.d_staging.grow(bytes, stream));
+  unsigned char* h = (unsigned char*)mu.h_staging;
+  if (host_vertices) memcpy(h, vertices, vert_bytes);
+  int32_t* h_pairs = (int32_t*)(h + vert_bytes);
+  int32_t* h_members = h_pairs + 2 * n_pairs;
+  int32_t* h_slots = h_members + 2 * n_members;
+  memcpy(h_pairs, plan.pairs.data(), 2 * n_pairs * sizeof(int32_t));
+  for (size_t k = 0; k < n_members; ++k) { h_members[2 * k] = plan.members[k]; h_members[2 * k + 1] = sh.members[(size_t)plan.members[k]].geom; }
+  if (n_slots) memcpy(h_slots, plan.slots.data(), n_slots * sizeof(int32_t));
+  unsigned char* d = (unsigned char*)mu.d_staging;
+  HIP_TRY(hipMemcpyAsync((void*)d, h, bytes, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipEventRecord(mu.staged, stream));
+  const double* d_vertices = host_vertices ? (const double*)d : vertices;
+  const int32_t* d_pairs = (const int32_t*)(d + vert_bytes);
+  const int32_t* d_members = d_pairs + 2 * n_pairs;
+  const int32_t* d_slots = d_members + 2 * n_members;
+  rt::FlatTriangle* tris = (rt::FlatTriangle*)ds->view.triangles;
+  hipLaunchKernelGGL(k_set_triangles, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, d_pairs, (int)n_pairs, d_vertices, tris);
+  HIP_TRY(hipGetLastError());
+  for (int32_t bi : plan.bvhs) {
+    const BvhShadow& b = sh.bvhs[(size_t)bi];
+    if (b.n_leaves == 0 || b.n_nodes == 0) continue;  // a leaf code for a root: only its triangles changed
+    BvhRefitArgs a;
+    a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
+    a.refs = ds->view.refs + b.first_ref;
+    a.spheres = ds->view.spheres; a.rects = ds->view.rects; a.triangles = ds->view.triangles;
+    a.leaves = mu.d_leaves + 3 * (size_t)b.leaf_first;
+    a.node_parent = mu.d_node_parent + 2 * (size_t)b.node_first;
+    a.arrivals = mu.d_arrivals + (size_t)b.node_first;
+    a.n_leaves = b.n_leaves; a.node_base = b.node_base;
+    HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)b.n_nodes * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_refit_bvh, dim3((unsigned)((b.n_leaves + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    if (ds->wide.nodes4) {
+      hipLaunchKernelGGL(k_refit_wide, dim3((unsigned)((b.n_nodes + 255) / 256)), dim3(256), 0, stream, (const rt::FlatNode*)ds->view.nodes,
+                         (FlatNode4*)ds->wide.nodes4, b.node_base, b.n_nodes);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (n_members) {
+    hipLaunchKernelGGL(k_member_local_boxes, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, stream, d_members, (int)n_members,
+                       ds->view.entries, ds->view.nodes, ds->view.refs, ds->view.spheres, ds->view.rects, ds->view.triangles, (double*)u.d_local_box);
+    HIP_TRY(hipGetLastError());
+    mu.local_box_stale = true;
+    for (int32_t t : plan.trees) {
+      const rtx_status st = launch_instance_refit(ds, u.shadow.trees[(size_t)t], stream);
+      if (st != RTX_OK) return st;
+    }
+  }
+  if (n_slots) {
+    hipLaunchKernelGGL(k_top_triangle_boxes, dim3(1), dim3(256), 0, stream, d_slots, (int)n_slots, ds->view.entries, ds->view.top_level,
+                       ds->view.triangles, (float*)ds->view.top_box32, (WorldDesc*)ds->world.desc);
+    HIP_TRY(hipGetLastError());
+  }
+  return RTX_OK;
+}

@@ -35,6 +35,7 @@
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
+#include "../host/set_triangles.hpp"
 #else
 // The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports its upload and its
 // table of scene operations (f32_bridge.hpp) and render.hip proper owns the handles.
@@ -164,6 +165,7 @@ struct SceneUpdate {
   UpdateShadow shadow;              // host: the slots' chains, the instance trees and their parent tables
   std::vector<double> local_box;    // host: FlatScene::member_local_box (an update's new boxes are checked before anything is enqueued)
   size_t n_entries = 0, n_nodes = 0, n_motion = 0, n_desc = 0;  // element counts of the arrays an update writes (rtx_device_scene_array)
+  size_t n_triangles = 0, n_top = 0;
   DeviceBuffer<double> d_local_box;
   DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
@@ -187,6 +189,21 @@ struct SceneUpdate {
   DeviceBuffer<unsigned char> r_sort_temp;      // the radix sort's temporary storage, grown on demand
 };
 
+#ifndef RTX_F32_TU
+// rtx_scene_set_triangles (mesh_update.inc): the shadow of the upload's meshes and what the device keeps of it.  f64 scenes only.
+struct MeshUpdate {
+  MeshShadow shadow;                             // host: id -> flat triangles, the BVHs' leaves and parent tables, members, plain slots
+  bool uploaded = false;                         // the tables below are resident: done by the first update
+  DeviceBuffer<int32_t> d_leaves, d_node_parent; // MeshShadow::leaves, ::node_parent
+  DeviceBuffer<unsigned int> d_arrivals;         // one counter per BVH node
+  DeviceBuffer<unsigned char> d_staging;         // one call's vertices (host entry) and index lists
+  void* h_staging = nullptr;                     // pinned; `staged` marks the end of the copy out of it
+  size_t h_staging_bytes = 0;
+  hipEvent_t staged = nullptr;
+  bool local_box_stale = false;                  // SceneUpdate::local_box lags behind d_local_box (scene_update.inc reads it back)
+};
+#endif
+
 struct DeviceScene {
   int device = -1;
   std::vector<DeviceBuffer<void>> allocations;  // the uploaded arrays
@@ -203,6 +220,9 @@ struct DeviceScene {
   WalkTuning walk;
   rt::LightView lights = {nullptr, nullptr, 0, 0};  // next-event estimation's light table (k_trace_nee), uploaded with the scene
   SceneUpdate upd;
+#ifndef RTX_F32_TU
+  MeshUpdate mesh;
+#endif
 };
 
 #define HIP_TRY(expr)                                                                      \
@@ -230,9 +250,15 @@ static rtx_status upload_array(DeviceScene* ds, const std::vector<T>& v, const T
 
 // Releases what is not device memory; the buffers go with the DeviceScene.
 static void free_scene_update(SceneUpdate* u);
+#ifndef RTX_F32_TU
+static void free_mesh_update(MeshUpdate* m);
+#endif
 static void free_device_scene(DeviceScene* ds) {
   if (!ds) return;
   free_scene_update(&ds->upd);
+#ifndef RTX_F32_TU
+  free_mesh_update(&ds->mesh);
+#endif
   Workspace& ws = ds->ws;
   if (ws.wave_host_ctrl) (void)hipHostFree(ws.wave_host_ctrl);
   for (int i = 0; i < 2; ++i)
@@ -313,6 +339,9 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 static size_t stack_bytes(uint32_t levels);
 static void plan_world_stacks(DeviceScene* ds);
 #include "scene_rebuild.inc" // k_member_boxes .. k_rebuild_emit: a new topology for an instance tree of a resident scene; its cost
+#ifndef RTX_F32_TU
+#include "mesh_update.inc"   // k_set_triangles .. k_top_triangle_boxes: new vertices for triangles of a resident scene, BVHs refitted (f64 only)
+#endif
 #include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
 // ------------------------------------------------------------------ launcher
@@ -1662,6 +1691,30 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
   const rtx_status st = check_set_transforms("rtx_scene_set_transforms", s, updates, n, &resolved);
   if (st != RTX_OK || n == 0) return st;
   return s->ops->set_transforms(s->device_scene, resolved.data(), n, (hipStream_t)hip_stream);
+}
+
+// ---- deforming meshes (mesh_update.inc).  The checks shared with rtx_flat_set_triangles (host/set_triangles.hpp) come first,
+// against the shadow the scene kept from its upload; nothing is enqueued before every check has passed.
+static rtx_status scene_set_triangles_any(const char* who, rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, bool host_vertices,
+                                          void* hip_stream) {
+  std::string err;
+  if (s && s->f32) {
+    set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 vertices of the untouched "
+              "triangles in touched leaves. Update the flat scene with rtx_flat_set_triangles and upload it again with rtx_scene_upload_f32");
+    return RTX_EUNSUPPORTED;
+  }
+  const MeshShadow* sh = s ? &scene_device(s)->mesh.shadow : nullptr;
+  if (!check_triangle_ids(who, s, sh, ids, n, vertices, &err)) { set_error(err); return RTX_EINVAL; }
+  if (!host_vertices && ((uintptr_t)vertices & 7)) { set_error(std::string(who) + ": d_vertices is not 8-byte aligned"); return RTX_EINVAL; }
+  if (n == 0) return RTX_OK;
+  if (host_vertices && !check_vertices_finite(who, vertices, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return scene_set_triangles_impl(scene_device(s), who, ids, n, vertices, host_vertices, (hipStream_t)hip_stream);
+}
+rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream) {
+  return scene_set_triangles_any("rtx_scene_set_triangles", s, ids, n, vertices, true, hip_stream);
+}
+rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream) {
+  return scene_set_triangles_any("rtx_scene_set_triangles_device", s, ids, n, d_vertices, false, hip_stream);
 }
 
 // ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands

@@ -135,6 +135,10 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   u.local_box = fs.member_local_box;
   u.n_entries = fs.entries.size(); u.n_nodes = fs.nodes.size(); u.n_motion = fs.motion32.size();
   u.n_desc = fs.top_level.size();
+  u.n_triangles = fs.triangles.size(); u.n_top = fs.top_box32.size() / 6;
+#ifndef RTX_F32_TU
+  ds->mesh.shadow = build_mesh_shadow(fs, u.shadow);  // rtx_scene_set_triangles (mesh_update.inc); its tables go up with the first update
+#endif
   if (fs.features & rt::F_INSTANCE)
     for (const rt::FlatEntry& e : fs.entries) u.n_desc += e.kind == rt::ENTRY_INSTANCE ? 1 : 0;
   if (!u.shadow.broken.empty() || u.shadow.trees.empty()) return RTX_OK;
@@ -161,16 +165,52 @@ static void free_scene_update(SceneUpdate* u) {
   u->h_staging = nullptr;
   u->staged = nullptr;
 }
+#ifndef RTX_F32_TU
+static void free_mesh_update(MeshUpdate* m) {
+  if (m->h_staging) (void)hipHostFree(m->h_staging);
+  if (m->staged) (void)hipEventDestroy(m->staged);
+  m->h_staging = nullptr;
+  m->staged = nullptr;
+}
+#endif
+
+// Instance tree t refitted on `stream` from d_local_box and the ops now in `entries` (also mesh_update.inc's last step).
+static rtx_status launch_instance_refit(DeviceScene* ds, const TreeShadow& t, hipStream_t stream) {
+  SceneUpdate& u = ds->upd;
+  RefitArgs a;
+  a.entries = ds->view.entries; a.top_level = ds->view.top_level;
+  a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
+  a.local_box = u.d_local_box + 6 * (size_t)t.member_first;
+  a.leaf_parent = u.d_leaf_parent + 2 * (size_t)t.member_first;
+  a.node_parent = u.d_node_parent + 2 * (size_t)t.node_first;
+  a.arrivals = u.d_arrivals + (size_t)t.node_first;
+  a.slot_ops64 = u.d_slot_ops64;
+  a.first_slot = t.first_slot; a.n_slots = t.n_slots; a.node_base = t.node_base;
+  HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)t.n_nodes * sizeof(unsigned int), stream));
+  hipLaunchKernelGGL(k_refit_instance_tree, dim3((unsigned)((t.n_slots + 255) / 256)), dim3(256), 0, stream, a);
+  HIP_TRY(hipGetLastError());
+  return RTX_OK;
+}
 
 // `resolved` (host memory, n > 0) has passed check_slot_ops_shape.  Every check against the scene comes first; then one copy,
 // k_set_slot_ops and one k_refit_instance_tree per tree that holds an updated member, all on `stream`.
 static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* resolved, int64_t n, hipStream_t stream) {
   SceneUpdate& u = ds->upd;
   std::string err;
-  if (!check_slot_ops_scene("rtx_scene_set_transforms", u.shadow, u.local_box.data(), resolved, n, &err)) { set_error(err); return RTX_EINVAL; }
   int cur = -1;
   HIP_TRY(hipGetDevice(&cur));
   if (cur != ds->device) { set_error("rtx_scene_set_transforms: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+#ifndef RTX_F32_TU
+  if (ds->mesh.local_box_stale) {
+    // rtx_scene_set_triangles* (either entry) recomputed members' local boxes on the device only -- the host holds neither the
+    // refitted nodes nor the untouched primitives of a touched member -- and the check below reads the host copy: the FIRST
+    // set_transforms after such an update waits for the device once and reads the boxes back (include/rtx_abi.h says so)
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(u.local_box.data(), (const double*)u.d_local_box, u.local_box.size() * sizeof(double), hipMemcpyDeviceToHost));
+    ds->mesh.local_box_stale = false;
+  }
+#endif
+  if (!check_slot_ops_scene("rtx_scene_set_transforms", u.shadow, u.local_box.data(), resolved, n, &err)) { set_error(err); return RTX_EINVAL; }
   // the pinned staging buffer is this scene's own: the copy of the previous update must have left it
   if (!u.staged) HIP_TRY(hipEventCreateWithFlags(&u.staged, hipEventDisableTiming));
   else HIP_TRY(hipEventSynchronize(u.staged));
@@ -200,19 +240,8 @@ static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* r
   HIP_TRY(hipGetLastError());
   for (size_t k = 0; k < u.shadow.trees.size(); ++k) {
     if (!touched[k]) continue;
-    const TreeShadow& t = u.shadow.trees[k];
-    RefitArgs a;
-    a.entries = ds->view.entries; a.top_level = ds->view.top_level;
-    a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
-    a.local_box = u.d_local_box + 6 * (size_t)t.member_first;
-    a.leaf_parent = u.d_leaf_parent + 2 * (size_t)t.member_first;
-    a.node_parent = u.d_node_parent + 2 * (size_t)t.node_first;
-    a.arrivals = u.d_arrivals + (size_t)t.node_first;
-    a.slot_ops64 = u.d_slot_ops64;
-    a.first_slot = t.first_slot; a.n_slots = t.n_slots; a.node_base = t.node_base;
-    HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)t.n_nodes * sizeof(unsigned int), stream));
-    hipLaunchKernelGGL(k_refit_instance_tree, dim3((unsigned)((t.n_slots + 255) / 256)), dim3(256), 0, stream, a);
-    HIP_TRY(hipGetLastError());
+    const rtx_status st = launch_instance_refit(ds, u.shadow.trees[k], stream);
+    if (st != RTX_OK) return st;
   }
   return RTX_OK;
 }
@@ -228,6 +257,8 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 2: p = ds->view.nodes32; have = u.n_nodes * sizeof(rt::FlatNode32); break;
     case 3: p = ds->view.motion32; have = u.n_motion * sizeof(rt::FlatMotion32); break;
     case 4: p = ds->world.desc; have = u.n_desc * sizeof(WorldDesc); break;
+    case 10: p = ds->view.triangles; have = u.n_triangles * sizeof(rt::FlatTriangle); break;
+    case 11: p = ds->view.top_box32; have = u.n_top * 6 * sizeof(float); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
     case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }

@@ -42,6 +42,11 @@ struct FlatScene {
   // The f32 side of the seam only (host/f32_layout.hpp fills it, an f64 flat leaves it empty): the ops of every top-level slot in
   // f64, RT_MAX_XFORM_OPS per slot, because the f32 scene's own entries hold them narrowed and its refit must start from doubles.
   std::vector<rt::XformOp64> slot_ops64;
+  // What rtx_*_set_triangles names a triangle by (host/set_triangles.hpp): per flat triangle, the ordinal of its first emission
+  // by the flattener -- array order is leaf order and a shared triangle has private copies, each carrying its original's id.
+  std::vector<int32_t> triangle_id;
+  // Per graph hittable at the time of the flatten: the id of an emitted triangle, -1 for anything else (rtx_flat_triangle_ids).
+  std::vector<int32_t> handle_triangle_id;
 
   // pointers into the vectors above (host memory)
   rt::SceneView view() const {

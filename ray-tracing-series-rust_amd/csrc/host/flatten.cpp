@@ -18,6 +18,7 @@
 #include <cstring>
 #include "../core/geometry.hpp"
 #include "../core/member_box.hpp"
+#include "../core/prim_box.hpp"
 #include "../core/shading.hpp"
 #include "flat_scene.hpp"
 
@@ -44,11 +45,14 @@ struct Flattener {
   BuildOptions opt;
   std::string err;
   std::vector<int64_t> prim_of;  // graph hittable -> PrimRef already emitted (-1: not yet)
+  int32_t next_triangle_id = 0;
   std::vector<int32_t> bvh_entry_of;  // graph BVH hittable -> its entry (-1: not yet): a reused handle (the reference holds
                                       // objects as Arc, so one BvhNode may sit under several Translates) is emitted once
 
   Flattener(const SceneGraph& gg, FlatScene& o, const BuildOptions& op)
-      : g(gg), out(o), opt(op), prim_of(gg.hittables.size(), -1), bvh_entry_of(gg.hittables.size(), -1) {}
+      : g(gg), out(o), opt(op), prim_of(gg.hittables.size(), -1), bvh_entry_of(gg.hittables.size(), -1) {
+    out.handle_triangle_id.assign(gg.hittables.size(), -1);
+  }
 
   bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
 
@@ -89,6 +93,9 @@ struct Flattener {
         for (int i = 0; i < 3; ++i) { t.v0[i] = o.f[i]; t.v1[i] = o.f[3 + i]; t.v2[i] = o.f[6 + i]; t.normal[i] = o.f[9 + i]; }
         t.mat = o.mat; t.pad = 0;
         out.triangles.push_back(t);
+        // its id: the ordinal of this first emission (FlatScene::triangle_id); every later copy or move carries it along
+        out.handle_triangle_id[(size_t)h] = next_triangle_id;
+        out.triangle_id.push_back(next_triangle_id++);
         ref = rt::make_primref(rt::PRIM_TRIANGLE, (uint32_t)out.triangles.size() - 1);
         break;
       }
@@ -167,14 +174,6 @@ struct Flattener {
   void prim_box(rt::PrimRef ref, double time0, double time1, double* b) const {
     uint32_t idx = rt::primref_index(ref);
     switch (rt::primref_type(ref)) {
-      case rt::PRIM_SPHERE: {  // hit.rs:239-244
-        const rt::FlatSphere& s = out.spheres[idx];
-        const double ar = std::fabs(s.radius);
-        Vec3 c = rt::v3(s.cx, s.cy, s.cz), r = rt::v3(ar, ar, ar);
-        Vec3 lo = c - r, hi = c + r;
-        b[0] = lo.x; b[1] = lo.y; b[2] = lo.z; b[3] = hi.x; b[4] = hi.y; b[5] = hi.z;
-        break;
-      }
       case rt::PRIM_MOVING_SPHERE: {  // hit.rs:317-327
         const rt::FlatMovingSphere& s = out.moving_spheres[idx];
         const double ar = std::fabs(s.radius);
@@ -195,21 +194,9 @@ struct Flattener {
         b[3] = std::fmax(hi0.x, hi1.x); b[4] = std::fmax(hi0.y, hi1.y); b[5] = std::fmax(hi0.z, hi1.z);
         break;
       }
-      case rt::PRIM_RECT: {  // hit.rs:503-508, 568-573, 633-638 (+-0.0001 on the thin axis)
-        const rt::FlatRect& q = out.rects[idx];
-        if (q.axis == rt::RECT_XY) { b[0] = q.a0; b[1] = q.b0; b[2] = q.k - 0.0001; b[3] = q.a1; b[4] = q.b1; b[5] = q.k + 0.0001; }
-        else if (q.axis == rt::RECT_XZ) { b[0] = q.a0; b[1] = q.k - 0.0001; b[2] = q.b0; b[3] = q.a1; b[4] = q.k + 0.0001; b[5] = q.b1; }
-        else { b[0] = q.k - 0.0001; b[1] = q.a0; b[2] = q.b0; b[3] = q.k + 0.0001; b[4] = q.a1; b[5] = q.b1; }
+      default:  // static spheres, rectangles, triangles: core/prim_box.hpp, shared with the refits of rtx_*_set_triangles
+        rt::static_prim_box(ref, out.spheres.data(), out.rects.data(), out.triangles.data(), b);
         break;
-      }
-      default: {  // hit.rs:164-177
-        const rt::FlatTriangle& t = out.triangles[idx];
-        for (int a = 0; a < 3; ++a) {
-          b[a] = std::fmin(std::fmin(t.v0[a], t.v1[a]), t.v2[a]);
-          b[3 + a] = std::fmax(std::fmax(t.v0[a], t.v1[a]), t.v2[a]);
-        }
-        break;
-      }
     }
   }
 
@@ -319,13 +306,15 @@ struct Flattener {
         }
         if (exclusive) {
           std::vector<rt::FlatTriangle> moved(in_leaf_order.size());
-          for (size_t k = 0; k < in_leaf_order.size(); ++k) moved[k] = out.triangles[in_leaf_order[k]];
-          for (size_t k = 0; k < in_leaf_order.size(); ++k) out.triangles[sorted_idx[k]] = moved[k];
+          std::vector<int32_t> moved_id(in_leaf_order.size());
+          for (size_t k = 0; k < in_leaf_order.size(); ++k) { moved[k] = out.triangles[in_leaf_order[k]]; moved_id[k] = out.triangle_id[in_leaf_order[k]]; }
+          for (size_t k = 0; k < in_leaf_order.size(); ++k) { out.triangles[sorted_idx[k]] = moved[k]; out.triangle_id[sorted_idx[k]] = moved_id[k]; }
         } else {
           const uint32_t base = (uint32_t)out.triangles.size();
           for (size_t k = 0; k < in_leaf_order.size(); ++k) {
             const rt::FlatTriangle copy = out.triangles[in_leaf_order[k]];
             out.triangles.push_back(copy);
+            out.triangle_id.push_back(out.triangle_id[in_leaf_order[k]]);
             sorted_idx[k] = base + (uint32_t)k;
           }
         }

@@ -1,0 +1,276 @@
+"""rtx_flat_set_triangles and rtx_flat_triangle_ids on the CPU: new vertices for named triangles of a flat scene, its BVHs
+refitted with their topology kept.
+
+The judge is always the FRESH flat scene -- the same world built from scratch with the displaced vertices and flattened
+(tests/deform_cases.py) -- and the oracle, never the code under test.  Every test calls a symbol the library did not have
+before.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from cast_rays_cases import same_bits
+from deform_cases import (CASES, call_set_triangles, refusals, FLAT_ARRAYS, MOTION32, NODE, NODE32, SHEET_LEAVES, TRIANGLE, cam_cfg, count_leaves, instanced, leaf_boxes, movers, narrow,
+                          seeded_rays, sheet, sheet_tris_for_leaves, tree_roots, triangles_by_id, update_of)
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+ORACLE_ARRAYS = ("refs", "spheres", "rects")  # no hook of the library's reads these: the oracle's view of the same FlatScene does
+
+
+def _arrays(flat):
+    """Every array an update may or may not touch, as bytes.  (Tests that call this take the `orc` fixture, which builds the oracle.)"""
+    import oracle_py
+    out = {name: flat.array(name) for name in FLAT_ARRAYS}
+    for name in ORACLE_ARRAYS:
+        out[name] = oracle_py.flat_array(flat.arrays_ptr(), name)[0]
+    return out
+
+
+def _same_arrays(flat, first):
+    now = _arrays(flat)
+    return all(np.array_equal(now[k], first[k]) for k in first)
+
+
+def _records(orc, flat, o, d):
+    out = np.zeros((len(o), 11))
+    for r in range(len(o)):
+        rec = orc.core_world_hit(flat.arrays_ptr(), tuple(o[r]), tuple(d[r]), 0.25, 0.001, float("inf"), rng_seed=1 + r)
+        if rec is not None:
+            out[r] = [1.0, rec["t"], *rec["p"], *rec["normal"], rec["u"], rec["v"], float(rec["front_face"])]
+    return out
+
+
+def _same_topology(now, first):
+    n, n0 = now["nodes"].view(NODE), first["nodes"].view(NODE)
+    m, m0 = now["nodes32"].view(NODE32), first["nodes32"].view(NODE32)
+    assert np.array_equal(n["child"], n0["child"]) and np.array_equal(n["pad"], n0["pad"])
+    assert np.array_equal(m["child"], m0["child"]) and np.array_equal(m["axis"], m0["axis"]) and np.array_equal(m["pad"], m0["pad"])
+    for k in ("entries", "top_level", "triangle_id") + ORACLE_ARRAYS:
+        assert np.array_equal(now[k], first[k]), k
+
+
+def _check_against_fresh(rtsr, orc, flat, fresh, first, audit=None):
+    """Everything the issue asks of an updated flat scene but the rays and the frame."""
+    now, judge = _arrays(flat), _arrays(fresh)
+    assert triangles_by_id(flat) == triangles_by_id(fresh)
+    assert np.array_equal(flat.array("triangles").view(TRIANGLE)["mat"], first["triangles"].view(TRIANGLE)["mat"])
+    rc, depth = orc.audit_flat_exact(flat.arrays_ptr(), **(audit or {"ask_first": True}))
+    assert rc == 0
+    _same_topology(now, first)
+    nodes, n32 = now["nodes"].view(NODE), now["nodes32"].view(NODE32)
+    assert np.array_equal(n32["lo"], narrow(nodes["bmin"], up=False)) and np.array_equal(n32["hi"], narrow(nodes["bmax"], up=True))
+    assert (len(now["motion32"]) > 0) == (len(first["motion32"]) > 0)
+    if len(now["motion32"]):
+        # where the first flatten kept a node's static box with zero slopes (every node outside a BVH of movers), so does the update
+        mo, mo0, n32_0 = now["motion32"].view(MOTION32), first["motion32"].view(MOTION32), first["nodes32"].view(NODE32)
+        static = np.array([np.array_equal(mo0["lo0"][i], n32_0["lo"][i]) and not mo0["dlo"][i].any() and not mo0["dhi"][i].any() for i in range(len(mo0))])
+        assert static.any()
+        assert np.array_equal(mo["lo0"][static], n32["lo"][static]) and np.array_equal(mo["hi0"][static], n32["hi"][static])
+        assert not mo["dlo"][static].any() and not mo["dhi"][static].any()
+        assert mo[~static].tobytes() == mo0[~static].tobytes()
+    # instance trees: local boxes and leaf boxes matched by slot (a fresh build may choose another topology above the same leaves)
+    assert np.array_equal(now["member_local_box"], judge["member_local_box"])
+    for root, fresh_root in zip(tree_roots(flat), tree_roots(fresh)):
+        leaves, _ = leaf_boxes(nodes, root)
+        fresh_leaves, _ = leaf_boxes(judge["nodes"].view(NODE), fresh_root)
+        assert sorted(leaves) == sorted(fresh_leaves)
+        for slot in leaves:
+            assert leaves[slot][0].tobytes() == fresh_leaves[slot][0].tobytes() and leaves[slot][1].tobytes() == fresh_leaves[slot][1].tobytes(), slot
+    assert np.array_equal(now["top_box32"], judge["top_box32"])
+    return depth
+
+
+@pytest.mark.parametrize("name", sorted(CASES))
+def test_an_updated_flat_scene_is_the_freshly_built_one(rtsr, orc, name):
+    case, moved = CASES[name](rtsr, False), CASES[name](rtsr, True)
+    flat, fresh = case.flatten(), moved.flatten()
+    first = _arrays(flat)
+    _, depth0 = orc.audit_flat_exact(flat.arrays_ptr(), ask_first=True)
+    if name == "line40":
+        assert depth0 >= 9
+    ids, verts = update_of(case, flat)
+    flat.set_triangles(ids, verts)
+    assert not np.array_equal(flat.array("nodes"), first["nodes"]) and not np.array_equal(flat.array("triangles"), first["triangles"])
+    assert _check_against_fresh(rtsr, orc, flat, fresh, first) == depth0
+    lit = instanced(rtsr, True, hoisted=True) if name == "instanced" else moved  # (the literal oracle has no instance tree)
+    _rays_and_frames(rtsr, orc, case, flat, fresh, lit, line=name == "line40")
+    # back to rest: every array as the first flatten left it, byte for byte
+    flat.set_triangles(*update_of(case, flat, moved=False))
+    back = _arrays(flat)
+    for k in first:
+        assert np.array_equal(back[k], first[k]), k
+
+
+def _rays_and_frames(rtsr, orc, case, flat, fresh, lit, line=False, seed=17):
+    """2 000 seeded rays through core_world_hit on the updated flat scene equal those on the fresh one bit for bit; a 48 x 32 x
+    4 spp O2 frame of the updated scene equals O2 of the fresh scene AND O1 of the fresh graph `lit` (which also proves the
+    case free of ties)."""
+    o, d = seeded_rays(2000, seed) if not line else seeded_rays(2000, seed, lo=(0.0, 0.5, 0.0), hi=(75.0, 22.0, 45.0))
+    want = _records(orc, fresh, o, d)
+    assert 200 < int(want[:, 0].sum())
+    got = _records(orc, flat, o, d)
+    assert same_bits(got, want).all(), "%d rays differ from the fresh scene" % int((~same_bits(got, want)).sum())
+    cam, cfg, h = cam_cfg(rtsr, case)
+    assert (cfg.image_width, h, cfg.samples_per_pixel) == (48, 32, 4)
+    a, a8 = orc.o2_render(flat.arrays_ptr(), cam, cfg, h, threads=4)
+    f, f8 = orc.o2_render(fresh.arrays_ptr(), cam, cfg, h, threads=4)
+    assert f.std() > 0.01 and np.array_equal(a, f) and np.array_equal(a8, f8)
+    l, l8 = orc.o1_render(lit.builder.graph_ptr(), lit.world, cam, cfg, h, threads=4)
+    assert np.array_equal(a, l) and np.array_equal(a8, l8)
+
+
+@pytest.mark.parametrize("max_leaf", [1, 0])
+@pytest.mark.parametrize("leaves", SHEET_LEAVES)
+def test_sheets_by_their_number_of_leaves(rtsr, orc, leaves, max_leaf):
+    n = sheet_tris_for_leaves(rtsr, leaves, max_leaf)
+    case, moved = sheet(rtsr, False, n, max_leaf), sheet(rtsr, True, n, max_leaf)
+    flat, fresh = case.flatten(), moved.flatten()
+    assert count_leaves(flat) == leaves
+    first = _arrays(flat)
+    _, depth0 = orc.audit_flat_exact(flat.arrays_ptr(), ask_first=True)
+    flat.set_triangles(*update_of(case, flat))
+    assert not np.array_equal(flat.array("nodes"), first["nodes"])
+    assert _check_against_fresh(rtsr, orc, flat, fresh, first) == depth0
+    _rays_and_frames(rtsr, orc, case, flat, fresh, moved, seed=leaves)
+    flat.set_triangles(*update_of(case, flat, moved=False))
+    assert _same_arrays(flat, first)
+
+
+def test_two_triangles_at_max_leaf_two(rtsr, orc):
+    """2 triangles at max_leaf 2: the smallest BVH.  build_bvh forces one inner node even when everything fits one leaf
+    (bvh_build.cpp: "so the root is a node"), so the flattener never emits a leaf code for a root: exactly ONE node holding two
+    one-triangle leaves.  (The leaf-code root the walkers and the update also accept is exercised where it can be made: by
+    hand, in tests/set_triangles_host_check.cpp.)"""
+    case, moved = sheet(rtsr, False, 2, 2), sheet(rtsr, True, 2, 2)
+    flat, fresh = case.flatten(), moved.flatten()
+    first = _arrays(flat)
+    assert len(first["nodes"]) // NODE.itemsize == 1 and count_leaves(flat) == 2
+    flat.set_triangles(*update_of(case, flat))
+    _check_against_fresh(rtsr, orc, flat, fresh, first)
+    _rays_and_frames(rtsr, orc, case, flat, fresh, moved, seed=2)
+    flat.set_triangles(*update_of(case, flat, moved=False))
+    assert _same_arrays(flat, first)
+
+
+@pytest.mark.parametrize("name", ["mixed", "shared", "instanced"])
+def test_partial_updates(rtsr, orc, name):
+    """One id, every 7th id, then two updates in a row: each judged by the scene built from scratch with just those displaced."""
+    case = CASES[name](rtsr, False)
+    flat = case.flatten()
+    first = _arrays(flat)
+    n_all = len(update_of(case, flat)[0])
+    for sel, kw in ((lambda k: k == 3, {"only": 3}), (lambda k: k % 7 == 0, {"every": 7})):
+        ids, verts = update_of(case, flat, **kw)
+        assert 0 < len(ids) < n_all
+        flat.set_triangles(ids, verts)
+        fresh = CASES[name](rtsr, sel).flatten()
+        _check_against_fresh(rtsr, orc, flat, fresh, first)
+        o, d = seeded_rays(300, 5)
+        assert same_bits(_records(orc, flat, o, d), _records(orc, fresh, o, d)).all()
+        flat.set_triangles(*update_of(case, flat, moved=False, **kw))
+        assert _same_arrays(flat, first)
+    # two updates in a row: the second moves what the first left
+    ids, verts = update_of(case, flat)
+    half = len(ids) // 2
+    flat.set_triangles(ids[:half], verts[:half])
+    _check_against_fresh(rtsr, orc, flat, CASES[name](rtsr, lambda k: k < half).flatten(), first)
+    flat.set_triangles(ids[half:], verts[half:])
+    _check_against_fresh(rtsr, orc, flat, CASES[name](rtsr, True).flatten(), first)
+
+
+def test_triangle_ids_name_a_mesh_face_by_face(rtsr):
+    case = CASES["shared"](rtsr, False)
+    flat = case.flatten()
+    by_id = triangles_by_id(flat)
+    assert sorted(by_id) == list(range(len(by_id)))
+    seen = []
+    for h, rest, _ in case.parts:
+        ids = flat.triangle_ids(case.builder, h)
+        assert ids.dtype == np.int32 and len(ids) == len(rest)
+        for k, i in enumerate(ids):  # face k's flat triangle holds face k's vertices
+            assert np.frombuffer(by_id[int(i)], dtype=TRIANGLE)["v"][0].tobytes() == rest[k].tobytes()
+        seen += list(ids)
+    assert sorted(seen) == list(range(len(by_id)))  # the parts' ids together: a permutation of all ids
+    n_flat = len(flat.array("triangle_id")) // 4
+    # the BVH shares `both` with a slot and lists `twice` twice, so it holds private copies of all 13 of its references
+    assert n_flat == len(by_id) + 13
+    b, hs = case.builder, case.handles
+    id_of = lambda h: int(flat.triangle_ids(b, h)[0])
+    # a handle listed twice yields its id twice; a BvhNode lists what its list lists; the world lists `both` at both places
+    assert list(flat.triangle_ids(b, hs["pair"])) == [id_of(hs["twice"])] * 2
+    in_bvh = list(flat.triangle_ids(b, hs["bvh"]))
+    assert in_bvh == list(flat.triangle_ids(b, hs["members"])) == list(flat.triangle_ids(b, case.parts[0][0])) + [id_of(hs["both"])] + [id_of(hs["twice"])] * 2
+    assert list(flat.triangle_ids(b, case.world)) == [id_of(hs["both"])] + in_bvh + [id_of(hs["alone"])]
+    # an object made after the flatten is one this flat scene did not flatten, even a list of triangles it knows
+    with pytest.raises(rtsr.RtxError) as e:
+        flat.triangle_ids(b, b.hittable_list([hs["twice"]]))
+    assert "after this flat scene was flattened" in str(e.value)
+    assert rtsr.lib.rtx_flat_triangle_ids(flat.ptr, b.ptr, 10 ** 6, None, 0) == -1 and "handle" in rtsr.last_error()
+    assert rtsr.lib.rtx_flat_triangle_ids(None, b.ptr, 0, None, 0) == -1
+    assert rtsr.lib.rtx_flat_triangle_ids(flat.ptr, None, 0, None, 0) == -1
+    # a cap smaller than the count: that many written, the count returned
+    out = (C.c_int32 * 2)(-7, -7)
+    n = rtsr.lib.rtx_flat_triangle_ids(flat.ptr, b.ptr, case.parts[0][0], out, 1)
+    assert n == len(case.parts[0][1]) and out[0] >= 0 and out[1] == -7
+    # one triangle handle: its id alone
+    assert len(flat.triangle_ids(b, case.parts[1][0])) == 1
+
+
+def test_every_refusal_leaves_the_flat_scene_unchanged(rtsr, orc):
+    case = CASES["mixed"](rtsr, False)
+    flat = case.flatten()
+    before = _arrays(flat)
+    n_ids = len(triangles_by_id(flat))
+    cases = refusals(n_ids)
+    assert len(cases) == 8
+    for name, ids, n, verts, word, _ in cases:
+        st = call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, ids, n, verts)
+        assert st == rtsr.RTX_EINVAL, name
+        assert "rtx_flat_set_triangles" in rtsr.last_error() and word in rtsr.last_error(), (name, rtsr.last_error())
+        assert _same_arrays(flat, before), name
+    assert call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, None, [0], None, np.ones(9)) == rtsr.RTX_EINVAL and "scene is NULL" in rtsr.last_error()
+    assert call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, [0], 0, np.ones(9)) == rtsr.RTX_OK  # n = 0: nothing to do
+    assert _same_arrays(flat, before)
+    # a BVH that holds a MovingSphere: its time-aware slopes would have to be derived again
+    mv = movers(rtsr)
+    mflat = mv.flatten()
+    mbefore = _arrays(mflat)
+    ids, verts = update_of(mv, mflat)
+    with pytest.raises(rtsr.RtxError) as e:
+        mflat.set_triangles(ids, verts)
+    assert e.value.status == rtsr.RTX_EUNSUPPORTED and "MovingSphere" in str(e.value)
+    assert _same_arrays(mflat, mbefore)
+    # the Python layer counts the vertices before the library sees them
+    with pytest.raises(ValueError):
+        flat.set_triangles([0, 1], np.ones(9))
+    # a good update after all the refusals still goes through
+    flat.set_triangles(*update_of(case, flat))
+    assert not np.array_equal(flat.array("nodes"), before["nodes"])
+
+
+def test_scene_entries_refuse_before_they_read_the_scene_arrays(rtsr):
+    """What needs no scene is checked first: NULLs and n < 0 on a scene pointer that is never dereferenced for them."""
+    good = np.ones(9)
+    for fn, who in ((rtsr.lib.rtx_scene_set_triangles, "rtx_scene_set_triangles"), (rtsr.lib.rtx_scene_set_triangles_device, "rtx_scene_set_triangles_device")):
+        assert call_set_triangles(rtsr, fn, None, [0], None, good, None) == rtsr.RTX_EINVAL and who + ": the scene is NULL" in rtsr.last_error()
+
+
+def test_host_update_is_clean_under_asan_and_ubsan(tmp_path):
+    """tests/set_triangles_host_check.cpp with the flattener and the builder under -fsanitize=address,undefined: full and
+    partial updates of a mixed BVH, a shared triangle and an instance tree against a fresh flatten, the refusals, and the
+    shadow's `broken` paths on hand-damaged arrays."""
+    host = os.path.join(ROOT, "ray-tracing-series-rust_amd", "csrc", "host")
+    exe = str(tmp_path / "set_triangles_host_check")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-fno-omit-frame-pointer",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Wno-unused-function", "-pthread",
+                    os.path.join(ROOT, "tests", "set_triangles_host_check.cpp"), os.path.join(host, "scene_graph.cpp"),
+                    os.path.join(host, "flatten.cpp"), os.path.join(host, "bvh_build.cpp"), "-o", exe], check=True)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:verify_asan_link_order=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    out = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert "set_triangles host check clean" in out.stdout and "runtime error" not in out.stderr and "AddressSanitizer" not in out.stderr
