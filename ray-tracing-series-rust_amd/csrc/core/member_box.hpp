@@ -1,7 +1,7 @@
 // The world box of one member of an instance tree, from its local box and its Translate / RotateY ops, and the outward
-// narrowing of a box plane to f32.  ONE text for the flattener (host/flatten.cpp), the host refit (host/set_transforms.hpp) and
-// the device refit (hip/scene_update.inc): a refitted tree is judged bit for bit against a tree flattened from scratch, so all
-// three must round alike.  Everything here is f64 arithmetic whatever rt::real is -- the f32 compilation refits from the same
+// narrowing of a box plane to f32.  ONE text for the flattener (host/flatten.cpp, which fills the ops itself: it is the judge of the rest), the host refit and rebuild (host/set_transforms.hpp, host/rebuild_instances.hpp) and the device's
+// (hip/scene_update.inc, hip/scene_rebuild.inc): a refitted tree is judged bit for bit against a tree flattened from scratch, so
+// all of them must round alike.  Everything here is f64 arithmetic whatever rt::real is -- the f32 compilation refits from the same
 // doubles and narrows last, as its converter does (host/f32_layout.hpp).
 //
 // Bit-exactness between the host and the device build rests on two things the build already pins for the whole core:
@@ -48,6 +48,31 @@ RT_HD void member_box_through_ops(const double* local, const XformOp64* ops, int
   }
   const double pad = mag * 0x1.0p-22;
   for (int a = 0; a < 3; ++a) { b[a] -= pad; b[3 + a] += pad; }
+}
+
+// The f64 ops of member slot `slot`, whose entry in the world list is S, into ops[RT_MAX_XFORM_OPS]; returns how many (0: the
+// member has no chain).  An f64 scene's entries hold them.  An f32 scene's went through a (float) cast, so it reads the f64 copy
+// it keeps beside them: slot_ops64, RT_MAX_XFORM_OPS per slot (NULL and never read in the f64 compilation).
+RT_HD int member_ops64(const FlatEntry& S, int32_t slot, const XformOp64* slot_ops64, XformOp64* ops) {
+  if (S.kind != ENTRY_XFORM) return 0;
+  const int n_ops = S.b < RT_MAX_XFORM_OPS ? S.b : RT_MAX_XFORM_OPS;
+  for (int k = 0; k < n_ops; ++k) {
+#ifdef RT_F32
+    ops[k] = slot_ops64[(size_t)slot * RT_MAX_XFORM_OPS + k];
+#else
+    ops[k].op = S.ops[k].op; ops[k].pad = 0;
+    for (int x = 0; x < 3; ++x) ops[k].v[x] = S.ops[k].v[x];
+#endif
+  }
+  return n_ops;
+}
+
+// The world box of that member NOW: its local box through the ops it has at this moment.  What every refit and rebuild, on the
+// host and on the device, starts from.
+RT_HD void member_world_box(const FlatEntry& S, int32_t slot, const XformOp64* slot_ops64, const double* local, double* b) {
+  XformOp64 ops[RT_MAX_XFORM_OPS];
+  const int n_ops = member_ops64(S, slot, slot_ops64, ops);
+  member_box_through_ops(local, ops, n_ops, b);
 }
 
 RT_HD bool box_is_finite(const double* b) {

@@ -66,3 +66,47 @@ class DeviceBuffer {
   T* p_ = nullptr;
   size_t bytes_ = 0;
 };
+
+// The one owner of a staging pair: a pinned host block, its device twin and the event that marks the end of the copy out of the
+// pinned block.  A call fills the block and copies it to the device on its stream; the next call must not write the block
+// before that copy has left it.  Same rules as DeviceBuffer: not copyable, freed once, in the destructor.
+class StagingBuffer {
+ public:
+  StagingBuffer() = default;
+  StagingBuffer(const StagingBuffer&) = delete;
+  StagingBuffer& operator=(const StagingBuffer&) = delete;
+  ~StagingBuffer() {
+    if (host_) (void)hipHostFree(host_);
+    if (copied_) (void)hipEventDestroy(copied_);
+  }
+
+  unsigned char* device() const { return device_; }
+
+  // Room for `bytes` on both sides and *host = the pinned block: waits for the previous copy to have left it, then grows the
+  // pinned side and the device side (DeviceBuffer::grow on `stream`).  Neither side keeps its contents.
+  hipError_t reserve(size_t bytes, hipStream_t stream, void** host) {
+    hipError_t e = copied_ ? hipEventSynchronize(copied_) : hipEventCreateWithFlags(&copied_, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    if (bytes > host_bytes_) {
+      if (host_) e = hipHostFree(host_);
+      host_ = nullptr;
+      host_bytes_ = 0;
+      if (e == hipSuccess) e = hipHostMalloc(&host_, bytes, hipHostMallocDefault);
+      if (e != hipSuccess) { host_ = nullptr; return e; }
+      host_bytes_ = bytes;
+    }
+    *host = host_;
+    return device_.grow(bytes, stream);
+  }
+  // The first `bytes` of the pinned block to the device on `stream`, and the event behind the copy.
+  hipError_t copy(size_t bytes, hipStream_t stream) {
+    const hipError_t e = hipMemcpyAsync((void*)device(), host_, bytes, hipMemcpyHostToDevice, stream);
+    return e != hipSuccess ? e : hipEventRecord(copied_, stream);
+  }
+
+ private:
+  void* host_ = nullptr;
+  size_t host_bytes_ = 0;
+  DeviceBuffer<unsigned char> device_;
+  hipEvent_t copied_ = nullptr;
+};

@@ -3,7 +3,8 @@
 //
 // New vertices for named triangles reach these device arrays and no other:
 //   triangles                       v0 v1 v2 and the normal of every flat copy of an id (k_set_triangles)
-//   nodes / nodes32 / motion32      every BVH that holds an updated triangle, refitted whole and bottom-up (k_refit_bvh)
+//   nodes / nodes32 / motion32      every BVH that holds an updated triangle, refitted whole and bottom-up (k_refit_bvh: a leaf's
+//                                   box, then scene_update.inc's refit_climb)
 //   nodes4                          the planes of every slot of those BVHs' wide records; which nodes the collapse opened is kept,
 //                                   so WidePlan::levels and every launch plan stand (k_refit_wide)
 //   d_local_box, then the instance tree above a touched member (k_member_local_boxes, k_refit_instance_tree of scene_update.inc)
@@ -42,11 +43,8 @@ struct BvhRefitArgs {
   int32_t n_leaves, node_base;
 };
 
-// One thread per leaf of ONE BVH -- every leaf, not only the touched ones: the thread unites its primitives' boxes, writes the
-// box where the leaf's parent keeps it and climbs.  The hand-off is k_refit_instance_tree's (scene_update.inc), which is
-// lbvh.hip's k_refit recipe: agent-scope stores of the f64 planes, a fence, an agent-scope arrival, a fence, agent-scope loads
-// of the sibling's planes -- a plain load of a box another CU stored can be served stale from this CU's L1.  Of the two threads
-// that reach a node the first leaves; unions are exact min / max, so the result does not depend on who arrives first.
+// One thread per leaf of ONE BVH -- every leaf, not only the touched ones: the union of its primitives' boxes, then the climb
+// (scene_update.inc: refit_climb).
 __global__ __launch_bounds__(256) void k_refit_bvh(BvhRefitArgs a) {
   const int l = (int)(blockIdx.x * 256u + threadIdx.x);
   if (l >= a.n_leaves) return;
@@ -54,35 +52,8 @@ __global__ __launch_bounds__(256) void k_refit_bvh(BvhRefitArgs a) {
   bvh_leaf_box(a.leaves[3 * (size_t)l], a.refs, a.spheres, a.rects, a.triangles, b);
   double lo[3], hi[3];
   for (int x = 0; x < 3; ++x) { lo[x] = b[x]; hi[x] = b[3 + x]; }
-  int32_t node = a.leaves[3 * (size_t)l + 1], c = a.leaves[3 * (size_t)l + 2];
-  for (;;) {
-    rt::FlatNode* nd = &a.nodes[node];
-    for (int x = 0; x < 3; ++x) {
-      __hip_atomic_store(&nd->bmin[c][x], lo[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(&nd->bmax[c][x], hi[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float l32 = rt::f32_narrow_down(lo[x]), h32 = rt::f32_narrow_up(hi[x]);
-      a.nodes32[node].lo[c][x] = l32;
-      a.nodes32[node].hi[c][x] = h32;
-      if (a.motion32) {  // a BVH without a moving sphere: its static box, no slope (flatten.cpp: build_motion_boxes)
-        a.motion32[node].lo0[c][x] = l32; a.motion32[node].hi0[c][x] = h32;
-        a.motion32[node].dlo[c][x] = 0.0f; a.motion32[node].dhi[c][x] = 0.0f;
-      }
-    }
-    const int32_t rel = node - a.node_base;
-    const int32_t parent = a.node_parent[2 * (size_t)rel], pc = a.node_parent[2 * (size_t)rel + 1];
-    if (parent < 0) return;  // the root: its two child boxes are the whole tree
-    __threadfence();
-    if (atomicAdd(&a.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
-    __threadfence();
-    for (int x = 0; x < 3; ++x) {
-      const double slo = __hip_atomic_load(&nd->bmin[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const double shi = __hip_atomic_load(&nd->bmax[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      lo[x] = rt::rt_fmin(lo[x], slo);
-      hi[x] = rt::rt_fmax(hi[x], shi);
-    }
-    node = parent;
-    c = pc;
-  }
+  const TreePiece t = {a.nodes, a.nodes32, a.motion32, a.node_parent, a.arrivals, a.node_base};
+  refit_climb(t, a.leaves[3 * (size_t)l + 1], a.leaves[3 * (size_t)l + 2], lo, hi);
 }
 
 // The f64 box the binary tree keeps for child code `code` below node i: the collapse (host/wide_tree.hpp) opens at most two
@@ -176,9 +147,8 @@ static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, con
   TrianglePlan plan;
   const rtx_status pst = plan_triangle_update(who, sh, ids, n, &plan, &err);
   if (pst != RTX_OK) { set_error(err); return pst; }
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error(std::string(who) + ": scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  const rtx_status dst = check_scene_device(ds, who, "was uploaded to");
+  if (dst != RTX_OK) return dst;
   if (!mu.uploaded) {
     if (!sh.leaves.empty()) HIP_TRY(mu.d_leaves.upload(sh.leaves.data(), sh.leaves.size()));
     if (!sh.node_parent.empty()) {
@@ -187,22 +157,13 @@ static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, con
     }
     mu.uploaded = true;
   }
-  // the pinned staging buffer is this scene's own: the copy of the previous update must have left it
-  if (!mu.staged) HIP_TRY(hipEventCreateWithFlags(&mu.staged, hipEventDisableTiming));
-  else HIP_TRY(hipEventSynchronize(mu.staged));
   // staging layout: [vertices, 72 B each (host entry only)] [pairs] [members: index, entry] [slots]
   const size_t vert_bytes = host_vertices ? (size_t)n * 9 * sizeof(double) : 0;
   const size_t n_pairs = plan.pairs.size() / 2, n_members = plan.members.size(), n_slots = plan.slots.size();
   const size_t bytes = vert_bytes + (2 * n_pairs + 2 * n_members + n_slots) * sizeof(int32_t);
-  if (bytes > mu.h_staging_bytes) {
-    if (mu.h_staging) HIP_TRY(hipHostFree(mu.h_staging));
-    mu.h_staging = nullptr;
-    mu.h_staging_bytes = 0;
-    HIP_TRY(hipHostMalloc(&mu.h_staging, bytes, hipHostMallocDefault));
-    mu.h_staging_bytes = bytes;
-  }
-  HIP_TRY(mu.d_staging.grow(bytes, stream));
-  unsigned char* h = (unsigned char*)mu.h_staging;
+  void* pinned = nullptr;
+  HIP_TRY(mu.staging.reserve(bytes, stream, &pinned));
+  unsigned char* h = (unsigned char*)pinned;
   if (host_vertices) memcpy(h, vertices, vert_bytes);
   int32_t* h_pairs = (int32_t*)(h + vert_bytes);
   int32_t* h_members = h_pairs + 2 * n_pairs;
@@ -210,9 +171,8 @@ static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, con
   memcpy(h_pairs, plan.pairs.data(), 2 * n_pairs * sizeof(int32_t));
   for (size_t k = 0; k < n_members; ++k) { h_members[2 * k] = plan.members[k]; h_members[2 * k + 1] = sh.members[(size_t)plan.members[k]].geom; }
   if (n_slots) memcpy(h_slots, plan.slots.data(), n_slots * sizeof(int32_t));
-  unsigned char* d = (unsigned char*)mu.d_staging;
-  HIP_TRY(hipMemcpyAsync((void*)d, h, bytes, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(mu.staged, stream));
+  HIP_TRY(mu.staging.copy(bytes, stream));
+  unsigned char* d = mu.staging.device();
   const double* d_vertices = host_vertices ? (const double*)d : vertices;
   const int32_t* d_pairs = (const int32_t*)(d + vert_bytes);
   const int32_t* d_members = d_pairs + 2 * n_pairs;

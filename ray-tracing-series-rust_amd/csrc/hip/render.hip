@@ -170,10 +170,7 @@ struct SceneUpdate {
   DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
   DeviceBuffer<rt::XformOp64> d_slot_ops64;     // the f32 compilation only: the slots' ops in f64
-  DeviceBuffer<unsigned char> d_staging;        // the update records of one call
-  void* h_staging = nullptr;                    // pinned; `staged` marks the end of the copy out of it
-  size_t h_staging_bytes = 0;
-  hipEvent_t staged = nullptr;
+  StagingBuffer staging;                        // the update records of one call
   // rtx_scene_rebuild_instance_trees (scene_rebuild.inc).  max_stack = member_stack + 1 + the deepest of tree_depth.
   int32_t member_stack = 0;                     // host: the members' own part of max_stack (their deepest BVH)
   std::vector<int32_t> tree_depth;              // host: per instance tree, as the trees now stand
@@ -196,10 +193,8 @@ struct MeshUpdate {
   bool uploaded = false;                         // the tables below are resident: done by the first update
   DeviceBuffer<int32_t> d_leaves, d_node_parent; // MeshShadow::leaves, ::node_parent
   DeviceBuffer<unsigned int> d_arrivals;         // one counter per BVH node
-  DeviceBuffer<unsigned char> d_staging;         // one call's vertices (host entry) and index lists
-  void* h_staging = nullptr;                     // pinned; `staged` marks the end of the copy out of it
-  size_t h_staging_bytes = 0;
-  hipEvent_t staged = nullptr;
+  StagingBuffer staging;                         // one call's vertices (host entry) and index lists; its own, so that a call does
+                                                 // not wait for the copy of the last rtx_scene_set_transforms
   bool local_box_stale = false;                  // SceneUpdate::local_box lags behind d_local_box (scene_update.inc reads it back)
 };
 #endif
@@ -248,17 +243,9 @@ static rtx_status upload_array(DeviceScene* ds, const std::vector<T>& v, const T
   return RTX_OK;
 }
 
-// Releases what is not device memory; the buffers go with the DeviceScene.
-static void free_scene_update(SceneUpdate* u);
-#ifndef RTX_F32_TU
-static void free_mesh_update(MeshUpdate* m);
-#endif
+// Releases what has no owner of its own; the buffers go with the DeviceScene.
 static void free_device_scene(DeviceScene* ds) {
   if (!ds) return;
-  free_scene_update(&ds->upd);
-#ifndef RTX_F32_TU
-  free_mesh_update(&ds->mesh);
-#endif
   Workspace& ws = ds->ws;
   if (ws.wave_host_ctrl) (void)hipHostFree(ws.wave_host_ctrl);
   for (int i = 0; i < 2; ++i)

@@ -5,14 +5,15 @@
 // boxes overlap and cull badly.  A rebuild gives tree k a new topology from the members' world boxes at the ops NOW in
 // `entries`, in place: the same n_slots member slots, the same piece of n_slots - 1 nodes.  For one tree of m members, all on
 // the caller's stream:
-//   k_member_boxes     one thread per member: its world box in f64 (k_refit_instance_tree's text), the block-reduced bounds
-//                      of the centroids
+//   k_member_boxes     one thread per member: its world box in f64 (member_world_box, what k_refit_instance_tree starts from),
+//                      the block-reduced bounds of the centroids
 //   k_member_morton    63-bit Morton codes (core/karras.hpp: lbvh.hip's arithmetic), then a stable radix sort (rocPRIM, through
 //                      lbvh.hip's rtx_sort_pairs_u64_u32 so that this file pulls no sort templates into render.hip)
 //   k_rebuild_radix    Karras' tree, one thread per internal node; internal node 0 is the root = node node_base
 //   k_rebuild_emit     one thread per member: depth of its leaf, then it writes its box into its parent's child box and climbs
-//                      with k_refit's visibility recipe; the second thread at a node unites the two f64 boxes, chooses the
-//                      split axis and goes on.  Everything goes into a SCRATCH piece (FlatNode / FlatNode32 / FlatMotion32 and
+//                      with k_refit's visibility recipe (stated at scene_update.inc's refit_climb; this climb exchanges f64 boxes
+//                      through box64 and keeps its own loop); the second thread at a node unites the two f64 boxes, chooses the
+//                      split axis and goes on.  The narrowed planes go through store_child_planes32.  Everything goes into a SCRATCH piece (FlatNode / FlatNode32 / FlatMotion32 and
 //                      the two parent tables), so that a tree too deep for the launchers' stacks is refused with the resident
 //                      tree untouched.
 // The host then reads the depths (and the new parent tables) in ONE wait on the stream, checks the stack budget and commits
@@ -57,8 +58,8 @@ struct MemberBoxArgs {
   int32_t first_slot, n_slots;
 };
 
-// One thread per member: member_local_box through the ops now in `entries` (slot_ops64 under RT_F32), in f64 -- the text of
-// k_refit_instance_tree.  Every thread of the block takes part in the reduction.
+// One thread per member: its world box at the ops now in `entries` (core/member_box.hpp: member_world_box), in f64.  Every
+// thread of the block takes part in the reduction.
 __global__ __launch_bounds__(256) void k_member_boxes(MemberBoxArgs a) {
   __shared__ double red[6][256];
   const int m = (int)(blockIdx.x * 256u + threadIdx.x);
@@ -66,23 +67,8 @@ __global__ __launch_bounds__(256) void k_member_boxes(MemberBoxArgs a) {
   double c[3] = {0.0, 0.0, 0.0};
   if (valid) {
     const int32_t slot = a.first_slot + m;
-    rt::XformOp64 ops[RT_MAX_XFORM_OPS];
-    int n_ops = 0;
-    const rt::FlatEntry* S = &a.entries[a.top_level[slot]];
-    if (S->kind == rt::ENTRY_XFORM) {
-      n_ops = S->b < RT_MAX_XFORM_OPS ? S->b : RT_MAX_XFORM_OPS;
-      for (int k = 0; k < n_ops; ++k) {
-#ifdef RT_F32
-        ops[k] = a.slot_ops64[(size_t)slot * RT_MAX_XFORM_OPS + k];
-#else
-        ops[k].op = S->ops[k].op; ops[k].pad = 0;
-        for (int x = 0; x < 3; ++x) ops[k].v[x] = S->ops[k].v[x];
-#endif
-      }
-    }
-    double local[6], b[6];
-    for (int x = 0; x < 6; ++x) local[x] = a.local_box[6 * (size_t)m + x];
-    rt::member_box_through_ops(local, ops, n_ops, b);
+    double b[6];
+    rt::member_world_box(a.entries[a.top_level[slot]], slot, a.slot_ops64, a.local_box + 6 * (size_t)m, b);
     for (int x = 0; x < 6; ++x) a.boxes[6 * (size_t)m + x] = b[x];
     for (int x = 0; x < 3; ++x) c[x] = 0.5 * (b[x] + b[3 + x]);
   }
@@ -169,13 +155,7 @@ __global__ __launch_bounds__(256) void k_rebuild_emit(RebuildEmitArgs a) {
       const rt::real lo = refit_plane_down(b[x]), hi = refit_plane_up(b[3 + x]);
       nd->bmin[c][x] = lo;
       nd->bmax[c][x] = hi;
-      const float l32 = rt::f32_narrow_down((double)lo), h32 = rt::f32_narrow_up((double)hi);
-      a.nodes32[node].lo[c][x] = l32;
-      a.nodes32[node].hi[c][x] = h32;
-      if (a.motion32) {  // an instance tree has no time interval: its static box, no slope
-        a.motion32[node].lo0[c][x] = l32; a.motion32[node].hi0[c][x] = h32;
-        a.motion32[node].dlo[c][x] = 0.0f; a.motion32[node].dhi[c][x] = 0.0f;
-      }
+      store_child_planes32(a.nodes32, a.motion32, node, c, x, lo, hi);
     }
     nd->child[c] = code;
     a.nodes32[node].child[c] = code;
@@ -263,15 +243,14 @@ static rtx_status scene_rebuild_impl(DeviceScene* ds, const int32_t* trees, int3
   if (!u.shadow.broken.empty()) { set_error(std::string(who) + ": " + u.shadow.broken); return RTX_EINVAL; }
   std::vector<int32_t> list;
   if (!check_rebuild_list(who, ds, u.shadow.trees.size(), trees, n, &list, &err)) { set_error(err); return RTX_EINVAL; }
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error(std::string(who) + ": scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  rtx_status st = check_scene_device(ds, who, "was uploaded to");
+  if (st != RTX_OK) return st;
   if (out) {
     out->trees_rebuilt = 0; out->max_depth = 0;
     out->max_stack_before = out->max_stack_after = ds->view.max_stack;
   }
   if (list.empty()) return RTX_OK;
-  rtx_status st = rebuild_scratch(ds);
+  st = rebuild_scratch(ds);
   if (st != RTX_OK) return st;
   int m_max = 0;
   for (int32_t k : list) m_max = std::max(m_max, (int)u.shadow.trees[(size_t)k].n_slots);
@@ -365,9 +344,8 @@ static rtx_status scene_tree_cost_impl(DeviceScene* ds, int32_t k, double* cost)
     set_error(std::string(who) + ": k is out of range (the scene has " + std::to_string(u.shadow.trees.size()) + " instance trees)");
     return RTX_EINVAL;
   }
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error(std::string(who) + ": scene lives on a different device than the current one"); return RTX_EINVAL; }
+  const rtx_status dst = check_scene_device(ds, who, "lives on");
+  if (dst != RTX_OK) return dst;
   const TreeShadow& t = u.shadow.trees[(size_t)k];
   HIP_TRY(hipDeviceSynchronize());  // after everything enqueued on the device, like rtx_device_scene_array
   HIP_TRY(u.r_terms.grow(((size_t)t.n_nodes + 1) * sizeof(double), nullptr));

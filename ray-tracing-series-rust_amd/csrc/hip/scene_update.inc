@@ -9,6 +9,11 @@
 // scratch with the new parameters -- the judge of tests/test_gpu_set_transforms.py.  Topology is not touched: child codes,
 // split axes and every other array stay as uploaded, and no existing kernel changes.
 //
+// What the other updates of a resident scene share lives here too, once: refit_climb (the bottom-up climb of this refit and of
+// mesh_update.inc's k_refit_bvh, with the one statement of its cross-workgroup visibility), store_child_planes32 (the narrowed
+// planes of a child; also scene_rebuild.inc's k_rebuild_emit) and, on the host side, check_scene_device.  A member's world box
+// is core/member_box.hpp's member_world_box; the pinned staging of a call is device_buffer.hpp's StagingBuffer.
+//
 // The boxes are computed in f64 in BOTH compilations and narrowed last: an f32 scene's node planes are the f64 planes rounded
 // down / up (host/f32_layout.hpp: "d6 u6"), so its refit starts from the f64 ops it keeps in SceneUpdate::slot_ops64 -- the
 // ops in its own entries went through a (float) cast.  Min and max commute with a monotone rounding, so above the leaves the
@@ -67,54 +72,53 @@ __device__ __forceinline__ rt::real refit_plane_up(double x) {
 #endif
 }
 
-// One thread per member slot of ONE tree -- every member, not only the moved ones: the thread recomputes the member's world box,
-// writes it where its parent node keeps it and climbs.  Of the two threads that reach a node the first leaves; the second
-// unites the node's two child boxes into the node's place in ITS parent.  lbvh.hip's k_refit recipe for visibility across
-// workgroups: the box stores, a fence, an agent-scope atomic arrival, a fence, agent-scope loads of the sibling's box.  Unions
-// are exact min / max, so the result does not depend on who arrives first.
-__global__ __launch_bounds__(256) void k_refit_instance_tree(RefitArgs a) {
-  const int m = (int)(blockIdx.x * 256u + threadIdx.x);
-  if (m >= a.n_slots) return;
-  const int32_t slot = a.first_slot + m;
-  rt::XformOp64 ops[RT_MAX_XFORM_OPS];
-  int n_ops = 0;
-  const rt::FlatEntry* S = &a.entries[a.top_level[slot]];
-  if (S->kind == rt::ENTRY_XFORM) {
-    n_ops = S->b < RT_MAX_XFORM_OPS ? S->b : RT_MAX_XFORM_OPS;
-    for (int k = 0; k < n_ops; ++k) {
-#ifdef RT_F32
-      ops[k] = a.slot_ops64[(size_t)slot * RT_MAX_XFORM_OPS + k];
-#else
-      ops[k].op = S->ops[k].op; ops[k].pad = 0;
-      for (int x = 0; x < 3; ++x) ops[k].v[x] = S->ops[k].v[x];
-#endif
-    }
+// Axis x of child c of `node` where the f32 walkers read it: the plane pair narrowed outward into FlatNode32 and, where the
+// scene has time-aware boxes, into FlatMotion32 as a static box without slopes (flatten.cpp: build_motion_boxes gives that to an
+// instance tree, which has no time interval, and to a BVH without a moving sphere).  Plain stores: each field is written by one
+// thread and read by nobody in the same launch.
+__device__ __forceinline__ void store_child_planes32(rt::FlatNode32* nodes32, rt::FlatMotion32* motion32, int32_t node, int c, int x, rt::real lo,
+                                                     rt::real hi) {
+  const float l32 = rt::f32_narrow_down((double)lo), h32 = rt::f32_narrow_up((double)hi);
+  nodes32[node].lo[c][x] = l32;
+  nodes32[node].hi[c][x] = h32;
+  if (motion32) {
+    motion32[node].lo0[c][x] = l32; motion32[node].hi0[c][x] = h32;
+    motion32[node].dlo[c][x] = 0.0f; motion32[node].dhi[c][x] = 0.0f;
   }
-  double local[6], b[6];
-  for (int x = 0; x < 6; ++x) local[x] = a.local_box[6 * (size_t)m + x];
-  rt::member_box_through_ops(local, ops, n_ops, b);
-  rt::real lo[3], hi[3];
-  for (int x = 0; x < 3; ++x) { lo[x] = refit_plane_down(b[x]); hi[x] = refit_plane_up(b[3 + x]); }
-  int32_t node = a.leaf_parent[2 * (size_t)m], c = a.leaf_parent[2 * (size_t)m + 1];
+}
+
+// One binary tree as a refit climbs it (an instance tree here, a BVH in mesh_update.inc): its nodes are
+// nodes[node_base .. node_base + n), and node_parent and arrivals are indexed by node - node_base.
+struct TreePiece {
+  rt::FlatNode* nodes;
+  rt::FlatNode32* nodes32;
+  rt::FlatMotion32* motion32;  // NULL: the scene has no time-aware boxes
+  const int32_t* node_parent;  // 2 per node: parent (-1: root), child index
+  unsigned int* arrivals;      // 1 per node, zero at launch
+  int32_t node_base;
+};
+
+// THE bottom-up climb of every refit.  A thread comes with the box (lo, hi) of child c of `node`: it writes the box where the
+// node keeps it and arrives at the node.  Of the two threads that reach a node the first leaves; the second unites the node's
+// two child boxes and carries the union to the node's place in ITS parent, up to the root.  Unions are exact min / max, so the
+// result does not depend on who arrives first.
+// Visibility across workgroups is lbvh.hip's k_refit recipe (MI355X_MICROARCH.md, inter-workgroup visibility: a CU's L1 is
+// never refreshed by another CU's stores, and the XCDs' L2s are not coherent): agent-scope relaxed stores of the FlatNode
+// planes, which a sibling's climber on another CU reads; __threadfence; the agent-scope atomic arrival; __threadfence;
+// agent-scope relaxed loads of the sibling's planes -- a plain load could be served stale from this CU's L1.
+__device__ __forceinline__ void refit_climb(const TreePiece& t, int32_t node, int32_t c, rt::real* lo, rt::real* hi) {
   for (;;) {
-    rt::FlatNode* nd = &a.nodes[node];
+    rt::FlatNode* nd = &t.nodes[node];
     for (int x = 0; x < 3; ++x) {
-      // a sibling's climber on another CU reads these: agent-scope stores, as in k_refit
       __hip_atomic_store(&nd->bmin[c][x], lo[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(&nd->bmax[c][x], hi[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float l32 = rt::f32_narrow_down((double)lo[x]), h32 = rt::f32_narrow_up((double)hi[x]);
-      a.nodes32[node].lo[c][x] = l32;
-      a.nodes32[node].hi[c][x] = h32;
-      if (a.motion32) {  // an instance tree has no time interval: its static box, no slope
-        a.motion32[node].lo0[c][x] = l32; a.motion32[node].hi0[c][x] = h32;
-        a.motion32[node].dlo[c][x] = 0.0f; a.motion32[node].dhi[c][x] = 0.0f;
-      }
+      store_child_planes32(t.nodes32, t.motion32, node, c, x, lo[x], hi[x]);
     }
-    const int32_t rel = node - a.node_base;
-    const int32_t parent = a.node_parent[2 * (size_t)rel], pc = a.node_parent[2 * (size_t)rel + 1];
+    const int32_t rel = node - t.node_base;
+    const int32_t parent = t.node_parent[2 * (size_t)rel], pc = t.node_parent[2 * (size_t)rel + 1];
     if (parent < 0) return;  // the root: its two child boxes are the whole tree
     __threadfence();
-    if (atomicAdd(&a.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
+    if (atomicAdd(&t.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
     __threadfence();
     for (int x = 0; x < 3; ++x) {
       const rt::real slo = __hip_atomic_load(&nd->bmin[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -125,6 +129,19 @@ __global__ __launch_bounds__(256) void k_refit_instance_tree(RefitArgs a) {
     node = parent;
     c = pc;
   }
+}
+
+// One thread per member slot of ONE tree -- every member, not only the moved ones: the member's world box, then the climb.
+__global__ __launch_bounds__(256) void k_refit_instance_tree(RefitArgs a) {
+  const int m = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (m >= a.n_slots) return;
+  const int32_t slot = a.first_slot + m;
+  double b[6];
+  rt::member_world_box(a.entries[a.top_level[slot]], slot, a.slot_ops64, a.local_box + 6 * (size_t)m, b);
+  rt::real lo[3], hi[3];
+  for (int x = 0; x < 3; ++x) { lo[x] = refit_plane_down(b[x]); hi[x] = refit_plane_up(b[3 + x]); }
+  const TreePiece t = {a.nodes, a.nodes32, a.motion32, a.node_parent, a.arrivals, a.node_base};
+  refit_climb(t, a.leaf_parent[2 * (size_t)m], a.leaf_parent[2 * (size_t)m + 1], lo, hi);
 }
 
 // ------------------------------------------------------------------ host side
@@ -159,20 +176,13 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   return RTX_OK;
 }
 
-static void free_scene_update(SceneUpdate* u) {
-  if (u->h_staging) (void)hipHostFree(u->h_staging);
-  if (u->staged) (void)hipEventDestroy(u->staged);
-  u->h_staging = nullptr;
-  u->staged = nullptr;
+// A resident scene is edited and read on its own device only.  verb: "was uploaded to" (the updates) or "lives on" (the readers).
+static rtx_status check_scene_device(const DeviceScene* ds, const char* who, const char* verb) {
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error(std::string(who) + ": scene " + verb + " a different device than the current one"); return RTX_EINVAL; }
+  return RTX_OK;
 }
-#ifndef RTX_F32_TU
-static void free_mesh_update(MeshUpdate* m) {
-  if (m->h_staging) (void)hipHostFree(m->h_staging);
-  if (m->staged) (void)hipEventDestroy(m->staged);
-  m->h_staging = nullptr;
-  m->staged = nullptr;
-}
-#endif
 
 // Instance tree t refitted on `stream` from d_local_box and the ops now in `entries` (also mesh_update.inc's last step).
 static rtx_status launch_instance_refit(DeviceScene* ds, const TreeShadow& t, hipStream_t stream) {
@@ -197,9 +207,8 @@ static rtx_status launch_instance_refit(DeviceScene* ds, const TreeShadow& t, hi
 static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* resolved, int64_t n, hipStream_t stream) {
   SceneUpdate& u = ds->upd;
   std::string err;
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("rtx_scene_set_transforms: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  const rtx_status dst = check_scene_device(ds, "rtx_scene_set_transforms", "was uploaded to");
+  if (dst != RTX_OK) return dst;
 #ifndef RTX_F32_TU
   if (ds->mesh.local_box_stale) {
     // rtx_scene_set_triangles* (either entry) recomputed members' local boxes on the device only -- the host holds neither the
@@ -211,19 +220,10 @@ static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* r
   }
 #endif
   if (!check_slot_ops_scene("rtx_scene_set_transforms", u.shadow, u.local_box.data(), resolved, n, &err)) { set_error(err); return RTX_EINVAL; }
-  // the pinned staging buffer is this scene's own: the copy of the previous update must have left it
-  if (!u.staged) HIP_TRY(hipEventCreateWithFlags(&u.staged, hipEventDisableTiming));
-  else HIP_TRY(hipEventSynchronize(u.staged));
   const size_t bytes = (size_t)n * sizeof(SlotOpsRecord);
-  if (bytes > u.h_staging_bytes) {
-    if (u.h_staging) HIP_TRY(hipHostFree(u.h_staging));
-    u.h_staging = nullptr;
-    u.h_staging_bytes = 0;
-    HIP_TRY(hipHostMalloc(&u.h_staging, bytes, hipHostMallocDefault));
-    u.h_staging_bytes = bytes;
-  }
-  HIP_TRY(u.d_staging.grow(bytes, stream));
-  SlotOpsRecord* rec = (SlotOpsRecord*)u.h_staging;
+  void* h = nullptr;
+  HIP_TRY(u.staging.reserve(bytes, stream, &h));
+  SlotOpsRecord* rec = (SlotOpsRecord*)h;
   std::vector<char> touched(u.shadow.trees.size(), 0);
   for (int64_t i = 0; i < n; ++i) {
     const SlotChain& c = u.shadow.slots[(size_t)resolved[i].slot];
@@ -233,9 +233,8 @@ static rtx_status scene_set_transforms_impl(DeviceScene* ds, const RtxSlotOps* r
     memcpy(rec[i].ops, resolved[i].ops, sizeof(rec[i].ops));
     if (c.tree >= 0) touched[(size_t)c.tree] = 1;
   }
-  HIP_TRY(hipMemcpyAsync((void*)(unsigned char*)u.d_staging, u.h_staging, bytes, hipMemcpyHostToDevice, stream));
-  HIP_TRY(hipEventRecord(u.staged, stream));
-  hipLaunchKernelGGL(k_set_slot_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const SlotOpsRecord*)(unsigned char*)u.d_staging,
+  HIP_TRY(u.staging.copy(bytes, stream));
+  hipLaunchKernelGGL(k_set_slot_ops, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const SlotOpsRecord*)u.staging.device(),
                      (int)n, (rt::FlatEntry*)ds->view.entries, (WorldDesc*)ds->world.desc, (rt::XformOp64*)u.d_slot_ops64);
   HIP_TRY(hipGetLastError());
   for (size_t k = 0; k < u.shadow.trees.size(); ++k) {
@@ -273,9 +272,8 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
   if (bytes != have) { set_error("rtx_device_scene_array: the array holds " + std::to_string(have) + " bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
   if (have == 0) return RTX_OK;
   if (!out) { set_error("rtx_device_scene_array: out is NULL"); return RTX_EINVAL; }
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("rtx_device_scene_array: scene lives on a different device than the current one"); return RTX_EINVAL; }
+  const rtx_status dst = check_scene_device(ds, "rtx_device_scene_array", "lives on");
+  if (dst != RTX_OK) return dst;
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(out, p, have, hipMemcpyDeviceToHost));
   return RTX_OK;

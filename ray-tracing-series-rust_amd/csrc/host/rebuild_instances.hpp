@@ -20,6 +20,7 @@
 #include <vector>
 #include "../core/karras.hpp"
 #include "f32_layout.hpp"
+#include "tree_refit.hpp"
 #include "update_shadow.hpp"
 
 namespace rtx {
@@ -39,13 +40,9 @@ inline double flat_instance_tree_cost(const FlatScene& fs, const TreeShadow& t) 
 // The world boxes of tree t's members at the ops now in `entries` (6 doubles per member, slot order).
 inline std::vector<double> member_boxes_now(const FlatScene& fs, const TreeShadow& t) {
   std::vector<double> boxes(6 * (size_t)t.n_slots);
-  for (int32_t m = 0; m < t.n_slots; ++m) {
-    const rt::FlatEntry& S = fs.entries[(size_t)fs.top_level[(size_t)(t.first_slot + m)]];
-    const int nops = S.kind == rt::ENTRY_XFORM ? S.b : 0;
-    rt::XformOp64 ops[RT_MAX_XFORM_OPS];
-    for (int i = 0; i < nops; ++i) { ops[i].op = S.ops[i].op; ops[i].pad = 0; for (int a = 0; a < 3; ++a) ops[i].v[a] = S.ops[i].v[a]; }
-    rt::member_box_through_ops(&fs.member_local_box[6 * (size_t)(t.member_first + m)], ops, nops, &boxes[6 * (size_t)m]);
-  }
+  for (int32_t m = 0; m < t.n_slots; ++m)
+    rt::member_world_box(fs.entries[(size_t)fs.top_level[(size_t)(t.first_slot + m)]], t.first_slot + m, nullptr,
+                         &fs.member_local_box[6 * (size_t)(t.member_first + m)], &boxes[6 * (size_t)m]);
   return boxes;
 }
 
@@ -133,16 +130,10 @@ inline void commit_rebuilt_tree(FlatScene* fs, const TreeShadow& t, int32_t k, c
     const size_t n = (size_t)(t.node_base + i);
     const rt::FlatNode& nd = r.nodes[(size_t)i];
     fs->nodes[n] = nd;
+    narrow_node_planes(fs, n);
     rt::FlatNode32& m = fs->nodes32[n];
-    for (int c = 0; c < 2; ++c)
-      for (int a = 0; a < 3; ++a) { m.lo[c][a] = narrow_down(nd.bmin[c][a]); m.hi[c][a] = narrow_up(nd.bmax[c][a]); }
     m.child[0] = nd.child[0]; m.child[1] = nd.child[1];
     m.axis = nd.pad[0]; m.pad = 0;
-    if (!fs->motion32.empty()) {
-      rt::FlatMotion32& mo = fs->motion32[n];
-      for (int c = 0; c < 2; ++c)
-        for (int a = 0; a < 3; ++a) { mo.lo0[c][a] = m.lo[c][a]; mo.hi0[c][a] = m.hi[c][a]; mo.dlo[c][a] = 0.0f; mo.dhi[c][a] = 0.0f; }
-    }
   }
   int32_t seen = 0;
   for (rt::FlatEntry& e : fs->entries)

@@ -12,6 +12,7 @@
 #include <vector>
 #include "../core/rt_math.hpp"
 #include "f32_layout.hpp"
+#include "tree_refit.hpp"
 #include "update_shadow.hpp"
 
 namespace rtx {
@@ -67,44 +68,11 @@ inline std::vector<RtxSlotOps> resolve_slot_ops(const RtxSlotOps* u, int64_t n) 
 
 // Instance tree t of fs, refitted bottom-up from the members' local boxes and the ops now in `entries`.
 inline void refit_instance_tree(FlatScene* fs, const TreeShadow& t) {
-  struct Box { double b[6]; };
-  // children before parents: a depth-first order from the root, walked backwards
-  std::vector<int32_t> order{t.root};
-  for (size_t k = 0; k < order.size(); ++k)
-    for (int c = 0; c < 2; ++c)
-      if (!rt::node_child_is_leaf(fs->nodes[(size_t)order[k]].child[c])) order.push_back(fs->nodes[(size_t)order[k]].child[c]);
-  std::vector<Box> whole((size_t)t.n_nodes);  // the union of a node's two child boxes, by node - node_base
-  for (size_t k = order.size(); k-- > 0;) {
-    const int32_t n = order[k];
-    rt::FlatNode& nd = fs->nodes[(size_t)n];
-    Box u;
-    for (int c = 0; c < 2; ++c) {
-      Box cb;
-      if (rt::node_child_is_leaf(nd.child[c])) {
-        const uint32_t slot = rt::leaf_first(nd.child[c]);
-        const rt::FlatEntry& S = fs->entries[(size_t)fs->top_level[slot]];
-        const int nops = S.kind == rt::ENTRY_XFORM ? S.b : 0;
-        rt::XformOp64 ops[RT_MAX_XFORM_OPS];
-        for (int i = 0; i < nops; ++i) { ops[i].op = S.ops[i].op; ops[i].pad = 0; for (int a = 0; a < 3; ++a) ops[i].v[a] = S.ops[i].v[a]; }
-        rt::member_box_through_ops(&fs->member_local_box[6 * (size_t)(t.member_first + (int32_t)slot - t.first_slot)], ops, nops, cb.b);
-      } else {
-        cb = whole[(size_t)(nd.child[c] - t.node_base)];
-      }
-      for (int a = 0; a < 3; ++a) { nd.bmin[c][a] = cb.b[a]; nd.bmax[c][a] = cb.b[3 + a]; }
-      if (c == 0) u = cb;
-      else for (int a = 0; a < 3; ++a) { u.b[a] = std::fmin(u.b[a], cb.b[a]); u.b[3 + a] = std::fmax(u.b[3 + a], cb.b[3 + a]); }
-    }
-    whole[(size_t)(n - t.node_base)] = u;
-    rt::FlatNode32& m = fs->nodes32[(size_t)n];
-    for (int c = 0; c < 2; ++c)
-      for (int a = 0; a < 3; ++a) { m.lo[c][a] = narrow_down(nd.bmin[c][a]); m.hi[c][a] = narrow_up(nd.bmax[c][a]); }
-    if (!fs->motion32.empty()) {
-      // an instance tree has no time interval: its time-aware boxes are its static ones, slopes 0 (flatten.cpp: build_motion_boxes)
-      rt::FlatMotion32& mo = fs->motion32[(size_t)n];
-      for (int c = 0; c < 2; ++c)
-        for (int a = 0; a < 3; ++a) { mo.lo0[c][a] = m.lo[c][a]; mo.hi0[c][a] = m.hi[c][a]; mo.dlo[c][a] = 0.0f; mo.dhi[c][a] = 0.0f; }
-    }
-  }
+  refit_tree_piece(fs, t.root, t.node_base, t.n_nodes, [&](int32_t code, double* b) {
+    const int32_t slot = (int32_t)rt::leaf_first(code);  // a leaf of an instance tree is one member slot
+    rt::member_world_box(fs->entries[(size_t)fs->top_level[(size_t)slot]], slot, nullptr,
+                         &fs->member_local_box[6 * (size_t)(t.member_first + slot - t.first_slot)], b);
+  });
 }
 
 // rtx_flat_set_transforms: every check first, then the edit.  false with *err set and *fs untouched.

@@ -318,36 +318,10 @@ RT_HD void top_triangle_box32(const rt::FlatTriangle* triangles, rt::PrimRef ref
 // BVH b of fs refitted whole, bottom-up: nodes, nodes32 and, where the scene has one, motion32's static copy.
 inline void refit_bvh(FlatScene* fs, const BvhShadow& b) {
   if (rt::node_child_is_leaf(b.root)) return;  // no node: only its triangles changed
-  struct Box { double b[6]; };
-  std::vector<int32_t> order{b.root};  // children before parents: a breadth-first order from the root, walked backwards
-  for (size_t k = 0; k < order.size(); ++k)
-    for (int c = 0; c < 2; ++c)
-      if (!rt::node_child_is_leaf(fs->nodes[(size_t)order[k]].child[c])) order.push_back(fs->nodes[(size_t)order[k]].child[c]);
-  std::vector<Box> whole((size_t)b.n_nodes);
   const rt::PrimRef* refs = fs->refs.data() + b.first_ref;
-  for (size_t k = order.size(); k-- > 0;) {
-    const int32_t n = order[k];
-    rt::FlatNode& nd = fs->nodes[(size_t)n];
-    Box u;
-    for (int c = 0; c < 2; ++c) {
-      Box cb;
-      if (rt::node_child_is_leaf(nd.child[c])) bvh_leaf_box(nd.child[c], refs, fs->spheres.data(), fs->rects.data(), fs->triangles.data(), cb.b);
-      else cb = whole[(size_t)(nd.child[c] - b.node_base)];
-      for (int a = 0; a < 3; ++a) { nd.bmin[c][a] = cb.b[a]; nd.bmax[c][a] = cb.b[3 + a]; }
-      if (c == 0) u = cb;
-      else for (int a = 0; a < 3; ++a) { u.b[a] = rt::rt_fmin(u.b[a], cb.b[a]); u.b[3 + a] = rt::rt_fmax(u.b[3 + a], cb.b[3 + a]); }
-    }
-    whole[(size_t)(n - b.node_base)] = u;
-    rt::FlatNode32& m = fs->nodes32[(size_t)n];
-    for (int c = 0; c < 2; ++c)
-      for (int a = 0; a < 3; ++a) { m.lo[c][a] = rt::f32_narrow_down(nd.bmin[c][a]); m.hi[c][a] = rt::f32_narrow_up(nd.bmax[c][a]); }
-    if (!fs->motion32.empty()) {
-      // a BVH without a moving sphere keeps its static boxes, slopes 0 (flatten.cpp: build_motion_boxes)
-      rt::FlatMotion32& mo = fs->motion32[(size_t)n];
-      for (int c = 0; c < 2; ++c)
-        for (int a = 0; a < 3; ++a) { mo.lo0[c][a] = m.lo[c][a]; mo.hi0[c][a] = m.hi[c][a]; mo.dlo[c][a] = 0.0f; mo.dhi[c][a] = 0.0f; }
-    }
-  }
+  refit_tree_piece(fs, b.root, b.node_base, b.n_nodes, [&](int32_t code, double* box) {
+    bvh_leaf_box(code, refs, fs->spheres.data(), fs->rects.data(), fs->triangles.data(), box);
+  });
 }
 
 // rtx_flat_set_triangles: every check first, then the edit.  Not RTX_OK: *err set and *fs untouched.

@@ -168,18 +168,22 @@ def shared(rtsr, moved):
     return case
 
 
-def instanced(rtsr, moved, hoisted=False):
+INSTANCED_POSE = (((0.4, 0.2, 0.3), 20.0), ((3.1, 0.3, 2.2), -35.0), ((1.2, 0.4, 4.0), None))
+
+
+def instanced(rtsr, moved, hoisted=False, pose=INSTANCED_POSE):
     """An instance tree of two Translate(RotateY(BvhNode(sheet))) and a Translate(list of 3 triangles), beside a ground sphere.
-    hoisted: the members written into the world list themselves -- the spelling the literal oracle renders."""
+    hoisted: the members written into the world list themselves -- the spelling the literal oracle renders.  pose: the three
+    members' (offset, angle in degrees; None: the member has no RotateY)."""
     m = _Maker(rtsr, 10, moved)
     b = m.b
     red, blue, grey = b.lambertian((0.8, 0.3, 0.3)), b.metal((0.6, 0.7, 0.9), 0.2), b.lambertian((0.5, 0.5, 0.5))
     members = []
-    for k, (off, ang) in enumerate((((0.4, 0.2, 0.3), 20.0), ((3.1, 0.3, 2.2), -35.0))):
+    for k, (off, ang) in enumerate(pose[:2]):
         v, f, cell = sheet_mesh(18 + 6 * k, origin=(0.2, 0.8, 0.3), extent=2.0, seed=4 + k)
         members.append(b.translate(off, b.rotate_y(ang, b.bvh_from_list(m.mesh(v, f, cell, red if k else blue), 0.0, 1.0))))
     tris = [m.triangle([(0.2 + 0.7 * k, 0.5, 0.3), (0.8 + 0.7 * k, 0.6, 0.5), (0.4 + 0.7 * k, 1.4, 0.9)], 0.4, red) for k in range(3)]
-    members.append(b.translate((1.2, 0.4, 4.0), b.hittable_list(tris)))
+    members.append(b.translate(pose[2][0], b.hittable_list(tris)))
     ground = b.sphere((2.3, -500.0, 2.4), 500.0, grey)
     world = b.hittable_list([ground] + members) if hoisted else b.hittable_list([ground, b.instance_bvh(b.hittable_list(members))])
     return Case(b, world, m.parts, look=((2.8, 5.5, 10.5), (2.8, 1.0, 2.4)))
@@ -273,6 +277,29 @@ def update_of(case, flat, moved=True, every=1, only=None):
     if only is not None:
         return ids[only:only + 1].copy(), verts[only:only + 1].copy()
     return ids[::every].copy(), verts[::every].copy()
+
+
+# One resident scene through all three update entries, on `instanced`: every triangle displaced; the members moved (the first
+# set_transforms after a mesh update reads the members' local boxes back); the tree rebuilt; every third triangle back to rest;
+# the members moved again.  Poses keep every coordinate away from 0, like the cases.
+SEQUENCE_POSES = ((((1.0, 0.5, 0.2), 50.0), ((2.5, 0.1, 3.0), -10.0), ((0.3, 0.6, 3.2), None)),
+                  (((0.6, 0.2, 0.1), 33.0), ((3.4, 0.4, 1.9), -60.0), ((1.5, 0.3, 4.4), None)))
+SEQUENCE_END = {"moved": lambda k: k % 3 != 0, "pose": SEQUENCE_POSES[1]}  # instanced(rtsr, **SEQUENCE_END): the end state from scratch
+
+
+def update_sequence(case, flat):
+    """[(name, apply)]: apply(target) makes the step's call on a Flat or a Scene.  flat: flattened from `case` = instanced at
+    rest (it only names the ids and the slots, so it may itself be a target)."""
+    first = flat.instance_tree(0)["first_slot"]
+
+    def ops(pose):
+        return {first + k: [("translate", off)] + ([("rotate_y", ang)] if ang is not None else []) for k, (off, ang) in enumerate(pose)}
+
+    return [("set_triangles", lambda s: s.set_triangles(*update_of(case, flat))),
+            ("set_transforms", lambda s: s.set_transforms(ops(SEQUENCE_POSES[0]))),
+            ("rebuild_instance_trees", lambda s: s.rebuild_instance_trees()),
+            ("set_triangles again", lambda s: s.set_triangles(*update_of(case, flat, moved=False, every=3))),
+            ("set_transforms again", lambda s: s.set_transforms(ops(SEQUENCE_POSES[1])))]
 
 
 def triangles_by_id(flat):

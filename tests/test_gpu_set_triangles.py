@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import cast_rays_cases as cc
-from deform_cases import (CASES, call_set_triangles, refusals, DEVICE_ARRAYS, NODE, NODE4, SHEET_LEAVES, cam_cfg, count_leaves, movers, narrow, sheet, sheet_tris_for_leaves, update_of)
+from deform_cases import (CASES, call_set_triangles, refusals, DEVICE_ARRAYS, NODE, NODE4, SHEET_LEAVES, cam_cfg, count_leaves, movers, narrow, sheet, sheet_tris_for_leaves, update_of, update_sequence)
 
 pytestmark = pytest.mark.gpu
 SWITCHES = ("RTX_TRACE_KERNEL", "RTX_WIDE")
@@ -114,6 +114,54 @@ def test_a_tree_from_the_gpu_builder_keeps_its_leaf_order(rtsr, orc):
     assert orc.audit_flat_exact(flat.arrays_ptr(), **audit)[0] == 0
     assert orc.audit_flat_exact(flat.arrays_ptr(), nodes=scene.array("nodes").view(orc.FLAT_NODE), **audit)[0] == 0
     _assert_arrays_equal(scene, _device(_upload(flat)), "karras")
+
+
+def test_three_host_updates_in_a_row_allocate_reuse_and_regrow_the_staging_buffer(rtsr):
+    """One resident sheet of 65 leaves through the host-vertex entry with 1 id, 7 ids, then every id: the pinned block and its
+    device twin are made by the first call and outgrown by the next two; a fourth call (back to rest) fits what is there.  The
+    arrays are compared after every call."""
+    case = sheet(rtsr, False, 65, 1)
+    flat = case.flatten()
+    assert count_leaves(flat) == 65
+    scene = _upload(flat)
+    first = _device(scene)
+    for what, kw, n in (("1 id", {"only": 3}, 1), ("7 ids", {"every": 10}, 7), ("every id", {}, 65)):
+        ids, verts = update_of(case, flat, **kw)
+        assert len(ids) == n
+        scene.set_triangles(ids, verts)
+        flat.set_triangles(ids, verts)
+        _assert_arrays_equal(scene, _device(_upload(flat)), what)
+    assert not np.array_equal(scene.array("nodes"), first["nodes"])
+    scene.set_triangles(*update_of(case, flat, moved=False))
+    back = _device(scene)
+    assert all(np.array_equal(back[k], first[k]) for k in DEVICE_ARRAYS)
+
+
+def test_one_scene_through_set_triangles_set_transforms_and_a_rebuild(rtsr):
+    """deform_cases.update_sequence on ONE resident scene: set_triangles, set_transforms (the first after a mesh update: it reads
+    the members' local boxes back), rebuild_instance_trees, set_triangles, set_transforms.  After every step the resident
+    arrays and max_stack are those of the flat scene taken through the same step on the host (the Morton rebuild) and uploaded
+    fresh; then one 48 x 27 frame at 4 spp on both.  The host sequence itself is held to the end state built from scratch by
+    tests/test_set_triangles_host.py."""
+    case = CASES["instanced"](rtsr, False)
+    flat = case.flatten()
+    assert flat.instances()["n_trees"] == 1 and flat.instance_tree(0)["n_slots"] == 3
+    scene = _upload(flat)
+    before = _device(scene)
+    for what, apply in update_sequence(case, flat):
+        apply(scene)
+        apply(flat)
+        _assert_arrays_equal(scene, _device(_upload(flat)), what)
+        assert scene.max_stack() == flat.info()["max_stack"], what
+        now = _device(scene)
+        assert what == "rebuild_instance_trees" or not np.array_equal(now["nodes"], before["nodes"]), what
+        before = now
+    cam = rtsr.Camera.new(case.look[0], case.look[1], (0.0, 1.0, 0.0), 35.0, 16.0 / 9.0, 0.0, 10.0, 0.0, 1.0)
+    cfg = rtsr.Config.new(16.0 / 9.0, 48, 4, 8, 4, seed=31)
+    assert (cfg.image_width, rtsr.image_height(cfg), cfg.samples_per_pixel) == (48, 27, 4)
+    want = _upload(flat).render(cam, cfg)
+    assert want.accum.std() > 0.01
+    _same_screen(scene.render(cam, cfg), want, "after the sequence")
 
 
 # ---- 2. the 4-wide tree

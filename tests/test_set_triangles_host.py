@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 from cast_rays_cases import same_bits
-from deform_cases import (CASES, call_set_triangles, refusals, FLAT_ARRAYS, MOTION32, NODE, NODE32, SHEET_LEAVES, TRIANGLE, cam_cfg, count_leaves, instanced, leaf_boxes, movers, narrow,
-                          seeded_rays, sheet, sheet_tris_for_leaves, tree_roots, triangles_by_id, update_of)
+from deform_cases import (CASES, call_set_triangles, refusals, FLAT_ARRAYS, MOTION32, NODE, NODE32, SEQUENCE_END, SHEET_LEAVES, TRIANGLE, cam_cfg, count_leaves, instanced, leaf_boxes,
+                          movers, narrow, seeded_rays, sheet, sheet_tris_for_leaves, tree_roots, triangles_by_id, update_of, update_sequence)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -181,6 +181,53 @@ def test_partial_updates(rtsr, orc, name):
     _check_against_fresh(rtsr, orc, flat, CASES[name](rtsr, lambda k: k < half).flatten(), first)
     flat.set_triangles(ids[half:], verts[half:])
     _check_against_fresh(rtsr, orc, flat, CASES[name](rtsr, True).flatten(), first)
+
+
+def test_a_sequence_through_all_three_updates_is_the_end_state_built_from_scratch(rtsr, orc):
+    """deform_cases.update_sequence on the host twin -- set_triangles, set_transforms, a Morton rebuild, set_triangles,
+    set_transforms -- against `instanced` built from scratch with the final vertices and the final pose.  This is what makes
+    the host twin a judge for tests/test_gpu_set_triangles.py's sequence on the device.  A rebuilt tree and a refitted BVH keep
+    their own topology, which a fresh build need not choose (the exception the tests above and
+    tests/test_rebuild_instances_host.py already make): what a topology cannot change is compared byte for byte, the boxes
+    above it are audited as exact unions, and rays and a frame see no difference."""
+    case = instanced(rtsr, False)
+    flat, fresh = case.flatten(), instanced(rtsr, **SEQUENCE_END).flatten()
+    first = _arrays(flat)
+    steps = update_sequence(case, flat)
+    assert [name for name, _ in steps] == ["set_triangles", "set_transforms", "rebuild_instance_trees", "set_triangles again", "set_transforms again"]
+    for name, apply in steps:
+        before = flat.array("nodes")
+        apply(flat)
+        assert name == "rebuild_instance_trees" or not np.array_equal(flat.array("nodes"), before), name
+    now, judge = _arrays(flat), _arrays(fresh)
+    assert triangles_by_id(flat) == triangles_by_id(fresh)
+    for k in ("member_local_box", "top_box32"):
+        assert np.array_equal(now[k], judge[k]), k
+    for k in ("top_level", "triangle_id") + ORACLE_ARRAYS:  # what no update writes
+        assert np.array_equal(now[k], first[k]), k
+    # entries: the ops of the final pose; only a tree's root node may differ (a rebuilt tree's root is the first node of its piece)
+    e, e_fresh = now["entries"].view(np.int32).reshape(-1, 40).copy(), judge["entries"].view(np.int32).reshape(-1, 40).copy()
+    for x in (e, e_fresh):
+        x[x[:, 0] == 5, 1] = 0
+    assert np.array_equal(e, e_fresh)
+    assert flat.instances()["n_trees"] == 1 and flat.instance_tree(0)["n_slots"] == 3
+    nodes, n32 = now["nodes"].view(NODE), now["nodes32"].view(NODE32)
+    for root, fresh_root in zip(tree_roots(flat), tree_roots(fresh)):
+        leaves, fresh_leaves = leaf_boxes(nodes, root)[0], leaf_boxes(judge["nodes"].view(NODE), fresh_root)[0]
+        assert sorted(leaves) == sorted(fresh_leaves) and len(leaves) == 3
+        for slot in leaves:
+            assert leaves[slot][0].tobytes() == fresh_leaves[slot][0].tobytes() and leaves[slot][1].tobytes() == fresh_leaves[slot][1].tobytes(), slot
+    assert orc.audit_flat_exact(flat.arrays_ptr(), ask_first=True)[0] == 0
+    assert np.array_equal(n32["lo"], narrow(nodes["bmin"], up=False)) and np.array_equal(n32["hi"], narrow(nodes["bmax"], up=True))
+    assert np.array_equal(n32["child"], nodes["child"])
+    assert len(now["motion32"]) == len(first["motion32"]) == 0
+    o, d = seeded_rays(2000, 23)
+    want = _records(orc, fresh, o, d)
+    assert 200 < int(want[:, 0].sum()) and same_bits(_records(orc, flat, o, d), want).all()
+    cam, cfg, h = cam_cfg(rtsr, case)
+    a, a8 = orc.o2_render(flat.arrays_ptr(), cam, cfg, h, threads=4)
+    f, f8 = orc.o2_render(fresh.arrays_ptr(), cam, cfg, h, threads=4)
+    assert f.std() > 0.01 and np.array_equal(a, f) and np.array_equal(a8, f8)
 
 
 def test_triangle_ids_name_a_mesh_face_by_face(rtsr):
