@@ -616,11 +616,14 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
  * 0 entries, 1 nodes, 2 nodes32, 3 the time-aware boxes, 4 k_trace_world's slot table, 7 the 4-wide culling tree (128 bytes per
  * node, indexed like nodes; 0 bytes when the scene walks its binary tree), 8 the stack levels its walks are launched with (one
  * int32, 0 without a wide tree), 9 the scene's max_stack as its binary walks are now launched with (one int32; a rebuild of
- * an instance tree changes it), 10 triangles, 11 top_box32 (6 floats per slot).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
+ * an instance tree changes it), 10 triangles, 11 top_box32 (6 floats per slot), 13 the static spheres (FlatSphere, 40 bytes
+ * each in an f64 scene), 14 the light table of next-event estimation (FlatLight, 40 bytes each; 0 bytes without sampled
+ * lights).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
  * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
- * instance tree, the box before the ops), 12: triangle_id (one int32 per flat triangle). */
+ * instance tree, the box before the ops), 12: triangle_id (one int32 per flat triangle).  14 is the light table an upload
+ * of the flat scene as it stands would build. */
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
 
 /* ---- instance trees: the quality of a tree as it stands, and a rebuild for the current pose ---------------------------------
@@ -716,6 +719,52 @@ rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, 
  * read-back: a vertex that is not finite gives that triangle and the boxes above it unspecified culling.  No index is derived
  * from a vertex, so nothing can leave an allocation. */
 rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream);
+
+/* ---- moving spheres: a new centre and radius for static spheres of a flat scene or of a resident f64 scene (an extension) ---
+ * The flattener emits a static sphere once per handle and neither permutes nor copies it, so a sphere's ID is its index in the
+ * flat scene's sphere array.  A sphere handle listed twice, or listed in the world list and in a BvhNode, has one id: both
+ * places move.  Moving and gravity spheres have no id.
+ *
+ * rtx_flat_sphere_ids: the ids of the static spheres below `object` (a sphere, a list, a BvhNode, an instance tree, a wrapper
+ * or medium around those), in list order; moving and gravity spheres are skipped.  Writes min(count, cap) ids, returns count;
+ * -1 (and rtx_last_error) for a NULL argument, a bad handle or an object this flat scene did not flatten. */
+int64_t rtx_flat_sphere_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap);
+/* spheres: n x 4 doubles, cx cy cz radius of sphere ids[i].  ids: a HOST array in all three entries, free for reuse on return.
+ *
+ * Meaning: the scene then answers every entry point -- rtx_render* through every walker (k_trace_lds included: it copies the
+ * culling boxes and the sphere records into LDS at every launch), light sampling, progressive handles made afterwards and
+ * their feature pass, rtx_scene_cast_rays*, rtx_scene_trace_rays* -- bit for bit as the scene built from scratch with those
+ * spheres.  Exempt, as for rtx_*_set_triangles: an exact tie inside one BVH goes by leaf order, and a box plane that is
+ * exactly zero takes its sign from the order of the unions.
+ *
+ * What is written, and nothing else: cx cy cz radius of the flat sphere (mat is untouched); the boxes of every BVH that holds
+ * an updated sphere, refitted whole and bottom-up in nodes, nodes32 and the static copy of the time-aware boxes (the TOPOLOGY
+ * is kept); on a resident scene with a 4-wide tree the planes of its slots (the stack levels and every launch plan stand);
+ * member_local_box and the instance tree above a touched member; top_box32 and the slot record's box of a plain top-level
+ * sphere, and the slot record's box of a medium whose boundary is the sphere (with the record's flags that are derived from
+ * those boxes and from the sphere's bytes); on a resident scene, when an updated sphere is a sampled light, the light table:
+ * that light's area, and every light's cdf and pmf (a light's pick weight is its area times the emission at its CENTRE, so a
+ * move alone can change every probability).  RtxFlatInfo::sah_cost is not updated.
+ *
+ * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, an id out of
+ * range or named twice; host entries: a value that is not finite (the radius may be negative -- the hollow glass ball -- or
+ * zero: rtx_sphere applies no rule to it either); device entry: a pointer that is not 8-byte aligned.  n = 0 is RTX_OK with
+ * nothing launched.  RTX_EUNSUPPORTED, the scene unchanged, checked before anything is enqueued: a touched BVH that holds a
+ * MovingSphere or GravitySphere (its time-aware slopes would have to be derived again), and a resident f32 scene: update the
+ * flat scene with rtx_flat_set_spheres and upload it again with rtx_scene_upload_f32. */
+rtx_status rtx_flat_set_spheres(rtx_flat* f, const int32_t* ids, int64_t n, const double* spheres);
+/* A resident f64 scene; spheres is a HOST array, staged with one copy.  Asynchronous on hip_stream, as
+ * rtx_scene_set_triangles: k_set_spheres, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
+ * k_refit_instance_tree per touched instance tree, k_sphere_slot_boxes, k_refresh_lights.  One update of a scene at a time;
+ * ordering against work on other streams is the caller's; progressive handles made earlier hold the old spheres.  rtx_multi_*
+ * scenes are not covered: update the flat scene and create the handle again.  The read-back by the FIRST
+ * rtx_scene_set_transforms after an update that touched a member of an instance tree applies as for rtx_scene_set_triangles. */
+rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, const double* spheres, void* hip_stream);
+/* d_spheres: a DEVICE pointer (8-byte aligned), e.g. the output of the caller's own animation kernel on hip_stream; it is read
+ * by work enqueued on hip_stream and must stay valid until that work is done.  Finiteness cannot be checked without a
+ * read-back: a value that is not finite gives that sphere and the boxes above it unspecified culling.  No index is derived
+ * from a value, so nothing can leave an allocation. */
+rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

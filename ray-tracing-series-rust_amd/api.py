@@ -157,7 +157,8 @@ _XFORM_NAMES = ("translate", "rotate_y")
 # rtx_flat_array / rtx_device_scene_array: `which` and the element size in an f64 and in an f32 scene
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
                 "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128),
-                "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4)}
+                "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4), "spheres": (13, 40, 24),
+                "lights": (14, 40, 40)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
@@ -281,6 +282,10 @@ ABI = {
     "rtx_flat_set_triangles": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
     "rtx_scene_set_triangles": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
     "rtx_scene_set_triangles_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
+    "rtx_flat_sphere_ids": (C.c_int64, [_VP, _VP, _H, C.POINTER(C.c_int32), C.c_int64]),
+    "rtx_flat_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
+    "rtx_scene_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
+    "rtx_scene_set_spheres_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
     "rtx_device_scene_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_flat_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_builder_graph": (_VP, [_VP]),
@@ -581,6 +586,25 @@ class Flat:
         ids, vertices = _triangle_update(ids, vertices)
         _check(lib.rtx_flat_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3)))
 
+    def sphere_ids(self, builder, handle):
+        """The ids of the static spheres below `handle` (a sphere, a list, a BvhNode, an instance tree, a wrapper or medium
+        around those) in list order (rtx_flat_sphere_ids) -> int32 array.  A sphere's id is its index in Flat.array("spheres");
+        moving and gravity spheres have none and are skipped."""
+        n = lib.rtx_flat_sphere_ids(self._p, builder.ptr, int(handle), None, 0)
+        if n < 0:
+            raise RtxError(RTX_EINVAL, last_error())
+        out = np.zeros(n, dtype=np.int32)
+        if n and lib.rtx_flat_sphere_ids(self._p, builder.ptr, int(handle), out.ctypes.data_as(C.POINTER(C.c_int32)), n) != n:
+            raise RtxError(RTX_EINVAL, last_error())
+        return out
+
+    def set_spheres(self, ids, spheres):
+        """A new centre and radius for the static spheres `ids`, in place (rtx_flat_set_spheres): the flat scene becomes the one
+        flattened from scratch with these spheres, its BVHs refitted with their topology kept.  spheres: n x 4 doubles,
+        cx cy cz radius of ids[i]."""
+        ids, spheres = _sphere_update(ids, spheres)
+        _check(lib.rtx_flat_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3)))
+
     def rebuild_instance_trees(self, trees=None, builder="morton"):
         """A new topology for instance trees from their members' boxes at the current pose, in place
         (rtx_flat_rebuild_instance_trees).  trees: tree indices, None for every tree.  builder: "morton" -- what
@@ -616,6 +640,17 @@ def _triangle_update(ids, vertices):
     if ids.size == 0:  # a pointer the library may compare with NULL
         return np.zeros(1, dtype=np.int32)[:0], np.zeros(1, dtype=np.float64)[:0]
     return ids, vertices
+
+
+def _sphere_update(ids, spheres):
+    """ids, spheres of set_spheres -> (contiguous int32 array of n ids, contiguous float64 array of 4 n values)."""
+    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+    spheres = np.ascontiguousarray(np.asarray(spheres, dtype=np.float64).reshape(-1))
+    if spheres.size != 4 * ids.size:
+        raise ValueError("spheres holds %d values, %d ids need %d (cx cy cz radius each)" % (spheres.size, ids.size, 4 * ids.size))
+    if ids.size == 0:  # a pointer the library may compare with NULL
+        return np.zeros(1, dtype=np.int32)[:0], np.zeros(1, dtype=np.float64)[:0]
+    return ids, spheres
 
 
 def _tree_list(trees):
@@ -752,6 +787,29 @@ class Scene:
         _check(lib.rtx_scene_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3),
                                            _VP(raw or None)))
 
+    def set_spheres(self, ids, spheres, stream=None):
+        """A new centre and radius for the static spheres `ids` of the RESIDENT f64 scene: every later call answers as on the
+        scene built from scratch with these spheres (its BVHs are refitted on the device, their topology kept; the light table
+        follows a sphere light).  spheres: n x 4 doubles cx cy cz radius as a numpy array (rtx_scene_set_spheres, staged with
+        one copy) or as a torch float64 tensor on the GPU (rtx_scene_set_spheres_device: e.g. an animation computed on
+        `stream`).  ids: host integers either way.  Enqueued on `stream` as in set_transforms."""
+        raw = getattr(stream, "cuda_stream", stream)
+        if hasattr(spheres, "data_ptr"):  # a torch tensor
+            import torch
+            if not spheres.is_cuda or spheres.dtype != torch.float64 or not spheres.is_contiguous():
+                raise ValueError("a tensor of spheres must be a contiguous float64 tensor on the GPU")
+            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+            if spheres.numel() != 4 * ids.size:
+                raise ValueError("spheres holds %d values, %d ids need %d (cx cy cz radius each)" % (spheres.numel(), ids.size, 4 * ids.size))
+            if ids.size == 0:
+                return  # n = 0 is RTX_OK with nothing launched; an empty tensor has no pointer to hand over
+            _check(lib.rtx_scene_set_spheres_device(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
+                                                    _VP(spheres.data_ptr() or None), _VP(raw or None)))
+            return
+        ids, spheres = _sphere_update(ids, spheres)
+        _check(lib.rtx_scene_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3),
+                                         _VP(raw or None)))
+
     def rebuild_instance_trees(self, trees=None, stream=None):
         """A new topology for instance trees of the RESIDENT scene from their members' boxes at the current pose
         (rtx_scene_rebuild_instance_trees; Morton codes, a radix sort and Karras' tree on the device).  trees: tree indices,
@@ -778,8 +836,8 @@ class Scene:
 
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
-        "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32" or "nodes4" (the 4-wide tree; empty when the
-        scene has none)."""
+        "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32", "spheres", "lights" (the light table of
+        next-event estimation; empty without sampled lights) or "nodes4" (the 4-wide tree; empty when the scene has none)."""
         return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)
 
     def wide_levels(self):

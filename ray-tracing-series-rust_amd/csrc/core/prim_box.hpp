@@ -1,10 +1,13 @@
 // The reference bounding box of one STATIC flattened primitive (hit.rs bounding_box impls): a sphere (with |radius|: see
 // host/flatten.cpp, prim_box), a rectangle (+-0.0001 on the thin axis) or a triangle.  ONE text for the flattener
-// (host/flatten.cpp), the host refit of rtx_flat_set_triangles (host/set_triangles.hpp) and the device refit of
-// rtx_scene_set_triangles (hip/mesh_update.inc): a refitted BVH is judged bit for bit against one flattened from scratch, so
-// all three must round alike.  Sums and differences of two doubles, min and max: exact or correctly rounded in either build.
+// (host/flatten.cpp), the host refits of rtx_flat_set_triangles / _set_spheres (host/set_triangles.hpp, host/set_spheres.hpp)
+// and the device refits of rtx_scene_set_triangles / _set_spheres (hip/mesh_update.inc, hip/sphere_update.inc): a refitted BVH
+// is judged bit for bit against one flattened from scratch, so all of them must round alike.  Sums and differences of two
+// doubles, min and max: exact or correctly rounded in either build.  The f32 boxes of top-level slots follow the same rule:
+// plain_slot_box32 and medium_sphere_box32 below are what the flattener, the upload and the updates all call.
 #pragma once
 #include "flat_types.hpp"
+#include "member_box.hpp"  // f32_narrow_down / _up, f32_step_down / _up
 
 namespace rt {
 
@@ -48,6 +51,41 @@ RT_HD void grow_ordered(double* box, const double* pb) {
     box[a] = rt_fmin(box[a], rt_fmin(pb[a], pb[3 + a]));
     box[3 + a] = rt_fmax(box[3 + a], rt_fmax(pb[a], pb[3 + a]));
   }
+}
+
+// The f32 box of a plain top-level slot (FlatScene::top_box32, WorldDesc::box) from the reference box b of its static
+// primitive: each axis ordered first (a sphere of negative radius has an inverted reference box, and "outward" must mean
+// outward), then narrowed outward; an axis with a NaN plane is left unbounded.  THE rule of the flattener ("boxes of the plain
+// static primitives") and of every update that moves such a primitive.
+RT_HD void plain_slot_box32(PrimRef ref, const FlatSphere* spheres, const FlatRect* rects, const FlatTriangle* triangles, float* bx) {
+  double b[6];
+  static_prim_box(ref, spheres, rects, triangles, b);
+  for (int a = 0; a < 3; ++a) {
+    const double blo = rt_fmin(b[a], b[3 + a]), bhi = rt_fmax(b[a], b[3 + a]);
+    if (b[a] == b[a] && b[3 + a] == b[3 + a]) { bx[a] = f32_narrow_down(blo); bx[3 + a] = f32_narrow_up(bhi); }
+    else { bx[a] = -__builtin_huge_valf(); bx[3 + a] = __builtin_huge_valf(); }
+  }
+}
+
+// The f32 box of a ConstantMedium whose boundary is one static sphere, untransformed (WorldDesc::box of such a slot): the
+// rounded sums centre -+ |radius| narrowed outward, then ONE MORE step outward, because the sum itself rounded once already.
+// false: a plane is not finite, and the slot goes without a box.
+RT_HD bool medium_sphere_box32(const FlatSphere& sp, float* bx) {
+  const double c[3] = {(double)sp.cx, (double)sp.cy, (double)sp.cz}, r = rt_fabs((double)sp.radius);
+  bool finite = true;
+  for (int a = 0; a < 3; ++a) {
+    float lo = f32_narrow_down(c[a] - r), hi = f32_narrow_up(c[a] + r);
+    if (rt_fabs(lo) < __builtin_huge_valf()) lo = f32_step_down(lo);  // (an infinite plane stays where it is)
+    if (rt_fabs(hi) < __builtin_huge_valf()) hi = f32_step_up(hi);
+    bx[a] = lo; bx[3 + a] = hi;
+    finite = finite && rt_fabs(lo) < __builtin_huge_valf() && rt_fabs(hi) < __builtin_huge_valf();
+  }
+  return finite;
+}
+
+// cx cy cz radius -> the record (mat and pad stay), with the casts SceneGraph::sphere and the flattener make.
+RT_HD void set_sphere_values(FlatSphere* s, const double* v) {
+  s->cx = (real)v[0]; s->cy = (real)v[1]; s->cz = (real)v[2]; s->radius = (real)v[3];
 }
 
 // v0 v1 v2 -> the record's vertices and normal = unit((v1 - v0) x (v2 - v0)) (hit.rs:96-107), by the functions

@@ -11,6 +11,7 @@
 #include "../host/scenes.hpp"
 #include "../host/light_table.hpp"
 #include "../host/set_transforms.hpp"
+#include "../host/set_spheres.hpp"
 #include "../host/set_triangles.hpp"
 #include "../host/rebuild_instances.hpp"
 #include "abi_internal.hpp"
@@ -374,15 +375,37 @@ rtx_status rtx_flat_set_triangles(rtx_flat* f, const int32_t* ids, int64_t n, co
   return st;
 }
 
+int64_t rtx_flat_sphere_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap) {
+  if (!f || !b || (!ids && cap > 0) || cap < 0) { set_error("rtx_flat_sphere_ids: NULL argument or cap < 0"); return -1; }
+  std::string err;
+  const int64_t n = flat_sphere_ids(f->scene, b->graph, object, ids, cap, &err);
+  if (n < 0) set_error(err);
+  return n;
+}
+
+rtx_status rtx_flat_set_spheres(rtx_flat* f, const int32_t* ids, int64_t n, const double* spheres) {
+  std::string err;
+  const rtx_status st = flat_set_spheres("rtx_flat_set_spheres", f ? &f->scene : nullptr, ids, n, spheres, &err);
+  if (st != RTX_OK) set_error(err);
+  return st;
+}
+
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes) {
   if (!f) { set_error("rtx_flat_array: NULL flat"); return RTX_EINVAL; }
   const FlatScene& s = f->scene;
   const void* p = nullptr;
   size_t have = 0;
+  std::vector<rt::FlatLight> lights;  // 14: the light table as an upload would build it now (host/light_table.hpp)
+  if (which == 14) {
+    lights = build_light_table(s).lights;
+    const rtx_status st = check_array_bytes("rtx_flat_array", lights.size() * sizeof(rt::FlatLight), out, bytes);
+    if (st == RTX_OK && !lights.empty()) memcpy(out, lights.data(), lights.size() * sizeof(rt::FlatLight));
+    return st;
+  }
 #define ARR(W, VEC) case W: p = s.VEC.data(); have = s.VEC.size() * sizeof(s.VEC[0]); break;
   switch (which) {
     ARR(0, entries) ARR(1, nodes) ARR(2, nodes32) ARR(3, motion32) ARR(5, top_level) ARR(6, member_local_box)
-    ARR(10, triangles) ARR(11, top_box32) ARR(12, triangle_id)
+    ARR(10, triangles) ARR(11, top_box32) ARR(12, triangle_id) ARR(13, spheres)
     default: set_error("rtx_flat_array: which names no host array"); return RTX_EINVAL;
   }
 #undef ARR

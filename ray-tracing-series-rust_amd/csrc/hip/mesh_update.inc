@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_top_triangle_boxes(const int32_t* __res
   for (int i = (int)threadIdx.x; i < n; i += 256) {
     const int32_t slot = slots[i];
     float bx[6];
-    top_triangle_box32(triangles, (rt::PrimRef)entries[top_level[slot]].a, bx);
+    rt::plain_slot_box32((rt::PrimRef)entries[top_level[slot]].a, nullptr, nullptr, triangles, bx);  // (a triangle slot: no sphere, no rectangle)
     bool finite = true;
     for (int x = 0; x < 6; ++x) {
       top_box32[6 * (size_t)slot + x] = bx[x];
@@ -136,12 +136,68 @@ __global__ __launch_bounds__(256) void k_top_triangle_boxes(const int32_t* __res
 }
 
 // ------------------------------------------------------------------ host side
+// The launches a triangle and a sphere update (sphere_update.inc) share.  The shadow's leaf and parent tables go up with the
+// first update of either kind.
+static rtx_status upload_mesh_tables(DeviceScene* ds) {
+  MeshUpdate& mu = ds->mesh;
+  const MeshShadow& sh = mu.shadow;
+  if (mu.uploaded) return RTX_OK;
+  if (!sh.leaves.empty()) HIP_TRY(mu.d_leaves.upload(sh.leaves.data(), sh.leaves.size()));
+  if (!sh.node_parent.empty()) {
+    HIP_TRY(mu.d_node_parent.upload(sh.node_parent.data(), sh.node_parent.size()));
+    HIP_TRY(mu.d_arrivals.alloc(sh.node_parent.size() / 2 * sizeof(unsigned int)));
+  }
+  mu.uploaded = true;
+  return RTX_OK;
+}
+
+// Every touched BVH refitted whole on `stream`: k_refit_bvh, then k_refit_wide where the scene has a 4-wide tree.
+static rtx_status launch_bvh_refits(DeviceScene* ds, const std::vector<int32_t>& bvhs, hipStream_t stream) {
+  MeshUpdate& mu = ds->mesh;
+  for (int32_t bi : bvhs) {
+    const BvhShadow& b = mu.shadow.bvhs[(size_t)bi];
+    if (b.n_leaves == 0 || b.n_nodes == 0) continue;  // a leaf code for a root: only its primitives changed
+    BvhRefitArgs a;
+    a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
+    a.refs = ds->view.refs + b.first_ref;
+    a.spheres = ds->view.spheres; a.rects = ds->view.rects; a.triangles = ds->view.triangles;
+    a.leaves = mu.d_leaves + 3 * (size_t)b.leaf_first;
+    a.node_parent = mu.d_node_parent + 2 * (size_t)b.node_first;
+    a.arrivals = mu.d_arrivals + (size_t)b.node_first;
+    a.n_leaves = b.n_leaves; a.node_base = b.node_base;
+    HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)b.n_nodes * sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_refit_bvh, dim3((unsigned)((b.n_leaves + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    if (ds->wide.nodes4) {
+      hipLaunchKernelGGL(k_refit_wide, dim3((unsigned)((b.n_nodes + 255) / 256)), dim3(256), 0, stream, (const rt::FlatNode*)ds->view.nodes,
+                         (FlatNode4*)ds->wide.nodes4, b.node_base, b.n_nodes);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  return RTX_OK;
+}
+
+// The local boxes of the touched members (d_members: index, entry per member, in the call's staging), then the instance trees
+// above them.  After the BVH refits on the same stream.
+static rtx_status launch_member_refits(DeviceScene* ds, const int32_t* d_members, size_t n_members, const std::vector<int32_t>& trees, hipStream_t stream) {
+  SceneUpdate& u = ds->upd;
+  if (!n_members) return RTX_OK;
+  hipLaunchKernelGGL(k_member_local_boxes, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, stream, d_members, (int)n_members,
+                     ds->view.entries, ds->view.nodes, ds->view.refs, ds->view.spheres, ds->view.rects, ds->view.triangles, (double*)u.d_local_box);
+  HIP_TRY(hipGetLastError());
+  ds->mesh.local_box_stale = true;
+  for (int32_t t : trees) {
+    const rtx_status st = launch_instance_refit(ds, u.shadow.trees[(size_t)t], stream);
+    if (st != RTX_OK) return st;
+  }
+  return RTX_OK;
+}
+
 // ids (host memory) have passed check_triangle_ids against ds->mesh.shadow.  vertices: host memory (staged here, one copy) when
 // host_vertices, else a device pointer.  Everything that can refuse comes first; then one copy and the launches, all on `stream`.
 static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, const int32_t* ids, int64_t n, const double* vertices, bool host_vertices,
                                            hipStream_t stream) {
   MeshUpdate& mu = ds->mesh;
-  SceneUpdate& u = ds->upd;
   const MeshShadow& sh = mu.shadow;
   std::string err;
   TrianglePlan plan;
@@ -149,14 +205,8 @@ static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, con
   if (pst != RTX_OK) { set_error(err); return pst; }
   const rtx_status dst = check_scene_device(ds, who, "was uploaded to");
   if (dst != RTX_OK) return dst;
-  if (!mu.uploaded) {
-    if (!sh.leaves.empty()) HIP_TRY(mu.d_leaves.upload(sh.leaves.data(), sh.leaves.size()));
-    if (!sh.node_parent.empty()) {
-      HIP_TRY(mu.d_node_parent.upload(sh.node_parent.data(), sh.node_parent.size()));
-      HIP_TRY(mu.d_arrivals.alloc(sh.node_parent.size() / 2 * sizeof(unsigned int)));
-    }
-    mu.uploaded = true;
-  }
+  rtx_status st = upload_mesh_tables(ds);
+  if (st != RTX_OK) return st;
   // staging layout: [vertices, 72 B each (host entry only)] [pairs] [members: index, entry] [slots]
   const size_t vert_bytes = host_vertices ? (size_t)n * 9 * sizeof(double) : 0;
   const size_t n_pairs = plan.pairs.size() / 2, n_members = plan.members.size(), n_slots = plan.slots.size();
@@ -180,36 +230,8 @@ static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, con
   rt::FlatTriangle* tris = (rt::FlatTriangle*)ds->view.triangles;
   hipLaunchKernelGGL(k_set_triangles, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, d_pairs, (int)n_pairs, d_vertices, tris);
   HIP_TRY(hipGetLastError());
-  for (int32_t bi : plan.bvhs) {
-    const BvhShadow& b = sh.bvhs[(size_t)bi];
-    if (b.n_leaves == 0 || b.n_nodes == 0) continue;  // a leaf code for a root: only its triangles changed
-    BvhRefitArgs a;
-    a.nodes = (rt::FlatNode*)ds->view.nodes; a.nodes32 = (rt::FlatNode32*)ds->view.nodes32; a.motion32 = (rt::FlatMotion32*)ds->view.motion32;
-    a.refs = ds->view.refs + b.first_ref;
-    a.spheres = ds->view.spheres; a.rects = ds->view.rects; a.triangles = ds->view.triangles;
-    a.leaves = mu.d_leaves + 3 * (size_t)b.leaf_first;
-    a.node_parent = mu.d_node_parent + 2 * (size_t)b.node_first;
-    a.arrivals = mu.d_arrivals + (size_t)b.node_first;
-    a.n_leaves = b.n_leaves; a.node_base = b.node_base;
-    HIP_TRY(hipMemsetAsync(a.arrivals, 0, (size_t)b.n_nodes * sizeof(unsigned int), stream));
-    hipLaunchKernelGGL(k_refit_bvh, dim3((unsigned)((b.n_leaves + 255) / 256)), dim3(256), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    if (ds->wide.nodes4) {
-      hipLaunchKernelGGL(k_refit_wide, dim3((unsigned)((b.n_nodes + 255) / 256)), dim3(256), 0, stream, (const rt::FlatNode*)ds->view.nodes,
-                         (FlatNode4*)ds->wide.nodes4, b.node_base, b.n_nodes);
-      HIP_TRY(hipGetLastError());
-    }
-  }
-  if (n_members) {
-    hipLaunchKernelGGL(k_member_local_boxes, dim3((unsigned)((n_members + 255) / 256)), dim3(256), 0, stream, d_members, (int)n_members,
-                       ds->view.entries, ds->view.nodes, ds->view.refs, ds->view.spheres, ds->view.rects, ds->view.triangles, (double*)u.d_local_box);
-    HIP_TRY(hipGetLastError());
-    mu.local_box_stale = true;
-    for (int32_t t : plan.trees) {
-      const rtx_status st = launch_instance_refit(ds, u.shadow.trees[(size_t)t], stream);
-      if (st != RTX_OK) return st;
-    }
-  }
+  if ((st = launch_bvh_refits(ds, plan.bvhs, stream)) != RTX_OK) return st;
+  if ((st = launch_member_refits(ds, d_members, n_members, plan.trees, stream)) != RTX_OK) return st;
   if (n_slots) {
     hipLaunchKernelGGL(k_top_triangle_boxes, dim3(1), dim3(256), 0, stream, d_slots, (int)n_slots, ds->view.entries, ds->view.top_level,
                        ds->view.triangles, (float*)ds->view.top_box32, (WorldDesc*)ds->world.desc);

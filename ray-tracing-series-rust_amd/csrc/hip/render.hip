@@ -27,6 +27,7 @@
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
 #include "../core/karras.hpp"
+#include "../core/prim_box.hpp"
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
 #include "../host/update_shadow.hpp"
@@ -35,6 +36,7 @@
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
+#include "../host/set_spheres.hpp"
 #include "../host/set_triangles.hpp"
 #else
 // The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports its upload and its
@@ -165,7 +167,7 @@ struct SceneUpdate {
   UpdateShadow shadow;              // host: the slots' chains, the instance trees and their parent tables
   std::vector<double> local_box;    // host: FlatScene::member_local_box (an update's new boxes are checked before anything is enqueued)
   size_t n_entries = 0, n_nodes = 0, n_motion = 0, n_desc = 0;  // element counts of the arrays an update writes (rtx_device_scene_array)
-  size_t n_triangles = 0, n_top = 0;
+  size_t n_triangles = 0, n_top = 0, n_spheres = 0;
   DeviceBuffer<double> d_local_box;
   DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
@@ -187,7 +189,8 @@ struct SceneUpdate {
 };
 
 #ifndef RTX_F32_TU
-// rtx_scene_set_triangles (mesh_update.inc): the shadow of the upload's meshes and what the device keeps of it.  f64 scenes only.
+// rtx_scene_set_triangles (mesh_update.inc) and rtx_scene_set_spheres (sphere_update.inc): the shadow of the upload's meshes and
+// spheres and what the device keeps of it.  f64 scenes only.
 struct MeshUpdate {
   MeshShadow shadow;                             // host: id -> flat triangles, the BVHs' leaves and parent tables, members, plain slots
   bool uploaded = false;                         // the tables below are resident: done by the first update
@@ -196,6 +199,8 @@ struct MeshUpdate {
   StagingBuffer staging;                         // one call's vertices (host entry) and index lists; its own, so that a call does
                                                  // not wait for the copy of the last rtx_scene_set_transforms
   bool local_box_stale = false;                  // SceneUpdate::local_box lags behind d_local_box (scene_update.inc reads it back)
+  std::vector<char> sphere_is_light;             // host, per flat sphere: it is a sampled light (an update of it refreshes the light table)
+  DeviceBuffer<double> d_light_weight;           // k_refresh_lights' pick weights, one per light; allocated by the first such update
 };
 #endif
 
@@ -328,6 +333,7 @@ static void plan_world_stacks(DeviceScene* ds);
 #include "scene_rebuild.inc" // k_member_boxes .. k_rebuild_emit: a new topology for an instance tree of a resident scene; its cost
 #ifndef RTX_F32_TU
 #include "mesh_update.inc"   // k_set_triangles .. k_top_triangle_boxes: new vertices for triangles of a resident scene, BVHs refitted (f64 only)
+#include "sphere_update.inc" // k_set_spheres, k_sphere_slot_boxes, k_refresh_lights: a new centre and radius for static spheres (f64 only)
 #endif
 #include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
@@ -1484,6 +1490,9 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
         return st;
       }
       ds->lights.n_lights = (int32_t)lt.lights.size();
+      ds->mesh.sphere_is_light.assign(fs.spheres.size(), 0);
+      for (const rt::FlatLight& L : lt.lights)
+        if (L.kind == rt::LIGHT_SPHERE) ds->mesh.sphere_is_light[(size_t)L.prim] = 1;
     }
   }
 #endif
@@ -1702,6 +1711,30 @@ rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, 
 }
 rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream) {
   return scene_set_triangles_any("rtx_scene_set_triangles_device", s, ids, n, d_vertices, false, hip_stream);
+}
+
+// ---- moving static spheres (sphere_update.inc), entry for entry like the deforming meshes above.
+static rtx_status scene_set_spheres_any(const char* who, rtx_scene* s, const int32_t* ids, int64_t n, const double* spheres, bool host_values,
+                                        void* hip_stream) {
+  std::string err;
+  // what needs no scene first: the handle is not read before these have passed
+  if (!check_sphere_args(who, s, ids, n, spheres, &err)) { set_error(err); return RTX_EINVAL; }
+  if (!host_values && ((uintptr_t)spheres & 7)) { set_error(std::string(who) + ": d_spheres is not 8-byte aligned"); return RTX_EINVAL; }
+  if (n == 0) return RTX_OK;
+  if (s->f32) {
+    set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 records of the untouched "
+              "primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres and upload it again with rtx_scene_upload_f32");
+    return RTX_EUNSUPPORTED;
+  }
+  if (!check_sphere_ids(who, &scene_device(s)->mesh.shadow, ids, n, &err)) { set_error(err); return RTX_EINVAL; }
+  if (host_values && !check_spheres_finite(who, spheres, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return scene_set_spheres_impl(scene_device(s), who, ids, n, spheres, host_values, (hipStream_t)hip_stream);
+}
+rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, const double* spheres, void* hip_stream) {
+  return scene_set_spheres_any("rtx_scene_set_spheres", s, ids, n, spheres, true, hip_stream);
+}
+rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream) {
+  return scene_set_spheres_any("rtx_scene_set_spheres_device", s, ids, n, d_spheres, false, hip_stream);
 }
 
 // ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands

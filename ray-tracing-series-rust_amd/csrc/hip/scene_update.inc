@@ -152,7 +152,7 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   u.local_box = fs.member_local_box;
   u.n_entries = fs.entries.size(); u.n_nodes = fs.nodes.size(); u.n_motion = fs.motion32.size();
   u.n_desc = fs.top_level.size();
-  u.n_triangles = fs.triangles.size(); u.n_top = fs.top_box32.size() / 6;
+  u.n_triangles = fs.triangles.size(); u.n_top = fs.top_box32.size() / 6; u.n_spheres = fs.spheres.size();
 #ifndef RTX_F32_TU
   ds->mesh.shadow = build_mesh_shadow(fs, u.shadow);  // rtx_scene_set_triangles (mesh_update.inc); its tables go up with the first update
 #endif
@@ -258,6 +258,8 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 4: p = ds->world.desc; have = u.n_desc * sizeof(WorldDesc); break;
     case 10: p = ds->view.triangles; have = u.n_triangles * sizeof(rt::FlatTriangle); break;
     case 11: p = ds->view.top_box32; have = u.n_top * 6 * sizeof(float); break;
+    case 13: p = ds->view.spheres; have = u.n_spheres * sizeof(rt::FlatSphere); break;
+    case 14: p = ds->lights.lights; have = (size_t)ds->lights.n_lights * sizeof(rt::FlatLight); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
     case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }

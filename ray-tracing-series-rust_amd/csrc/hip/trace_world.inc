@@ -87,17 +87,8 @@ static std::vector<WorldDesc> build_world_desc(const FlatScene& fs) {
       if (d.flags & WD_MEDIUM) {
         // A medium only acts where the ray is inside its boundary within (t_min, closest) (hit.rs:969-975: t1 >= t2 returns
         // before the uniform is drawn), i.e. inside the boundary's box: the same conservative f32 test applies.
-        const rt::FlatSphere& sp = fs.spheres[rt::primref_index((rt::PrimRef)G->a)];
-        const double c[3] = {(double)sp.cx, (double)sp.cy, (double)sp.cz}, r = std::fabs((double)sp.radius);
-        bool finite = true;
-        for (int a = 0; a < 3; ++a) {
-          float lo = (float)(c[a] - r), hi = (float)(c[a] + r);
-          if ((double)lo > c[a] - r) lo = std::nextafterf(lo, -INFINITY);
-          if ((double)hi < c[a] + r) hi = std::nextafterf(hi, INFINITY);
-          lo = std::nextafterf(lo, -INFINITY); hi = std::nextafterf(hi, INFINITY);  // the sum above rounded once already
-          d.box[a] = lo; d.box[3 + a] = hi;
-          finite = finite && std::isfinite(lo) && std::isfinite(hi);
-        }
+        // (core/prim_box.hpp: medium_sphere_box32, the rule rtx_scene_set_spheres shares)
+        const bool finite = rt::medium_sphere_box32(fs.spheres[rt::primref_index((rt::PrimRef)G->a)], d.box);
         if (finite) d.flags |= WD_BOXED_PRIM;
       }
     }

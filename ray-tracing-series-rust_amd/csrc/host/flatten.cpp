@@ -52,6 +52,7 @@ struct Flattener {
   Flattener(const SceneGraph& gg, FlatScene& o, const BuildOptions& op)
       : g(gg), out(o), opt(op), prim_of(gg.hittables.size(), -1), bvh_entry_of(gg.hittables.size(), -1) {
     out.handle_triangle_id.assign(gg.hittables.size(), -1);
+    out.handle_sphere_id.assign(gg.hittables.size(), -1);
   }
 
   bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
@@ -77,6 +78,8 @@ struct Flattener {
         rt::FlatSphere s;
         s.cx = o.f[0]; s.cy = o.f[1]; s.cz = o.f[2]; s.radius = o.f[3]; s.mat = o.mat; s.pad = 0;
         out.spheres.push_back(s);
+        // its id: its index in `spheres` -- a static sphere is emitted once per handle and never moved or copied
+        out.handle_sphere_id[(size_t)h] = (int32_t)out.spheres.size() - 1;
         ref = rt::make_primref(rt::PRIM_SPHERE, (uint32_t)out.spheres.size() - 1);
         break;
       }
@@ -634,17 +637,8 @@ struct Flattener {
       if (e.kind != rt::ENTRY_PRIM) continue;
       const rt::PrimRef ref = (rt::PrimRef)e.a;
       if (rt::primref_type(ref) == rt::PRIM_MOVING_SPHERE || rt::primref_type(ref) == rt::PRIM_GRAVITY_SPHERE) continue;
-      double b[6];
-      prim_box(ref, 0.0, 0.0, b);
-      for (int a = 0; a < 3; ++a) {
-        // ordered first: a sphere of negative radius has an inverted reference box, and "outward" must mean outward
-        const double blo = std::fmin(b[a], b[3 + a]), bhi = std::fmax(b[a], b[3 + a]);
-        float lo = (float)blo;
-        if ((double)lo > blo) lo = std::nextafterf(lo, -INFINITY);
-        float hi = (float)bhi;
-        if ((double)hi < bhi) hi = std::nextafterf(hi, INFINITY);
-        if (b[a] == b[a] && b[3 + a] == b[3 + a]) { bx[a] = lo; bx[3 + a] = hi; }
-      }
+      // (core/prim_box.hpp: the rule the updates of a resident scene share)
+      rt::plain_slot_box32(ref, out.spheres.data(), out.rects.data(), out.triangles.data(), bx);
     }
     // f32 culling copy of every node: lo rounded down, hi rounded up
     out.nodes32.resize(out.nodes.size());

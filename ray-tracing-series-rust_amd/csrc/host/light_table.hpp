@@ -15,6 +15,53 @@
 #include "../core/integrator.hpp"
 #include "flat_scene.hpp"
 
+namespace rt {
+
+// ---- what the host builder below and rtx_scene_set_spheres' k_refresh_lights (hip/sphere_update.inc) share, so that a light
+// table recomputed on the device equals the one built from scratch byte for byte.
+// The area of light L and its centre, from the primitive as it now stands.
+RT_HD real light_area_centre(const FlatLight& L, const FlatSphere* spheres, const FlatRect* rects, Point3* centre) {
+  if (L.kind == LIGHT_RECT) {
+    const FlatRect& r = rects[L.prim];
+    const real a = (r.a0 + r.a1) * real(0.5), b = (r.b0 + r.b1) * real(0.5);
+    *centre = r.axis == RECT_XY ? v3(a, b, r.k) : (r.axis == RECT_XZ ? v3(a, r.k, b) : v3(r.k, a, b));
+    return (real)(rt_fabs((double)(r.a1 - r.a0)) * rt_fabs((double)(r.b1 - r.b0)));
+  }
+  const FlatSphere& sp = spheres[L.prim];
+  *centre = v3(sp.cx, sp.cy, sp.cz);
+  return (real)(4.0 * 3.14159265358979323846 * (double)sp.radius * (double)sp.radius);
+}
+// The pick weight of a light: its area times the max channel of the emitted colour at its centre -- Texture::value at
+// (0.5, 0.5, centre) of the light's texture tree -- and 0 unless that is finite and positive.
+RT_HD double light_pick_weight(const SceneView& sv, int32_t mat, real area, Point3 centre) {
+  const Color c = texture_value<F_ALL, false>(sv, sv.materials[mat].tex, real(0.5), real(0.5), centre, nullptr);
+  // (std::max's comparisons, spelled out: what a NaN channel does is part of the table's bytes)
+  const double yz = (double)c.y < (double)c.z ? (double)c.z : (double)c.y;
+  const double m = (double)c.x < yz ? yz : (double)c.x;
+  const double inf = __builtin_huge_val();
+  return rt_fabs(m) < inf && m > 0.0 && rt_fabs((double)area) < inf ? (double)area * m : 0.0;
+}
+// weight[0 .. n) -> cdf and pmf of lights[0 .. n): the serial sum, uniform weights when it is not positive and finite,
+// cdf = 1 for the last light.  Serial on purpose: the order of the additions is part of the bytes.
+RT_HD void light_cdf_pass(FlatLight* lights, double* weight, int32_t n) {
+  double sum = 0.0;
+  for (int32_t k = 0; k < n; ++k) sum += weight[k];
+  if (!(sum > 0.0) || !(rt_fabs(sum) < __builtin_huge_val())) {
+    for (int32_t k = 0; k < n; ++k) weight[k] = 1.0;
+    sum = (double)n;
+  }
+  double acc = 0.0, prev = 0.0;
+  for (int32_t k = 0; k < n; ++k) {
+    acc += weight[k];
+    const double cdf = k + 1 == n ? 1.0 : acc / sum;
+    lights[k].cdf = (real)cdf;
+    lights[k].pmf = (real)(cdf - prev);
+    prev = cdf;
+  }
+}
+
+}  // namespace rt
+
 namespace rtx {
 
 struct LightTable {
@@ -78,26 +125,11 @@ inline LightTable build_light_table(const FlatScene& fs) {
         L.slot = (int32_t)s;
         L.prim = (int32_t)i;
         L.mat = mat;
+        L.kind = type == rt::PRIM_RECT ? rt::LIGHT_RECT : rt::LIGHT_SPHERE;
+        (type == rt::PRIM_RECT ? t.n_rect : t.n_sphere) += 1;
         rt::Point3 centre;
-        if (type == rt::PRIM_RECT) {
-          const rt::FlatRect& r = fs.rects[i];
-          L.kind = rt::LIGHT_RECT;
-          L.area = (rt::real)(std::fabs((double)(r.a1 - r.a0)) * std::fabs((double)(r.b1 - r.b0)));
-          const rt::real a = (r.a0 + r.a1) * rt::real(0.5), b = (r.b0 + r.b1) * rt::real(0.5);
-          centre = r.axis == rt::RECT_XY ? rt::v3(a, b, r.k) : (r.axis == rt::RECT_XZ ? rt::v3(a, r.k, b) : rt::v3(r.k, a, b));
-          t.n_rect += 1;
-        } else {
-          const rt::FlatSphere& sp = fs.spheres[i];
-          L.kind = rt::LIGHT_SPHERE;
-          L.area = (rt::real)(4.0 * M_PI * (double)sp.radius * (double)sp.radius);
-          centre = rt::v3(sp.cx, sp.cy, sp.cz);
-          t.n_sphere += 1;
-        }
-        // the emitted colour at the centre: Texture::value at (0.5, 0.5, centre) of the light's texture tree
-        const rt::Color c = rt::texture_value<rt::F_ALL, false>(sv, fs.materials[mat].tex, rt::real(0.5), rt::real(0.5), centre,
-                                                                 nullptr);
-        const double m = std::max((double)c.x, std::max((double)c.y, (double)c.z));
-        weight.push_back(std::isfinite(m) && m > 0.0 && std::isfinite((double)L.area) ? (double)L.area * m : 0.0);
+        L.area = rt::light_area_centre(L, fs.spheres.data(), fs.rects.data(), &centre);
+        weight.push_back(rt::light_pick_weight(sv, mat, L.area, centre));
         t.total_area += (double)L.area;
         t.slot_light[s] = (int32_t)t.lights.size();
         t.lights.push_back(L);
@@ -106,20 +138,7 @@ inline LightTable build_light_table(const FlatScene& fs) {
     }
     if (!sampled && entry_emits(fs, e)) t.n_unsampled += 1;
   }
-  double sum = 0.0;
-  for (double w : weight) sum += w;
-  if (!(sum > 0.0) || !std::isfinite(sum)) {
-    for (double& w : weight) w = 1.0;
-    sum = (double)weight.size();
-  }
-  double acc = 0.0, prev = 0.0;
-  for (size_t k = 0; k < t.lights.size(); ++k) {
-    acc += weight[k];
-    const double cdf = k + 1 == t.lights.size() ? 1.0 : acc / sum;
-    t.lights[k].cdf = (rt::real)cdf;
-    t.lights[k].pmf = (rt::real)(cdf - prev);
-    prev = cdf;
-  }
+  rt::light_cdf_pass(t.lights.data(), weight.data(), (int32_t)t.lights.size());
   return t;
 }
 

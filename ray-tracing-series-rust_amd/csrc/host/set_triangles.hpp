@@ -42,6 +42,12 @@ struct MeshShadow {
   std::vector<int32_t> node_parent;              // 2 per BVH node: parent (absolute node index, -1 for a root), which child
   std::vector<MemberGeom> members;               // in the order of member_local_box
   std::vector<int32_t> prim_slot;                // 2 per plain top-level slot whose entry is one triangle: the slot, the entry
+  // rtx_*_set_spheres (host/set_spheres.hpp): a static sphere's id is its flat index, so there is no id table
+  std::vector<int32_t> sph_first, sph_entry;     // flat sphere -> the PRIM / GROUP / BVH entries that refer to it
+  // 4 per top-level slot whose f32 box comes from ONE static sphere: the slot; the sphere's PRIM entry; 0 a plain slot
+  // (top_box32 and the slot record's box), 1 the boundary of a medium without a chain (the slot record's box); for a plain slot
+  // whose next slot is such a medium, that medium's PRIM entry (the slot record says whether both hold the same sphere), else -1
+  std::vector<int32_t> sphere_slot;
   std::string broken;                            // not empty: the arrays are not what the flattener emits; the message says how
 };
 
@@ -84,19 +90,31 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     if (e.kind == rt::ENTRY_BVH) { *first = e.b; *count = e.c; return true; }
     return false;
   };
+  // (the same two passes give flat sphere -> entries)
+  const size_t n_sph = fs.spheres.size();
   sh.tri_first.assign(n_tri + 1, 0);
+  sh.sph_first.assign(n_sph + 1, 0);
   for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int32_t> at;
+    std::vector<int32_t> at, sph_at;
     if (pass == 1) {
       for (size_t t = 0; t < n_tri; ++t) sh.tri_first[t + 1] += sh.tri_first[t];
       sh.tri_entry.resize((size_t)sh.tri_first[n_tri]);
       at.assign(sh.tri_first.begin(), sh.tri_first.end() - 1);
+      for (size_t t = 0; t < n_sph; ++t) sh.sph_first[t + 1] += sh.sph_first[t];
+      sh.sph_entry.resize((size_t)sh.sph_first[n_sph]);
+      sph_at.assign(sh.sph_first.begin(), sh.sph_first.end() - 1);
     }
     for (size_t k = 0; k < n_ent; ++k) {
       const rt::FlatEntry& e = fs.entries[k];
       auto note = [&](rt::PrimRef r) {
-        if (rt::primref_type(r) != rt::PRIM_TRIANGLE) return true;
-        const uint32_t t = rt::primref_index(r);
+        const uint32_t ty = rt::primref_type(r), t = rt::primref_index(r);
+        if (ty == rt::PRIM_SPHERE) {
+          if (t >= n_sph) return false;
+          if (pass == 0) sh.sph_first[(size_t)t + 1]++;
+          else sh.sph_entry[(size_t)sph_at[t]++] = (int32_t)k;
+          return true;
+        }
+        if (ty != rt::PRIM_TRIANGLE) return true;
         if (t >= n_tri) return false;
         if (pass == 0) sh.tri_first[(size_t)t + 1]++;
         else sh.tri_entry[(size_t)at[t]++] = (int32_t)k;
@@ -104,11 +122,11 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
       };
       int64_t first = 0, count = 0;
       if (e.kind == rt::ENTRY_PRIM) {
-        if (!note((rt::PrimRef)e.a)) return broken("a primitive entry names a triangle outside the triangle array");
+        if (!note((rt::PrimRef)e.a)) return broken("a primitive entry names a triangle outside the triangle array, or a sphere outside the sphere array");
       } else if (run_of(e, &first, &count)) {
         if (first < 0 || count < 0 || (uint64_t)(first + count) > n_ref) return broken("an entry's references lie outside the reference array");
         for (int64_t i = 0; i < count; ++i)
-          if (!note(fs.refs[(size_t)(first + i)])) return broken("a reference names a triangle outside the triangle array");
+          if (!note(fs.refs[(size_t)(first + i)])) return broken("a reference names a triangle outside the triangle array, or a sphere outside the sphere array");
       }
     }
   }
@@ -195,6 +213,20 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     const rt::FlatEntry& e = fs.entries[(size_t)x];
     if (e.kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)e.a) == rt::PRIM_TRIANGLE) { sh.prim_slot.push_back((int32_t)k); sh.prim_slot.push_back(x); }
   }
+  // ---- slots whose f32 box comes from one static sphere (flatten.cpp: "boxes of the plain static primitives"; trace_world.inc:
+  // build_world_desc, the boundary sphere of a medium)
+  auto sphere_prim = [&](int32_t x) { return fs.entries[(size_t)x].kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)fs.entries[(size_t)x].a) == rt::PRIM_SPHERE; };
+  auto medium_sphere = [&](size_t k) -> int32_t {  // the PRIM entry of the boundary sphere of slot k, -1
+    if (k >= fs.top_level.size()) return -1;
+    const rt::FlatEntry& e = fs.entries[(size_t)fs.top_level[k]];
+    if (e.kind != rt::ENTRY_MEDIUM || e.a < 0 || (size_t)e.a >= n_ent) return -1;
+    return sphere_prim(e.a) ? e.a : -1;
+  };
+  for (size_t k = 0; k < fs.top_level.size(); ++k) {
+    const int32_t x = fs.top_level[k], m = medium_sphere(k);
+    if (sphere_prim(x)) { sh.sphere_slot.push_back((int32_t)k); sh.sphere_slot.push_back(x); sh.sphere_slot.push_back(0); sh.sphere_slot.push_back(medium_sphere(k + 1)); }
+    else if (m >= 0) { sh.sphere_slot.push_back((int32_t)k); sh.sphere_slot.push_back(m); sh.sphere_slot.push_back(1); sh.sphere_slot.push_back(-1); }
+  }
   return sh;
 }
 
@@ -229,6 +261,28 @@ inline bool check_vertices_finite(const char* who, const double* vertices, int64
   return true;
 }
 
+// From the touched entries (one flag per entry) to the BVHs to refit, the members whose local box changes and the instance
+// trees above them: the half of a plan the triangle and the sphere updates share.  what: "triangle" / "sphere", for the
+// message.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
+inline rtx_status plan_touched_entries(const char* who, const char* what, const MeshShadow& sh, const std::vector<char>& touched,
+                                       std::vector<int32_t>* bvhs, std::vector<int32_t>* members, std::vector<int32_t>* trees, std::string* err) {
+  for (size_t b = 0; b < sh.bvhs.size(); ++b) {
+    if (!touched[(size_t)sh.bvhs[b].entry]) continue;
+    if (sh.bvhs[b].timed) {
+      *err = std::string(who) + ": ids name a " + what + " of a BVH that holds a MovingSphere or GravitySphere (entry " + std::to_string(sh.bvhs[b].entry) +
+             "): its time-aware boxes would have to be derived again. Flatten the scene anew";
+      return RTX_EUNSUPPORTED;
+    }
+    bvhs->push_back((int32_t)b);
+  }
+  for (size_t m = 0; m < sh.members.size(); ++m) {
+    if (!touched[(size_t)sh.members[m].geom]) continue;
+    members->push_back((int32_t)m);
+    if (trees->empty() || trees->back() != sh.members[m].tree) trees->push_back(sh.members[m].tree);
+  }
+  return RTX_OK;
+}
+
 // ids (checked) -> what to write and refit.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
 inline rtx_status plan_triangle_update(const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n,
                                        TrianglePlan* plan, std::string* err) {
@@ -241,20 +295,8 @@ inline rtx_status plan_triangle_update(const char* who, const MeshShadow& sh, co
       plan->pairs.push_back((int32_t)i);
       for (int32_t q = sh.tri_first[(size_t)t]; q < sh.tri_first[(size_t)t + 1]; ++q) touched[(size_t)sh.tri_entry[(size_t)q]] = 1;
     }
-  for (size_t b = 0; b < sh.bvhs.size(); ++b) {
-    if (!touched[(size_t)sh.bvhs[b].entry]) continue;
-    if (sh.bvhs[b].timed) {
-      *err = std::string(who) + ": ids name a triangle of a BVH that holds a MovingSphere or GravitySphere (entry " + std::to_string(sh.bvhs[b].entry) +
-             "): its time-aware boxes would have to be derived again. Flatten the scene anew";
-      return RTX_EUNSUPPORTED;
-    }
-    plan->bvhs.push_back((int32_t)b);
-  }
-  for (size_t m = 0; m < sh.members.size(); ++m) {
-    if (!touched[(size_t)sh.members[m].geom]) continue;
-    plan->members.push_back((int32_t)m);
-    if (plan->trees.empty() || plan->trees.back() != sh.members[m].tree) plan->trees.push_back(sh.members[m].tree);
-  }
+  const rtx_status st = plan_touched_entries(who, "triangle", sh, touched, &plan->bvhs, &plan->members, &plan->trees, err);
+  if (st != RTX_OK) return st;
   for (size_t k = 0; k < sh.prim_slot.size(); k += 2)
     if (touched[(size_t)sh.prim_slot[k + 1]]) plan->slots.push_back(sh.prim_slot[k]);
   return RTX_OK;
@@ -304,17 +346,6 @@ RT_HD void member_local_box_of(const rt::FlatEntry& G, const rt::FlatNode* nodes
   }
 }
 
-// A plain triangle slot's top_box32 (flatten.cpp: "boxes of the plain static primitives"): the ordered box narrowed outward.
-RT_HD void top_triangle_box32(const rt::FlatTriangle* triangles, rt::PrimRef ref, float* bx) {
-  double b[6];
-  rt::static_prim_box(ref, nullptr, nullptr, triangles, b);
-  for (int a = 0; a < 3; ++a) {
-    const double blo = rt::rt_fmin(b[a], b[3 + a]), bhi = rt::rt_fmax(b[a], b[3 + a]);
-    if (b[a] == b[a] && b[3 + a] == b[3 + a]) { bx[a] = rt::f32_narrow_down(blo); bx[3 + a] = rt::f32_narrow_up(bhi); }
-    else { bx[a] = -__builtin_huge_valf(); bx[3 + a] = __builtin_huge_valf(); }
-  }
-}
-
 // BVH b of fs refitted whole, bottom-up: nodes, nodes32 and, where the scene has one, motion32's static copy.
 inline void refit_bvh(FlatScene* fs, const BvhShadow& b) {
   if (rt::node_child_is_leaf(b.root)) return;  // no node: only its triangles changed
@@ -346,7 +377,7 @@ inline rtx_status flat_set_triangles(const char* who, FlatScene* fs, const int32
                         fs->triangles.data(), &fs->member_local_box[6 * (size_t)m]);
   for (int32_t t : plan.trees) refit_instance_tree(fs, us.trees[(size_t)t]);
   for (int32_t slot : plan.slots)
-    top_triangle_box32(fs->triangles.data(), (rt::PrimRef)fs->entries[(size_t)fs->top_level[(size_t)slot]].a, &fs->top_box32[6 * (size_t)slot]);
+    rt::plain_slot_box32((rt::PrimRef)fs->entries[(size_t)fs->top_level[(size_t)slot]].a, nullptr, nullptr, fs->triangles.data(), &fs->top_box32[6 * (size_t)slot]);
   return RTX_OK;
 }
 
