@@ -23,12 +23,20 @@ struct LdsSceneDims {  // what k_trace_lds (trace_lds.inc) copies into LDS
 #define LDSK_BLOCK 1024
 #define LDSK_MAX_SLOTS 8190u    // leaf item: first < 2^13, count <= 4
 #define LDSK_MAX_NODES 8191u     // node item = split axis << 13 | index: the axis travels with the item
-#define LDSK_NODE_DWORDS 21u     // per child and axis [lo, hi, lo] (18) + the two child items + 1 of padding (odd stride: no LDS bank pile-up)
+#define LDSK_NODE_DWORDS 21u     // per child and axis [lo, hi, lo] (18) + the two child items + 1 of padding (odd stride: no LDS bank pile-up; record 0's holds the root's item)
 #define LDSK_MOTION_NODE_DWORDS 39u  // time-aware boxes: per child 9 planes + 9 slopes + the item (19), twice, + 1 of padding
 #define LDSK_MOTION1_NODE_DWORDS 27u  // ... when everything moves along ONE axis: per child 9 planes + that axis's 3 slopes + the item (13)
 #define LDSK_OFF_NODES 0u  // where the node array starts: the kernel's constant (its dynamic LDS starts at address 0, which plan_lds checks)
 #define LDSK_LEVEL_BYTES (LDSK_BLOCK * 2u)  // one stack level of the workgroup: a push or a pop moves a thread's top by exactly this
 #define LDSK_LDS_MAX (160u * 1024u)  // what the launcher fits `total` into (and no more than the device reports)
+
+// A work item is a 16-bit value kept sign-extended in a register: node >= 0 (split axis << 13 | index), leaf < -1
+// (0x8000 | first_slot << 2 | count - 1: at most 0xFFF7 = -9), done = -1 -- so "is a node" and "is a leaf" are one signed compare each.
+#define LDSK_DONE (-1)
+__host__ __device__ inline int32_t ldsk_item(int32_t child) {  // (a node's item still wants its split axis: the caller has the node)
+  if (child >= 0) return child;
+  return (int32_t)(short)(unsigned short)(0x8000u | (rt::leaf_first(child) << 2) | (rt::leaf_count(child) - 1u));
+}
 
 struct LdsKernelLayout {
   uint32_t off_nodes, off_refs, off_spheres, off_moving, off_stacks, off_ring, total;

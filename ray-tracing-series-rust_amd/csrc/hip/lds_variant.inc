@@ -40,6 +40,30 @@ inline void lds_record_counts(uint32_t features, uint32_t static_preset, uint32_
   out[2] = moving ? n_static : 0u;
 }
 
+#ifdef LDSK_DONE  // (wants ldsk_item: lds_layout.inc first, as in render.hip and tests/lds_entry_host_check.cpp)
+// Where a walk of k_trace_lds enters the tree: out[0] is the first work item, out[1] the item under it on the stack, or
+// LDSK_DONE for "nothing".  A root that is a leaf-first node (split "axis" 3: child 0, a leaf, is visited first whatever the
+// ray's direction -- bvh_build.cpp) leaves the same state behind for every ray that may hit both children: the leaf in hand,
+// child 1 stacked.  A walk that STARTS in that state skips the root step; a ray whose root step would have culled a child
+// meets that cull one step later (the leaf's own exact test, the children of child 1), and for a ray that is finite in every
+// component culling never decides a result (core/cull32.hpp; the kernel sends the others through the root).  The stack is no
+// deeper than after the root step, so its levels stay what the tree's height asks for.
+// Any other root is entered as before: {root, LDSK_DONE}.
+// N: any node record with child[2] and axis (FlatNode32).
+// Host and device: the kernel asks it of the tree it is about to copy (trace_lds.inc), a test asks it on the host.
+template <class N>
+__host__ __device__ inline void lds_entry_pair(const N* nodes, int32_t root, int32_t out[2]) {
+  const int32_t axis = nodes[root].axis, c0 = nodes[root].child[0], c1 = nodes[root].child[1];
+  if (axis == 3 && c0 < 0) {
+    out[0] = ldsk_item(c0);
+    out[1] = c1 >= 0 ? (c1 | (nodes[c1].axis << 13)) : ldsk_item(c1);
+  } else {
+    out[0] = root | (axis << 13);
+    out[1] = LDSK_DONE;
+  }
+}
+#endif
+
 // A BVH's interval admits time-aware boxes when it is ordered: the boxes are lerps between its two ends (flatten.cpp).
 inline bool lds_motion_interval_ok(double bvh_t0, double bvh_t1) { return bvh_t0 < bvh_t1; }
 

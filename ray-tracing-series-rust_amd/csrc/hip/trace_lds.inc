@@ -19,7 +19,6 @@
 // field at a compile-time offset from one per-lane base address).  Everything else -- regeneration through the per-wave ring, cost-weighted node/leaf voting, f32 culling, carry-over of straggler walks,
 // shading -- is k_trace_vote's logic; results are bit-identical (tests/test_gpu_parity.py).
 
-#define LDSK_DONE (-1)
 #define LDSK_NO_REF 0xFFFFFFFFu  // "nothing hit yet" in Closest::ref (primitive type 7 does not exist): k_trace_lds keeps no separate flag
 #ifndef LDSK_NODE_BURST
 #define LDSK_NODE_BURST 1  // node steps per vote (2 measured: see DESIGN.md 4)
@@ -45,7 +44,12 @@ __device__ __forceinline__ const LdsByte* lds_at(uint32_t addr) { return (const 
 struct LdsStack16 {  // slot (level, thread) at bottom + level * LDSK_LEVEL_BYTES
   uint32_t bottom, sp;
   __device__ __forceinline__ void init() { *(LdsU16*)lds_at(bottom) = 0xFFFFu; sp = bottom; }  // 0xFFFF sign-extends to LDSK_DONE
-  __device__ __forceinline__ void reset() { sp = bottom; }
+  // empty, then `under` (16 bits, wave-uniform) pushed unless it is "done" -- without a branch: "done" is written over slot 0,
+  // which holds it already
+  __device__ __forceinline__ void reset_with(uint32_t under) {
+    sp = bottom + (under != 0xFFFFu ? LDSK_LEVEL_BYTES : 0u);
+    set_top((int32_t)under);
+  }
   __device__ __forceinline__ void set_top(int32_t v) { *(LdsU16*)lds_at(sp) = (unsigned short)v; }
   __device__ __forceinline__ void push(int32_t v) { sp += LDSK_LEVEL_BYTES; set_top(v); }
   __device__ __forceinline__ int32_t top() const { return (int32_t)*(const LdsI16*)lds_at(sp); }  // ds_read_i16: sign-extending
@@ -60,12 +64,7 @@ struct LdsStack16 {  // slot (level, thread) at bottom + level * LDSK_LEVEL_BYTE
     sp += (uint32_t)d * LDSK_LEVEL_BYTES;
   }
 };
-// A work item is a 16-bit value kept sign-extended in a register: node >= 0 (split axis << 13 | index), leaf < -1
-// (0x8000 | first_slot << 2 | count - 1: at most 0xFFF7 = -9), done = -1 -- so "is a node" and "is a leaf" are one signed compare each.
-__host__ __device__ __forceinline__ int32_t ldsk_item(int32_t child) {
-  if (child >= 0) return child;
-  return (int32_t)(short)(unsigned short)(0x8000u | (rt::leaf_first(child) << 2) | (rt::leaf_count(child) - 1u));
-}
+// (the work items these stacks hold: ldsk_item, lds_layout.inc)
 
 // MOTION: time-aware culling boxes (core/flat_types.hpp: FlatMotion32).  Every plane of a child block is followed, 36 bytes on, by
 // its slope over the BVH's time interval, and a node step evaluates plane + s * slope (one fma) with the ray's own normalised
@@ -91,13 +90,24 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   constexpr uint32_t MA = MOTION >= 2u ? MOTION - 2u : 0u;                                                                     // the one moving axis
   constexpr uint32_t CB = CBD * 4u;                                             // ... in bytes
   constexpr uint32_t ITEM_OFF = CB - 4u;                                        // the child's work item closes its block
+  constexpr uint32_t ROOT_ITEM_DWORD = 2u * CBD;                                // node record 0's dword of padding holds the root's item
   static_assert((F & ~(rt::F_SPHERE | rt::F_MOVING_SPHERE | rt::F_BVH | rt::F_LAMBERTIAN | rt::F_METAL |
                        rt::F_DIELECTRIC | rt::F_CHECKER)) == 0, "k_trace_lds caches spheres and moving spheres only");
   extern __shared__ __attribute__((aligned(16))) unsigned char ldsk[];
   const LdsKernelLayout L = ldsk_layout(stack_levels, RING ? ring_cap : 0u, dims);
   const uint32_t lane = threadIdx.x & 63u;
   const rt::FlatEntry& bvh = sv.entries[sv.top_level[0]];
-  const int32_t root = bvh.a | (sv.nodes32[bvh.a].axis << 13);
+  // Where every walk enters (lds_entry_pair, lds_variant.inc): the root -- or, under a leaf-first root (Book-1: the ground's leaf
+  // beside the tree of everything else), the state the root step leaves for a ray that may hit both children: the leaf in hand,
+  // child 1 on stack level 1.  The root step is then not run at all.  A ray it would have spared the leaf finds no root in range
+  // in the leaf's exact test; a ray it would have spared child 1 finds both of child 1's boxes culled one step later, a step the
+  // wave runs for its other lanes anyway; the tie rule of leaf_test does not ask in which order the leaves came.  The stack is
+  // as deep as after the root step, so the sentinel slot and `stack_levels` are what they were.  (Rays with a component that is
+  // not finite are the exception: see the bounce begin.)
+  // Both items in ONE scalar register, where `root` was (the kernel has no scalar register to spare: a second one costs a VGPR).
+  int32_t entry_pair[2];
+  lds_entry_pair(sv.nodes32, bvh.a, entry_pair);
+  const uint32_t entry = ((uint32_t)entry_pair[0] & 0xFFFFu) | ((uint32_t)entry_pair[1] << 16);  // wave-uniform
   const uint32_t first_ref = (uint32_t)bvh.b;
 
   // ---- geometry -> LDS
@@ -134,6 +144,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
       }
       lds_nodes[node * ND + field] = v;
     }
+    if (threadIdx.x == 0) lds_nodes[ROOT_ITEM_DWORD] = (uint32_t)(bvh.a | (sv.nodes32[bvh.a].axis << 13));
     // The primitive records ride in LDS IN LEAF-SLOT ORDER: record k is the primitive of slot k of the BVH's reference list, so a
     // leaf step goes from its item straight to the record (no reference fetch: one dependent LDS read less per test, and the
     // reference array -- 2 KB on Book-1, what its ring of 64 was short of -- is not copied at all).  A reference of this kernel
@@ -243,8 +254,23 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
         if (UNI && mv_common != 0u) mv_ratio = (ps.ray.time - mv_t0) / (mv_t1 - mv_t0);
         if (MOTION) s32 = __builtin_fminf(__builtin_fmaxf((float)((ps.ray.time - motion_t0) * motion_inv_dt), 0.f), 1.f);
         best.t = RT_INFINITY; best.ref = LDSK_NO_REF; best.order = 0;
-        stack.reset();
-        cur = root;
+        // (unpacked HERE, from a copy the compiler cannot see through: hoisted out of the loop, the two items, "is there a second"
+        // and the address of level 1 each want a register of their own for the whole kernel)
+        uint32_t e = entry;
+        asm volatile("" : "+s"(e));
+        cur = (int32_t)(short)e;
+        stack.reset_with(e >> 16);
+        // ... for a ray that is finite in every component.  A box test also rules out rays no primitive test can: with an infinite
+        // or NaN component (a frame one pixel wide or high has such primary rays: u = x / 0) the sphere's quadratic has a NaN
+        // root, which `root < t_min || t_max < root` lets through, while the box's planes all lie at distance 0 and cull it.
+        // Such a lane starts at the root as before.  One number tells: the slopes' product is finite and not 0 (no direction
+        // component is 0, infinite or NaN), and adding 0 x (the sum of the origin terms and the time) leaves it so.
+        float fin = (q.oix + q.oiy) + q.oiz;
+        if (UNI) fin += (float)ps.ray.time;
+        if (!__builtin_amdgcn_classf(__builtin_fmaf(fin, 0.f, (q.ix * q.iy) * q.iz), 0x198u)) {  // +- normal or denormal
+          cur = *(const LdsI32*)lds_at(LDSK_OFF_NODES + ROOT_ITEM_DWORD * 4u);
+          stack.sp = stack.bottom;
+        }
         midwalk = true;
       }
     }
