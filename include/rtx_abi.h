@@ -706,13 +706,16 @@ int64_t rtx_flat_triangle_ids(const rtx_flat* f, const rtx_builder* b, rtx_handl
  * rtx_flat_set_triangles and upload it again with rtx_scene_upload_f32. */
 rtx_status rtx_flat_set_triangles(rtx_flat* f, const int32_t* ids, int64_t n, const double* vertices);
 /* A resident f64 scene; vertices is a HOST array, staged with one copy.  Asynchronous on hip_stream, as
- * rtx_scene_set_transforms: k_set_triangles, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
- * k_refit_instance_tree per touched instance tree, k_top_triangle_boxes.  One update of a scene at a time; ordering against
+ * rtx_scene_set_transforms: k_set_prims, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
+ * k_refit_instance_tree per touched instance tree, k_slot_boxes.  One update of a scene at a time; ordering against
  * work on other streams is the caller's; progressive handles made earlier hold the old shape.  rtx_multi_* scenes are not
  * covered: update the flat scene and create the handle again.
  * After an update (through either resident entry) that touched a member of an instance tree, the FIRST
  * rtx_scene_set_transforms that follows waits for the device once and reads the members' new local boxes back (48 bytes a
- * member) before it checks the new pose against them; that one call is not asynchronous.  Later ones are again. */
+ * member) before it checks the new pose against them; that one call is not asynchronous.  Later ones are again.
+ * The resident entries of both kinds check in one order: what needs no scene first (a NULL argument, n < 0, the alignment of a
+ * device pointer, n = 0) -- the handle is not read before these have passed, so an argument fault on an f32 scene is
+ * RTX_EINVAL and n = 0 on one is RTX_OK --, then the f32 refusal, the ids, the finiteness of host values. */
 rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream);
 /* d_vertices: a DEVICE pointer (8-byte aligned), e.g. the output of the caller's own skinning kernel on hip_stream; it is read
  * by work enqueued on hip_stream and must stay valid until that work is done.  Finiteness cannot be checked without a
@@ -754,8 +757,8 @@ int64_t rtx_flat_sphere_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle 
  * flat scene with rtx_flat_set_spheres and upload it again with rtx_scene_upload_f32. */
 rtx_status rtx_flat_set_spheres(rtx_flat* f, const int32_t* ids, int64_t n, const double* spheres);
 /* A resident f64 scene; spheres is a HOST array, staged with one copy.  Asynchronous on hip_stream, as
- * rtx_scene_set_triangles: k_set_spheres, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
- * k_refit_instance_tree per touched instance tree, k_sphere_slot_boxes, k_refresh_lights.  One update of a scene at a time;
+ * rtx_scene_set_triangles: k_set_prims, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and
+ * k_refit_instance_tree per touched instance tree, k_slot_boxes, k_refresh_lights.  One update of a scene at a time;
  * ordering against work on other streams is the caller's; progressive handles made earlier hold the old spheres.  rtx_multi_*
  * scenes are not covered: update the flat scene and create the handle again.  The read-back by the FIRST
  * rtx_scene_set_transforms after an update that touched a member of an instance tree applies as for rtx_scene_set_triangles. */

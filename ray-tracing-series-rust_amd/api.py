@@ -571,38 +571,26 @@ class Flat:
         """The ids of the triangles below `handle` (a triangle, a mesh's list, a BvhNode, a wrapper or medium around those) in
         list order, a mesh's faces in face order (rtx_flat_triangle_ids) -> int32 array.  A triangle's id is the ordinal of its
         first emission by the flattener; Flat.array("triangle_id") holds the id of every flat triangle."""
-        n = lib.rtx_flat_triangle_ids(self._p, builder.ptr, int(handle), None, 0)
-        if n < 0:
-            raise RtxError(RTX_EINVAL, last_error())
-        out = np.zeros(n, dtype=np.int32)
-        if n and lib.rtx_flat_triangle_ids(self._p, builder.ptr, int(handle), out.ctypes.data_as(C.POINTER(C.c_int32)), n) != n:
-            raise RtxError(RTX_EINVAL, last_error())
-        return out
+        return _prim_ids(lib.rtx_flat_triangle_ids, self, builder, handle)
 
     def set_triangles(self, ids, vertices):
         """New vertices for the triangles `ids`, in place (rtx_flat_set_triangles): the flat scene becomes the one flattened from
         scratch with these vertices, its BVHs refitted with their topology kept.  vertices: n x 9 (or n x 3 x 3) doubles, v0 v1 v2
         of ids[i]."""
-        ids, vertices = _triangle_update(ids, vertices)
+        ids, vertices = _prim_update(ids, vertices, *_TRIANGLE_VALUES)
         _check(lib.rtx_flat_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3)))
 
     def sphere_ids(self, builder, handle):
         """The ids of the static spheres below `handle` (a sphere, a list, a BvhNode, an instance tree, a wrapper or medium
         around those) in list order (rtx_flat_sphere_ids) -> int32 array.  A sphere's id is its index in Flat.array("spheres");
         moving and gravity spheres have none and are skipped."""
-        n = lib.rtx_flat_sphere_ids(self._p, builder.ptr, int(handle), None, 0)
-        if n < 0:
-            raise RtxError(RTX_EINVAL, last_error())
-        out = np.zeros(n, dtype=np.int32)
-        if n and lib.rtx_flat_sphere_ids(self._p, builder.ptr, int(handle), out.ctypes.data_as(C.POINTER(C.c_int32)), n) != n:
-            raise RtxError(RTX_EINVAL, last_error())
-        return out
+        return _prim_ids(lib.rtx_flat_sphere_ids, self, builder, handle)
 
     def set_spheres(self, ids, spheres):
         """A new centre and radius for the static spheres `ids`, in place (rtx_flat_set_spheres): the flat scene becomes the one
         flattened from scratch with these spheres, its BVHs refitted with their topology kept.  spheres: n x 4 doubles,
         cx cy cz radius of ids[i]."""
-        ids, spheres = _sphere_update(ids, spheres)
+        ids, spheres = _prim_update(ids, spheres, *_SPHERE_VALUES)
         _check(lib.rtx_flat_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3)))
 
     def rebuild_instance_trees(self, trees=None, builder="morton"):
@@ -631,26 +619,48 @@ class Flat:
         return Scene(self, f32=f32)
 
 
-def _triangle_update(ids, vertices):
-    """ids, vertices of set_triangles -> (contiguous int32 array of n ids, contiguous float64 array of 9 n values)."""
-    ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
-    vertices = np.ascontiguousarray(np.asarray(vertices, dtype=np.float64).reshape(-1))
-    if vertices.size != 9 * ids.size:
-        raise ValueError("vertices holds %d values, %d ids need %d (v0 v1 v2 each)" % (vertices.size, ids.size, 9 * ids.size))
-    if ids.size == 0:  # a pointer the library may compare with NULL
-        return np.zeros(1, dtype=np.int32)[:0], np.zeros(1, dtype=np.float64)[:0]
-    return ids, vertices
+_TRIANGLE_VALUES = (9, "vertices", "v0 v1 v2")        # width, name, each: what a set_* call holds per id
+_SPHERE_VALUES = (4, "spheres", "cx cy cz radius")
 
 
-def _sphere_update(ids, spheres):
-    """ids, spheres of set_spheres -> (contiguous int32 array of n ids, contiguous float64 array of 4 n values)."""
+def _prim_ids(fn, flat, builder, handle):
+    """rtx_flat_triangle_ids / rtx_flat_sphere_ids: once for the count, once for the ids -> int32 array."""
+    n = fn(flat.ptr, builder.ptr, int(handle), None, 0)
+    if n < 0:
+        raise RtxError(RTX_EINVAL, last_error())
+    out = np.zeros(n, dtype=np.int32)
+    if n and fn(flat.ptr, builder.ptr, int(handle), out.ctypes.data_as(C.POINTER(C.c_int32)), n) != n:
+        raise RtxError(RTX_EINVAL, last_error())
+    return out
+
+
+def _prim_update(ids, values, width, name, each):
+    """ids, values of a set_* call -> (contiguous int32 array of n ids, contiguous float64 array of width * n values)."""
     ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
-    spheres = np.ascontiguousarray(np.asarray(spheres, dtype=np.float64).reshape(-1))
-    if spheres.size != 4 * ids.size:
-        raise ValueError("spheres holds %d values, %d ids need %d (cx cy cz radius each)" % (spheres.size, ids.size, 4 * ids.size))
+    values = np.ascontiguousarray(np.asarray(values, dtype=np.float64).reshape(-1))
+    if values.size != width * ids.size:
+        raise ValueError("%s holds %d values, %d ids need %d (%s each)" % (name, values.size, ids.size, width * ids.size, each))
     if ids.size == 0:  # a pointer the library may compare with NULL
         return np.zeros(1, dtype=np.int32)[:0], np.zeros(1, dtype=np.float64)[:0]
-    return ids, spheres
+    return ids, values
+
+
+def _scene_set_prims(scene, host_fn, device_fn, ids, values, stream, width, name, each):
+    """Scene.set_triangles / set_spheres: a torch tensor on the GPU goes to the device entry as it is, anything else is staged."""
+    raw = getattr(stream, "cuda_stream", stream)
+    if hasattr(values, "data_ptr"):  # a torch tensor
+        import torch
+        if not values.is_cuda or values.dtype != torch.float64 or not values.is_contiguous():
+            raise ValueError("a tensor of %s must be a contiguous float64 tensor on the GPU" % name)
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
+        if values.numel() != width * ids.size:
+            raise ValueError("%s holds %d values, %d ids need %d (%s each)" % (name, values.numel(), ids.size, width * ids.size, each))
+        if ids.size == 0:
+            return  # n = 0 is RTX_OK with nothing launched; an empty tensor has no pointer to hand over
+        _check(device_fn(scene.ptr, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), _VP(values.data_ptr() or None), _VP(raw or None)))
+        return
+    ids, values = _prim_update(ids, values, width, name, each)
+    _check(host_fn(scene.ptr, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), values.ctypes.data_as(_D3), _VP(raw or None)))
 
 
 def _tree_list(trees):
@@ -770,22 +780,7 @@ class Scene:
         numpy array (rtx_scene_set_triangles, staged with one copy) or as a torch float64 tensor on the GPU
         (rtx_scene_set_triangles_device: e.g. the output of a skinning kernel on `stream`).  ids: host integers either way.
         Enqueued on `stream` as in set_transforms."""
-        raw = getattr(stream, "cuda_stream", stream)
-        if hasattr(vertices, "data_ptr"):  # a torch tensor
-            import torch
-            if not vertices.is_cuda or vertices.dtype != torch.float64 or not vertices.is_contiguous():
-                raise ValueError("a tensor of vertices must be a contiguous float64 tensor on the GPU")
-            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
-            if vertices.numel() != 9 * ids.size:
-                raise ValueError("vertices holds %d values, %d ids need %d (v0 v1 v2 each)" % (vertices.numel(), ids.size, 9 * ids.size))
-            if ids.size == 0:
-                return  # n = 0 is RTX_OK with nothing launched; an empty tensor has no pointer to hand over
-            _check(lib.rtx_scene_set_triangles_device(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
-                                                      _VP(vertices.data_ptr() or None), _VP(raw or None)))
-            return
-        ids, vertices = _triangle_update(ids, vertices)
-        _check(lib.rtx_scene_set_triangles(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), vertices.ctypes.data_as(_D3),
-                                           _VP(raw or None)))
+        _scene_set_prims(self, lib.rtx_scene_set_triangles, lib.rtx_scene_set_triangles_device, ids, vertices, stream, *_TRIANGLE_VALUES)
 
     def set_spheres(self, ids, spheres, stream=None):
         """A new centre and radius for the static spheres `ids` of the RESIDENT f64 scene: every later call answers as on the
@@ -793,22 +788,7 @@ class Scene:
         follows a sphere light).  spheres: n x 4 doubles cx cy cz radius as a numpy array (rtx_scene_set_spheres, staged with
         one copy) or as a torch float64 tensor on the GPU (rtx_scene_set_spheres_device: e.g. an animation computed on
         `stream`).  ids: host integers either way.  Enqueued on `stream` as in set_transforms."""
-        raw = getattr(stream, "cuda_stream", stream)
-        if hasattr(spheres, "data_ptr"):  # a torch tensor
-            import torch
-            if not spheres.is_cuda or spheres.dtype != torch.float64 or not spheres.is_contiguous():
-                raise ValueError("a tensor of spheres must be a contiguous float64 tensor on the GPU")
-            ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1))
-            if spheres.numel() != 4 * ids.size:
-                raise ValueError("spheres holds %d values, %d ids need %d (cx cy cz radius each)" % (spheres.numel(), ids.size, 4 * ids.size))
-            if ids.size == 0:
-                return  # n = 0 is RTX_OK with nothing launched; an empty tensor has no pointer to hand over
-            _check(lib.rtx_scene_set_spheres_device(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
-                                                    _VP(spheres.data_ptr() or None), _VP(raw or None)))
-            return
-        ids, spheres = _sphere_update(ids, spheres)
-        _check(lib.rtx_scene_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3),
-                                         _VP(raw or None)))
+        _scene_set_prims(self, lib.rtx_scene_set_spheres, lib.rtx_scene_set_spheres_device, ids, spheres, stream, *_SPHERE_VALUES)
 
     def rebuild_instance_trees(self, trees=None, stream=None):
         """A new topology for instance trees of the RESIDENT scene from their members' boxes at the current pose

@@ -1,7 +1,7 @@
 // The reference bounding box of one STATIC flattened primitive (hit.rs bounding_box impls): a sphere (with |radius|: see
 // host/flatten.cpp, prim_box), a rectangle (+-0.0001 on the thin axis) or a triangle.  ONE text for the flattener
-// (host/flatten.cpp), the host refits of rtx_flat_set_triangles / _set_spheres (host/set_triangles.hpp, host/set_spheres.hpp)
-// and the device refits of rtx_scene_set_triangles / _set_spheres (hip/mesh_update.inc, hip/sphere_update.inc): a refitted BVH
+// (host/flatten.cpp), the host refits of rtx_flat_set_triangles / _set_spheres (host/set_triangles.hpp)
+// and the device refits of rtx_scene_set_triangles / _set_spheres (hip/mesh_update.inc): a refitted BVH
 // is judged bit for bit against one flattened from scratch, so all of them must round alike.  Sums and differences of two
 // doubles, min and max: exact or correctly rounded in either build.  The f32 boxes of top-level slots follow the same rule:
 // plain_slot_box32 and medium_sphere_box32 below are what the flattener, the upload and the updates all call.

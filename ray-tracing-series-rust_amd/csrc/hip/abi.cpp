@@ -11,7 +11,6 @@
 #include "../host/scenes.hpp"
 #include "../host/light_table.hpp"
 #include "../host/set_transforms.hpp"
-#include "../host/set_spheres.hpp"
 #include "../host/set_triangles.hpp"
 #include "../host/rebuild_instances.hpp"
 #include "abi_internal.hpp"
@@ -363,7 +362,7 @@ rtx_status rtx_flat_instance_tree_cost(const rtx_flat* f, int32_t k, double* cos
 int64_t rtx_flat_triangle_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap) {
   if (!f || !b || (!ids && cap > 0) || cap < 0) { set_error("rtx_flat_triangle_ids: NULL argument or cap < 0"); return -1; }
   std::string err;
-  const int64_t n = flat_triangle_ids(f->scene, b->graph, object, ids, cap, &err);
+  const int64_t n = flat_prim_ids(KIND_TRIANGLE, "rtx_flat_triangle_ids", f->scene, b->graph, object, ids, cap, &err);
   if (n < 0) set_error(err);
   return n;
 }
@@ -378,7 +377,7 @@ rtx_status rtx_flat_set_triangles(rtx_flat* f, const int32_t* ids, int64_t n, co
 int64_t rtx_flat_sphere_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap) {
   if (!f || !b || (!ids && cap > 0) || cap < 0) { set_error("rtx_flat_sphere_ids: NULL argument or cap < 0"); return -1; }
   std::string err;
-  const int64_t n = flat_sphere_ids(f->scene, b->graph, object, ids, cap, &err);
+  const int64_t n = flat_prim_ids(KIND_SPHERE, "rtx_flat_sphere_ids", f->scene, b->graph, object, ids, cap, &err);
   if (n < 0) set_error(err);
   return n;
 }

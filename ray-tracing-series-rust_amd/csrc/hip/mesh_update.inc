@@ -1,32 +1,48 @@
-// rtx_scene_set_triangles / rtx_scene_set_triangles_device on a resident f64 scene (included by render.hip, namespace rtx; the
-// f64 compilation only: an f32 scene does not hold the f64 vertices of the untouched triangles in a touched leaf).
+// rtx_scene_set_triangles / rtx_scene_set_spheres and their _device entries on a resident f64 scene: ONE update path for "new
+// records of a static primitive kind" (included by render.hip, namespace rtx; the f64 compilation only: an f32 scene does not
+// hold the f64 records of the untouched primitives in a touched leaf, which a refit starts from).
 //
-// New vertices for named triangles reach these device arrays and no other:
-//   triangles                       v0 v1 v2 and the normal of every flat copy of an id (k_set_triangles)
-//   nodes / nodes32 / motion32      every BVH that holds an updated triangle, refitted whole and bottom-up (k_refit_bvh: a leaf's
+// New values for named primitives reach these device arrays and no other:
+//   triangles                       v0 v1 v2 and the normal of every flat copy of a triangle id (k_set_prims)
+//   spheres                         cx cy cz radius of the record of a sphere id; mat stays (k_set_prims)
+//   nodes / nodes32 / motion32      every BVH that holds an updated primitive, refitted whole and bottom-up (k_refit_bvh: a leaf's
 //                                   box, then scene_update.inc's refit_climb)
 //   nodes4                          the planes of every slot of those BVHs' wide records; which nodes the collapse opened is kept,
 //                                   so WidePlan::levels and every launch plan stand (k_refit_wide)
 //   d_local_box, then the instance tree above a touched member (k_member_local_boxes, k_refit_instance_tree of scene_update.inc)
-//   top_box32 / WorldDesc::box      a plain top-level triangle slot (k_top_triangle_boxes)
+//   top_box32 / WorldDesc           a plain top-level slot of one updated triangle or sphere: both boxes and the record's "box is
+//                                   finite" flag (k_slot_boxes, with core/prim_box.hpp's rules)
+// and for spheres only:
+//   WorldDesc                       the boundary sphere of a medium: the record's box and "box is finite" flag; a plain sphere
+//                                   slot before such a medium: the "same sphere as the medium behind me" flag (k_slot_boxes)
+//   the light table                 when an updated sphere is a sampled light: its area, and every light's cdf and pmf
+//                                   (k_refresh_lights, with host/light_table.hpp's weight rule and cdf pass)
 // with the arithmetic of the flattener (core/prim_box.hpp, host/set_triangles.hpp), so that the arrays equal those of the
-// host-updated flat scene uploaded afresh -- the judge of tests/test_gpu_set_triangles.py.  Topology is not touched: child
-// codes, split axes, refs, entries; SceneView, the trace kernels and their arguments do not change.
+// host-updated flat scene uploaded afresh -- the judge of tests/test_gpu_set_triangles.py and tests/test_gpu_set_spheres.py.
+// k_trace_lds copies nodes32 and the sphere records into LDS at the start of every launch and keeps no packed copy from the
+// upload, so it needs nothing more.  Topology is not touched: child codes, split axes, refs, entries; SceneView, the trace
+// kernels, their arguments and every launch plan do not change.
 //
-// No index is derived from a vertex.  Every index a kernel forms comes from a table the host built from the caller's ids and
-// the upload's shadow, both checked against the array sizes (host/set_triangles.hpp: build_mesh_shadow, check_triangle_ids);
-// a vertex is only ever stored or compared.  A non-finite vertex through the device entry therefore cannot leave an
-// allocation: it gives its triangle and the boxes above it unspecified culling.
+// No index is derived from a value.  Every index a kernel forms comes from a table the host built from the caller's ids and
+// the upload's shadow, both checked against the array sizes (host/set_triangles.hpp: build_mesh_shadow, check_prim_ids); a
+// value is only ever stored, added or compared.  A non-finite value through a device entry therefore cannot leave an
+// allocation: it gives its primitive and the boxes above it unspecified culling.  The kernels here need no visibility beyond
+// kernel boundaries: each thread writes what only it owns (the climb of a refit states its own, once, in scene_update.inc).
 
-// One thread per (flat triangle, vertex triple): pairs[2 i] = flat index, pairs[2 i + 1] = index of the triple in `vertices`.
-__global__ __launch_bounds__(256) void k_set_triangles(const int32_t* __restrict__ pairs, int n_pairs, const double* __restrict__ vertices,
-                                                      rt::FlatTriangle* __restrict__ triangles) {
+__device__ __forceinline__ void set_record(rt::FlatTriangle* t, const double* v) { rt::set_triangle_vertices(t, v); }
+__device__ __forceinline__ void set_record(rt::FlatSphere* s, const double* v) { rt::set_sphere_values(s, v); }
+
+// One thread per (flat record, the caller's W values for it): pairs[2 i] = flat index, pairs[2 i + 1] = index of the W-tuple in
+// `values`.
+template <int W, class Record>
+__global__ __launch_bounds__(256) void k_set_prims(const int32_t* __restrict__ pairs, int n_pairs, const double* __restrict__ values,
+                                                  Record* __restrict__ records) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= n_pairs) return;
-  double v[9];
-  const double* src = vertices + 9 * (size_t)pairs[2 * (size_t)i + 1];
-  for (int k = 0; k < 9; ++k) v[k] = src[k];
-  rt::set_triangle_vertices(&triangles[pairs[2 * (size_t)i]], v);
+  double v[W];
+  const double* src = values + W * (size_t)pairs[2 * (size_t)i + 1];
+  for (int k = 0; k < W; ++k) v[k] = src[k];
+  set_record(&records[pairs[2 * (size_t)i]], v);
 }
 
 struct BvhRefitArgs {
@@ -116,28 +132,62 @@ __global__ __launch_bounds__(256) void k_member_local_boxes(const int32_t* __res
   for (int x = 0; x < 6; ++x) local_box[6 * (size_t)list[2 * (size_t)i] + x] = b[x];
 }
 
-// One block: the touched plain triangle slots.  top_box32 and the box (and the flag that says it is finite) of the slot's
-// WorldDesc record, as build_world_desc derives them.
-__global__ __launch_bounds__(256) void k_top_triangle_boxes(const int32_t* __restrict__ slots, int n, const rt::FlatEntry* __restrict__ entries,
-                                                           const int32_t* __restrict__ top_level, const rt::FlatTriangle* __restrict__ triangles,
-                                                           float* __restrict__ top_box32, WorldDesc* __restrict__ desc) {
-  for (int i = (int)threadIdx.x; i < n; i += 256) {
-    const int32_t slot = slots[i];
-    float bx[6];
-    rt::plain_slot_box32((rt::PrimRef)entries[top_level[slot]].a, nullptr, nullptr, triangles, bx);  // (a triangle slot: no sphere, no rectangle)
-    bool finite = true;
+// One thread per listed slot: slots[2 i] = the slot, slots[2 i + 1] = 0 a plain triangle or static sphere, 1 a medium bounded
+// by a sphere.  top_box32 (plain only) and the box, the WD_BOXED_PRIM and the WD_PAIR flag of the slot's WorldDesc record, as
+// the flattener and build_world_desc derive them; a triangle slot has no WD_SPHERE flag and so no pair rule.  A thread writes
+// its own slot's record only; of the next slot's it reads what no update changes (flags other than WD_BOXED_PRIM, g_a).
+__global__ __launch_bounds__(256) void k_slot_boxes(const int32_t* __restrict__ slots, int n, int n_top, const rt::FlatEntry* __restrict__ entries,
+                                                   const int32_t* __restrict__ top_level, const rt::FlatSphere* __restrict__ spheres,
+                                                   const rt::FlatRect* __restrict__ rects, const rt::FlatTriangle* __restrict__ triangles,
+                                                   float* __restrict__ top_box32, WorldDesc* __restrict__ desc) {
+  const int i = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (i >= n) return;
+  const int32_t slot = slots[2 * (size_t)i];
+  const bool medium = slots[2 * (size_t)i + 1] != 0;
+  const rt::FlatEntry E = entries[top_level[slot]];
+  const rt::PrimRef ref = (rt::PrimRef)(medium ? entries[E.a].a : E.a);
+  float bx[6];
+  bool finite = true;
+  if (medium) finite = rt::medium_sphere_box32(spheres[rt::primref_index(ref)], bx);
+  else {
+    rt::plain_slot_box32(ref, spheres, rects, triangles, bx);
     for (int x = 0; x < 6; ++x) {
       top_box32[6 * (size_t)slot + x] = bx[x];
-      if (desc) desc[slot].box[x] = bx[x];
       finite = finite && rt::rt_fabs(bx[x]) < __builtin_huge_valf();
     }
-    if (desc) desc[slot].flags = finite ? (desc[slot].flags | WD_BOXED_PRIM) : (desc[slot].flags & ~WD_BOXED_PRIM);
   }
+  if (!desc) return;
+  for (int x = 0; x < 6; ++x) desc[slot].box[x] = bx[x];
+  int32_t flags = finite ? (desc[slot].flags | WD_BOXED_PRIM) : (desc[slot].flags & ~WD_BOXED_PRIM);
+  if (!medium && (flags & WD_SPHERE) && slot + 1 < n_top) {
+    const int32_t next = desc[slot + 1].flags;
+    if ((next & WD_SPHERE) && (next & WD_MEDIUM)) {
+      const rt::FlatSphere& a = spheres[rt::primref_index(ref)];
+      const rt::FlatSphere& b = spheres[rt::primref_index((rt::PrimRef)desc[slot + 1].g_a)];
+      // centre and radius, bit for bit (build_world_desc compares the bytes)
+      const bool same = __double_as_longlong(a.cx) == __double_as_longlong(b.cx) && __double_as_longlong(a.cy) == __double_as_longlong(b.cy) &&
+                        __double_as_longlong(a.cz) == __double_as_longlong(b.cz) && __double_as_longlong(a.radius) == __double_as_longlong(b.radius);
+      flags = same ? (flags | WD_PAIR) : (flags & ~WD_PAIR);
+    }
+  }
+  desc[slot].flags = flags;
+}
+
+// ONE block.  A thread per light (in strides of the block) for the area and the pick weight; then one thread for the serial
+// sum, the fallback and the cdf: lights are few, and the serial order of the additions is what makes the bytes the host's.
+__global__ __launch_bounds__(256) void k_refresh_lights(rt::SceneView sv, rt::FlatLight* __restrict__ lights, int32_t n_lights, double* __restrict__ weight) {
+  for (int32_t k = (int32_t)threadIdx.x; k < n_lights; k += 256) {
+    rt::Point3 centre;
+    const rt::real area = rt::light_area_centre(lights[k], sv.spheres, sv.rects, &centre);
+    if (lights[k].kind == rt::LIGHT_SPHERE) lights[k].area = area;
+    weight[k] = rt::light_pick_weight(sv, lights[k].mat, area, centre);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) rt::light_cdf_pass(lights, weight, n_lights);
 }
 
 // ------------------------------------------------------------------ host side
-// The launches a triangle and a sphere update (sphere_update.inc) share.  The shadow's leaf and parent tables go up with the
-// first update of either kind.
+// The shadow's leaf and parent tables go up with the first update of either kind.
 static rtx_status upload_mesh_tables(DeviceScene* ds) {
   MeshUpdate& mu = ds->mesh;
   const MeshShadow& sh = mu.shadow;
@@ -193,48 +243,59 @@ static rtx_status launch_member_refits(DeviceScene* ds, const int32_t* d_members
   return RTX_OK;
 }
 
-// ids (host memory) have passed check_triangle_ids against ds->mesh.shadow.  vertices: host memory (staged here, one copy) when
-// host_vertices, else a device pointer.  Everything that can refuse comes first; then one copy and the launches, all on `stream`.
-static rtx_status scene_set_triangles_impl(DeviceScene* ds, const char* who, const int32_t* ids, int64_t n, const double* vertices, bool host_vertices,
-                                           hipStream_t stream) {
+// ids (host memory) have passed check_prim_ids against ds->mesh.shadow.  values: host memory (staged here, one copy) when
+// host_values, else a device pointer.  Everything that can refuse comes first; then one copy and the launches, all on `stream`.
+static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const char* who, const int32_t* ids, int64_t n, const double* values,
+                                       bool host_values, hipStream_t stream) {
   MeshUpdate& mu = ds->mesh;
   const MeshShadow& sh = mu.shadow;
+  const bool tri = K.type == rt::PRIM_TRIANGLE;
   std::string err;
-  TrianglePlan plan;
-  const rtx_status pst = plan_triangle_update(who, sh, ids, n, &plan, &err);
+  UpdatePlan plan;
+  const rtx_status pst = plan_prim_update(K, who, sh, ids, n, &plan, &err);
   if (pst != RTX_OK) { set_error(err); return pst; }
   const rtx_status dst = check_scene_device(ds, who, "was uploaded to");
   if (dst != RTX_OK) return dst;
   rtx_status st = upload_mesh_tables(ds);
   if (st != RTX_OK) return st;
-  // staging layout: [vertices, 72 B each (host entry only)] [pairs] [members: index, entry] [slots]
-  const size_t vert_bytes = host_vertices ? (size_t)n * 9 * sizeof(double) : 0;
-  const size_t n_pairs = plan.pairs.size() / 2, n_members = plan.members.size(), n_slots = plan.slots.size();
-  const size_t bytes = vert_bytes + (2 * n_pairs + 2 * n_members + n_slots) * sizeof(int32_t);
+  bool lights = false;  // a listed sphere is a sampled light
+  for (int64_t i = 0; !tri && i < n; ++i) lights = lights || ((size_t)ids[i] < mu.sphere_is_light.size() && mu.sphere_is_light[(size_t)ids[i]]);
+  if (lights && !mu.d_light_weight) HIP_TRY(mu.d_light_weight.alloc((size_t)ds->lights.n_lights * sizeof(double)));
+  // staging layout: [values, width x 8 B each (host entry only)] [pairs] [members: index, entry] [slots: slot, kind]
+  const size_t value_bytes = host_values ? (size_t)n * (size_t)K.width * sizeof(double) : 0;
+  const size_t n_pairs = plan.pairs.size() / 2, n_members = plan.members.size(), n_slots = plan.slots.size() / 2;
+  const size_t bytes = value_bytes + (2 * n_pairs + 2 * n_members + 2 * n_slots) * sizeof(int32_t);
   void* pinned = nullptr;
   HIP_TRY(mu.staging.reserve(bytes, stream, &pinned));
   unsigned char* h = (unsigned char*)pinned;
-  if (host_vertices) memcpy(h, vertices, vert_bytes);
-  int32_t* h_pairs = (int32_t*)(h + vert_bytes);
+  if (host_values) memcpy(h, values, value_bytes);
+  int32_t* h_pairs = (int32_t*)(h + value_bytes);
   int32_t* h_members = h_pairs + 2 * n_pairs;
   int32_t* h_slots = h_members + 2 * n_members;
   memcpy(h_pairs, plan.pairs.data(), 2 * n_pairs * sizeof(int32_t));
   for (size_t k = 0; k < n_members; ++k) { h_members[2 * k] = plan.members[k]; h_members[2 * k + 1] = sh.members[(size_t)plan.members[k]].geom; }
-  if (n_slots) memcpy(h_slots, plan.slots.data(), n_slots * sizeof(int32_t));
+  if (n_slots) memcpy(h_slots, plan.slots.data(), 2 * n_slots * sizeof(int32_t));
   HIP_TRY(mu.staging.copy(bytes, stream));
   unsigned char* d = mu.staging.device();
-  const double* d_vertices = host_vertices ? (const double*)d : vertices;
-  const int32_t* d_pairs = (const int32_t*)(d + vert_bytes);
+  const double* d_values = host_values ? (const double*)d : values;
+  const int32_t* d_pairs = (const int32_t*)(d + value_bytes);
   const int32_t* d_members = d_pairs + 2 * n_pairs;
   const int32_t* d_slots = d_members + 2 * n_members;
-  rt::FlatTriangle* tris = (rt::FlatTriangle*)ds->view.triangles;
-  hipLaunchKernelGGL(k_set_triangles, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, d_pairs, (int)n_pairs, d_vertices, tris);
+  const dim3 pair_grid((unsigned)((n_pairs + 255) / 256));
+  if (tri) hipLaunchKernelGGL((k_set_prims<9, rt::FlatTriangle>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatTriangle*)ds->view.triangles);
+  else hipLaunchKernelGGL((k_set_prims<4, rt::FlatSphere>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatSphere*)ds->view.spheres);
   HIP_TRY(hipGetLastError());
   if ((st = launch_bvh_refits(ds, plan.bvhs, stream)) != RTX_OK) return st;
   if ((st = launch_member_refits(ds, d_members, n_members, plan.trees, stream)) != RTX_OK) return st;
   if (n_slots) {
-    hipLaunchKernelGGL(k_top_triangle_boxes, dim3(1), dim3(256), 0, stream, d_slots, (int)n_slots, ds->view.entries, ds->view.top_level,
-                       ds->view.triangles, (float*)ds->view.top_box32, (WorldDesc*)ds->world.desc);
+    hipLaunchKernelGGL(k_slot_boxes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, stream, d_slots, (int)n_slots, ds->view.n_top_level,
+                       ds->view.entries, ds->view.top_level, ds->view.spheres, ds->view.rects, ds->view.triangles, (float*)ds->view.top_box32,
+                       (WorldDesc*)ds->world.desc);
+    HIP_TRY(hipGetLastError());
+  }
+  if (lights) {
+    hipLaunchKernelGGL(k_refresh_lights, dim3(1), dim3(256), 0, stream, ds->view, (rt::FlatLight*)ds->lights.lights, ds->lights.n_lights,
+                       (double*)mu.d_light_weight);
     HIP_TRY(hipGetLastError());
   }
   return RTX_OK;

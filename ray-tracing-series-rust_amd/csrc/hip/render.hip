@@ -36,7 +36,6 @@
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
 #include "abi_internal.hpp"
-#include "../host/set_spheres.hpp"
 #include "../host/set_triangles.hpp"
 #else
 // The f32 compilation of this file (render_f32.hip) sees none of the C ABI's handle types: it exports its upload and its
@@ -189,8 +188,8 @@ struct SceneUpdate {
 };
 
 #ifndef RTX_F32_TU
-// rtx_scene_set_triangles (mesh_update.inc) and rtx_scene_set_spheres (sphere_update.inc): the shadow of the upload's meshes and
-// spheres and what the device keeps of it.  f64 scenes only.
+// rtx_scene_set_triangles and rtx_scene_set_spheres (mesh_update.inc): the shadow of the upload's meshes and spheres and what
+// the device keeps of it.  f64 scenes only.
 struct MeshUpdate {
   MeshShadow shadow;                             // host: id -> flat triangles, the BVHs' leaves and parent tables, members, plain slots
   bool uploaded = false;                         // the tables below are resident: done by the first update
@@ -332,8 +331,7 @@ static size_t stack_bytes(uint32_t levels);
 static void plan_world_stacks(DeviceScene* ds);
 #include "scene_rebuild.inc" // k_member_boxes .. k_rebuild_emit: a new topology for an instance tree of a resident scene; its cost
 #ifndef RTX_F32_TU
-#include "mesh_update.inc"   // k_set_triangles .. k_top_triangle_boxes: new vertices for triangles of a resident scene, BVHs refitted (f64 only)
-#include "sphere_update.inc" // k_set_spheres, k_sphere_slot_boxes, k_refresh_lights: a new centre and radius for static spheres (f64 only)
+#include "mesh_update.inc"   // k_set_prims .. k_refresh_lights: new records for triangles / static spheres of a resident scene, BVHs refitted (f64 only)
 #endif
 #include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
@@ -1689,52 +1687,39 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
   return s->ops->set_transforms(s->device_scene, resolved.data(), n, (hipStream_t)hip_stream);
 }
 
-// ---- deforming meshes (mesh_update.inc).  The checks shared with rtx_flat_set_triangles (host/set_triangles.hpp) come first,
-// against the shadow the scene kept from its upload; nothing is enqueued before every check has passed.
-static rtx_status scene_set_triangles_any(const char* who, rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, bool host_vertices,
-                                          void* hip_stream) {
+// ---- deforming meshes and moving static spheres (mesh_update.inc): one ladder for the four entries.  What needs no scene
+// comes first -- the handle is not read before it has passed -- then the checks shared with rtx_flat_set_triangles /
+// _set_spheres (host/set_triangles.hpp) against the shadow the scene kept from its upload; nothing is enqueued before every
+// check has passed.
+static rtx_status scene_set_prims_any(const PrimKind& K, const char* who, rtx_scene* s, const int32_t* ids, int64_t n, const double* values,
+                                      bool host_values, void* hip_stream) {
   std::string err;
-  if (s && s->f32) {
-    set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 vertices of the untouched "
-              "triangles in touched leaves. Update the flat scene with rtx_flat_set_triangles and upload it again with rtx_scene_upload_f32");
-    return RTX_EUNSUPPORTED;
-  }
-  const MeshShadow* sh = s ? &scene_device(s)->mesh.shadow : nullptr;
-  if (!check_triangle_ids(who, s, sh, ids, n, vertices, &err)) { set_error(err); return RTX_EINVAL; }
-  if (!host_vertices && ((uintptr_t)vertices & 7)) { set_error(std::string(who) + ": d_vertices is not 8-byte aligned"); return RTX_EINVAL; }
-  if (n == 0) return RTX_OK;
-  if (host_vertices && !check_vertices_finite(who, vertices, n, &err)) { set_error(err); return RTX_EINVAL; }
-  return scene_set_triangles_impl(scene_device(s), who, ids, n, vertices, host_vertices, (hipStream_t)hip_stream);
-}
-rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream) {
-  return scene_set_triangles_any("rtx_scene_set_triangles", s, ids, n, vertices, true, hip_stream);
-}
-rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream) {
-  return scene_set_triangles_any("rtx_scene_set_triangles_device", s, ids, n, d_vertices, false, hip_stream);
-}
-
-// ---- moving static spheres (sphere_update.inc), entry for entry like the deforming meshes above.
-static rtx_status scene_set_spheres_any(const char* who, rtx_scene* s, const int32_t* ids, int64_t n, const double* spheres, bool host_values,
-                                        void* hip_stream) {
-  std::string err;
-  // what needs no scene first: the handle is not read before these have passed
-  if (!check_sphere_args(who, s, ids, n, spheres, &err)) { set_error(err); return RTX_EINVAL; }
-  if (!host_values && ((uintptr_t)spheres & 7)) { set_error(std::string(who) + ": d_spheres is not 8-byte aligned"); return RTX_EINVAL; }
+  if (!check_prim_args(K, who, s, ids, n, values, &err)) { set_error(err); return RTX_EINVAL; }
+  if (!host_values && ((uintptr_t)values & 7)) { set_error(std::string(who) + ": " + K.d_arg + " is not 8-byte aligned"); return RTX_EINVAL; }
   if (n == 0) return RTX_OK;
   if (s->f32) {
-    set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 records of the untouched "
-              "primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres and upload it again with rtx_scene_upload_f32");
+    set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 " +
+              (K.type == rt::PRIM_TRIANGLE
+                   ? "vertices of the untouched triangles in touched leaves. Update the flat scene with rtx_flat_set_triangles"
+                   : "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres") +
+              " and upload it again with rtx_scene_upload_f32");
     return RTX_EUNSUPPORTED;
   }
-  if (!check_sphere_ids(who, &scene_device(s)->mesh.shadow, ids, n, &err)) { set_error(err); return RTX_EINVAL; }
-  if (host_values && !check_spheres_finite(who, spheres, n, &err)) { set_error(err); return RTX_EINVAL; }
-  return scene_set_spheres_impl(scene_device(s), who, ids, n, spheres, host_values, (hipStream_t)hip_stream);
+  if (!check_prim_ids(K, who, scene_device(s)->mesh.shadow, ids, n, &err)) { set_error(err); return RTX_EINVAL; }
+  if (host_values && !check_prims_finite(K, who, values, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return scene_set_prims_impl(scene_device(s), K, who, ids, n, values, host_values, (hipStream_t)hip_stream);
+}
+rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream) {
+  return scene_set_prims_any(KIND_TRIANGLE, "rtx_scene_set_triangles", s, ids, n, vertices, true, hip_stream);
+}
+rtx_status rtx_scene_set_triangles_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_vertices, void* hip_stream) {
+  return scene_set_prims_any(KIND_TRIANGLE, "rtx_scene_set_triangles_device", s, ids, n, d_vertices, false, hip_stream);
 }
 rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, const double* spheres, void* hip_stream) {
-  return scene_set_spheres_any("rtx_scene_set_spheres", s, ids, n, spheres, true, hip_stream);
+  return scene_set_prims_any(KIND_SPHERE, "rtx_scene_set_spheres", s, ids, n, spheres, true, hip_stream);
 }
 rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream) {
-  return scene_set_spheres_any("rtx_scene_set_spheres_device", s, ids, n, d_spheres, false, hip_stream);
+  return scene_set_prims_any(KIND_SPHERE, "rtx_scene_set_spheres_device", s, ids, n, d_spheres, false, hip_stream);
 }
 
 // ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands

@@ -47,7 +47,7 @@ struct FlatScene {
   std::vector<int32_t> triangle_id;
   // Per graph hittable at the time of the flatten: the id of an emitted triangle, -1 for anything else (rtx_flat_triangle_ids).
   std::vector<int32_t> handle_triangle_id;
-  // What rtx_*_set_spheres names a static sphere by (host/set_spheres.hpp): its index in `spheres` -- a static sphere is emitted
+  // What rtx_*_set_spheres names a static sphere by (host/set_triangles.hpp): its index in `spheres` -- a static sphere is emitted
   // once per handle and is neither permuted nor copied.  Per graph hittable at the time of the flatten: that index, -1 for
   // anything else (rtx_flat_sphere_ids).  Last, so that nothing that reads this struct by its layout moves.
   std::vector<int32_t> handle_sphere_id;

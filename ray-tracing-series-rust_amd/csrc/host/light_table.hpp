@@ -17,7 +17,7 @@
 
 namespace rt {
 
-// ---- what the host builder below and rtx_scene_set_spheres' k_refresh_lights (hip/sphere_update.inc) share, so that a light
+// ---- what the host builder below and rtx_scene_set_spheres' k_refresh_lights (hip/mesh_update.inc) share, so that a light
 // table recomputed on the device equals the one built from scratch byte for byte.
 // The area of light L and its centre, from the primitive as it now stands.
 RT_HD real light_area_centre(const FlatLight& L, const FlatSphere* spheres, const FlatRect* rects, Point3* centre) {

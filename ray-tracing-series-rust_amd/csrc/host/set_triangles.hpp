@@ -1,16 +1,22 @@
-// rtx_flat_set_triangles on the host, the shadow a scene keeps for rtx_scene_set_triangles, and the checks and the plan of an
-// update that all three entries share.  Pure host code of the f64 side: abi.cpp, render.hip's f64 compilation and
-// tests/set_triangles_host_check.cpp compile it.  The twin of host/set_transforms.hpp.
+// rtx_flat_set_triangles, rtx_flat_set_spheres and the two rtx_flat_*_ids on the host, the shadow a scene keeps for the resident
+// entries, and the ONE update path "new records for named static primitives" that all six entries share: argument check, id
+// check, finiteness, plan, edit.  A kind (PrimKind: a triangle, a static sphere) is a constant; where the kinds differ in code
+// and not in data, the shared function asks which one it has.  Pure host code of the f64 side: abi.cpp, render.hip's f64
+// compilation and tests/set_{triangles,spheres}_host_check.cpp compile it.  The twin of host/set_transforms.hpp.
 //
-// An update gives named triangles new vertices; the result must be the flat scene flatten_scene builds from scratch with those
-// vertices, byte for byte where a vertex reaches: the triangle records (every flat copy of an id), the boxes in `nodes`,
-// `nodes32` and the static copy in `motion32` of every BVH that holds an updated triangle, `member_local_box` and the
-// instance tree above a touched member, and `top_box32` of a plain triangle slot.  Topology (child, axis, pad), refs, entries,
-// sah_cost and every other array stay as they are; a fresh build may choose another topology, which is culling only.
+// An update gives named primitives new values -- a triangle v0 v1 v2, a static sphere cx cy cz radius (mat stays) -- and the
+// result must be the flat scene flatten_scene builds from scratch with those values, byte for byte where a value reaches: the
+// records (every flat copy of a triangle id), the boxes in `nodes`, `nodes32` and the static copy in `motion32` of every BVH
+// that holds an updated primitive, `member_local_box` and the instance tree above a touched member, and `top_box32` of a plain
+// slot of the kind.  Topology (child, axis, pad), refs, entries, sah_cost and every other array stay as they are; a fresh build
+// may choose another topology, which is culling only.  A flat scene keeps no light table and no slot records: both are derived
+// from these arrays when asked for (host/light_table.hpp) or at upload (hip/trace_world.inc).
 //
-// No index is ever derived from a vertex: every index an update uses comes from the caller's ids (checked against the id
-// table) or from the shadow, which build_mesh_shadow validates against the array sizes.  A vertex only ever becomes a
-// coordinate, a normal or a box plane.
+// A triangle's id is the ordinal of its first emission (FlatScene::triangle_id: a BVH stores copies in leaf order).  A sphere's
+// id is its index in FlatScene::spheres: the flattener emits a static sphere once per handle and neither moves nor copies it.
+// No index is ever derived from a value: every index an update uses comes from the caller's ids (checked against the shadow)
+// or from the shadow, which build_mesh_shadow validates against the array sizes.  A value only ever becomes a coordinate, a
+// radius, a normal or a box plane.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -41,23 +47,34 @@ struct MeshShadow {
   std::vector<int32_t> leaves;                   // 3 per leaf: leaf code, the node that holds its box, which child
   std::vector<int32_t> node_parent;              // 2 per BVH node: parent (absolute node index, -1 for a root), which child
   std::vector<MemberGeom> members;               // in the order of member_local_box
-  std::vector<int32_t> prim_slot;                // 2 per plain top-level slot whose entry is one triangle: the slot, the entry
-  // rtx_*_set_spheres (host/set_spheres.hpp): a static sphere's id is its flat index, so there is no id table
+  // a static sphere's id is its flat index, so there is no id table
   std::vector<int32_t> sph_first, sph_entry;     // flat sphere -> the PRIM / GROUP / BVH entries that refer to it
-  // 4 per top-level slot whose f32 box comes from ONE static sphere: the slot; the sphere's PRIM entry; 0 a plain slot
-  // (top_box32 and the slot record's box), 1 the boundary of a medium without a chain (the slot record's box); for a plain slot
-  // whose next slot is such a medium, that medium's PRIM entry (the slot record says whether both hold the same sphere), else -1
-  std::vector<int32_t> sphere_slot;
+  // 4 per top-level slot whose f32 box comes from ONE triangle or static sphere: the slot; the primitive's PRIM entry; 0 a plain
+  // slot (top_box32 and the slot record's box), 1 the boundary sphere of a medium without a chain (the slot record's box); for
+  // a plain sphere slot whose next slot is such a medium, that medium's PRIM entry (the slot record says whether both hold the
+  // same sphere), else -1.  A plain triangle slot is (slot, entry, 0, -1).
+  std::vector<int32_t> slot_box;
   std::string broken;                            // not empty: the arrays are not what the flattener emits; the message says how
 };
 
+// A kind of static primitive an update can name.  Data only; code that differs asks `type`.
+struct PrimKind {
+  uint32_t type;             // rt::PRIM_TRIANGLE / rt::PRIM_SPHERE
+  int width;                 // doubles per record of the caller's values
+  const char* noun;          // in messages
+  const char* count_phrase;  // "the scene has N ..."
+  const char *arg, *d_arg;   // the values' argument name in the host and in the device entry
+};
+constexpr PrimKind KIND_TRIANGLE = {rt::PRIM_TRIANGLE, 9, "triangle", "triangle ids", "vertices", "d_vertices"};
+constexpr PrimKind KIND_SPHERE = {rt::PRIM_SPHERE, 4, "sphere", "static spheres", "spheres", "d_spheres"};
+
 // One update, resolved against the shadow: what to write and what to refit.
-struct TrianglePlan {
-  std::vector<int32_t> pairs;    // 2 per flat copy: flat triangle index, index of the caller's vertex triple
+struct UpdatePlan {
+  std::vector<int32_t> pairs;    // 2 per flat record: its index in triangles / spheres, index of the caller's record of values
   std::vector<int32_t> bvhs;     // touched BVHs (indices in MeshShadow::bvhs), ascending
   std::vector<int32_t> members;  // touched members (indices in MeshShadow::members), ascending
   std::vector<int32_t> trees;    // instance trees that hold one, ascending
-  std::vector<int32_t> slots;    // touched plain triangle slots, ascending
+  std::vector<int32_t> slots;    // 2 per slot whose f32 box is derived again: the slot, 0 plain / 1 medium boundary; ascending
 };
 
 inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us) {
@@ -188,7 +205,7 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     sh.bvh_of_entry[k] = (int32_t)sh.bvhs.size();
     sh.bvhs.push_back(b);
   }
-  // ---- members of instance trees, plain triangle slots
+  // ---- members of instance trees
   auto geom_of_slot = [&](size_t slot) -> int32_t {
     int32_t x = fs.top_level[slot];
     if (x < 0 || (size_t)x >= n_ent) return -1;
@@ -210,60 +227,63 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
   for (size_t k = 0; k < fs.top_level.size(); ++k) {
     const int32_t x = fs.top_level[k];
     if (x < 0 || (size_t)x >= n_ent) return broken("the world list names an entry outside the entry array");
-    const rt::FlatEntry& e = fs.entries[(size_t)x];
-    if (e.kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)e.a) == rt::PRIM_TRIANGLE) { sh.prim_slot.push_back((int32_t)k); sh.prim_slot.push_back(x); }
   }
-  // ---- slots whose f32 box comes from one static sphere (flatten.cpp: "boxes of the plain static primitives"; trace_world.inc:
-  // build_world_desc, the boundary sphere of a medium)
-  auto sphere_prim = [&](int32_t x) { return fs.entries[(size_t)x].kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)fs.entries[(size_t)x].a) == rt::PRIM_SPHERE; };
+  // ---- slots whose f32 box comes from one triangle or static sphere (flatten.cpp: "boxes of the plain static primitives";
+  // trace_world.inc: build_world_desc, the boundary sphere of a medium)
+  auto prim_of = [&](int32_t x, uint32_t ty) { return fs.entries[(size_t)x].kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)fs.entries[(size_t)x].a) == ty; };
   auto medium_sphere = [&](size_t k) -> int32_t {  // the PRIM entry of the boundary sphere of slot k, -1
     if (k >= fs.top_level.size()) return -1;
     const rt::FlatEntry& e = fs.entries[(size_t)fs.top_level[k]];
     if (e.kind != rt::ENTRY_MEDIUM || e.a < 0 || (size_t)e.a >= n_ent) return -1;
-    return sphere_prim(e.a) ? e.a : -1;
+    return prim_of(e.a, rt::PRIM_SPHERE) ? e.a : -1;
   };
   for (size_t k = 0; k < fs.top_level.size(); ++k) {
     const int32_t x = fs.top_level[k], m = medium_sphere(k);
-    if (sphere_prim(x)) { sh.sphere_slot.push_back((int32_t)k); sh.sphere_slot.push_back(x); sh.sphere_slot.push_back(0); sh.sphere_slot.push_back(medium_sphere(k + 1)); }
-    else if (m >= 0) { sh.sphere_slot.push_back((int32_t)k); sh.sphere_slot.push_back(m); sh.sphere_slot.push_back(1); sh.sphere_slot.push_back(-1); }
+    if (prim_of(x, rt::PRIM_TRIANGLE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, -1});
+    else if (prim_of(x, rt::PRIM_SPHERE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, medium_sphere(k + 1)});
+    else if (m >= 0) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, m, 1, -1});
   }
   return sh;
 }
 
-// The checks every entry makes before it looks at a vertex.  `scene`, `vertices`: compared with NULL, never read.
-inline bool check_triangle_ids(const char* who, const void* scene, const MeshShadow* sh, const int32_t* ids, int64_t n, const void* vertices,
-                               std::string* err) {
+// The checks every entry makes before it looks at the scene or at a value: all four pointers are compared with NULL and never
+// read.
+inline bool check_prim_args(const PrimKind& K, const char* who, const void* scene, const int32_t* ids, int64_t n, const void* values, std::string* err) {
   if (!scene) { *err = std::string(who) + ": the scene is NULL"; return false; }
   if (n < 0) { *err = std::string(who) + ": n < 0"; return false; }
   if (!ids) { *err = std::string(who) + ": ids is NULL"; return false; }
-  if (!vertices) { *err = std::string(who) + ": vertices is NULL"; return false; }
-  if (n == 0) return true;
-  if (!sh->broken.empty()) { *err = std::string(who) + ": " + sh->broken; return false; }
+  if (!values) { *err = std::string(who) + ": " + K.arg + " is NULL"; return false; }
+  return true;
+}
+// ids[0 .. n), n > 0, against the scene's shadow.
+inline bool check_prim_ids(const PrimKind& K, const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n, std::string* err) {
+  if (!sh.broken.empty()) { *err = std::string(who) + ": " + sh.broken; return false; }
+  const int64_t n_ids = K.type == rt::PRIM_TRIANGLE ? (int64_t)sh.n_ids : (int64_t)sh.sph_first.size() - 1;
   for (int64_t i = 0; i < n; ++i)
-    if (ids[i] < 0 || ids[i] >= sh->n_ids) {
-      *err = std::string(who) + ": ids[" + std::to_string(i) + "] is out of range (the scene has " + std::to_string(sh->n_ids) + " triangle ids)";
+    if (ids[i] < 0 || ids[i] >= n_ids) {
+      *err = std::string(who) + ": ids[" + std::to_string(i) + "] is out of range (the scene has " + std::to_string(n_ids) + " " + K.count_phrase + ")";
       return false;
     }
   std::vector<int32_t> sorted(ids, ids + n);
   std::sort(sorted.begin(), sorted.end());
   for (size_t i = 1; i < sorted.size(); ++i)
-    if (sorted[i] == sorted[i - 1]) { *err = std::string(who) + ": ids names triangle " + std::to_string(sorted[i]) + " twice"; return false; }
+    if (sorted[i] == sorted[i - 1]) { *err = std::string(who) + ": ids names " + K.noun + " " + std::to_string(sorted[i]) + " twice"; return false; }
   return true;
 }
 
-// Host entries only.
-inline bool check_vertices_finite(const char* who, const double* vertices, int64_t n, std::string* err) {
-  for (int64_t i = 0; i < 9 * n; ++i)
-    if (!std::isfinite(vertices[i])) {
-      *err = std::string(who) + ": vertices[" + std::to_string(i / 9) + "][" + std::to_string(i % 9) + "] is not finite";
+// Host entries only.  A sphere's radius gets the rule rtx_sphere applies -- none -- beyond being finite: a negative one (the
+// hollow glass ball) and zero are legal.
+inline bool check_prims_finite(const PrimKind& K, const char* who, const double* values, int64_t n, std::string* err) {
+  for (int64_t i = 0; i < K.width * n; ++i)
+    if (!std::isfinite(values[i])) {
+      *err = std::string(who) + ": " + K.arg + "[" + std::to_string(i / K.width) + "][" + std::to_string(i % K.width) + "] is not finite";
       return false;
     }
   return true;
 }
 
 // From the touched entries (one flag per entry) to the BVHs to refit, the members whose local box changes and the instance
-// trees above them: the half of a plan the triangle and the sphere updates share.  what: "triangle" / "sphere", for the
-// message.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
+// trees above them.  what: the kind's noun, for the message.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
 inline rtx_status plan_touched_entries(const char* who, const char* what, const MeshShadow& sh, const std::vector<char>& touched,
                                        std::vector<int32_t>* bvhs, std::vector<int32_t>* members, std::vector<int32_t>* trees, std::string* err) {
   for (size_t b = 0; b < sh.bvhs.size(); ++b) {
@@ -284,21 +304,33 @@ inline rtx_status plan_touched_entries(const char* who, const char* what, const 
 }
 
 // ids (checked) -> what to write and refit.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
-inline rtx_status plan_triangle_update(const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n,
-                                       TrianglePlan* plan, std::string* err) {
-  *plan = TrianglePlan();
+inline rtx_status plan_prim_update(const PrimKind& K, const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n, UpdatePlan* plan,
+                                   std::string* err) {
+  *plan = UpdatePlan();
   std::vector<char> touched(sh.bvh_of_entry.size(), 0);
-  for (int64_t i = 0; i < n; ++i)
-    for (int32_t k = sh.id_first[(size_t)ids[i]]; k < sh.id_first[(size_t)ids[i] + 1]; ++k) {
-      const int32_t t = sh.id_flat[(size_t)k];
-      plan->pairs.push_back(t);
+  // The one loop of an update that runs per id on the caller's thread (871 200 ids in scripts/bench_set_triangles.py): each kind
+  // keeps its own, on its own tables -- one loop that picks the tables per kind measured 2 % to 11 % slower a call.
+  if (K.type == rt::PRIM_TRIANGLE) {  // an id names every flat copy of the triangle
+    for (int64_t i = 0; i < n; ++i)
+      for (int32_t k = sh.id_first[(size_t)ids[i]]; k < sh.id_first[(size_t)ids[i] + 1]; ++k) {
+        const int32_t t = sh.id_flat[(size_t)k];
+        plan->pairs.push_back(t);
+        plan->pairs.push_back((int32_t)i);
+        for (int32_t q = sh.tri_first[(size_t)t]; q < sh.tri_first[(size_t)t + 1]; ++q) touched[(size_t)sh.tri_entry[(size_t)q]] = 1;
+      }
+  } else {  // an id is the flat index of the sphere
+    for (int64_t i = 0; i < n; ++i) {
+      plan->pairs.push_back(ids[i]);
       plan->pairs.push_back((int32_t)i);
-      for (int32_t q = sh.tri_first[(size_t)t]; q < sh.tri_first[(size_t)t + 1]; ++q) touched[(size_t)sh.tri_entry[(size_t)q]] = 1;
+      for (int32_t q = sh.sph_first[(size_t)ids[i]]; q < sh.sph_first[(size_t)ids[i] + 1]; ++q) touched[(size_t)sh.sph_entry[(size_t)q]] = 1;
     }
-  const rtx_status st = plan_touched_entries(who, "triangle", sh, touched, &plan->bvhs, &plan->members, &plan->trees, err);
+  }
+  const rtx_status st = plan_touched_entries(who, K.noun, sh, touched, &plan->bvhs, &plan->members, &plan->trees, err);
   if (st != RTX_OK) return st;
-  for (size_t k = 0; k < sh.prim_slot.size(); k += 2)
-    if (touched[(size_t)sh.prim_slot[k + 1]]) plan->slots.push_back(sh.prim_slot[k]);
+  for (size_t k = 0; k < sh.slot_box.size(); k += 4) {
+    const int32_t next = sh.slot_box[k + 3];  // a plain sphere slot before a medium: their "same sphere" flag hangs on either
+    if (touched[(size_t)sh.slot_box[k + 1]] || (next >= 0 && touched[(size_t)next])) { plan->slots.push_back(sh.slot_box[k]); plan->slots.push_back(sh.slot_box[k + 2]); }
+  }
   return RTX_OK;
 }
 
@@ -355,46 +387,58 @@ inline void refit_bvh(FlatScene* fs, const BvhShadow& b) {
   });
 }
 
-// rtx_flat_set_triangles: every check first, then the edit.  Not RTX_OK: *err set and *fs untouched.
-inline rtx_status flat_set_triangles(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* vertices, std::string* err) {
-  MeshShadow sh;
-  UpdateShadow us;
-  if (fs && n > 0) {
-    us = build_update_shadow(*fs);
-    sh = build_mesh_shadow(*fs, us);
-  }
-  if (!check_triangle_ids(who, fs, &sh, ids, n, vertices, err)) return RTX_EINVAL;
+// rtx_flat_set_triangles / rtx_flat_set_spheres: every check first, then the edit.  Not RTX_OK: *err set and *fs untouched.
+inline rtx_status flat_set_prims(const PrimKind& K, const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* values, std::string* err) {
+  if (!check_prim_args(K, who, fs, ids, n, values, err)) return RTX_EINVAL;
   if (n == 0) return RTX_OK;
-  if (!check_vertices_finite(who, vertices, n, err)) return RTX_EINVAL;
-  TrianglePlan plan;
-  const rtx_status st = plan_triangle_update(who, sh, ids, n, &plan, err);
+  const UpdateShadow us = build_update_shadow(*fs);
+  const MeshShadow sh = build_mesh_shadow(*fs, us);
+  if (!check_prim_ids(K, who, sh, ids, n, err)) return RTX_EINVAL;
+  if (!check_prims_finite(K, who, values, n, err)) return RTX_EINVAL;
+  UpdatePlan plan;
+  const rtx_status st = plan_prim_update(K, who, sh, ids, n, &plan, err);
   if (st != RTX_OK) return st;
-  for (size_t k = 0; k < plan.pairs.size(); k += 2)
-    rt::set_triangle_vertices(&fs->triangles[(size_t)plan.pairs[k]], vertices + 9 * (size_t)plan.pairs[k + 1]);
+  for (size_t k = 0; k < plan.pairs.size(); k += 2) {
+    const double* v = values + (size_t)K.width * (size_t)plan.pairs[k + 1];
+    if (K.type == rt::PRIM_TRIANGLE) rt::set_triangle_vertices(&fs->triangles[(size_t)plan.pairs[k]], v);
+    else rt::set_sphere_values(&fs->spheres[(size_t)plan.pairs[k]], v);
+  }
   for (int32_t b : plan.bvhs) refit_bvh(fs, sh.bvhs[(size_t)b]);
   for (int32_t m : plan.members)
     member_local_box_of(fs->entries[(size_t)sh.members[(size_t)m].geom], fs->nodes.data(), fs->refs.data(), fs->spheres.data(), fs->rects.data(),
                         fs->triangles.data(), &fs->member_local_box[6 * (size_t)m]);
   for (int32_t t : plan.trees) refit_instance_tree(fs, us.trees[(size_t)t]);
-  for (int32_t slot : plan.slots)
-    rt::plain_slot_box32((rt::PrimRef)fs->entries[(size_t)fs->top_level[(size_t)slot]].a, nullptr, nullptr, fs->triangles.data(), &fs->top_box32[6 * (size_t)slot]);
+  for (size_t k = 0; k < plan.slots.size(); k += 2)
+    if (plan.slots[k + 1] == 0)  // (a medium slot has no top_box32: its box lives in the slot record an upload derives)
+      rt::plain_slot_box32((rt::PrimRef)fs->entries[(size_t)fs->top_level[(size_t)plan.slots[k]]].a, fs->spheres.data(), fs->rects.data(),
+                           fs->triangles.data(), &fs->top_box32[6 * (size_t)plan.slots[k]]);
   return RTX_OK;
 }
+inline rtx_status flat_set_triangles(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* vertices, std::string* err) {
+  return flat_set_prims(KIND_TRIANGLE, who, fs, ids, n, vertices, err);
+}
+inline rtx_status flat_set_spheres(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* spheres, std::string* err) {
+  return flat_set_prims(KIND_SPHERE, who, fs, ids, n, spheres, err);
+}
 
-// rtx_flat_triangle_ids: the ids of the triangles below `object`, in list order.  -1 with *err set.
-inline int64_t flat_triangle_ids(const FlatScene& fs, const SceneGraph& g, int32_t object, int32_t* ids, int64_t cap, std::string* err) {
-  if (!g.valid_hittable(object)) { *err = "rtx_flat_triangle_ids: bad object handle"; return -1; }
+// rtx_flat_triangle_ids / rtx_flat_sphere_ids (`who`): the ids of the primitives of the kind below `object`, in list order.  -1
+// with *err set.  (A MovingSphere or GravitySphere has no children and no id: skipped.)
+inline int64_t flat_prim_ids(const PrimKind& K, const char* who, const FlatScene& fs, const SceneGraph& g, int32_t object, int32_t* ids, int64_t cap,
+                             std::string* err) {
+  const bool tri = K.type == rt::PRIM_TRIANGLE;
+  const std::vector<int32_t>& handle_id = tri ? fs.handle_triangle_id : fs.handle_sphere_id;
+  if (!g.valid_hittable(object)) { *err = std::string(who) + ": bad object handle"; return -1; }
   int64_t count = 0;
   std::vector<std::pair<int32_t, int>> todo{{object, 0}};  // depth-first, children in list order
   while (!todo.empty()) {
     const std::pair<int32_t, int> at = todo.back();
     todo.pop_back();
-    if (at.second > 80) { *err = "rtx_flat_triangle_ids: objects nested deeper than 80"; return -1; }
-    if ((size_t)at.first >= fs.handle_triangle_id.size()) { *err = "rtx_flat_triangle_ids: the object was made after this flat scene was flattened"; return -1; }
+    if (at.second > 80) { *err = std::string(who) + ": objects nested deeper than 80"; return -1; }
+    if ((size_t)at.first >= handle_id.size()) { *err = std::string(who) + ": the object was made after this flat scene was flattened"; return -1; }
     const GHittable& o = g.hittables[(size_t)at.first];
-    if (o.kind == H_TRIANGLE) {
-      const int32_t id = fs.handle_triangle_id[(size_t)at.first];
-      if (id < 0) { *err = "rtx_flat_triangle_ids: this flat scene did not flatten the object (a triangle below it has no id)"; return -1; }
+    if (o.kind == (tri ? H_TRIANGLE : H_SPHERE)) {
+      const int32_t id = handle_id[(size_t)at.first];
+      if (id < 0) { *err = std::string(who) + ": this flat scene did not flatten the object (a " + K.noun + " below it has no id)"; return -1; }
       if (ids && count < cap) ids[count] = id;
       ++count;
       continue;

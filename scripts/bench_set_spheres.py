@@ -11,7 +11,7 @@ and max beside it; everything runs in one process.  No threshold: these are the 
 
 Per scene --
   update_device_ms          rtx_scene_set_spheres_device (values already on the device): the copy of the index lists,
-                            k_set_spheres, k_refit_bvh (and k_refit_wide where the scene has a wide tree), between two events;
+                            k_set_prims, k_refit_bvh (and k_refit_wide where the scene has a wide tree), between two events;
   update_call_ms            wall time of that call itself (checks, plan, staging, enqueue; it does not wait);
   update_host_device_ms     the same between events for rtx_scene_set_spheres (values staged from the host: 32 B a sphere);
   rebuild_graph_ms / rebuild_flatten_ms / rebuild_upload_ms

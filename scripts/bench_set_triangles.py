@@ -11,7 +11,7 @@ warm-up runs, with the min and max beside it; everything runs in one process and
 
 Measurement 1, per N: one update of EVERY triangle --
   update_device_ms          rtx_scene_set_triangles_device (vertices already on the device): the copy of the index lists,
-                            k_set_triangles, k_refit_bvh (and k_refit_wide where the scene has a wide tree), between two events;
+                            k_set_prims, k_refit_bvh (and k_refit_wide where the scene has a wide tree), between two events;
   update_call_ms            wall time of that call itself (checks, plan, staging, enqueue; it does not wait);
   update_host_device_ms     the same between events for rtx_scene_set_triangles (vertices staged from the host: 72 B a triangle);
 beside what the same change costs without the feature, wall time, the device idle before and after --

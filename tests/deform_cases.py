@@ -8,11 +8,11 @@ handed to set_triangles.  All seeded, all small; everything here runs on the CPU
 Coordinates stay away from 0: a box plane that is +0 in one union order and -0 in another is the same plane to every walker
 but not the same bytes, and the tests compare bytes.
 """
-import ctypes as C
-
 import numpy as np
 
+import update_cases
 from set_transforms_cases import NODE, NODE32, MOTION32, narrow, leaf_boxes, tree_roots  # noqa: F401  (re-exported)
+from update_cases import INSTANCED_POSE, Case, cam_cfg  # noqa: F401  (re-exported)
 
 TRIANGLE = np.dtype([("v", np.float64, (3, 3)), ("normal", np.float64, (3,)), ("mat", np.int32), ("pad", np.int32)])
 NODE4 = np.dtype([("lo", np.float32, (3, 4)), ("hi", np.float32, (3, 4)), ("child", np.int32, (4,)), ("pad", np.int32, (4,))])
@@ -50,25 +50,13 @@ def sheet_mesh(n_tris, origin=(0.3, 1.0, 0.4), extent=4.0, seed=0):
     return v, np.array(faces[:n_tris], dtype=np.int64), cell
 
 
-class Case:
-    def __init__(self, builder, world, parts, flatten=None, look=((2.3, 5.0, 8.5), (2.3, 1.0, 2.4))):
-        self.builder, self.world, self.parts, self.flatten_opt, self.look = builder, world, parts, dict(flatten or {}), look
-
-    def flatten(self):
-        return self.builder.flatten(self.world, **self.flatten_opt)
-
-
-class _Maker:
-    """Adds deformable triangles to a builder and notes (handle, rest triangles, moved triangles) per part.  moved: False (at
-    rest), True (every triangle displaced) or a predicate on the triangle's position in update_of's full list -- the fresh
-    scene of a partial update.  Meshes are given to the builder triangle by triangle (no shared vertex records), so that one
-    triangle can move alone; the displacement is a function of position, so shared corners still move together."""
-
-    def __init__(self, rtsr, seed, moved):
-        self.b, self.moved, self.parts, self.k = rtsr.Builder(seed), moved, [], 0
+class _Maker(update_cases.Maker):
+    """Deformable triangles: (handle, rest triangles, moved triangles) per part.  Meshes are given to the builder triangle by
+    triangle (no shared vertex records), so that one triangle can move alone; the displacement is a function of position, so
+    shared corners still move together."""
 
     def _pick(self, rest, mv):
-        on = np.array([self.moved(self.k + i) if callable(self.moved) else bool(self.moved) for i in range(len(rest))])
+        on = np.array([self.on(self.k + i) for i in range(len(rest))])
         self.k += len(rest)
         return np.where(on[:, None, None], mv, rest)
 
@@ -166,9 +154,6 @@ def shared(rtsr, moved):
     case = Case(b, world, m.parts)
     case.handles = {"pair": pair, "members": members, "bvh": bvh, "both": both, "twice": twice, "alone": alone}
     return case
-
-
-INSTANCED_POSE = (((0.4, 0.2, 0.3), 20.0), ((3.1, 0.3, 2.2), -35.0), ((1.2, 0.4, 4.0), None))
 
 
 def instanced(rtsr, moved, hoisted=False, pose=INSTANCED_POSE):
@@ -314,32 +299,8 @@ def triangles_by_id(flat):
     return out
 
 
-def cam_cfg(rtsr, case, width=48, spp=4, depth=8, seed=31):
-    cam = rtsr.Camera.new(case.look[0], case.look[1], (0.0, 1.0, 0.0), 35.0, 1.5, 0.0, 10.0, 0.0, 1.0)
-    cfg = rtsr.Config.new(1.5, width, spp, depth, 4, seed=seed)
-    return cam, cfg, rtsr.image_height(cfg)
-
-
 def seeded_rays(n, seed, lo=(-0.5, 0.3, -0.5), hi=(5.5, 4.0, 5.5)):
-    """Origins on a box around the scene, aimed at points inside it."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(lo), np.array(hi)
-    o = lo + (hi - lo) * rng.uniform(0.0, 1.0, (n, 3))
-    o[:, 1] = hi[1] + rng.uniform(0.5, 3.0, n)
-    side = rng.integers(0, 3, n)
-    o[side == 1, 0] = lo[0] - 2.0
-    o[side == 2, 2] = hi[2] + 2.0
-    target = lo + (hi - lo) * rng.uniform(0.15, 0.85, (n, 3))
-    target[:, 1] = rng.uniform(0.5, 2.5, n)
-    d = target - o
-    return o, d
-
-
-def call_set_triangles(rtsr, fn, handle, ids, n, verts, *rest):
-    ia = np.ascontiguousarray(ids, dtype=np.int32) if ids is not None else None
-    va = np.ascontiguousarray(verts, dtype=np.float64) if verts is not None else None
-    return fn(handle, ia.ctypes.data_as(C.POINTER(C.c_int32)) if ia is not None else None, len(ia) if n is None else n,
-              va.ctypes.data_as(C.POINTER(C.c_double)) if va is not None else None, *rest)
+    return update_cases.seeded_rays(n, seed, lo, hi, (0.5, 2.5))
 
 
 def refusals(n_ids):

@@ -13,7 +13,7 @@
 #include <string>
 #include <vector>
 #include "../ray-tracing-series-rust_amd/csrc/host/light_table.hpp"
-#include "../ray-tracing-series-rust_amd/csrc/host/set_spheres.hpp"
+#include "../ray-tracing-series-rust_amd/csrc/host/set_triangles.hpp"
 
 namespace rtx {
 // the GPU builder lives in csrc/hip/lbvh.hip: not part of a CPU-only program

@@ -13,13 +13,14 @@ The rule of every full update (assert_update_can_show): at least one sphere LEAV
 by more than 2 |r| along one axis -- and at least another SHRINKS.  A refit that was not made cannot hide behind either: the
 first needs the boxes above it to grow, the second to shrink.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
+import update_cases
 from deform_cases import sheet_mesh
 from set_transforms_cases import NODE, NODE32, MOTION32, narrow, leaf_boxes, tree_roots  # noqa: F401  (re-exported)
+from update_cases import INSTANCED_POSE, cam_cfg  # noqa: F401  (re-exported)
 
 SPHERE = np.dtype([("c", np.float64, (3,)), ("radius", np.float64), ("mat", np.int32), ("pad", np.int32)])
 LIGHT = np.dtype([("kind", np.int32), ("slot", np.int32), ("prim", np.int32), ("mat", np.int32), ("area", np.float64), ("cdf", np.float64), ("pmf", np.float64)])
@@ -56,28 +57,20 @@ def assert_update_can_show(rest, moved):
     assert (shrinks & ~leaves).any(), "no other sphere shrinks"
 
 
-class Case:
+class Case(update_cases.Case):
     def __init__(self, builder, world, parts, flatten=None, look=((3.0, 5.0, 11.0), (3.0, 0.8, 3.0))):
-        self.builder, self.world, self.parts, self.flatten_opt, self.look = builder, world, parts, dict(flatten or {}), look
-
-    def flatten(self):
-        return self.builder.flatten(self.world, **self.flatten_opt)
+        super().__init__(builder, world, parts, flatten, look)
 
 
-class _Maker:
-    """Adds movable spheres to a builder and notes (handle, rest values, moved values) per sphere.  moved: False (at rest), True
-    (every sphere moved) or a predicate on the sphere's position in update_of's full list -- the fresh scene of a partial
-    update.  to: where this sphere goes instead of moved_values' place (the lamp's updates, the fog's common move)."""
-
-    def __init__(self, rtsr, seed, moved):
-        self.b, self.moved, self.parts, self.k = rtsr.Builder(seed), moved, [], 0
+class _Maker(update_cases.Maker):
+    """Movable spheres: (handle, rest values, moved values) per sphere.  to: where this sphere goes instead of moved_values'
+    place (the lamp's updates, the fog's common move)."""
 
     def sphere(self, c, r, mat, to=None):
         rest = np.array([c[0], c[1], c[2], r], dtype=np.float64)
         mv = np.array(to, dtype=np.float64) if to is not None else moved_values(rest, self.k)
-        on = self.moved(self.k) if callable(self.moved) else bool(self.moved)
+        use = mv if self.on(self.k) else rest
         self.k += 1
-        use = mv if on else rest
         h = self.b.sphere(tuple(use[:3]), float(use[3]), mat)
         self.parts.append((h, rest, mv))
         return h
@@ -189,9 +182,6 @@ def lamp(rtsr, moved, to="other cell", dark_rect=False):
     return case
 
 
-INSTANCED_POSE = (((0.4, 0.2, 0.3), 20.0), ((3.1, 0.3, 2.2), -35.0), ((1.2, 0.4, 4.0), None))
-
-
 def instanced(rtsr, moved, pose=INSTANCED_POSE, tris_moved=False):
     """An instance tree whose members are a sphere, a group of spheres and a BVH of spheres (and, for the sequence, a BVH of
     triangles), each under a Translate and two under a RotateY as well.  tris_moved: the mesh member displaced (the sequence)."""
@@ -298,31 +288,8 @@ def book1_update(flat, builder, world):
     return np.array(small, dtype=np.int32), rest, mv
 
 
-def cam_cfg(rtsr, case, width=48, spp=4, depth=8, seed=31):
-    cam = rtsr.Camera.new(case.look[0], case.look[1], (0.0, 1.0, 0.0), 35.0, 1.5, 0.0, 10.0, 0.0, 1.0)
-    cfg = rtsr.Config.new(1.5, width, spp, depth, 4, seed=seed)
-    return cam, cfg, rtsr.image_height(cfg)
-
-
-def seeded_rays(n, seed, lo=(-0.5, 0.3, -0.5), hi=(6.5, 3.5, 6.5)):
-    """Origins on a box around the scene, aimed at points inside it."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.array(lo), np.array(hi)
-    o = lo + (hi - lo) * rng.uniform(0.0, 1.0, (n, 3))
-    o[:, 1] = hi[1] + rng.uniform(0.5, 3.0, n)
-    side = rng.integers(0, 3, n)
-    o[side == 1, 0] = lo[0] - 2.0
-    o[side == 2, 2] = hi[2] + 2.0
-    target = lo + (hi - lo) * rng.uniform(0.15, 0.85, (n, 3))
-    target[:, 1] = rng.uniform(0.3, 2.2, n)
-    return o, target - o
-
-
-def call_set_spheres(rtsr, fn, handle, ids, n, vals, *rest):
-    ia = np.ascontiguousarray(ids, dtype=np.int32) if ids is not None else None
-    va = np.ascontiguousarray(vals, dtype=np.float64) if vals is not None else None
-    return fn(handle, ia.ctypes.data_as(C.POINTER(C.c_int32)) if ia is not None else None, len(ia) if n is None else n,
-              va.ctypes.data_as(C.POINTER(C.c_double)) if va is not None else None, *rest)
+def seeded_rays(n, seed):
+    return update_cases.seeded_rays(n, seed, (-0.5, 0.3, -0.5), (6.5, 3.5, 6.5), (0.3, 2.2))
 
 
 def refusals(n_ids):

@@ -6,46 +6,19 @@ scene uploaded afresh (rtx_flat_set_spheres, which tests/test_set_spheres_host.p
 and every ENTRY POINT on the updated scene answers bit for bit as on a FRESH upload of the same world built from scratch with
 the moved spheres.  Frames are 48 x 32 at 4 spp."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import cast_rays_cases as cc
 from sphere_update_cases import (CASES, DESC, DEVICE_ARRAYS, FORCED_KERNELS, LDS_CASES, LIGHT, WD_BOXED_PRIM, WD_PAIR, assert_update_can_show, beside_movers, book1, book1_update,
-                                 call_set_spheres, cam_cfg, instanced, refusals, rest_and_moved, seeded_rays, update_of)
+                                 cam_cfg, instanced, refusals, rest_and_moved, seeded_rays, update_of)
+from update_cases import KERNEL_OF, assert_arrays_equal as _assert_arrays_equal, call_set_prims, device_arrays, same_screen as _same_screen, updated_pair
+from update_cases import upload as _upload
 
 pytestmark = pytest.mark.gpu
-SWITCHES = ("RTX_TRACE_KERNEL", "RTX_WIDE")
-KERNEL_OF = {"simple": "k_trace_simple", "vote": "k_trace_vote", "world": "k_trace_world", "wavefront": "k_wf_trace"}
-
-
-def _upload(flat, env=None):
-    """flat.upload() under the given RTX_* switches (read once per upload)."""
-    old = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    try:
-        return flat.upload()
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 def _device(scene):
-    out = {k: scene.array(k) for k in DEVICE_ARRAYS}
-    out["plans"] = np.array([scene.wide_levels(), scene.max_stack()], dtype=np.int32).view(np.uint8)  # which = 8, 9
-    return out
-
-
-def _assert_arrays_equal(scene, want, what):
-    now = _device(scene)
-    for k in want:
-        assert now[k].size == want[k].size and np.array_equal(now[k], want[k]), "%s: %s differs from the host-updated scene uploaded fresh in %d bytes" % (
-            what, k, int((now[k] != want[k]).sum()) if now[k].size == want[k].size else -1)
+    return device_arrays(scene, DEVICE_ARRAYS + ("plans",))
 
 
 def _check_patterns(rtsr, case_fn, env=None):
@@ -177,25 +150,7 @@ _PAIRS = {}
 
 
 def _pair(rtsr, name, env=()):
-    """(updated scene, fresh scene, host-updated flat, fresh flat, case): uploaded at rest and updated on the device, and the
-    same world built from scratch with the moved spheres.  Built once per case for the default switches."""
-    if name in _PAIRS and not env:
-        return _PAIRS[name]
-    case, moved = CASES[name](rtsr, False), CASES[name](rtsr, True)
-    flat, fresh_flat = case.flatten(), moved.flatten()
-    scene = _upload(flat, dict(env))
-    ids, vals = update_of(case, flat)
-    scene.set_spheres(ids, vals)
-    flat.set_spheres(ids, vals)
-    pair = (scene, _upload(fresh_flat, dict(env)), flat, fresh_flat, case)
-    if not env:
-        _PAIRS[name] = pair
-    return pair
-
-
-def _same_screen(a, b, what):
-    bad = int((a.accum != b.accum).any(axis=2).sum())
-    assert bad == 0 and np.array_equal(a.rgb8, b.rgb8), "%s: %d pixels differ from the fresh upload" % (what, bad)
+    return updated_pair(_PAIRS, rtsr, CASES, update_of, "set_spheres", name, env)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
@@ -338,7 +293,60 @@ def test_one_scene_through_spheres_triangles_transforms_a_rebuild_and_spheres_ag
     _same_screen(scene.render(cam, cfg), want, "after the sequence")
 
 
-# ---- 5. refusals
+# ---- 5. the slot boxes of both kinds
+SLOT_ARRAYS = ("top_box32", "world_desc", "triangles", "spheres")
+
+
+@pytest.mark.parametrize("n_tris", [256, 257])
+def test_triangle_and_sphere_slots_get_their_boxes_from_one_kernel(rtsr, n_tris):
+    """k_slot_boxes on a world of plain slots alone, no BVH over them: a triangle, a glass ball, the fog inside it (bounded by a
+    sphere of the very same bytes: WD_PAIR), then n_tris - 1 more triangles.  256 triangle slots fill one block of the grid, 257
+    cross into the second.  Every triangle updated, the ball moved alone (the pair flag clears), the ball set back (it returns);
+    then the first and the last triangle alone, which must leave every slot not listed as it was.  After every step the four
+    arrays are those of the host-updated flat scene uploaded afresh, and the step has changed what it should."""
+    from deform_cases import displace
+    b = rtsr.Builder(3)
+    red, glass = b.lambertian((0.8, 0.3, 0.3)), b.dielectric(1.5)
+    rest = np.array([[(0.3 + 0.02 * k, 1.0 + 0.001 * k, 0.4), (0.5 + 0.02 * k, 1.1, 0.5 + 0.003 * k), (0.4 + 0.02 * k, 1.6, 0.9)] for k in range(n_tris)])
+    moved = displace(rest, 0.4)
+    tris = [b.triangle(tuple(t[0]), tuple(t[1]), tuple(t[2]), red) for t in rest]
+    ball_rest, ball_moved = np.array([[1.71, 1.32, 2.93, 1.1]]), np.array([[4.13, 1.74, 2.21, 0.85]])
+    ball, inside = b.sphere(tuple(ball_rest[0, :3]), ball_rest[0, 3], glass), b.sphere(tuple(ball_rest[0, :3]), ball_rest[0, 3], glass)
+    world = b.hittable_list([tris[0], ball, b.constant_medium((0.2, 0.4, 0.9), 0.8, inside)] + tris[1:])
+    flat = b.flatten(world)
+    assert flat.info()["n_top_level"] == n_tris + 2 and flat.info()["n_bvh"] == 0 and flat.instances()["n_trees"] == 0
+    tri_ids, ball_id = flat.triangle_ids(b, world), flat.sphere_ids(b, ball)
+    assert len(tri_ids) == n_tris and len(set(tri_ids.tolist())) == n_tris and len(ball_id) == 1
+    slot_of = lambda k: 0 if k == 0 else k + 2  # triangle number k -> its slot
+    scene = _upload(flat)
+    desc = lambda a: a["world_desc"].view(DESC)
+    now = lambda: device_arrays(scene, SLOT_ARRAYS)
+    first = now()
+    assert len(desc(first)) == n_tris + 2 and desc(first)["flags"][1] & WD_PAIR and all(desc(first)["flags"] & WD_BOXED_PRIM)
+
+    def step(what, setter, ids, values, changed, paired):
+        before = now()
+        getattr(scene, setter)(ids, values)
+        getattr(flat, setter)(ids, values)
+        after = now()
+        _assert_arrays_equal(scene, device_arrays(_upload(flat), SLOT_ARRAYS), what)
+        for k in SLOT_ARRAYS:  # the step shows where it should, and nowhere else
+            assert np.array_equal(after[k], before[k]) == (k not in changed), (what, k)
+        assert bool(desc(after)["flags"][1] & WD_PAIR) == paired and all(desc(after)["flags"] & WD_BOXED_PRIM), what
+        return before, after
+
+    step("every triangle", "set_triangles", tri_ids, moved.reshape(-1, 9), ("top_box32", "world_desc", "triangles"), True)
+    step("the ball alone", "set_spheres", ball_id, ball_moved, ("top_box32", "world_desc", "spheres"), False)
+    step("the ball back", "set_spheres", ball_id, ball_rest, ("top_box32", "world_desc", "spheres"), True)
+    for k in (0, n_tris - 1):  # one triangle back to rest: its slot alone
+        before, after = step("triangle %d alone" % k, "set_triangles", tri_ids[k:k + 1], rest[k].reshape(1, 9), ("top_box32", "world_desc", "triangles"), True)
+        others = np.arange(n_tris + 2) != slot_of(k)
+        assert np.array_equal(after["top_box32"].view(np.float32).reshape(-1, 6)[others], before["top_box32"].view(np.float32).reshape(-1, 6)[others])
+        assert np.array_equal(desc(after)[others], desc(before)[others])
+        assert not np.array_equal(desc(after)["box"][~others], desc(before)["box"][~others])
+
+
+# ---- 6. refusals
 def test_scene_refusals_enqueue_nothing(rtsr):
     case = CASES["mixed"](rtsr, False)
     flat = case.flatten()
@@ -347,7 +355,7 @@ def test_scene_refusals_enqueue_nothing(rtsr):
     first, frame = _device(scene), scene.render(cam, cfg)
     n_ids = flat.info()["n_spheres"]
     for name, ids, n, vals, word, host_only in refusals(n_ids):  # duplicate ids and values that are not finite among them
-        st = call_set_spheres(rtsr, rtsr.lib.rtx_scene_set_spheres, scene.ptr, ids, n, vals, None)
+        st = call_set_prims(rtsr, rtsr.lib.rtx_scene_set_spheres, scene.ptr, ids, n, vals, None)
         assert st == rtsr.RTX_EINVAL and "rtx_scene_set_spheres" in rtsr.last_error() and word in rtsr.last_error(), (name, rtsr.last_error())
     import torch
     good = torch.ones(8, dtype=torch.float64).cuda()

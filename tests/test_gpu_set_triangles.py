@@ -5,43 +5,17 @@ Two judges, neither the code under test: the resident ARRAYS after an update are
 scene uploaded afresh (rtx_flat_set_triangles, which tests/test_set_triangles_host.py holds to a fresh flatten and to the
 oracle), and every ENTRY POINT on the updated scene answers bit for bit as on a FRESH upload of the same world built from
 scratch with the displaced vertices."""
-import os
-
 import numpy as np
 import pytest
 
 import cast_rays_cases as cc
-from deform_cases import (CASES, call_set_triangles, refusals, DEVICE_ARRAYS, NODE, NODE4, SHEET_LEAVES, cam_cfg, count_leaves, movers, narrow, sheet, sheet_tris_for_leaves, update_of, update_sequence)
+from deform_cases import (CASES, refusals, DEVICE_ARRAYS, NODE, NODE4, SHEET_LEAVES, cam_cfg, count_leaves, movers, narrow, sheet, sheet_tris_for_leaves, update_of, update_sequence)
+from update_cases import KERNEL_OF, assert_arrays_equal as _assert_arrays_equal, call_set_prims, device_arrays, same_screen as _same_screen, updated_pair
+from update_cases import upload as _upload
 
 pytestmark = pytest.mark.gpu
-SWITCHES = ("RTX_TRACE_KERNEL", "RTX_WIDE")
-KERNEL_OF = {"simple": "k_trace_simple", "vote": "k_trace_vote", "world": "k_trace_world", "wavefront": "k_wf_trace"}
-
-
-def _upload(flat, env=None):
-    """flat.upload() under the given RTX_* switches (read once per upload)."""
-    old = {k: os.environ.get(k) for k in SWITCHES}
-    for k in SWITCHES:
-        os.environ.pop(k, None)
-    os.environ.update(env or {})
-    try:
-        return flat.upload()
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 def _device(scene):
-    return {k: scene.array(k) for k in DEVICE_ARRAYS}
-
-
-def _assert_arrays_equal(scene, want, what):
-    for k in DEVICE_ARRAYS:
-        dev = scene.array(k)
-        assert dev.size == want[k].size and np.array_equal(dev, want[k]), "%s: %s differs from the host-updated scene uploaded fresh in %d bytes" % (
-            what, k, int((dev != want[k]).sum()) if dev.size == want[k].size else -1)
+    return device_arrays(scene, DEVICE_ARRAYS)
 
 
 def _check_patterns(rtsr, orc, case_fn, audit):
@@ -220,25 +194,7 @@ _PAIRS = {}
 
 
 def _pair(rtsr, name, env=()):
-    """(updated scene, fresh scene, host-updated flat, fresh flat, case): uploaded at rest and updated on the device, and the
-    same world built from scratch with the displaced vertices.  Built once per case for the default switches."""
-    if name in _PAIRS and not env:
-        return _PAIRS[name]
-    case, moved = CASES[name](rtsr, False), CASES[name](rtsr, True)
-    flat, fresh_flat = case.flatten(), moved.flatten()
-    scene = _upload(flat, dict(env))
-    ids, verts = update_of(case, flat)
-    scene.set_triangles(ids, verts)
-    flat.set_triangles(ids, verts)
-    pair = (scene, _upload(fresh_flat, dict(env)), flat, fresh_flat, case)
-    if not env:  # (a scene under a forced kernel keeps that kernel's workspace: not kept beyond its one frame)
-        _PAIRS[name] = pair
-    return pair
-
-
-def _same_screen(a, b, what):
-    bad = int((a.accum != b.accum).any(axis=2).sum())
-    assert bad == 0 and np.array_equal(a.rgb8, b.rgb8), "%s: %d pixels differ from the fresh upload" % (what, bad)
+    return updated_pair(_PAIRS, rtsr, CASES, update_of, "set_triangles", name, env)
 
 
 @pytest.mark.parametrize("name", ENTRY_CASES)
@@ -366,7 +322,7 @@ def test_scene_refusals_enqueue_nothing(rtsr):
     first, frame = _device(scene), scene.render(cam, cfg)
     n_ids = int(flat.array("triangle_id").view(np.int32).max()) + 1
     for name, ids, n, verts, word, host_only in refusals(n_ids):
-        st = call_set_triangles(rtsr, rtsr.lib.rtx_scene_set_triangles, scene.ptr, ids, n, verts, None)
+        st = call_set_prims(rtsr, rtsr.lib.rtx_scene_set_triangles, scene.ptr, ids, n, verts, None)
         assert st == rtsr.RTX_EINVAL and "rtx_scene_set_triangles" in rtsr.last_error() and word in rtsr.last_error(), (name, rtsr.last_error())
     import torch
     good = torch.ones(18, dtype=torch.float64).cuda()

@@ -14,20 +14,16 @@ import pytest
 
 from cast_rays_cases import same_bits
 from sphere_update_cases import (CASES, FLAT_ARRAYS, LIGHT, MOTION32, NODE, NODE32, SPHERE, assert_update_can_show, beside_movers, book1, book1_update,
-                                 call_set_spheres, cam_cfg, instanced, lamp, leaf_boxes, narrow, refusals, rest_and_moved, seeded_rays, tree_roots,
+                                 cam_cfg, instanced, lamp, leaf_boxes, narrow, refusals, rest_and_moved, seeded_rays, tree_roots,
                                  update_of)
+from update_cases import assert_same_topology, call_set_prims, flat_arrays, hit_records as _records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_ARRAYS = ("refs", "rects")  # no hook of the library's reads these: the oracle's view of the same FlatScene does
 
 
 def _arrays(flat):
-    """Every array an update may or may not touch, as bytes.  (Tests that call this take the `orc` fixture, which builds the oracle.)"""
-    import oracle_py
-    out = {name: flat.array(name) for name in FLAT_ARRAYS}
-    for name in ORACLE_ARRAYS:
-        out[name] = oracle_py.flat_array(flat.arrays_ptr(), name)[0]
-    return out
+    return flat_arrays(flat, FLAT_ARRAYS, ORACLE_ARRAYS)
 
 
 def _same_arrays(flat, first):
@@ -49,22 +45,8 @@ def _assert_back_at_rest(flat, first):
             assert np.array_equal(x, y), (k, f)  # numeric equality: +0 == -0
 
 
-def _records(orc, flat, o, d):
-    out = np.zeros((len(o), 11))
-    for r in range(len(o)):
-        rec = orc.core_world_hit(flat.arrays_ptr(), tuple(o[r]), tuple(d[r]), 0.25, 0.001, float("inf"), rng_seed=1 + r)
-        if rec is not None:
-            out[r] = [1.0, rec["t"], *rec["p"], *rec["normal"], rec["u"], rec["v"], float(rec["front_face"])]
-    return out
-
-
 def _same_topology(now, first):
-    n, n0 = now["nodes"].view(NODE), first["nodes"].view(NODE)
-    m, m0 = now["nodes32"].view(NODE32), first["nodes32"].view(NODE32)
-    assert np.array_equal(n["child"], n0["child"]) and np.array_equal(n["pad"], n0["pad"])
-    assert np.array_equal(m["child"], m0["child"]) and np.array_equal(m["axis"], m0["axis"]) and np.array_equal(m["pad"], m0["pad"])
-    for k in ("entries", "top_level", "triangles") + ORACLE_ARRAYS:
-        assert np.array_equal(now[k], first[k]), k
+    assert_same_topology(now, first, ("entries", "top_level", "triangles") + ORACLE_ARRAYS)
 
 
 def _check_against_fresh(rtsr, orc, flat, fresh, first):
@@ -269,12 +251,12 @@ def test_every_refusal_leaves_the_flat_scene_unchanged(rtsr, orc):
     cases = refusals(n_ids)
     assert len(cases) == 8
     for name, ids, n, vals, word, _ in cases:
-        st = call_set_spheres(rtsr, rtsr.lib.rtx_flat_set_spheres, flat.ptr, ids, n, vals)
+        st = call_set_prims(rtsr, rtsr.lib.rtx_flat_set_spheres, flat.ptr, ids, n, vals)
         assert st == rtsr.RTX_EINVAL, name
         assert "rtx_flat_set_spheres" in rtsr.last_error() and word in rtsr.last_error(), (name, rtsr.last_error())
         assert _same_arrays(flat, before), name
-    assert call_set_spheres(rtsr, rtsr.lib.rtx_flat_set_spheres, None, [0], None, np.ones(4)) == rtsr.RTX_EINVAL and "scene is NULL" in rtsr.last_error()
-    assert call_set_spheres(rtsr, rtsr.lib.rtx_flat_set_spheres, flat.ptr, [0], 0, np.ones(4)) == rtsr.RTX_OK  # n = 0: nothing to do
+    assert call_set_prims(rtsr, rtsr.lib.rtx_flat_set_spheres, None, [0], None, np.ones(4)) == rtsr.RTX_EINVAL and "scene is NULL" in rtsr.last_error()
+    assert call_set_prims(rtsr, rtsr.lib.rtx_flat_set_spheres, flat.ptr, [0], 0, np.ones(4)) == rtsr.RTX_OK  # n = 0: nothing to do
     assert _same_arrays(flat, before)
     # a negative radius and a radius of zero are legal: rtx_sphere applies no rule to it
     two = flat.array("spheres").view(SPHERE)[:2]

@@ -13,8 +13,9 @@ import numpy as np
 import pytest
 
 from cast_rays_cases import same_bits
-from deform_cases import (CASES, call_set_triangles, refusals, FLAT_ARRAYS, MOTION32, NODE, NODE32, SEQUENCE_END, SHEET_LEAVES, TRIANGLE, cam_cfg, count_leaves, instanced, leaf_boxes,
+from deform_cases import (CASES, refusals, FLAT_ARRAYS, MOTION32, NODE, NODE32, SEQUENCE_END, SHEET_LEAVES, TRIANGLE, cam_cfg, count_leaves, instanced, leaf_boxes,
                           movers, narrow, seeded_rays, sheet, sheet_tris_for_leaves, tree_roots, triangles_by_id, update_of, update_sequence)
+from update_cases import assert_same_topology, call_set_prims, flat_arrays, hit_records as _records
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,12 +24,7 @@ ORACLE_ARRAYS = ("refs", "spheres", "rects")  # no hook of the library's reads t
 
 
 def _arrays(flat):
-    """Every array an update may or may not touch, as bytes.  (Tests that call this take the `orc` fixture, which builds the oracle.)"""
-    import oracle_py
-    out = {name: flat.array(name) for name in FLAT_ARRAYS}
-    for name in ORACLE_ARRAYS:
-        out[name] = oracle_py.flat_array(flat.arrays_ptr(), name)[0]
-    return out
+    return flat_arrays(flat, FLAT_ARRAYS, ORACLE_ARRAYS)
 
 
 def _same_arrays(flat, first):
@@ -36,22 +32,8 @@ def _same_arrays(flat, first):
     return all(np.array_equal(now[k], first[k]) for k in first)
 
 
-def _records(orc, flat, o, d):
-    out = np.zeros((len(o), 11))
-    for r in range(len(o)):
-        rec = orc.core_world_hit(flat.arrays_ptr(), tuple(o[r]), tuple(d[r]), 0.25, 0.001, float("inf"), rng_seed=1 + r)
-        if rec is not None:
-            out[r] = [1.0, rec["t"], *rec["p"], *rec["normal"], rec["u"], rec["v"], float(rec["front_face"])]
-    return out
-
-
 def _same_topology(now, first):
-    n, n0 = now["nodes"].view(NODE), first["nodes"].view(NODE)
-    m, m0 = now["nodes32"].view(NODE32), first["nodes32"].view(NODE32)
-    assert np.array_equal(n["child"], n0["child"]) and np.array_equal(n["pad"], n0["pad"])
-    assert np.array_equal(m["child"], m0["child"]) and np.array_equal(m["axis"], m0["axis"]) and np.array_equal(m["pad"], m0["pad"])
-    for k in ("entries", "top_level", "triangle_id") + ORACLE_ARRAYS:
-        assert np.array_equal(now[k], first[k]), k
+    assert_same_topology(now, first, ("entries", "top_level", "triangle_id") + ORACLE_ARRAYS)
 
 
 def _check_against_fresh(rtsr, orc, flat, fresh, first, audit=None):
@@ -276,12 +258,12 @@ def test_every_refusal_leaves_the_flat_scene_unchanged(rtsr, orc):
     cases = refusals(n_ids)
     assert len(cases) == 8
     for name, ids, n, verts, word, _ in cases:
-        st = call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, ids, n, verts)
+        st = call_set_prims(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, ids, n, verts)
         assert st == rtsr.RTX_EINVAL, name
         assert "rtx_flat_set_triangles" in rtsr.last_error() and word in rtsr.last_error(), (name, rtsr.last_error())
         assert _same_arrays(flat, before), name
-    assert call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, None, [0], None, np.ones(9)) == rtsr.RTX_EINVAL and "scene is NULL" in rtsr.last_error()
-    assert call_set_triangles(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, [0], 0, np.ones(9)) == rtsr.RTX_OK  # n = 0: nothing to do
+    assert call_set_prims(rtsr, rtsr.lib.rtx_flat_set_triangles, None, [0], None, np.ones(9)) == rtsr.RTX_EINVAL and "scene is NULL" in rtsr.last_error()
+    assert call_set_prims(rtsr, rtsr.lib.rtx_flat_set_triangles, flat.ptr, [0], 0, np.ones(9)) == rtsr.RTX_OK  # n = 0: nothing to do
     assert _same_arrays(flat, before)
     # a BVH that holds a MovingSphere: its time-aware slopes would have to be derived again
     mv = movers(rtsr)
@@ -304,7 +286,7 @@ def test_scene_entries_refuse_before_they_read_the_scene_arrays(rtsr):
     """What needs no scene is checked first: NULLs and n < 0 on a scene pointer that is never dereferenced for them."""
     good = np.ones(9)
     for fn, who in ((rtsr.lib.rtx_scene_set_triangles, "rtx_scene_set_triangles"), (rtsr.lib.rtx_scene_set_triangles_device, "rtx_scene_set_triangles_device")):
-        assert call_set_triangles(rtsr, fn, None, [0], None, good, None) == rtsr.RTX_EINVAL and who + ": the scene is NULL" in rtsr.last_error()
+        assert call_set_prims(rtsr, fn, None, [0], None, good, None) == rtsr.RTX_EINVAL and who + ": the scene is NULL" in rtsr.last_error()
 
 
 def test_host_update_is_clean_under_asan_and_ubsan(tmp_path):
