@@ -26,6 +26,7 @@
 #include "../../../include/rtx_abi.h"
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
+#include "../core/item_order.hpp"
 #include "../core/karras.hpp"
 #include "../core/prim_box.hpp"
 #include "../host/flat_scene.hpp"
@@ -82,6 +83,7 @@ struct TraceSwitches {
   bool mv_common = true, motion = true, motion_axis = true;  // RTX_MV_COMMON / _MOTION / _MOTION_AXIS
   bool single_leaf = true, pass_pipeline = true, validate = false;  // RTX_SINGLE_LEAF / _PASS_PIPELINE; RTX_VALIDATE: set at all
   uint32_t chunk = TRACE_CHUNK;  // RTX_CHUNK [64, 65536]: sample indices a k_trace_lds wave reserves per grab
+  uint32_t item_group = 0;       // RTX_ITEM_GROUP [1, 2^30]: pixels per group of a pass's item order (core/item_order.hpp); 0: WalkTuning's
   uint32_t world_threshold = 8;  // RTX_WORLD_THRESHOLD [0, 64]: k_trace_world's walk steps go first while this many lanes walk (0: majority)
   uint32_t walk_threshold = 0, regen_min = 0, leaf_weight = 0;  // RTX_WALK_THRESHOLD / _REGEN_MIN / _LEAF_WEIGHT [1, 64]; 0: WalkTuning's
   // wavefront integrator: RTX_WF_PATHS [256, 2^27] path slots; RTX_WF_REFILL [1, 64] free lanes a wave waits for before it takes new
@@ -99,6 +101,7 @@ struct Workspace {
   DeviceBuffer<double> accum;
   DeviceBuffer<rt::TraceCounters> counters;
   DeviceBuffer<unsigned int> work_counter;  // two: one per pass stream
+  DeviceBuffer<PassMap> pass_map;           // two likewise: a pass's item order and pixel map, where its trace kernel reads them (k_pass_begin)
   DeviceBuffer<unsigned long long> diag;    // region counters of the diagnostic instantiations (diag_clear / diag_print)
   hipEvent_t ev[2] = {nullptr, nullptr};  // trace time of a pass (stats)
   hipStream_t aux_stream = nullptr;
@@ -159,6 +162,13 @@ struct WalkTuning {
   uint32_t regen_min = 1;         // wide k_trace_vote: lanes that must be waiting before the wave regenerates
   uint32_t leaf_weight = 3;       // node lanes x weight >= leaf lanes -> node step
   bool single_leaf = false;       // every BVH leaf holds one primitive (k_trace_lds tests it without a loop)
+  // Pixels per group of a pass's item order (core/item_order.hpp), per kernel family; ITEM_GROUP_MAX: one group, a wave's 64
+  // consecutive items are a row strip of one sample.  RTX_ITEM_GROUP overrides all five.  (profiles/item_order/)
+  // Measured (short runs, two each): k_trace_lds on C2 8304 in the row-strip order, 8699 / 8712 / 8689 / 8652 / 8592 / 8520 /
+  // 8510 Msamples/s with 1 / 2 / 4 / 8 / 16 / 32 / 64; k_trace_world on C3 794 -> 825 / 826 / 827 / 827 / 823 / 819 / 814; wide
+  // k_trace_vote on C4 within 0.3 % of the row-strip order for every size: kept.  Wavefront and simple: not measured, kept.
+  uint32_t item_group_lds = 2, item_group_vote = rt::ITEM_GROUP_MAX, item_group_world = 4,
+           item_group_wavefront = rt::ITEM_GROUP_MAX, item_group_simple = rt::ITEM_GROUP_MAX;
 };
 
 // rtx_scene_set_transforms (scene_update.inc): what an update needs beside the scene's arrays, kept from the upload.
@@ -396,6 +406,7 @@ static TraceSwitches read_switches() {
   sw.single_leaf = flag("RTX_SINGLE_LEAF") != 0; sw.pass_pipeline = flag("RTX_PASS_PIPELINE") != 0;
   sw.validate = getenv("RTX_VALIDATE") != nullptr;
   sw.chunk = num("RTX_CHUNK", 64, 65536, sw.chunk);
+  sw.item_group = num("RTX_ITEM_GROUP", 1, (int)rt::ITEM_GROUP_MAX, 0);
   sw.world_threshold = num("RTX_WORLD_THRESHOLD", 0, 64, sw.world_threshold);
   sw.walk_threshold = num("RTX_WALK_THRESHOLD", 1, 64, 0); sw.regen_min = num("RTX_REGEN_MIN", 1, 64, 0); sw.leaf_weight = num("RTX_LEAF_WEIGHT", 1, 64, 0);
   const char* wp = getenv("RTX_WF_PATHS");
@@ -424,7 +435,7 @@ static uint32_t grid_size(uint32_t total, uint32_t block, uint64_t resident) {
 // What every trace launch of one pass takes (render_impl's pass loop).
 struct PassArgs {
   rt::RenderParams rp;
-  ShardMap sm;
+  ShardMap sm;                    // points at the pass's PassMap (render_impl writes one per pass: k_pass_begin)
   uint32_t s_begin, total, npix;  // absolute index of the pass's first sample; (sample, pixel) items of the pass; pixels of the shard
   double* samples;                // this pass's half of the sample buffer, its work counter and stream
   unsigned int* work_counter;
@@ -542,7 +553,7 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
   const uint32_t threshold = ds->walk.walk_threshold | (ds->walk.regen_min << 16);
 #define LAUNCH_VOTE_WIDE(FEAT, DIAGF, THRESHOLD, MAP)                                                                  \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, false, true, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
-                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter,             \
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.samples, a.work_counter,             \
                      DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, THRESHOLD, (uint32_t)wt.levels,              \
                      (uint32_t)p.bvh_pos, wt.nodes4, p.tri_base, lds_tables, p.top)
   // a triangle mesh in a room of rectangles, no spheres / lists / glass (the dragon room): the leaner instantiation
@@ -569,7 +580,6 @@ static rtx_status launch_vote_wide(DeviceScene* ds, const PassArgs& a, bool diag
 
 static rtx_status launch_vote(DeviceScene* ds, const PassArgs& a) {
   const VotePlan& p = ds->vote;
-  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   const bool diag = ds->sw.kernel == ForcedKernel::vote && ds->sw.diag && !a.active;  // (diagnostics: uniform passes only)
   if (a.preset == 1 && ds->wide.nodes4) return launch_vote_wide(ds, a, diag);
   const bool ring = p.ring[a.preset];
@@ -577,7 +587,7 @@ static rtx_status launch_vote(DeviceScene* ds, const PassArgs& a) {
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * (uint64_t)p.blocks_per_cu[a.preset]);
 #define LAUNCH_VOTE3(FEAT, DIAGF, RINGF, MAP)                                                                            \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_vote<FEAT, DIAGF, RINGF, false, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
-                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter,              \
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.samples, a.work_counter,              \
                      DIAGF ? ds->ws.diag : nullptr, ds->walk.leaf_weight, ds->walk.walk_threshold, a.stack_levels,      \
                      (uint32_t)p.bvh_pos, (const FlatNode4*)nullptr, p.tri_base, 0u, p.top)
 #define LAUNCH_VOTE2(FEAT, RINGF) with_map(a, [&](auto map) { LAUNCH_VOTE3(FEAT, false, RINGF, map); })
@@ -702,7 +712,6 @@ static rtx_status plan_world(DeviceScene* ds, const FlatScene& fs) {
 
 static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   const WorldPlan& p = ds->world;
-  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   const bool wide = ds->wide.nodes4 != nullptr;
   const bool book2 = (a.feat & ~P_BOOK2) == 0;
   const bool has_gravity = (a.feat & rt::F_GRAVITY_SPHERE) != 0;
@@ -720,7 +729,7 @@ static rtx_status launch_world(DeviceScene* ds, const PassArgs& a) {
   const rt::SceneView& v = ds->view;
 #define LAUNCH_WORLD3(FEAT, WIDEF, DIAGF, MAP)                                                                               \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_world<FEAT, WIDEF, WORLD_WPS, DIAGF, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), lds, \
-                     a.stream, v, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, a.work_counter, v.entries, v.top_level, v.spheres, \
+                     a.stream, v, a.rp, MAP, a.s_begin, a.total, a.samples, a.work_counter, v.entries, v.top_level, v.spheres, \
                      v.moving_spheres, v.rects, v.triangles, v.materials, v.textures, v.refs, ds->wide.nodes4, p.desc,     \
                      ds->walk.leaf_weight, ds->sw.world_threshold, levels, p.perlin_lds, p.mat_lds, p.tex_lds,             \
                      DIAGF ? ds->ws.diag : nullptr)
@@ -837,7 +846,6 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
 // *variant: the instantiation launched, as RtxRenderStats.trace_variant reports it (lds_variant.inc).
 static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera* cam, int32_t* variant) {
   const LdsPlan& p = ds->lds;
-  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
   *variant = lds_trace_variant(p.motion.ok, p.motion_t0, p.motion_t1, (double)cam->time1, (double)cam->time2, p.motion_axis, p.mv_common);
   const bool motion = (*variant & LDSV_TIME_BOXES) != 0;
@@ -850,7 +858,7 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
 #define LAUNCH_LDS2(FEAT, RINGF, MOTIONF)                                                                               \
   with_map(a, [&](auto map) {                                                                                           \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, decltype(map)>), dim3(grid), dim3(LDSK_BLOCK), L.total, \
-                       a.stream, ds->view, a.rp, map, a.s_begin, a.total, a.npix, a.samples, a.work_counter, wk.leaf_weight, \
+                       a.stream, ds->view, a.rp, map, a.s_begin, a.total, a.samples, a.work_counter, wk.leaf_weight, \
                        wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,  \
                        m_t0, m_inv, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1);                        \
   })
@@ -871,7 +879,7 @@ static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
   const uint32_t grid = grid_size(a.total, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
 #define LAUNCH_SIMPLE2(FEAT, MAP)                                                                                       \
   hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_simple<FEAT, COUNT, decltype(MAP)>), dim3(grid), dim3(TRACE_BLOCK), a.stack_lds, \
-                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.npix, a.samples, ds->ws.counters)
+                     a.stream, ds->view, a.rp, MAP, a.s_begin, a.total, a.samples, ds->ws.counters)
 #define LAUNCH_SIMPLE(FEAT) with_map(a, [&](auto map) { LAUNCH_SIMPLE2(FEAT, map); })
   const bool inst = (a.feat & rt::F_INSTANCE) != 0;
   if constexpr (COUNT) {  // (counting renders are never adaptive)
@@ -891,14 +899,13 @@ static void launch_simple(const DeviceScene* ds, const PassArgs& a) {
 // Three presets cover every world the default launcher accepts: the dragon room exactly, any world without GravitySpheres, and
 // everything.  Persistent: as many blocks as are resident, at most one per TRACE_CHUNK items.
 static rtx_status launch_nee(const DeviceScene* ds, const PassArgs& a) {
-  HIP_TRY(hipMemsetAsync(a.work_counter, 0, sizeof(unsigned int), a.stream));
   const int preset = (a.feat & rt::F_INSTANCE) ? 3 : ((a.feat & ~P_MESH_ROOM) == 0 ? 0 : ((a.feat & rt::F_GRAVITY_SPHERE) ? 2 : 1));
 #define LAUNCH_NEE(FEAT, MAP)                                                                                                   \
   do {                                                                                                                          \
     const int nb = occupancy(k_trace_nee<FEAT, decltype(MAP)>, a.stack_lds);                                                    \
     const uint32_t grid = grid_size(a.total, TRACE_CHUNK, (uint64_t)ds->n_cu * (uint64_t)(nb > 0 ? nb : 1) * (TRACE_BLOCK / 64)); \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_nee<FEAT, decltype(MAP)>), dim3((grid + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64)),     \
-                       dim3(TRACE_BLOCK), a.stack_lds, a.stream, ds->view, ds->lights, a.rp, MAP, a.s_begin, a.total, a.npix,     \
+                       dim3(TRACE_BLOCK), a.stack_lds, a.stream, ds->view, ds->lights, a.rp, MAP, a.s_begin, a.total,     \
                        a.samples, a.work_counter);                                                                              \
   } while (0)
   with_map(a, [&](auto map) {
@@ -972,7 +979,7 @@ static rtx_status wave_pass(DeviceScene* ds, const PassArgs& a) {
   for (;; ++it) {
     with_map(a, [&](auto map) {
       hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wf_generate<decltype(map)>), dim3(n_seg), dim3(WF_SEG), 0, stream, pool, a.rp, map,
-                         a.s_begin, a.total, a.npix);
+                         a.s_begin, a.total);
     });
     if ((uint32_t)(it + 1) % check_every == 0u) {
       HIP_TRY(hipMemsetAsync(pool.ctrl, 0, 16, stream));
@@ -1016,6 +1023,18 @@ static void plan_walk(DeviceScene* ds, const LeafScan& leaves) {
   if (sw.leaf_weight) w.leaf_weight = sw.leaf_weight;
   if (!sw.single_leaf) w.single_leaf = false;
   if (sw.walk_threshold) w.walk_threshold = sw.walk_threshold;
+  if (sw.item_group) w.item_group_lds = w.item_group_vote = w.item_group_world = w.item_group_wavefront = w.item_group_simple = sw.item_group;
+}
+
+// Pixels per group of the item order of a pass traced by `kernel` (k_trace_nee: the world kernel's).
+static uint32_t item_group_of(const WalkTuning& w, int32_t kernel) {
+  switch (kernel) {
+    case RTX_KERNEL_SIMPLE: return w.item_group_simple;
+    case RTX_KERNEL_LDS: return w.item_group_lds;
+    case RTX_KERNEL_WAVEFRONT: return w.item_group_wavefront;
+    case RTX_KERNEL_VOTE: return w.item_group_vote;
+    default: return w.item_group_world;
+  }
 }
 
 // ------------------------------------------------------------------ render
@@ -1104,6 +1123,7 @@ static rtx_status prepare_workspace(DeviceScene* ds, uint64_t sample_buffer_byte
   }
   if (!ws.counters) HIP_TRY(ws.counters.alloc(sizeof(rt::TraceCounters)));
   if (!ws.work_counter) HIP_TRY(ws.work_counter.alloc(2 * sizeof(unsigned int)));
+  if (!ws.pass_map) HIP_TRY(ws.pass_map.alloc(2 * sizeof(PassMap)));
   if (pipeline && !ws.aux_stream) {
     HIP_TRY(hipStreamCreateWithFlags(&ws.aux_stream, hipStreamNonBlocking));
     for (int i = 0; i < 3; ++i) HIP_TRY(hipEventCreateWithFlags(&ws.ev_pass[i], hipEventDisableTiming));
@@ -1173,7 +1193,7 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
   if (nee) { set_error("render: light sampling is f64 only"); return RTX_EUNSUPPORTED; }  // (the *_ex entries reject it first)
 #endif
   const int32_t kernel = nee ? (int32_t)RTX_KERNEL_NEE : choose_trace_kernel(ds, preset, COUNT);
-  PassArgs a = {rp, {w, sh.block_rows, sh.shard_index, sh.shard_count}, 0u, 0u, (uint32_t)nitem, nullptr, nullptr, stream,
+  PassArgs a = {rp, {nullptr}, 0u, 0u, (uint32_t)nitem, nullptr, nullptr, stream,
                 preset, feat, stack_levels, stack_bytes(stack_levels), adaptive ? range->active : nullptr};
 
   float trace_ms = 0.f;
@@ -1197,7 +1217,11 @@ static rtx_status render_impl(DeviceScene* ds, const RtxCamera* cam, const RtxCo
       a.stream = half ? ws.aux_stream : stream;  // every launch of the pass goes to this stream
       a.samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)nitem * 3u;
       a.work_counter = ws.work_counter + half;
+      a.sm.pass = ws.pass_map + half;
       if (stats) HIP_TRY(hipEventRecord(ws.ev[0], a.stream));
+      const PassMap pm = {rt::make_item_order((uint32_t)nitem, s_count, item_group_of(ds->walk, kernel)), rt::make_div32((uint32_t)w),
+                          rt::make_div32((uint32_t)sh.block_rows), (uint32_t)sh.shard_index, (uint32_t)sh.shard_count};
+      hipLaunchKernelGGL(k_pass_begin, dim3(1), dim3(64), 0, a.stream, a.work_counter, ws.pass_map + half, pm);
       switch (kernel) {
         case RTX_KERNEL_SIMPLE: launch_simple<COUNT>(ds, a); break;
         case RTX_KERNEL_LDS: st = launch_lds(ds, a, cam, &variant); break;

@@ -24,7 +24,7 @@ static_assert(P_ALL == (1u << 20) - 1u, "the presets of worlds without instance 
 template <uint32_t F, bool COUNT, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_simple(rt::SceneView sv, rt::RenderParams rp,
                                                                SM sm, uint32_t s_begin,
-                                                               uint32_t total, uint32_t npix,
+                                                               uint32_t total,
                                                                double* __restrict__ samples,
                                                                rt::TraceCounters* counters) {
   extern __shared__ int32_t lds_stack[];
@@ -36,9 +36,9 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_simple(rt::SceneView sv, 
   for (uint64_t g64 = (uint64_t)blockIdx.x * TRACE_BLOCK + threadIdx.x; g64 < total;
        g64 += (uint64_t)gridDim.x * TRACE_BLOCK) {
     const uint32_t g = (uint32_t)g64;
-    uint32_t i, j;
-    const uint32_t s_local = item_pixel(sm, npix, g, &i, &j);
-    store_sample(samples, g, rt::trace_sample<F, COUNT>(sv, rp, i, j, s_begin + s_local, stack, &cnt));
+    uint32_t i, j, s_local;
+    const uint32_t slot = item_pixel(sm, g, &i, &j, &s_local);
+    store_sample(samples, slot, rt::trace_sample<F, COUNT>(sv, rp, i, j, s_begin + s_local, stack, &cnt));
   }
   if (COUNT) flush_counters(cnt, counters);
 }

@@ -73,7 +73,7 @@ struct LdsStack16 {  // slot (level, thread) at bottom + level * LDSK_LEVEL_BYTE
 // that axis's planes carry slopes -- 4 fmas and 4 LDS dwords per child pair instead of 12 and 12, node records of 27 dwords.
 template <uint32_t F, bool RING, uint32_t MOTION, class SM = ShardMap>
 __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::RenderParams rp, SM sm,
-                                                          uint32_t s_begin, uint32_t total, uint32_t npix,
+                                                          uint32_t s_begin, uint32_t total,
                                                           double* __restrict__ samples, unsigned int* work_counter,
                                                           uint32_t leaf_weight, uint32_t walk_threshold, uint32_t chunk, uint32_t ring_cap,
                                                           uint32_t stack_levels, LdsSceneDims dims, rt::real motion_t0, rt::real motion_inv_dt,
@@ -190,7 +190,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
   uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
   bool queue_empty = false;               // wave-uniform
   bool active = false;
-  uint32_t g = 0;
+  uint32_t g = 0;  // the path's slot of the sample buffer (start_path)
   rt::PathState ps;
   bool midwalk = false;
   rt::Ray32 q = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -231,8 +231,7 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
         if (chunk_pos < chunk_end) {
           const uint32_t avail = chunk_end - chunk_pos;
           if (!active && rank < avail) {
-            g = chunk_pos + rank;
-            start_path(rp, sm, npix, s_begin, g, &ps);
+            g = start_path(rp, sm, s_begin, chunk_pos + rank, &ps);
             active = true;
           }
           chunk_pos += (n_need < avail) ? n_need : avail;

@@ -11,7 +11,7 @@
 // kernel writes.
 template <uint32_t F, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_nee(rt::SceneView sv, rt::LightView lv, rt::RenderParams rp, SM sm,
-                                                            uint32_t s_begin, uint32_t total, uint32_t npix,
+                                                            uint32_t s_begin, uint32_t total,
                                                             double* __restrict__ samples, unsigned int* __restrict__ work_counter) {
   extern __shared__ int32_t lds_stack[];
   LdsStack stack;
@@ -19,14 +19,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_trace_nee(rt::SceneView sv, rt:
   stack.n = 0;
   const uint32_t lane = threadIdx.x & 63u;
   uint32_t next = 0, end = 0;  // this lane's next item of the wave's chunk; the chunk's end (wave-uniform)
-  uint32_t item = 0;
+  uint32_t item = 0;  // the live path's slot of the sample buffer
   bool live = false;
   rt::PathState ps;
   rt::real last_pdf = rt::real(-1.0);
   for (;;) {
     if (!live && next < end) {
-      start_path(rp, sm, npix, s_begin, next, &ps);
-      item = next;
+      item = start_path(rp, sm, s_begin, next, &ps);
       next += 64u;
       last_pdf = rt::real(-1.0);
       live = true;

@@ -5,7 +5,7 @@
 // the whole block, or only around the row stores and loads) changed these kernels' instructions; as text the compiler sees what
 // it saw when each kernel spelled the block out.  Uses the kernel's locals: n_need and rank (count of the lanes without a path,
 // and each one's rank among them), ring_f, ring_g, ring_n, chunk_pos, chunk_end, queue_empty, chunk, lane, active, ps, g and
-// the pass's arguments.  The row order (origin, direction, time, RNG state; then the item) and path_begin's constants
+// the pass's arguments.  The row order (origin, direction, time, RNG state; then the sample's slot) and path_begin's constants
 // (core/integrator.hpp) live here and nowhere else.
 //
 // Regeneration (Philox seeding, pixel jitter, lens rejection loop, camera ray: ~600 VALU) runs for the whole wave at once and
@@ -22,16 +22,18 @@ for (int rep = 0; rep < 2 && ring_n < n_need && !queue_empty; ++rep) {
   const uint32_t m = room < avail ? room : avail;
   RING_DIAG(wave_ballot(lane < m));
   if (lane < m) {
-    const uint32_t gg = chunk_pos + lane;
-    rt::PathState fresh;
-    start_path(rp, sm, npix, s_begin, gg, &fresh);
+    // start_path in two halves, the sample's slot stored in between: nothing of the item's map stays in a register across
+    // path_begin, where this kernel's register count peaks
     const uint32_t slot = ring_n + lane;
+    uint32_t pi, pj, s_local;
+    ring_g[slot] = item_pixel(sm, chunk_pos + lane, &pi, &pj, &s_local);
+    rt::PathState fresh;
+    rt::path_begin(rp, pi, pj, s_begin + s_local, &fresh);
     ring_f[0 * RING_CAP + slot] = fresh.ray.origin.x; ring_f[1 * RING_CAP + slot] = fresh.ray.origin.y;
     ring_f[2 * RING_CAP + slot] = fresh.ray.origin.z; ring_f[3 * RING_CAP + slot] = fresh.ray.direction.x;
     ring_f[4 * RING_CAP + slot] = fresh.ray.direction.y; ring_f[5 * RING_CAP + slot] = fresh.ray.direction.z;
     ring_f[6 * RING_CAP + slot] = fresh.ray.time;
     ring_f[7 * RING_CAP + slot] = rt::bits_f64(fresh.rng.s0); ring_f[8 * RING_CAP + slot] = rt::bits_f64(fresh.rng.s1);
-    ring_g[slot] = gg;
   }
   chunk_pos += m;
   ring_n += m;

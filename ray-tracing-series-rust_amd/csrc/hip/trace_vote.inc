@@ -176,7 +176,7 @@ __device__ __forceinline__ void walk_node_step4(const FlatNode4* __restrict__ no
 template <uint32_t F, bool DIAG, bool RING, bool WIDE, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv, rt::RenderParams rp,
                                                             SM sm, uint32_t s_begin, uint32_t total,
-                                                            uint32_t npix, double* __restrict__ samples,
+                                                            double* __restrict__ samples,
                                                             unsigned int* work_counter,
                                                             unsigned long long* diag, uint32_t leaf_weight,
                                                             uint32_t walk_threshold, uint32_t stack_levels, uint32_t bvh_pos,
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
   uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
   bool queue_empty = false;               // wave-uniform
   bool active = false;
-  uint32_t g = 0;
+  uint32_t g = 0;  // the path's slot of the sample buffer (start_path)
   rt::PathState ps;
   // walk state, kept across outer iterations so an unfinished walk can be carried over
   bool midwalk = false;
@@ -257,8 +257,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, 4) void k_trace_vote(rt::SceneView sv,
         uint32_t avail = chunk_end - chunk_pos;
         DIAG_ADD(1, wave_ballot(!active && rank < avail));
         if (!active && rank < avail) {
-          g = chunk_pos + rank;
-          start_path(rp, sm, npix, s_begin, g, &ps);
+          g = start_path<WIDE>(rp, sm, s_begin, chunk_pos + rank, &ps);
           active = true;
         }
         chunk_pos += (n_need < avail) ? n_need : avail;

@@ -57,7 +57,7 @@ struct WavePool {
   rt::real* product;         // [3][P]
   rt::real* output;          // [3][P]
   int32_t* depth;            // [P] bounces left | WF_HAS_OUTPUT
-  uint32_t* g;               // [P] sample index inside the pass, WF_FREE
+  uint32_t* g;               // [P] the path's slot of the pass's sample buffer, WF_FREE
   rt::real* hit_t;           // [P]
   uint32_t* hit_ref;         // [P]
   uint32_t* free_list;       // [P]: segment b lists its free slots at [b * WF_SEG, b * WF_SEG + n_free[b])
@@ -88,8 +88,7 @@ __global__ __launch_bounds__(256) void k_wf_count(WavePool pool) {
 
 // Segment b refills its free slots: its m-th sample is sample ((m / 64) * n_seg + b) * 64 + m % 64 of the pass.
 template <class SM>
-__global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total,
-                                                        uint32_t npix) {
+__global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total) {
   const uint32_t b = blockIdx.x, k = threadIdx.x, n_seg = gridDim.x;
   const uint32_t n_free = pool.n_free[b], cur = pool.cursor[b];
   if (n_free == 0u) return;
@@ -103,7 +102,7 @@ __global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::Rende
   const uint32_t P = pool.P;
   const uint32_t slot = pool.free_list[b * WF_SEG + k];
   rt::PathState ps;
-  start_path(rp, sm, npix, s_begin, g, &ps);
+  const uint32_t sample_slot = start_path(rp, sm, s_begin, g, &ps);
   const bool ended = rt::path_bounce_begin(&ps);  // world.rs:64-67 (max_depth >= 1: never at birth in f64)
   pool.ray[0 * (size_t)P + slot] = ps.ray.origin.x; pool.ray[1 * (size_t)P + slot] = ps.ray.origin.y; pool.ray[2 * (size_t)P + slot] = ps.ray.origin.z;
   pool.ray[3 * (size_t)P + slot] = ps.ray.direction.x; pool.ray[4 * (size_t)P + slot] = ps.ray.direction.y; pool.ray[5 * (size_t)P + slot] = ps.ray.direction.z;
@@ -112,7 +111,7 @@ __global__ __launch_bounds__(WF_SEG) void k_wf_generate(WavePool pool, rt::Rende
   pool.product[slot] = ps.product.x; pool.product[(size_t)P + slot] = ps.product.y; pool.product[2 * (size_t)P + slot] = ps.product.z;
   pool.depth[slot] = ps.depth < 0 ? 0 : ps.depth;
   pool.hit_ref[slot] = ended ? WF_ENDED : WF_NOHIT;
-  pool.g[slot] = g;
+  pool.g[slot] = sample_slot;
 }
 
 // The BVH query of every live slot.

@@ -156,7 +156,7 @@ __device__ __forceinline__ bool direct_closest(const rt::SceneView& sv, const rt
 // DIAG: per-region counters (executions by the wave, lanes taking part) -- diagnostic build only (RTX_TRACE_KERNEL=world_diag).
 template <uint32_t F, bool WIDE, int WAVES_PER_SIMD, bool DIAG = false, class SM = ShardMap>
 __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
-    rt::SceneView sv_in, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total, uint32_t npix,
+    rt::SceneView sv_in, rt::RenderParams rp, SM sm, uint32_t s_begin, uint32_t total,
     double* __restrict__ samples, unsigned int* __restrict__ work_counter, const rt::FlatEntry* __restrict__ entries_ro,
     const int32_t* __restrict__ top_level_ro, const rt::FlatSphere* __restrict__ spheres_ro,
     const rt::FlatMovingSphere* __restrict__ msph_ro, const rt::FlatRect* __restrict__ rects_ro,
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
   uint32_t chunk_pos = 0, chunk_end = 0;  // wave-uniform
   bool queue_empty = false;               // wave-uniform
   uint32_t stage = WS_NEED;
-  uint32_t g = 0;
+  uint32_t g = 0;  // the path's slot of the sample buffer (start_path)
   rt::PathState ps;
   // the lane's scan of the world list
   int32_t ei = 0;              // entry being processed
@@ -587,8 +587,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
           const uint32_t n_want = (uint32_t)__popcll(need_mask);
           const uint32_t avail = chunk_end - chunk_pos;
           if (stage == WS_NEED && rank < avail) {
-            g = chunk_pos + rank;
-            start_path(rp, sm, npix, s_begin, g, &ps);
+            g = start_path(rp, sm, s_begin, chunk_pos + rank, &ps);
             begin_bounce_fast();
           }
           chunk_pos += (n_want < avail) ? n_want : avail;
