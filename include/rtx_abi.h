@@ -618,12 +618,13 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
  * int32, 0 without a wide tree), 9 the scene's max_stack as its binary walks are now launched with (one int32; a rebuild of
  * an instance tree changes it), 10 triangles, 11 top_box32 (6 floats per slot), 13 the static spheres (FlatSphere, 40 bytes
  * each in an f64 scene), 14 the light table of next-event estimation (FlatLight, 40 bytes each; 0 bytes without sampled
- * lights).  bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
+ * lights), 15 materials and 16 textures (FlatMaterial / FlatTexture: 48 bytes each in an f64 scene, 32 in an f32 scene).
+ * bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
  * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
  * instance tree, the box before the ops), 12: triangle_id (one int32 per flat triangle).  14 is the light table an upload
- * of the flat scene as it stands would build. */
+ * of the flat scene as it stands would build; 15 and 16 are the host's materials and textures (48 bytes each). */
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
 
 /* ---- instance trees: the quality of a tree as it stands, and a rebuild for the current pose ---------------------------------
@@ -768,6 +769,88 @@ rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, co
  * read-back: a value that is not finite gives that sphere and the boxes above it unspecified culling.  No index is derived
  * from a value, so nothing can leave an allocation. */
 rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream);
+
+/* ---- relighting and look development: new shading parameters -----------------------------------------------------------------
+ * Editing colours, a noise scale, a metal, a glass's index or a fog's density of a flattened or a resident scene gives the
+ * scene that rtx_flatten (and rtx_scene_upload / rtx_scene_upload_f32) build from scratch when the builder calls are made with
+ * the new values: byte for byte in every array a value reaches, and every entry point answers bit for bit as on that scene.
+ * No primitive, BVH or image is re-sent.
+ *
+ * Indices.  A material or texture index is the BUILDER'S HANDLE (rtx_lambertian .. rtx_isotropic, rtx_solid_color .. rtx_image_*:
+ * the graph's materials and textures flatten 1:1, in order) and what rtx_scene_cast_rays reports in ids[:, 1].  A medium is named
+ * by its top-level slot (rtx_flat_top_level_kind 4); the phase material and colour texture that rtx_constant_medium made inside
+ * have no handle of the caller's: walk rtx_flat_medium_info -> rtx_flat_material_info -> tex.
+ *
+ * What each edit writes, with the builder's own arithmetic (csrc/core/shading_edit.hpp), and nothing else:
+ *   RTX_SHADE_SOLID_COLOR     the texture's colour, and the copy of it the flattener keeps in EVERY Lambertian / DiffuseLight /
+ *                             Isotropic material that names the texture (kernels for worlds without checker, noise and image
+ *                             textures read only that copy).  A checker that has the texture as a child holds no copy.
+ *   RTX_SHADE_NOISE_SCALE     the texture's scale; its Perlin tables are kept.
+ *   RTX_SHADE_METAL           albedo = r g b, fuzz clamped from above to 1 as rtx_metal does (a negative fuzz passes as it does there).
+ *   RTX_SHADE_DIELECTRIC      ir, and the three constants the flattener derives from it (1 / ir, two reflectance terms), in f64.
+ *   RTX_SHADE_MEDIUM_DENSITY  -1 / density in the medium's entry and, on a resident scene, in k_trace_world's slot record.
+ * An f32 scene takes every value computed in f64 as above through the converter's (float) cast.  On a resident f64 scene that
+ * holds a light table, a batch with a texture edit recomputes every light's pick weight, cdf and pmf on the device
+ * (k_refresh_lights: the recomputation rtx_scene_set_spheres runs, by the function that built the table; when no light's colour
+ * changed it leaves the same bytes).
+ *
+ * Refused with RTX_EINVAL, the scene unchanged, nothing enqueued, the message naming the edit's position and field, checked in
+ * this order: a NULL scene, NULL edits with n > 0, n < 0; then per edit an unknown `what`, an index out of range, a target of the
+ * wrong kind (the message names the spelling that works), a value that is not finite (no other rule: the builder applies none,
+ * density 0 gives -inf as rtx_constant_medium does), a non-zero unused v; then one target -- (texture | material | slot, index)
+ * -- named twice in the call.  Last, a resident scene on another device than the current one.  n = 0 is RTX_OK, nothing launched.
+ *
+ * Outside an edit: kinds do not change; which texture a material names does not change; a checker's children do not change;
+ * Perlin tables do not change; image texels are not edited; RtxFlatInfo is unaffected.  rtx_multi_* scenes are not covered:
+ * edit the flat scene and create the handle again. */
+#define RTX_SHADE_SOLID_COLOR    0  /* index: texture (RTX_TEX_SOLID);       v = r g b      : rtx_solid_color's rgb            */
+#define RTX_SHADE_NOISE_SCALE    1  /* index: texture (RTX_TEX_NOISE);       v[0] = scale   : rtx_noise's scale, tables kept   */
+#define RTX_SHADE_METAL          2  /* index: material (RTX_MAT_METAL);      v = r g b fuzz : rtx_metal's arguments            */
+#define RTX_SHADE_DIELECTRIC     3  /* index: material (RTX_MAT_DIELECTRIC); v[0] = ir      : rtx_dielectric's ir              */
+#define RTX_SHADE_MEDIUM_DENSITY 4  /* index: top-level slot of kind 4;      v[0] = density : rtx_constant_medium's density    */
+typedef struct RtxShadingEdit {     /* 40 B; unused v must be 0 */
+  int32_t what, index;
+  double v[4];
+} RtxShadingEdit;
+/* The material and texture kinds as the flat arrays hold them. */
+#define RTX_MAT_LAMBERTIAN    0
+#define RTX_MAT_METAL         1
+#define RTX_MAT_DIELECTRIC    2
+#define RTX_MAT_DIFFUSE_LIGHT 3
+#define RTX_MAT_ISOTROPIC     4
+#define RTX_TEX_SOLID   0
+#define RTX_TEX_CHECKER 1
+#define RTX_TEX_NOISE   2
+#define RTX_TEX_IMAGE   3
+/* Host-only inspectors: from an index to what may be edited.  RTX_EINVAL for a NULL argument, an index out of range, or (medium)
+ * a slot that is not a ConstantMedium. */
+typedef struct RtxMaterialInfo {    /* 40 B */
+  int32_t kind, tex;                /* RTX_MAT_*; the texture a Lambertian / DiffuseLight / Isotropic names, -1 for the others */
+  double albedo[3];                 /* Metal: the colour; texture-carrying kinds: the colour of `tex` when that is a SolidColor;
+                                       Dielectric: 1 / ir and the two reflectance terms */
+  double param;                     /* Metal: fuzz as stored (<= 1); Dielectric: ir */
+} RtxMaterialInfo;
+typedef struct RtxTextureInfo {     /* 48 B */
+  int32_t kind, a, b, pad;          /* RTX_TEX_*; checker: a = even, b = odd; noise: a = its Perlin table; image: a = its image */
+  double color[3];                  /* SolidColor */
+  double scale;                     /* Noise */
+} RtxTextureInfo;
+typedef struct RtxMediumInfo {      /* 16 B */
+  int32_t material, pad;            /* the phase material (Isotropic) rtx_constant_medium made */
+  double neg_inv_density;           /* -1 / density, as stored */
+} RtxMediumInfo;
+rtx_status rtx_flat_material_info(const rtx_flat* f, int32_t index, RtxMaterialInfo* out);
+rtx_status rtx_flat_texture_info(const rtx_flat* f, int32_t index, RtxTextureInfo* out);
+rtx_status rtx_flat_medium_info(const rtx_flat* f, int32_t slot, RtxMediumInfo* out);
+/* Host only.  Edits the flat scene in place (materials, textures, entries); it can then be uploaded, or handed to
+ * rtx_multi_create, without flattening again. */
+rtx_status rtx_flat_set_shading(rtx_flat* f, const RtxShadingEdit* edits, int64_t n);
+/* The same on a resident scene of either precision.  `edits` is a HOST array, free for reuse on return; the work -- one small
+ * copy, k_set_shading with one thread per written record, and k_refresh_lights after a texture edit on an f64 scene with a light
+ * table -- is asynchronous on hip_stream.  Ordering against renders and casts on OTHER streams is the caller's business; two
+ * updates of one scene may not run concurrently (issue them on one stream, or synchronise).  A progressive handle made before an
+ * edit holds samples of the old look, and the features it has already computed are those of the old look too: make a new one. */
+rtx_status rtx_scene_set_shading(rtx_scene* s, const RtxShadingEdit* edits, int64_t n, void* hip_stream);
 
 /* ---- the time-sweep renderer: render_scene_with_time(t0, t1, path, world)  world.rs:1249-1330 ------------------------ */
 /* One frame of the reference's video experiment on a scene that is ALREADY resident on the GPU (many frames, one

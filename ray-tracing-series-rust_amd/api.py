@@ -150,6 +150,29 @@ class RtxRebuildStats(C.Structure):
                 ("reserved", C.c_int32 * 4)]
 
 
+class RtxShadingEdit(C.Structure):
+    _fields_ = [("what", C.c_int32), ("index", C.c_int32), ("v", C.c_double * 4)]
+
+
+class RtxMaterialInfo(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("tex", C.c_int32), ("albedo", C.c_double * 3), ("param", C.c_double)]
+
+
+class RtxTextureInfo(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("pad", C.c_int32), ("color", C.c_double * 3),
+                ("scale", C.c_double)]
+
+
+class RtxMediumInfo(C.Structure):
+    _fields_ = [("material", C.c_int32), ("pad", C.c_int32), ("neg_inv_density", C.c_double)]
+
+
+RTX_SHADE_SOLID_COLOR, RTX_SHADE_NOISE_SCALE, RTX_SHADE_METAL, RTX_SHADE_DIELECTRIC, RTX_SHADE_MEDIUM_DENSITY = 0, 1, 2, 3, 4
+_SHADE_NAMES = ("solid_color", "noise_scale", "metal", "dielectric", "medium_density")
+RTX_MAT_LAMBERTIAN, RTX_MAT_METAL, RTX_MAT_DIELECTRIC, RTX_MAT_DIFFUSE_LIGHT, RTX_MAT_ISOTROPIC = 0, 1, 2, 3, 4
+MATERIAL_KINDS = ("lambertian", "metal", "dielectric", "diffuse_light", "isotropic")
+RTX_TEX_SOLID, RTX_TEX_CHECKER, RTX_TEX_NOISE, RTX_TEX_IMAGE = 0, 1, 2, 3
+TEXTURE_KINDS = ("solid_color", "checker", "noise", "image")
 RTX_REBUILD_MORTON, RTX_REBUILD_SAH = 0, 1
 _REBUILD_NAMES = ("morton", "sah")
 RTX_XFORM_TRANSLATE, RTX_XFORM_ROTATE_Y = 0, 1
@@ -158,7 +181,7 @@ _XFORM_NAMES = ("translate", "rotate_y")
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
                 "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128),
                 "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4), "spheres": (13, 40, 24),
-                "lights": (14, 40, 40)}
+                "lights": (14, 40, 40), "materials": (15, 48, 32), "textures": (16, 48, 32)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
@@ -286,6 +309,11 @@ ABI = {
     "rtx_flat_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
     "rtx_scene_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
     "rtx_scene_set_spheres_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
+    "rtx_flat_material_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMaterialInfo)]),
+    "rtx_flat_texture_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxTextureInfo)]),
+    "rtx_flat_medium_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMediumInfo)]),
+    "rtx_flat_set_shading": (C.c_int32, [_VP, C.POINTER(RtxShadingEdit), C.c_int64]),
+    "rtx_scene_set_shading": (C.c_int32, [_VP, C.POINTER(RtxShadingEdit), C.c_int64, _VP]),
     "rtx_device_scene_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_flat_array": (C.c_int32, [_VP, C.c_int32, _VP, C.c_size_t]),
     "rtx_builder_graph": (_VP, [_VP]),
@@ -593,6 +621,36 @@ class Flat:
         ids, spheres = _prim_update(ids, spheres, *_SPHERE_VALUES)
         _check(lib.rtx_flat_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3)))
 
+    def set_shading(self, edits):
+        """New shading parameters, in place (rtx_flat_set_shading): the flat scene becomes the one flattened from scratch when
+        the builder calls are made with the new values.  edits: a list of ("solid_color", tex, (r, g, b)) | ("noise_scale", tex,
+        s) | ("metal", mat, (r, g, b), fuzz) | ("dielectric", mat, ir) | ("medium_density", slot, d); tex and mat are the
+        builder's handles (what cast_rays reports in ids[:, 1] is a mat), slot an index in the world list.  ValueError for a
+        malformed tuple; RtxError for what the scene does not admit."""
+        arr = _shading_edits(edits)
+        _check(lib.rtx_flat_set_shading(self._p, arr, len(arr)))
+
+    def material(self, index):
+        """Material `index` as the flat scene holds it (rtx_flat_material_info): kind (a name of MATERIAL_KINDS), tex, albedo,
+        param."""
+        info = RtxMaterialInfo()
+        _check(lib.rtx_flat_material_info(self._p, int(index), C.byref(info)))
+        return {"kind": MATERIAL_KINDS[info.kind], "tex": info.tex, "albedo": tuple(info.albedo), "param": info.param}
+
+    def texture(self, index):
+        """Texture `index` as the flat scene holds it (rtx_flat_texture_info): kind (a name of TEXTURE_KINDS), a, b, color,
+        scale."""
+        info = RtxTextureInfo()
+        _check(lib.rtx_flat_texture_info(self._p, int(index), C.byref(info)))
+        return {"kind": TEXTURE_KINDS[info.kind], "a": info.a, "b": info.b, "color": tuple(info.color), "scale": info.scale}
+
+    def medium(self, slot):
+        """The ConstantMedium in top-level slot `slot` (rtx_flat_medium_info): material (its phase material, whose tex is the
+        fog's colour) and neg_inv_density as stored."""
+        info = RtxMediumInfo()
+        _check(lib.rtx_flat_medium_info(self._p, int(slot), C.byref(info)))
+        return {"material": info.material, "neg_inv_density": info.neg_inv_density}
+
     def rebuild_instance_trees(self, trees=None, builder="morton"):
         """A new topology for instance trees from their members' boxes at the current pose, in place
         (rtx_flat_rebuild_instance_trees).  trees: tree indices, None for every tree.  builder: "morton" -- what
@@ -707,6 +765,41 @@ def _slot_ops(flat, updates):
     return (RtxSlotOps * len(updates)).from_buffer(arr) if len(updates) else (RtxSlotOps * 0)()
 
 
+def _shading_edits(edits):
+    """edits of Flat.set_shading / Scene.set_shading -> a ctypes array of RtxShadingEdit.  Raises ValueError for a tuple of the
+    wrong shape before the library sees anything; what the scene decides (ranges, kinds, finiteness) is the library's."""
+    if isinstance(edits, (dict, str, bytes)) or not hasattr(edits, "__iter__"):
+        raise ValueError("edits must be a list of tuples")
+    edits = list(edits)
+    arr = (RtxShadingEdit * max(len(edits), 1))()
+    shapes = {"solid_color": '("solid_color", tex, (r, g, b))', "noise_scale": '("noise_scale", tex, scale)',
+              "metal": '("metal", mat, (r, g, b), fuzz)', "dielectric": '("dielectric", mat, ir)',
+              "medium_density": '("medium_density", slot, density)'}
+    for i, e in enumerate(edits):
+        if not isinstance(e, (tuple, list)) or len(e) < 2 or e[0] not in _SHADE_NAMES:
+            raise ValueError("edit %d: expected one of %s, got %r" % (i, " | ".join(shapes.values()), e))
+        what, index = e[0], e[1]
+        if len(e) != (4 if what == "metal" else 3):
+            raise ValueError("edit %d: expected %s, got %r" % (i, shapes[what], e))
+        if isinstance(index, bool) or not isinstance(index, (int, np.integer)):
+            raise ValueError("edit %d: index %r is not an integer" % (i, index))
+        try:
+            if what in ("solid_color", "metal"):
+                vals = [float(x) for x in e[2]]
+                if len(vals) != 3:
+                    raise TypeError
+                if what == "metal":
+                    vals.append(float(e[3]))
+            else:
+                vals = [float(e[2])]
+        except (TypeError, ValueError):
+            raise ValueError("edit %d: expected %s, got %r" % (i, shapes[what], e))
+        arr[i].what, arr[i].index = _SHADE_NAMES.index(what), int(index)
+        for a, x in enumerate(vals):
+            arr[i].v[a] = x
+    return (RtxShadingEdit * len(edits)).from_buffer(arr) if edits else (RtxShadingEdit * 0)()
+
+
 def _scene_array(call, flat, name, f32):
     """One array through rtx_flat_array / rtx_device_scene_array as a uint8 numpy array; the size comes from Flat.info()."""
     info = flat.info()
@@ -790,6 +883,15 @@ class Scene:
         `stream`).  ids: host integers either way.  Enqueued on `stream` as in set_transforms."""
         _scene_set_prims(self, lib.rtx_scene_set_spheres, lib.rtx_scene_set_spheres_device, ids, spheres, stream, *_SPHERE_VALUES)
 
+    def set_shading(self, edits, stream=None):
+        """New shading parameters for the RESIDENT scene of either precision (rtx_scene_set_shading): every later call answers as
+        on a scene flattened and uploaded from scratch with the new colours, scales, metal / glass parameters and densities
+        (the light table follows an emitted colour).  edits as in Flat.set_shading.  Enqueued on `stream` as in set_transforms.
+        A progressive handle made earlier holds the old look."""
+        arr = _shading_edits(edits)
+        raw = getattr(stream, "cuda_stream", stream)
+        _check(lib.rtx_scene_set_shading(self._p, arr, len(arr), _VP(raw or None)))
+
     def rebuild_instance_trees(self, trees=None, stream=None):
         """A new topology for instance trees of the RESIDENT scene from their members' boxes at the current pose
         (rtx_scene_rebuild_instance_trees; Morton codes, a radix sort and Karras' tree on the device).  trees: tree indices,
@@ -817,7 +919,8 @@ class Scene:
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
         "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32", "spheres", "lights" (the light table of
-        next-event estimation; empty without sampled lights) or "nodes4" (the 4-wide tree; empty when the scene has none)."""
+        next-event estimation; empty without sampled lights), "materials", "textures" or "nodes4" (the 4-wide tree; empty when
+        the scene has none)."""
         return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)
 
     def wide_levels(self):

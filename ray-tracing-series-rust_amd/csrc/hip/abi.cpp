@@ -13,7 +13,15 @@
 #include "../host/set_transforms.hpp"
 #include "../host/set_triangles.hpp"
 #include "../host/rebuild_instances.hpp"
+#include "../host/set_shading.hpp"
 #include "abi_internal.hpp"
+
+static_assert(RTX_MAT_LAMBERTIAN == rt::MAT_LAMBERTIAN && RTX_MAT_METAL == rt::MAT_METAL && RTX_MAT_DIELECTRIC == rt::MAT_DIELECTRIC &&
+              RTX_MAT_DIFFUSE_LIGHT == rt::MAT_DIFFUSE_LIGHT && RTX_MAT_ISOTROPIC == rt::MAT_ISOTROPIC, "RTX_MAT_* are rt::MAT_*");
+static_assert(RTX_TEX_SOLID == rt::TEX_SOLID && RTX_TEX_CHECKER == rt::TEX_CHECKER && RTX_TEX_NOISE == rt::TEX_NOISE &&
+              RTX_TEX_IMAGE == rt::TEX_IMAGE, "RTX_TEX_* are rt::TEX_*");
+static_assert(sizeof(RtxShadingEdit) == 40 && sizeof(rt::ShadingWrite) == 40, "RtxShadingEdit layout");
+static_assert(sizeof(RtxMaterialInfo) == 40 && sizeof(RtxTextureInfo) == 48 && sizeof(RtxMediumInfo) == 16, "shading inspectors' layout");
 
 namespace rtx {
 static thread_local std::string g_last_error;
@@ -389,6 +397,54 @@ rtx_status rtx_flat_set_spheres(rtx_flat* f, const int32_t* ids, int64_t n, cons
   return st;
 }
 
+rtx_status rtx_flat_material_info(const rtx_flat* f, int32_t index, RtxMaterialInfo* o) {
+  if (!f || !o) { set_error("rtx_flat_material_info: NULL argument"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  if (index < 0 || (size_t)index >= s.materials.size()) {
+    set_error("rtx_flat_material_info: index is out of range (the scene has " + std::to_string(s.materials.size()) + " materials)");
+    return RTX_EINVAL;
+  }
+  const rt::FlatMaterial& m = s.materials[(size_t)index];
+  o->kind = m.kind; o->tex = m.tex;
+  for (int a = 0; a < 3; ++a) o->albedo[a] = m.albedo[a];
+  o->param = m.param;
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_texture_info(const rtx_flat* f, int32_t index, RtxTextureInfo* o) {
+  if (!f || !o) { set_error("rtx_flat_texture_info: NULL argument"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  if (index < 0 || (size_t)index >= s.textures.size()) {
+    set_error("rtx_flat_texture_info: index is out of range (the scene has " + std::to_string(s.textures.size()) + " textures)");
+    return RTX_EINVAL;
+  }
+  const rt::FlatTexture& t = s.textures[(size_t)index];
+  o->kind = t.kind; o->a = t.a; o->b = t.b; o->pad = 0;
+  for (int a = 0; a < 3; ++a) o->color[a] = t.color[a];
+  o->scale = t.scale;
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_medium_info(const rtx_flat* f, int32_t slot, RtxMediumInfo* o) {
+  if (!f || !o) { set_error("rtx_flat_medium_info: NULL argument"); return RTX_EINVAL; }
+  const FlatScene& s = f->scene;
+  if (slot < 0 || (size_t)slot >= s.top_level.size()) {
+    set_error("rtx_flat_medium_info: slot is out of range (the world list has " + std::to_string(s.top_level.size()) + " slots)");
+    return RTX_EINVAL;
+  }
+  const rt::FlatEntry& E = s.entries[(size_t)s.top_level[(size_t)slot]];
+  if (E.kind != rt::ENTRY_MEDIUM) { set_error("rtx_flat_medium_info: slot is not a ConstantMedium (rtx_flat_top_level_kind 4)"); return RTX_EINVAL; }
+  o->material = E.b; o->pad = 0;
+  o->neg_inv_density = E.f[0];
+  return RTX_OK;
+}
+
+rtx_status rtx_flat_set_shading(rtx_flat* f, const RtxShadingEdit* edits, int64_t n) {
+  std::string err;
+  if (!flat_set_shading("rtx_flat_set_shading", f ? &f->scene : nullptr, edits, n, &err)) { set_error(err); return RTX_EINVAL; }
+  return RTX_OK;
+}
+
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes) {
   if (!f) { set_error("rtx_flat_array: NULL flat"); return RTX_EINVAL; }
   const FlatScene& s = f->scene;
@@ -404,7 +460,7 @@ rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t by
 #define ARR(W, VEC) case W: p = s.VEC.data(); have = s.VEC.size() * sizeof(s.VEC[0]); break;
   switch (which) {
     ARR(0, entries) ARR(1, nodes) ARR(2, nodes32) ARR(3, motion32) ARR(5, top_level) ARR(6, member_local_box)
-    ARR(10, triangles) ARR(11, top_box32) ARR(12, triangle_id) ARR(13, spheres)
+    ARR(10, triangles) ARR(11, top_box32) ARR(12, triangle_id) ARR(13, spheres) ARR(15, materials) ARR(16, textures)
     default: set_error("rtx_flat_array: which names no host array"); return RTX_EINVAL;
   }
 #undef ARR

@@ -52,6 +52,9 @@ struct RtxSceneOps {
   rtx_status (*rebuild_instance_trees)(void* device_scene, const int32_t* trees, int32_t n, hipStream_t stream, RtxRebuildStats* out);
   // rtx_scene_instance_tree_cost (blocking)
   rtx_status (*instance_tree_cost)(void* device_scene, int32_t k, double* cost);
+  // rtx_scene_set_shading (shading_update.inc): n > 0 edits in host memory, already through the checks that need no scene; checks
+  // the rest against the scene's shadow, then enqueues
+  rtx_status (*set_shading)(void* device_scene, const RtxShadingEdit* edits, int64_t n, hipStream_t stream);
 };
 
 // A stable radix sort of (64-bit key, 32-bit value) pairs on `stream` (lbvh.hip, which already carries rocPRIM's sort: neither

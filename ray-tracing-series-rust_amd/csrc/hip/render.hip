@@ -32,6 +32,7 @@
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
 #include "../host/update_shadow.hpp"
+#include "../host/set_shading.hpp"
 #include "../host/wide_tree.hpp"
 #include "device_buffer.hpp"
 #include "f32_bridge.hpp"
@@ -182,6 +183,7 @@ struct SceneUpdate {
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
   DeviceBuffer<rt::XformOp64> d_slot_ops64;     // the f32 compilation only: the slots' ops in f64
   StagingBuffer staging;                        // the update records of one call
+  ShadingShadow shading;                        // host: what rtx_scene_set_shading checks and plans its edits against (shading_update.inc)
   // rtx_scene_rebuild_instance_trees (scene_rebuild.inc).  max_stack = member_stack + 1 + the deepest of tree_depth.
   int32_t member_stack = 0;                     // host: the members' own part of max_stack (their deepest BVH)
   std::vector<int32_t> tree_depth;              // host: per instance tree, as the trees now stand
@@ -343,6 +345,7 @@ static void plan_world_stacks(DeviceScene* ds);
 #ifndef RTX_F32_TU
 #include "mesh_update.inc"   // k_set_prims .. k_refresh_lights: new records for triangles / static spheres of a resident scene, BVHs refitted (f64 only)
 #endif
+#include "shading_update.inc" // k_set_shading: new colours, noise scales, metal / glass parameters and fog densities on a resident scene
 #include "cull_hooks.inc"    // k_cull_verdicts, k_walk_steps: test hooks of the f32 culling code (rtx_device_cull_verdicts / _walk_steps)
 
 // ------------------------------------------------------------------ launcher
@@ -1544,6 +1547,7 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
     free_device_scene(ds);
     return st;
   }
+  build_scene_shading(ds, fs);
   *out = ds;
   return RTX_OK;
 }
@@ -1584,6 +1588,9 @@ static const RtxSceneOps scene_ops = {
       return scene_rebuild_impl((DeviceScene*)ds, trees, n, stream, out);
     },
     [](void* ds, int32_t k, double* cost) { return scene_tree_cost_impl((DeviceScene*)ds, k, cost); },
+    [](void* ds, const RtxShadingEdit* edits, int64_t n, hipStream_t stream) {
+      return scene_set_shading_impl((DeviceScene*)ds, edits, n, stream);
+    },
 };
 
 }  // namespace rtx
@@ -1709,6 +1716,15 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
   const rtx_status st = check_set_transforms("rtx_scene_set_transforms", s, updates, n, &resolved);
   if (st != RTX_OK || n == 0) return st;
   return s->ops->set_transforms(s->device_scene, resolved.data(), n, (hipStream_t)hip_stream);
+}
+
+// ---- relighting (shading_update.inc).  What needs no scene is checked first -- the handle is not read before it has passed --
+// then the scene's own compilation checks the edits against its shadow of the upload, plans and enqueues.
+rtx_status rtx_scene_set_shading(rtx_scene* s, const RtxShadingEdit* edits, int64_t n, void* hip_stream) {
+  std::string err;
+  if (!check_shading_args("rtx_scene_set_shading", s, edits, n, &err)) { set_error(err); return RTX_EINVAL; }
+  if (n == 0) return RTX_OK;
+  return s->ops->set_shading(s->device_scene, edits, n, (hipStream_t)hip_stream);
 }
 
 // ---- deforming meshes and moving static spheres (mesh_update.inc): one ladder for the four entries.  What needs no scene

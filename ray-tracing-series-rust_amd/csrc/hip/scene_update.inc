@@ -260,6 +260,8 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 11: p = ds->view.top_box32; have = u.n_top * 6 * sizeof(float); break;
     case 13: p = ds->view.spheres; have = u.n_spheres * sizeof(rt::FlatSphere); break;
     case 14: p = ds->lights.lights; have = (size_t)ds->lights.n_lights * sizeof(rt::FlatLight); break;
+    case 15: p = ds->view.materials; have = u.n_materials * sizeof(rt::FlatMaterial); break;
+    case 16: p = ds->view.textures; have = u.n_textures * sizeof(rt::FlatTexture); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
     case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }
