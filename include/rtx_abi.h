@@ -254,7 +254,9 @@ int32_t rtx_shard_rows(const RtxConfig* cfg, const RtxShard* shard); /* number o
 /* Asynchronous on `hip_stream` (a hipStream_t, may be NULL = default stream); outputs are DEVICE
  * pointers sized for the shard (rows*w*3).  d_accum_rgb / d_rgb8 may each be NULL.  Scratch comes
  * from a per-scene workspace that grows on demand (the only call here that may allocate).
- * stats may be NULL; if non-NULL the call synchronises the stream to read timers. */
+ * stats may be NULL; if non-NULL the call synchronises the stream to read timers.
+ * One more host wait: on a scene whose k_trace_lds plan has time-aware boxes, the FIRST launch of that kernel after
+ * rtx_scene_set_moving_spheres* waits once for the update to finish (see there). */
 rtx_status rtx_render_device(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
                              const RtxShard* shard, double* d_accum_rgb, uint8_t* d_rgb8,
                              void* hip_stream, RtxRenderStats* stats);
@@ -618,13 +620,15 @@ rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int
  * int32, 0 without a wide tree), 9 the scene's max_stack as its binary walks are now launched with (one int32; a rebuild of
  * an instance tree changes it), 10 triangles, 11 top_box32 (6 floats per slot), 13 the static spheres (FlatSphere, 40 bytes
  * each in an f64 scene), 14 the light table of next-event estimation (FlatLight, 40 bytes each; 0 bytes without sampled
- * lights), 15 materials and 16 textures (FlatMaterial / FlatTexture: 48 bytes each in an f64 scene, 32 in an f32 scene).
+ * lights), 15 materials and 16 textures (FlatMaterial / FlatTexture: 48 bytes each in an f64 scene, 32 in an f32 scene),
+ * 17 the MovingSpheres (FlatMovingSphere, 80 bytes each in an f64 scene, 44 in an f32 scene).
  * bytes must be the array's size (elements as the scene's precision lays them out); RTX_EINVAL
  * naming the size otherwise. */
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes);
 /* The same for the host arrays of a flat scene, which adds 5: top_level, 6: member_local_box (6 doubles per member of an
  * instance tree, the box before the ops), 12: triangle_id (one int32 per flat triangle).  14 is the light table an upload
- * of the flat scene as it stands would build; 15 and 16 are the host's materials and textures (48 bytes each). */
+ * of the flat scene as it stands would build; 15 and 16 are the host's materials and textures (48 bytes each), 17 its MovingSpheres
+ * (80 bytes each). */
 rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t bytes);
 
 /* ---- instance trees: the quality of a tree as it stands, and a rebuild for the current pose ---------------------------------
@@ -769,6 +773,50 @@ rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, co
  * read-back: a value that is not finite gives that sphere and the boxes above it unspecified culling.  No index is derived
  * from a value, so nothing can leave an allocation. */
 rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream);
+
+/* ---- motion blur on a resident scene: new end centres and a radius for MovingSpheres (an extension) -------------------------
+ * A MovingSphere's c0 / c1 are its centre at time0 / time1 -- with the camera's shutter, the reference's motion blur.  An
+ * animation with blur gives every mover a new (c0, c1) per frame.  The flattener emits a MovingSphere once per handle, so a
+ * mover's ID is its index in the flat scene's moving-sphere array (rtx_flat_array 17: FlatMovingSphere, 80 bytes each).
+ *
+ * rtx_flat_moving_sphere_ids: the twin of rtx_flat_sphere_ids for MovingSpheres; every other kind is skipped. */
+int64_t rtx_flat_moving_sphere_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap);
+/* movers: n x 7 doubles, c0 xyz, c1 xyz, radius of mover ids[i]; time0, time1 and the material stay.  ids: a HOST array in all
+ * three entries, free for reuse on return.
+ *
+ * Meaning, as for rtx_*_set_spheres: the scene then answers every entry point bit for bit as the scene built from scratch with
+ * those values, with the same exemptions (a tie inside one BVH, the sign of a zero plane, a fresh build's other topology).
+ *
+ * What is written, and nothing else: c0, c1, radius of the record; of every BVH that holds an updated mover, refitted whole and
+ * bottom-up with its TOPOLOGY kept, the boxes over the BVH's own interval in nodes and nodes32 (and the 4-wide tree's planes on
+ * a resident scene that has one) and the time-aware boxes: for a BVH with time0 < time1 and no GravitySphere the planes and
+ * slopes derived from the unions at its two ends, else the static copy without slopes; on a resident scene the box, the
+ * "box holds for the mover's own interval" flag and its two times in the slot record of a plain mover in the world list.
+ *
+ * The one value-dependent fact of a launch plan follows: k_trace_lds's time-aware variant is instantiated by the axes along
+ * which the time-aware boxes have slopes (RTX_LDS_VARIANT_ONE_AXIS) and sized by them.  The refit records those axes on the
+ * device; on a scene with such a plan the FIRST render, cast or query that launches k_trace_lds after an update waits ON THE
+ * HOST, once, for the update to finish and plans the variant again, as an upload of the new values would (rtx_render_device
+ * is asynchronous but for this wait).
+ *
+ * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, an id out of
+ * range or named twice; host entries: a value that is not finite (the radius may be negative or zero, as for rtx_moving_sphere);
+ * device entry: a pointer that is not 8-byte aligned.  n = 0 is RTX_OK with nothing launched.  RTX_EUNSUPPORTED, the scene
+ * unchanged, checked before anything is enqueued: a resident f32 scene (update the flat scene and upload it again with
+ * rtx_scene_upload_f32; this is checked before the ids, which need the tables only an f64 scene keeps), and a touched BVH
+ * that also holds a GravitySphere: that centre is not linear in time and its box needs its height table.
+ * rtx_*_set_spheres and rtx_*_set_triangles still refuse a BVH that holds a mover. */
+rtx_status rtx_flat_set_moving_spheres(rtx_flat* f, const int32_t* ids, int64_t n, const double* movers);
+/* A resident f64 scene; movers is a HOST array, staged with one copy.  Asynchronous on hip_stream, as rtx_scene_set_spheres:
+ * k_set_prims, then per touched BVH k_refit_timed_bvh (and k_refit_wide), k_slot_boxes, and where a k_trace_lds plan hangs on
+ * the slopes one 4-byte copy to the host behind them.  One update of a scene at a time; ordering against work on other streams
+ * is the caller's; progressive handles made earlier hold the old values.  rtx_multi_* scenes are not covered. */
+rtx_status rtx_scene_set_moving_spheres(rtx_scene* s, const int32_t* ids, int64_t n, const double* movers, void* hip_stream);
+/* d_movers: a DEVICE pointer (8-byte aligned), e.g. the poses at shutter open and close computed by the caller's own kernel on
+ * hip_stream; it is read by work enqueued on hip_stream and must stay valid until that work is done.  Finiteness cannot be
+ * checked without a read-back: a value that is not finite gives that mover and the boxes above it unspecified culling.  No
+ * index is derived from a value, so nothing can leave an allocation. */
+rtx_status rtx_scene_set_moving_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_movers, void* hip_stream);
 
 /* ---- relighting and look development: new shading parameters -----------------------------------------------------------------
  * Editing colours, a noise scale, a metal, a glass's index or a fog's density of a flattened or a resident scene gives the

@@ -181,7 +181,7 @@ _XFORM_NAMES = ("translate", "rotate_y")
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
                 "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128),
                 "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4), "spheres": (13, 40, 24),
-                "lights": (14, 40, 40), "materials": (15, 48, 32), "textures": (16, 48, 32)}
+                "lights": (14, 40, 40), "materials": (15, 48, 32), "textures": (16, 48, 32), "moving_spheres": (17, 80, 44)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
@@ -309,6 +309,10 @@ ABI = {
     "rtx_flat_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
     "rtx_scene_set_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
     "rtx_scene_set_spheres_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
+    "rtx_flat_moving_sphere_ids": (C.c_int64, [_VP, _VP, _H, C.POINTER(C.c_int32), C.c_int64]),
+    "rtx_flat_set_moving_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
+    "rtx_scene_set_moving_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
+    "rtx_scene_set_moving_spheres_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
     "rtx_flat_material_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMaterialInfo)]),
     "rtx_flat_texture_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxTextureInfo)]),
     "rtx_flat_medium_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMediumInfo)]),
@@ -621,6 +625,19 @@ class Flat:
         ids, spheres = _prim_update(ids, spheres, *_SPHERE_VALUES)
         _check(lib.rtx_flat_set_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), spheres.ctypes.data_as(_D3)))
 
+    def moving_sphere_ids(self, builder, handle):
+        """The ids of the MovingSpheres below `handle` (a mover, a list, a BvhNode, a wrapper or medium around those) in list
+        order (rtx_flat_moving_sphere_ids) -> int32 array.  A mover's id is its index in Flat.array("moving_spheres"); every
+        other kind is skipped."""
+        return _prim_ids(lib.rtx_flat_moving_sphere_ids, self, builder, handle)
+
+    def set_moving_spheres(self, ids, movers):
+        """New end centres and a radius for the MovingSpheres `ids`, in place (rtx_flat_set_moving_spheres): the flat scene
+        becomes the one flattened from scratch with these values, its BVHs and their time-aware boxes refitted with their
+        topology kept.  movers: n x 7 doubles, c0 xyz, c1 xyz, radius of ids[i]; time0, time1 and the material stay."""
+        ids, movers = _prim_update(ids, movers, *_MOVER_VALUES)
+        _check(lib.rtx_flat_set_moving_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), movers.ctypes.data_as(_D3)))
+
     def set_shading(self, edits):
         """New shading parameters, in place (rtx_flat_set_shading): the flat scene becomes the one flattened from scratch when
         the builder calls are made with the new values.  edits: a list of ("solid_color", tex, (r, g, b)) | ("noise_scale", tex,
@@ -679,6 +696,7 @@ class Flat:
 
 _TRIANGLE_VALUES = (9, "vertices", "v0 v1 v2")        # width, name, each: what a set_* call holds per id
 _SPHERE_VALUES = (4, "spheres", "cx cy cz radius")
+_MOVER_VALUES = (7, "movers", "c0 xyz, c1 xyz, radius")
 
 
 def _prim_ids(fn, flat, builder, handle):
@@ -883,6 +901,19 @@ class Scene:
         `stream`).  ids: host integers either way.  Enqueued on `stream` as in set_transforms."""
         _scene_set_prims(self, lib.rtx_scene_set_spheres, lib.rtx_scene_set_spheres_device, ids, spheres, stream, *_SPHERE_VALUES)
 
+    def set_moving_spheres(self, ids, movers, stream=None):
+        """New end centres and a radius for the MovingSpheres `ids` of the RESIDENT f64 scene -- a frame of an animation with
+        motion blur: c0 / c1 are the poses at shutter open and close.  Every later call answers as on the scene built from
+        scratch with these values (its BVHs and time-aware boxes are refitted on the device, their topology kept).  movers:
+        n x 7 doubles c0 xyz, c1 xyz, radius as a numpy array (rtx_scene_set_moving_spheres, staged with one copy) or as a
+        torch float64 tensor on the GPU (rtx_scene_set_moving_spheres_device).  ids: host integers either way.  Enqueued on
+        `stream` as in set_transforms; the first k_trace_lds launch afterwards waits once on the host where that kernel's plan
+        hangs on the slopes (include/rtx_abi.h).  A tensor without a `stream` is taken on torch's current stream."""
+        if stream is None and hasattr(movers, "data_ptr") and getattr(movers, "is_cuda", False):
+            import torch
+            stream = torch.cuda.current_stream(movers.device)
+        _scene_set_prims(self, lib.rtx_scene_set_moving_spheres, lib.rtx_scene_set_moving_spheres_device, ids, movers, stream, *_MOVER_VALUES)
+
     def set_shading(self, edits, stream=None):
         """New shading parameters for the RESIDENT scene of either precision (rtx_scene_set_shading): every later call answers as
         on a scene flattened and uploaded from scratch with the new colours, scales, metal / glass parameters and densities
@@ -918,7 +949,7 @@ class Scene:
 
     def array(self, name):
         """A copy of one resident array as bytes, after everything enqueued (rtx_device_scene_array; a test hook): "entries",
-        "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32", "spheres", "lights" (the light table of
+        "nodes", "nodes32", "motion32", "world_desc", "triangles", "top_box32", "spheres", "moving_spheres", "lights" (the light table of
         next-event estimation; empty without sampled lights), "materials", "textures" or "nodes4" (the 4-wide tree; empty when
         the scene has none)."""
         return _scene_array(lambda out, n: lib.rtx_device_scene_array(self._p, SCENE_ARRAYS[name][0], out, n), self._flat, name, self.is_f32)

@@ -110,3 +110,50 @@ class StagingBuffer {
   DeviceBuffer<unsigned char> device_;
   hipEvent_t copied_ = nullptr;
 };
+
+// The one owner of a small read-back: a pinned host block of 32-bit words, and the event behind the copy INTO it.  fetch enqueues
+// the copy of n device words on `stream`; wait blocks the host until the latest fetch has landed and gives the words.  Same
+// rules as DeviceBuffer: not copyable, freed once, in the destructor.
+class ReadbackWords {
+ public:
+  ReadbackWords() = default;
+  ReadbackWords(const ReadbackWords&) = delete;
+  ReadbackWords& operator=(const ReadbackWords&) = delete;
+  ~ReadbackWords() {
+    if (host_) (void)hipHostFree(host_);
+    if (landed_) (void)hipEventDestroy(landed_);
+  }
+
+  bool pending() const { return pending_; }
+
+  hipError_t fetch(const unsigned int* d_words, size_t n, hipStream_t stream) {
+    hipError_t e = landed_ ? hipSuccess : hipEventCreateWithFlags(&landed_, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    if (n > count_) {
+      // (a copy still in flight targets the old block: let it land before the block goes)
+      if (pending_) e = hipEventSynchronize(landed_);
+      if (e == hipSuccess && host_) e = hipHostFree(host_);
+      host_ = nullptr;
+      count_ = 0;
+      if (e == hipSuccess) e = hipHostMalloc((void**)&host_, n * sizeof(unsigned int), hipHostMallocDefault);
+      if (e != hipSuccess) { host_ = nullptr; return e; }
+      count_ = n;
+    }
+    e = hipMemcpyAsync(host_, d_words, n * sizeof(unsigned int), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipEventRecord(landed_, stream);
+    if (e == hipSuccess) pending_ = true;
+    return e;
+  }
+  hipError_t wait(const unsigned int** words) {
+    const hipError_t e = pending_ ? hipEventSynchronize(landed_) : hipSuccess;
+    pending_ = false;
+    *words = host_;
+    return e;
+  }
+
+ private:
+  unsigned int* host_ = nullptr;
+  size_t count_ = 0;
+  hipEvent_t landed_ = nullptr;
+  bool pending_ = false;
+};

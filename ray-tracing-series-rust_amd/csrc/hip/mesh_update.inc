@@ -12,7 +12,15 @@
 //   d_local_box, then the instance tree above a touched member (k_member_local_boxes, k_refit_instance_tree of scene_update.inc)
 //   top_box32 / WorldDesc           a plain top-level slot of one updated triangle or sphere: both boxes and the record's "box is
 //                                   finite" flag (k_slot_boxes, with core/prim_box.hpp's rules)
-// and for spheres only:
+// for MovingSpheres (rtx_scene_set_moving_spheres*; DESIGN.md 8.7):
+//   moving_spheres                  c0 c1 radius of the record of a mover id; time0, time1, mat stay (k_set_prims)
+//   nodes / nodes32 / motion32      every BVH that holds an updated mover (k_refit_timed_bvh): the unions over the BVH's own interval
+//                                   and, where the BVH gets time-aware boxes, the planes and slopes from the unions at its two ends
+//                                   (scene_update.inc's refit_climb<true>, core/mover_box.hpp's rules); nodes4 as above
+//   WorldDesc                       a plain mover in the world list: its box, WD_TIME_BOX and the two times (k_slot_boxes)
+//   the slope mask                  one word per BVH, the axes its slopes run along: read back by launch_lds, which plans
+//                                   k_trace_lds's time-aware instantiation by it (render.hip: plan_lds_motion_axis)
+// and for static spheres only:
 //   WorldDesc                       the boundary sphere of a medium: the record's box and "box is finite" flag; a plain sphere
 //                                   slot before such a medium: the "same sphere as the medium behind me" flag (k_slot_boxes)
 //   the light table                 when an updated sphere is a sampled light: its area, and every light's cdf and pmf
@@ -31,6 +39,7 @@
 
 __device__ __forceinline__ void set_record(rt::FlatTriangle* t, const double* v) { rt::set_triangle_vertices(t, v); }
 __device__ __forceinline__ void set_record(rt::FlatSphere* s, const double* v) { rt::set_sphere_values(s, v); }
+__device__ __forceinline__ void set_record(rt::FlatMovingSphere* s, const double* v) { rt::set_moving_sphere_values(s, v); }
 
 // One thread per (flat record, the caller's W values for it): pairs[2 i] = flat index, pairs[2 i + 1] = index of the W-tuple in
 // `values`.
@@ -70,6 +79,37 @@ __global__ __launch_bounds__(256) void k_refit_bvh(BvhRefitArgs a) {
   for (int x = 0; x < 3; ++x) { lo[x] = b[x]; hi[x] = b[3 + x]; }
   const TreePiece t = {a.nodes, a.nodes32, a.motion32, a.node_parent, a.arrivals, a.node_base};
   refit_climb(t, a.leaves[3 * (size_t)l + 1], a.leaves[3 * (size_t)l + 2], lo, hi);
+}
+
+struct TimedRefitArgs {
+  BvhRefitArgs tree;                // motion32: NULL when this BVH gets time-aware boxes (no static copy is written), else as k_refit_bvh's
+  const rt::FlatMovingSphere* movers;
+  rt::FlatMotion32* time_boxes;     // the scene's motion32 when this BVH gets time-aware boxes, else NULL
+  double* scratch;                  // 24 doubles per node of this BVH (scene_update.inc: EndBoxes)
+  unsigned int* slope_mask;         // this BVH's word, zero at launch
+  double t0, t1;                    // the BVH's own interval
+};
+
+// k_refit_bvh for a BVH that holds MovingSpheres, whose values have just changed: one thread per leaf, every leaf.  The leaf's
+// union over [t0, t1] climbs into nodes / nodes32 as a static BVH's box does; where the BVH gets time-aware boxes the unions AT
+// t0 and AT t1 climb with it and become motion32 (scene_update.inc: refit_climb<true>).  A BVH that gets none -- an interval that
+// is not ordered, a scene without motion32 -- takes the plain climb, with the static copy where the scene has motion32.
+__global__ __launch_bounds__(256) void k_refit_timed_bvh(TimedRefitArgs a) {
+  const int l = (int)(blockIdx.x * 256u + threadIdx.x);
+  if (l >= a.tree.n_leaves) return;
+  const int32_t code = a.tree.leaves[3 * (size_t)l];
+  double b[6];
+  timed_leaf_box(code, a.tree.refs, a.tree.spheres, a.movers, a.tree.rects, a.tree.triangles, a.t0, a.t1, b);
+  double lo[3], hi[3];
+  for (int x = 0; x < 3; ++x) { lo[x] = b[x]; hi[x] = b[3 + x]; }
+  const TreePiece t = {a.tree.nodes, a.tree.nodes32, a.tree.motion32, a.tree.node_parent, a.tree.arrivals, a.tree.node_base};
+  const int32_t node = a.tree.leaves[3 * (size_t)l + 1], c = a.tree.leaves[3 * (size_t)l + 2];
+  if (!a.time_boxes) { refit_climb(t, node, c, lo, hi); return; }
+  EndBoxes e;
+  e.motion32 = a.time_boxes; e.scratch = a.scratch; e.slope_mask = a.slope_mask;
+  timed_leaf_box(code, a.tree.refs, a.tree.spheres, a.movers, a.tree.rects, a.tree.triangles, a.t0, a.t0, e.b[0]);
+  timed_leaf_box(code, a.tree.refs, a.tree.spheres, a.movers, a.tree.rects, a.tree.triangles, a.t1, a.t1, e.b[1]);
+  refit_climb<true>(t, node, c, lo, hi, &e);
 }
 
 // The f64 box the binary tree keeps for child code `code` below node i: the collapse (host/wide_tree.hpp) opens at most two
@@ -133,18 +173,32 @@ __global__ __launch_bounds__(256) void k_member_local_boxes(const int32_t* __res
 }
 
 // One thread per listed slot: slots[2 i] = the slot, slots[2 i + 1] = 0 a plain triangle or static sphere, 1 a medium bounded
-// by a sphere.  top_box32 (plain only) and the box, the WD_BOXED_PRIM and the WD_PAIR flag of the slot's WorldDesc record, as
+// by a sphere, 2 a plain MovingSphere (the record's box, WD_TIME_BOX and its two times by core/mover_box.hpp's rule, as
+// build_world_desc sets them: a box that is not finite clears the flag and the times; top_box32 of such a slot is unbounded and stays).  top_box32 (plain only) and the box, the WD_BOXED_PRIM and the WD_PAIR flag of the slot's WorldDesc record, as
 // the flattener and build_world_desc derive them; a triangle slot has no WD_SPHERE flag and so no pair rule.  A thread writes
 // its own slot's record only; of the next slot's it reads what no update changes (flags other than WD_BOXED_PRIM, g_a).
 __global__ __launch_bounds__(256) void k_slot_boxes(const int32_t* __restrict__ slots, int n, int n_top, const rt::FlatEntry* __restrict__ entries,
                                                    const int32_t* __restrict__ top_level, const rt::FlatSphere* __restrict__ spheres,
                                                    const rt::FlatRect* __restrict__ rects, const rt::FlatTriangle* __restrict__ triangles,
-                                                   float* __restrict__ top_box32, WorldDesc* __restrict__ desc) {
+                                                   const rt::FlatMovingSphere* __restrict__ movers, float* __restrict__ top_box32,
+                                                   WorldDesc* __restrict__ desc) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= n) return;
   const int32_t slot = slots[2 * (size_t)i];
-  const bool medium = slots[2 * (size_t)i + 1] != 0;
+  const bool medium = slots[2 * (size_t)i + 1] == 1;
   const rt::FlatEntry E = entries[top_level[slot]];
+  if (slots[2 * (size_t)i + 1] == 2) {
+    if (!desc) return;
+    const rt::FlatMovingSphere ms = movers[rt::primref_index((rt::PrimRef)E.a)];
+    float bx[6];
+    for (int x = 0; x < 6; ++x) bx[x] = top_box32[6 * (size_t)slot + x];  // what build_world_desc starts from
+    const bool finite = rt::mover_slot_box32(ms, bx);
+    for (int x = 0; x < 6; ++x) desc[slot].box[x] = bx[x];
+    desc[slot].flags = finite ? (desc[slot].flags | WD_TIME_BOX) : (desc[slot].flags & ~WD_TIME_BOX);
+    desc[slot].neg_inv_density = finite ? ms.time0 : rt::real(0);
+    desc[slot].aux = finite ? ms.time1 : rt::real(0);
+    return;
+  }
   const rt::PrimRef ref = (rt::PrimRef)(medium ? entries[E.a].a : E.a);
   float bx[6];
   bool finite = true;
@@ -227,6 +281,48 @@ static rtx_status launch_bvh_refits(DeviceScene* ds, const std::vector<int32_t>&
   return RTX_OK;
 }
 
+// The same for an update of MovingSpheres: k_refit_timed_bvh per touched BVH, with the climb's scratch and the slope words
+// (allocated here, by the first such update); then the words on their way to launch_lds where a k_trace_lds plan hangs on them.
+static rtx_status launch_timed_refits(DeviceScene* ds, const std::vector<int32_t>& bvhs, hipStream_t stream) {
+  MeshUpdate& mu = ds->mesh;
+  const size_t n_bvh_nodes = mu.shadow.node_parent.size() / 2;
+  bool slopes = false;
+  for (int32_t bi : bvhs) {
+    const BvhShadow& b = mu.shadow.bvhs[(size_t)bi];
+    if (b.n_leaves == 0 || b.n_nodes == 0) continue;  // a leaf code for a root: only its records changed
+    const bool time_boxes = b.time_boxes && ds->view.motion32;
+    if (time_boxes && !mu.d_end_boxes) HIP_TRY(mu.d_end_boxes.alloc(24 * n_bvh_nodes * sizeof(double)));
+    if (time_boxes && !mu.d_slope_mask) HIP_TRY(mu.d_slope_mask.upload(mu.slope_mask.data(), mu.slope_mask.size()));
+    TimedRefitArgs a;
+    a.tree.nodes = (rt::FlatNode*)ds->view.nodes; a.tree.nodes32 = (rt::FlatNode32*)ds->view.nodes32;
+    a.tree.motion32 = time_boxes ? nullptr : (rt::FlatMotion32*)ds->view.motion32;
+    a.tree.refs = ds->view.refs + b.first_ref;
+    a.tree.spheres = ds->view.spheres; a.tree.rects = ds->view.rects; a.tree.triangles = ds->view.triangles;
+    a.tree.leaves = mu.d_leaves + 3 * (size_t)b.leaf_first;
+    a.tree.node_parent = mu.d_node_parent + 2 * (size_t)b.node_first;
+    a.tree.arrivals = mu.d_arrivals + (size_t)b.node_first;
+    a.tree.n_leaves = b.n_leaves; a.tree.node_base = b.node_base;
+    a.movers = ds->view.moving_spheres;
+    a.time_boxes = time_boxes ? (rt::FlatMotion32*)ds->view.motion32 : nullptr;
+    a.scratch = time_boxes ? mu.d_end_boxes + 24 * (size_t)b.node_first : nullptr;
+    a.slope_mask = time_boxes ? mu.d_slope_mask + (size_t)bi : nullptr;
+    a.t0 = b.t0; a.t1 = b.t1;
+    HIP_TRY(hipMemsetAsync(a.tree.arrivals, 0, (size_t)b.n_nodes * sizeof(unsigned int), stream));
+    if (time_boxes) HIP_TRY(hipMemsetAsync(a.slope_mask, 0, sizeof(unsigned int), stream));
+    hipLaunchKernelGGL(k_refit_timed_bvh, dim3((unsigned)((b.n_leaves + 255) / 256)), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    slopes = slopes || time_boxes;
+    if (ds->wide.nodes4) {
+      hipLaunchKernelGGL(k_refit_wide, dim3((unsigned)((b.n_nodes + 255) / 256)), dim3(256), 0, stream, (const rt::FlatNode*)ds->view.nodes,
+                         (FlatNode4*)ds->wide.nodes4, b.node_base, b.n_nodes);
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  // a k_trace_lds plan is a world of ONE BVH: its word is the first (and only) one
+  if (slopes && ds->lds.motion_planned) HIP_TRY(mu.slope_readback.fetch(mu.d_slope_mask, 1, stream));
+  return RTX_OK;
+}
+
 // The local boxes of the touched members (d_members: index, entry per member, in the call's staging), then the instance trees
 // above them.  After the BVH refits on the same stream.
 static rtx_status launch_member_refits(DeviceScene* ds, const int32_t* d_members, size_t n_members, const std::vector<int32_t>& trees, hipStream_t stream) {
@@ -249,7 +345,7 @@ static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const
                                        bool host_values, hipStream_t stream) {
   MeshUpdate& mu = ds->mesh;
   const MeshShadow& sh = mu.shadow;
-  const bool tri = K.type == rt::PRIM_TRIANGLE;
+  const bool tri = K.type == rt::PRIM_TRIANGLE, mov = K.type == rt::PRIM_MOVING_SPHERE;
   std::string err;
   UpdatePlan plan;
   const rtx_status pst = plan_prim_update(K, who, sh, ids, n, &plan, &err);
@@ -259,7 +355,7 @@ static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const
   rtx_status st = upload_mesh_tables(ds);
   if (st != RTX_OK) return st;
   bool lights = false;  // a listed sphere is a sampled light
-  for (int64_t i = 0; !tri && i < n; ++i) lights = lights || ((size_t)ids[i] < mu.sphere_is_light.size() && mu.sphere_is_light[(size_t)ids[i]]);
+  for (int64_t i = 0; !tri && !mov && i < n; ++i) lights = lights || ((size_t)ids[i] < mu.sphere_is_light.size() && mu.sphere_is_light[(size_t)ids[i]]);
   if (lights && !mu.d_light_weight) HIP_TRY(mu.d_light_weight.alloc((size_t)ds->lights.n_lights * sizeof(double)));
   // staging layout: [values, width x 8 B each (host entry only)] [pairs] [members: index, entry] [slots: slot, kind]
   const size_t value_bytes = host_values ? (size_t)n * (size_t)K.width * sizeof(double) : 0;
@@ -283,14 +379,15 @@ static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const
   const int32_t* d_slots = d_members + 2 * n_members;
   const dim3 pair_grid((unsigned)((n_pairs + 255) / 256));
   if (tri) hipLaunchKernelGGL((k_set_prims<9, rt::FlatTriangle>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatTriangle*)ds->view.triangles);
+  else if (mov) hipLaunchKernelGGL((k_set_prims<7, rt::FlatMovingSphere>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatMovingSphere*)ds->view.moving_spheres);
   else hipLaunchKernelGGL((k_set_prims<4, rt::FlatSphere>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatSphere*)ds->view.spheres);
   HIP_TRY(hipGetLastError());
-  if ((st = launch_bvh_refits(ds, plan.bvhs, stream)) != RTX_OK) return st;
+  if ((st = mov ? launch_timed_refits(ds, plan.bvhs, stream) : launch_bvh_refits(ds, plan.bvhs, stream)) != RTX_OK) return st;
   if ((st = launch_member_refits(ds, d_members, n_members, plan.trees, stream)) != RTX_OK) return st;
   if (n_slots) {
     hipLaunchKernelGGL(k_slot_boxes, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, stream, d_slots, (int)n_slots, ds->view.n_top_level,
-                       ds->view.entries, ds->view.top_level, ds->view.spheres, ds->view.rects, ds->view.triangles, (float*)ds->view.top_box32,
-                       (WorldDesc*)ds->world.desc);
+                       ds->view.entries, ds->view.top_level, ds->view.spheres, ds->view.rects, ds->view.triangles, ds->view.moving_spheres,
+                       (float*)ds->view.top_box32, (WorldDesc*)ds->world.desc);
     HIP_TRY(hipGetLastError());
   }
   if (lights) {

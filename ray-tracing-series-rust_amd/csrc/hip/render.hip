@@ -28,6 +28,7 @@
 #include "../core/integrator.hpp"
 #include "../core/item_order.hpp"
 #include "../core/karras.hpp"
+#include "../core/mover_box.hpp"
 #include "../core/prim_box.hpp"
 #include "../host/flat_scene.hpp"
 #include "../host/light_table.hpp"
@@ -153,7 +154,11 @@ struct LdsPlan {
   LdsFit motion;
   int motion_axis = -1;           // 0 / 1 / 2: every slope of the time-aware boxes is zero except along this axis (-1: no such axis)
   double motion_t0 = 0.0, motion_t1 = 0.0;
-  bool mv_common = false;         // every MovingSphere of the scene has the same (time0, time1) = (mv_t0, mv_t1): one division per bounce
+  // the time-aware variant is planned: `motion` was fitted into lds_max bytes and is fitted again when the slopes change
+  // (plan_lds_motion_axis; rtx_scene_set_moving_spheres)
+  bool motion_planned = false;
+  uint32_t lds_max = 0;
+  bool mv_common = false;        // every MovingSphere of the scene has the same (time0, time1) = (mv_t0, mv_t1): one division per bounce
   double mv_t0 = 0.0, mv_t1 = 1.0;
 };
 
@@ -177,7 +182,7 @@ struct SceneUpdate {
   UpdateShadow shadow;              // host: the slots' chains, the instance trees and their parent tables
   std::vector<double> local_box;    // host: FlatScene::member_local_box (an update's new boxes are checked before anything is enqueued)
   size_t n_entries = 0, n_nodes = 0, n_motion = 0, n_desc = 0;  // element counts of the arrays an update writes (rtx_device_scene_array)
-  size_t n_triangles = 0, n_top = 0, n_spheres = 0;
+  size_t n_triangles = 0, n_top = 0, n_spheres = 0, n_moving_spheres = 0;
   DeviceBuffer<double> d_local_box;
   DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
@@ -212,6 +217,11 @@ struct MeshUpdate {
   bool local_box_stale = false;                  // SceneUpdate::local_box lags behind d_local_box (scene_update.inc reads it back)
   std::vector<char> sphere_is_light;             // host, per flat sphere: it is a sampled light (an update of it refreshes the light table)
   DeviceBuffer<double> d_light_weight;           // k_refresh_lights' pick weights, one per light; allocated by the first such update
+  // rtx_scene_set_moving_spheres (k_refit_timed_bvh); allocated by the first such update
+  std::vector<unsigned int> slope_mask;          // host, per BVH: the axes its time-aware boxes have a slope along, as uploaded
+  DeviceBuffer<unsigned int> d_slope_mask;       // the same words, kept current by the refits
+  DeviceBuffer<double> d_end_boxes;              // the climb's scratch: 24 doubles per BVH node (scene_update.inc: EndBoxes)
+  ReadbackWords slope_readback;                  // d_slope_mask on its way to launch_lds, which plans k_trace_lds's instantiation by it
 };
 #endif
 
@@ -770,6 +780,20 @@ static void fit_lds(LdsFit* f, bool want_ring, uint32_t lds_max) {
     }
 }
 
+// What k_trace_lds's time-aware variant takes from the VALUES of the time-aware boxes, the one value-dependent fact of a launch
+// plan.  slope_mask: the axes along which any record has a slope (core/mover_box.hpp: bit 0 x, 1 y, 2 z).  Slopes along y and
+// nowhere else select the instantiation whose node records carry no x / z slopes (the y-only one exists: Book-1 at HEAD); the
+// record size enters the LDS layout, so the variant is fitted again.  At upload (plan_lds) and at the first k_trace_lds launch
+// after rtx_scene_set_moving_spheres changed the boxes (launch_lds).
+static void plan_lds_motion_axis(LdsPlan* p, const TraceSwitches& sw, uint32_t slope_mask) {
+  const bool y_only = slope_mask == 2u && sw.motion_axis;
+  p->motion_axis = y_only ? 1 : -1;
+  p->motion.dims.node_dwords = y_only ? LDSK_MOTION1_NODE_DWORDS : LDSK_MOTION_NODE_DWORDS;
+  p->motion.ok = false;
+  p->motion.ring_cap = 0;
+  if (p->motion_planned && p->plain.ok) fit_lds(&p->motion, sw.ring != 0, p->lds_max);
+}
+
 // The plain and time-aware variants for a sphere world of one BVH.  The record dims chosen here must match the
 // instantiation launch_lds picks for the scene (UNI: trace_lds.inc).
 static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan& leaves) {
@@ -792,17 +816,6 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
   p.motion.levels = levels;
   p.motion.dims = p.plain.dims;
   p.motion.dims.node_dwords = LDSK_MOTION_NODE_DWORDS;
-  {
-    // slopes along one axis only?  (a scene whose spheres all move the same way; the y-only instantiation exists: Book-1 at HEAD)
-    bool moves[3] = {false, false, false};
-    for (const rt::FlatMotion32& m : fs.motion32)
-      for (int ch = 0; ch < 2; ++ch)
-        for (int a = 0; a < 3; ++a) moves[a] = moves[a] || m.dlo[ch][a] != 0.0f || m.dhi[ch][a] != 0.0f;
-    if (!fs.motion32.empty() && moves[1] && !moves[0] && !moves[2] && sw.motion_axis) {
-      p.motion_axis = 1;
-      p.motion.dims.node_dwords = LDSK_MOTION1_NODE_DWORDS;
-    }
-  }
   if (leaves.max_count <= 4 && max_end <= LDSK_MAX_SLOTS && sw.scene_lds != 0 && lds_max > 0) {
     const bool want_ring = sw.ring != 0;
     fit_lds(&p.plain, want_ring, (uint32_t)lds_max);
@@ -810,9 +823,12 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
     // the time-aware instantiation: the world's one BVH holds moving spheres and came with an interval
     if (p.plain.ok && !fs.motion32.empty() && (fs.features & rt::F_MOVING_SPHERE) && lds_motion_interval_ok((double)be.f[0], (double)be.f[1]) && sw.motion) {
       p.motion_t0 = (double)be.f[0]; p.motion_t1 = (double)be.f[1];
-      fit_lds(&p.motion, want_ring, (uint32_t)lds_max);
+      p.motion_planned = true;
+      p.lds_max = (uint32_t)lds_max;
     }
   }
+  // slopes along one axis only?  (a scene whose spheres all move the same way)  The record size and the fit follow.
+  plan_lds_motion_axis(&p, sw, rt::motion_slope_mask(fs.motion32.data(), fs.motion32.size()));
   if (p.plain.ok) {
     // the limit is a property of the function, not of this scene: raise it to the device maximum once, so that
     // scenes uploaded earlier (with other LDS sizes) keep launching
@@ -848,6 +864,15 @@ static rtx_status plan_lds(DeviceScene* ds, const FlatScene& fs, const LeafScan&
 
 // *variant: the instantiation launched, as RtxRenderStats.trace_variant reports it (lds_variant.inc).
 static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera* cam, int32_t* variant) {
+#ifndef RTX_F32_TU
+  if (ds->mesh.slope_readback.pending()) {
+    // rtx_scene_set_moving_spheres* refitted the time-aware boxes since the last launch: ONE host wait for the axes their slopes
+    // now run along (the scene's one BVH: plan_lds), and the variant is planned by them as at upload
+    const unsigned int* words = nullptr;
+    HIP_TRY(ds->mesh.slope_readback.wait(&words));
+    plan_lds_motion_axis(&ds->lds, ds->sw, words[0]);
+  }
+#endif
   const LdsPlan& p = ds->lds;
   // time-aware boxes when the scene has them and every ray's time lies inside the BVH's interval (camera.rs:69: [time1, time2))
   *variant = lds_trace_variant(p.motion.ok, p.motion_t0, p.motion_t1, (double)cam->time1, (double)cam->time2, p.motion_axis, p.mv_common);
@@ -1737,16 +1762,21 @@ static rtx_status scene_set_prims_any(const PrimKind& K, const char* who, rtx_sc
   if (!check_prim_args(K, who, s, ids, n, values, &err)) { set_error(err); return RTX_EINVAL; }
   if (!host_values && ((uintptr_t)values & 7)) { set_error(std::string(who) + ": " + K.d_arg + " is not 8-byte aligned"); return RTX_EINVAL; }
   if (n == 0) return RTX_OK;
+  const bool mov = K.type == rt::PRIM_MOVING_SPHERE;
+  // (the movers' entries check every RTX_EINVAL that needs no shadow before the first RTX_EUNSUPPORTED; the ids need the shadow,
+  // which only an f64 scene keeps)
+  if (mov && host_values && !check_prims_finite(K, who, values, n, &err)) { set_error(err); return RTX_EINVAL; }
   if (s->f32) {
     set_error(std::string(who) + ": needs an f64 scene (rtx_scene_upload): an f32 scene does not hold the f64 " +
               (K.type == rt::PRIM_TRIANGLE
                    ? "vertices of the untouched triangles in touched leaves. Update the flat scene with rtx_flat_set_triangles"
-                   : "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres") +
+                   : mov ? "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_moving_spheres"
+                         : "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres") +
               " and upload it again with rtx_scene_upload_f32");
     return RTX_EUNSUPPORTED;
   }
   if (!check_prim_ids(K, who, scene_device(s)->mesh.shadow, ids, n, &err)) { set_error(err); return RTX_EINVAL; }
-  if (host_values && !check_prims_finite(K, who, values, n, &err)) { set_error(err); return RTX_EINVAL; }
+  if (!mov && host_values && !check_prims_finite(K, who, values, n, &err)) { set_error(err); return RTX_EINVAL; }
   return scene_set_prims_impl(scene_device(s), K, who, ids, n, values, host_values, (hipStream_t)hip_stream);
 }
 rtx_status rtx_scene_set_triangles(rtx_scene* s, const int32_t* ids, int64_t n, const double* vertices, void* hip_stream) {
@@ -1760,6 +1790,12 @@ rtx_status rtx_scene_set_spheres(rtx_scene* s, const int32_t* ids, int64_t n, co
 }
 rtx_status rtx_scene_set_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_spheres, void* hip_stream) {
   return scene_set_prims_any(KIND_SPHERE, "rtx_scene_set_spheres_device", s, ids, n, d_spheres, false, hip_stream);
+}
+rtx_status rtx_scene_set_moving_spheres(rtx_scene* s, const int32_t* ids, int64_t n, const double* movers, void* hip_stream) {
+  return scene_set_prims_any(KIND_MOVING_SPHERE, "rtx_scene_set_moving_spheres", s, ids, n, movers, true, hip_stream);
+}
+rtx_status rtx_scene_set_moving_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_movers, void* hip_stream) {
+  return scene_set_prims_any(KIND_MOVING_SPHERE, "rtx_scene_set_moving_spheres_device", s, ids, n, d_movers, false, hip_stream);
 }
 
 // ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands

@@ -10,7 +10,7 @@
 // split axes and every other array stay as uploaded, and no existing kernel changes.
 //
 // What the other updates of a resident scene share lives here too, once: refit_climb (the bottom-up climb of this refit and of
-// mesh_update.inc's k_refit_bvh, with the one statement of its cross-workgroup visibility), store_child_planes32 (the narrowed
+// mesh_update.inc's k_refit_bvh and k_refit_timed_bvh, with the one statement of its cross-workgroup visibility), store_child_planes32 (the narrowed
 // planes of a child; also scene_rebuild.inc's k_rebuild_emit) and, on the host side, check_scene_device.  A member's world box
 // is core/member_box.hpp's member_world_box; the pinned staging of a call is device_buffer.hpp's StagingBuffer.
 //
@@ -98,15 +98,30 @@ struct TreePiece {
   int32_t node_base;
 };
 
+// What a climber of a BVH with time-aware boxes carries beside (lo, hi) (mesh_update.inc: k_refit_timed_bvh; TIMED below): the
+// unions of its subtree AT the BVH's time0 and AT its time1, in f64 -- FlatMotion32 keeps only their narrowed planes and slopes,
+// so a parent could not be derived from its children's records.
+struct EndBoxes {
+  double b[2][6];              // [at time0, at time1][lo xyz, hi xyz]
+  rt::FlatMotion32* motion32;  // the scene's, not NULL (TreePiece::motion32 is NULL for such a climb: no static copy is written)
+  double* scratch;             // 24 doubles per node of the piece, by node - node_base: [end][child][lo xyz, hi xyz]
+  unsigned int* slope_mask;    // this BVH's word: the OR of core/mover_box.hpp's axis bits over every slope written
+};
+
 // THE bottom-up climb of every refit.  A thread comes with the box (lo, hi) of child c of `node`: it writes the box where the
 // node keeps it and arrives at the node.  Of the two threads that reach a node the first leaves; the second unites the node's
 // two child boxes and carries the union to the node's place in ITS parent, up to the root.  Unions are exact min / max, so the
-// result does not depend on who arrives first.
+// result does not depend on who arrives first.  TIMED: the two end boxes travel the same way; at every node the climber writes
+// child c's time-aware planes from them (core/mover_box.hpp: motion_child_planes) and parks them in the scratch for its sibling.
 // Visibility across workgroups is lbvh.hip's k_refit recipe (MI355X_MICROARCH.md, inter-workgroup visibility: a CU's L1 is
 // never refreshed by another CU's stores, and the XCDs' L2s are not coherent): agent-scope relaxed stores of the FlatNode
-// planes, which a sibling's climber on another CU reads; __threadfence; the agent-scope atomic arrival; __threadfence;
-// agent-scope relaxed loads of the sibling's planes -- a plain load could be served stale from this CU's L1.
-__device__ __forceinline__ void refit_climb(const TreePiece& t, int32_t node, int32_t c, rt::real* lo, rt::real* hi) {
+// planes -- and, TIMED, of the end boxes in the scratch -- which a sibling's climber on another CU reads; __threadfence; the
+// agent-scope atomic arrival; __threadfence; agent-scope relaxed loads of the sibling's planes and end boxes -- a plain load
+// could be served stale from this CU's L1.  (nodes32 and motion32 are written with plain stores: nobody reads them in the
+// launch.  The slope mask is an agent-scope atomic OR that only the host reads, after the kernel.)
+template <bool TIMED = false>
+__device__ __forceinline__ void refit_climb(const TreePiece& t, int32_t node, int32_t c, rt::real* lo, rt::real* hi, EndBoxes* e = nullptr) {
+  unsigned int moves = 0u;
   for (;;) {
     rt::FlatNode* nd = &t.nodes[node];
     for (int x = 0; x < 3; ++x) {
@@ -115,16 +130,37 @@ __device__ __forceinline__ void refit_climb(const TreePiece& t, int32_t node, in
       store_child_planes32(t.nodes32, t.motion32, node, c, x, lo[x], hi[x]);
     }
     const int32_t rel = node - t.node_base;
+    if constexpr (TIMED) {
+      rt::FlatMotion32* m = &e->motion32[node];
+      moves |= rt::motion_child_planes(e->b[0], e->b[1], m->lo0[c], m->dlo[c], m->hi0[c], m->dhi[c]);
+      double* mine = e->scratch + 24 * (size_t)rel + 6 * c;
+      for (int end = 0; end < 2; ++end)
+        for (int k = 0; k < 6; ++k) __hip_atomic_store(&mine[12 * end + k], e->b[end][k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     const int32_t parent = t.node_parent[2 * (size_t)rel], pc = t.node_parent[2 * (size_t)rel + 1];
-    if (parent < 0) return;  // the root: its two child boxes are the whole tree
+    auto leave = [&] {  // (a climber ORs the axes of all the slopes it wrote, once)
+      if constexpr (TIMED)
+        if (moves) (void)__hip_atomic_fetch_or(e->slope_mask, moves, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    if (parent < 0) { leave(); return; }  // the root: its two child boxes are the whole tree
     __threadfence();
-    if (atomicAdd(&t.arrivals[rel], 1u) == 0u) return;  // first of the two: the sibling's climber finishes the node
+    if (atomicAdd(&t.arrivals[rel], 1u) == 0u) { leave(); return; }  // first of the two: the sibling's climber finishes the node
     __threadfence();
     for (int x = 0; x < 3; ++x) {
       const rt::real slo = __hip_atomic_load(&nd->bmin[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       const rt::real shi = __hip_atomic_load(&nd->bmax[1 - c][x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       lo[x] = rt::rt_fmin(lo[x], slo);
       hi[x] = rt::rt_fmax(hi[x], shi);
+    }
+    if constexpr (TIMED) {
+      const double* theirs = e->scratch + 24 * (size_t)rel + 6 * (1 - c);
+      for (int end = 0; end < 2; ++end)
+        for (int x = 0; x < 3; ++x) {
+          const double slo = __hip_atomic_load(&theirs[12 * end + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const double shi = __hip_atomic_load(&theirs[12 * end + 3 + x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          e->b[end][x] = rt::rt_fmin(e->b[end][x], slo);
+          e->b[end][3 + x] = rt::rt_fmax(e->b[end][3 + x], shi);
+        }
     }
     node = parent;
     c = pc;
@@ -153,8 +189,16 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   u.n_entries = fs.entries.size(); u.n_nodes = fs.nodes.size(); u.n_motion = fs.motion32.size();
   u.n_desc = fs.top_level.size();
   u.n_triangles = fs.triangles.size(); u.n_top = fs.top_box32.size() / 6; u.n_spheres = fs.spheres.size();
+  u.n_moving_spheres = fs.moving_spheres.size();
 #ifndef RTX_F32_TU
   ds->mesh.shadow = build_mesh_shadow(fs, u.shadow);  // rtx_scene_set_triangles (mesh_update.inc); its tables go up with the first update
+  // per BVH, the axes along which its time-aware boxes have a slope as uploaded: what k_refit_timed_bvh keeps current from then on
+  ds->mesh.slope_mask.assign(ds->mesh.shadow.bvhs.size(), 0u);
+  if (ds->mesh.shadow.broken.empty() && !fs.motion32.empty())
+    for (size_t b = 0; b < ds->mesh.shadow.bvhs.size(); ++b) {
+      const BvhShadow& B = ds->mesh.shadow.bvhs[b];
+      ds->mesh.slope_mask[b] = rt::motion_slope_mask(fs.motion32.data() + B.node_base, (size_t)B.n_nodes);
+    }
 #endif
   if (fs.features & rt::F_INSTANCE)
     for (const rt::FlatEntry& e : fs.entries) u.n_desc += e.kind == rt::ENTRY_INSTANCE ? 1 : 0;
@@ -262,6 +306,7 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 14: p = ds->lights.lights; have = (size_t)ds->lights.n_lights * sizeof(rt::FlatLight); break;
     case 15: p = ds->view.materials; have = u.n_materials * sizeof(rt::FlatMaterial); break;
     case 16: p = ds->view.textures; have = u.n_textures * sizeof(rt::FlatTexture); break;
+    case 17: p = ds->view.moving_spheres; have = u.n_moving_spheres * sizeof(rt::FlatMovingSphere); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
     case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }

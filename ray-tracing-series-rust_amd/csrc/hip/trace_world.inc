@@ -69,18 +69,9 @@ static std::vector<WorldDesc> build_world_desc(const FlatScene& fs) {
       if (finite) d.flags |= WD_BOXED_PRIM;
     }
     if (E->kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)E->a) == rt::PRIM_MOVING_SPHERE) {
-      // centre(t) is linear in t (hit.rs:275-278), so the boxes at time0 and time1 bound every time between them
+      // (core/mover_box.hpp: mover_slot_box32, the rule rtx_scene_set_moving_spheres shares)
       const rt::FlatMovingSphere& ms = fs.moving_spheres[rt::primref_index((rt::PrimRef)E->a)];
-      const double r = std::fabs((double)ms.radius);
-      bool finite = ms.time0 < ms.time1;
-      for (int a = 0; a < 3 && finite; ++a) {
-        const double mn = std::fmin((double)ms.c0[a], (double)ms.c1[a]) - r, mx = std::fmax((double)ms.c0[a], (double)ms.c1[a]) + r;
-        float lo = std::nextafterf((float)mn, -INFINITY), hi = std::nextafterf((float)mx, INFINITY);
-        lo = std::nextafterf(lo, -INFINITY); hi = std::nextafterf(hi, INFINITY);  // (float) rounds to nearest: two steps out cover it and the f64 sum
-        d.box[a] = lo; d.box[3 + a] = hi;
-        finite = std::isfinite(lo) && std::isfinite(hi);
-      }
-      if (finite) { d.flags |= WD_TIME_BOX; d.neg_inv_density = ms.time0; d.aux = ms.time1; }
+      if (rt::mover_slot_box32(ms, d.box)) { d.flags |= WD_TIME_BOX; d.neg_inv_density = ms.time0; d.aux = ms.time1; }
     }
     if (!(d.flags & WD_XFORM) && G->kind == rt::ENTRY_PRIM && rt::primref_type((rt::PrimRef)G->a) == rt::PRIM_SPHERE) {
       d.flags |= WD_SPHERE;

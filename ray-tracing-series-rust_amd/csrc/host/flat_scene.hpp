@@ -51,6 +51,9 @@ struct FlatScene {
   // once per handle and is neither permuted nor copied.  Per graph hittable at the time of the flatten: that index, -1 for
   // anything else (rtx_flat_sphere_ids).  Last, so that nothing that reads this struct by its layout moves.
   std::vector<int32_t> handle_sphere_id;
+  // The same for what rtx_*_set_moving_spheres names a MovingSphere by: its index in `moving_spheres`, -1 for anything else
+  // (rtx_flat_moving_sphere_ids).  Appended behind the last, for the same reason.
+  std::vector<int32_t> handle_moving_sphere_id;
 
   // pointers into the vectors above (host memory)
   rt::SceneView view() const {

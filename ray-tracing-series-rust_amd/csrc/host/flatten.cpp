@@ -53,6 +53,7 @@ struct Flattener {
       : g(gg), out(o), opt(op), prim_of(gg.hittables.size(), -1), bvh_entry_of(gg.hittables.size(), -1) {
     out.handle_triangle_id.assign(gg.hittables.size(), -1);
     out.handle_sphere_id.assign(gg.hittables.size(), -1);
+    out.handle_moving_sphere_id.assign(gg.hittables.size(), -1);
   }
 
   bool fail(const std::string& m) { if (err.empty()) err = m; return false; }
@@ -88,6 +89,8 @@ struct Flattener {
         for (int i = 0; i < 3; ++i) { s.c0[i] = o.f[i]; s.c1[i] = o.f[3 + i]; }
         s.time0 = o.f[6]; s.time1 = o.f[7]; s.radius = o.f[8]; s.mat = o.mat; s.pad = 0;
         out.moving_spheres.push_back(s);
+        // its id: its index in `moving_spheres` -- emitted once per handle, like a static sphere
+        out.handle_moving_sphere_id[(size_t)h] = (int32_t)out.moving_spheres.size() - 1;
         ref = rt::make_primref(rt::PRIM_MOVING_SPHERE, (uint32_t)out.moving_spheres.size() - 1);
         break;
       }

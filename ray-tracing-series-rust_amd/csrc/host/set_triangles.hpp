@@ -12,6 +12,11 @@
 // may choose another topology, which is culling only.  A flat scene keeps no light table and no slot records: both are derived
 // from these arrays when asked for (host/light_table.hpp) or at upload (hip/trace_world.inc).
 //
+// rtx_flat_set_moving_spheres (KIND_MOVING_SPHERE: c0 xyz, c1 xyz, radius; time0, time1, mat stay) runs the same path; what
+// differs is the refit: a BVH that holds a mover keeps the unions over its own interval in `nodes` and, where the flattener gives
+// it time-aware boxes, planes and slopes in `motion32` derived from the unions at the interval's two ends (refit_timed_bvh,
+// core/mover_box.hpp).  Only a BVH that also holds a GravitySphere is refused there.
+//
 // A triangle's id is the ordinal of its first emission (FlatScene::triangle_id: a BVH stores copies in leaf order).  A sphere's
 // id is its index in FlatScene::spheres: the flattener emits a static sphere once per handle and neither moves nor copies it.
 // No index is ever derived from a value: every index an update uses comes from the caller's ids (checked against the shadow)
@@ -22,6 +27,7 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include "../core/mover_box.hpp"
 #include "../core/prim_box.hpp"
 #include "set_transforms.hpp"
 
@@ -33,7 +39,13 @@ struct BvhShadow {
   int32_t node_base, n_nodes;   // its nodes are nodes[node_base .. node_base + n_nodes): a builder appends a tree in one piece
   int32_t node_first;           // index of its first node in the per-node tables (MeshShadow::node_parent, the arrival counters)
   int32_t leaf_first, n_leaves; // its leaves in MeshShadow::leaves
-  int32_t timed;                // holds a MovingSphere or GravitySphere: its boxes depend on a time interval, no refit
+  int32_t timed;                // holds a MovingSphere or GravitySphere: its boxes depend on a time interval, no refit by
+                                // rtx_*_set_triangles / _set_spheres
+  // rtx_*_set_moving_spheres: it holds a MovingSphere; it holds a GravitySphere (refused: that centre is not linear in time);
+  // it gets time-aware boxes -- the flattener's condition (flatten.cpp: build_motion_boxes): a root that is a node, time0 < time1,
+  // a mover, no gravity sphere
+  int32_t has_mover, has_gravity, time_boxes;
+  double t0, t1;                // its own interval (FlatEntry::f)
 };
 struct MemberGeom {
   int32_t slot, geom, tree;     // a member of an instance tree: its slot, its PRIM / GROUP / BVH entry, its tree
@@ -54,12 +66,15 @@ struct MeshShadow {
   // a plain sphere slot whose next slot is such a medium, that medium's PRIM entry (the slot record says whether both hold the
   // same sphere), else -1.  A plain triangle slot is (slot, entry, 0, -1).
   std::vector<int32_t> slot_box;
+  // a moving sphere's id is its flat index too (the flattener emits a mover once per handle)
+  std::vector<int32_t> mov_first, mov_entry;     // flat moving sphere -> the PRIM / GROUP / BVH entries that refer to it
+  std::vector<int32_t> mover_slot;               // 2 per plain top-level slot whose record is one mover: the slot, its PRIM entry
   std::string broken;                            // not empty: the arrays are not what the flattener emits; the message says how
 };
 
-// A kind of static primitive an update can name.  Data only; code that differs asks `type`.
+// A kind of primitive an update can name.  Data only; code that differs asks `type`.
 struct PrimKind {
-  uint32_t type;             // rt::PRIM_TRIANGLE / rt::PRIM_SPHERE
+  uint32_t type;             // rt::PRIM_TRIANGLE / rt::PRIM_SPHERE / rt::PRIM_MOVING_SPHERE
   int width;                 // doubles per record of the caller's values
   const char* noun;          // in messages
   const char* count_phrase;  // "the scene has N ..."
@@ -67,6 +82,7 @@ struct PrimKind {
 };
 constexpr PrimKind KIND_TRIANGLE = {rt::PRIM_TRIANGLE, 9, "triangle", "triangle ids", "vertices", "d_vertices"};
 constexpr PrimKind KIND_SPHERE = {rt::PRIM_SPHERE, 4, "sphere", "static spheres", "spheres", "d_spheres"};
+constexpr PrimKind KIND_MOVING_SPHERE = {rt::PRIM_MOVING_SPHERE, 7, "moving sphere", "moving spheres", "movers", "d_movers"};
 
 // One update, resolved against the shadow: what to write and what to refit.
 struct UpdatePlan {
@@ -74,7 +90,7 @@ struct UpdatePlan {
   std::vector<int32_t> bvhs;     // touched BVHs (indices in MeshShadow::bvhs), ascending
   std::vector<int32_t> members;  // touched members (indices in MeshShadow::members), ascending
   std::vector<int32_t> trees;    // instance trees that hold one, ascending
-  std::vector<int32_t> slots;    // 2 per slot whose f32 box is derived again: the slot, 0 plain / 1 medium boundary; ascending
+  std::vector<int32_t> slots;    // 2 per slot whose f32 box is derived again: the slot, 0 plain / 1 medium boundary / 2 a plain mover; ascending
 };
 
 inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us) {
@@ -108,11 +124,12 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     return false;
   };
   // (the same two passes give flat sphere -> entries)
-  const size_t n_sph = fs.spheres.size();
+  const size_t n_sph = fs.spheres.size(), n_mov = fs.moving_spheres.size();
   sh.tri_first.assign(n_tri + 1, 0);
   sh.sph_first.assign(n_sph + 1, 0);
+  sh.mov_first.assign(n_mov + 1, 0);
   for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int32_t> at, sph_at;
+    std::vector<int32_t> at, sph_at, mov_at;
     if (pass == 1) {
       for (size_t t = 0; t < n_tri; ++t) sh.tri_first[t + 1] += sh.tri_first[t];
       sh.tri_entry.resize((size_t)sh.tri_first[n_tri]);
@@ -120,6 +137,9 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
       for (size_t t = 0; t < n_sph; ++t) sh.sph_first[t + 1] += sh.sph_first[t];
       sh.sph_entry.resize((size_t)sh.sph_first[n_sph]);
       sph_at.assign(sh.sph_first.begin(), sh.sph_first.end() - 1);
+      for (size_t t = 0; t < n_mov; ++t) sh.mov_first[t + 1] += sh.mov_first[t];
+      sh.mov_entry.resize((size_t)sh.mov_first[n_mov]);
+      mov_at.assign(sh.mov_first.begin(), sh.mov_first.end() - 1);
     }
     for (size_t k = 0; k < n_ent; ++k) {
       const rt::FlatEntry& e = fs.entries[k];
@@ -129,6 +149,12 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
           if (t >= n_sph) return false;
           if (pass == 0) sh.sph_first[(size_t)t + 1]++;
           else sh.sph_entry[(size_t)sph_at[t]++] = (int32_t)k;
+          return true;
+        }
+        if (ty == rt::PRIM_MOVING_SPHERE) {
+          if (t >= n_mov) return false;
+          if (pass == 0) sh.mov_first[(size_t)t + 1]++;
+          else sh.mov_entry[(size_t)mov_at[t]++] = (int32_t)k;
           return true;
         }
         if (ty != rt::PRIM_TRIANGLE) return true;
@@ -163,11 +189,15 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     b.entry = (int32_t)k; b.root = e.a; b.first_ref = e.b; b.n_refs = e.c;
     b.node_first = (int32_t)(sh.node_parent.size() / 2);
     b.leaf_first = (int32_t)(sh.leaves.size() / 3);
-    b.node_base = 0; b.n_nodes = 0; b.timed = 0;
+    b.node_base = 0; b.n_nodes = 0; b.timed = 0; b.has_mover = 0; b.has_gravity = 0;
+    b.t0 = (double)e.f[0]; b.t1 = (double)e.f[1];
     for (int32_t i = 0; i < e.c; ++i) {
       const uint32_t ty = rt::primref_type(fs.refs[(size_t)e.b + (size_t)i]);
       if (ty == rt::PRIM_MOVING_SPHERE || ty == rt::PRIM_GRAVITY_SPHERE) b.timed = 1;
+      if (ty == rt::PRIM_MOVING_SPHERE) b.has_mover = 1;
+      if (ty == rt::PRIM_GRAVITY_SPHERE) b.has_gravity = 1;
     }
+    b.time_boxes = (e.a >= 0 && b.t0 < b.t1 && b.has_mover && !b.has_gravity) ? 1 : 0;
     auto leaf_ok = [&](int32_t code) { return (int64_t)rt::leaf_first(code) + (int64_t)rt::leaf_count(code) <= (int64_t)e.c; };
     if (rt::node_child_is_leaf(e.a)) {
       if (!leaf_ok(e.a)) return broken("a BVH's leaf names references outside its run");
@@ -242,7 +272,9 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     if (prim_of(x, rt::PRIM_TRIANGLE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, -1});
     else if (prim_of(x, rt::PRIM_SPHERE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, medium_sphere(k + 1)});
     else if (m >= 0) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, m, 1, -1});
+    if (prim_of(x, rt::PRIM_MOVING_SPHERE)) sh.mover_slot.insert(sh.mover_slot.end(), {(int32_t)k, x});
   }
+  if (!fs.motion32.empty() && fs.motion32.size() != n_node) return broken("motion32 does not hold one record per node");
   return sh;
 }
 
@@ -258,7 +290,8 @@ inline bool check_prim_args(const PrimKind& K, const char* who, const void* scen
 // ids[0 .. n), n > 0, against the scene's shadow.
 inline bool check_prim_ids(const PrimKind& K, const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n, std::string* err) {
   if (!sh.broken.empty()) { *err = std::string(who) + ": " + sh.broken; return false; }
-  const int64_t n_ids = K.type == rt::PRIM_TRIANGLE ? (int64_t)sh.n_ids : (int64_t)sh.sph_first.size() - 1;
+  const int64_t n_ids = K.type == rt::PRIM_TRIANGLE ? (int64_t)sh.n_ids
+                        : K.type == rt::PRIM_SPHERE ? (int64_t)sh.sph_first.size() - 1 : (int64_t)sh.mov_first.size() - 1;
   for (int64_t i = 0; i < n; ++i)
     if (ids[i] < 0 || ids[i] >= n_ids) {
       *err = std::string(who) + ": ids[" + std::to_string(i) + "] is out of range (the scene has " + std::to_string(n_ids) + " " + K.count_phrase + ")";
@@ -283,12 +316,19 @@ inline bool check_prims_finite(const PrimKind& K, const char* who, const double*
 }
 
 // From the touched entries (one flag per entry) to the BVHs to refit, the members whose local box changes and the instance
-// trees above them.  what: the kind's noun, for the message.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere.
+// trees above them.  what: the kind's noun, for the message.  RTX_EUNSUPPORTED when a touched BVH holds a Moving- or GravitySphere;
+// movers (an update OF MovingSpheres, which refits the time-aware boxes too): only when it holds a GravitySphere.
 inline rtx_status plan_touched_entries(const char* who, const char* what, const MeshShadow& sh, const std::vector<char>& touched,
-                                       std::vector<int32_t>* bvhs, std::vector<int32_t>* members, std::vector<int32_t>* trees, std::string* err) {
+                                       std::vector<int32_t>* bvhs, std::vector<int32_t>* members, std::vector<int32_t>* trees, std::string* err,
+                                       bool movers = false) {
   for (size_t b = 0; b < sh.bvhs.size(); ++b) {
     if (!touched[(size_t)sh.bvhs[b].entry]) continue;
-    if (sh.bvhs[b].timed) {
+    if (movers && sh.bvhs[b].has_gravity) {
+      *err = std::string(who) + ": ids name a " + what + " of a BVH that also holds a GravitySphere (entry " + std::to_string(sh.bvhs[b].entry) +
+             "): a GravitySphere's centre is not linear in time and its box needs its height table, which a refit does not read. Flatten the scene anew";
+      return RTX_EUNSUPPORTED;
+    }
+    if (!movers && sh.bvhs[b].timed) {
       *err = std::string(who) + ": ids name a " + what + " of a BVH that holds a MovingSphere or GravitySphere (entry " + std::to_string(sh.bvhs[b].entry) +
              "): its time-aware boxes would have to be derived again. Flatten the scene anew";
       return RTX_EUNSUPPORTED;
@@ -318,15 +358,27 @@ inline rtx_status plan_prim_update(const PrimKind& K, const char* who, const Mes
         plan->pairs.push_back((int32_t)i);
         for (int32_t q = sh.tri_first[(size_t)t]; q < sh.tri_first[(size_t)t + 1]; ++q) touched[(size_t)sh.tri_entry[(size_t)q]] = 1;
       }
-  } else {  // an id is the flat index of the sphere
+  } else if (K.type == rt::PRIM_SPHERE) {  // an id is the flat index of the sphere
     for (int64_t i = 0; i < n; ++i) {
       plan->pairs.push_back(ids[i]);
       plan->pairs.push_back((int32_t)i);
       for (int32_t q = sh.sph_first[(size_t)ids[i]]; q < sh.sph_first[(size_t)ids[i] + 1]; ++q) touched[(size_t)sh.sph_entry[(size_t)q]] = 1;
     }
+  } else {  // ... of the moving sphere
+    for (int64_t i = 0; i < n; ++i) {
+      plan->pairs.push_back(ids[i]);
+      plan->pairs.push_back((int32_t)i);
+      for (int32_t q = sh.mov_first[(size_t)ids[i]]; q < sh.mov_first[(size_t)ids[i] + 1]; ++q) touched[(size_t)sh.mov_entry[(size_t)q]] = 1;
+    }
   }
-  const rtx_status st = plan_touched_entries(who, K.noun, sh, touched, &plan->bvhs, &plan->members, &plan->trees, err);
+  const bool movers = K.type == rt::PRIM_MOVING_SPHERE;
+  const rtx_status st = plan_touched_entries(who, K.noun, sh, touched, &plan->bvhs, &plan->members, &plan->trees, err, movers);
   if (st != RTX_OK) return st;
+  if (movers) {  // a plain mover in the world list: the slot record's box and WD_TIME_BOX (no top_box32, no medium, no pair rule)
+    for (size_t k = 0; k < sh.mover_slot.size(); k += 2)
+      if (touched[(size_t)sh.mover_slot[k + 1]]) { plan->slots.push_back(sh.mover_slot[k]); plan->slots.push_back(2); }
+    return RTX_OK;
+  }
   for (size_t k = 0; k < sh.slot_box.size(); k += 4) {
     const int32_t next = sh.slot_box[k + 3];  // a plain sphere slot before a medium: their "same sphere" flag hangs on either
     if (touched[(size_t)sh.slot_box[k + 1]] || (next >= 0 && touched[(size_t)next])) { plan->slots.push_back(sh.slot_box[k]); plan->slots.push_back(sh.slot_box[k + 2]); }
@@ -343,6 +395,23 @@ RT_HD void bvh_leaf_box(int32_t code, const rt::PrimRef* refs, const rt::FlatSph
   for (uint32_t i = 0; i < count; ++i) {
     double pb[6];
     rt::static_prim_box(refs[first + i], spheres, rects, triangles, pb);
+    for (int a = 0; a < 3; ++a) { b[a] = rt::rt_fmin(b[a], pb[a]); b[3 + a] = rt::rt_fmax(b[3 + a], pb[3 + a]); }
+  }
+}
+
+// The box of a leaf of a BVH that holds MovingSpheres, over [ta, tb] (ta == tb: at that instant): a mover gives
+// core/mover_box.hpp's box, a static member its static box whatever the times (flatten.cpp: prim_box).  No GravitySphere: its
+// reference would get the empty box (plan_touched_entries refuses such a BVH first).
+RT_HD void timed_leaf_box(int32_t code, const rt::PrimRef* refs, const rt::FlatSphere* spheres, const rt::FlatMovingSphere* movers,
+                          const rt::FlatRect* rects, const rt::FlatTriangle* triangles, double ta, double tb, double* b) {
+  const double inf = __builtin_huge_val();
+  for (int a = 0; a < 3; ++a) { b[a] = inf; b[3 + a] = -inf; }
+  const uint32_t first = rt::leaf_first(code), count = rt::leaf_count(code);
+  for (uint32_t i = 0; i < count; ++i) {
+    double pb[6];
+    const rt::PrimRef ref = refs[first + i];
+    if (rt::primref_type(ref) == rt::PRIM_MOVING_SPHERE) rt::moving_sphere_box(movers[rt::primref_index(ref)], ta, tb, pb);
+    else rt::static_prim_box(ref, spheres, rects, triangles, pb);
     for (int a = 0; a < 3; ++a) { b[a] = rt::rt_fmin(b[a], pb[a]); b[3 + a] = rt::rt_fmax(b[3 + a], pb[3 + a]); }
   }
 }
@@ -387,7 +456,46 @@ inline void refit_bvh(FlatScene* fs, const BvhShadow& b) {
   });
 }
 
-// rtx_flat_set_triangles / rtx_flat_set_spheres: every check first, then the edit.  Not RTX_OK: *err set and *fs untouched.
+// BVH b of fs, which holds MovingSpheres, refitted whole and bottom-up after their values changed.  nodes and nodes32 get the
+// unions over the BVH's own interval [t0, t1], as refit_bvh gives a static BVH its boxes; motion32 gets the static copy without
+// slopes where b gets no time-aware boxes, else -- a second climb, carrying the unions AT t0 and AT t1 -- the planes
+// core/mover_box.hpp makes of a child's two end boxes.  flatten.cpp derives the same top-down (motion_box_at): unions are exact
+// min / max, so the order does not show.
+inline void refit_timed_bvh(FlatScene* fs, const BvhShadow& b) {
+  if (rt::node_child_is_leaf(b.root)) return;  // no node: only its records changed
+  const rt::PrimRef* refs = fs->refs.data() + b.first_ref;
+  auto leaf_at = [&](int32_t code, double ta, double tb, double* box) {
+    timed_leaf_box(code, refs, fs->spheres.data(), fs->moving_spheres.data(), fs->rects.data(), fs->triangles.data(), ta, tb, box);
+  };
+  refit_tree_piece(fs, b.root, b.node_base, b.n_nodes, [&](int32_t code, double* box) { leaf_at(code, b.t0, b.t1, box); });
+  if (!b.time_boxes || fs->motion32.empty()) return;
+  struct Ends { double b[2][6]; };
+  std::vector<int32_t> order{b.root};  // children before parents: breadth-first from the root, walked backwards
+  for (size_t k = 0; k < order.size(); ++k)
+    for (int c = 0; c < 2; ++c)
+      if (!rt::node_child_is_leaf(fs->nodes[(size_t)order[k]].child[c])) order.push_back(fs->nodes[(size_t)order[k]].child[c]);
+  std::vector<Ends> whole((size_t)b.n_nodes);  // the two end unions of a node's whole subtree, by node - node_base
+  for (size_t k = order.size(); k-- > 0;) {
+    const int32_t n = order[k];
+    const rt::FlatNode& nd = fs->nodes[(size_t)n];
+    rt::FlatMotion32& m = fs->motion32[(size_t)n];
+    Ends u;
+    for (int c = 0; c < 2; ++c) {
+      Ends cb;
+      if (rt::node_child_is_leaf(nd.child[c])) { leaf_at(nd.child[c], b.t0, b.t0, cb.b[0]); leaf_at(nd.child[c], b.t1, b.t1, cb.b[1]); }
+      else cb = whole[(size_t)(nd.child[c] - b.node_base)];
+      (void)rt::motion_child_planes(cb.b[0], cb.b[1], m.lo0[c], m.dlo[c], m.hi0[c], m.dhi[c]);
+      if (c == 0) u = cb;
+      else
+        for (int e = 0; e < 2; ++e)
+          for (int a = 0; a < 3; ++a) { u.b[e][a] = rt::rt_fmin(u.b[e][a], cb.b[e][a]); u.b[e][3 + a] = rt::rt_fmax(u.b[e][3 + a], cb.b[e][3 + a]); }
+    }
+    whole[(size_t)(n - b.node_base)] = u;
+  }
+}
+
+// rtx_flat_set_triangles / rtx_flat_set_spheres / rtx_flat_set_moving_spheres: every check first, then the edit.  Not RTX_OK: *err
+// set and *fs untouched.
 inline rtx_status flat_set_prims(const PrimKind& K, const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* values, std::string* err) {
   if (!check_prim_args(K, who, fs, ids, n, values, err)) return RTX_EINVAL;
   if (n == 0) return RTX_OK;
@@ -401,15 +509,19 @@ inline rtx_status flat_set_prims(const PrimKind& K, const char* who, FlatScene* 
   for (size_t k = 0; k < plan.pairs.size(); k += 2) {
     const double* v = values + (size_t)K.width * (size_t)plan.pairs[k + 1];
     if (K.type == rt::PRIM_TRIANGLE) rt::set_triangle_vertices(&fs->triangles[(size_t)plan.pairs[k]], v);
-    else rt::set_sphere_values(&fs->spheres[(size_t)plan.pairs[k]], v);
+    else if (K.type == rt::PRIM_SPHERE) rt::set_sphere_values(&fs->spheres[(size_t)plan.pairs[k]], v);
+    else rt::set_moving_sphere_values(&fs->moving_spheres[(size_t)plan.pairs[k]], v);
   }
-  for (int32_t b : plan.bvhs) refit_bvh(fs, sh.bvhs[(size_t)b]);
+  for (int32_t b : plan.bvhs) {
+    if (K.type == rt::PRIM_MOVING_SPHERE) refit_timed_bvh(fs, sh.bvhs[(size_t)b]);
+    else refit_bvh(fs, sh.bvhs[(size_t)b]);
+  }
   for (int32_t m : plan.members)
     member_local_box_of(fs->entries[(size_t)sh.members[(size_t)m].geom], fs->nodes.data(), fs->refs.data(), fs->spheres.data(), fs->rects.data(),
                         fs->triangles.data(), &fs->member_local_box[6 * (size_t)m]);
   for (int32_t t : plan.trees) refit_instance_tree(fs, us.trees[(size_t)t]);
   for (size_t k = 0; k < plan.slots.size(); k += 2)
-    if (plan.slots[k + 1] == 0)  // (a medium slot has no top_box32: its box lives in the slot record an upload derives)
+    if (plan.slots[k + 1] == 0)  // (a medium or a plain mover slot has no top_box32: its box lives in the slot record an upload derives)
       rt::plain_slot_box32((rt::PrimRef)fs->entries[(size_t)fs->top_level[(size_t)plan.slots[k]]].a, fs->spheres.data(), fs->rects.data(),
                            fs->triangles.data(), &fs->top_box32[6 * (size_t)plan.slots[k]]);
   return RTX_OK;
@@ -420,13 +532,19 @@ inline rtx_status flat_set_triangles(const char* who, FlatScene* fs, const int32
 inline rtx_status flat_set_spheres(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* spheres, std::string* err) {
   return flat_set_prims(KIND_SPHERE, who, fs, ids, n, spheres, err);
 }
+// movers: n x 7 doubles, c0 xyz, c1 xyz, radius; time0, time1 and mat stay.
+inline rtx_status flat_set_moving_spheres(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* movers, std::string* err) {
+  return flat_set_prims(KIND_MOVING_SPHERE, who, fs, ids, n, movers, err);
+}
 
-// rtx_flat_triangle_ids / rtx_flat_sphere_ids (`who`): the ids of the primitives of the kind below `object`, in list order.  -1
-// with *err set.  (A MovingSphere or GravitySphere has no children and no id: skipped.)
+// rtx_flat_triangle_ids / rtx_flat_sphere_ids / rtx_flat_moving_sphere_ids (`who`): the ids of the primitives of the kind below
+// `object`, in list order.  -1 with *err set.  (A primitive of another kind has no children and no id of this kind: skipped.  The
+// flattener emits a handle once -- prim_of in flatten.cpp -- so a handle has one record and is returned once per place it is listed.)
 inline int64_t flat_prim_ids(const PrimKind& K, const char* who, const FlatScene& fs, const SceneGraph& g, int32_t object, int32_t* ids, int64_t cap,
                              std::string* err) {
-  const bool tri = K.type == rt::PRIM_TRIANGLE;
-  const std::vector<int32_t>& handle_id = tri ? fs.handle_triangle_id : fs.handle_sphere_id;
+  const std::vector<int32_t>& handle_id = K.type == rt::PRIM_TRIANGLE ? fs.handle_triangle_id
+                                          : K.type == rt::PRIM_SPHERE ? fs.handle_sphere_id : fs.handle_moving_sphere_id;
+  const int32_t h_kind = K.type == rt::PRIM_TRIANGLE ? H_TRIANGLE : K.type == rt::PRIM_SPHERE ? H_SPHERE : H_MOVING_SPHERE;
   if (!g.valid_hittable(object)) { *err = std::string(who) + ": bad object handle"; return -1; }
   int64_t count = 0;
   std::vector<std::pair<int32_t, int>> todo{{object, 0}};  // depth-first, children in list order
@@ -436,7 +554,7 @@ inline int64_t flat_prim_ids(const PrimKind& K, const char* who, const FlatScene
     if (at.second > 80) { *err = std::string(who) + ": objects nested deeper than 80"; return -1; }
     if ((size_t)at.first >= handle_id.size()) { *err = std::string(who) + ": the object was made after this flat scene was flattened"; return -1; }
     const GHittable& o = g.hittables[(size_t)at.first];
-    if (o.kind == (tri ? H_TRIANGLE : H_SPHERE)) {
+    if (o.kind == h_kind) {
       const int32_t id = handle_id[(size_t)at.first];
       if (id < 0) { *err = std::string(who) + ": this flat scene did not flatten the object (a " + K.noun + " below it has no id)"; return -1; }
       if (ids && count < cap) ids[count] = id;
