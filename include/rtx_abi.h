@@ -818,6 +818,52 @@ rtx_status rtx_scene_set_moving_spheres(rtx_scene* s, const int32_t* ids, int64_
  * index is derived from a value, so nothing can leave an allocation. */
 rtx_status rtx_scene_set_moving_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_movers, void* hip_stream);
 
+/* ---- moving walls, boxes and area lights: new extents for rectangles of a flat scene or of a resident f64 scene (an extension)
+ * Rectangles are what walls, the six faces of a RectPrism, the boundary box of a medium and rectangular area lights are made
+ * of.  The flattener neither permutes nor copies a rectangle, so a rectangle's ID is its index in the flat scene's rectangle
+ * array (rtx_flat_array 19: FlatRect, 48 bytes each -- a0 a1 b0 b1 k as doubles, then axis and material as int32).
+ *
+ * rtx_flat_rect_ids: the ids of every rectangle the flattener emitted from the handles below `object` (a rectangle, a
+ * RectPrism, a list, a BvhNode, an instance tree, a Translate, RotateY or ConstantMedium around those), handle by handle in list
+ * order, a handle's rectangles in emission order.  A rectangle handle has one id however often it is listed.  A RectPrism has
+ * six per emission -- front, back, top, bottom, right, left: the order of RectPrism::new -- and is emitted anew from every place
+ * it is reached from, so one prism handle under two Translates has twelve, and they are returned together, from the world and
+ * from the prism's own handle alike.  No id is returned twice.  Writes min(count, cap) ids, returns count; -1 (and
+ * rtx_last_error) for a NULL argument, a bad handle or an object this flat scene did not flatten. */
+int64_t rtx_flat_rect_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap);
+/* rects: n x 5 doubles a0 a1 b0 b1 k of rectangle ids[i] -- the constructor's (x0, x1, y0, y1, k) in FlatRect's own order; the
+ * axis and the material stay.  ids: a HOST array in all three entries, free for reuse on return.
+ *
+ * Meaning, as for rtx_*_set_spheres: the scene then answers every entry point bit for bit as the scene built from scratch with
+ * those values, with the same exemptions (a tie inside one BVH, the sign of a zero plane, a fresh build's other topology).
+ *
+ * What is written, and nothing else: a0 a1 b0 b1 k of the record; the boxes of every BVH that holds an updated rectangle,
+ * refitted whole and bottom-up with the TOPOLOGY kept (nodes, nodes32, the static copy of the time-aware boxes, the 4-wide
+ * tree's planes on a resident scene that has one); member_local_box and the instance tree above a touched member -- a
+ * rectangle, a prism or a BVH under a chain, also as the boundary of a medium; top_box32 and the slot record's box of a plain
+ * top-level rectangle; on a resident scene, when an updated rectangle is a sampled light, the light table: that light's area
+ * and every light's cdf and pmf.  On a resident scene k_trace_vote's launch argument holds a copy of up to eight top-level
+ * rectangle records: the host entry rewrites the copy before it returns; the device entry, which never sees the values, gives
+ * the copy up when it holds a touched rectangle, and launches walk the world list from then on -- the same image, slower by
+ * the list walk's dependent loads.
+ *
+ * RTX_EINVAL, the message naming the field, nothing enqueued and the scene unchanged: a NULL argument, n < 0, an id out of
+ * range or named twice; host entries: a value that is not finite (no other rule: an inverted or an empty extent is what the
+ * constructor would store); device entry: a pointer that is not 8-byte aligned.  n = 0 is RTX_OK with nothing launched.
+ * RTX_EUNSUPPORTED, the scene unchanged, checked before anything is enqueued: a touched BVH that holds a MovingSphere or
+ * GravitySphere, and a resident f32 scene: update the flat scene with rtx_flat_set_rects and upload it again with
+ * rtx_scene_upload_f32. */
+rtx_status rtx_flat_set_rects(rtx_flat* f, const int32_t* ids, int64_t n, const double* rects);
+/* A resident f64 scene; rects is a HOST array, staged with one copy.  Asynchronous on hip_stream, as rtx_scene_set_spheres:
+ * k_set_prims, then per touched BVH k_refit_bvh (and k_refit_wide), k_member_local_boxes and k_refit_instance_tree per touched
+ * instance tree, k_slot_boxes, k_refresh_lights.  One update of a scene at a time; ordering against work on other streams is
+ * the caller's; progressive handles made earlier hold the old rectangles.  rtx_multi_* scenes are not covered. */
+rtx_status rtx_scene_set_rects(rtx_scene* s, const int32_t* ids, int64_t n, const double* rects, void* hip_stream);
+/* d_rects: a DEVICE pointer (8-byte aligned); it is read by work enqueued on hip_stream and must stay valid until that work is
+ * done.  Finiteness cannot be checked without a read-back: a value that is not finite gives that rectangle and the boxes above
+ * it unspecified culling.  No index is derived from a value, so nothing can leave an allocation. */
+rtx_status rtx_scene_set_rects_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_rects, void* hip_stream);
+
 /* ---- relighting and look development: new shading parameters -----------------------------------------------------------------
  * Editing colours, a noise scale, a metal, a glass's index or a fog's density of a flattened or a resident scene gives the
  * scene that rtx_flatten (and rtx_scene_upload / rtx_scene_upload_f32) build from scratch when the builder calls are made with

@@ -181,7 +181,8 @@ _XFORM_NAMES = ("translate", "rotate_y")
 SCENE_ARRAYS = {"entries": (0, 160, 104), "nodes": (1, 112, 64), "nodes32": (2, 64, 64), "motion32": (3, 96, 96),
                 "world_desc": (4, 192, 136), "top_level": (5, 4, 4), "member_local_box": (6, 8, 8), "nodes4": (7, 128, 128),
                 "triangles": (10, 104, 56), "top_box32": (11, 4, 4), "triangle_id": (12, 4, 4), "spheres": (13, 40, 24),
-                "lights": (14, 40, 40), "materials": (15, 48, 32), "textures": (16, 48, 32), "moving_spheres": (17, 80, 44)}
+                "lights": (14, 40, 40), "materials": (15, 48, 32), "textures": (16, 48, 32), "moving_spheres": (17, 80, 44),
+                "rects": (19, 48, 28)}
 
 RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_rays)
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
@@ -313,6 +314,10 @@ ABI = {
     "rtx_flat_set_moving_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
     "rtx_scene_set_moving_spheres": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
     "rtx_scene_set_moving_spheres_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
+    "rtx_flat_rect_ids": (C.c_int64, [_VP, _VP, _H, C.POINTER(C.c_int32), C.c_int64]),
+    "rtx_flat_set_rects": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3]),
+    "rtx_scene_set_rects": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _D3, _VP]),
+    "rtx_scene_set_rects_device": (C.c_int32, [_VP, C.POINTER(C.c_int32), C.c_int64, _VP, _VP]),
     "rtx_flat_material_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMaterialInfo)]),
     "rtx_flat_texture_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxTextureInfo)]),
     "rtx_flat_medium_info": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxMediumInfo)]),
@@ -638,6 +643,20 @@ class Flat:
         ids, movers = _prim_update(ids, movers, *_MOVER_VALUES)
         _check(lib.rtx_flat_set_moving_spheres(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), movers.ctypes.data_as(_D3)))
 
+    def rect_ids(self, builder, handle):
+        """The ids of every rectangle emitted from the handles below `handle` (a rectangle, a RectPrism, a list, a BvhNode, an
+        instance tree, a wrapper or medium around those), handle by handle in list order (rtx_flat_rect_ids) -> int32 array.  A
+        rectangle's id is its index in Flat.array("rects"); a RectPrism gives six per emission in the order of prism_rects --
+        twelve for one prism under two Translates -- and no id is returned twice."""
+        return _prim_ids(lib.rtx_flat_rect_ids, self, builder, handle)
+
+    def set_rects(self, ids, rects):
+        """New extents for the rectangles `ids`, in place (rtx_flat_set_rects): the flat scene becomes the one flattened from
+        scratch with these rectangles, its BVHs refitted with their topology kept.  rects: n x 5 doubles, a0 a1 b0 b1 k of
+        ids[i] -- the constructor's (x0, x1, y0, y1, k); the axis and the material stay."""
+        ids, rects = _prim_update(ids, rects, *_RECT_VALUES)
+        _check(lib.rtx_flat_set_rects(self._p, ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids), rects.ctypes.data_as(_D3)))
+
     def set_shading(self, edits):
         """New shading parameters, in place (rtx_flat_set_shading): the flat scene becomes the one flattened from scratch when
         the builder calls are made with the new values.  edits: a list of ("solid_color", tex, (r, g, b)) | ("noise_scale", tex,
@@ -697,6 +716,16 @@ class Flat:
 _TRIANGLE_VALUES = (9, "vertices", "v0 v1 v2")        # width, name, each: what a set_* call holds per id
 _SPHERE_VALUES = (4, "spheres", "cx cy cz radius")
 _MOVER_VALUES = (7, "movers", "c0 xyz, c1 xyz, radius")
+_RECT_VALUES = (5, "rects", "a0 a1 b0 b1 k")
+
+
+def prism_rects(p0, p1):
+    """The (6, 5) values a0 a1 b0 b1 k of the six rectangles of Builder.rect_prism(p0, p1), in the order the flattener emits them
+    (RectPrism::new: front, back, top, bottom, right, left -- two XY, two XZ, two YZ rectangles).  Moving a box of a resident
+    scene is scene.set_rects(flat.rect_ids(b, box), prism_rects(p0, p1))."""
+    (x0, y0, z0), (x1, y1, z1) = [float(v) for v in p0], [float(v) for v in p1]
+    return np.array([[x0, x1, y0, y1, z1], [x0, x1, y0, y1, z0], [x0, x1, z0, z1, y1], [x0, x1, z0, z1, y0],
+                     [y0, y1, z0, z1, x1], [y0, y1, z0, z1, x0]], dtype=np.float64)
 
 
 def _prim_ids(fn, flat, builder, handle):
@@ -913,6 +942,18 @@ class Scene:
             import torch
             stream = torch.cuda.current_stream(movers.device)
         _scene_set_prims(self, lib.rtx_scene_set_moving_spheres, lib.rtx_scene_set_moving_spheres_device, ids, movers, stream, *_MOVER_VALUES)
+
+    def set_rects(self, ids, rects, stream=None):
+        """New extents for the rectangles `ids` of the RESIDENT f64 scene -- a wall, the faces of a box (prism_rects), the boundary
+        of a fog, an area light that slides or shrinks.  Every later call answers as on the scene built from scratch with these
+        values (BVHs and instance trees are refitted on the device, their topology kept; slot boxes and the light table follow).
+        rects: n x 5 doubles a0 a1 b0 b1 k as a numpy array (rtx_scene_set_rects, staged with one copy) or as a torch float64
+        tensor on the GPU (rtx_scene_set_rects_device).  ids: host integers either way.  Enqueued on `stream` as in
+        set_transforms; a tensor without a `stream` is taken on torch's current stream."""
+        if stream is None and hasattr(rects, "data_ptr") and getattr(rects, "is_cuda", False):
+            import torch
+            stream = torch.cuda.current_stream(rects.device)
+        _scene_set_prims(self, lib.rtx_scene_set_rects, lib.rtx_scene_set_rects_device, ids, rects, stream, *_RECT_VALUES)
 
     def set_shading(self, edits, stream=None):
         """New shading parameters for the RESIDENT scene of either precision (rtx_scene_set_shading): every later call answers as

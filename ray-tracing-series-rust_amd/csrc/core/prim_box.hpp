@@ -88,6 +88,12 @@ RT_HD void set_sphere_values(FlatSphere* s, const double* v) {
   s->cx = (real)v[0]; s->cy = (real)v[1]; s->cz = (real)v[2]; s->radius = (real)v[3];
 }
 
+// a0 a1 b0 b1 k -> the record (axis and mat stay): the constructor's (x0, x1, y0, y1, k), FlatRect's own order, with the casts
+// the flattener makes.  No rule beyond that: an inverted or empty extent is what the constructor would have stored.
+RT_HD void set_rect_values(FlatRect* q, const double* v) {
+  q->a0 = (real)v[0]; q->a1 = (real)v[1]; q->b0 = (real)v[2]; q->b1 = (real)v[3]; q->k = (real)v[4];
+}
+
 // v0 v1 v2 -> the record's vertices and normal = unit((v1 - v0) x (v2 - v0)) (hit.rs:96-107), by the functions
 // SceneGraph::triangle calls; mat and pad stay.  A zero-area triangle gets the NaN normal a fresh build gives it.
 RT_HD void set_triangle_vertices(FlatTriangle* t, const double* v) {

@@ -412,6 +412,21 @@ rtx_status rtx_flat_set_moving_spheres(rtx_flat* f, const int32_t* ids, int64_t 
   return st;
 }
 
+int64_t rtx_flat_rect_ids(const rtx_flat* f, const rtx_builder* b, rtx_handle object, int32_t* ids, int64_t cap) {
+  if (!f || !b || (!ids && cap > 0) || cap < 0) { set_error("rtx_flat_rect_ids: NULL argument or cap < 0"); return -1; }
+  std::string err;
+  const int64_t n = flat_rect_ids("rtx_flat_rect_ids", f->scene, b->graph, object, ids, cap, &err);
+  if (n < 0) set_error(err);
+  return n;
+}
+
+rtx_status rtx_flat_set_rects(rtx_flat* f, const int32_t* ids, int64_t n, const double* rects) {
+  std::string err;
+  const rtx_status st = flat_set_rects("rtx_flat_set_rects", f ? &f->scene : nullptr, ids, n, rects, &err);
+  if (st != RTX_OK) set_error(err);
+  return st;
+}
+
 rtx_status rtx_flat_material_info(const rtx_flat* f, int32_t index, RtxMaterialInfo* o) {
   if (!f || !o) { set_error("rtx_flat_material_info: NULL argument"); return RTX_EINVAL; }
   const FlatScene& s = f->scene;
@@ -476,7 +491,7 @@ rtx_status rtx_flat_array(const rtx_flat* f, int32_t which, void* out, size_t by
   switch (which) {
     ARR(0, entries) ARR(1, nodes) ARR(2, nodes32) ARR(3, motion32) ARR(5, top_level) ARR(6, member_local_box)
     ARR(10, triangles) ARR(11, top_box32) ARR(12, triangle_id) ARR(13, spheres) ARR(15, materials) ARR(16, textures)
-    ARR(17, moving_spheres)
+    ARR(17, moving_spheres) ARR(19, rects)
     default: set_error("rtx_flat_array: which names no host array"); return RTX_EINVAL;
   }
 #undef ARR

@@ -25,8 +25,17 @@
 //                                   slot before such a medium: the "same sphere as the medium behind me" flag (k_slot_boxes)
 //   the light table                 when an updated sphere is a sampled light: its area, and every light's cdf and pmf
 //                                   (k_refresh_lights, with host/light_table.hpp's weight rule and cdf pass)
+// for rectangles (rtx_scene_set_rects*; DESIGN.md 8.8) -- walls, the six faces of a RectPrism, the boundary box of a medium,
+// rectangular area lights:
+//   rects                           a0 a1 b0 b1 k of the record of a rectangle id; axis and mat stay (k_set_prims)
+//   nodes / nodes32 / motion32 / nodes4, d_local_box and the instance trees, top_box32 / WorldDesc of a plain rectangle slot:
+//                                   as for a triangle
+//   the light table                 when an updated rectangle is a sampled light: as for a sphere
+//   VotePlan::top                   the HOST's copy of up to eight top-level rectangle records that travels to k_trace_vote as a
+//                                   kernel argument (refresh_vote_top: rewritten by the host entry, given up by the device entry)
 // with the arithmetic of the flattener (core/prim_box.hpp, host/set_triangles.hpp), so that the arrays equal those of the
-// host-updated flat scene uploaded afresh -- the judge of tests/test_gpu_set_triangles.py and tests/test_gpu_set_spheres.py.
+// host-updated flat scene uploaded afresh -- the judge of tests/test_gpu_set_triangles.py, tests/test_gpu_set_spheres.py,
+// tests/test_gpu_set_moving_spheres.py and tests/test_gpu_set_rects.py.
 // k_trace_lds copies nodes32 and the sphere records into LDS at the start of every launch and keeps no packed copy from the
 // upload, so it needs nothing more.  Topology is not touched: child codes, split axes, refs, entries; SceneView, the trace
 // kernels, their arguments and every launch plan do not change.
@@ -40,6 +49,7 @@
 __device__ __forceinline__ void set_record(rt::FlatTriangle* t, const double* v) { rt::set_triangle_vertices(t, v); }
 __device__ __forceinline__ void set_record(rt::FlatSphere* s, const double* v) { rt::set_sphere_values(s, v); }
 __device__ __forceinline__ void set_record(rt::FlatMovingSphere* s, const double* v) { rt::set_moving_sphere_values(s, v); }
+__device__ __forceinline__ void set_record(rt::FlatRect* q, const double* v) { rt::set_rect_values(q, v); }
 
 // One thread per (flat record, the caller's W values for it): pairs[2 i] = flat index, pairs[2 i + 1] = index of the W-tuple in
 // `values`.
@@ -172,7 +182,7 @@ __global__ __launch_bounds__(256) void k_member_local_boxes(const int32_t* __res
   for (int x = 0; x < 6; ++x) local_box[6 * (size_t)list[2 * (size_t)i] + x] = b[x];
 }
 
-// One thread per listed slot: slots[2 i] = the slot, slots[2 i + 1] = 0 a plain triangle or static sphere, 1 a medium bounded
+// One thread per listed slot: slots[2 i] = the slot, slots[2 i + 1] = 0 a plain triangle, static sphere or rectangle, 1 a medium bounded
 // by a sphere, 2 a plain MovingSphere (the record's box, WD_TIME_BOX and its two times by core/mover_box.hpp's rule, as
 // build_world_desc sets them: a box that is not finite clears the flag and the times; top_box32 of such a slot is unbounded and stays).  top_box32 (plain only) and the box, the WD_BOXED_PRIM and the WD_PAIR flag of the slot's WorldDesc record, as
 // the flattener and build_world_desc derive them; a triangle slot has no WD_SPHERE flag and so no pair rule.  A thread writes
@@ -229,11 +239,13 @@ __global__ __launch_bounds__(256) void k_slot_boxes(const int32_t* __restrict__ 
 
 // ONE block.  A thread per light (in strides of the block) for the area and the pick weight; then one thread for the serial
 // sum, the fallback and the cdf: lights are few, and the serial order of the additions is what makes the bytes the host's.
+// Every light's area is stored back, a rectangle's as a sphere's: light_area_centre is the function that built the table, so an
+// untouched light gets the bytes it had.
 __global__ __launch_bounds__(256) void k_refresh_lights(rt::SceneView sv, rt::FlatLight* __restrict__ lights, int32_t n_lights, double* __restrict__ weight) {
   for (int32_t k = (int32_t)threadIdx.x; k < n_lights; k += 256) {
     rt::Point3 centre;
     const rt::real area = rt::light_area_centre(lights[k], sv.spheres, sv.rects, &centre);
-    if (lights[k].kind == rt::LIGHT_SPHERE) lights[k].area = area;
+    lights[k].area = area;
     weight[k] = rt::light_pick_weight(sv, lights[k].mat, area, centre);
   }
   __syncthreads();
@@ -339,13 +351,31 @@ static rtx_status launch_member_refits(DeviceScene* ds, const int32_t* d_members
   return RTX_OK;
 }
 
+// k_trace_vote's copy of the top-level rectangle records (render.hip: VoteTop, a kernel argument made at upload) after an update
+// of rectangles.  pairs: 2 per flat rectangle, its index and the index of its values.  values (host memory): the copy takes them
+// by the function the kernel stores them with, before the call returns -- a launch reads its arguments when it is enqueued, so
+// a render enqueued after this call sees the new records and one enqueued before it the old, as with `rects` itself on one
+// stream.  values == NULL (the device entry: the host never sees them): a copy that holds a touched rectangle is given up for
+// good, top.n = -1, and every later launch walks the world list as it does for a world of more than eight plain entries -- the
+// same hits, three dependent scalar loads per entry and ray instead of one (DESIGN.md 8.8).
+static void refresh_vote_top(DeviceScene* ds, const std::vector<int32_t>& pairs, const double* values) {
+  VoteTop& top = ds->vote.top;
+  if (top.n < 0) return;
+  for (size_t k = 0; k < pairs.size(); k += 2)
+    for (int32_t i = 0; i < top.n; ++i) {
+      if (rt::primref_type((rt::PrimRef)top.ref[i]) != rt::PRIM_RECT || rt::primref_index((rt::PrimRef)top.ref[i]) != (uint32_t)pairs[k]) continue;
+      if (!values) { top.n = -1; return; }
+      rt::set_rect_values(&top.rect[i], values + 5 * (size_t)pairs[k + 1]);
+    }
+}
+
 // ids (host memory) have passed check_prim_ids against ds->mesh.shadow.  values: host memory (staged here, one copy) when
 // host_values, else a device pointer.  Everything that can refuse comes first; then one copy and the launches, all on `stream`.
 static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const char* who, const int32_t* ids, int64_t n, const double* values,
                                        bool host_values, hipStream_t stream) {
   MeshUpdate& mu = ds->mesh;
   const MeshShadow& sh = mu.shadow;
-  const bool tri = K.type == rt::PRIM_TRIANGLE, mov = K.type == rt::PRIM_MOVING_SPHERE;
+  const bool tri = K.type == rt::PRIM_TRIANGLE, mov = K.type == rt::PRIM_MOVING_SPHERE, rect = K.type == rt::PRIM_RECT;
   std::string err;
   UpdatePlan plan;
   const rtx_status pst = plan_prim_update(K, who, sh, ids, n, &plan, &err);
@@ -354,8 +384,9 @@ static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const
   if (dst != RTX_OK) return dst;
   rtx_status st = upload_mesh_tables(ds);
   if (st != RTX_OK) return st;
-  bool lights = false;  // a listed sphere is a sampled light
-  for (int64_t i = 0; !tri && !mov && i < n; ++i) lights = lights || ((size_t)ids[i] < mu.sphere_is_light.size() && mu.sphere_is_light[(size_t)ids[i]]);
+  bool lights = false;  // a listed sphere or rectangle is a sampled light
+  const std::vector<char>& is_light = rect ? mu.rect_is_light : mu.sphere_is_light;
+  for (int64_t i = 0; !tri && !mov && i < n; ++i) lights = lights || ((size_t)ids[i] < is_light.size() && is_light[(size_t)ids[i]]);
   if (lights && !mu.d_light_weight) HIP_TRY(mu.d_light_weight.alloc((size_t)ds->lights.n_lights * sizeof(double)));
   // staging layout: [values, width x 8 B each (host entry only)] [pairs] [members: index, entry] [slots: slot, kind]
   const size_t value_bytes = host_values ? (size_t)n * (size_t)K.width * sizeof(double) : 0;
@@ -378,7 +409,9 @@ static rtx_status scene_set_prims_impl(DeviceScene* ds, const PrimKind& K, const
   const int32_t* d_members = d_pairs + 2 * n_pairs;
   const int32_t* d_slots = d_members + 2 * n_members;
   const dim3 pair_grid((unsigned)((n_pairs + 255) / 256));
-  if (tri) hipLaunchKernelGGL((k_set_prims<9, rt::FlatTriangle>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatTriangle*)ds->view.triangles);
+  if (rect) refresh_vote_top(ds, plan.pairs, host_values ? values : nullptr);  // (nothing below refuses: only a HIP error ends the call early)
+  if (rect) hipLaunchKernelGGL((k_set_prims<5, rt::FlatRect>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatRect*)ds->view.rects);
+  else if (tri) hipLaunchKernelGGL((k_set_prims<9, rt::FlatTriangle>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatTriangle*)ds->view.triangles);
   else if (mov) hipLaunchKernelGGL((k_set_prims<7, rt::FlatMovingSphere>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatMovingSphere*)ds->view.moving_spheres);
   else hipLaunchKernelGGL((k_set_prims<4, rt::FlatSphere>), pair_grid, dim3(256), 0, stream, d_pairs, (int)n_pairs, d_values, (rt::FlatSphere*)ds->view.spheres);
   HIP_TRY(hipGetLastError());

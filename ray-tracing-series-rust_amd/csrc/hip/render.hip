@@ -182,7 +182,7 @@ struct SceneUpdate {
   UpdateShadow shadow;              // host: the slots' chains, the instance trees and their parent tables
   std::vector<double> local_box;    // host: FlatScene::member_local_box (an update's new boxes are checked before anything is enqueued)
   size_t n_entries = 0, n_nodes = 0, n_motion = 0, n_desc = 0;  // element counts of the arrays an update writes (rtx_device_scene_array)
-  size_t n_triangles = 0, n_top = 0, n_spheres = 0, n_moving_spheres = 0;
+  size_t n_triangles = 0, n_top = 0, n_spheres = 0, n_moving_spheres = 0, n_rects = 0;
   DeviceBuffer<double> d_local_box;
   DeviceBuffer<int32_t> d_leaf_parent, d_node_parent;
   DeviceBuffer<unsigned int> d_arrivals;        // one counter per tree node
@@ -216,6 +216,7 @@ struct MeshUpdate {
                                                  // not wait for the copy of the last rtx_scene_set_transforms
   bool local_box_stale = false;                  // SceneUpdate::local_box lags behind d_local_box (scene_update.inc reads it back)
   std::vector<char> sphere_is_light;             // host, per flat sphere: it is a sampled light (an update of it refreshes the light table)
+  std::vector<char> rect_is_light;               // the same per flat rectangle
   DeviceBuffer<double> d_light_weight;           // k_refresh_lights' pick weights, one per light; allocated by the first such update
   // rtx_scene_set_moving_spheres (k_refit_timed_bvh); allocated by the first such update
   std::vector<unsigned int> slope_mask;          // host, per BVH: the axes its time-aware boxes have a slope along, as uploaded
@@ -1541,8 +1542,11 @@ static rtx_status scene_upload_impl(const FlatScene& fs, DeviceScene** out) {
       }
       ds->lights.n_lights = (int32_t)lt.lights.size();
       ds->mesh.sphere_is_light.assign(fs.spheres.size(), 0);
-      for (const rt::FlatLight& L : lt.lights)
+      ds->mesh.rect_is_light.assign(fs.rects.size(), 0);
+      for (const rt::FlatLight& L : lt.lights) {
         if (L.kind == rt::LIGHT_SPHERE) ds->mesh.sphere_is_light[(size_t)L.prim] = 1;
+        else if (L.kind == rt::LIGHT_RECT) ds->mesh.rect_is_light[(size_t)L.prim] = 1;
+      }
     }
   }
 #endif
@@ -1771,6 +1775,7 @@ static rtx_status scene_set_prims_any(const PrimKind& K, const char* who, rtx_sc
               (K.type == rt::PRIM_TRIANGLE
                    ? "vertices of the untouched triangles in touched leaves. Update the flat scene with rtx_flat_set_triangles"
                    : mov ? "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_moving_spheres"
+                   : K.type == rt::PRIM_RECT ? "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_rects"
                          : "records of the untouched primitives in touched leaves. Update the flat scene with rtx_flat_set_spheres") +
               " and upload it again with rtx_scene_upload_f32");
     return RTX_EUNSUPPORTED;
@@ -1796,6 +1801,12 @@ rtx_status rtx_scene_set_moving_spheres(rtx_scene* s, const int32_t* ids, int64_
 }
 rtx_status rtx_scene_set_moving_spheres_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_movers, void* hip_stream) {
   return scene_set_prims_any(KIND_MOVING_SPHERE, "rtx_scene_set_moving_spheres_device", s, ids, n, d_movers, false, hip_stream);
+}
+rtx_status rtx_scene_set_rects(rtx_scene* s, const int32_t* ids, int64_t n, const double* rects, void* hip_stream) {
+  return scene_set_prims_any(KIND_RECT, "rtx_scene_set_rects", s, ids, n, rects, true, hip_stream);
+}
+rtx_status rtx_scene_set_rects_device(rtx_scene* s, const int32_t* ids, int64_t n, const double* d_rects, void* hip_stream) {
+  return scene_set_prims_any(KIND_RECT, "rtx_scene_set_rects_device", s, ids, n, d_rects, false, hip_stream);
 }
 
 // ---- instance trees of a resident scene: a new topology for the current pose, and the cost of a tree as it stands

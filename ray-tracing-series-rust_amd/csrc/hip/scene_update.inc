@@ -190,6 +190,7 @@ static rtx_status build_scene_update(DeviceScene* ds, const FlatScene& fs) {
   u.n_desc = fs.top_level.size();
   u.n_triangles = fs.triangles.size(); u.n_top = fs.top_box32.size() / 6; u.n_spheres = fs.spheres.size();
   u.n_moving_spheres = fs.moving_spheres.size();
+  u.n_rects = fs.rects.size();
 #ifndef RTX_F32_TU
   ds->mesh.shadow = build_mesh_shadow(fs, u.shadow);  // rtx_scene_set_triangles (mesh_update.inc); its tables go up with the first update
   // per BVH, the axes along which its time-aware boxes have a slope as uploaded: what k_refit_timed_bvh keeps current from then on
@@ -307,6 +308,7 @@ static rtx_status scene_read_array_impl(DeviceScene* ds, int32_t which, void* ou
     case 15: p = ds->view.materials; have = u.n_materials * sizeof(rt::FlatMaterial); break;
     case 16: p = ds->view.textures; have = u.n_textures * sizeof(rt::FlatTexture); break;
     case 17: p = ds->view.moving_spheres; have = u.n_moving_spheres * sizeof(rt::FlatMovingSphere); break;
+    case 19: p = ds->view.rects; have = u.n_rects * sizeof(rt::FlatRect); break;
     case 7: p = ds->wide.nodes4; have = ds->wide.nodes4 ? u.n_nodes * sizeof(FlatNode4) : 0; break;
     case 9:  // max_stack as the binary walks are now launched with: host memory, one int32
       if (bytes != sizeof(int32_t) || !out) { set_error("rtx_device_scene_array: the array holds 4 bytes, not " + std::to_string(bytes)); return RTX_EINVAL; }

@@ -54,6 +54,12 @@ struct FlatScene {
   // The same for what rtx_*_set_moving_spheres names a MovingSphere by: its index in `moving_spheres`, -1 for anything else
   // (rtx_flat_moving_sphere_ids).  Appended behind the last, for the same reason.
   std::vector<int32_t> handle_moving_sphere_id;
+  // What rtx_*_set_rects names a rectangle by: its index in `rects` -- a rectangle is neither permuted nor copied.  Per graph
+  // hittable at the time of the flatten, the rectangles emitted from it, in emission order: handle h owns
+  // handle_rect_id[handle_rect_first[h] .. handle_rect_first[h + 1]).  A rectangle handle is emitted once and owns one; a
+  // RectPrism owns six per emission (the order of emit_prism) and is emitted anew from every place it is reached; anything
+  // else owns none (rtx_flat_rect_ids).  Appended behind the last, for the same reason.
+  std::vector<int32_t> handle_rect_first, handle_rect_id;
 
   // pointers into the vectors above (host memory)
   rt::SceneView view() const {

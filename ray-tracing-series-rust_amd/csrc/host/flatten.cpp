@@ -46,6 +46,7 @@ struct Flattener {
   std::string err;
   std::vector<int64_t> prim_of;  // graph hittable -> PrimRef already emitted (-1: not yet)
   int32_t next_triangle_id = 0;
+  std::vector<int32_t> rect_handle;   // per flat rectangle: the graph hittable it was emitted from (a rectangle or a RectPrism)
   std::vector<int32_t> bvh_entry_of;  // graph BVH hittable -> its entry (-1: not yet): a reused handle (the reference holds
                                       // objects as Arc, so one BvhNode may sit under several Translates) is emitted once
 
@@ -63,10 +64,11 @@ struct Flattener {
            kind == H_XZ_RECT || kind == H_YZ_RECT || kind == H_GRAVITY_SPHERE;
   }
 
-  rt::PrimRef emit_rect(int32_t axis, double a0, double a1, double b0, double b1, double k, int32_t mat) {
+  rt::PrimRef emit_rect(int32_t h, int32_t axis, double a0, double a1, double b0, double b1, double k, int32_t mat) {
     rt::FlatRect q;
     q.a0 = a0; q.a1 = a1; q.b0 = b0; q.b1 = b1; q.k = k; q.axis = axis; q.mat = mat;
     out.rects.push_back(q);
+    rect_handle.push_back(h);
     return rt::make_primref(rt::PRIM_RECT, (uint32_t)out.rects.size() - 1);
   }
 
@@ -115,24 +117,24 @@ struct Flattener {
         ref = rt::make_primref(rt::PRIM_GRAVITY_SPHERE, (uint32_t)out.gravity_spheres.size() - 1);
         break;
       }
-      case H_XY_RECT: ref = emit_rect(rt::RECT_XY, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
-      case H_XZ_RECT: ref = emit_rect(rt::RECT_XZ, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
-      default: ref = emit_rect(rt::RECT_YZ, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
+      case H_XY_RECT: ref = emit_rect(h, rt::RECT_XY, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
+      case H_XZ_RECT: ref = emit_rect(h, rt::RECT_XZ, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
+      default: ref = emit_rect(h, rt::RECT_YZ, o.f[0], o.f[1], o.f[2], o.f[3], o.f[4], o.mat); break;
     }
     prim_of[h] = (int64_t)ref;
     return ref;
   }
 
   // RectPrism::new (hit.rs:720-769): six sides in the reference's add() order.
-  void emit_prism(const GHittable& o, std::vector<rt::PrimRef>* refs) {
+  void emit_prism(int32_t h, const GHittable& o, std::vector<rt::PrimRef>* refs) {
     const double* p0 = &o.f[0];
     const double* p1 = &o.f[3];
-    refs->push_back(emit_rect(rt::RECT_XY, p0[0], p1[0], p0[1], p1[1], p1[2], o.mat));
-    refs->push_back(emit_rect(rt::RECT_XY, p0[0], p1[0], p0[1], p1[1], p0[2], o.mat));
-    refs->push_back(emit_rect(rt::RECT_XZ, p0[0], p1[0], p0[2], p1[2], p1[1], o.mat));
-    refs->push_back(emit_rect(rt::RECT_XZ, p0[0], p1[0], p0[2], p1[2], p0[1], o.mat));
-    refs->push_back(emit_rect(rt::RECT_YZ, p0[1], p1[1], p0[2], p1[2], p1[0], o.mat));
-    refs->push_back(emit_rect(rt::RECT_YZ, p0[1], p1[1], p0[2], p1[2], p0[0], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_XY, p0[0], p1[0], p0[1], p1[1], p1[2], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_XY, p0[0], p1[0], p0[1], p1[1], p0[2], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_XZ, p0[0], p1[0], p0[2], p1[2], p1[1], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_XZ, p0[0], p1[0], p0[2], p1[2], p0[1], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_YZ, p0[1], p1[1], p0[2], p1[2], p1[0], o.mat));
+    refs->push_back(emit_rect(h, rt::RECT_YZ, p0[1], p1[1], p0[2], p1[2], p0[0], o.mat));
   }
 
   // Primitives of h in list order; lists and prisms are inlined.  handles (optional) receives, per reference, the
@@ -141,7 +143,7 @@ struct Flattener {
     if (depth > 64) return fail("hittable lists nested deeper than 64");
     const GHittable& o = g.hittables[h];
     if (is_prim(o.kind)) { refs->push_back(emit_prim(h)); if (handles) handles->push_back(h); return true; }
-    if (o.kind == H_RECT_PRISM) { emit_prism(o, refs); if (handles) handles->resize(refs->size(), -1); return true; }
+    if (o.kind == H_RECT_PRISM) { emit_prism(h, o, refs); if (handles) handles->resize(refs->size(), -1); return true; }
     // A list or another BvhNode inside a BVH (or inside a transformed / medium list): BvhNode::from_list takes any Hittable
     // (bvh.rs:85-93).  The closest hit over nested containers of plain primitives is the closest hit over the primitives, so the
     // inner container dissolves into the outer one's primitive set and ONE tree is built over all of them (a BVH is a culling
@@ -660,6 +662,13 @@ struct Flattener {
       m.axis = n.pad[0]; m.pad = 0;
     }
     build_motion_boxes();
+    // handle -> the rectangles emitted from it, in emission order (FlatScene::handle_rect_first / _id)
+    out.handle_rect_first.assign(g.hittables.size() + 1, 0);
+    for (int32_t h : rect_handle) out.handle_rect_first[(size_t)h + 1]++;
+    for (size_t h = 0; h < g.hittables.size(); ++h) out.handle_rect_first[h + 1] += out.handle_rect_first[h];
+    out.handle_rect_id.resize(rect_handle.size());
+    std::vector<int32_t> at(out.handle_rect_first.begin(), out.handle_rect_first.end() - 1);
+    for (size_t r = 0; r < rect_handle.size(); ++r) out.handle_rect_id[(size_t)at[(size_t)rect_handle[r]]++] = (int32_t)r;
     return true;
   }
 

@@ -17,6 +17,10 @@
 // it time-aware boxes, planes and slopes in `motion32` derived from the unions at the interval's two ends (refit_timed_bvh,
 // core/mover_box.hpp).  Only a BVH that also holds a GravitySphere is refused there.
 //
+// rtx_flat_set_rects (KIND_RECT: a0 a1 b0 b1 k; axis and mat stay) runs the static path as a triangle does: a rectangle's id is
+// its index in FlatScene::rects, a plain rectangle slot gets top_box32 like a triangle slot, and rtx_flat_rect_ids lists what
+// the flattener emitted from a handle (FlatScene::handle_rect_first / _id: a RectPrism is six rectangles per emission).
+//
 // A triangle's id is the ordinal of its first emission (FlatScene::triangle_id: a BVH stores copies in leaf order).  A sphere's
 // id is its index in FlatScene::spheres: the flattener emits a static sphere once per handle and neither moves nor copies it.
 // No index is ever derived from a value: every index an update uses comes from the caller's ids (checked against the shadow)
@@ -61,14 +65,17 @@ struct MeshShadow {
   std::vector<MemberGeom> members;               // in the order of member_local_box
   // a static sphere's id is its flat index, so there is no id table
   std::vector<int32_t> sph_first, sph_entry;     // flat sphere -> the PRIM / GROUP / BVH entries that refer to it
-  // 4 per top-level slot whose f32 box comes from ONE triangle or static sphere: the slot; the primitive's PRIM entry; 0 a plain
+  // 4 per top-level slot whose f32 box comes from ONE triangle, static sphere or rectangle: the slot; the primitive's PRIM entry; 0 a plain
   // slot (top_box32 and the slot record's box), 1 the boundary sphere of a medium without a chain (the slot record's box); for
   // a plain sphere slot whose next slot is such a medium, that medium's PRIM entry (the slot record says whether both hold the
-  // same sphere), else -1.  A plain triangle slot is (slot, entry, 0, -1).
+  // same sphere), else -1.  A plain triangle or rectangle slot is (slot, entry, 0, -1).
   std::vector<int32_t> slot_box;
   // a moving sphere's id is its flat index too (the flattener emits a mover once per handle)
   std::vector<int32_t> mov_first, mov_entry;     // flat moving sphere -> the PRIM / GROUP / BVH entries that refer to it
   std::vector<int32_t> mover_slot;               // 2 per plain top-level slot whose record is one mover: the slot, its PRIM entry
+  // a rectangle's id is its flat index as well (a rectangle is neither copied nor permuted); a plain rectangle slot sits in
+  // slot_box as (slot, entry, 0, -1), like a triangle's
+  std::vector<int32_t> rect_first, rect_entry;   // flat rectangle -> the PRIM / GROUP / BVH entries that refer to it
   std::string broken;                            // not empty: the arrays are not what the flattener emits; the message says how
 };
 
@@ -83,6 +90,7 @@ struct PrimKind {
 constexpr PrimKind KIND_TRIANGLE = {rt::PRIM_TRIANGLE, 9, "triangle", "triangle ids", "vertices", "d_vertices"};
 constexpr PrimKind KIND_SPHERE = {rt::PRIM_SPHERE, 4, "sphere", "static spheres", "spheres", "d_spheres"};
 constexpr PrimKind KIND_MOVING_SPHERE = {rt::PRIM_MOVING_SPHERE, 7, "moving sphere", "moving spheres", "movers", "d_movers"};
+constexpr PrimKind KIND_RECT = {rt::PRIM_RECT, 5, "rectangle", "rectangles", "rects", "d_rects"};
 
 // One update, resolved against the shadow: what to write and what to refit.
 struct UpdatePlan {
@@ -124,13 +132,17 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
     return false;
   };
   // (the same two passes give flat sphere -> entries)
-  const size_t n_sph = fs.spheres.size(), n_mov = fs.moving_spheres.size();
+  const size_t n_sph = fs.spheres.size(), n_mov = fs.moving_spheres.size(), n_rect = fs.rects.size();
   sh.tri_first.assign(n_tri + 1, 0);
   sh.sph_first.assign(n_sph + 1, 0);
   sh.mov_first.assign(n_mov + 1, 0);
+  sh.rect_first.assign(n_rect + 1, 0);
   for (int pass = 0; pass < 2; ++pass) {
-    std::vector<int32_t> at, sph_at, mov_at;
+    std::vector<int32_t> at, sph_at, mov_at, rect_at;
     if (pass == 1) {
+      for (size_t t = 0; t < n_rect; ++t) sh.rect_first[t + 1] += sh.rect_first[t];
+      sh.rect_entry.resize((size_t)sh.rect_first[n_rect]);
+      rect_at.assign(sh.rect_first.begin(), sh.rect_first.end() - 1);
       for (size_t t = 0; t < n_tri; ++t) sh.tri_first[t + 1] += sh.tri_first[t];
       sh.tri_entry.resize((size_t)sh.tri_first[n_tri]);
       at.assign(sh.tri_first.begin(), sh.tri_first.end() - 1);
@@ -155,6 +167,12 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
           if (t >= n_mov) return false;
           if (pass == 0) sh.mov_first[(size_t)t + 1]++;
           else sh.mov_entry[(size_t)mov_at[t]++] = (int32_t)k;
+          return true;
+        }
+        if (ty == rt::PRIM_RECT) {
+          if (t >= n_rect) return false;
+          if (pass == 0) sh.rect_first[(size_t)t + 1]++;
+          else sh.rect_entry[(size_t)rect_at[t]++] = (int32_t)k;
           return true;
         }
         if (ty != rt::PRIM_TRIANGLE) return true;
@@ -269,7 +287,7 @@ inline MeshShadow build_mesh_shadow(const FlatScene& fs, const UpdateShadow& us)
   };
   for (size_t k = 0; k < fs.top_level.size(); ++k) {
     const int32_t x = fs.top_level[k], m = medium_sphere(k);
-    if (prim_of(x, rt::PRIM_TRIANGLE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, -1});
+    if (prim_of(x, rt::PRIM_TRIANGLE) || prim_of(x, rt::PRIM_RECT)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, -1});
     else if (prim_of(x, rt::PRIM_SPHERE)) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, x, 0, medium_sphere(k + 1)});
     else if (m >= 0) sh.slot_box.insert(sh.slot_box.end(), {(int32_t)k, m, 1, -1});
     if (prim_of(x, rt::PRIM_MOVING_SPHERE)) sh.mover_slot.insert(sh.mover_slot.end(), {(int32_t)k, x});
@@ -291,7 +309,8 @@ inline bool check_prim_args(const PrimKind& K, const char* who, const void* scen
 inline bool check_prim_ids(const PrimKind& K, const char* who, const MeshShadow& sh, const int32_t* ids, int64_t n, std::string* err) {
   if (!sh.broken.empty()) { *err = std::string(who) + ": " + sh.broken; return false; }
   const int64_t n_ids = K.type == rt::PRIM_TRIANGLE ? (int64_t)sh.n_ids
-                        : K.type == rt::PRIM_SPHERE ? (int64_t)sh.sph_first.size() - 1 : (int64_t)sh.mov_first.size() - 1;
+                        : K.type == rt::PRIM_SPHERE ? (int64_t)sh.sph_first.size() - 1
+                        : K.type == rt::PRIM_RECT ? (int64_t)sh.rect_first.size() - 1 : (int64_t)sh.mov_first.size() - 1;
   for (int64_t i = 0; i < n; ++i)
     if (ids[i] < 0 || ids[i] >= n_ids) {
       *err = std::string(who) + ": ids[" + std::to_string(i) + "] is out of range (the scene has " + std::to_string(n_ids) + " " + K.count_phrase + ")";
@@ -363,6 +382,12 @@ inline rtx_status plan_prim_update(const PrimKind& K, const char* who, const Mes
       plan->pairs.push_back(ids[i]);
       plan->pairs.push_back((int32_t)i);
       for (int32_t q = sh.sph_first[(size_t)ids[i]]; q < sh.sph_first[(size_t)ids[i] + 1]; ++q) touched[(size_t)sh.sph_entry[(size_t)q]] = 1;
+    }
+  } else if (K.type == rt::PRIM_RECT) {  // ... of the rectangle
+    for (int64_t i = 0; i < n; ++i) {
+      plan->pairs.push_back(ids[i]);
+      plan->pairs.push_back((int32_t)i);
+      for (int32_t q = sh.rect_first[(size_t)ids[i]]; q < sh.rect_first[(size_t)ids[i] + 1]; ++q) touched[(size_t)sh.rect_entry[(size_t)q]] = 1;
     }
   } else {  // ... of the moving sphere
     for (int64_t i = 0; i < n; ++i) {
@@ -510,6 +535,7 @@ inline rtx_status flat_set_prims(const PrimKind& K, const char* who, FlatScene* 
     const double* v = values + (size_t)K.width * (size_t)plan.pairs[k + 1];
     if (K.type == rt::PRIM_TRIANGLE) rt::set_triangle_vertices(&fs->triangles[(size_t)plan.pairs[k]], v);
     else if (K.type == rt::PRIM_SPHERE) rt::set_sphere_values(&fs->spheres[(size_t)plan.pairs[k]], v);
+    else if (K.type == rt::PRIM_RECT) rt::set_rect_values(&fs->rects[(size_t)plan.pairs[k]], v);
     else rt::set_moving_sphere_values(&fs->moving_spheres[(size_t)plan.pairs[k]], v);
   }
   for (int32_t b : plan.bvhs) {
@@ -536,6 +562,10 @@ inline rtx_status flat_set_spheres(const char* who, FlatScene* fs, const int32_t
 inline rtx_status flat_set_moving_spheres(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* movers, std::string* err) {
   return flat_set_prims(KIND_MOVING_SPHERE, who, fs, ids, n, movers, err);
 }
+// rects: n x 5 doubles a0 a1 b0 b1 k; axis and mat stay.
+inline rtx_status flat_set_rects(const char* who, FlatScene* fs, const int32_t* ids, int64_t n, const double* rects, std::string* err) {
+  return flat_set_prims(KIND_RECT, who, fs, ids, n, rects, err);
+}
 
 // rtx_flat_triangle_ids / rtx_flat_sphere_ids / rtx_flat_moving_sphere_ids (`who`): the ids of the primitives of the kind below
 // `object`, in list order.  -1 with *err set.  (A primitive of another kind has no children and no id of this kind: skipped.  The
@@ -559,6 +589,38 @@ inline int64_t flat_prim_ids(const PrimKind& K, const char* who, const FlatScene
       if (id < 0) { *err = std::string(who) + ": this flat scene did not flatten the object (a " + K.noun + " below it has no id)"; return -1; }
       if (ids && count < cap) ids[count] = id;
       ++count;
+      continue;
+    }
+    for (size_t c = o.children.size(); c-- > 0;) todo.push_back({o.children[c], at.second + 1});
+  }
+  return count;
+}
+
+// rtx_flat_rect_ids: the ids of every rectangle the flattener emitted from the handles below `object`, handle by handle in list
+// order, a handle's rectangles in emission order (FlatScene::handle_rect_first / _id).  A rectangle handle owns one id however
+// often it is listed; a RectPrism owns six per emission, in the order of emit_prism, and is emitted once per place it is reached
+// from -- so a prism under two Translates gives twelve, from the world and from the prism's own handle alike.  Every id is
+// returned once, with the first reach of its handle: what rtx_*_set_rects takes (it refuses an id named twice).  -1 with *err set.
+inline int64_t flat_rect_ids(const char* who, const FlatScene& fs, const SceneGraph& g, int32_t object, int32_t* ids, int64_t cap, std::string* err) {
+  if (!g.valid_hittable(object)) { *err = std::string(who) + ": bad object handle"; return -1; }
+  int64_t count = 0;
+  std::vector<char> seen(g.hittables.size(), 0);
+  std::vector<std::pair<int32_t, int>> todo{{object, 0}};  // depth-first, children in list order
+  while (!todo.empty()) {
+    const std::pair<int32_t, int> at = todo.back();
+    todo.pop_back();
+    if (at.second > 80) { *err = std::string(who) + ": objects nested deeper than 80"; return -1; }
+    if ((size_t)at.first + 1 >= fs.handle_rect_first.size()) { *err = std::string(who) + ": the object was made after this flat scene was flattened"; return -1; }
+    const GHittable& o = g.hittables[(size_t)at.first];
+    if (o.kind == H_XY_RECT || o.kind == H_XZ_RECT || o.kind == H_YZ_RECT || o.kind == H_RECT_PRISM) {
+      const int32_t first = fs.handle_rect_first[(size_t)at.first], end = fs.handle_rect_first[(size_t)at.first + 1];
+      if (first == end) { *err = std::string(who) + ": this flat scene did not flatten the object (a rectangle below it has no id)"; return -1; }
+      if (seen[(size_t)at.first]) continue;
+      seen[(size_t)at.first] = 1;
+      for (int32_t k = first; k < end; ++k) {
+        if (ids && count < cap) ids[count] = fs.handle_rect_id[(size_t)k];
+        ++count;
+      }
       continue;
     }
     for (size_t c = o.children.size(); c-- > 0;) todo.push_back({o.children[c], at.second + 1});
