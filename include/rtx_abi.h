@@ -484,7 +484,8 @@ rtx_status rtx_progressive_create_ex(const rtx_scene* s, const RtxCamera* cam, c
  * reference's brute-force loop is unbounded there) and reports a miss.
  * RTX_EINVAL before any device call: a NULL scene, batch or hits; n < 0; n > 0 with a NULL origin or direction; a NaN t_min or
  * t_max_all -- the message names the field.  n = 0 is RTX_OK: nothing is launched, nothing written.  An all-NULL RtxRayHits
- * with n > 0 is legal (a timing run). */
+ * with n > 0 is legal (a timing run).  Since then an any-hit walk exists that returns what the medium's draw is a sample of:
+ * the section "occlusion queries" below (rtx_scene_occlusion*). */
 typedef struct RtxRayBatch {
   int64_t n;                 /* rays */
   const double* origin;      /* [n][3] */
@@ -513,6 +514,39 @@ rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, cons
  * be 16-byte aligned, every other column 8: RTX_EINVAL naming the column otherwise, before any device call.  A batch of more
  * than 2^30 rays goes out as several launches, none indexing past 2^31 rays. */
 rtx_status rtx_scene_cast_rays_device(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits, void* hip_stream);
+
+/* ---- occlusion queries: any-hit segment casts with exact fog depth ----------------------------------------------------- */
+/* An extension: is the segment [t_min, t_max_r] of ray r free, and how much fog lies on it -- shadows, ambient occlusion, line
+ * of sight, light baking through media.  The batch is the RtxRayBatch of a cast (seed and stream_step are not read); the
+ * result is ONE double per ray, tau[r]:
+ *   +inf  when some non-medium top-level entry has a primitive that prim_t accepts in [t_min, t_max_r] -- the test world_hit
+ *         applies, with t_max never narrowed.  The walk returns at the first such primitive (an any-hit walk: no near-first
+ *         order, no record); WHICH surface blocked is not reported, it would depend on the visiting order.
+ *   else  the sum over the ConstantMedium slots of the world list, in ascending slot order starting from +0.0, of each slot's
+ *         optical depth.  The boundary is asked exactly as world_hit asks it: two closest queries, rec1 over (-inf, inf) and rec2
+ *         from rec1.t + 0.0001.  t1 = max(rec1.t, t_min), t2 = min(rec2.t, t_max_r); the slot contributes nothing if a query
+ *         misses or t1 >= t2; t1 < 0 becomes 0; the depth is ((t2 - t1) * length(direction)) / (-neg_inv_density) with the
+ *         entry's f[0] as stored: one subtraction, one multiplication, one division.  Density 0 is stored as -inf and gives
+ *         depth +0.  An INFINITE density gives +inf, indistinguishable from a blocker.
+ *   NaN   on a scene with GravitySpheres for a ray whose time lies more than 10 s past the spheres' stored trajectory: a ray
+ *         that was not tested must not read as clear (rtx_scene_trace_rays' rule, not the cast's "miss").
+ * ConstantMedium::hit misses with probability exp(-density * distance_inside), so the transmittance of the segment is
+ * exp(-tau): the expectation of "the closest-hit cast reports no hit at all" over independent streams (stream_step = 1),
+ * the product over overlapping media included.  It is computed by the caller, never on the device.  On a scene without media,
+ * or whose media all have density 0, isinf(tau[r]) equals ids[r][0] == 1 of rtx_scene_cast_rays for every ray.
+ * No draw is made and only + - * / and sqrt are used: results are deterministic, independent of how a batch is split into
+ * calls, and equal to the CPU core's (core/occlusion.hpp: world_occlusion) bit for bit in f64 and in f32.  An f32 scene
+ * narrows the ray, t_min and t_max with the cast's conversions and widens tau.
+ * The query does not use the render workspace and may run beside a render, as the cast does.
+ * RTX_EINVAL before any device call and before the handle is read: a NULL scene, batch or tau; n < 0; n > 0 with a NULL origin
+ * or direction; a NaN t_min or t_max_all -- the message names the field.  n = 0 is RTX_OK: nothing is launched, nothing
+ * written. */
+/* Host pointers, blocking; staged in slices of RTX_CAST_HOST_SLICE rays (56 B in, 8 B out a ray). */
+rtx_status rtx_scene_occlusion(const rtx_scene* s, const RtxRayBatch* rays, double* tau);
+/* Device pointers, asynchronous on hip_stream: returns after the launch.  d_tau and every ray column must be 8-byte aligned:
+ * RTX_EINVAL naming the pointer otherwise, before any device call.  A batch of more than 2^30 rays goes out as several
+ * launches. */
+rtx_status rtx_scene_occlusion_device(const rtx_scene* s, const RtxRayBatch* rays, double* d_tau, void* hip_stream);
 
 /* ---- radiance queries: the estimator's radiance along a caller's rays on a resident scene ------------------------------ */
 /* An extension: what the path tracer gathers along the caller's own rays -- fisheye, equirectangular or orthographic cameras,

@@ -291,6 +291,8 @@ ABI = {
     "rtx_ray_batch_defaults": (None, [C.POINTER(RtxRayBatch)]),
     "rtx_scene_cast_rays": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits)]),
     "rtx_scene_cast_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), C.POINTER(RtxRayHits), _VP]),
+    "rtx_scene_occlusion": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), _VP]),
+    "rtx_scene_occlusion_device": (C.c_int32, [_VP, C.POINTER(RtxRayBatch), _VP, _VP]),
     "rtx_radiance_rays_defaults": (None, [C.POINTER(RtxRadianceRays)]),
     "rtx_scene_trace_rays": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_scene_trace_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
@@ -1039,6 +1041,23 @@ class Scene:
         current stream for it.  Every array is float64 and C-contiguous: origins and directions (n, 3), times and t_max (n,)."""
         return _cast_rays(self, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want)
 
+    def occlusion(self, origins, directions, times=None, t_max=None, *, t_min=0.001, t_max_all=float("inf"), stream=None):
+        """Any-hit casts of a batch of segments (rtx_scene_occlusion*): tau[r] is +inf when a surface lies on
+        [t_min, t_max[r]] of Ray(origins[r], directions[r], times[r]), else the summed optical depth of the ConstantMedia on
+        it (0 when the segment is clear), NaN for a ray past a GravitySphere scene's time limit -> Occlusion with .tau,
+        .blocked and .transmittance.  Deterministic: no stream is drawn from.  Arrays as in cast_rays: numpy goes through the
+        host entry; torch tensors on the GPU are passed by data_ptr() and the call is only ENQUEUED, on `stream` (a
+        torch.cuda.Stream or a raw hipStream_t) or, when None, on torch's current stream for that device."""
+        return _occlusion(self, origins, directions, times, t_max, t_min, t_max_all, stream)
+
+    def occlusion_between(self, a, b, eps=1e-6):
+        """occlusion of the segments from a[r] to b[r]: direction = b - a, t_max_all = 1 - eps -- the interval next-event
+        estimation gives its shadow ray (RT_NEE_SHADOW_EPS), so a surface AT b does not block."""
+        _ray_arrays([("a", a, 3), ("b", b, 3)])
+        if not 0.0 <= eps < 1.0:
+            raise ValueError("eps: expected 0 <= eps < 1, got %r" % (eps,))
+        return _occlusion(self, a, b - a, None, None, 0.001, 1.0 - eps, None)
+
     def trace_rays(self, origins, directions, times=None, *, spp=1, max_depth=50, background=(0.7, 0.8, 1.0), seed=1,
                    first_sample=0, first_ray=0, light_sampling=False, sumsq=False, out=None, sample_buffer_bytes=0,
                    want_stats=False):
@@ -1143,6 +1162,54 @@ def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed,
     else:
         _check(lib.rtx_scene_cast_rays(scene.ptr, C.byref(batch), C.byref(hits)))
     return RayHits(n, cols)
+
+
+class Occlusion:
+    """What Scene.occlusion returns: n and tau (n,) float64 -- a numpy array, or a torch tensor on the rays' device.
+    blocked = isinf(tau): a surface on the segment (or a medium of infinite density).  transmittance = exp(-tau), computed
+    here in the caller's array library, never on the scene's kernels: 0 where blocked, 1 where clear, NaN where tau is."""
+
+    def __init__(self, n, tau):
+        self.n, self.tau = n, tau
+
+    @property
+    def blocked(self):
+        return self.tau.isinf() if _is_torch(self.tau) else np.isinf(self.tau)
+
+    @property
+    def transmittance(self):
+        return (-self.tau).exp() if _is_torch(self.tau) else np.exp(-self.tau)
+
+
+def _occlusion(scene, origins, directions, times, t_max, t_min, t_max_all, stream):
+    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
+    if t_min != t_min:
+        raise ValueError("t_min: NaN")
+    if t_max_all != t_max_all:
+        raise ValueError("t_max_all: NaN")
+    if stream is not None and not on_device:
+        raise ValueError("stream: only for torch tensors on the GPU (numpy arrays go through the blocking host entry)")
+    batch = RtxRayBatch()
+    lib.rtx_ray_batch_defaults(C.byref(batch))
+    batch.n, batch.t_min, batch.t_max_all = n, t_min, t_max_all
+    if on_device:
+        import torch
+        ptr = lambda a: a.data_ptr() if a is not None and n else None
+        store = torch.empty((max(n, 1),), device=origins.device, dtype=torch.float64)  # (tau may not be NULL, even for n = 0)
+    else:
+        ptr = lambda a: a.ctypes.data if a is not None and n else None
+        store = np.empty((max(n, 1),), dtype=np.float64)
+    tau = store[:n]
+    batch.origin, batch.direction, batch.time, batch.t_max = ptr(origins), ptr(directions), ptr(times), ptr(t_max)
+    if on_device:
+        with torch.cuda.device(origins.device):
+            if stream is None:
+                stream = torch.cuda.current_stream(origins.device)
+            handle = getattr(stream, "cuda_stream", stream)
+            _check(lib.rtx_scene_occlusion_device(scene.ptr, C.byref(batch), _VP(store.data_ptr()), _VP(handle or None)))
+    else:
+        _check(lib.rtx_scene_occlusion(scene.ptr, C.byref(batch), _VP(store.ctypes.data)))
+    return Occlusion(n, tau)
 
 
 class RadianceSums:

@@ -41,6 +41,20 @@ rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* ra
   set_error(std::string(who) + ": " + bad);
   return RTX_EINVAL;
 }
+rtx_status check_occlusion(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const double* tau) {
+  const char* bad = nullptr;
+  if (!s) bad = "scene is NULL";
+  else if (!rays) bad = "rays is NULL";
+  else if (!tau) bad = "tau is NULL";
+  else if (rays->n < 0) bad = "rays->n < 0";
+  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
+  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
+  else if (rays->t_min != rays->t_min) bad = "rays->t_min is NaN";
+  else if (rays->t_max_all != rays->t_max_all) bad = "rays->t_max_all is NaN";
+  if (!bad) return RTX_OK;
+  set_error(std::string(who) + ": " + bad);
+  return RTX_EINVAL;
+}
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb) {
   const char* bad = nullptr;
   if (!s) bad = "scene is NULL";

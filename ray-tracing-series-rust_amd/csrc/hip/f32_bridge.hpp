@@ -55,6 +55,8 @@ struct RtxSceneOps {
   // rtx_scene_set_shading (shading_update.inc): n > 0 edits in host memory, already through the checks that need no scene; checks
   // the rest against the scene's shadow, then enqueues
   rtx_status (*set_shading)(void* device_scene, const RtxShadingEdit* edits, int64_t n, hipStream_t stream);
+  // occlusion queries (occlusion.inc: k_occlusion): device pointers, arguments already checked
+  rtx_status (*occlusion)(void* device_scene, const RtxRayBatch* rays, double* d_tau, hipStream_t stream);
 };
 
 // A stable radix sort of (64-bit key, 32-bit value) pairs on `stream` (lbvh.hip, which already carries rocPRIM's sort: neither

@@ -26,6 +26,7 @@
 #include "../../../include/rtx_abi.h"
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
+#include "../core/occlusion.hpp"
 #include "../core/item_order.hpp"
 #include "../core/karras.hpp"
 #include "../core/mover_box.hpp"
@@ -346,6 +347,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
 #include "cast_rays.inc"     // k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
 #include "trace_rays.inc"    // k_trace_rays: the estimator's radiance along a caller's rays (rtx_scene_trace_rays*)
+#include "occlusion.inc"     // k_occlusion: any-hit segment casts with exact fog depth (rtx_scene_occlusion*)
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
@@ -1392,6 +1394,41 @@ static rtx_status launch_cast_rays(DeviceScene* ds, const RtxRayBatch* b, const 
   return RTX_OK;
 }
 
+// Occlusion queries (occlusion.inc: k_occlusion): tau of the batch's rays.  Device pointers, asynchronous on stream; the
+// arguments were checked by the entry point (check_occlusion).  The device check, the stack check and the launch split are
+// launch_cast_rays'.
+static rtx_status launch_occlusion(DeviceScene* ds, const RtxRayBatch* b, double* d_tau, hipStream_t stream) {
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != ds->device) { set_error("occlusion: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
+  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("occlusion: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
+  const uint32_t feat = ds->view.features;
+  for (int64_t first = 0; first < b->n; first += CAST_LAUNCH_RAYS) {
+    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, b->n - first);
+    OcclusionArgs a;
+    a.origin = b->origin + 3 * first;
+    a.direction = b->direction + 3 * first;
+    a.time = b->time ? b->time + first : nullptr;
+    a.t_max = b->t_max ? b->t_max + first : nullptr;
+    a.t_min = b->t_min;
+    a.t_max_all = b->t_max_all;
+    a.time_limit = (feat & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
+    a.tau = d_tau + first;
+    const uint32_t grid = grid_size(n, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
+#define LAUNCH_OCCLUSION(FEAT)                                                                                                \
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_occlusion<FEAT>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, \
+                       ds->view, a, n)
+    // the presets of k_cast_rays, by its rule: instance trees, everything (GravitySpheres), any other world
+    if (feat & rt::F_INSTANCE) LAUNCH_OCCLUSION(P_INST);
+    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_OCCLUSION(P_ALL);
+    else LAUNCH_OCCLUSION(P_ANY);
+#undef LAUNCH_OCCLUSION
+    HIP_TRY(hipGetLastError());
+  }
+  return RTX_OK;
+}
+
 // One pass of a radiance query (trace_rays.inc: k_trace_rays) on `stream`: its work counter zeroed, then the persistent launch --
 // as many blocks as are resident, at most one wave per TRACE_CHUNK items (launch_nee's rule).
 static rtx_status launch_trace_rays_pass(const DeviceScene* ds, const rt::RenderParams& rp, const RadianceArgs& ra, bool nee,
@@ -1620,6 +1657,9 @@ static const RtxSceneOps scene_ops = {
     [](void* ds, const RtxShadingEdit* edits, int64_t n, hipStream_t stream) {
       return scene_set_shading_impl((DeviceScene*)ds, edits, n, stream);
     },
+    [](void* ds, const RtxRayBatch* rays, double* d_tau, hipStream_t stream) {
+      return launch_occlusion((DeviceScene*)ds, rays, d_tau, stream);
+    },
 };
 
 }  // namespace rtx
@@ -1735,6 +1775,50 @@ rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, cons
     if (hits->ids) HIP_TRY(hipMemcpy(hits->ids + 4 * first, d_ids, n * 16, hipMemcpyDeviceToHost));
   }
   HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxRayHits (a timing run) still returns after its launches
+  return RTX_OK;
+}
+
+// ---- occlusion queries.  The arguments are checked first (abi.cpp: check_occlusion), before any device call and before the
+// handle is read.
+rtx_status rtx_scene_occlusion_device(const rtx_scene* s, const RtxRayBatch* rays, double* d_tau, void* hip_stream) {
+  const rtx_status st = check_occlusion("rtx_scene_occlusion_device", s, rays, d_tau);
+  if (st != RTX_OK || rays->n == 0) return st;
+  const struct { const void* p; const char* name; } cols[] = {{rays->origin, "rays->origin"}, {rays->direction, "rays->direction"},
+                                                               {rays->time, "rays->time"},     {rays->t_max, "rays->t_max"},
+                                                               {d_tau, "d_tau"}};
+  for (const auto& c : cols)
+    if ((uintptr_t)c.p & 7) {
+      set_error(std::string("rtx_scene_occlusion_device: ") + c.name + " is not 8-byte aligned");
+      return RTX_EINVAL;
+    }
+  return s->ops->occlusion(s->device_scene, rays, d_tau, (hipStream_t)hip_stream);
+}
+
+// Host pointers: slices of RTX_CAST_HOST_SLICE rays staged through device buffers (in: 56 B a ray, out: 8 B), one after the
+// other on the null stream.
+rtx_status rtx_scene_occlusion(const rtx_scene* s, const RtxRayBatch* rays, double* tau) {
+  rtx_status st = check_occlusion("rtx_scene_occlusion", s, rays, tau);
+  if (st != RTX_OK || rays->n == 0) return st;
+  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_CAST_HOST_SLICE);
+  DeviceBuffer<double> d_o, d_d, d_time, d_tmax, d_tau;
+  HIP_TRY(d_o.alloc(cap * 24));
+  HIP_TRY(d_d.alloc(cap * 24));
+  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
+  if (rays->t_max) HIP_TRY(d_tmax.alloc(cap * 8));
+  HIP_TRY(d_tau.alloc(cap * 8));
+  for (int64_t first = 0; first < rays->n; first += RTX_CAST_HOST_SLICE) {
+    const size_t n = (size_t)std::min<int64_t>(RTX_CAST_HOST_SLICE, rays->n - first);
+    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
+    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
+    if (rays->t_max) HIP_TRY(hipMemcpy(d_tmax, rays->t_max + first, n * 8, hipMemcpyHostToDevice));
+    RtxRayBatch b = *rays;
+    b.n = (int64_t)n;
+    b.origin = d_o; b.direction = d_d; b.time = d_time; b.t_max = d_tmax;
+    if ((st = s->ops->occlusion(s->device_scene, &b, d_tau, (hipStream_t) nullptr)) != RTX_OK) return st;
+    // (a blocking copy on the null stream waits for the launch)
+    HIP_TRY(hipMemcpy(tau + first, d_tau, n * 8, hipMemcpyDeviceToHost));
+  }
   return RTX_OK;
 }
 
