@@ -76,6 +76,7 @@ struct VoteTop {
 // RTX_TRACE_KERNEL: the kernel family a render is forced to (none: choose_trace_kernel decides).
 enum class ForcedKernel { none, simple, vote, world, wavefront };
 
+constexpr uint32_t RETIRE_UNSET = 0xFFFFFFFFu;
 // Every RTX_* switch of the launcher, read once per rtx_scene_upload by read_switches (DESIGN section 4 lists them).  A numeric
 // switch outside its range keeps the default; an on/off switch is off when set to anything atoi reads as 0.
 struct TraceSwitches {
@@ -89,6 +90,8 @@ struct TraceSwitches {
   uint32_t item_group = 0;       // RTX_ITEM_GROUP [1, 2^30]: pixels per group of a pass's item order (core/item_order.hpp); 0: WalkTuning's
   uint32_t world_threshold = 8;  // RTX_WORLD_THRESHOLD [0, 64]: k_trace_world's walk steps go first while this many lanes walk (0: majority)
   uint32_t walk_threshold = 0, regen_min = 0, leaf_weight = 0;  // RTX_WALK_THRESHOLD / _REGEN_MIN / _LEAF_WEIGHT [1, 64]; 0: WalkTuning's
+  // RTX_RETIRE_DONE [0, 64] / RTX_RETIRE_MIN [0, 64]: k_trace_lds's miss-retire rule (trace_lds.inc), D and M; RETIRE_UNSET: WalkTuning's
+  uint32_t retire_done = RETIRE_UNSET, retire_min = RETIRE_UNSET;
   // wavefront integrator: RTX_WF_PATHS [256, 2^27] path slots; RTX_WF_REFILL [1, 64] free lanes a wave waits for before it takes new
   // slots; RTX_WF_CHECK [1, 4096] iterations between two looks at the counters; RTX_WF_OCC [4, 6] blocks per CU k_wf_trace is
   // compiled for (mesh room); RTX_WF_VERBOSE set at all
@@ -169,6 +172,13 @@ struct WalkTuning {
   uint32_t regen_min = 1;         // wide k_trace_vote: lanes that must be waiting before the wave regenerates
   uint32_t leaf_weight = 3;       // node lanes x weight >= leaf lanes -> node step
   bool single_leaf = false;       // every BVH leaf holds one primitive (k_trace_lds tests it without a loop)
+  // k_trace_lds with a ring, miss retire (trace_lds.inc): a round hands its finished misses on once more than
+  // retire_done (D) walks of it are complete and at least retire_min (M) of the complete ones are misses.  D = 0: off, a round
+  // ends as a whole.  With the rule on a round may end later: retire_walk_threshold replaces walk_threshold for those launches.
+  // Measured on C2 (short runs, Msamples/s; profiles/miss_retire/): off 8650, parent 8661 - 8712; threshold 12 with D / M
+  // 40 / 12, 16, 20 -> 8694, 8792, 8798, 44 / 16, 20 -> 8762, 8778, 48 / 20 -> 8753, D >= 52 never fires; D / M 44 / 18 with
+  // threshold 6, 8, 10, 14, 16 -> 8815, 8845, 8858, 8733, 8668; at 8 - 11 every D of 40, 44 and M of 16, 20 lies within 8840 - 8867.
+  uint32_t retire_done = 44, retire_min = 18, retire_walk_threshold = 10;
   // Pixels per group of a pass's item order (core/item_order.hpp), per kernel family; ITEM_GROUP_MAX: one group, a wave's 64
   // consecutive items are a row strip of one sample.  RTX_ITEM_GROUP overrides all five.  (profiles/item_order/)
   // Measured (short runs, two each): k_trace_lds on C2 8304 in the row-strip order, 8699 / 8712 / 8689 / 8652 / 8592 / 8520 /
@@ -425,6 +435,7 @@ static TraceSwitches read_switches() {
   sw.item_group = num("RTX_ITEM_GROUP", 1, (int)rt::ITEM_GROUP_MAX, 0);
   sw.world_threshold = num("RTX_WORLD_THRESHOLD", 0, 64, sw.world_threshold);
   sw.walk_threshold = num("RTX_WALK_THRESHOLD", 1, 64, 0); sw.regen_min = num("RTX_REGEN_MIN", 1, 64, 0); sw.leaf_weight = num("RTX_LEAF_WEIGHT", 1, 64, 0);
+  sw.retire_done = num("RTX_RETIRE_DONE", 0, 64, RETIRE_UNSET); sw.retire_min = num("RTX_RETIRE_MIN", 0, 64, RETIRE_UNSET);
   const char* wp = getenv("RTX_WF_PATHS");
   if (wp && atol(wp) >= 256 && atol(wp) <= (1l << 27)) sw.wf_paths = (uint32_t)atol(wp);
   sw.wf_refill = num("RTX_WF_REFILL", 1, 64, sw.wf_refill); sw.wf_check = num("RTX_WF_CHECK", 1, 4096, sw.wf_check);
@@ -886,11 +897,14 @@ static rtx_status launch_lds(DeviceScene* ds, const PassArgs& a, const RtxCamera
   const LdsKernelLayout L = ldsk_layout(f.levels, f.ring_cap, f.dims);
   const uint32_t grid = grid_size(a.total, LDSK_BLOCK, (uint64_t)ds->n_cu);
   const WalkTuning& wk = ds->walk;
+  // the tuning word of trace_lds.inc: threshold, "one primitive per leaf", D (off travels as 127: no wave has that many walkers), M
+  const uint32_t tuning = ((ring && wk.retire_done) ? wk.retire_walk_threshold : wk.walk_threshold) | (wk.single_leaf ? 0x100u : 0u) |
+                          ((wk.retire_done ? wk.retire_done : 127u) << 16) | (wk.retire_min << 24);
 #define LAUNCH_LDS2(FEAT, RINGF, MOTIONF)                                                                               \
   with_map(a, [&](auto map) {                                                                                           \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_lds<FEAT, RINGF, MOTIONF, decltype(map)>), dim3(grid), dim3(LDSK_BLOCK), L.total, \
                        a.stream, ds->view, a.rp, map, a.s_begin, a.total, a.samples, a.work_counter, wk.leaf_weight, \
-                       wk.walk_threshold | (wk.single_leaf ? 0x100u : 0u), ds->sw.chunk, f.ring_cap, f.levels, f.dims,  \
+                       tuning, ds->sw.chunk, f.ring_cap, f.levels, f.dims,  \
                        m_t0, m_inv, p.mv_common ? 1u : 0u, (rt::real)p.mv_t0, (rt::real)p.mv_t1);                        \
   })
 #define LAUNCH_LDS(FEAT, MOTIONF) do { if (ring) { LAUNCH_LDS2(FEAT, true, MOTIONF); } else { LAUNCH_LDS2(FEAT, false, MOTIONF); } } while (0)
@@ -1053,7 +1067,9 @@ static void plan_walk(DeviceScene* ds, const LeafScan& leaves) {
   if (sw.regen_min) w.regen_min = sw.regen_min;
   if (sw.leaf_weight) w.leaf_weight = sw.leaf_weight;
   if (!sw.single_leaf) w.single_leaf = false;
-  if (sw.walk_threshold) w.walk_threshold = sw.walk_threshold;
+  if (sw.walk_threshold) w.walk_threshold = w.retire_walk_threshold = sw.walk_threshold;
+  if (sw.retire_done != RETIRE_UNSET) w.retire_done = sw.retire_done;
+  if (sw.retire_min != RETIRE_UNSET) w.retire_min = sw.retire_min;
   if (sw.item_group) w.item_group_lds = w.item_group_vote = w.item_group_world = w.item_group_wavefront = w.item_group_simple = sw.item_group;
 }
 

@@ -79,9 +79,14 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
                                                           uint32_t stack_levels, LdsSceneDims dims, rt::real motion_t0, rt::real motion_inv_dt,
                                                           uint32_t mv_common, rt::real mv_t0, rt::real mv_t1) {
   static_assert(!MOTION || (F & rt::F_MOVING_SPHERE), "time-aware boxes only make sense with moving spheres");
-  // the launcher packs two small numbers into one kernel argument: bits 0-7 the walk threshold, bit 8 "every leaf holds one primitive"
+  // the launcher packs four small numbers into one kernel argument: bits 0-7 the walk threshold, bit 8 "every leaf holds one
+  // primitive", bits 16-22 and 24-30 the miss-retire rule's D and M (below, at the vote).  With a ring the word stays packed in
+  // its ONE scalar register and is unpacked where a number is used, from a copy the compiler cannot see through (as `entry`
+  // below): unpacked here, threshold, D and M each held a register for the whole kernel and pushed five other values into lanes
+  // of the spill register, read back once per bounce.
   const bool single_leaf = (walk_threshold & 0x100u) != 0u;
-  walk_threshold &= 0xFFu;
+  const uint32_t tuning = walk_threshold;
+  if (!RING) walk_threshold &= 0xFFu;
   constexpr bool UNI = (F & rt::F_MOVING_SPHERE) != 0;               // static spheres as moving spheres that stand still (see the copy below)
   constexpr uint32_t FL = UNI ? (F & ~rt::F_SPHERE) : F;             // what the leaf tests and the HitRecord are compiled for
   static_assert(MOTION <= 4u, "0: no slopes, 1: all axes, 2 + a: axis a only");
@@ -274,7 +279,10 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
       }
     }
     // ---- walk: cost-weighted node/leaf vote with carry-over of stragglers
-    const uint32_t threshold = (queue_empty && ring_n == 0u) ? 1u : walk_threshold;
+    const bool no_refill = queue_empty && ring_n == 0u;  // wave-uniform
+    uint32_t tn = tuning;
+    if (RING) asm volatile("" : "+s"(tn));
+    const uint32_t threshold = no_refill ? 1u : (RING ? (tn & 0xFFu) : walk_threshold);
     auto node_step = [&]() {
       // the child that is near along the node's split axis is tested and queued first; which block that is is decided in
       // the ADDRESS (block 1 starts 40 bytes after block 0), not by selecting results afterwards
@@ -339,12 +347,26 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
     // The vote closes the loop instead of opening it: the ballots are convergent operations, which the compiler will not duplicate
     // to rotate the loop itself, and an exit test at the head of a loop with divergent regions inside becomes a "stop" lane mask
     // carried to the latch.  At the latch the wave-uniform compare is the back edge's own condition (s_cmp + s_cbranch_scc).
+    //
+    // Miss retire (RING only; DESIGN.md 4, item 17).  A round ends when fewer than `threshold` lanes still walk, and until then a
+    // lane whose walk found nothing waits for a shading block of which it needs five operations and a store.  With D != 0 the
+    // loop's exit compare gets a per-round right-hand side, max(threshold, walkers at this entry - D): the walkers are
+    // wave-uniform already, so a step gets no new ballot.  When the loop leaves above `threshold` the round is not over: only
+    // the finished MISSES pass the shading block (its miss branch), store and go inactive, the next outer iteration hands them
+    // rays from the ring and votes on with a new right-hand side; finished hits wait as they are, in the state they have
+    // between the loop's exit and the shading block anyway.  One ballot at that exit skips the pass when fewer than M lanes
+    // would retire: the misses wait too, and the next exit point lies D lanes further.  Off when no refill is possible
+    // (`no_refill`: the threshold is 1 then and a round ends as a whole) and for D = 0.
+    bool round_over = true;
     {
       // cur == LDSK_DONE whenever a lane is not in a walk, so the item alone tells the lane's state
       bool is_node = cur >= 0;
       bool is_leaf = cur < -1;
       uint32_t n_node = (uint32_t)__popcll(wave_ballot(is_node)), n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
-      if (n_node + n_leaf >= threshold) {
+      // (the launcher sends "off" as D = 127: no wave has that many walkers, and neither has one that cannot refill)
+      int32_t exit_at = (int32_t)threshold;
+      if (RING) exit_at = max(exit_at, (int32_t)(n_node + n_leaf) - (int32_t)(no_refill ? 127u : ((tn >> 16) & 0x7Fu)));
+      if (n_node + n_leaf >= (uint32_t)exit_at) {
         do {
           if (n_node * leaf_weight >= n_leaf) {
             if (is_node) node_step();
@@ -368,11 +390,19 @@ __global__ __launch_bounds__(LDSK_BLOCK) void k_trace_lds(rt::SceneView sv, rt::
           is_leaf = cur < -1;
           n_node = (uint32_t)__popcll(wave_ballot(is_node));
           n_leaf = (uint32_t)__popcll(wave_ballot(is_leaf));
-        } while (n_node + n_leaf >= threshold);
+        } while (n_node + n_leaf >= (uint32_t)exit_at);
       }
+      if (RING) round_over = n_node + n_leaf < threshold;
     }
-    // ---- shade the lanes whose walk is complete
-    if (midwalk && cur == LDSK_DONE) {
+    // ---- shade the lanes whose walk is complete; in a round that is not over, the misses among them (if there are M)
+    bool shade = midwalk && cur == LDSK_DONE;
+    if (!round_over) {
+      shade = shade && best.ref == LDSK_NO_REF;
+      uint32_t tm = tuning;
+      asm volatile("" : "+s"(tm));
+      if ((uint32_t)__popcll(wave_ballot(shade)) < (tm >> 24)) shade = false;
+    }
+    if (shade) {
       midwalk = false;
       rt::HitRecord rec;
       const bool hit = best.ref != LDSK_NO_REF;
