@@ -1064,6 +1064,36 @@ int oracle_o1_hit(const void* graph_ptr, int32_t handle, const double o[3], cons
   out[7] = rec.u; out[8] = rec.v; out[9] = rec.front_face ? 1.0 : 0.0;
   return 1;
 }
+// Material::scatter of one material of a graph on a given ray and hit record, on the stream of rng_seed:
+// out = {direction xyz, attenuation xyz, draws consumed}.  1: scattered, 0: not (out[0..6) then hold what scatter left there:
+// a Metal's direction, zeros otherwise), -1: bad handle.  The draws are counted by stepping a copy of the stream to the state
+// scatter left (-1 if 4096 steps do not reach it).
+int oracle_o1_scatter(const void* graph_ptr, int32_t material_handle, const double o[3], const double d[3], double time,
+                      const double p[3], const double normal[3], int32_t front_face, double u, double v, uint64_t rng_seed,
+                      double out[7]) {
+  const rtx::SceneGraph* g = (const rtx::SceneGraph*)graph_ptr;
+  if (!g || !g->valid_material(material_handle)) return -1;
+  World wb;
+  wb.g = g;
+  wb.textures.resize(g->textures.size());
+  wb.materials.resize(g->materials.size());
+  const Material* m = wb.material(material_handle);
+  HitRecord rec;
+  rec.p = Point3(p[0], p[1], p[2]);
+  rec.normal = Vec3(normal[0], normal[1], normal[2]);
+  rec.u = u; rec.v = v; rec.front_face = front_face != 0; rec.mat_ptr = m;
+  Rng rng = rt::rng_for_sample(rng_seed, 0, 0);
+  Rng walk = rng;
+  Ray scattered(Point3(0, 0, 0), Vec3(0, 0, 0), 0.0);
+  Color attenuation(0, 0, 0);
+  const bool did = m->scatter(Ray(Point3(o[0], o[1], o[2]), Vec3(d[0], d[1], d[2]), time), rec, rng, &scattered, &attenuation);
+  out[0] = scattered.direction.x(); out[1] = scattered.direction.y(); out[2] = scattered.direction.z();
+  out[3] = attenuation.x(); out[4] = attenuation.y(); out[5] = attenuation.z();
+  int draws = 0;
+  while ((walk.s0 != rng.s0 || walk.s1 != rng.s1) && draws < 4096) { rt::rng_next_u64(walk); ++draws; }
+  out[6] = (walk.s0 == rng.s0 && walk.s1 == rng.s1) ? (double)draws : -1.0;
+  return did ? 1 : 0;
+}
 // Texture::value of one texture of a graph (recursing as texture.rs does, to any depth): out = the colour.  -1: bad handle.
 int oracle_o1_texture_value(const void* graph_ptr, int32_t texture_handle, double u, double v, const double p[3], double out[3]) {
   const rtx::SceneGraph* g = (const rtx::SceneGraph*)graph_ptr;

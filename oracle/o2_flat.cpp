@@ -184,6 +184,34 @@ int oracle_core_world_hit_mat(const void* flat, const double o[3], const double 
   *mat = (int32_t)rec.mat;
   return 1;
 }
+// material_scatter of one material record of a flattened scene on a given ray and hit record, on the stream of rng_seed:
+// out = {direction xyz, attenuation xyz, draws consumed} as oracle_o1_scatter counts them.  1: scattered, 0: not, -1: no such
+// record.
+int oracle_core_scatter(const void* flat, int32_t material_index, const double o[3], const double d[3], double time,
+                        const double p[3], const double normal[3], int32_t front_face, double u, double v, uint64_t rng_seed,
+                        double out[7]) {
+  if (!flat) return -1;
+  const rtx::FlatScene& fs = *(const rtx::FlatScene*)flat;
+  if (material_index < 0 || (size_t)material_index >= fs.materials.size()) return -1;
+  const rt::SceneView sv = fs.view();
+  rt::HitRecord rec;
+  memset(&rec, 0, sizeof(rec));
+  rec.p = rt::v3(p[0], p[1], p[2]);
+  rec.normal = rt::v3(normal[0], normal[1], normal[2]);
+  rec.u = u; rec.v = v; rec.front_face = front_face != 0; rec.mat = material_index;
+  rt::Rng rng = rt::rng_for_sample(rng_seed, 0, 0);
+  rt::Rng walk = rng;
+  rt::Ray scattered = rt::make_ray(rt::v3(0, 0, 0), rt::v3(0, 0, 0), 0.0);
+  rt::Color attenuation = rt::v3(0, 0, 0);
+  const rt::Ray r_in = rt::make_ray(rt::v3(o[0], o[1], o[2]), rt::v3(d[0], d[1], d[2]), time);
+  const bool did = rt::material_scatter<rt::F_ALL, false>(sv, fs.materials[(size_t)material_index], r_in, rec, rng, &scattered, &attenuation, nullptr);
+  out[0] = scattered.direction.x; out[1] = scattered.direction.y; out[2] = scattered.direction.z;
+  out[3] = attenuation.x; out[4] = attenuation.y; out[5] = attenuation.z;
+  int draws = 0;
+  while ((walk.s0 != rng.s0 || walk.s1 != rng.s1) && draws < 4096) { rt::rng_next_u64(walk); ++draws; }
+  out[6] = (walk.s0 == rng.s0 && walk.s1 == rng.s1) ? (double)draws : -1.0;
+  return did ? 1 : 0;
+}
 // texture_value of one texture record of a flattened scene: out = the colour.  -1: no such record.
 int oracle_core_texture_value(const void* flat, int32_t texture_index, double u, double v, const double p[3], double out[3]) {
   if (!flat) return -1;

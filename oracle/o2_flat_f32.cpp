@@ -204,6 +204,35 @@ int oracle_core32_texture_value(const void* flat, int32_t texture_index, double 
   return 1;
 }
 
+// material_scatter of one material record of the narrowed scene, ray and record narrowed: out = {direction xyz, attenuation
+// xyz} widened, draws consumed (oracle_core_scatter's conventions).
+int oracle_core32_scatter(const void* flat, int32_t material_index, const double o[3], const double d[3], double time,
+                          const double p[3], const double normal[3], int32_t front_face, double u, double v, uint64_t rng_seed,
+                          double out[7]) {
+  if (!flat) return -1;
+  rtx::FlatScene fs;
+  if (!narrow_scene(flat, &fs)) return -1;
+  if (material_index < 0 || (size_t)material_index >= fs.materials.size()) return -1;
+  const rt::SceneView sv = fs.view();
+  rt::HitRecord rec;
+  memset(&rec, 0, sizeof(rec));
+  rec.p = rt::v3((float)p[0], (float)p[1], (float)p[2]);
+  rec.normal = rt::v3((float)normal[0], (float)normal[1], (float)normal[2]);
+  rec.u = (float)u; rec.v = (float)v; rec.front_face = front_face != 0; rec.mat = material_index;
+  rt::Rng rng = rt::rng_for_sample(rng_seed, 0, 0);
+  rt::Rng walk = rng;
+  rt::Ray scattered = rt::make_ray(rt::v3(0, 0, 0), rt::v3(0, 0, 0), 0.0f);
+  rt::Color attenuation = rt::v3(0, 0, 0);
+  const rt::Ray r_in = rt::make_ray(rt::v3((float)o[0], (float)o[1], (float)o[2]), rt::v3((float)d[0], (float)d[1], (float)d[2]), (float)time);
+  const bool did = rt::material_scatter<rt::F_ALL, false>(sv, fs.materials[(size_t)material_index], r_in, rec, rng, &scattered, &attenuation, nullptr);
+  out[0] = scattered.direction.x; out[1] = scattered.direction.y; out[2] = scattered.direction.z;
+  out[3] = attenuation.x; out[4] = attenuation.y; out[5] = attenuation.z;
+  int draws = 0;
+  while ((walk.s0 != rng.s0 || walk.s1 != rng.s1) && draws < 4096) { rt::rng_next_u64(walk); ++draws; }
+  out[6] = (walk.s0 == rng.s0 && walk.s1 == rng.s1) ? (double)draws : -1.0;
+  return did ? 1 : 0;
+}
+
 // path_bounce_begin on a ray given as six doubles (narrowed) with `depth` bounces left: 1 when the path ends there.
 int oracle_core32_path_ends(const double o[3], const double d[3], int32_t depth) {
   rt::PathState ps;

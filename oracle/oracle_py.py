@@ -119,6 +119,9 @@ def load():
     for name in ("oracle_o1_texture_value", "oracle_core_texture_value", "oracle_core32_texture_value"):
         getattr(lib, name).restype = C.c_int
         getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, _D, _D]
+    for name in ("oracle_o1_scatter", "oracle_core_scatter", "oracle_core32_scatter"):
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_int32, _D, _D, C.c_double, _D, _D, C.c_int32, C.c_double, C.c_double, C.c_uint64, _D]
     lib.oracle_flat_array.restype = C.c_void_p
     lib.oracle_flat_array.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
@@ -416,6 +419,28 @@ def core_texture_value(flat_arrays_ptr, texture_index, u, v, p, f32=False):
     """texture_value of the product's core over a flat scene's texture record (a graph texture handle is its index); f32: the
     float build over the narrowed scene, (u, v, p) narrowed, the float colour widened."""
     return _texture_value("oracle_core32_texture_value" if f32 else "oracle_core_texture_value", flat_arrays_ptr, texture_index, u, v, p)
+
+
+def _scatter(name, ptr, mat, o, d, p, normal, front_face, time, u, v, rng_seed):
+    out = (C.c_double * 7)()
+    rc = getattr(load(), name)(ptr, int(mat), _d3(o), _d3(d), float(time), _d3(p), _d3(normal), 1 if front_face else 0, float(u), float(v),
+                               int(rng_seed), out)
+    if rc < 0:
+        raise ValueError("%s: no material %r" % (name, mat))
+    return {"scattered": rc == 1, "direction": tuple(out[0:3]), "attenuation": tuple(out[3:6]), "draws": int(out[6])}
+
+
+def o1_scatter(graph_ptr, material_handle, o, d, p, normal, front_face, time=0.0, u=0.0, v=0.0, rng_seed=1):
+    """The literal Material::scatter of a graph's material on the ray (o, d, time) and the hit record (p, normal, front_face, u,
+    v), on the stream of rng_seed -> scattered, direction, attenuation (meaningful when scattered) and the draws consumed."""
+    return _scatter("oracle_o1_scatter", graph_ptr, material_handle, o, d, p, normal, front_face, time, u, v, rng_seed)
+
+
+def core_scatter(flat_arrays_ptr, material_index, o, d, p, normal, front_face, time=0.0, u=0.0, v=0.0, rng_seed=1, f32=False):
+    """material_scatter of the product's core on a flat scene's material record (a graph material handle is its index); f32: the
+    float build over the narrowed scene, ray and record narrowed, the results widened."""
+    return _scatter("oracle_core32_scatter" if f32 else "oracle_core_scatter", flat_arrays_ptr, material_index, o, d, p, normal, front_face,
+                    time, u, v, rng_seed)
 
 
 def audit_motion(flat_arrays_ptr, n_times=16):

@@ -179,9 +179,56 @@ static int check_textures() {
   return 0;
 }
 
+// The scatter probes on every material kind: a fuzzy and a clamped metal, glass on both faces and past the critical angle, a
+// Lambertian, a light and the phase material of a medium; unit, short and long incident directions; several streams.  O1 and
+// the f64 core must agree bit for bit on the verdict, the direction, the draws consumed and (where it scattered) the
+// attenuation; the float core runs beside them.
+static int check_scatter() {
+  rtx::SceneGraph g(1);
+  const double grey[3] = {0.5, 0.25, 1.0}, c[3] = {0.0, 0.0, 0.0};
+  const int32_t mats[] = {g.lambertian(g.solid_color(grey)), g.metal(grey, 0.0), g.metal(grey, 0.3), g.metal(grey, 1.7), g.metal(grey, -0.5),
+                          g.dielectric(1.5), g.dielectric(1.0), g.dielectric(1.0 / 1.5), g.diffuse_light(g.solid_color(grey))};
+  const int32_t world = g.list_new();
+  for (int32_t m : mats) g.list_add(world, g.sphere(c, 1.0, m));
+  const int32_t fog = g.constant_medium(grey, 0.5, g.sphere(c, 2.0, mats[0]));
+  g.list_add(world, fog);
+  if (world < 0 || fog < 0) { fprintf(stderr, "scatter: construction failed: %s\n", g.error.c_str()); return 1; }
+  rtx::BuildOptions bo;
+  rtx::FlatScene fs;
+  std::string err;
+  if (!rtx::flatten_scene(g, world, bo, &fs, &err)) { fprintf(stderr, "scatter: flatten: %s\n", err.c_str()); return 1; }
+  const double dirs[][3] = {{0.0, -1.0, 0.0}, {0.6, -0.8, 0.0}, {0.0007, -0.0001, 0.0002}, {6.9, -0.7, 0.4}, {0.999, -0.04, 0.0}};
+  const double o[3] = {0.0, 1.0, 0.0}, n[3] = {0.0, 1.0, 0.0};
+  int count = 0;
+  for (int32_t m = 0; m < (int32_t)g.materials.size(); ++m)
+    for (const auto& d : dirs)
+      for (int ff = 0; ff < 2; ++ff)
+        for (uint64_t seed = 1; seed <= 3; ++seed) {
+          double a[7], b[7], f[7];
+          const int ra = oracle_o1_scatter(&g, m, o, d, 0.25, c, n, ff, 0.5, 0.5, seed, a);
+          const int rb = oracle_core_scatter(&fs, m, o, d, 0.25, c, n, ff, 0.5, 0.5, seed, b);
+          const int rf = oracle_core32_scatter(&fs, m, o, d, 0.25, c, n, ff, 0.5, 0.5, seed, f);
+          if (ra < 0 || rb < 0 || rf < 0) { fprintf(stderr, "scatter: a probe failed on material %d\n", m); return 1; }
+          if (ra != rb || memcmp(a, b, 3 * sizeof(double)) != 0 || a[6] != b[6] || a[6] < 0.0 || (ra == 1 && memcmp(a + 3, b + 3, 3 * sizeof(double)) != 0)) {
+            fprintf(stderr, "scatter: O1 and the core differ on material %d\n", m);
+            return 1;
+          }
+          ++count;
+        }
+  double out[7];
+  if (oracle_o1_scatter(&g, -1, o, dirs[0], 0.0, c, n, 1, 0, 0, 1, out) != -1 ||
+      oracle_core_scatter(&fs, (int32_t)fs.materials.size(), o, dirs[0], 0.0, c, n, 1, 0, 0, 1, out) != -1) {
+    fprintf(stderr, "scatter: a bad index was not refused\n");
+    return 1;
+  }
+  printf("scatter: %d probes, O1 == core\n", count);
+  return 0;
+}
+
 int main() {
   int bad = 0;
   bad += check_textures();
+  bad += check_scatter();
   for (int32_t sid : {2, 5, 6, 7, 11}) bad += check_features(sid);  // image texture; box media; Book-2; moving spheres + lens; mesh
   const int32_t scenes[] = {0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12, 13, 100, 101};
   for (int32_t sid : scenes) bad += check_scene(sid, 40, sid == 4 || sid == 5 || sid == 6 || sid == 12 ? 1.0 : 1.6, 2, false);

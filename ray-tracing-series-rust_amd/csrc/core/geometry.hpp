@@ -584,6 +584,22 @@ RT_HD void instance_walk(const SceneView& sv, int32_t root, const Ray& r, real t
 // A ConstantMedium asks its boundary twice (rec1 over (-inf, inf), rec2 from rec1.t + 0.0001),
 // then draws one uniform from the path's stream -- inside the intersection, exactly where
 // the reference draws it (hit.rs:969).
+// Where the second query starts: rec1.t + 0.0001 (hit.rs:962).  A float absorbs the 0.0001 from |t| = 2048 on -- a direction of
+// length 0.001 nine units from the boundary, or a boundary 2048 units away -- and the second query then finds the ENTRY face
+// again (the range tests accept t == t_min): t1 >= t2 and the medium is never there.  The float build steps to the next float
+// instead; the double build is the reference's expression.
+RT_HD real medium_second_t_min(real t) {
+#if defined(RT_F32)
+  const real q = t + real(0.0001);
+  if (q > t || !(rt_fabs(t) < RT_INFINITY)) return q;
+  union { float f; uint32_t u; } c;
+  c.f = t;
+  c.u = t > real(0.0) ? c.u + 1u : c.u - 1u;  // (|t| >= 2048 here: never a zero)
+  return c.f;
+#else
+  return t + real(0.0001);
+#endif
+}
 // SLOT = true (next-event estimation only, core/integrator.hpp) also reports the top-level slot of the winning entry in
 // *hit_slot; every other caller leaves it false and compiles to the same code as without it.
 template <uint32_t F, bool COUNT, class STACK, bool SLOT = false>
@@ -646,7 +662,7 @@ RT_HD bool world_hit(const SceneView& sv, const Ray& r, real t_min, real t_max, 
     for (int q = 0; q < n_query; ++q) {
       geom_closest<F, COUNT>(sv, geom_rec, rq, q_min, q_max, &best, stack, cnt);
       if (!best.hit) { ok = false; break; }
-      if (q == 0) { rec1_t = best.t; q_min = rec1_t + real(0.0001); }
+      if (q == 0) { rec1_t = best.t; q_min = medium_second_t_min(rec1_t); }
     }
     if (!ok) continue;
 

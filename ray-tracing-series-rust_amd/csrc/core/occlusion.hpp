@@ -169,7 +169,7 @@ RT_HD real world_occlusion(const SceneView& sv, const Ray& r, real t_min, real t
     geom_closest<F, false>(sv, geom_rec, rq, -RT_INFINITY, RT_INFINITY, &best, stack, nullptr);
     if (!best.hit) continue;
     const real rec1_t = best.t;
-    geom_closest<F, false>(sv, geom_rec, rq, rec1_t + real(0.0001), RT_INFINITY, &best, stack, nullptr);
+    geom_closest<F, false>(sv, geom_rec, rq, medium_second_t_min(rec1_t), RT_INFINITY, &best, stack, nullptr);
     if (!best.hit) continue;
     real t1 = rt_fmax(rec1_t, t_min);
     const real t2 = rt_fmin(best.t, t_max);

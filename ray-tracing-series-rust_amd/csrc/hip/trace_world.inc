@@ -484,7 +484,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
               else {  // rec2 = boundary.hit(rec1.t + 0.0001, inf)
                 aux_t = best.t;
                 const rt::Ray rq = slot_ray();
-                begin_walk(rq, aux_t + 0.0001, RT_INFINITY, walk_root, first_ref);
+                begin_walk(rq, rt::medium_second_t_min(aux_t), RT_INFINITY, walk_root, first_ref);
                 ph = 1u;
               }
             } else {
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
               if (as_medium && real_roots) {
                 const int32_t me = is_medium ? e : e + 1;
                 rt::real t2;
-                if (rt::sphere_pick(r1, r2, -RT_INFINITY, RT_INFINITY, &t) && rt::sphere_pick(r1, r2, t + 0.0001 + guard, RT_INFINITY, &t2)) {
+                if (rt::sphere_pick(r1, r2, -RT_INFINITY, RT_INFINITY, &t) && rt::sphere_pick(r1, r2, rt::medium_second_t_min(t) + guard, RT_INFINITY, &t2)) {
                   // hit.rs:969-985, as medium_decide above, for entry `me`
                   rt::real t1 = rt::rt_fmax(t, rt::ray_t_min(ps.ray));
                   t2 = rt::rt_fmin(t2, closest);
@@ -553,7 +553,7 @@ __global__ __launch_bounds__(TRACE_BLOCK, WAVES_PER_SIMD) void k_trace_world(
             } else {
               rt::real t2;
               if (direct_closest<F>(sv, G, rq, -RT_INFINITY, RT_INFINITY, &t, &ref) &&
-                  direct_closest<F>(sv, G, rq, t + 0.0001, RT_INFINITY, &t2, &ref))
+                  direct_closest<F>(sv, G, rq, rt::medium_second_t_min(t), RT_INFINITY, &t2, &ref))
                 medium_decide(t, t2);
             }
           }
