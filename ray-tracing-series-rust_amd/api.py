@@ -1132,36 +1132,52 @@ def _ray_arrays(given):
     return n, on_device
 
 
+class _QueryArrays:
+    """Of a batch that _ray_arrays has checked: column addresses, result arrays of the rays' kind, the choice of the entry point."""
+
+    def __init__(self, given):
+        self.n, self.on_device = _ray_arrays(given)
+        if self.on_device:
+            import torch
+            self.torch, self.device = torch, given[0][1].device
+
+    def addr(self, a):
+        return a.data_ptr() if self.on_device else a.ctypes.data
+
+    def ptr(self, a):
+        """The address of a column; None for a column that was left out, and for every column of an empty batch."""
+        return self.addr(a) if a is not None and self.n else None
+
+    def empty(self, shape, dtype="float64"):
+        if self.on_device:
+            return self.torch.empty(shape, device=self.device, dtype=getattr(self.torch, dtype))
+        return np.empty(shape, dtype=getattr(np, dtype))
+
+    def call(self, host_fn, device_fn, args, tail=(), stream=None):
+        """numpy: host_fn(*args, *tail).  torch: device_fn(*args, stream or torch's current one, *tail), the rays' GPU current."""
+        if not self.on_device:
+            return _check(host_fn(*args, *tail))
+        with self.torch.cuda.device(self.device):
+            if stream is None:
+                stream = self.torch.cuda.current_stream(self.device)
+            handle = getattr(stream, "cuda_stream", stream)
+            _check(device_fn(*args, _VP(handle or None), *tail))
+
+
 def _cast_rays(scene, origins, directions, times, t_max, t_min, t_max_all, seed, stream_step, want):
     want = tuple(want)
     for name in want:
         if name not in RAY_COLUMNS:
             raise ValueError("want: unknown column %r (expected some of %s)" % (name, ", ".join(RAY_COLUMNS)))
-    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
-    if on_device:
-        import torch
+    io = _QueryArrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
     batch = RtxRayBatch()
     lib.rtx_ray_batch_defaults(C.byref(batch))
-    batch.n, batch.t_min, batch.t_max_all, batch.seed, batch.stream_step = n, t_min, t_max_all, seed, stream_step
-    cols = {}
-    if on_device:
-        ptr = lambda a: a.data_ptr() if a is not None and n else None
-        for name in want:
-            cols[name] = torch.empty((n,) + _RAY_COLUMN_SHAPES[name], device=origins.device,
-                                     dtype=torch.int32 if name == "ids" else torch.float64)
-    else:
-        ptr = lambda a: a.ctypes.data if a is not None and n else None
-        for name in want:
-            cols[name] = np.empty((n,) + _RAY_COLUMN_SHAPES[name], dtype=np.int32 if name == "ids" else np.float64)
-    batch.origin, batch.direction, batch.time, batch.t_max = ptr(origins), ptr(directions), ptr(times), ptr(t_max)
-    hits = RtxRayHits(*[ptr(cols.get(name)) for name in RAY_COLUMNS])
-    if on_device:
-        with torch.cuda.device(origins.device):
-            stream = torch.cuda.current_stream(origins.device).cuda_stream
-            _check(lib.rtx_scene_cast_rays_device(scene.ptr, C.byref(batch), C.byref(hits), _VP(stream or None)))
-    else:
-        _check(lib.rtx_scene_cast_rays(scene.ptr, C.byref(batch), C.byref(hits)))
-    return RayHits(n, cols)
+    batch.n, batch.t_min, batch.t_max_all, batch.seed, batch.stream_step = io.n, t_min, t_max_all, seed, stream_step
+    cols = {name: io.empty((io.n,) + _RAY_COLUMN_SHAPES[name], "int32" if name == "ids" else "float64") for name in want}
+    batch.origin, batch.direction, batch.time, batch.t_max = io.ptr(origins), io.ptr(directions), io.ptr(times), io.ptr(t_max)
+    hits = RtxRayHits(*[io.ptr(cols.get(name)) for name in RAY_COLUMNS])
+    io.call(lib.rtx_scene_cast_rays, lib.rtx_scene_cast_rays_device, (scene.ptr, C.byref(batch), C.byref(hits)))
+    return RayHits(io.n, cols)
 
 
 class Occlusion:
@@ -1182,34 +1198,20 @@ class Occlusion:
 
 
 def _occlusion(scene, origins, directions, times, t_max, t_min, t_max_all, stream):
-    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
+    io = _QueryArrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0), ("t_max", t_max, 0)])
     if t_min != t_min:
         raise ValueError("t_min: NaN")
     if t_max_all != t_max_all:
         raise ValueError("t_max_all: NaN")
-    if stream is not None and not on_device:
+    if stream is not None and not io.on_device:
         raise ValueError("stream: only for torch tensors on the GPU (numpy arrays go through the blocking host entry)")
     batch = RtxRayBatch()
     lib.rtx_ray_batch_defaults(C.byref(batch))
-    batch.n, batch.t_min, batch.t_max_all = n, t_min, t_max_all
-    if on_device:
-        import torch
-        ptr = lambda a: a.data_ptr() if a is not None and n else None
-        store = torch.empty((max(n, 1),), device=origins.device, dtype=torch.float64)  # (tau may not be NULL, even for n = 0)
-    else:
-        ptr = lambda a: a.ctypes.data if a is not None and n else None
-        store = np.empty((max(n, 1),), dtype=np.float64)
-    tau = store[:n]
-    batch.origin, batch.direction, batch.time, batch.t_max = ptr(origins), ptr(directions), ptr(times), ptr(t_max)
-    if on_device:
-        with torch.cuda.device(origins.device):
-            if stream is None:
-                stream = torch.cuda.current_stream(origins.device)
-            handle = getattr(stream, "cuda_stream", stream)
-            _check(lib.rtx_scene_occlusion_device(scene.ptr, C.byref(batch), _VP(store.data_ptr()), _VP(handle or None)))
-    else:
-        _check(lib.rtx_scene_occlusion(scene.ptr, C.byref(batch), _VP(store.ctypes.data)))
-    return Occlusion(n, tau)
+    batch.n, batch.t_min, batch.t_max_all = io.n, t_min, t_max_all
+    store = io.empty((max(io.n, 1),))  # (tau may not be NULL, even for n = 0)
+    batch.origin, batch.direction, batch.time, batch.t_max = io.ptr(origins), io.ptr(directions), io.ptr(times), io.ptr(t_max)
+    io.call(lib.rtx_scene_occlusion, lib.rtx_scene_occlusion_device, (scene.ptr, C.byref(batch), _VP(io.addr(store))), stream=stream)
+    return Occlusion(io.n, store[:io.n])
 
 
 class RadianceSums:
@@ -1226,9 +1228,8 @@ class RadianceSums:
 
 def _trace_rays(scene, origins, directions, times, spp, max_depth, background, seed, first_sample, first_ray, light_sampling,
                 sumsq, out, sample_buffer_bytes, want_stats):
-    n, on_device = _ray_arrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0)])
-    if on_device:
-        import torch
+    io = _QueryArrays([("origins", origins, 3), ("directions", directions, 3), ("times", times, 0)])
+    n, on_device = io.n, io.on_device
     for name, v, lo in (("spp", spp, 1), ("max_depth", max_depth, 1), ("first_sample", first_sample, 0), ("first_ray", first_ray, 0)):
         if int(v) != v or v < lo:
             raise ValueError("%s: must be an integer >= %d, not %r" % (name, lo, v))
@@ -1247,29 +1248,19 @@ def _trace_rays(scene, origins, directions, times, spp, max_depth, background, s
         if sumsq and out.sumsq is None:
             raise ValueError("out: has no sumsq to continue")
         s_arr, q_arr = out.sum, out.sumsq
-    elif on_device:
-        s_arr = torch.empty((n, 3), device=origins.device, dtype=torch.float64)
-        q_arr = torch.empty((n, 3), device=origins.device, dtype=torch.float64) if sumsq else None
     else:
-        s_arr = np.empty((n, 3), dtype=np.float64)
-        q_arr = np.empty((n, 3), dtype=np.float64) if sumsq else None
+        s_arr = io.empty((n, 3))
+        q_arr = io.empty((n, 3)) if sumsq else None
     q = RtxRadianceRays()
     lib.rtx_radiance_rays_defaults(C.byref(q))
-    ptr = (lambda a: a.data_ptr() if a is not None and n else None) if on_device else (lambda a: a.ctypes.data if a is not None and n else None)
-    q.n, q.origin, q.direction, q.time = n, ptr(origins), ptr(directions), ptr(times)
+    q.n, q.origin, q.direction, q.time = n, io.ptr(origins), io.ptr(directions), io.ptr(times)
     q.first_ray, q.first_sample, q.samples, q.max_depth = first_ray, first_sample, spp, max_depth
     q.accumulate, q.seed, q.light_sampling, q.sample_buffer_bytes = 1 if out is not None else 0, seed, 1 if light_sampling else 0, sample_buffer_bytes
     q.background[:] = background
     stats = RtxRenderStats() if want_stats else None
     # (n = 0: the entry still wants a sum pointer; any non-NULL one does, nothing is written)
-    sp = _VP((s_arr.data_ptr() if on_device else s_arr.ctypes.data) or 8)
-    qp = _VP(ptr(q_arr))
-    if on_device:
-        with torch.cuda.device(origins.device):
-            stream = torch.cuda.current_stream(origins.device).cuda_stream
-            _check(lib.rtx_scene_trace_rays_device(scene.ptr, C.byref(q), sp, qp, _VP(stream or None), C.byref(stats) if stats else None))
-    else:
-        _check(lib.rtx_scene_trace_rays(scene.ptr, C.byref(q), sp, qp, C.byref(stats) if stats else None))
+    io.call(lib.rtx_scene_trace_rays, lib.rtx_scene_trace_rays_device,
+            (scene.ptr, C.byref(q), _VP(io.addr(s_arr) or 8), _VP(io.ptr(q_arr))), tail=(C.byref(stats) if stats else None,))
     if out is not None:
         out.spp += spp
         out.stats = stats

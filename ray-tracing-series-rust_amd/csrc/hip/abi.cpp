@@ -27,42 +27,32 @@ namespace rtx {
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
-rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits) {
-  const char* bad = nullptr;
-  if (!s) bad = "scene is NULL";
-  else if (!rays) bad = "rays is NULL";
-  else if (!hits) bad = "hits is NULL";
-  else if (rays->n < 0) bad = "rays->n < 0";
-  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
-  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
-  else if (rays->t_min != rays->t_min) bad = "rays->t_min is NaN";
-  else if (rays->t_max_all != rays->t_max_all) bad = "rays->t_max_all is NaN";
-  if (!bad) return RTX_OK;
-  set_error(std::string(who) + ": " + bad);
-  return RTX_EINVAL;
+// RTX_OK, or RTX_EINVAL with the message "<who>: <bad>".
+static rtx_status refuse(const char* who, const char* bad) {
+  if (bad) set_error(std::string(who) + ": " + bad);
+  return bad ? RTX_EINVAL : RTX_OK;
 }
-rtx_status check_occlusion(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const double* tau) {
-  const char* bad = nullptr;
-  if (!s) bad = "scene is NULL";
-  else if (!rays) bad = "rays is NULL";
-  else if (!tau) bad = "tau is NULL";
-  else if (rays->n < 0) bad = "rays->n < 0";
-  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
-  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
-  else if (rays->t_min != rays->t_min) bad = "rays->t_min is NaN";
-  else if (rays->t_max_all != rays->t_max_all) bad = "rays->t_max_all is NaN";
-  if (!bad) return RTX_OK;
-  set_error(std::string(who) + ": " + bad);
-  return RTX_EINVAL;
+// The rungs every ray query's check opens with (Rays: RtxRayBatch or RtxRadianceRays); NULL when they all pass.
+template <class Rays>
+static const char* bad_ray_columns(const rtx_scene* s, const Rays* rays, const void* out, const char* out_is_null) {
+  if (!s) return "scene is NULL";
+  if (!rays) return "rays is NULL";
+  if (!out) return out_is_null;
+  if (rays->n < 0) return "rays->n < 0";
+  if (rays->n > 0 && !rays->origin) return "rays->origin is NULL";
+  if (rays->n > 0 && !rays->direction) return "rays->direction is NULL";
+  return nullptr;
+}
+rtx_status check_ray_batch(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const void* out, const char* out_name) {
+  const std::string out_is_null = std::string(out_name) + " is NULL";
+  const char* bad = bad_ray_columns(s, rays, out, out_is_null.c_str());
+  if (!bad && rays->t_min != rays->t_min) bad = "rays->t_min is NaN";
+  else if (!bad && rays->t_max_all != rays->t_max_all) bad = "rays->t_max_all is NaN";
+  return refuse(who, bad);
 }
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb) {
-  const char* bad = nullptr;
-  if (!s) bad = "scene is NULL";
-  else if (!rays) bad = "rays is NULL";
-  else if (!sum_rgb) bad = "sum_rgb is NULL";
-  else if (rays->n < 0) bad = "rays->n < 0";
-  else if (rays->n > 0 && !rays->origin) bad = "rays->origin is NULL";
-  else if (rays->n > 0 && !rays->direction) bad = "rays->direction is NULL";
+  const char* bad = bad_ray_columns(s, rays, sum_rgb, "sum_rgb is NULL");
+  if (bad) {}  // (a common rung)
   else if (rays->samples < 1) bad = "rays->samples < 1";
   else if (rays->max_depth < 1) bad = "rays->max_depth < 1 (Config::new asserts max_depth > 0, world.rs:36-40)";
   else if (rays->reserved != 0) bad = "rays->reserved is not 0";
@@ -71,9 +61,7 @@ rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadian
   else if (rays->background[0] != rays->background[0] || rays->background[1] != rays->background[1] ||
            rays->background[2] != rays->background[2]) bad = "rays->background is NaN";
   else if ((uint64_t)rays->first_sample + (uint64_t)rays->samples > (1ull << 32)) bad = "rays->first_sample + rays->samples is past 2^32";
-  if (!bad) return RTX_OK;
-  set_error(std::string(who) + ": " + bad);
-  return RTX_EINVAL;
+  return refuse(who, bad);
 }
 rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved) {
   std::string err;

@@ -38,12 +38,10 @@ inline rtx_scene* make_scene_handle(void* ds, const RtxSceneOps* ops, int32_t f3
 }
 inline void free_scene_handle(rtx_scene* s) { delete s; }
 
-// The argument checks of rtx_scene_cast_rays and rtx_scene_cast_rays_device (abi.cpp; no device call): RTX_EINVAL with a
-// message that names the entry point `who` and the offending field.
-rtx_status check_cast(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits);
-// The same ladder for rtx_scene_occlusion and rtx_scene_occlusion_device, with `tau` in the place of `hits`.
-rtx_status check_occlusion(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const double* tau);
-// The same for rtx_scene_trace_rays and rtx_scene_trace_rays_device.
+// The argument checks of the ray queries' entry points (abi.cpp; no device call): RTX_EINVAL with a message that names the entry
+// point `who` and the offending field.  rtx_scene_cast_rays* and rtx_scene_occlusion* (out, out_name: hits as "hits", tau as "tau"):
+rtx_status check_ray_batch(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const void* out, const char* out_name);
+// rtx_scene_trace_rays*: the same first rungs, then the radiance batch's own fields.
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb);
 // The checks of rtx_scene_set_transforms that need no scene (host/set_transforms.hpp: check_slot_ops_shape; s is compared with
 // NULL and not read), then *resolved = the updates with every angle turned into sin / cos as the flat arrays hold them.

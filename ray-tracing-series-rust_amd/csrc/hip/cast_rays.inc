@@ -17,12 +17,18 @@
 // where it can): a wave's three accesses touch the same twelve 128-byte lines, so HBM sees every line once and the cost is
 // address traffic in the vector cache.  No LDS beyond the walk stack, no barrier.
 
-// A launch's rays and result columns (device pointers; a NULL column is not read / not written) -- a kernel argument, so every
-// test on it is wave-uniform.
-struct CastArgs {
+// The ray columns every query kernel takes (device pointers): the first member of CastArgs, OcclusionArgs and RadianceArgs.
+// Each kernel reads and narrows a ray with its own lines: a shared loader reordered the code of 15 of the 18 instantiations.
+struct QueryRays {
   const double* origin;     // [n][3]
   const double* direction;  // [n][3]
   const double* time;       // [n] or NULL: 0
+};
+
+// A launch's rays and result columns (device pointers; a NULL column is not read / not written) -- a kernel argument, so every
+// test on it is wave-uniform.
+struct CastArgs {
+  QueryRays rays;
   const double* t_max;      // [n] or NULL: t_max_all
   double t_min, t_max_all;
   double time_limit;        // scenes with GravitySpheres: a ray later than this is not cast (DeviceScene::gravity_time_limit)
@@ -47,13 +53,13 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_cast_rays(rt::SceneView sv, Cas
     const bool live = r < n;
     double o[3] = {0.0, 0.0, 0.0}, d[3] = {0.0, 0.0, 0.0};
     if (live) {
-      for (int c = 0; c < 3; ++c) { o[c] = a.origin[3 * (size_t)r + c]; d[c] = a.direction[3 * (size_t)r + c]; }
+      for (int c = 0; c < 3; ++c) { o[c] = a.rays.origin[3 * (size_t)r + c]; d[c] = a.rays.direction[3 * (size_t)r + c]; }
     }
     rt::HitRecord rec;
     int32_t slot = -1;
     bool hit = false;
     if (live) {
-      const double time = a.time ? a.time[r] : 0.0;
+      const double time = a.rays.time ? a.rays.time[r] : 0.0;
       const double t_max = a.t_max ? a.t_max[r] : a.t_max_all;
       const rt::Ray ray = rt::make_ray(rt::v3((rt::real)o[0], (rt::real)o[1], (rt::real)o[2]),
                                        rt::v3((rt::real)d[0], (rt::real)d[1], (rt::real)d[2]), (rt::real)time);

@@ -11,9 +11,7 @@
 // GravitySpheres' time limit is not tested and answers NaN (k_trace_rays' rule): a ray that was not tested must not read as clear.
 
 struct OcclusionArgs {
-  const double* origin;     // [n][3]
-  const double* direction;  // [n][3]
-  const double* time;       // [n] or NULL: 0
+  QueryRays rays;           // cast_rays.inc
   const double* t_max;      // [n] or NULL: t_max_all
   double t_min, t_max_all;
   double time_limit;        // scenes with GravitySpheres: a ray later than this is not tested (DeviceScene::gravity_time_limit)
@@ -32,8 +30,8 @@ __global__ __launch_bounds__(TRACE_BLOCK) void k_occlusion(rt::SceneView sv, Occ
     const uint32_t r = first + lane;
     if (r < n) {
       double o[3], d[3];
-      for (int c = 0; c < 3; ++c) { o[c] = a.origin[3 * (size_t)r + c]; d[c] = a.direction[3 * (size_t)r + c]; }
-      const double time = a.time ? a.time[r] : 0.0;
+      for (int c = 0; c < 3; ++c) { o[c] = a.rays.origin[3 * (size_t)r + c]; d[c] = a.rays.direction[3 * (size_t)r + c]; }
+      const double time = a.rays.time ? a.rays.time[r] : 0.0;
       const double t_max = a.t_max ? a.t_max[r] : a.t_max_all;
       double tau = __builtin_nan("");
       if (!(time > a.time_limit)) {

@@ -36,6 +36,7 @@
 #include "../host/update_shadow.hpp"
 #include "../host/set_shading.hpp"
 #include "../host/wide_tree.hpp"
+#include "../host/ray_slices.hpp"  // for_ray_slices, slice_of: how the ray queries cut a batch (host-compilable: tests/ray_slices_host_check.cpp)
 #include "device_buffer.hpp"
 #include "f32_bridge.hpp"
 #ifndef RTX_F32_TU
@@ -355,7 +356,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_wave.inc"    // k_wf_generate / k_wf_trace / k_wf_shade: the split-kernel integrator (path state in HBM)
 #include "post_kernels.inc"  // k_reduce_samples, k_tonemap, device self tests
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
-#include "cast_rays.inc"     // k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
+#include "cast_rays.inc"     // QueryRays; k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
 #include "trace_rays.inc"    // k_trace_rays: the estimator's radiance along a caller's rays (rtx_scene_trace_rays*)
 #include "occlusion.inc"     // k_occlusion: any-hit segment casts with exact fog depth (rtx_scene_occlusion*)
 #ifndef RTX_F32_TU
@@ -1341,13 +1342,16 @@ static rtx_status tonemap_impl(const double* accum, uint8_t* rgb8, const int32_t
   return RTX_OK;
 }
 
+#include "queries.inc"       // check_walk_launch, with_query_preset, launch_cast_rays, launch_occlusion, trace_rays_impl: the launchers of
+                             // the ray queries (here, not beside their kernels: they plan passes with prepare_workspace)
+
 // The feature pass of a whole-image progressive handle (denoise.inc: k_features): feature_spp first hits per pixel into the
 // float4 albedo / normal buffers of w * h pixels.  Asynchronous on stream.
 static rtx_status features_impl(DeviceScene* ds, const RtxCamera* cam, const RtxConfig* cfg, int32_t feature_spp,
                                 float4* d_albedo, float4* d_normal, hipStream_t stream) {
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("features: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
+  size_t stack_lds = 0;
+  const rtx_status st = check_walk_launch(ds, "features", &stack_lds);
+  if (st != RTX_OK) return st;
   if ((ds->view.features & rt::F_GRAVITY_SPHERE) && !(cam->time2 <= ds->gravity_time_limit)) {
     set_error("features: shutter time beyond the GravitySpheres' stored trajectory");
     return RTX_EINVAL;
@@ -1355,213 +1359,14 @@ static rtx_status features_impl(DeviceScene* ds, const RtxCamera* cam, const Rtx
   const rt::RenderParams rp = make_params(cam, cfg);
   const uint64_t npix = (uint64_t)rp.image_width * (uint64_t)rp.image_height;
   if (npix == 0) return RTX_OK;
-  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
-  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("features: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
   const uint32_t grid = grid_size((uint32_t)npix, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
   if (ds->view.features & rt::F_INSTANCE)
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_INST>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_INST>), dim3(grid), dim3(TRACE_BLOCK), stack_lds, stream, ds->view,
                        rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
   else
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_ALL>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, ds->view,
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_features<P_ALL>), dim3(grid), dim3(TRACE_BLOCK), stack_lds, stream, ds->view,
                        rp, (uint32_t)npix, (uint32_t)feature_spp, d_albedo, d_normal);
   HIP_TRY(hipGetLastError());
-  return RTX_OK;
-}
-
-// Ray queries (cast_rays.inc: k_cast_rays): the batch's rays against the scene, the requested columns written.  Device
-// pointers, asynchronous on stream; the arguments were checked by the entry point (check_cast).  A launch indexes rays with
-// 32 bits, so a batch goes out in slices of CAST_LAUNCH_RAYS, ray `first` of a slice on the stream seed + first * stream_step.
-static const int64_t CAST_LAUNCH_RAYS = (int64_t)1 << 30;
-static rtx_status launch_cast_rays(DeviceScene* ds, const RtxRayBatch* b, const RtxRayHits* h, hipStream_t stream) {
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("cast_rays: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
-  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
-  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("cast_rays: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
-  const uint32_t feat = ds->view.features;
-  for (int64_t first = 0; first < b->n; first += CAST_LAUNCH_RAYS) {
-    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, b->n - first);
-    CastArgs a;
-    a.origin = b->origin + 3 * first;
-    a.direction = b->direction + 3 * first;
-    a.time = b->time ? b->time + first : nullptr;
-    a.t_max = b->t_max ? b->t_max + first : nullptr;
-    a.t_min = b->t_min;
-    a.t_max_all = b->t_max_all;
-    a.time_limit = (feat & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
-    a.seed = b->seed + (uint64_t)first * b->stream_step;
-    a.stream_step = b->stream_step;
-    a.t = h->t ? h->t + first : nullptr;
-    a.p = h->p ? h->p + 3 * first : nullptr;
-    a.normal = h->normal ? h->normal + 3 * first : nullptr;
-    a.uv = h->uv ? h->uv + 2 * first : nullptr;
-    a.ids = h->ids ? h->ids + 4 * first : nullptr;
-    const uint32_t grid = grid_size(n, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
-#define LAUNCH_CAST(FEAT)                                                                                                     \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cast_rays<FEAT>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, \
-                       ds->view, a, n)
-    // the presets of k_features and k_trace_nee: instance trees, everything (GravitySpheres), any other world
-    if (feat & rt::F_INSTANCE) LAUNCH_CAST(P_INST);
-    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_CAST(P_ALL);
-    else LAUNCH_CAST(P_ANY);
-#undef LAUNCH_CAST
-    HIP_TRY(hipGetLastError());
-  }
-  return RTX_OK;
-}
-
-// Occlusion queries (occlusion.inc: k_occlusion): tau of the batch's rays.  Device pointers, asynchronous on stream; the
-// arguments were checked by the entry point (check_occlusion).  The device check, the stack check and the launch split are
-// launch_cast_rays'.
-static rtx_status launch_occlusion(DeviceScene* ds, const RtxRayBatch* b, double* d_tau, hipStream_t stream) {
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("occlusion: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
-  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
-  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("occlusion: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
-  const uint32_t feat = ds->view.features;
-  for (int64_t first = 0; first < b->n; first += CAST_LAUNCH_RAYS) {
-    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, b->n - first);
-    OcclusionArgs a;
-    a.origin = b->origin + 3 * first;
-    a.direction = b->direction + 3 * first;
-    a.time = b->time ? b->time + first : nullptr;
-    a.t_max = b->t_max ? b->t_max + first : nullptr;
-    a.t_min = b->t_min;
-    a.t_max_all = b->t_max_all;
-    a.time_limit = (feat & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
-    a.tau = d_tau + first;
-    const uint32_t grid = grid_size(n, TRACE_BLOCK, (uint64_t)ds->n_cu * 8);
-#define LAUNCH_OCCLUSION(FEAT)                                                                                                \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_occlusion<FEAT>), dim3(grid), dim3(TRACE_BLOCK), stack_bytes(stack_levels), stream, \
-                       ds->view, a, n)
-    // the presets of k_cast_rays, by its rule: instance trees, everything (GravitySpheres), any other world
-    if (feat & rt::F_INSTANCE) LAUNCH_OCCLUSION(P_INST);
-    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_OCCLUSION(P_ALL);
-    else LAUNCH_OCCLUSION(P_ANY);
-#undef LAUNCH_OCCLUSION
-    HIP_TRY(hipGetLastError());
-  }
-  return RTX_OK;
-}
-
-// One pass of a radiance query (trace_rays.inc: k_trace_rays) on `stream`: its work counter zeroed, then the persistent launch --
-// as many blocks as are resident, at most one wave per TRACE_CHUNK items (launch_nee's rule).
-static rtx_status launch_trace_rays_pass(const DeviceScene* ds, const rt::RenderParams& rp, const RadianceArgs& ra, bool nee,
-                                         uint32_t s_begin, uint32_t total, uint32_t n, double* samples, unsigned int* work_counter,
-                                         size_t stack_lds, hipStream_t stream) {
-  HIP_TRY(hipMemsetAsync(work_counter, 0, sizeof(unsigned int), stream));
-  const uint32_t feat = ds->view.features;
-#define LAUNCH_RAYS(FEAT, NEE)                                                                                                   \
-  do {                                                                                                                          \
-    const int nb = occupancy(k_trace_rays<FEAT, NEE>, stack_lds);                                                               \
-    const uint32_t grid = grid_size(total, TRACE_CHUNK, (uint64_t)ds->n_cu * (uint64_t)(nb > 0 ? nb : 1) * (TRACE_BLOCK / 64)); \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_trace_rays<FEAT, NEE>), dim3((grid + TRACE_BLOCK / 64 - 1) / (TRACE_BLOCK / 64)),      \
-                       dim3(TRACE_BLOCK), stack_lds, stream, ds->view, ds->lights, rp, ra, s_begin, total, n, samples,          \
-                       work_counter);                                                                                           \
-  } while (0)
-  // the presets of k_cast_rays and k_features: instance trees, everything (GravitySpheres), any other world
-#ifndef RTX_F32_TU
-  if (nee) {
-    if (feat & rt::F_INSTANCE) LAUNCH_RAYS(P_INST, true);
-    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_RAYS(P_ALL, true);
-    else LAUNCH_RAYS(P_ANY, true);
-  } else
-#endif
-  {
-    if (feat & rt::F_INSTANCE) LAUNCH_RAYS(P_INST, false);
-    else if (feat & rt::F_GRAVITY_SPHERE) LAUNCH_RAYS(P_ALL, false);
-    else LAUNCH_RAYS(P_ANY, false);
-  }
-#undef LAUNCH_RAYS
-  HIP_TRY(hipGetLastError());
-  return RTX_OK;
-}
-
-// Radiance queries (trace_rays.inc: k_trace_rays): q->samples samples of the estimator along every ray of the batch, summed in
-// sample order onto d_sum (and their squares onto d_sumsq unless NULL).  Device pointers, asynchronous on stream unless stats
-// is asked for; the arguments were checked by the entry point (check_trace_rays).  Passes are planned by prepare_workspace and
-// run as a render's do: two deep when the sample buffer does not hold the call, even passes on the caller's stream, odd ones on
-// ws.aux_stream, reductions in pass order.  A launch indexes rays with 32 bits, so a batch goes out in slices of
-// CAST_LAUNCH_RAYS, ray r of a slice that starts at `first` on the stream of first_ray + first + r.
-static rtx_status trace_rays_impl(DeviceScene* ds, const RtxRadianceRays* q, double* d_sum, double* d_sumsq, hipStream_t stream,
-                                  RtxRenderStats* stats) {
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != ds->device) { set_error("trace_rays: scene was uploaded to a different device than the current one"); return RTX_EINVAL; }
-  const uint32_t stack_levels = (uint32_t)ds->view.max_stack + 1u;
-  if (stack_bytes(stack_levels) > 64 * 1024) { set_error("trace_rays: BVH too deep for the LDS traversal stack"); return RTX_EUNSUPPORTED; }
-  const bool nee = q->light_sampling != 0;
-#ifdef RTX_F32_TU
-  if (nee) { set_error("trace_rays: light sampling is f64 only"); return RTX_EUNSUPPORTED; }  // (the entry points reject it first)
-#endif
-  rt::RenderParams rp;
-  memset(&rp, 0, sizeof(rp));  // no camera, no image: path_begin_ray reads neither
-  rp.background = rt::v3(q->background[0], q->background[1], q->background[2]);
-  rp.samples_per_pixel = q->samples;
-  rp.max_depth = q->max_depth;
-  rp.seed = q->seed;
-  const uint32_t spp = (uint32_t)q->samples;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  Workspace& ws = ds->ws;
-  float trace_ms = 0.f;
-  int passes = 0;
-  size_t sample_bytes = 0;
-  for (int64_t first = 0; first < q->n; first += CAST_LAUNCH_RAYS) {
-    const uint32_t n = (uint32_t)std::min<int64_t>(CAST_LAUNCH_RAYS, q->n - first);
-    double* sum = d_sum + 3 * first;
-    double* sumsq = d_sumsq ? d_sumsq + 3 * first : nullptr;
-    PassPlan pp;
-    const rtx_status st = prepare_workspace(ds, q->sample_buffer_bytes, n, n, spp, stats != nullptr, stream, &sum, &pp);
-    if (st != RTX_OK) return st;
-    sample_bytes = std::max(sample_bytes, pp.sample_bytes);
-    RadianceArgs ra;
-    ra.origin = q->origin + 3 * first;
-    ra.direction = q->direction + 3 * first;
-    ra.time = q->time ? q->time + first : nullptr;
-    ra.time_limit = (ds->view.features & rt::F_GRAVITY_SPHERE) ? ds->gravity_time_limit : 1e300;
-    ra.first_ray = q->first_ray + (uint64_t)first;
-    if (pp.pipeline) {
-      HIP_TRY(hipEventRecord(ws.ev_pass[2], stream));
-      HIP_TRY(hipStreamWaitEvent(ws.aux_stream, ws.ev_pass[2], 0));
-    }
-    int k = 0;  // passes of this launch slice
-    for (uint32_t s_off = 0; s_off < spp; s_off += pp.spp_pass, ++k, ++passes) {
-      const int half = pp.pipeline ? (k & 1) : 0;
-      const uint32_t s_count = spp - s_off < pp.spp_pass ? spp - s_off : pp.spp_pass;
-      const uint32_t total = (uint32_t)((uint64_t)s_count * n);
-      const hipStream_t ps = half ? ws.aux_stream : stream;
-      double* samples = ws.samples + (size_t)half * (size_t)pp.spp_pass * (size_t)n * 3u;
-      if (stats) HIP_TRY(hipEventRecord(ws.ev[0], ps));
-      const rtx_status lst = launch_trace_rays_pass(ds, rp, ra, nee, q->first_sample + s_off, total, n, samples, ws.work_counter + half,
-                                                    stack_bytes(stack_levels), ps);
-      if (lst != RTX_OK) return lst;
-      if (stats) {
-        HIP_TRY(hipEventRecord(ws.ev[1], ps));
-        HIP_TRY(hipEventSynchronize(ws.ev[1]));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]));
-        trace_ms += ms;
-      }
-      const uint32_t pgrid = (n + 255u) / 256u;
-      if (pp.pipeline && k > 0) HIP_TRY(hipStreamWaitEvent(ps, ws.ev_pass[1 - half], 0));  // the previous pass's sums are in
-      const int first_pass = s_off == 0 && !q->accumulate ? 1 : 0;
-      if (sumsq) hipLaunchKernelGGL(k_reduce_samples_moments, dim3(pgrid), dim3(256), 0, ps, samples, sum, sumsq, n, s_count, first_pass);
-      else hipLaunchKernelGGL(k_reduce_samples, dim3(pgrid), dim3(256), 0, ps, samples, sum, n, s_count, first_pass);
-      HIP_TRY(hipGetLastError());
-      if (pp.pipeline) HIP_TRY(hipEventRecord(ws.ev_pass[half], ps));
-    }
-    if (pp.pipeline && k > 0 && ((k - 1) & 1)) HIP_TRY(hipStreamWaitEvent(stream, ws.ev_pass[1], 0));
-  }
-  if (stats) {
-    HIP_TRY(hipStreamSynchronize(stream));
-    stats->trace_ms = trace_ms;
-    stats->trace_launches = passes;
-    stats->passes = passes;
-    stats->trace_kernel = RTX_KERNEL_RAYS;
-    stats->sample_buffer_bytes = sample_bytes;
-    stats->samples = (uint64_t)spp * (uint64_t)q->n;
-  }
   return RTX_OK;
 }
 
@@ -1737,107 +1542,6 @@ rtx_status rtx_render_device(const rtx_scene* s, const RtxCamera* cam, const Rtx
   return render_any(s, cam, cfg, shard, d_accum_rgb, d_rgb8, (hipStream_t)hip_stream, stats);
 }
 
-// ---- ray queries.  The arguments are checked first (abi.cpp: check_cast), before any device call.
-rtx_status rtx_scene_cast_rays_device(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits, void* hip_stream) {
-  const rtx_status st = check_cast("rtx_scene_cast_rays_device", s, rays, hits);
-  if (st != RTX_OK || rays->n == 0) return st;
-  // the kernel stores uv as double2 and ids as int4, and every other column as doubles
-  const struct { const void* p; uintptr_t mask; const char* name; } cols[] = {
-      {rays->origin, 7, "rays->origin"}, {rays->direction, 7, "rays->direction"}, {rays->time, 7, "rays->time"},
-      {rays->t_max, 7, "rays->t_max"},   {hits->t, 7, "hits->t"},                 {hits->p, 7, "hits->p"},
-      {hits->normal, 7, "hits->normal"}, {hits->uv, 15, "hits->uv"},              {hits->ids, 15, "hits->ids"}};
-  for (const auto& c : cols)
-    if ((uintptr_t)c.p & c.mask) {
-      set_error(std::string("rtx_scene_cast_rays_device: ") + c.name + " is not " + (c.mask == 15 ? "16" : "8") + "-byte aligned");
-      return RTX_EINVAL;
-    }
-  return s->ops->cast_rays(s->device_scene, rays, hits, (hipStream_t)hip_stream);
-}
-
-// Host pointers: slices of RTX_CAST_HOST_SLICE rays staged through device buffers (in: 56 B a ray, out: 88 B), one after the
-// other on the null stream; a slice's seed is advanced as the launcher advances a launch's.
-rtx_status rtx_scene_cast_rays(const rtx_scene* s, const RtxRayBatch* rays, const RtxRayHits* hits) {
-  rtx_status st = check_cast("rtx_scene_cast_rays", s, rays, hits);
-  if (st != RTX_OK || rays->n == 0) return st;
-  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_CAST_HOST_SLICE);
-  DeviceBuffer<double> d_o, d_d, d_time, d_tmax, d_t, d_p, d_n, d_uv;
-  DeviceBuffer<int32_t> d_ids;
-  HIP_TRY(d_o.alloc(cap * 24));
-  HIP_TRY(d_d.alloc(cap * 24));
-  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
-  if (rays->t_max) HIP_TRY(d_tmax.alloc(cap * 8));
-  if (hits->t) HIP_TRY(d_t.alloc(cap * 8));
-  if (hits->p) HIP_TRY(d_p.alloc(cap * 24));
-  if (hits->normal) HIP_TRY(d_n.alloc(cap * 24));
-  if (hits->uv) HIP_TRY(d_uv.alloc(cap * 16));
-  if (hits->ids) HIP_TRY(d_ids.alloc(cap * 16));
-  for (int64_t first = 0; first < rays->n; first += RTX_CAST_HOST_SLICE) {
-    const size_t n = (size_t)std::min<int64_t>(RTX_CAST_HOST_SLICE, rays->n - first);
-    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
-    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
-    if (rays->t_max) HIP_TRY(hipMemcpy(d_tmax, rays->t_max + first, n * 8, hipMemcpyHostToDevice));
-    RtxRayBatch b = *rays;
-    b.n = (int64_t)n;
-    b.origin = d_o; b.direction = d_d; b.time = d_time; b.t_max = d_tmax;
-    b.seed = rays->seed + (uint64_t)first * rays->stream_step;
-    const RtxRayHits h = {d_t, d_p, d_n, d_uv, d_ids};
-    if ((st = s->ops->cast_rays(s->device_scene, &b, &h, (hipStream_t) nullptr)) != RTX_OK) return st;
-    // (a blocking copy on the null stream waits for the launch)
-    if (hits->t) HIP_TRY(hipMemcpy(hits->t + first, d_t, n * 8, hipMemcpyDeviceToHost));
-    if (hits->p) HIP_TRY(hipMemcpy(hits->p + 3 * first, d_p, n * 24, hipMemcpyDeviceToHost));
-    if (hits->normal) HIP_TRY(hipMemcpy(hits->normal + 3 * first, d_n, n * 24, hipMemcpyDeviceToHost));
-    if (hits->uv) HIP_TRY(hipMemcpy(hits->uv + 2 * first, d_uv, n * 16, hipMemcpyDeviceToHost));
-    if (hits->ids) HIP_TRY(hipMemcpy(hits->ids + 4 * first, d_ids, n * 16, hipMemcpyDeviceToHost));
-  }
-  HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxRayHits (a timing run) still returns after its launches
-  return RTX_OK;
-}
-
-// ---- occlusion queries.  The arguments are checked first (abi.cpp: check_occlusion), before any device call and before the
-// handle is read.
-rtx_status rtx_scene_occlusion_device(const rtx_scene* s, const RtxRayBatch* rays, double* d_tau, void* hip_stream) {
-  const rtx_status st = check_occlusion("rtx_scene_occlusion_device", s, rays, d_tau);
-  if (st != RTX_OK || rays->n == 0) return st;
-  const struct { const void* p; const char* name; } cols[] = {{rays->origin, "rays->origin"}, {rays->direction, "rays->direction"},
-                                                               {rays->time, "rays->time"},     {rays->t_max, "rays->t_max"},
-                                                               {d_tau, "d_tau"}};
-  for (const auto& c : cols)
-    if ((uintptr_t)c.p & 7) {
-      set_error(std::string("rtx_scene_occlusion_device: ") + c.name + " is not 8-byte aligned");
-      return RTX_EINVAL;
-    }
-  return s->ops->occlusion(s->device_scene, rays, d_tau, (hipStream_t)hip_stream);
-}
-
-// Host pointers: slices of RTX_CAST_HOST_SLICE rays staged through device buffers (in: 56 B a ray, out: 8 B), one after the
-// other on the null stream.
-rtx_status rtx_scene_occlusion(const rtx_scene* s, const RtxRayBatch* rays, double* tau) {
-  rtx_status st = check_occlusion("rtx_scene_occlusion", s, rays, tau);
-  if (st != RTX_OK || rays->n == 0) return st;
-  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_CAST_HOST_SLICE);
-  DeviceBuffer<double> d_o, d_d, d_time, d_tmax, d_tau;
-  HIP_TRY(d_o.alloc(cap * 24));
-  HIP_TRY(d_d.alloc(cap * 24));
-  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
-  if (rays->t_max) HIP_TRY(d_tmax.alloc(cap * 8));
-  HIP_TRY(d_tau.alloc(cap * 8));
-  for (int64_t first = 0; first < rays->n; first += RTX_CAST_HOST_SLICE) {
-    const size_t n = (size_t)std::min<int64_t>(RTX_CAST_HOST_SLICE, rays->n - first);
-    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
-    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
-    if (rays->t_max) HIP_TRY(hipMemcpy(d_tmax, rays->t_max + first, n * 8, hipMemcpyHostToDevice));
-    RtxRayBatch b = *rays;
-    b.n = (int64_t)n;
-    b.origin = d_o; b.direction = d_d; b.time = d_time; b.t_max = d_tmax;
-    if ((st = s->ops->occlusion(s->device_scene, &b, d_tau, (hipStream_t) nullptr)) != RTX_OK) return st;
-    // (a blocking copy on the null stream waits for the launch)
-    HIP_TRY(hipMemcpy(tau + first, d_tau, n * 8, hipMemcpyDeviceToHost));
-  }
-  return RTX_OK;
-}
-
 // ---- moving objects.  What needs no scene is checked first (abi.cpp: check_set_transforms), then the scene's own compilation
 // checks the rest against its shadow of the upload and enqueues (scene_update.inc).
 rtx_status rtx_scene_set_transforms(rtx_scene* s, const RtxSlotOps* updates, int64_t n, void* hip_stream) {
@@ -1929,75 +1633,6 @@ rtx_status rtx_scene_instance_tree_cost(const rtx_scene* s, int32_t k, double* c
 rtx_status rtx_device_scene_array(const rtx_scene* s, int32_t which, void* out, size_t bytes) {
   if (!s) { set_error("rtx_device_scene_array: NULL scene"); return RTX_EINVAL; }
   return s->ops->read_array(s->device_scene, which, out, bytes);
-}
-
-// ---- radiance queries.  The arguments are checked first (abi.cpp: check_trace_rays), before any device call.
-rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
-                                       void* hip_stream, RtxRenderStats* stats) {
-  const rtx_status st = check_trace_rays("rtx_scene_trace_rays_device", s, rays, d_sum_rgb);
-  if (st != RTX_OK) return st;
-  const struct { const void* p; const char* name; } cols[] = {{rays->origin, "rays->origin"}, {rays->direction, "rays->direction"},
-                                                              {rays->time, "rays->time"}, {d_sum_rgb, "sum_rgb"}, {d_sumsq_rgb, "sumsq_rgb"}};
-  for (const auto& c : cols)
-    if ((uintptr_t)c.p & 7) {
-      set_error(std::string("rtx_scene_trace_rays_device: ") + c.name + " is not 8-byte aligned");
-      return RTX_EINVAL;
-    }
-  if (rays->n == 0) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    return RTX_OK;
-  }
-  if (rays->light_sampling && s->f32) {
-    set_error("rtx_scene_trace_rays_device: light sampling needs an f64 scene (rtx_scene_upload)");
-    return RTX_EUNSUPPORTED;
-  }
-  return s->ops->trace_rays(s->device_scene, rays, d_sum_rgb, d_sumsq_rgb, (hipStream_t)hip_stream, stats);
-}
-
-// Host pointers: slices of RTX_TRACE_HOST_SLICE rays staged through device buffers (in: 56 B a ray, sums: 48 B), one after the
-// other on the null stream; slice k's first_ray is advanced by its offset, as the launcher advances a launch's.
-rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays, double* sum_rgb, double* sumsq_rgb,
-                                RtxRenderStats* stats) {
-  rtx_status st = check_trace_rays("rtx_scene_trace_rays", s, rays, sum_rgb);
-  if (st != RTX_OK) return st;
-  if (stats) memset(stats, 0, sizeof(*stats));
-  if (rays->n == 0) return RTX_OK;
-  if (rays->light_sampling && s->f32) {
-    set_error("rtx_scene_trace_rays: light sampling needs an f64 scene (rtx_scene_upload)");
-    return RTX_EUNSUPPORTED;
-  }
-  const size_t cap = (size_t)std::min<int64_t>(rays->n, RTX_TRACE_HOST_SLICE);
-  DeviceBuffer<double> d_o, d_d, d_time, d_sum, d_sumsq;
-  HIP_TRY(d_o.alloc(cap * 24));
-  HIP_TRY(d_d.alloc(cap * 24));
-  if (rays->time) HIP_TRY(d_time.alloc(cap * 8));
-  HIP_TRY(d_sum.alloc(cap * 24));
-  if (sumsq_rgb) HIP_TRY(d_sumsq.alloc(cap * 24));
-  for (int64_t first = 0; first < rays->n; first += RTX_TRACE_HOST_SLICE) {
-    const size_t n = (size_t)std::min<int64_t>(RTX_TRACE_HOST_SLICE, rays->n - first);
-    HIP_TRY(hipMemcpy(d_o, rays->origin + 3 * first, n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_d, rays->direction + 3 * first, n * 24, hipMemcpyHostToDevice));
-    if (rays->time) HIP_TRY(hipMemcpy(d_time, rays->time + first, n * 8, hipMemcpyHostToDevice));
-    if (rays->accumulate) {
-      HIP_TRY(hipMemcpy(d_sum, sum_rgb + 3 * first, n * 24, hipMemcpyHostToDevice));
-      if (sumsq_rgb) HIP_TRY(hipMemcpy(d_sumsq, sumsq_rgb + 3 * first, n * 24, hipMemcpyHostToDevice));
-    }
-    RtxRadianceRays b = *rays;
-    b.n = (int64_t)n;
-    b.origin = d_o; b.direction = d_d; b.time = d_time;
-    b.first_ray = rays->first_ray + (uint64_t)first;
-    RtxRenderStats one;
-    if ((st = s->ops->trace_rays(s->device_scene, &b, d_sum, d_sumsq, (hipStream_t) nullptr, stats ? &one : nullptr)) != RTX_OK) return st;
-    // (a blocking copy on the null stream waits for the launches; the odd passes were joined to it)
-    HIP_TRY(hipMemcpy(sum_rgb + 3 * first, d_sum, n * 24, hipMemcpyDeviceToHost));
-    if (sumsq_rgb) HIP_TRY(hipMemcpy(sumsq_rgb + 3 * first, d_sumsq, n * 24, hipMemcpyDeviceToHost));
-    if (stats) {
-      stats->samples += one.samples; stats->trace_ms += one.trace_ms; stats->trace_launches += one.trace_launches;
-      stats->passes += one.passes; stats->trace_kernel = one.trace_kernel;
-      stats->sample_buffer_bytes = std::max(stats->sample_buffer_bytes, one.sample_buffer_bytes);
-    }
-  }
-  return RTX_OK;
 }
 
 rtx_status rtx_render_count(const rtx_scene* s, const RtxCamera* cam, const RtxConfig* cfg,
@@ -2135,6 +1770,7 @@ extern "C" rtx_status rtx_render_scene_with_time(const rtx_scene* s, double t0, 
   return rtx_write_ppm(path, cfg.image_width, rtx_image_height(&cfg), rgb.data());  // screen.write_to_ppm_file(path)
 }
 
+#include "query_entries.inc"  // rtx_scene_cast_rays*, rtx_scene_occlusion*, rtx_scene_trace_rays*: the entry points of the ray queries
 #include "multi.inc"  // rtx_multi_*: one process, several GPUs, one RCCL gather
 #include "progressive.inc"  // rtx_progressive_*: a frame accumulated over several calls, with its noise estimate
 #endif  // !RTX_F32_TU

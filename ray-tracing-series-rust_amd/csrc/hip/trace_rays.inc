@@ -16,9 +16,7 @@
 
 // A launch's rays (device pointers) -- a kernel argument, so every test on it is wave-uniform.
 struct RadianceArgs {
-  const double* origin;     // [n][3]
-  const double* direction;  // [n][3]
-  const double* time;       // [n] or NULL: 0
+  QueryRays rays;           // cast_rays.inc
   double time_limit;        // scenes with GravitySpheres: a ray later than this is not traced (DeviceScene::gravity_time_limit)
   uint64_t first_ray;       // index of the launch's ray 0 in the caller's whole batch: the stream key's pixel word
 };
@@ -29,8 +27,8 @@ __device__ __forceinline__ bool start_ray_path(const rt::RenderParams& rp, const
   const uint32_t s_local = g / n;
   const uint32_t r = g - s_local * n;
   double o[3], d[3];
-  for (int c = 0; c < 3; ++c) { o[c] = a.origin[3 * (size_t)r + c]; d[c] = a.direction[3 * (size_t)r + c]; }
-  const double time = a.time ? a.time[r] : 0.0;
+  for (int c = 0; c < 3; ++c) { o[c] = a.rays.origin[3 * (size_t)r + c]; d[c] = a.rays.direction[3 * (size_t)r + c]; }
+  const double time = a.rays.time ? a.rays.time[r] : 0.0;
   if (time > a.time_limit) {
     const double nan = __builtin_nan("");
     double* out = samples + 3 * (size_t)g;
