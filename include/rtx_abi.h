@@ -599,6 +599,87 @@ rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays,
 rtx_status rtx_scene_trace_rays_device(const rtx_scene* s, const RtxRadianceRays* rays, double* d_sum_rgb, double* d_sumsq_rgb,
                                        void* hip_stream, RtxRenderStats* stats);
 
+/* ---- gather queries: light arriving at a caller's points, the start directions drawn on the device --------------------- */
+/* An extension: what a light-map or an irradiance-probe bake asks of a resident scene.  A radiance query takes every ray as
+ * given, so a bake would upload one ray per (point, direction); a gather query takes the POINTS (56 B each, whatever the
+ * sample count) and draws each sample's start direction from the sample's own stream.  Two forms share one rule:
+ *   surface gather (normal not NULL): the path starts as if it had just scattered off a white Lambertian surface at p with
+ *     normal n.  The mean sample is E / pi, the radiosity of a white diffuse texel: irradiance = pi * sum / samples.
+ *   probe gather (normal NULL): the start direction is uniform over the sphere.  Mean radiance = sum / samples, fluence
+ *     4 pi times that.  With sh_order = 1 | 2 every sample is projected on the device onto the real orthonormal spherical
+ *     harmonics of orders 0..sh_order (K = 4 or 9 coefficients per channel): coefficient estimate = 4 pi * S / samples.
+ * MEANING.  Sample s of point r is one path of core/integrator.hpp (trace_gather_sample[_nee]):
+ *     rng     = rng_for_sample(seed, first_point + r, first_sample + s)
+ *     u       = random_unit_vector(rng)          -- the reference's rejection loop: the FIRST draws of the stream
+ *     surface : dir = normal_r + u; if near_zero(dir) dir = normal_r        (Lambertian::scatter's rule, hit.rs:1039-1051)
+ *     probe   : dir = u
+ *     ray     = Ray(p_r, dir, time_r); product = (1, 1, 1); output = 0; depth = max_depth
+ *     surface and light_sampling = 1 and the scene has sampled lights:
+ *               output += the light connection of a Lambertian vertex {p_r, normal_r} of albedo (1, 1, 1), made after the
+ *               scatter draw; the first ray carries that vertex' pdf (the power heuristic weighs a light it hits)
+ *     then the estimator's bounce loop to the end, unchanged (ray_color's, world.rs:52-93; light_sampling = 1:
+ *     RtxIntegratorOptions').
+ * The normal is taken AS GIVEN and is not normalised, as Ray::new takes a direction; no two-sided flip is made.  The ray
+ * leaves p with the path's own t_min, so a point that lies on a surface does not hit that surface.  A gather through a
+ * non-white albedo is the caller's multiplication.  Only a UNIT normal makes the start direction the cosine lobe: E / pi is
+ * what a unit normal gathers, and with light_sampling = 1 the start vertex weighs its two strategies by that lobe's density,
+ * so a normal of another length biases it (a zero normal -- what a cast reports for a hit inside a medium -- gathers
+ * uniformly over the sphere and, with light sampling, loses the direct light of its first segment).
+ * PLAIN OUTPUT (sh_order = 0): sum [n][3] and the optional sumsq [n][3], added in ascending sample order, the square and the
+ * add separately rounded -- rtx_scene_trace_rays' rule.
+ * SH OUTPUT (sh_order = 1 | 2, probe form only; with normals RTX_EINVAL): with K = 4 or 9, sum [n][K][3] and the optional
+ * sumsq [n][K][3] are updated for s ascending, then i = 0 .. K-1, then c = 0 .. 2 by
+ *     v = Y_i(dir_s) * L_s[c];  S += v;  Q += v * v            (every operation separately rounded in f64)
+ * Y_i is the real orthonormal basis in the order (0,0), (1,-1), (1,0), (1,1), (2,-2), (2,-1), (2,0), (2,1), (2,2), evaluated on
+ * the start direction (a unit vector); core/sh_basis.hpp holds its constants as double literals and fixes its order of
+ * operations.
+ * Points are f64 columns for both kinds of scene.  An f32 scene is supported with light_sampling = 0: p and n are narrowed
+ * with a (float) cast, the samples are widened before they are added, and the direction that enters Y_i is the float
+ * direction, widened.
+ * THE CONTRACT (rtx_scene_trace_rays'): a point's sums depend only on (scene, point, first_point + r, seed, the sample range,
+ * max_depth, background, estimator, form, sh_order) -- not on how the batch is cut into calls, staging slices, launches or
+ * passes.  With accumulate = 1, two calls over the samples [0, a) and [a, a + b) leave the bits of one call over [0, a + b).
+ * A point later than a GravitySphere scene's time limit gives NaN sums (rtx_scene_trace_rays' rule).  The query uses the
+ * scene's render workspace: the one-render-in-flight-per-rtx_scene rule applies.
+ * RTX_EINVAL before any device call, the message naming the field: a NULL scene, struct or sum; n < 0; n > 0 with a NULL
+ * position; samples < 1; max_depth < 1; a non-zero reserved word; a light_sampling or accumulate other than 0 / 1; an
+ * sh_order other than 0 / 1 / 2; sh_order > 0 with normals; a NaN background; first_sample + samples past 2^32; (device
+ * entry) a pointer that is not 8-byte aligned.  An f32 scene with light_sampling = 1 is RTX_EUNSUPPORTED.  n = 0 is RTX_OK:
+ * nothing is launched, nothing written. */
+typedef struct RtxGatherPoints {   /* 112 B */
+  int64_t n;                 /* points */
+  const double* position;    /* [n][3] */
+  const double* normal;      /* [n][3], not normalised: the surface form; NULL: the probe form */
+  const double* time;        /* [n] or NULL: every point at time 0 */
+  uint64_t first_point;      /* index of point 0 in the caller's whole batch: the stream key's pixel word */
+  uint32_t first_sample;     /* absolute index of the first sample traced by this call */
+  int32_t samples;           /* >= 1 */
+  int32_t max_depth;         /* >= 1: bounces AFTER the start vertex */
+  int32_t accumulate;        /* 0: sums start at 0; 1: sum / sumsq are continued in place */
+  uint64_t seed;
+  double background[3];
+  int32_t light_sampling;    /* RtxIntegratorOptions' meaning; f32 scene with 1: RTX_EUNSUPPORTED */
+  int32_t sh_order;          /* 0: plain sums [n][3]; 1 | 2 (probe form only): SH sums [n][4][3] | [n][9][3] */
+  uint64_t sample_buffer_bytes; /* RtxConfig's meaning: 0 = the default budget */
+  int32_t reserved[2];       /* must be 0 */
+} RtxGatherPoints;
+/* Zeroes *g, then samples = 1, max_depth = 50, seed = 1, background = (0.7, 0.8, 1). */
+void rtx_gather_points_defaults(RtxGatherPoints* g);
+/* Host pointers, blocking; staged in slices of RTX_TRACE_HOST_SLICE points (56 B in, 48 B of sums a point and coefficient).
+ * sum is required, sumsq and stats are optional.  stats->trace_kernel is RTX_KERNEL_RAYS (the gather kernel has k_trace_rays'
+ * scheduling), stats->samples = n * samples. */
+rtx_status rtx_scene_gather(const rtx_scene* s, const RtxGatherPoints* points, double* sum, double* sumsq, RtxRenderStats* stats);
+/* Device pointers, asynchronous on hip_stream: returns after the launches unless stats is not NULL, which synchronises.  A
+ * batch of more than 2^30 points goes out as several launches. */
+rtx_status rtx_scene_gather_device(const rtx_scene* s, const RtxGatherPoints* points, double* d_sum, double* d_sumsq,
+                                   void* hip_stream, RtxRenderStats* stats);
+/* Host only, no device call: dir [n][samples][3] = the start directions `dir` above of samples [first_sample, first_sample +
+ * samples) of points [first_point, first_point + n), computed by the core function the kernels run, in f64 arithmetic
+ * (f32 = 0) or in float arithmetic, widened (f32 = 1: what an f32 scene draws).  Of the struct only n, normal, first_point,
+ * first_sample, samples and seed are read.  For callers who project onto a basis of their own.  RTX_EINVAL: a NULL
+ * struct or dir, n < 0, samples < 1, a sample range past 2^32, f32 other than 0 / 1. */
+rtx_status rtx_gather_directions(const RtxGatherPoints* points, int32_t f32, double* dir);
+
 /* ---- moving objects: new parameters for the Translate / RotateY chains of top-level slots --------------------------------
  * Setting the ops of top-level slots on a flattened or a resident scene gives the scene that rtx_flatten (and rtx_scene_upload)
  * build from scratch with those rtx_translate offsets and rtx_rotate_y angles: every entry point answers bit for bit as it

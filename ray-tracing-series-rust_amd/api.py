@@ -133,6 +133,14 @@ class RtxRadianceRays(C.Structure):
                 ("light_sampling", C.c_int32), ("reserved", C.c_int32), ("sample_buffer_bytes", C.c_uint64)]
 
 
+class RtxGatherPoints(C.Structure):
+    _fields_ = [("n", C.c_int64), ("position", C.c_void_p), ("normal", C.c_void_p), ("time", C.c_void_p),
+                ("first_point", C.c_uint64), ("first_sample", C.c_uint32), ("samples", C.c_int32), ("max_depth", C.c_int32),
+                ("accumulate", C.c_int32), ("seed", C.c_uint64), ("background", C.c_double * 3),
+                ("light_sampling", C.c_int32), ("sh_order", C.c_int32), ("sample_buffer_bytes", C.c_uint64),
+                ("reserved", C.c_int32 * 2)]
+
+
 class _RtxSlotOp(C.Structure):
     _fields_ = [("op", C.c_int32), ("pad", C.c_int32), ("v", C.c_double * 3)]
 
@@ -296,6 +304,10 @@ ABI = {
     "rtx_radiance_rays_defaults": (None, [C.POINTER(RtxRadianceRays)]),
     "rtx_scene_trace_rays": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_scene_trace_rays_device": (C.c_int32, [_VP, C.POINTER(RtxRadianceRays), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_gather_points_defaults": (None, [C.POINTER(RtxGatherPoints)]),
+    "rtx_scene_gather": (C.c_int32, [_VP, C.POINTER(RtxGatherPoints), _VP, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_scene_gather_device": (C.c_int32, [_VP, C.POINTER(RtxGatherPoints), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
+    "rtx_gather_directions": (C.c_int32, [C.POINTER(RtxGatherPoints), C.c_int32, _VP]),
     "rtx_flat_slot_chain": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_int32)]),
     "rtx_flat_instance_tree": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxInstanceTree)]),
     "rtx_flat_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64]),
@@ -1071,6 +1083,22 @@ class Scene:
         return _trace_rays(self, origins, directions, times, spp, max_depth, background, seed, first_sample, first_ray,
                            light_sampling, sumsq, out, sample_buffer_bytes, want_stats)
 
+    def gather(self, points, normals=None, times=None, *, spp=1, max_depth=50, background=(0.7, 0.8, 1.0), seed=1,
+               light_sampling=False, sh_order=0, first_point=0, first_sample=0, sumsq=True, out=None, stream=None,
+               sample_buffer_bytes=0, want_stats=False):
+        """Light arriving at a batch of points (rtx_scene_gather*): samples first_sample .. first_sample + spp - 1 of every
+        point, each a whole path whose start direction is drawn on the device from the stream of (seed, first_point + r,
+        sample).  With normals (n, 3) -- taken as given, not normalised -- the path starts as if it had scattered off a white
+        Lambertian surface there (the surface form: .irradiance = pi * mean); without, the direction is uniform over the
+        sphere (the probe form), and sh_order = 1 | 2 projects every sample onto 4 | 9 real spherical harmonics per channel
+        (.sum is then (n, K, 3) and .sh = 4 pi * sum / spp the coefficient estimates).  -> GatherSums with .sum, .sumsq (or
+        None), .spp, .mean, .irradiance, .sh.  Arrays as in trace_rays: numpy goes through the host entry; torch tensors on
+        the GPU are passed by data_ptr() and the call is only ENQUEUED, on `stream` or torch's current one (want_stats=True
+        synchronises).  out=: a GatherSums of the same points whose sums are continued in place; first_sample must then be
+        out.spp.  Uses the scene's render workspace: one render, radiance or gather query in flight per Scene."""
+        return _gather(self, points, normals, times, spp, max_depth, background, seed, light_sampling, sh_order, first_point,
+                       first_sample, sumsq, out, stream, sample_buffer_bytes, want_stats)
+
 
 _RAY_COLUMN_SHAPES = {"t": (), "p": (3,), "normal": (3,), "uv": (2,), "ids": (4,)}
 
@@ -1266,6 +1294,113 @@ def _trace_rays(scene, origins, directions, times, spp, max_depth, background, s
         out.stats = stats
         return out
     return RadianceSums(n, spp, s_arr, q_arr, stats)
+
+
+class GatherSums:
+    """What Scene.gather returns: n points, spp samples summed per point so far, the form ("surface" or "probe") and sh_order;
+    sum and sumsq (or None) of shape (n, 3), or (n, K, 3) with sh_order > 0 (numpy arrays, or torch tensors on the points'
+    device).  mean = sum / spp; irradiance = pi * mean (the surface form, else None); sh = 4 pi * sum / spp, the coefficient
+    estimates (sh_order > 0, else None)."""
+
+    def __init__(self, n, spp, sum, sumsq, surface, sh_order, stats=None):
+        self.n, self.spp, self.sum, self.sumsq, self.surface, self.sh_order, self.stats = n, spp, sum, sumsq, surface, sh_order, stats
+
+    @property
+    def form(self):
+        return "surface" if self.surface else "probe"
+
+    @property
+    def mean(self):
+        return self.sum / self.spp
+
+    @property
+    def irradiance(self):
+        return self.sum * (np.pi / self.spp) if self.surface else None
+
+    @property
+    def sh(self):
+        return self.sum * (4.0 * np.pi / self.spp) if self.sh_order > 0 else None
+
+
+def _gather_scalars(spp, max_depth, first_sample, first_point, sh_order):
+    for name, v, lo in (("spp", spp, 1), ("max_depth", max_depth, 1), ("first_sample", first_sample, 0), ("first_point", first_point, 0)):
+        if int(v) != v or v < lo:
+            raise ValueError("%s: must be an integer >= %d, not %r" % (name, lo, v))
+    if first_sample + spp > 2 ** 32:
+        raise ValueError("first_sample: first_sample + spp is past 2^32")
+    if sh_order not in (0, 1, 2):
+        raise ValueError("sh_order: must be 0, 1 or 2, not %r" % (sh_order,))
+
+
+def _gather(scene, points, normals, times, spp, max_depth, background, seed, light_sampling, sh_order, first_point, first_sample,
+            sumsq, out, stream, sample_buffer_bytes, want_stats):
+    # (normals may be left out: the probe form; a column that is given is checked like any other)
+    io = _QueryArrays([("points", points, 3)] + ([("normals", normals, 3)] if normals is not None else []) + [("times", times, 0)])
+    n, on_device = io.n, io.on_device
+    _gather_scalars(spp, max_depth, first_sample, first_point, sh_order)
+    surface = normals is not None
+    if sh_order and surface:
+        raise ValueError("sh_order: spherical harmonics are for the probe form (normals=None)")
+    background = tuple(float(c) for c in background)
+    if len(background) != 3 or any(c != c for c in background):
+        raise ValueError("background: three numbers, none a NaN")
+    if stream is not None and not on_device:
+        raise ValueError("stream: only for torch tensors on the GPU (numpy arrays go through the blocking host entry)")
+    shape = (n, 3) if sh_order == 0 else (n, (sh_order + 1) ** 2, 3)
+    if out is not None:
+        if not isinstance(out, GatherSums):
+            raise ValueError("out: expected what an earlier gather call returned")
+        if out.n != n or _is_torch(out.sum) != on_device or (on_device and out.sum.device != points.device):
+            raise ValueError("out: holds %d points of another kind or device, the batch has %d" % (out.n, n))
+        if out.surface != surface or out.sh_order != sh_order:
+            raise ValueError("out: holds %s sums of sh_order %d, the call asks for %s sums of sh_order %d"
+                             % (out.form, out.sh_order, "surface" if surface else "probe", sh_order))
+        if first_sample != out.spp:
+            raise ValueError("out: holds %d samples per point, so first_sample must be %d, not %d" % (out.spp, out.spp, first_sample))
+        if sumsq and out.sumsq is None:
+            sumsq = False  # (what the first call asked for holds)
+        s_arr, q_arr = out.sum, out.sumsq
+    else:
+        s_arr = io.empty(shape)
+        q_arr = io.empty(shape) if sumsq else None
+    q = RtxGatherPoints()
+    lib.rtx_gather_points_defaults(C.byref(q))
+    q.n, q.position, q.normal, q.time = n, io.ptr(points), io.ptr(normals), io.ptr(times)
+    q.first_point, q.first_sample, q.samples, q.max_depth = first_point, first_sample, spp, max_depth
+    q.accumulate, q.seed, q.light_sampling, q.sh_order = 1 if out is not None else 0, seed, 1 if light_sampling else 0, sh_order
+    q.sample_buffer_bytes = sample_buffer_bytes
+    q.background[:] = background
+    if surface and n == 0:
+        q.normal = 8  # (an empty batch has no column addresses; the form is still the surface one)
+    stats = RtxRenderStats() if want_stats else None
+    io.call(lib.rtx_scene_gather, lib.rtx_scene_gather_device,
+            (scene.ptr, C.byref(q), _VP(io.addr(s_arr) or 8), _VP(io.ptr(q_arr))), tail=(C.byref(stats) if stats else None,), stream=stream)
+    if out is not None:
+        out.spp += spp
+        out.stats = stats
+        return out
+    return GatherSums(n, spp, s_arr, q_arr, surface, sh_order, stats)
+
+
+def gather_directions(n, normals=None, *, spp=1, seed=1, first_point=0, first_sample=0, f32=False):
+    """The start directions Scene.gather draws (rtx_gather_directions; host only, no GPU): (n, spp, 3) float64, the direction of
+    sample first_sample + s of point first_point + r -- normals[r] + a unit vector with normals (n, 3), a unit vector without
+    -- in f64 arithmetic or, f32=True, in an f32 scene's float arithmetic, widened."""
+    if int(n) != n or n < 0:
+        raise ValueError("n: must be an integer >= 0, not %r" % (n,))
+    _gather_scalars(spp, 1, first_sample, first_point, 0)
+    if normals is not None:
+        if not isinstance(normals, np.ndarray) or normals.dtype != np.float64 or not normals.flags["C_CONTIGUOUS"] or normals.shape != (n, 3):
+            raise ValueError("normals: expected a contiguous float64 numpy array of shape (%d, 3)" % n)
+    q = RtxGatherPoints()
+    lib.rtx_gather_points_defaults(C.byref(q))
+    q.n, q.first_point, q.first_sample, q.samples, q.seed = n, first_point, first_sample, spp, seed
+    q.normal = normals.ctypes.data if normals is not None and n else None
+    if normals is not None and n == 0:
+        q.normal = 8
+    out = np.empty((n, spp, 3))
+    _check(lib.rtx_gather_directions(C.byref(q), 1 if f32 else 0, _VP(out.ctypes.data or 8)))
+    return out
 
 
 class Progressive:

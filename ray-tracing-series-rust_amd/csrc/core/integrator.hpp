@@ -319,4 +319,82 @@ RT_HD Color trace_ray_sample_nee(const SceneView& sv, const LightView& lv, const
   return ps.output;
 }
 
+// ---- gather queries: a path that starts AT a caller's point (rtx_scene_gather*) ------------------
+// The start direction is drawn from the sample's own stream, so its first draws are random_unit_vector's rejection loop.
+// Surface form: the path leaves p as if it had just scattered off a white Lambertian surface with the given normal
+// (Lambertian::scatter's rule, hit.rs:1039-1051: normal + unit vector, the normal itself when that sum is near zero); the
+// normal is taken as given, not normalised.  Probe form: the unit vector itself, uniform over the sphere.
+RT_HD Vec3 gather_direction(Rng& rng, bool surface, Vec3 normal) {
+  const Vec3 u = random_unit_vector(rng);
+  if (!surface) return u;
+  Vec3 dir = normal + u;
+  if (near_zero(dir)) dir = normal;
+  return dir;
+}
+
+// The start direction of sample `sample` of point `point_index` alone (rtx_gather_directions, k_reduce_samples_sh's replay).
+RT_HD Vec3 gather_sample_direction(uint64_t seed, uint64_t point_index, uint32_t sample, bool surface, Vec3 normal) {
+  Rng rng = rng_for_sample(seed, point_index, sample);
+  return gather_direction(rng, surface, normal);
+}
+
+// The ray leaves p with the path's own ray_t_min, so a point that lies on a surface does not hit that surface.
+RT_HD void path_begin_gather(const RenderParams& rp, Point3 p, Vec3 normal, bool surface, real time, uint64_t point_index,
+                             uint32_t sample, PathState* ps) {
+  ps->rng = rng_for_sample(rp.seed, point_index, sample);
+  const Vec3 dir = gather_direction(ps->rng, surface, normal);
+  ps->ray = make_ray(p, dir, time);
+  ps->product = v3(1, 1, 1);
+  ps->output = v3(0, 0, 0);
+  ps->depth = rp.max_depth;
+}
+
+// The surface form under next-event estimation: the start vertex makes the light connection a diffuse vertex makes (after the
+// scatter draw, as path_bounce_end_nee orders them; max_depth >= 1, so the connection is always allowed) with albedo (1, 1, 1),
+// and the first ray carries the Lambertian pdf it was scattered with.
+template <uint32_t F, bool COUNT, class STACK>
+RT_HD void path_begin_gather_nee(const SceneView& sv, const LightView& lv, const RenderParams& rp, Point3 p, Vec3 normal, real time,
+                                 uint64_t point_index, uint32_t sample, PathState* ps, real* last_pdf, STACK& stack,
+                                 TraceCounters* cnt) {
+  path_begin_gather(rp, p, normal, true, time, point_index, sample, ps);
+  *last_pdf = real(-1.0);
+  if (lv.n_lights > 0) {
+    HitRecord rec;
+    rec.p = p;
+    rec.normal = normal;
+    rec.t = real(0.0); rec.u = real(0.0); rec.v = real(0.0);
+    rec.front_face = true;
+    rec.mat = -1;
+    ps->output += nee_connect<F, COUNT>(sv, lv, ps, rec, MAT_LAMBERTIAN, v3(1, 1, 1), ps->rng, stack, cnt);
+    *last_pdf = nee_bsdf_pdf(MAT_LAMBERTIAN, rec, ps->ray.direction);
+  }
+}
+
+// Whole gather sample on one thread (the host checker; k_gather runs the same steps).
+template <uint32_t F, bool COUNT, class STACK>
+RT_HD Color trace_gather_sample(const SceneView& sv, const RenderParams& rp, Point3 p, Vec3 normal, bool surface, real time,
+                                uint64_t point_index, uint32_t sample, STACK& stack, TraceCounters* cnt) {
+  PathState ps;
+  path_begin_gather(rp, p, normal, surface, time, point_index, sample, &ps);
+  if (COUNT) cnt->samples++;
+  while (!path_step<F, COUNT>(sv, rp, &ps, stack, cnt)) {
+  }
+  return ps.output;
+}
+
+// surface = false: the probe form has no start vertex, so it is the plain start followed by path_step_nee.
+template <uint32_t F, bool COUNT, class STACK>
+RT_HD Color trace_gather_sample_nee(const SceneView& sv, const LightView& lv, const RenderParams& rp, Point3 p, Vec3 normal,
+                                    bool surface, real time, uint64_t point_index, uint32_t sample, STACK& stack,
+                                    TraceCounters* cnt) {
+  PathState ps;
+  real last_pdf = real(-1.0);
+  if (surface) path_begin_gather_nee<F, COUNT>(sv, lv, rp, p, normal, time, point_index, sample, &ps, &last_pdf, stack, cnt);
+  else path_begin_gather(rp, p, normal, false, time, point_index, sample, &ps);
+  if (COUNT) cnt->samples++;
+  while (!path_step_nee<F, COUNT>(sv, lv, rp, &ps, &last_pdf, stack, cnt)) {
+  }
+  return ps.output;
+}
+
 }  // namespace rt

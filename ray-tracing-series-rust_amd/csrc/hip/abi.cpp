@@ -63,6 +63,25 @@ rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadian
   else if ((uint64_t)rays->first_sample + (uint64_t)rays->samples > (1ull << 32)) bad = "rays->first_sample + rays->samples is past 2^32";
   return refuse(who, bad);
 }
+rtx_status check_gather(const char* who, const rtx_scene* s, const RtxGatherPoints* g, const double* sum) {
+  const char* bad = nullptr;
+  if (!s) bad = "scene is NULL";
+  else if (!g) bad = "points is NULL";
+  else if (!sum) bad = "sum is NULL";
+  else if (g->n < 0) bad = "points->n < 0";
+  else if (g->n > 0 && !g->position) bad = "points->position is NULL";
+  else if (g->samples < 1) bad = "points->samples < 1";
+  else if (g->max_depth < 1) bad = "points->max_depth < 1 (Config::new asserts max_depth > 0, world.rs:36-40)";
+  else if (g->reserved[0] != 0 || g->reserved[1] != 0) bad = "points->reserved is not 0";
+  else if (g->light_sampling != 0 && g->light_sampling != 1) bad = "points->light_sampling is neither 0 nor 1";
+  else if (g->accumulate != 0 && g->accumulate != 1) bad = "points->accumulate is neither 0 nor 1";
+  else if (g->sh_order < 0 || g->sh_order > 2) bad = "points->sh_order is not 0, 1 or 2";
+  else if (g->sh_order > 0 && g->normal) bad = "points->sh_order > 0 with points->normal: spherical harmonics are for the probe form";
+  else if (g->background[0] != g->background[0] || g->background[1] != g->background[1] ||
+           g->background[2] != g->background[2]) bad = "points->background is NaN";
+  else if ((uint64_t)g->first_sample + (uint64_t)g->samples > (1ull << 32)) bad = "points->first_sample + points->samples is past 2^32";
+  return refuse(who, bad);
+}
 rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved) {
   std::string err;
   if (!check_slot_ops_shape(who, s, updates, n, &err)) { set_error(err); return RTX_EINVAL; }
@@ -517,6 +536,15 @@ void rtx_radiance_rays_defaults(RtxRadianceRays* r) {
   r->max_depth = 50;
   r->seed = 1;
   r->background[0] = 0.7; r->background[1] = 0.8; r->background[2] = 1.0;
+}
+
+void rtx_gather_points_defaults(RtxGatherPoints* g) {
+  if (!g) return;
+  memset(g, 0, sizeof(*g));
+  g->samples = 1;
+  g->max_depth = 50;
+  g->seed = 1;
+  g->background[0] = 0.7; g->background[1] = 0.8; g->background[2] = 1.0;
 }
 
 int32_t rtx_flat_top_level_kind(const rtx_flat* f, int32_t index) {

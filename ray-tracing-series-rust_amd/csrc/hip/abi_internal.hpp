@@ -43,6 +43,8 @@ inline void free_scene_handle(rtx_scene* s) { delete s; }
 rtx_status check_ray_batch(const char* who, const rtx_scene* s, const RtxRayBatch* rays, const void* out, const char* out_name);
 // rtx_scene_trace_rays*: the same first rungs, then the radiance batch's own fields.
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb);
+// rtx_scene_gather*: the gather batch's fields.
+rtx_status check_gather(const char* who, const rtx_scene* s, const RtxGatherPoints* points, const double* sum);
 // The checks of rtx_scene_set_transforms that need no scene (host/set_transforms.hpp: check_slot_ops_shape; s is compared with
 // NULL and not read), then *resolved = the updates with every angle turned into sin / cos as the flat arrays hold them.
 rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved);

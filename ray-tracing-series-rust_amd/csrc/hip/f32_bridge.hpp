@@ -57,6 +57,10 @@ struct RtxSceneOps {
   rtx_status (*set_shading)(void* device_scene, const RtxShadingEdit* edits, int64_t n, hipStream_t stream);
   // occlusion queries (occlusion.inc: k_occlusion): device pointers, arguments already checked
   rtx_status (*occlusion)(void* device_scene, const RtxRayBatch* rays, double* d_tau, hipStream_t stream);
+  // gather queries (gather.inc: k_gather, k_reduce_samples_sh): device pointers, arguments already checked; stats may be NULL,
+  // non-NULL synchronises.  Uses the scene's render workspace.
+  rtx_status (*gather)(void* device_scene, const RtxGatherPoints* points, double* d_sum, double* d_sumsq, hipStream_t stream,
+                       RtxRenderStats* stats);
 };
 
 // A stable radix sort of (64-bit key, 32-bit value) pairs on `stream` (lbvh.hip, which already carries rocPRIM's sort: neither
@@ -69,6 +73,8 @@ void rtx_f32_set_error(const char* msg);  // defined by the f64 compilation: bot
 // rtx_device_math's float entries (fn >= 32): one arithmetic building block as the f32 compilation evaluates it
 // (post_kernels.inc: k_device_math_f32); device pointers, asynchronous on the null stream.
 hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, long long n, double* d_out);
+// rtx_gather_directions with f32 = 1 (gather.inc: gather_directions_impl as the f32 compilation has it); host only
+void rtx_f32_gather_directions(const RtxGatherPoints* points, double* dir);
 // rtx_device_cull_verdicts / rtx_device_walk_steps with f32 = 1 (cull_hooks.inc as the f32 compilation has it); host pointers
 rtx_status rtx_f32_cull_verdicts(int64_t n, const double* box, const double* ray, float* ray32, float* key, uint32_t* verdict);
 rtx_status rtx_f32_walk_steps(int32_t kind, int32_t bottom, const void* nodes, int64_t n_nodes, int32_t levels, int64_t n,

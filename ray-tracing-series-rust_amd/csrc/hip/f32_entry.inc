@@ -43,6 +43,8 @@ hipError_t rtx_f32_device_math(int fn, const double* d_x, const double* d_y, lon
   return hipGetLastError();
 }
 
+void rtx_f32_gather_directions(const RtxGatherPoints* points, double* dir) { gather_directions_impl(points, dir); }
+
 rtx_status rtx_f32_cull_verdicts(int64_t n, const double* box, const double* ray, float* ray32, float* key, uint32_t* verdict) {
   return cull_verdicts_impl(n, box, ray, ray32, key, verdict);
 }

@@ -161,4 +161,71 @@ rtx_status rtx_scene_trace_rays(const rtx_scene* s, const RtxRadianceRays* rays,
   });
 }
 
+// ---- gather queries
+static rtx_status check_gather_precision(const char* who, const rtx_scene* s, const RtxGatherPoints* points) {
+  if (points->light_sampling && s->f32) {
+    set_error(std::string(who) + ": light sampling needs an f64 scene (rtx_scene_upload)");
+    return RTX_EUNSUPPORTED;
+  }
+  return RTX_OK;
+}
+
+rtx_status rtx_scene_gather_device(const rtx_scene* s, const RtxGatherPoints* points, double* d_sum, double* d_sumsq, void* hip_stream,
+                                   RtxRenderStats* stats) {
+  rtx_status st = check_gather("rtx_scene_gather_device", s, points, d_sum);
+  if (st != RTX_OK) return st;
+  st = check_aligned("rtx_scene_gather_device", {{points->position, 7, "points->position"}, {points->normal, 7, "points->normal"},
+                                                 {points->time, 7, "points->time"},         {d_sum, 7, "sum"},
+                                                 {d_sumsq, 7, "sumsq"}});
+  if (st != RTX_OK) return st;
+  if (stats && points->n == 0) memset(stats, 0, sizeof(*stats));
+  if (points->n == 0) return RTX_OK;
+  if ((st = check_gather_precision("rtx_scene_gather_device", s, points)) != RTX_OK) return st;
+  return s->ops->gather(s->device_scene, points, d_sum, d_sumsq, (hipStream_t)hip_stream, stats);
+}
+
+// Host pointers: in 56 B a point, sums 48 B a point and coefficient (copied in as well when the call continues them).
+rtx_status rtx_scene_gather(const rtx_scene* s, const RtxGatherPoints* points, double* sum, double* sumsq, RtxRenderStats* stats) {
+  rtx_status st = check_gather("rtx_scene_gather", s, points, sum);
+  if (st != RTX_OK) return st;
+  if (stats) memset(stats, 0, sizeof(*stats));
+  if (points->n == 0) return RTX_OK;
+  if ((st = check_gather_precision("rtx_scene_gather", s, points)) != RTX_OK) return st;
+  const bool cont = points->accumulate != 0;
+  const size_t sum_bytes = 24 * (size_t)sh_coeffs(points->sh_order);
+  StagedColumn cols[] = {{points->position, 24, true, false}, {points->normal, 24, true, false}, {points->time, 8, true, false},
+                         {sum, sum_bytes, cont, true},        {sumsq, sum_bytes, cont, true}};
+  HIP_TRY(stage_alloc(cols, std::min<int64_t>(points->n, RTX_TRACE_HOST_SLICE)));
+  return for_ray_slices(points->n, RTX_TRACE_HOST_SLICE, [&](int64_t first, int64_t count) -> rtx_status {
+    HIP_TRY(stage_copy(cols, first, count, false));
+    RtxGatherPoints b = slice_of(*points, first, count);
+    b.position = cols[0].dev; b.normal = cols[1].dev; b.time = cols[2].dev;
+    RtxRenderStats one;
+    const rtx_status lst = s->ops->gather(s->device_scene, &b, cols[3].dev, cols[4].dev, (hipStream_t) nullptr, stats ? &one : nullptr);
+    if (lst != RTX_OK) return lst;
+    HIP_TRY(stage_copy(cols, first, count, true));  // (the odd passes were joined to the null stream)
+    if (stats) {
+      stats->samples += one.samples; stats->trace_ms += one.trace_ms; stats->trace_launches += one.trace_launches;
+      stats->passes += one.passes; stats->trace_kernel = one.trace_kernel;
+      stats->sample_buffer_bytes = std::max(stats->sample_buffer_bytes, one.sample_buffer_bytes);
+    }
+    return RTX_OK;
+  });
+}
+
+// Host only: the start directions the kernels draw, by the core function they run, in either compilation's arithmetic.
+rtx_status rtx_gather_directions(const RtxGatherPoints* points, int32_t f32, double* dir) {
+  const char* bad = nullptr;
+  if (!points) bad = "points is NULL";
+  else if (!dir) bad = "dir is NULL";
+  else if (points->n < 0) bad = "points->n < 0";
+  else if (points->samples < 1) bad = "points->samples < 1";
+  else if ((uint64_t)points->first_sample + (uint64_t)points->samples > (1ull << 32)) bad = "points->first_sample + points->samples is past 2^32";
+  else if (f32 != 0 && f32 != 1) bad = "f32 is neither 0 nor 1";
+  if (bad) { set_error(std::string("rtx_gather_directions: ") + bad); return RTX_EINVAL; }
+  if (f32) rtx_f32_gather_directions(points, dir);
+  else gather_directions_impl(points, dir);
+  return RTX_OK;
+}
+
 }  // extern "C"

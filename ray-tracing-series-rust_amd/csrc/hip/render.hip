@@ -358,6 +358,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "denoise.inc"       // k_features (first-hit albedo / normal), the a-trous filter of a progressive frame
 #include "cast_rays.inc"     // QueryRays; k_cast_rays: closest-hit casts of a caller's ray batch (rtx_scene_cast_rays*)
 #include "trace_rays.inc"    // k_trace_rays: the estimator's radiance along a caller's rays (rtx_scene_trace_rays*)
+#include "gather.inc"        // k_gather, k_reduce_samples_sh: light arriving at a caller's points (rtx_scene_gather*)
 #include "occlusion.inc"     // k_occlusion: any-hit segment casts with exact fog depth (rtx_scene_occlusion*)
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
@@ -1480,6 +1481,9 @@ static const RtxSceneOps scene_ops = {
     },
     [](void* ds, const RtxRayBatch* rays, double* d_tau, hipStream_t stream) {
       return launch_occlusion((DeviceScene*)ds, rays, d_tau, stream);
+    },
+    [](void* ds, const RtxGatherPoints* points, double* d_sum, double* d_sumsq, hipStream_t stream, RtxRenderStats* stats) {
+      return gather_impl((DeviceScene*)ds, points, d_sum, d_sumsq, stream, stats);
     },
 };
 

@@ -52,4 +52,15 @@ inline RtxRadianceRays slice_of(const RtxRadianceRays& q, int64_t first, int64_t
   return s;
 }
 
+// Points [first, first + count) of a gather batch: point r of the slice keeps the stream key first_point + first + r.
+inline RtxGatherPoints slice_of(const RtxGatherPoints& q, int64_t first, int64_t count) {
+  RtxGatherPoints s = q;
+  s.n = count;
+  s.position = slice_of(q.position, 3, first);
+  s.normal = slice_of(q.normal, 3, first);
+  s.time = slice_of(q.time, 1, first);
+  s.first_point = q.first_point + (uint64_t)first;
+  return s;
+}
+
 }  // namespace rtx
