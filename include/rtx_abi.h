@@ -680,6 +680,90 @@ rtx_status rtx_scene_gather_device(const rtx_scene* s, const RtxGatherPoints* po
  * struct or dir, n < 0, samples < 1, a sample range past 2^32, f32 other than 0 / 1. */
 rtx_status rtx_gather_directions(const RtxGatherPoints* points, int32_t f32, double* dir);
 
+/* ---- nearest-point queries: the closest surface of a resident scene per point ------------------------------------------- */
+/* An extension: how far is point r from the scene, and where is the closest surface -- clearance and collision tests against
+ * the objects the update calls move, distance-field bakes, snapping gather points onto a surface, proximity falloff.  Not a
+ * ray: the walk prunes by a box's distance to the point against a bound that shrinks as candidates are found
+ * (core/nearest.hpp: world_nearest, which states the order of every operation below once, for the kernel and the CPU alike).
+ *
+ * CANDIDATES of point r (p, time, r_max) are all primitives of the world list: the primitive of a PRIM slot, every ref of a
+ * GROUP, every ref of a BVH, the same under an XFORM chain, the members of an instance tree (the plain slots they are).  A
+ * ConstantMedium slot contributes its boundary's primitives only when media = 1, reported with the phase material
+ * (FlatEntry::b); with media = 0 the slot is skipped.
+ *
+ * prim_nearest gives, per candidate, a point q on it.  All arithmetic is in rt::real with + - * /, sqrt, fabs, fmin, fmax only:
+ *   Sphere / MovingSphere  centre c = (cx, cy, cz) or moving_sphere_center(s, time); v = p - c; len = sqrt(dot(v, v));
+ *                          q = c + v * (fabs(radius) / len); when len == 0, q = c + (fabs(radius), 0, 0).
+ *   Rectangle              the two in-plane coordinates of p clamped: fmin(fmax(p_a, a0), a1), fmin(fmax(p_b, b0), b1); the
+ *                          third is k.  A rectangle with a0 > a1 or b0 > b1 is not a candidate (no ray can hit it either).
+ *   Triangle               the closest point by barycentric region, tested in this order, with ab = v1 - v0, ac = v2 - v0,
+ *                          ap = p - v0, d1 = dot(ab, ap), d2 = dot(ac, ap); bp = p - v1, d3 = dot(ab, bp), d4 = dot(ac, bp);
+ *                          cp = p - v2, d5 = dot(ab, cp), d6 = dot(ac, cp):
+ *                            vertex v0   d1 <= 0 and d2 <= 0                                   q = v0
+ *                            vertex v1   d3 >= 0 and d4 <= d3                                  q = v1
+ *                            edge v0v1   vc = d1 d4 - d3 d2 <= 0, d1 >= 0, d3 <= 0             q = v0 + ab * (d1 / (d1 - d3))
+ *                            vertex v2   d6 >= 0 and d5 <= d6                                  q = v2
+ *                            edge v0v2   vb = d5 d2 - d1 d6 <= 0, d2 >= 0, d6 <= 0             q = v0 + ac * (d2 / (d2 - d6))
+ *                            edge v1v2   va = d3 d6 - d5 d4 <= 0, d4 - d3 >= 0, d5 - d6 >= 0   q = v1 + (v2 - v1) * ((d4 - d3) / ((d4 - d3) + (d5 - d6)))
+ *                            face        denom = 1 / (va + vb + vc)                            q = (v0 + ab * (vb denom)) + ac * (vc denom)
+ *                          then every coordinate of q is clamped into [min, max] of the three vertices' (a no-op unless the
+ *                          region tests of a sliver cancelled).  A triangle whose stored normal is NaN has zero area and is
+ *                          not a candidate.
+ *   under an XFORM chain   p goes in through the ops outermost first, with xform_ray's origin arithmetic; q comes back out
+ *                          innermost first, with xform_record's p arithmetic.
+ * THE KEY is d2 = dot(p_local - q_local, p_local - q_local) in the frame where the primitive lives, the same for every kind.  A
+ * candidate replaces the best so far when d2 < best_d2, or when d2 == best_d2 and its (slot, order) is lexicographically
+ * smaller; order is the ref's position in its entry's ref list (the order of Closest), 0 for a PRIM entry.  The search starts
+ * from best_d2 = r_max * r_max with nothing found: d2 == r_max^2 is found, a NaN d2 never wins (a MovingSphere with
+ * time0 == time1 is never found), a NaN r_max finds nothing.  The answer is therefore a function of the flat scene's arrays
+ * alone: not of visiting order or of how a batch is split, and d not of leaf size or builder either.  The builder does order
+ * a BVH's ref list (and stores a mesh's triangles in that order), so among candidates that tie EXACTLY inside one BVH -- the
+ * triangles sharing the mesh vertex or edge that p is nearest to -- the one named by ids, and the arithmetic its q went
+ * through, are those of the first in that build's list.
+ *
+ * OUTPUTS, any of which may be NULL (all NULL: a timing run):
+ *   d   [n]     sqrt(best_d2), +inf when nothing is found
+ *   q   [n][3]  the point in the world frame, 0 when nothing is found
+ *   ids [n][4]  int32 {material, top-level slot, PrimType (0 sphere, 1 moving sphere, 2 rectangle, 3 triangle), index in that
+ *               type's array -- the id rtx_flat_sphere_ids / _triangle_ids / _rect_ids / _moving_sphere_ids hand out},
+ *               all -1 when nothing is found
+ * An f32 scene narrows p, time and r_max with the cast's conversions and widens what it writes.  Results are deterministic and
+ * equal the CPU core's bit for bit in both precisions.  Under a RotateY, |p - q| equals d only to rounding: the stored sin / cos
+ * are not exactly a rotation, and d is taken in the member's frame.
+ *
+ * NOT SUPPORTED: scenes with GravitySpheres return RTX_EUNSUPPORTED -- their BVH boxes are the union of the boxes at the two
+ * ends of the interval, not of the trajectory between, so no distance bound follows from them; k > 1 neighbours; signed
+ * distance.
+ *
+ * RTX_EINVAL before any device call, the message naming the field: a NULL scene, batch or result struct; n < 0; n > 0 with NULL
+ * points; a NaN or negative r_max_all; media other than 0 / 1; a non-zero reserved word.  RTX_EUNSUPPORTED for a BVH too deep
+ * for the LDS traversal stack; both are refused before the host entry stages anything.  n = 0 is RTX_OK.  A NaN coordinate
+ * of p is defined -- every d2 is NaN, nothing is found -- but costly: no box bounds a NaN, so that point visits every
+ * primitive of the scene.  The query does not use the render workspace and may run beside a render, as
+ * the cast does. */
+typedef struct RtxPointBatch {
+  int64_t n;
+  const double* points;  /* [n][3] */
+  const double* time;    /* [n] or NULL: 0 */
+  const double* r_max;   /* [n] or NULL: r_max_all */
+  double r_max_all;      /* defaults: +inf */
+  int32_t media;         /* 0 / 1 */
+  int32_t reserved;      /* must be 0 */
+} RtxPointBatch;
+typedef struct RtxNearest {
+  double* d;     /* [n] */
+  double* q;     /* [n][3] */
+  int32_t* ids;  /* [n][4] */
+} RtxNearest;
+/* Zeroes *b, then r_max_all = +inf. */
+void rtx_point_batch_defaults(RtxPointBatch* b);
+/* Host pointers, blocking; staged in slices of RTX_CAST_HOST_SLICE points (40 B in, 48 B out a point). */
+rtx_status rtx_scene_nearest(const rtx_scene* s, const RtxPointBatch* points, const RtxNearest* out);
+/* Device pointers, asynchronous on hip_stream: returns after the launch.  ids must be 16-byte aligned and every other column
+ * 8-byte aligned: RTX_EINVAL naming the pointer otherwise, before any device call.  A batch of more than 2^30 points goes out
+ * as several launches. */
+rtx_status rtx_scene_nearest_device(const rtx_scene* s, const RtxPointBatch* points, const RtxNearest* out, void* hip_stream);
+
 /* ---- moving objects: new parameters for the Translate / RotateY chains of top-level slots --------------------------------
  * Setting the ops of top-level slots on a flattened or a resident scene gives the scene that rtx_flatten (and rtx_scene_upload)
  * build from scratch with those rtx_translate offsets and rtx_rotate_y angles: every entry point answers bit for bit as it

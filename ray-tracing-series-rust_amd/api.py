@@ -141,6 +141,15 @@ class RtxGatherPoints(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class RtxPointBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("points", C.c_void_p), ("time", C.c_void_p), ("r_max", C.c_void_p),
+                ("r_max_all", C.c_double), ("media", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RtxNearest(C.Structure):
+    _fields_ = [("d", C.c_void_p), ("q", C.c_void_p), ("ids", C.c_void_p)]
+
+
 class _RtxSlotOp(C.Structure):
     _fields_ = [("op", C.c_int32), ("pad", C.c_int32), ("v", C.c_double * 3)]
 
@@ -196,6 +205,7 @@ RTX_KERNEL_RAYS = 9  # RtxRenderStats.trace_kernel of a radiance query (k_trace_
 # RtxRenderStats.trace_variant: which k_trace_lds ran (0 for every other kernel)
 RTX_LDS_VARIANT_TIME_BOXES, RTX_LDS_VARIANT_ONE_AXIS, RTX_LDS_VARIANT_COMMON_RATIO = 1, 2, 4
 RAY_COLUMNS = ("t", "p", "normal", "uv", "ids")  # the columns of RtxRayHits, in its order
+NEAREST_COLUMNS = ("d", "q", "ids")  # the columns of RtxNearest, in its order
 
 
 def _integrator_options(light_sampling):
@@ -308,6 +318,9 @@ ABI = {
     "rtx_scene_gather": (C.c_int32, [_VP, C.POINTER(RtxGatherPoints), _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_scene_gather_device": (C.c_int32, [_VP, C.POINTER(RtxGatherPoints), _VP, _VP, _VP, C.POINTER(RtxRenderStats)]),
     "rtx_gather_directions": (C.c_int32, [C.POINTER(RtxGatherPoints), C.c_int32, _VP]),
+    "rtx_point_batch_defaults": (None, [C.POINTER(RtxPointBatch)]),
+    "rtx_scene_nearest": (C.c_int32, [_VP, C.POINTER(RtxPointBatch), C.POINTER(RtxNearest)]),
+    "rtx_scene_nearest_device": (C.c_int32, [_VP, C.POINTER(RtxPointBatch), C.POINTER(RtxNearest), _VP]),
     "rtx_flat_slot_chain": (C.c_int32, [_VP, C.c_int32, C.POINTER(C.c_int32)]),
     "rtx_flat_instance_tree": (C.c_int32, [_VP, C.c_int32, C.POINTER(RtxInstanceTree)]),
     "rtx_flat_set_transforms": (C.c_int32, [_VP, C.POINTER(RtxSlotOps), C.c_int64]),
@@ -1099,6 +1112,16 @@ class Scene:
         return _gather(self, points, normals, times, spp, max_depth, background, seed, light_sampling, sh_order, first_point,
                        first_sample, sumsq, out, stream, sample_buffer_bytes, want_stats)
 
+    def nearest(self, points, times=None, r_max=None, *, r_max_all=float("inf"), media=False, want=NEAREST_COLUMNS, stream=None):
+        """The closest surface point of the scene per point (rtx_scene_nearest*): over every primitive of the world list
+        (a ConstantMedium's boundary only with media=True), the point q that minimises |points[r] - q|^2 at times[r] within
+        r_max[r] (or r_max_all) -> Nearest with the columns named in `want`: .d (n,) +inf when nothing is found, .q (n, 3),
+        .ids (n, 4) int32 {material, top-level slot, PrimType, index in that type's array}, all -1 when nothing is found;
+        and .found, .material, .slot, .prim_type, .prim_index.  Deterministic, no stream is drawn from; scenes with
+        GravitySpheres raise RtxError (RTX_EUNSUPPORTED).  Arrays as in occlusion: numpy goes through the host entry; torch
+        tensors on the GPU are passed by data_ptr() and the call is only ENQUEUED, on `stream` or torch's current one."""
+        return _nearest(self, points, times, r_max, r_max_all, media, want, stream)
+
 
 _RAY_COLUMN_SHAPES = {"t": (), "p": (3,), "normal": (3,), "uv": (2,), "ids": (4,)}
 
@@ -1240,6 +1263,51 @@ def _occlusion(scene, origins, directions, times, t_max, t_min, t_max_all, strea
     batch.origin, batch.direction, batch.time, batch.t_max = io.ptr(origins), io.ptr(directions), io.ptr(times), io.ptr(t_max)
     io.call(lib.rtx_scene_occlusion, lib.rtx_scene_occlusion_device, (scene.ptr, C.byref(batch), _VP(io.addr(store))), stream=stream)
     return Occlusion(io.n, store[:io.n])
+
+
+_NEAREST_COLUMN_SHAPES = {"d": (), "q": (3,), "ids": (4,)}
+
+
+class Nearest:
+    """What Scene.nearest returns: n and, for each requested column, an attribute of that name (None when not asked for): d (n,)
+    +inf when nothing is found; q (n, 3); ids (n, 4) int32 {material index, top-level slot, PrimType, index in that type's
+    array}, all -1 when nothing is found -- numpy arrays, or torch tensors on the points' device."""
+
+    def __init__(self, n, columns):
+        self.n = n
+        self.columns = tuple(columns)
+        for name in NEAREST_COLUMNS:
+            setattr(self, name, columns.get(name))
+
+    def _id(self, k):
+        return self.ids[:, k] if self.ids is not None else None
+
+    @property
+    def found(self):
+        return self.ids[:, 1] >= 0 if self.ids is not None else None
+
+    material = property(lambda self: self._id(0))
+    slot = property(lambda self: self._id(1))
+    prim_type = property(lambda self: self._id(2))
+    prim_index = property(lambda self: self._id(3))
+
+
+def _nearest(scene, points, times, r_max, r_max_all, media, want, stream):
+    want = tuple(want)
+    for name in want:
+        if name not in NEAREST_COLUMNS:
+            raise ValueError("want: unknown column %r (expected some of %s)" % (name, ", ".join(NEAREST_COLUMNS)))
+    io = _QueryArrays([("points", points, 3), ("times", times, 0), ("r_max", r_max, 0)])
+    if stream is not None and not io.on_device:
+        raise ValueError("stream: only for torch tensors on the GPU (numpy arrays go through the blocking host entry)")
+    batch = RtxPointBatch()
+    lib.rtx_point_batch_defaults(C.byref(batch))
+    batch.n, batch.r_max_all, batch.media = io.n, r_max_all, 1 if media else 0
+    batch.points, batch.time, batch.r_max = io.ptr(points), io.ptr(times), io.ptr(r_max)
+    cols = {name: io.empty((io.n,) + _NEAREST_COLUMN_SHAPES[name], "int32" if name == "ids" else "float64") for name in want}
+    out = RtxNearest(*[io.ptr(cols.get(name)) for name in NEAREST_COLUMNS])
+    io.call(lib.rtx_scene_nearest, lib.rtx_scene_nearest_device, (scene.ptr, C.byref(batch), C.byref(out)), stream=stream)
+    return Nearest(io.n, cols)
 
 
 class RadianceSums:

@@ -82,6 +82,19 @@ rtx_status check_gather(const char* who, const rtx_scene* s, const RtxGatherPoin
   else if ((uint64_t)g->first_sample + (uint64_t)g->samples > (1ull << 32)) bad = "points->first_sample + points->samples is past 2^32";
   return refuse(who, bad);
 }
+rtx_status check_point_batch(const char* who, const rtx_scene* s, const RtxPointBatch* b, const RtxNearest* out) {
+  const char* bad = nullptr;
+  if (!s) bad = "scene is NULL";
+  else if (!b) bad = "points is NULL";
+  else if (!out) bad = "out is NULL";
+  else if (b->n < 0) bad = "points->n < 0";
+  else if (b->n > 0 && !b->points) bad = "points->points is NULL";
+  else if (b->r_max_all != b->r_max_all) bad = "points->r_max_all is NaN";
+  else if (b->r_max_all < 0.0) bad = "points->r_max_all < 0";
+  else if (b->media != 0 && b->media != 1) bad = "points->media is neither 0 nor 1";
+  else if (b->reserved != 0) bad = "points->reserved is not 0";
+  return refuse(who, bad);
+}
 rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved) {
   std::string err;
   if (!check_slot_ops_shape(who, s, updates, n, &err)) { set_error(err); return RTX_EINVAL; }
@@ -527,6 +540,12 @@ void rtx_ray_batch_defaults(RtxRayBatch* b) {
   b->t_min = 0.001;
   b->t_max_all = HUGE_VAL;
   b->seed = 1;
+}
+
+void rtx_point_batch_defaults(RtxPointBatch* b) {
+  if (!b) return;
+  memset(b, 0, sizeof(*b));
+  b->r_max_all = HUGE_VAL;
 }
 
 void rtx_radiance_rays_defaults(RtxRadianceRays* r) {

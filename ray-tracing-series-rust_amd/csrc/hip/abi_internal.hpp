@@ -45,6 +45,8 @@ rtx_status check_ray_batch(const char* who, const rtx_scene* s, const RtxRayBatc
 rtx_status check_trace_rays(const char* who, const rtx_scene* s, const RtxRadianceRays* rays, const double* sum_rgb);
 // rtx_scene_gather*: the gather batch's fields.
 rtx_status check_gather(const char* who, const rtx_scene* s, const RtxGatherPoints* points, const double* sum);
+// rtx_scene_nearest*: the point batch's fields.
+rtx_status check_point_batch(const char* who, const rtx_scene* s, const RtxPointBatch* points, const RtxNearest* out);
 // The checks of rtx_scene_set_transforms that need no scene (host/set_transforms.hpp: check_slot_ops_shape; s is compared with
 // NULL and not read), then *resolved = the updates with every angle turned into sin / cos as the flat arrays hold them.
 rtx_status check_set_transforms(const char* who, const rtx_scene* s, const RtxSlotOps* updates, int64_t n, std::vector<RtxSlotOps>* resolved);

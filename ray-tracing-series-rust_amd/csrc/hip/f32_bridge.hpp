@@ -61,6 +61,11 @@ struct RtxSceneOps {
   // non-NULL synchronises.  Uses the scene's render workspace.
   rtx_status (*gather)(void* device_scene, const RtxGatherPoints* points, double* d_sum, double* d_sumsq, hipStream_t stream,
                        RtxRenderStats* stats);
+  // nearest-point queries (nearest.inc: k_nearest): device pointers in both structs, arguments already checked
+  rtx_status (*nearest)(void* device_scene, const RtxPointBatch* points, const RtxNearest* out, hipStream_t stream);
+  // what nearest refuses whatever the batch (a scene with GravitySpheres, a BVH too deep for the LDS stack): asked by the host
+  // entry before it stages anything
+  rtx_status (*nearest_supported)(void* device_scene);
 };
 
 // A stable radix sort of (64-bit key, 32-bit value) pairs on `stream` (lbvh.hip, which already carries rocPRIM's sort: neither

@@ -1,4 +1,4 @@
-// The launchers of the three ray queries (included by render.hip, namespace rtx, so compiled for both precisions).  Device
+// The launchers of the ray queries, the gather and the nearest-point query (included by render.hip, namespace rtx, so compiled for both precisions).  Device
 // pointers, asynchronous on the caller's stream; the arguments were checked by the entry point (query_entries.inc, abi.cpp).
 // Each is a check (check_walk_launch), the launch slices of the batch (host/ray_slices.hpp), the kernel's argument struct, the
 // launch of the scene's preset (with_query_preset).
@@ -60,6 +60,34 @@ static rtx_status launch_occlusion(DeviceScene* ds, const RtxRayBatch* b, double
     const OcclusionArgs a = {{s.origin, s.direction, s.time}, s.t_max, s.t_min, s.t_max_all, query_time_limit(ds), slice_of(d_tau, 1, first)};
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_occlusion<decltype(preset)::value>), grid, dim3(TRACE_BLOCK), stack_lds, stream, ds->view, a,
                        (uint32_t)s.n);
+  });
+}
+
+// Nearest-point queries (nearest.inc: k_nearest): the requested columns of the batch's points.  Scenes with GravitySpheres are
+// refused (include/rtx_abi.h says why), so of with_query_preset's three only P_INST and P_ANY are instantiated.
+// check_nearest_launch is what refuses, for the launcher and -- before anything is staged -- for the host entry.
+static rtx_status check_nearest_launch(const DeviceScene* ds, size_t* stack_lds) {
+  if (ds->view.features & rt::F_GRAVITY_SPHERE) {
+    set_error("nearest: scenes with GravitySpheres are not supported (their boxes do not bound the trajectory)");
+    return RTX_EUNSUPPORTED;
+  }
+  return check_walk_launch(ds, "nearest", stack_lds);
+}
+static rtx_status launch_nearest(DeviceScene* ds, const RtxPointBatch* b, const RtxNearest* out, hipStream_t stream) {
+  size_t stack_lds = 0;
+  const rtx_status st = check_nearest_launch(ds, &stack_lds);
+  if (st != RTX_OK) return st;
+  return for_ray_slices(b->n, CAST_LAUNCH_RAYS, [&](int64_t first, int64_t count) -> rtx_status {
+    const dim3 grid(grid_size((uint32_t)count, TRACE_BLOCK, (uint64_t)ds->n_cu * 8));
+    const RtxPointBatch s = slice_of(*b, first, count);
+    const RtxNearest o = slice_of(*out, first);
+    const NearestArgs a = {s.points, s.time, s.r_max, s.r_max_all, s.media, o.d, o.q, o.ids};
+    if (ds->view.features & rt::F_INSTANCE)
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nearest<P_INST>), grid, dim3(TRACE_BLOCK), stack_lds, stream, ds->view, a, (uint32_t)s.n);
+    else
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(k_nearest<P_ANY>), grid, dim3(TRACE_BLOCK), stack_lds, stream, ds->view, a, (uint32_t)s.n);
+    HIP_TRY(hipGetLastError());
+    return RTX_OK;
   });
 }
 

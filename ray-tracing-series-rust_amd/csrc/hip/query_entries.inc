@@ -1,7 +1,7 @@
-// The entry points of the three ray queries (included by render.hip's f64-only tail; the launchers: queries.inc).  A device entry
+// The entry points of the ray queries and of the nearest-point query (included by render.hip's f64-only tail; the launchers: queries.inc).  A device entry
 // takes the caller's device columns, asynchronous on the caller's stream; a host entry stages slices of RTX_*_HOST_SLICE rays
 // (cut by host/ray_slices.hpp, as the launcher cuts a launch's) through device buffers, one after the other on the null stream.
-// The arguments are checked first (abi.cpp: check_ray_batch, check_trace_rays), before any device call and before the handle is read.
+// The arguments are checked first (abi.cpp: check_ray_batch, check_trace_rays, check_gather, check_point_batch), before any device call and before the handle is read.
 
 // One column of a host entry, staged through a device buffer of its own: host pointer (NULL: the caller left the column out, its
 // device pointer stays NULL), bytes per ray, copied in before the call?, copied out after it?
@@ -109,6 +109,41 @@ rtx_status rtx_scene_occlusion(const rtx_scene* s, const RtxRayBatch* rays, doub
     HIP_TRY(stage_copy(cols, first, count, true));
     return RTX_OK;
   });
+}
+
+// ---- nearest-point queries
+rtx_status rtx_scene_nearest_device(const rtx_scene* s, const RtxPointBatch* points, const RtxNearest* out, void* hip_stream) {
+  rtx_status st = check_point_batch("rtx_scene_nearest_device", s, points, out);
+  if (st != RTX_OK || points->n == 0) return st;
+  // the kernel stores ids as int4 and every other column as doubles
+  st = check_aligned("rtx_scene_nearest_device", {{points->points, 7, "points->points"}, {points->time, 7, "points->time"},
+                                                  {points->r_max, 7, "points->r_max"},   {out->d, 7, "out->d"},
+                                                  {out->q, 7, "out->q"},                 {out->ids, 15, "out->ids"}});
+  if (st != RTX_OK) return st;
+  return s->ops->nearest(s->device_scene, points, out, (hipStream_t)hip_stream);
+}
+
+// Host pointers: in 40 B a point, out 48 B.
+rtx_status rtx_scene_nearest(const rtx_scene* s, const RtxPointBatch* points, const RtxNearest* out) {
+  rtx_status st = check_point_batch("rtx_scene_nearest", s, points, out);
+  if (st != RTX_OK || points->n == 0) return st;
+  if ((st = s->ops->nearest_supported(s->device_scene)) != RTX_OK) return st;  // refused before a byte is staged
+  StagedColumn cols[] = {{points->points, 24, true, false}, {points->time, 8, true, false}, {points->r_max, 8, true, false},
+                         {out->d, 8, false, true},          {out->q, 24, false, true},      {out->ids, 16, false, true}};
+  HIP_TRY(stage_alloc(cols, std::min<int64_t>(points->n, RTX_CAST_HOST_SLICE)));
+  st = for_ray_slices(points->n, RTX_CAST_HOST_SLICE, [&](int64_t first, int64_t count) -> rtx_status {
+    HIP_TRY(stage_copy(cols, first, count, false));
+    RtxPointBatch b = slice_of(*points, first, count);
+    b.points = cols[0].dev; b.time = cols[1].dev; b.r_max = cols[2].dev;
+    const RtxNearest o = {cols[3].dev, cols[4].dev, (int32_t*)(double*)cols[5].dev};
+    const rtx_status lst = s->ops->nearest(s->device_scene, &b, &o, (hipStream_t) nullptr);
+    if (lst != RTX_OK) return lst;
+    HIP_TRY(stage_copy(cols, first, count, true));
+    return RTX_OK;
+  });
+  if (st != RTX_OK) return st;
+  HIP_TRY(hipDeviceSynchronize());  // an all-NULL RtxNearest (a timing run) still returns after its launches
+  return RTX_OK;
 }
 
 // ---- radiance queries

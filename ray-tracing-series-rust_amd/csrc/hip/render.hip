@@ -27,6 +27,7 @@
 #include "../core/cull32.hpp"
 #include "../core/integrator.hpp"
 #include "../core/occlusion.hpp"
+#include "../core/nearest.hpp"
 #include "../core/item_order.hpp"
 #include "../core/karras.hpp"
 #include "../core/mover_box.hpp"
@@ -360,6 +361,7 @@ __device__ __forceinline__ void flush_counters(const rt::TraceCounters& c, rt::T
 #include "trace_rays.inc"    // k_trace_rays: the estimator's radiance along a caller's rays (rtx_scene_trace_rays*)
 #include "gather.inc"        // k_gather, k_reduce_samples_sh: light arriving at a caller's points (rtx_scene_gather*)
 #include "occlusion.inc"     // k_occlusion: any-hit segment casts with exact fog depth (rtx_scene_occlusion*)
+#include "nearest.inc"       // k_nearest: the closest surface point of the world list per point (rtx_scene_nearest*)
 #ifndef RTX_F32_TU
 #include "trace_nee.inc"     // k_trace_nee: next-event estimation with MIS (rtx_render_ex, light_sampling = 1; f64 only)
 #endif
@@ -1485,6 +1487,10 @@ static const RtxSceneOps scene_ops = {
     [](void* ds, const RtxGatherPoints* points, double* d_sum, double* d_sumsq, hipStream_t stream, RtxRenderStats* stats) {
       return gather_impl((DeviceScene*)ds, points, d_sum, d_sumsq, stream, stats);
     },
+    [](void* ds, const RtxPointBatch* points, const RtxNearest* out, hipStream_t stream) {
+      return launch_nearest((DeviceScene*)ds, points, out, stream);
+    },
+    [](void* ds) { size_t stack_lds = 0; return check_nearest_launch((DeviceScene*)ds, &stack_lds); },
 };
 
 }  // namespace rtx

@@ -63,4 +63,17 @@ inline RtxGatherPoints slice_of(const RtxGatherPoints& q, int64_t first, int64_t
   return s;
 }
 
+// Points [first, first + count) of a nearest-point batch, and the result columns of the points from `first` on.
+inline RtxPointBatch slice_of(const RtxPointBatch& b, int64_t first, int64_t count) {
+  RtxPointBatch s = b;
+  s.n = count;
+  s.points = slice_of(b.points, 3, first);
+  s.time = slice_of(b.time, 1, first);
+  s.r_max = slice_of(b.r_max, 1, first);
+  return s;
+}
+inline RtxNearest slice_of(const RtxNearest& o, int64_t first) {
+  return {slice_of(o.d, 1, first), slice_of(o.q, 3, first), slice_of(o.ids, 4, first)};
+}
+
 }  // namespace rtx
